@@ -8,6 +8,19 @@ gradient all-reduce when N > 1) of cnn_L3_melspec2 over one synthetic batch of 6
     python bench.py --gpus N --steps K --warmup W        # N > 1: re-executes itself under torch.distributed.run
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W          # how the driver launches it
+    python bench.py --gpus 1 --steps K --warmup W --full                # + everything below the headline
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR    # + DIR/<name>.npy of the last timed step
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, higher_is_better,
+dtype, ms_per_step, the timed steps' losses).  Everything else it can measure -- the per-kernel / roofline figures, the
+exchange timing, the saturated-head region, the configs[1] / configs[4]-shard lines under "secondary" and the CPU
+baseline -- runs only with `--full`, after the timed region, and adds its fields to the same line.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step, right after the timed region, as float32
+.npy files (at most DUMP_MAX_BYTES in all): the full step's loss, accuracy, probabilities, logits and every parameter
+after the update (`param.<name with / as .>.npy`, BatchNorm moving statistics included); for a tower workload, the
+gradients of the tower's trainable parameters.  Inputs and initial weights are seeded, so two builds run with the same
+arguments can be compared array by array.
 
 One process per GPU.  For N > 1 the gradient exchange is the library's own (`l3_comm_init` + `l3_step_dp`:
 ncclAllReduce per gradient bucket on the communicator's HIP stream, overlapped with backward); the
@@ -15,7 +28,7 @@ ncclUniqueId travels over the launcher's env:// store, no torch process group is
 (`--comm torch` selects the torch.distributed test double instead).
 
 Rank 0 prints ONE JSON line.  Timed region = exactly K plain steps between barrier + torch.cuda.synchronize();
-the per-kernel numbers come from `--roofline-steps` FURTHER steps with hipEvents around every launch and the
+with `--full`, the per-kernel numbers come from `--roofline-steps` FURTHER steps with hipEvents around every launch and the
 two towers serialised on one stream (which is what a per-kernel duration means and what
 `rocprofv3 --kernel-trace --stats -- python bench.py --serial` shows, profiles/*_kernel_stats.csv):
   roofline       the top rocprof symbol of the step.  frac = ISSUED flops / (duration * MFMA peak);
@@ -79,6 +92,25 @@ def dlogits_nonzero_frac(probs, labels_onehot, eps=1e-7):
     categorical_crossentropy clips the probabilities to [1e-7, 1 - 1e-7]; outside, d loss / d logits is exactly zero)."""
     p = (np.asarray(probs, np.float64) * np.asarray(labels_onehot, np.float64)).sum(axis=1)
     return float(np.mean((p > eps) & (p < 1.0 - eps)))
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6          # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """arrays: (name, array) pairs -> out_dir/<name>.npy in float32.  Should they exceed max_bytes together, every array
+    larger than an equal share of it is replaced by a sample of its flattened elements of that size, drawn with a seed
+    derived from its name (the same indices in every run and every build)."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = [(n, np.asarray(a, dtype=np.float32)) for n, a in arrays]
+    share = max_bytes // max(len(arrays), 1) // 4          # elements
+    sample = sum(a.nbytes for _, a in arrays) > max_bytes
+    for name, a in arrays:
+        if sample and a.size > share:
+            idx = np.sort(np.random.RandomState(zlib.crc32(name.encode())).choice(a.size, share, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def _time_cpu_steps(tr, v, a, l, n_timed, warm=1):
@@ -281,17 +313,20 @@ def tower_bench(args, eng, B, world, rank, ranks, json_out):
         return time.perf_counter() - t0
 
     run(True, args.warmup)
-    t_fwd = ranks.max(run(False, args.steps))
+    t_fwd = ranks.max(run(False, args.steps)) if args.full else None
     elapsed = ranks.max(run(True, args.steps))
-    eng.set_tower_overlap(False)
-    eng.profile_enable(True)
-    run(True, args.roofline_steps)
-    prof = eng.profile_read()
+    if args.dump_outputs and rank == 0:          # what the pass computes: the gradients of the tower's weights
+        dump_outputs(args.dump_outputs, [('grad.' + name.replace('/', '.'), eng.get_grad(name, shape))
+                                         for name, shape, trainable in eng.param_table()
+                                         if trainable and name.startswith(tower + '_model/')])
+    prof = None
+    if args.full:
+        eng.set_tower_overlap(False)
+        eng.profile_enable(True)
+        run(True, args.roofline_steps)
+        prof = eng.profile_read()
     if rank == 0:
-        ig_ms = prof['conv_fwd']['ms'] + prof['conv_dgrad']['ms']
-        ex = prof['conv_fwd']['executed_flops'] + prof['conv_dgrad']['executed_flops']
-        al = prof['conv_fwd']['flops'] + prof['conv_dgrad']['flops']
-        json_out.write(json.dumps({
+        out = {
             "metric": "%s-tower samples/sec, training-mode forward + backward (stand-in loss = mean of the tower output, "
                       "no optimizer step)" % tower,
             "value": B * world * args.steps / elapsed, "unit": "samples/s", "n_gpus": world, "steps": args.steps,
@@ -300,13 +335,19 @@ def tower_bench(args, eng, B, world, rank, ranks, json_out):
             "config": {"workload": "cnn_L3_melspec2 %s tower only (%s), batch %d per GPU, inputs resident in HBM" %
                                    (tower, "mel front-end + audio conv kernels" if tower == 'audio' else "vision conv kernels", B),
                        "parallelism": "replicas%d" % world},
-            "forward_only": {"value": B * world * args.steps / t_fwd, "unit": "samples/s", "ms_per_step": 1e3 * t_fwd / args.steps},
-            "roofline": {"bound": "mfma", "achieved": ex / (ig_ms * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
-                         "frac": ex / (ig_ms * 1e-3) / 1e12 / peak, "algorithmic_frac": al / (ig_ms * 1e-3) / 1e12 / peak,
-                         "traffic": None, "kernel": "forward + dgrad convolution launches of the tower",
-                         "measured": "%d further fwd+bwd passes with hipEvents around every launch" % args.roofline_steps},
-            "kernel_ms_per_step": {k: v['ms'] / args.roofline_steps for k, v in prof.items()},
-            "cpu_baseline": None}) + '\n')
+            "cpu_baseline": None}
+        if prof is not None:
+            ig_ms = prof['conv_fwd']['ms'] + prof['conv_dgrad']['ms']
+            ex = prof['conv_fwd']['executed_flops'] + prof['conv_dgrad']['executed_flops']
+            al = prof['conv_fwd']['flops'] + prof['conv_dgrad']['flops']
+            out.update({
+                "forward_only": {"value": B * world * args.steps / t_fwd, "unit": "samples/s", "ms_per_step": 1e3 * t_fwd / args.steps},
+                "roofline": {"bound": "mfma", "achieved": ex / (ig_ms * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
+                             "frac": ex / (ig_ms * 1e-3) / 1e12 / peak, "algorithmic_frac": al / (ig_ms * 1e-3) / 1e12 / peak,
+                             "traffic": None, "kernel": "forward + dgrad convolution launches of the tower",
+                             "measured": "%d further fwd+bwd passes with hipEvents around every launch" % args.roofline_steps},
+                "kernel_ms_per_step": {k: v['ms'] / args.roofline_steps for k, v in prof.items()}})
+        json_out.write(json.dumps(out) + '\n')
         json_out.flush()
     ranks.close()
     eng.close()
@@ -425,8 +466,14 @@ def main():
     ap.add_argument('--batch-per-gpu', type=int, default=64)
     ap.add_argument('--model', default='cnn_L3_melspec2')
     ap.add_argument('--lr', type=float, default=1e-4)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--quick-cpu-baseline', action='store_true', help='one timed CPU step instead of the 8(d) protocol')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also measure everything beside the headline: per-kernel / roofline figures, '
+                         'the exchange timing, the saturated-head region, the secondary configurations and the CPU baseline '
+                         '(each still subject to its --no-* / --roofline-steps option below)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB in all)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--quick-cpu-baseline', action='store_true', help='--full: one timed CPU step instead of the 8(d) protocol')
     ap.add_argument('--workload', default='full', choices=['full', 'audio_tower', 'vision_tower'],
                     help="full: the AVC training step (the metric).  audio_tower / vision_tower: one sub-network alone, "
                          "training-mode forward + backward from mean(output), no optimizer step -- SURVEY 8(d) config 2 "
@@ -442,10 +489,10 @@ def main():
                     help="dense_2/kernel starts at this multiple of its he_normal draw so that the synthetic batch has live loss "
                          "gradients (see live_head(); 1.0 = SURVEY 8(d)'s untouched head, where every sample is clipped and backward "
                          "runs on zeros)")
-    ap.add_argument('--no-saturated', action='store_true', help='skip the second timed region on the untouched (saturated) head')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the configs[1] / configs[4]-shard lines under "secondary"')
+    ap.add_argument('--no-saturated', action='store_true', help='--full: skip the second timed region on the untouched (saturated) head')
+    ap.add_argument('--no-secondary', action='store_true', help='--full: skip the configs[1] / configs[4]-shard lines under "secondary"')
     ap.add_argument('--roofline-steps', type=int, default=5,
-                    help='further steps, outside the timed region, with per-launch hipEvents and the towers serialised')
+                    help='--full: further steps, outside the timed region, with per-launch hipEvents and the towers serialised')
     ap.add_argument('--serial', action='store_true', help='run the timed region with the towers serialised too')
     ap.add_argument('--comm', default='native', choices=['native', 'torch'],
                     help="N > 1: native = RCCL inside libl3hip (l3_comm_init / l3_step_dp); torch = torch.distributed double")
@@ -454,6 +501,8 @@ def main():
                     help='a rank that is still running after this long dumps every thread\'s stack to stderr and exits: a collective '
                          'that never completes becomes a failed run with a traceback, not a hang (0 = off)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.watchdog_seconds > 0:
         import faulthandler
         faulthandler.dump_traceback_later(args.watchdog_seconds, exit=True)
@@ -488,7 +537,8 @@ def main():
 
     if args.serial:
         eng.set_tower_overlap(False)
-    init_params = eng.get_params() if args.head_scale != 1.0 else None      # 8(d)'s untouched initialisation (saturated regime below)
+    # 8(d)'s untouched initialisation (saturated regime below, --full)
+    init_params = eng.get_params() if args.full and not args.no_saturated and args.head_scale != 1.0 else None
     if args.head_scale != 1.0:
         live_head(eng, args.head_scale)
 
@@ -519,9 +569,13 @@ def main():
 
     # ---- timed region: exactly K plain steps (no profiling events) ---------------------------------------------
     elapsed, host_cores, losses, loss, live0, live1 = timed_region(True)
-    # ---- per-kernel durations: further steps, hipEvents around every launch, towers serialised ---------------
+    if args.dump_outputs and rank == 0:
+        loss_, acc_, probs_, logits_ = eng.step_results(want_probs=True)
+        dump_outputs(args.dump_outputs, [('loss', loss_), ('accuracy', acc_), ('probs', probs_), ('logits', logits_)] +
+                     [('param.' + name.replace('/', '.'), w) for name, w in eng.get_params().items()])
+    # ---- --full only: per-kernel durations: further steps, hipEvents around every launch, towers serialised ---------
     prof, prof_steps = None, args.roofline_steps
-    if prof_steps > 0:
+    if args.full and prof_steps > 0:
         eng.set_tower_overlap(False)
         eng.profile_enable(True)
         for _ in range(prof_steps):
@@ -533,7 +587,7 @@ def main():
         eng.set_tower_overlap(not args.serial)
     # ---- the exchange, as the step sees it (in-library communicator only): further steps in l3_comm_timing mode ----
     comm_timing = None
-    if ranks.native is not None:
+    if args.full and ranks.native is not None:
         eng.comm_timing(True)
         for _ in range(max(prof_steps, 3)):
             trainer.step(args.lr)
@@ -701,12 +755,12 @@ def main():
                                   "traffic_source": None if ew_cnt is None else "profiles/pmc_traffic.json (builder-side rocprofv3 --pmc pass over "
                                                                                 "the BatchNorm / pool kernels of one step; not measured in this run)",
                                   "note": "BatchNorm / ReLU / pool / moving-average kernels (HBM-bound family)"}
-        if world == 1 and args.dtype == 'f32' and not args.no_secondary:
+        if args.full and world == 1 and args.dtype == 'f32' and not args.no_secondary:
             try:
                 out["secondary"] = secondary_lines(args, local_rank, tstream)
             except Exception as exc:          # never at the headline's expense
                 out["secondary"] = {"error": repr(exc)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.model, quick=args.quick_cpu_baseline)
             out["cpu_baseline"]["host"] = host_cpu_info()
             out["x_cpu_baseline"] = value / out["cpu_baseline"]["value"]

@@ -7,13 +7,13 @@ O=gpurun_out/$TAG; mkdir -p $O
 R=$GRAFT_REPO_ROOT
 nproc > $O/host.txt; lscpu | grep "Model name" >> $O/host.txt; cat /sys/fs/cgroup/cpu.max >> $O/host.txt 2>/dev/null
 if [ -z "$QUICK" ]; then
-timeout -k 10 900 python bench.py > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driverargs_line.json 2>/dev/null
-timeout -k 10 600 python bench.py --force-comm --no-cpu-baseline --no-secondary > $O/bench_forcecomm_line.json 2>/dev/null
-timeout -k 10 600 python bench.py --fp32-conv f2x2 --no-cpu-baseline --no-secondary > $O/bench_f2x2_line.json 2>/dev/null
-timeout -k 10 600 python bench.py --dtype bf16 --batch-per-gpu 128 --no-cpu-baseline > $O/bench_bf16_b128_line.json 2>/dev/null
-timeout -k 10 600 python bench.py --workload audio_tower --no-cpu-baseline > $O/audio_tower_line.json 2>/dev/null
-timeout -k 10 600 python bench.py --workload vision_tower --no-cpu-baseline > $O/vision_tower_line.json 2>/dev/null
+timeout -k 10 900 python bench.py --full > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driverargs_line.json 2>/dev/null
+timeout -k 10 600 python bench.py --full --force-comm --no-cpu-baseline --no-secondary > $O/bench_forcecomm_line.json 2>/dev/null
+timeout -k 10 600 python bench.py --full --fp32-conv f2x2 --no-cpu-baseline --no-secondary > $O/bench_f2x2_line.json 2>/dev/null
+timeout -k 10 600 python bench.py --full --dtype bf16 --batch-per-gpu 128 --no-cpu-baseline > $O/bench_bf16_b128_line.json 2>/dev/null
+timeout -k 10 600 python bench.py --full --workload audio_tower --no-cpu-baseline > $O/audio_tower_line.json 2>/dev/null
+timeout -k 10 600 python bench.py --full --workload vision_tower --no-cpu-baseline > $O/vision_tower_line.json 2>/dev/null
 fi
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_f32 -o f32 -- python $R/bench.py --serial --steps 10 --no-cpu-baseline --no-secondary --no-saturated --roofline-steps 0 > $R/$O/prof_f32.log 2>&1
