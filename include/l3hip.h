@@ -231,6 +231,16 @@ int l3_bn_stats_replicas_dev(l3_engine *e, int world, void **gathered_dev);
 int l3_embed_audio(l3_engine *e, const float *audio, int64_t n, int pool_h, int pool_w, float *out);
 int l3_embed_vision(l3_engine *e, const float *video, int64_t n, int pool_h, int pool_w, float *out);
 int64_t l3_embed_dim(const l3_engine *e, int vision, int pool_h, int pool_w);
+/* get_l3_frames_uniform -- data/usc/features.py:256-306: one audio embedding per 1-second frame of whole clips.
+ * samples: n_samples floats, one or more clips back to back.  table: n_frames rows of {start, lo, hi} (int64):
+ * frames[f] = samples[start_f .. start_f + 48000), zero outside [lo_f, hi_f) -- every frame padded on its own, as the
+ * front-end pads it in training.  The framing rule (reference padding and librosa.util.frame) is the caller's:
+ * l3embedding_amd/features.py frame_table.  The samples and the table go to the device once; per engine batch the frames are
+ * gathered there (clips.hip) and run through the path of l3_embed_audio; one device-to-host copy of out (n_frames, D) and
+ * one host wait per call (up to 256 MiB of output).  L3_EINVAL (message in l3_last_error) for a NULL pointer, a row with
+ * lo < 0, lo > hi or hi > n_samples, a bad pooling size, or a model without an audio embedding layer (tiny_L3). */
+int l3_embed_audio_frames(l3_engine *e, const float *samples, int64_t n_samples, const int64_t *table,
+                          int64_t n_frames, int pool_h, int pool_w, float *out);
 
 /* Diagnostics / parity taps. */
 int l3_get_activation(l3_engine *e, const char *name, float *dst, int64_t numel); /* e.g. "audio_model/frontend", "vision_model/conv2d_1" */
@@ -304,6 +314,9 @@ int l3_op_maxpool_fwd(int device, const float *x, float *y, int n, int h, int wd
 int l3_op_maxpool_bwd(int device, const float *x, const float *dy, float *dx, int n, int h,
                       int wd, int c, int ph, int pw, int sh, int sw, int same);
 int l3_op_frontend(int device, int model_type, const float *audio, int n, int db_max_scope, float *out);
+/* The frame gather of l3_embed_audio_frames on its own: frames (n_frames, 48000) from samples + table as above (parity tests). */
+int l3_op_gather_frames(int device, const float *samples, int64_t n_samples, const int64_t *table,
+                        int64_t n_frames, float *frames);
 /* keras BatchNormalization batch moments (vision_model.py:124-187, audio_model.py:370-433) from the partial sums the
  * convolution epilogues leave: nblk rows of [sum, sum of squares][c] about pivot[c] over `rows` elements per channel.
  * Runs the engine's second reduction stage on a buffer of exactly nblk rows; L3_EINVAL if it wrote past them. */

@@ -101,6 +101,8 @@ SIGNATURES = {
     'l3_embed_audio': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     'l3_embed_vision': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     'l3_embed_dim': (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    'l3_embed_audio_frames': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                        C.c_void_p]),
     'l3_get_activation': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     'l3_activation_numel': (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
     'l3_sync': (C.c_int, [C.c_void_p]),
@@ -121,6 +123,7 @@ SIGNATURES = {
     'l3_op_maxpool_fwd': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 9),
     'l3_op_maxpool_bwd': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9),
     'l3_op_frontend': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'l3_op_gather_frames': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     'l3_op_bn_stats_from_partials': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_float,
                                                C.c_void_p, C.c_void_p]),
     'l3_op_preprocess': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -447,6 +450,22 @@ class Engine(object):
         check(self.lib.l3_embed_audio(self.h, _ptr(a), a.shape[0], pool[0], pool[1], _ptr(out)), self.h)
         return out
 
+    def embed_audio_frames(self, samples, table, pool, out=None):
+        """l3_embed_audio_frames: samples (n,) float32 (clips back to back), table (n_frames, 3) int64 {start, lo, hi}
+        (features.frame_table) -> (n_frames, D) embeddings, written into `out` when given (C-contiguous float32)."""
+        s = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 3)
+        d = self.lib.l3_embed_dim(self.h, 0, pool[0], pool[1])
+        if out is None:
+            out = np.empty((t.shape[0], max(d, 0)), np.float32)
+        elif out.dtype != np.float32 or not out.flags['C_CONTIGUOUS'] or out.shape != (t.shape[0], d):
+            raise ValueError('out must be a C-contiguous float32 array of shape %s' % ((t.shape[0], d),))
+        if s.size == 0:
+            s = np.zeros(1, np.float32)[:0]
+        check(self.lib.l3_embed_audio_frames(self.h, _ptr(s), s.size, _ptr(t), t.shape[0], pool[0], pool[1], _ptr(out)),
+              self.h)
+        return out
+
     def embed_vision(self, video, pool=(7, 7)):
         v = _f32(video)
         d = self.lib.l3_embed_dim(self.h, 1, pool[0], pool[1])
@@ -603,6 +622,18 @@ def op_frontend(model_type, audio, db_max_scope='sample', device=0):
              'cnn_L3_melspec1': (128, 199), 'cnn_L3_melspec2': (256, 199)}[model_type]
     out = np.empty((n, probe[0], probe[1], 1), np.float32)
     check(lib.l3_op_frontend(device, MODEL_IDS[model_type], _ptr(a), n, 0 if db_max_scope == 'sample' else 1, _ptr(out)))
+    return out
+
+
+def op_gather_frames(samples, table, device=0):
+    """l3_op_gather_frames: the (n_frames, 48000) frames l3_embed_audio_frames feeds the front-end."""
+    lib = load()
+    s = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+    t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 3)
+    if s.size == 0:
+        s = np.zeros(1, np.float32)[:0]
+    out = np.empty((t.shape[0], 48000), np.float32)
+    check(lib.l3_op_gather_frames(device, _ptr(s), s.size, _ptr(t), t.shape[0], _ptr(out)))
     return out
 
 

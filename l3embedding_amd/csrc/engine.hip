@@ -29,7 +29,7 @@ namespace {
 
 using namespace l3;
 
-static thread_local std::string g_create_error;
+static thread_local std::string g_create_error;      // l3_last_error(NULL): l3_create and the operator entry points
 
 constexpr float BN_EPS = 1e-3f;
 constexpr float BN_MOMENTUM = 0.99f;
@@ -208,6 +208,10 @@ struct l3_engine {
     // scratch
     float *red_scratch = nullptr, *wg_scratch = nullptr, *sq_scratch = nullptr, *emb_out = nullptr;
     size_t emb_out_cap = 0;
+    // l3_embed_audio_frames: the call's clip samples and frame table (grown on demand)
+    float* clip_samples = nullptr;
+    int64_t* clip_table = nullptr;
+    size_t clip_samples_cap = 0, clip_table_cap = 0;
     bool last_training = false;
     bool fwd_done = false;
 
@@ -265,6 +269,24 @@ int dev_alloc(l3_engine* e, void** p, size_t bytes) {
 template <class T>
 int dev_alloc_t(l3_engine* e, T** p, size_t count) {
     return dev_alloc(e, reinterpret_cast<void**>(p), count * sizeof(T));
+}
+// a buffer that grows on demand: the old one is freed (hipFree waits for the device) when `count` exceeds `*cap`
+template <class T>
+int dev_grow_t(l3_engine* e, T** p, size_t* cap, size_t count) {
+    if (count <= *cap) return L3_OK;
+    if (*p != nullptr) {
+        for (auto it = e->allocs.begin(); it != e->allocs.end(); ++it)
+            if (*it == (void*)*p) {
+                e->allocs.erase(it);
+                break;
+            }
+        (void)hipFree(*p);
+        *p = nullptr;
+        *cap = 0;
+    }
+    int rc = dev_alloc_t(e, p, count);
+    if (rc == L3_OK) *cap = count;
+    return rc;
 }
 
 // ---- TF padding helpers ---------------------------------------------------------------------
@@ -1700,6 +1722,9 @@ Tower* find_tower_tensor(l3_engine* e, const std::string& name, Tensor** out) {
 
 }  // namespace
 
+// the message l3_last_error(NULL) returns after an operator entry point (ops.hip) rejected its arguments
+void l3::set_op_error(const std::string& msg) { g_create_error = msg; }
+
 // =====================================================================================================
 // C ABI
 // =====================================================================================================
@@ -2556,25 +2581,42 @@ int64_t l3_embed_dim(const l3_engine* e, int vision, int pool_h, int pool_w) {
     return (int64_t)ho * wo * t.C;
 }
 
-static int embed_common(l3_engine* e, bool vision, const float* in, int64_t n, int ph, int pw, float* out) {
-    if (!e || !in || !out || n < 0) return L3_EINVAL;
-    HIPCHK(e, hipSetDevice(e->cfg.device));
+// Where the input rows of one engine batch come from: the caller's host rows (l3_embed_audio / l3_embed_vision) or the clip
+// frames gathered on the device from the samples and frame table l3_embed_audio_frames uploaded.
+struct EmbedSource {
+    const float* host = nullptr;          // n rows, host memory
+    const float* samples = nullptr;       // device (audio only)
+    const int64_t* table = nullptr;       // device, n x {start, lo, hi}
+};
+
+// Pooled rows stay on the device between two copies to the host; one copy (and one host wait) per call up to this many bytes.
+constexpr size_t EMBED_OUT_BYTES = (size_t)256 << 20;
+
+static int embed_check(l3_engine* e, bool vision, int ph, int pw, int64_t* D) {
     Tower& tw = vision ? e->vis : e->aud;
     if (tw.emb_conv_op < 0) {
         e->err = "model type has no embedding layer";
         return L3_EINVAL;
     }
-    const int64_t D = l3_embed_dim(e, vision ? 1 : 0, ph, pw);
-    if (D < 0) {
+    *D = l3_embed_dim(e, vision ? 1 : 0, ph, pw);
+    if (*D < 0) {
         e->err = "bad pooling size";
         return L3_EINVAL;
     }
+    return L3_OK;
+}
+
+// load_embedding(...).predict on n rows: per engine batch, the input rows -> (audio) front-end -> solo tower forward ->
+// MaxPooling2D into the device output buffer; the pooled rows go to the host when the buffer is full and at the end.
+static int embed_rows(l3_engine* e, bool vision, const EmbedSource& src, int64_t n, int ph, int pw, int64_t D, float* out) {
+    Tower& tw = vision ? e->vis : e->aud;
     const int B = e->B;
-    if ((size_t)B * D > e->emb_out_cap) {
-        int rc = dev_alloc_t(e, &e->emb_out, (size_t)B * D);
-        if (rc) return rc;
-        e->emb_out_cap = (size_t)B * D;
-    }
+    int64_t cap_rows = (int64_t)(EMBED_OUT_BYTES / ((size_t)D * 4)) / B * B;
+    if (cap_rows < B) cap_rows = B;
+    const int64_t need_rows = (n + B - 1) / B * B;
+    if (cap_rows > need_rows) cap_rows = need_rows;
+    int rc = dev_grow_t(e, &e->emb_out, &e->emb_out_cap, (size_t)cap_rows * D);
+    if (rc) return rc;
     const Tensor& t = tw.t[tw.ops[tw.emb_conv_op].out];
     PoolGeom pg{};
     pg.N = B; pg.H = t.H; pg.W = t.W; pg.C = t.C; pg.ph = ph; pg.pw = pw; pg.sh = ph; pg.sw = pw;
@@ -2583,22 +2625,41 @@ static int embed_common(l3_engine* e, bool vision, const float* in, int64_t n, i
     pg.out_batch_stride = D;
     const size_t per = vision ? (size_t)224 * 224 * 3 : (size_t)AUDIO_T;
     float* dst_in = vision ? e->video : e->audio;
+    int64_t f0 = 0;                 // first row the device output buffer holds
     for (int64_t s0 = 0; s0 < n; s0 += B) {
         const int64_t cnt = n - s0 < B ? n - s0 : B;
-        HIPCHK(e, hipMemcpyAsync(dst_in, in + (size_t)s0 * per, (size_t)cnt * per * 4, hipMemcpyHostToDevice, e->stream));
-        if (cnt < B) HIPCHK(e, hipMemsetAsync(dst_in + (size_t)cnt * per, 0, (size_t)(B - cnt) * per * 4, e->stream));
+        if (src.host) {
+            HIPCHK(e, hipMemcpyAsync(dst_in, src.host + (size_t)s0 * per, (size_t)cnt * per * 4, hipMemcpyHostToDevice, e->stream));
+            if (cnt < B) HIPCHK(e, hipMemsetAsync(dst_in + (size_t)cnt * per, 0, (size_t)(B - cnt) * per * 4, e->stream));
+        } else {
+            gather_frames(src.samples, src.table + 3 * s0, dst_in, B, (int)cnt, AUDIO_T, e->stream);
+        }
         if (!vision) {
-            int rc = run_frontend(e);
+            rc = run_frontend(e);
             if (rc) return rc;
         }
         set_solo(e, tw, 1);
         tower_forward(e, tw, false);
-        maxpool_fwd(t.d, e->emb_out, pg, e->stream);
-        HIPCHK(e, hipMemcpyAsync(out + (size_t)s0 * D, e->emb_out, (size_t)cnt * D * 4, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, l3::stream_wait(e->stream));
+        maxpool_fwd(t.d, e->emb_out + (size_t)(s0 - f0) * D, pg, e->stream);
+        if (s0 + cnt == n || s0 + 2 * B - f0 > cap_rows) {
+            HIPCHK(e, hipMemcpyAsync(out + (size_t)f0 * D, e->emb_out, (size_t)(s0 + cnt - f0) * D * 4, hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(e, l3::stream_wait(e->stream));
+            f0 = s0 + B;
+        }
     }
     prof_collect(e);
     return L3_OK;
+}
+
+static int embed_common(l3_engine* e, bool vision, const float* in, int64_t n, int ph, int pw, float* out) {
+    if (!e || !in || !out || n < 0) return L3_EINVAL;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    int64_t D = 0;
+    int rc = embed_check(e, vision, ph, pw, &D);
+    if (rc) return rc;
+    EmbedSource src;
+    src.host = in;
+    return embed_rows(e, vision, src, n, ph, pw, D, out);
 }
 
 int l3_embed_audio(l3_engine* e, const float* audio, int64_t n, int pool_h, int pool_w, float* out) {
@@ -2606,6 +2667,38 @@ int l3_embed_audio(l3_engine* e, const float* audio, int64_t n, int pool_h, int 
 }
 int l3_embed_vision(l3_engine* e, const float* video, int64_t n, int pool_h, int pool_w, float* out) {
     return embed_common(e, true, video, n, pool_h, pool_w, out);
+}
+
+int l3_embed_audio_frames(l3_engine* e, const float* samples, int64_t n_samples, const int64_t* table, int64_t n_frames,
+                          int pool_h, int pool_w, float* out) {
+    if (!e) return L3_EINVAL;
+    if (!samples || !table || !out) {
+        e->err = "l3_embed_audio_frames: samples, table and out must not be NULL";
+        return L3_EINVAL;
+    }
+    if (n_samples < 0 || n_frames < 0) {
+        e->err = "l3_embed_audio_frames: n_samples and n_frames must be >= 0";
+        return L3_EINVAL;
+    }
+    int64_t D = 0;
+    int rc = embed_check(e, false, pool_h, pool_w, &D);
+    if (rc) return rc;
+    int64_t bad = 0;
+    if (const char* why = frame_table_error(table, n_frames, n_samples, &bad)) {
+        e->err = std::string("l3_embed_audio_frames: frame ") + std::to_string(bad) + ": " + why;
+        return L3_EINVAL;
+    }
+    if (n_frames == 0) return L3_OK;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    if ((rc = dev_grow_t(e, &e->clip_samples, &e->clip_samples_cap, (size_t)n_samples))) return rc;
+    if ((rc = dev_grow_t(e, &e->clip_table, &e->clip_table_cap, (size_t)n_frames * 3))) return rc;
+    if (n_samples > 0)
+        HIPCHK(e, hipMemcpyAsync(e->clip_samples, samples, (size_t)n_samples * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->clip_table, table, (size_t)n_frames * 3 * 8, hipMemcpyHostToDevice, e->stream));
+    EmbedSource src;
+    src.samples = e->clip_samples;
+    src.table = e->clip_table;
+    return embed_rows(e, false, src, n_frames, pool_h, pool_w, D, out);
 }
 
 int l3_activation_numel(l3_engine* e, const char* name, int64_t* numel) {

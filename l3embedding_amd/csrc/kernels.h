@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 namespace l3 {
 
 struct ConvGeom {
@@ -270,6 +272,24 @@ void dft_fused(const float* audio, const float* win, const float* b1, const floa
 void spec_to_features(const float* spec, const float* melw, const int* mel_start, const int* mel_len,
                       const int* mel_off, float* out, int B, const FrontendCfg& c, hipStream_t s, const float* nyq = nullptr);
 void db_normalize(float* x, float* smax, int B, int64_t per_sample, int batch_scope, hipStream_t s);
+
+// frames of whole clips (clips.hip; data/usc/features.py:276-300): out row r (T floats) = samples[start_r + j] where
+// lo_r <= start_r + j < hi_r, else 0; table = rows x {start, lo, hi}; rows >= n_real are zeroed
+void gather_frames(const float* samples, const int64_t* table, float* out, int rows, int n_real, int T, hipStream_t s);
+void set_op_error(const std::string& msg);       // engine.hip: l3_last_error(NULL) of an operator entry point
+// host-side check of such a table against a buffer of n_samples: nullptr if every row is valid, else what is wrong
+inline const char* frame_table_error(const int64_t* table, int64_t n_frames, int64_t n_samples, int64_t* bad_row) {
+    const int64_t lim = (int64_t)1 << 62;          // start + j never overflows
+    for (int64_t r = 0; r < n_frames; ++r) {
+        const int64_t start = table[3 * r], lo = table[3 * r + 1], hi = table[3 * r + 2];
+        *bad_row = r;
+        if (lo < 0) return "lo < 0";
+        if (lo > hi) return "lo > hi";
+        if (hi > n_samples) return "hi > n_samples";
+        if (start < -lim || start > lim) return "start out of range";
+    }
+    return nullptr;
+}
 
 // head: dense + softmax + categorical cross-entropy
 void dense_fwd(const float* x, const float* w, const float* b, float* y, int B, int K, int N, int relu,

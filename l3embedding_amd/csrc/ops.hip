@@ -468,6 +468,35 @@ int l3_op_preprocess(int device, const uint8_t* video_u8, int64_t nv, float* vid
     return sc.status();
 }
 
+int l3_op_gather_frames(int device, const float* samples, int64_t n_samples, const int64_t* table, int64_t n_frames,
+                        float* frames) {
+    if (!samples || !table || !frames || n_samples < 0 || n_frames < 0) {
+        set_op_error("l3_op_gather_frames: NULL pointer or negative count");
+        return L3_EINVAL;
+    }
+    int64_t bad = 0;
+    if (const char* why = frame_table_error(table, n_frames, n_samples, &bad)) {
+        set_op_error(std::string("l3_op_gather_frames: frame ") + std::to_string(bad) + ": " + why);
+        return L3_EINVAL;
+    }
+    Scope sc(device);
+    if (!sc.ok) {
+        set_op_error("l3_op_gather_frames: HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)");
+        return L3_EHIP;
+    }
+    constexpr int T = 48000;
+    const float* d_s = sc.put(samples, (size_t)n_samples);
+    const int64_t* d_t = sc.put(table, (size_t)n_frames * 3);
+    float* d_f = sc.alloc<float>((size_t)n_frames * T);
+    if (!sc.ok) return L3_ENOMEM;
+    for (int64_t r0 = 0; r0 < n_frames; r0 += 65535) {
+        const int rows = (int)(n_frames - r0 < 65535 ? n_frames - r0 : 65535);
+        gather_frames(d_s, d_t + 3 * r0, d_f + (size_t)r0 * T, rows, rows, T, sc.s);
+    }
+    sc.get(frames, d_f, (size_t)n_frames * T);
+    return sc.status();
+}
+
 int l3_op_frontend(int device, int model_type, const float* audio, int n, int db_max_scope, float* out) {
     // runs the engine's own front-end path on a throw-away engine of batch n
     l3_config cfg{};

@@ -740,10 +740,93 @@ class EmbeddingModel(object):
             return e.embed_audio(x, self.pool)
         return e.embed_vision(x, self.pool)
 
+    # Caps of one l3_embed_audio_frames call of predict_clips (device memory held by a call: the samples, the frame table
+    # and the pooled rows): at most CLIP_CALL_FRAMES frames and CLIP_CALL_SAMPLES samples (256 MiB of float32) -- or one
+    # engine batch of frames, whatever its span, if that is more.  Larger inputs are split into several calls at engine-batch
+    # boundaries of the frame list: between clips or inside one clip's frames.
+    CLIP_CALL_FRAMES = 4096
+    CLIP_CALL_SAMPLES = 1 << 26
+
+    def predict_clips(self, clips, hop_length, batch_size=32):
+        """get_l3_frames_uniform's framing + predict for many clips at once (data/usc/features.py:276-306): clips is a
+        sequence of 1-D float32 arrays at 48 kHz, hop_length the hop in samples.  Returns one (n_i, D) array per clip, n_i
+        from features.frame_table.  The engine is chosen as predict chooses it (the model's current one, else batch
+        min(batch_size, frames)).  Each clip is sent to the device once and cut into frames there.  Under
+        db_max_scope = 'sample' the frames of consecutive clips share engine batches; under 'batch' (the dB maximum over
+        an engine batch, kapre 0.1.3.1) every clip starts a new engine batch, so the batches are those of one predict call
+        per clip."""
+        from .features import frame_table
+        if self.embedding_type != 'audio':
+            raise TypeError('predict_clips needs an audio embedding model')
+        clips = [np.asarray(c, dtype=np.float32) for c in clips]
+        for c in clips:
+            if c.ndim != 1:
+                raise ValueError('every clip must be a 1-D array (got shape %s)' % (c.shape,))
+        lengths = np.array([c.size for c in clips], np.int64)
+        table, counts = frame_table(lengths, hop_length)
+        if not clips:
+            return []
+        total = int(counts.sum())
+        e = self.base._ensure_engine(self.base._engine.batch if self.base._engine is not None else max(1, min(batch_size, total)))
+        B = e.batch
+        ends = np.cumsum(lengths)
+        # rows of the engine's frame list: under 'batch' scope each clip padded to whole engine batches with empty frames
+        if self.base.db_max_scope == 'sample':
+            rows, row0 = table, np.concatenate([[0], np.cumsum(counts)[:-1]])
+        else:
+            padded = -(-counts // B) * B
+            row0 = np.concatenate([[0], np.cumsum(padded)[:-1]])
+            rows = np.empty((int(padded.sum()), 3), np.int64)
+            rows[:] = np.repeat(ends, padded)[:, None]                  # empty frames at the clip's end: lo == hi
+            first = np.concatenate([[0], np.cumsum(counts)[:-1]])
+            for i in range(len(clips)):
+                rows[row0[i]:row0[i] + counts[i]] = table[first[i]:first[i] + counts[i]]
+        # samples each row reads: [a, b) -- ascending over the rows, so a call's rows read one contiguous stretch
+        a = np.maximum(rows[:, 0], rows[:, 1])
+        b = np.maximum(np.minimum(rows[:, 0] + 48000, rows[:, 2]), a)
+        b = np.maximum.accumulate(b)
+        D = int(e.lib.l3_embed_dim(e.h, 0, self.pool[0], self.pool[1]))
+        out = np.empty((len(rows), D), np.float32)
+        max_frames = max(B, self.CLIP_CALL_FRAMES // B * B)
+        offs = ends - lengths
+        r0, n = 0, len(rows)
+        while r0 < n:
+            r1 = min(n, r0 + B)
+            while r1 < n:
+                r2 = min(n, r1 + B)
+                if r2 - r0 > max_frames or b[r2 - 1] - a[r0] > self.CLIP_CALL_SAMPLES:
+                    break
+                r1 = r2
+            base, top = int(a[r0]), int(b[r1 - 1])
+            t = np.empty((r1 - r0, 3), np.int64)
+            t[:, 0] = rows[r0:r1, 0] - base
+            t[:, 1] = a[r0:r1] - base
+            t[:, 2] = np.maximum(np.minimum(rows[r0:r1, 0] + 48000, rows[r0:r1, 2]), a[r0:r1]) - base
+            e.embed_audio_frames(_clip_span(clips, offs, base, top), t, self.pool, out=out[r0:r1])
+            r0 = r1
+        return [out[row0[i]:row0[i] + counts[i]] for i in range(len(clips))]
+
     @property
     def output_shape(self):
         e = self.base._ensure_engine(self.base._engine.batch if self.base._engine is not None else 1)
         return (None, int(e.lib.l3_embed_dim(e.h, 1 if self.embedding_type == 'vision' else 0, self.pool[0], self.pool[1])))
+
+
+def _clip_span(clips, offs, base, top):
+    """Samples [base, top) of the clips laid back to back (offs: each clip's first sample): a view when the span lies in one
+    clip, else a concatenation of the pieces."""
+    i = int(np.searchsorted(offs, base, side='right')) - 1 if len(offs) else 0
+    pieces = []
+    while base < top:
+        while offs[i] + clips[i].size <= base:
+            i += 1
+        lo = base - int(offs[i])
+        hi = min(clips[i].size, top - int(offs[i]))
+        pieces.append(clips[i][lo:hi])
+        base += hi - lo
+    if len(pieces) == 1:
+        return pieces[0]
+    return np.concatenate(pieces) if pieces else np.zeros(0, np.float32)
 
 
 # ---------------------------------------------------------------------------------------------------
