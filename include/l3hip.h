@@ -325,6 +325,60 @@ int l3_op_bn_stats_from_partials(int device, const float *part, int nblk, int c,
 int l3_op_preprocess(int device, const uint8_t *video_u8, int64_t nv, float *video,
                      const int16_t *audio_i16, int64_t na, float *audio);
 
+/* ---- Downstream MLP classifier (classifier/train.py:230-391) ------------------------------------------------------------------
+ * construct_mlp_model (train.py:230-257): Dense(512, relu) -> Dense(128, relu) -> Dense(C, softmax), kernel_regularizer
+ * l2(weight_decay) on each kernel (biases not regularised), compiled with keras-2.0.9 Adam(lr) and categorical_crossentropy; fit as
+ * train_mlp does (train.py:260-391).  fp32 throughout on the fp32 matrix cores; deterministic (no float atomics).  A handle owns its
+ * device buffers and one stream; calls on one handle are not re-entrant.  Errors: l3_last_error(NULL) gives the message. */
+typedef struct l3_mlp l3_mlp;
+/* construct_mlp_model(input_shape=(D,), weight_decay, num_classes=C) + Adam state for batches of up to `batch` rows (1..4096),
+ * 2 <= C <= 64.  Kernels: keras glorot_uniform (U(-l, l), l = sqrt(6 / (fan_in + fan_out))) from a host generator seeded with
+ * `seed`; biases zero; Adam moments zero. */
+int l3_mlp_create(int device, int D, int C, int batch, float weight_decay, uint64_t seed, l3_mlp **m);
+void l3_mlp_destroy(l3_mlp *m);
+/* D*512 + 512 + 512*128 + 128 + 128*C + C */
+int64_t l3_mlp_param_count(const l3_mlp *m);
+/* m.fit's x / y and validation_data (train.py:357-359): float32 (n, D) row-major features and int32 class indices, copied to the
+ * device once (replacing any earlier set).  n_valid may be 0 (no validation: val_* are NaN).  L3_EINVAL: a label outside [0, C),
+ * n_train <= 0, more than 2^31 - 1 rows; L3_ENOMEM: more than 64 GiB of features (the documented cap) or a failed allocation. */
+int l3_mlp_set_data(l3_mlp *m, const float *X_train, const int32_t *y_train, int64_t n_train,
+                    const float *X_valid, const int32_t *y_valid, int64_t n_valid);
+/* One epoch of keras fit (shuffle=True): the ceil(n_train / batch) Adam steps over the rows in `perm` order (a permutation of
+ * [0, n_train) drawn by the caller; the last batch is partial), Adam steps t0 + 1, t0 + 2, ... (t0 = steps taken before), then
+ * the validation rows.  stats_out[4] = loss, acc, val_loss, val_acc as keras logs them: a batch's loss is its mean cross-entropy +
+ * weight_decay * sum of the squared kernels before its update, loss / acc are batch-size-weighted means over the epoch, val_loss
+ * holds the L2 term of the end-of-epoch weights.  No host synchronisation between the steps. */
+int l3_mlp_epoch(l3_mlp *m, const int32_t *perm, float lr, int64_t t0, double *stats_out);
+/* m.predict(X) (train.py:372-384): softmax probabilities (n, C) of host rows X (n, D), staged in large row blocks. */
+int l3_mlp_predict(l3_mlp *m, const float *X, int64_t n, float *probs_out);
+/* get_weights / set_weights in keras order: dense_1 kernel (D,512), bias (512), dense_2 kernel (512,128), bias (128), dense_3
+ * kernel (128,C), bias (C), concatenated; n must be l3_mlp_param_count.  set_weights leaves the Adam moments as they are. */
+int l3_mlp_get_weights(l3_mlp *m, float *dst, int64_t n);
+int l3_mlp_set_weights(l3_mlp *m, const float *src, int64_t n);
+
+/* Operators of the MLP step on their own (host buffers; parity tests).  x has n_x rows of K floats; idx (int32, may be NULL =
+ * identity) picks the `rows` rows the product uses, in order -- the gathered rows of the epoch's shuffle.
+ * y (rows, N) = act(x[idx] . w + b), w (K, N); relu 0/1.  The first layer's split-K path included. */
+int l3_op_mlp_dense_fwd(int device, const float *x, int64_t n_x, const int32_t *idx, int rows, int K, int N, const float *w,
+                        const float *b, int relu, float *y);
+/* dx (rows, K) = (dy (rows, N) . w^T) * [h > 0]; h (rows, K) NULL: no ReLU mask */
+int l3_op_mlp_dense_bwd_x(int device, const float *dy, const float *w, const float *h, int rows, int K, int N, float *dx);
+/* dw (K, N) = x[idx]^T . dy, db (N) = column sums of dy: the kernel of l3_op_mlp_wgrad_adam with Adam switched off */
+int l3_op_mlp_wgrad(int device, const float *x, int64_t n_x, const int32_t *idx, int rows, int K, int N, const float *dy, float *dw,
+                    float *db);
+/* The fused step: the same gradient, + 2 * weight_decay * w (kernel only), keras Adam at lr_t (beta 0.9 / 0.999, eps 1e-8) on
+ * w, b and their moments (all in/out); w2_out (may be NULL) = sum of the PRE-update w^2.  Bit for bit l3_op_mlp_wgrad followed
+ * by l3_op_adam. */
+int l3_op_mlp_wgrad_adam(int device, const float *x, int64_t n_x, const int32_t *idx, int rows, int K, int N, const float *dy,
+                         float *w, float *b, float *mw, float *vw, float *mb, float *vb, float weight_decay, float lr_t,
+                         float *w2_out);
+/* softmax + keras categorical_crossentropy of logits z (rows, C <= 64) against class indices; gscale scales the gradient dz (keras
+ * mean: 1 / rows).  probs / dz / ce (per-row loss) / correct (per-row 0/1) may each be NULL. */
+int l3_op_mlp_softmax_ce(int device, const float *z, const int32_t *labels, int rows, int C, float gscale, float *probs, float *dz,
+                         float *ce, float *correct);
+/* The engine's Adam kernel (keras 2.0.9 + L2 gradient 2 * l2 * p on the first n_l2 elements) on its own: p, m, v in/out. */
+int l3_op_adam(int device, float *p, const float *g, float *m, float *v, int64_t n, int64_t n_l2, float l2x2, float lr_t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,24 @@ SIGNATURES = {
     'l3_op_bn_stats_from_partials': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_float,
                                                C.c_void_p, C.c_void_p]),
     'l3_op_preprocess': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    # downstream MLP classifier (csrc/mlp.hip)
+    'l3_mlp_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.POINTER(C.c_void_p)]),
+    'l3_mlp_destroy': (None, [C.c_void_p]),
+    'l3_mlp_param_count': (C.c_int64, [C.c_void_p]),
+    'l3_mlp_set_data': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_mlp_epoch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.POINTER(C.c_double)]),
+    'l3_mlp_predict': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_mlp_get_weights': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_mlp_set_weights': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_op_mlp_dense_fwd': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_void_p]),
+    'l3_op_mlp_dense_bwd_x': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'l3_op_mlp_wgrad': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    'l3_op_mlp_wgrad_adam': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+                             + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p]),
+    'l3_op_mlp_softmax_ce': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 4),
+    'l3_op_adam': (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_float, C.c_float]),
 }
 
 
@@ -646,3 +664,149 @@ def op_preprocess(video_u8=None, audio_i16=None, device=0):
     check(lib.l3_op_preprocess(device, _ptr(v), 0 if v is None else v.size, _ptr(vo),
                                _ptr(a), 0 if a is None else a.size, _ptr(ao)))
     return vo, ao
+
+
+# ---- downstream MLP classifier (classifier/train.py:230-391; csrc/mlp.hip) ---------------------------------------------------------
+MLP_HIDDEN = (512, 128)
+MLP_MAX_CLASSES = 64
+MLP_MAX_BATCH = 4096
+
+
+def mlp_shapes(D, num_classes):
+    """keras get_weights() order of construct_mlp_model: kernel (in, out), bias per Dense layer."""
+    return [(D, 512), (512,), (512, 128), (128,), (128, num_classes), (num_classes,)]
+
+
+def _i32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+
+
+class MLP(object):
+    """RAII wrapper over an l3_mlp handle: construct_mlp_model + Adam state on one device."""
+
+    def __init__(self, D, num_classes, batch, weight_decay=1e-5, seed=0, device=0):
+        self.lib = load()
+        self.D, self.C, self.batch, self.weight_decay = int(D), int(num_classes), int(batch), float(weight_decay)
+        h = C.c_void_p()
+        check(self.lib.l3_mlp_create(int(device), self.D, self.C, self.batch, self.weight_decay, int(seed) & (2 ** 64 - 1),
+                                     C.byref(h)), None)
+        self.h = h
+        self.n_train = self.n_valid = 0
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_mlp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def param_count(self):
+        return int(self.lib.l3_mlp_param_count(self.h))
+
+    def get_weights(self):
+        flat = np.empty(self.param_count(), np.float32)
+        check(self.lib.l3_mlp_get_weights(self.h, _ptr(flat), flat.size))
+        out, o = [], 0
+        for shp in mlp_shapes(self.D, self.C):
+            n = int(np.prod(shp))
+            out.append(flat[o:o + n].reshape(shp).copy())
+            o += n
+        return out
+
+    def set_weights(self, weights):
+        shapes = mlp_shapes(self.D, self.C)
+        if len(weights) != len(shapes):
+            raise ValueError('expected %d arrays, got %d' % (len(shapes), len(weights)))
+        for w, shp in zip(weights, shapes):
+            if tuple(np.shape(w)) != shp:
+                raise ValueError('weight shape %s, expected %s' % (np.shape(w), shp))
+        flat = np.concatenate([np.asarray(w, np.float32).ravel() for w in weights])
+        check(self.lib.l3_mlp_set_weights(self.h, _ptr(flat), flat.size))
+
+    def set_data(self, X_train, y_train, X_valid=None, y_valid=None):
+        xt, yt = _f32(X_train), _i32(y_train)
+        xv = _f32(X_valid) if X_valid is not None else None
+        yv = _i32(y_valid) if y_valid is not None else None
+        nv = 0 if xv is None else xv.shape[0]
+        check(self.lib.l3_mlp_set_data(self.h, _ptr(xt), _ptr(yt), xt.shape[0], _ptr(xv), _ptr(yv), nv))
+        self.n_train, self.n_valid = xt.shape[0], nv
+
+    def epoch(self, perm, lr, t0):
+        """-> dict(loss, acc, val_loss, val_acc) of one epoch over the rows in `perm` order, Adam steps t0 + 1, ..."""
+        p = _i32(perm)
+        if p.shape != (self.n_train,):
+            raise ValueError('perm must have n_train = %d entries' % self.n_train)
+        st = (C.c_double * 4)()
+        check(self.lib.l3_mlp_epoch(self.h, _ptr(p), float(lr), int(t0), st))
+        return dict(loss=st[0], acc=st[1], val_loss=st[2], val_acc=st[3])
+
+    def predict(self, X):
+        x = _f32(X)
+        out = np.empty((x.shape[0], self.C), np.float32)
+        if x.shape[0]:
+            check(self.lib.l3_mlp_predict(self.h, _ptr(x), x.shape[0], _ptr(out)))
+        return out
+
+
+def op_mlp_dense_fwd(x, w, b, idx=None, relu=True, device=0):
+    x, w, b = _f32(x), _f32(w), _f32(b)
+    idx = _i32(idx)
+    rows = x.shape[0] if idx is None else idx.shape[0]
+    K, N = w.shape
+    y = np.empty((rows, N), np.float32)
+    check(load().l3_op_mlp_dense_fwd(device, _ptr(x), x.shape[0], _ptr(idx), rows, K, N, _ptr(w), _ptr(b), int(bool(relu)),
+                                     _ptr(y)))
+    return y
+
+
+def op_mlp_dense_bwd_x(dy, w, h=None, device=0):
+    dy, w, h = _f32(dy), _f32(w), _f32(h)
+    K, N = w.shape
+    dx = np.empty((dy.shape[0], K), np.float32)
+    check(load().l3_op_mlp_dense_bwd_x(device, _ptr(dy), _ptr(w), _ptr(h), dy.shape[0], K, N, _ptr(dx)))
+    return dx
+
+
+def op_mlp_wgrad(x, dy, idx=None, device=0):
+    x, dy, idx = _f32(x), _f32(dy), _i32(idx)
+    rows, N = dy.shape
+    K = x.shape[1]
+    dw, db = np.empty((K, N), np.float32), np.empty(N, np.float32)
+    check(load().l3_op_mlp_wgrad(device, _ptr(x), x.shape[0], _ptr(idx), rows, K, N, _ptr(dy), _ptr(dw), _ptr(db)))
+    return dw, db
+
+
+def op_mlp_wgrad_adam(x, dy, w, b, mw, vw, mb, vb, weight_decay, lr_t, idx=None, device=0):
+    """-> (w, b, mw, vw, mb, vb) after one fused step, sum of the pre-update w^2"""
+    x, dy, idx = _f32(x), _f32(dy), _i32(idx)
+    st = [np.array(a, np.float32, copy=True, order='C') for a in (w, b, mw, vw, mb, vb)]
+    rows, N = dy.shape
+    K = x.shape[1]
+    w2 = np.zeros(1, np.float32)
+    check(load().l3_op_mlp_wgrad_adam(device, _ptr(x), x.shape[0], _ptr(idx), rows, K, N, _ptr(dy), *[_ptr(a) for a in st],
+                                      float(weight_decay), float(lr_t), _ptr(w2)))
+    return tuple(st), float(w2[0])
+
+
+def op_mlp_softmax_ce(z, labels, gscale=None, device=0):
+    """-> probs, dz, per-row ce, per-row correct (0/1); gscale defaults to keras' mean, 1 / rows"""
+    z, labels = _f32(z), _i32(labels)
+    rows, Cn = z.shape
+    probs, dz = np.empty_like(z), np.empty_like(z)
+    ce, cor = np.empty(rows, np.float32), np.empty(rows, np.float32)
+    g = 1.0 / rows if gscale is None else gscale
+    check(load().l3_op_mlp_softmax_ce(device, _ptr(z), _ptr(labels), rows, Cn, float(g), _ptr(probs), _ptr(dz), _ptr(ce),
+                                      _ptr(cor)))
+    return probs, dz, ce, cor
+
+
+def op_adam(p, g, m, v, n_l2, l2x2, lr_t, device=0):
+    """The engine's Adam kernel on flat arrays -> (p, m, v)"""
+    p, m, v = [np.array(a, np.float32, copy=True).ravel() for a in (p, m, v)]
+    g = _f32(g).ravel()
+    check(load().l3_op_adam(device, _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.size, int(n_l2), float(l2x2), float(lr_t)))
+    return p, m, v

@@ -1,0 +1,387 @@
+"""The downstream sound classifier trained on L3 embeddings: the reference's classifier/train.py (construct_mlp_model :230-257,
+train_mlp :260-391, train_param_search :394-492, train :495-709 for model_type='mlp') and classifier/metrics.py:8-46.
+
+The MLP trains on the GPU through the l3_mlp handle of libl3hip (csrc/mlp.hip); everything here is the Keras-shaped shell around
+it.  Deviations from the reference, all deliberate:
+  * the epoch shuffle is drawn from np.random.RandomState(random_state) (the reference's seeding is commented out, so its runs
+    are not reproducible); the Glorot initialisation is seeded with random_state too;
+  * the random start delay and the Google Sheets logging of train() are skipped; config.json has git_commit None;
+  * the scalers are pickled with `pickle` (the reference uses sklearn's joblib; these are NumPy restatements, usc.py);
+  * SVM, random forest and StratifiedShuffleSplit (sklearn on the host) are not built: they raise.
+"""
+import datetime
+import getpass
+import json
+import logging
+import os
+import pickle as pk
+from itertools import product
+
+import numpy as np
+
+from . import _lib, callbacks, kerasfile
+from .usc import get_split, preprocess_split_data
+
+LOGGER = logging.getLogger('classifier')
+
+DATASET_NUM_CLASSES = {
+    'us8k': 10,
+    'esc50': 50,
+    'dcase2013': 10,
+}
+
+ONLY_MLP = 'only the mlp classifier is built (model_type {!r}: the SVM and random forest are sklearn on the host, with no GPU path)'
+NO_SSS = ('the parameter search without a validation fold needs sklearn\'s StratifiedShuffleSplit, which is not built: '
+          'search on the validation fold instead')
+
+
+class EarlyStopping(callbacks.Callback):
+    """[3P] keras.callbacks.EarlyStopping of keras 2.0.x (monitor 'val_loss', mode min, min_delta 0): the wait counter is tested
+    BEFORE it is incremented, so training stops at the end of the (patience + 1)-th epoch in a row without improvement."""
+
+    def __init__(self, monitor='val_loss', patience=0, min_delta=0.0):
+        self.monitor, self.patience, self.min_delta = monitor, int(patience), abs(min_delta)
+
+    def on_train_begin(self, logs=None):
+        self.wait = 0
+        self.stopped_epoch = 0
+        self.best = np.inf
+
+    def on_epoch_end(self, epoch, logs=None):
+        current = (logs or {}).get(self.monitor)
+        if current is None:
+            return
+        if current + self.min_delta < self.best:
+            self.best = current
+            self.wait = 0
+        else:
+            if self.wait >= self.patience:
+                self.stopped_epoch = epoch
+                self.model.stop_training = True
+            self.wait += 1
+
+
+class MetricCallback(callbacks.Callback):
+    """train.py:46-80: the per-epoch loss / accuracy series train_mlp reports."""
+
+    SERIES = (('train_loss', 'loss'), ('train_acc', 'acc'), ('valid_loss', 'val_loss'), ('valid_acc', 'val_acc'))
+
+    def __init__(self, valid_data=None, verbose=False):
+        self.valid_data, self.verbose = valid_data, verbose
+
+    def on_train_begin(self, logs=None):
+        for attr, _ in self.SERIES:
+            setattr(self, attr, [])
+
+    def on_epoch_end(self, epoch, logs=None):
+        logs = logs or {}
+        for attr, key in self.SERIES:
+            getattr(self, attr).append(logs.get(key))
+        if self.verbose:
+            LOGGER.info('epoch %d: %s', epoch, ', '.join('%s %.6f' % (k, logs[k]) for _, k in self.SERIES if k in logs))
+
+
+class MLPModel(object):
+    """What train_mlp uses of the Keras Model construct_mlp_model returns: compile / fit / predict / save_weights /
+    load_weights / get_weights / set_weights.  The state lives on the GPU (an l3_mlp handle, created for the batch size of the
+    first fit); the Adam step count and moments carry over between fit calls as Keras' optimizer state does, so a later fit
+    must use the same batch size (a different one raises ValueError once the model has trained)."""
+
+    name = 'urban_sound_classifier'
+
+    def __init__(self, input_dim, weight_decay=1e-5, num_classes=10, seed=0, device=0):
+        self.input_dim, self.weight_decay, self.num_classes = int(input_dim), float(weight_decay), int(num_classes)
+        self.seed, self.device = int(seed), device
+        self.lr = 1e-3
+        self.stop_training = False
+        self.iterations = 0
+        self._h = None
+        self._weights = None
+
+    def _handle(self, batch=64):
+        if self._h is not None and self._h.batch != batch and self.iterations > 0:
+            # a new handle would carry the weights over but start Adam's moments from zero, which Keras never does
+            raise ValueError('this model trained with batch size %d; fitting with batch size %d would reset its optimizer '
+                             'state' % (self._h.batch, batch))
+        if self._h is None or self._h.batch != batch:
+            weights = self.get_weights() if (self._h is not None or self._weights is not None) else None
+            if self._h is not None:
+                self._h.close()
+            self._h = _lib.MLP(self.input_dim, self.num_classes, batch, weight_decay=self.weight_decay, seed=self.seed,
+                               device=self.device)
+            if weights is not None:
+                self._h.set_weights(weights)
+            self._weights = None
+        return self._h
+
+    def compile(self, optimizer=None, loss='categorical_crossentropy', metrics=None, lr=None):
+        if loss != 'categorical_crossentropy':
+            raise ValueError('only categorical_crossentropy is built')
+        if lr is None:
+            lr = getattr(optimizer, 'lr', 1e-3) if optimizer is not None else 1e-3
+        self.lr = float(lr)
+
+    def get_weights(self):
+        if self._h is None and self._weights is not None:
+            return [w.copy() for w in self._weights]
+        return self._handle().get_weights() if self._h is None else self._h.get_weights()
+
+    def set_weights(self, weights):
+        if self._h is None:
+            shapes = _lib.mlp_shapes(self.input_dim, self.num_classes)
+            if [tuple(np.shape(w)) for w in weights] != shapes:
+                raise ValueError('weight shapes %s, expected %s' % ([np.shape(w) for w in weights], shapes))
+            self._weights = [np.asarray(w, np.float32).copy() for w in weights]
+        else:
+            self._h.set_weights(weights)
+
+    def save_weights(self, filepath, overwrite=True):
+        kerasfile.save_dense_weights(filepath, self.get_weights())
+
+    def load_weights(self, filepath):
+        self.set_weights(kerasfile.load_dense_weights(filepath))
+
+    def predict(self, x, batch_size=None, verbose=0):
+        return self._handle(self._h.batch if self._h is not None else 64).predict(x)
+
+    def fit(self, x, y, batch_size=64, epochs=1, verbose=0, callbacks=None, validation_split=0.0, validation_data=None,
+            shuffle=True, random_state=None):
+        """keras Model.fit with shuffle=True: y one-hot (n, C); validation_split takes the LAST fraction of x before any
+        shuffling (split_at = int(n * (1 - validation_split))).  -> {'loss': [...], 'acc': [...], 'val_loss': ..., 'val_acc': ...}"""
+        x = np.asarray(x, np.float32)
+        labels = np.argmax(np.asarray(y), axis=1).astype(np.int32)
+        if validation_data is not None:
+            vx = np.asarray(validation_data[0], np.float32)
+            vy = np.argmax(np.asarray(validation_data[1]), axis=1).astype(np.int32)
+        elif validation_split and 0.0 < validation_split < 1.0:
+            split_at = int(len(x) * (1.0 - validation_split))
+            x, vx = x[:split_at], x[split_at:]
+            labels, vy = labels[:split_at], labels[split_at:]
+        else:
+            vx = vy = None
+        h = self._handle(int(batch_size))
+        h.set_data(x, labels, vx, vy)
+        rs = np.random.RandomState(random_state)
+        cbs = list(callbacks or [])
+        for cb in cbs:
+            cb.set_model(self)
+            cb.set_params({'epochs': epochs, 'batch_size': batch_size, 'samples': len(x)})
+        history = {}
+        self.stop_training = False
+        for cb in cbs:
+            cb.on_train_begin()
+        steps = -(-len(x) // int(batch_size))
+        for epoch in range(int(epochs)):
+            for cb in cbs:
+                cb.on_epoch_begin(epoch)
+            perm = rs.permutation(len(x)) if shuffle else np.arange(len(x))
+            logs = h.epoch(perm, self.lr, self.iterations)
+            self.iterations += steps
+            if vx is None:
+                logs = {k: logs[k] for k in ('loss', 'acc')}
+            for k, v in logs.items():
+                history.setdefault(k, []).append(v)
+            if verbose:
+                LOGGER.info('Epoch %d/%d - %s', epoch + 1, epochs, ' - '.join('%s: %.4f' % kv for kv in sorted(logs.items())))
+            for cb in cbs:
+                cb.on_epoch_end(epoch, dict(logs))
+            if self.stop_training:
+                break
+        for cb in cbs:
+            cb.on_train_end()
+        return history
+
+
+def construct_mlp_model(input_shape, weight_decay=1e-5, num_classes=10, seed=0):
+    """train.py:230-257: Dense(512, relu) -> Dense(128, relu) -> Dense(num_classes, softmax), l2(weight_decay) on each kernel.
+    -> (model, input_shape, output_shape)"""
+    m = MLPModel(int(np.prod(input_shape)), weight_decay=weight_decay, num_classes=num_classes, seed=seed)
+    return m, tuple(input_shape), (num_classes,)
+
+
+def one_hot(labels, num_classes):
+    labels = np.asarray(labels).reshape(-1).astype(np.int64)
+    out = np.zeros((labels.size, num_classes))
+    out[np.arange(labels.size), labels] = 1.0
+    return out
+
+
+def _class_indices(a):
+    """class indices from labels, one-hot rows or probability rows"""
+    a = np.asarray(a)
+    return a.argmax(axis=1) if a.ndim == 2 else a
+
+
+def compute_metrics(y, pred, num_classes=10):
+    """classifier/metrics.py:8-46: overall accuracy, the accuracy within each true class (NaN for a class with no example)
+    and their unweighted mean.  y and pred may be indices or (n, C) rows."""
+    truth, guess = _class_indices(y), _class_indices(pred)
+    hit = truth == guess
+    per_class = []
+    for c in range(num_classes):
+        members = truth == c
+        per_class.append(hit[members].mean() if members.any() else np.nan)
+    return {'accuracy': hit.mean(), 'class_accuracy': per_class, 'average_class_accuracy': np.mean(per_class)}
+
+
+def _series_metrics(series, at):
+    """loss / accuracy at the checkpoint epoch and their whole histories, from a MetricCallback's two series"""
+    loss, acc = series
+    return {'loss': loss[at], 'loss_history': list(loss), 'accuracy': acc[at], 'accuracy_history': list(acc)}
+
+
+def _file_predictions(frame_probs, file_idxs):
+    """one class per file: the argmax of the mean of its frames' probabilities"""
+    return np.array([frame_probs[s:e].mean(axis=0).argmax() for s, e in file_idxs])
+
+
+def train_mlp(train_data, valid_data, test_data, model_dir, batch_size=64, num_epochs=100, valid_split=0.15, patience=20,
+              learning_rate=1e-4, weight_decay=1e-5, num_classes=10, random_state=12345678, verbose=False, **kwargs):
+    """classifier/train.py:260-391 -> (model, train_metrics, valid_metrics, test_metrics).  With a validation split the
+    last `valid_split` of the training rows validate (keras validation_split); with one, valid_split is ignored."""
+    features = train_data['features']
+    targets = one_hot(train_data['labels'], num_classes)
+    held_out = None
+    if valid_data:
+        held_out = (valid_data['features'], one_hot(valid_data['labels'], num_classes))
+
+    model, _, _ = construct_mlp_model(features.shape[1:], weight_decay=weight_decay, num_classes=num_classes,
+                                      seed=random_state)
+    best_path = os.path.join(model_dir, 'model.h5')
+    series = MetricCallback(valid_data, verbose=verbose)
+    hooks = [callbacks.ModelCheckpoint(best_path, monitor='val_loss', save_best_only=True, save_weights_only=True),
+             EarlyStopping(monitor='val_loss', patience=patience),
+             callbacks.LossHistory(os.path.join(model_dir, 'history_checkpoint.pkl')),
+             callbacks.CSVLogger(os.path.join(model_dir, 'history_csvlog.csv'), separator=',', append=True),
+             series]
+    model.compile(lr=learning_rate)
+    model.fit(features, targets, batch_size=batch_size, epochs=num_epochs, callbacks=hooks, validation_data=held_out,
+              validation_split=0.0 if held_out is not None else valid_split, verbose=2 if verbose else 0,
+              random_state=random_state)
+
+    # back to the lowest-val_loss checkpoint; its epoch is the first minimum of the series
+    model.load_weights(best_path)
+    best = int(np.argmin(series.valid_loss))
+
+    train_metrics = _series_metrics((series.train_loss, series.train_acc), best)
+    on_train = compute_metrics(targets, model.predict(features), num_classes=num_classes)
+    train_metrics['class_accuracy'] = on_train['class_accuracy']
+    train_metrics['average_class_accuracy'] = on_train['average_class_accuracy']
+    valid_metrics = _series_metrics((series.valid_loss, series.valid_acc), best)
+    if held_out is not None:
+        valid_metrics.update(compute_metrics(held_out[1], model.predict(held_out[0]), num_classes=num_classes))
+    test_metrics = {}
+    if test_data:
+        per_file = _file_predictions(model.predict(test_data['features']), test_data['file_idxs'])
+        test_metrics = compute_metrics(test_data['labels'], per_file, num_classes=num_classes)
+    return model, train_metrics, valid_metrics, test_metrics
+
+
+def train_param_search(train_data, valid_data, test_data, model_dir, train_func, search_space, valid_ratio=0.15,
+                       train_with_valid=True, **kwargs):
+    """classifier/train.py:394-492 on the validation-fold path: train_func once per point of the grid (the product of the
+    search_space values, in key order), keep the point with the best validation accuracy (the first one on ties), then either
+    retrain on train + valid shuffled together with no validation data (train_with_valid) or keep that run.  Without a
+    validation fold the reference splits with sklearn's StratifiedShuffleSplit, which is not built."""
+    if not valid_data:
+        raise ValueError(NO_SSS)
+    names = list(search_space)
+    runs = []                       # (point, model, train metrics, valid metrics, test metrics)
+    for point in product(*(search_space[n] for n in names)):
+        LOGGER.info('Search point %s', dict(zip(names, point)))
+        kwargs.update(zip(names, point))
+        runs.append((point,) + tuple(train_func(train_data, valid_data, test_data, model_dir, **kwargs)))
+    accuracies = [run[3]['accuracy'] for run in runs]
+    chosen = runs[int(np.argmax(accuracies))]
+    point = chosen[0]
+    LOGGER.info('Chosen %s (validation accuracy %s)', dict(zip(names, point)), chosen[3]['accuracy'])
+    kwargs.update(zip(names, point))
+
+    if train_with_valid:
+        merged_labels = np.concatenate((train_data['labels'], valid_data['labels']))
+        mix = np.random.permutation(merged_labels.size)
+        merged = {'features': np.vstack((train_data['features'], valid_data['features']))[mix], 'labels': merged_labels[mix]}
+        model, train_metrics, _, test_metrics = train_func(merged, None, test_data, model_dir, **kwargs)
+    else:
+        model, train_metrics, test_metrics = chosen[1], dict(chosen[2]), chosen[4]
+
+    search_record = {'search_params': names, 'search_params_best_values': point}
+    train_metrics.update(search_record, search={run[0]: run[2] for run in runs})
+    valid_metrics = dict(chosen[3])
+    valid_metrics.update(search_record, search={run[0]: run[3] for run in runs})
+    return model, train_metrics, valid_metrics, test_metrics
+
+
+def _dataset_of(features_dir):
+    """'.../features/us8k/l3/...' -> ('us8k', 'us8k/l3/...'): the path after the last 'features/' and its first part"""
+    at = features_dir.rindex('features')
+    desc = features_dir[at + len('features/'):]
+    return desc.split('/')[0], desc
+
+
+def _dump(path, obj):
+    with open(path, 'wb') as fh:
+        pk.dump(obj, fh, protocol=pk.HIGHEST_PROTOCOL)
+
+
+def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='framewise', train_batch_size=64, patience=20,
+          random_state=20171021, parameter_search=False, parameter_search_valid_fold=True, parameter_search_valid_ratio=0.15,
+          parameter_search_train_with_valid=False, gsheet_id=None, google_dev_app_name=None, verbose=False, non_overlap=False,
+          non_overlap_chunk_size=10, use_min_max=False, **model_args):
+    """classifier/train.py:495-709 for model_type='mlp': one cross-validation fold (fold_num is 1-based) of the features under
+    `features_dir` (its path names the dataset after 'features/'), written to
+    <output_dir>/classifier/<features desc>/<mode>/<overlap>/<min-max>/mlp/fold<N>/<timestamp>/: config.json,
+    min_max_scaler.pkl, stdizer.pkl, model.h5, history_checkpoint.pkl, history_csvlog.csv, results.pkl.
+    -> that directory."""
+    if model_type != 'mlp':
+        raise ValueError(ONLY_MLP.format(model_type))
+    if parameter_search and not parameter_search_valid_fold:
+        raise ValueError(NO_SSS)
+    if gsheet_id:
+        LOGGER.warning('Google Sheets logging is not built; gsheet_id ignored')
+    dataset, desc = _dataset_of(features_dir)
+    if dataset not in DATASET_NUM_CLASSES:
+        raise ValueError('the features directory must name a dataset right after "features/" (one of {})'.format(
+            ', '.join(sorted(DATASET_NUM_CLASSES))))
+
+    variant = [feature_mode, 'non-overlap' if non_overlap else 'overlap', 'min-max' if use_min_max else 'no-min-max',
+               model_type]
+    model_id = os.path.join(desc, *variant)
+    stamp = datetime.datetime.now().strftime('%Y%m%d%H%M%S')
+    model_dir = os.path.join(output_dir, 'classifier', model_id, 'fold%d' % fold_num, stamp)
+    os.makedirs(model_dir, exist_ok=True)
+
+    # the run's settings under the reference's config.json keys (no git metadata: git_commit is None)
+    settings = dict(username=getpass.getuser(), features_dir=features_dir, output_dir=output_dir, model_dir=model_dir,
+                    model_id=model_id, fold_num=fold_num, parameter_search=parameter_search,
+                    parameter_search_valid_fold=parameter_search_valid_fold,
+                    parameter_search_valid_ratio=parameter_search_valid_ratio,
+                    parameter_search_train_with_valid=parameter_search_train_with_valid, model_type=model_type,
+                    feature_mode=feature_mode, train_batch_size=train_batch_size, patience=patience, non_overlap=non_overlap,
+                    non_overlap_chunk_size=non_overlap_chunk_size, random_state=random_state, verbose=verbose,
+                    git_commit=None, gsheet_id=gsheet_id, google_dev_app_name=google_dev_app_name)
+    settings.update(model_args)
+    with open(os.path.join(model_dir, 'config.json'), 'w') as fh:
+        json.dump(settings, fh)
+
+    with_valid_fold = parameter_search_valid_fold or not parameter_search
+    LOGGER.info('Fold %d of %s: loading and preprocessing', fold_num, dataset)
+    splits = get_split(features_dir, fold_num - 1, dataset, valid=with_valid_fold)
+    scalers = preprocess_split_data(*splits, feature_mode=feature_mode, non_overlap=non_overlap,
+                                    non_overlap_chunk_size=int(non_overlap_chunk_size), use_min_max=use_min_max)
+    for name, scaler in zip(('min_max_scaler.pkl', 'stdizer.pkl'), scalers):
+        _dump(os.path.join(model_dir, name), scaler)
+
+    common = dict(batch_size=train_batch_size, patience=patience, random_state=random_state,
+                  num_classes=DATASET_NUM_CLASSES[dataset], verbose=verbose)
+    if parameter_search:
+        grid = {'learning_rate': [1e-5, 1e-4, 1e-3], 'weight_decay': [1e-5, 1e-4, 1e-3]}
+        outcome = train_param_search(*splits, model_dir, train_func=train_mlp, search_space=grid,
+                                     valid_ratio=parameter_search_valid_ratio,
+                                     train_with_valid=parameter_search_train_with_valid, **dict(common, **model_args))
+    else:
+        outcome = train_mlp(*splits, model_dir, **dict(common, **model_args))
+    _, train_metrics, valid_metrics, test_metrics = outcome
+    _dump(os.path.join(model_dir, 'results.pkl'), {'train': train_metrics, 'valid': valid_metrics, 'test': test_metrics})
+    LOGGER.info('Fold %d done: results in %s', fold_num, model_dir)
+    return model_dir

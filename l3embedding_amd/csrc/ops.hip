@@ -11,6 +11,7 @@
 #include "../../include/l3hip.h"
 #include "kernels.h"
 #include "knobs.h"
+#include "mlp.h"
 
 namespace {
 using namespace l3;
@@ -519,3 +520,165 @@ int l3_op_frontend(int device, int model_type, const float* audio, int n, int db
 }
 
 }  // extern "C"
+
+// ---- MLP classifier operators (mlp.hip; classifier/train.py:230-257) ---------------------------------------------------------
+namespace {
+int mlp_op_check(const char* name, int device, bool ptrs_ok, int rows, int K, int N, const int32_t* idx, int64_t n_x) {
+    if (!ptrs_ok || rows <= 0 || K <= 0 || N <= 0 || n_x < 0) {
+        set_op_error(std::string(name) + ": NULL pointer or non-positive size");
+        return L3_EINVAL;
+    }
+    if (!idx && n_x < rows) {
+        set_op_error(std::string(name) + ": fewer rows in x than `rows`");
+        return L3_EINVAL;
+    }
+    for (int i = 0; idx && i < rows; ++i)
+        if (idx[i] < 0 || idx[i] >= n_x) {
+            set_op_error(std::string(name) + ": idx[" + std::to_string(i) + "] outside [0, n_x)");
+            return L3_EINVAL;
+        }
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= device || device < 0) {
+        set_op_error(std::string(name) + ": HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)");
+        return L3_EHIP;
+    }
+    return L3_OK;
+}
+}  // namespace
+
+extern "C" int l3_op_mlp_dense_fwd(int device, const float* x, int64_t n_x, const int32_t* idx, int rows, int K, int N, const float* w,
+                                   const float* b, int relu, float* y) {
+    const int rc = mlp_op_check("l3_op_mlp_dense_fwd", device, x && w && b && y, rows, K, N, idx, n_x);
+    if (rc != L3_OK) return rc;
+    Scope sc(device);
+    const float* dx = sc.put(x, (size_t)n_x * K);
+    const int* di = idx ? sc.put(idx, rows) : nullptr;
+    const float* dw = sc.put(w, (size_t)K * N);
+    const float* db = sc.put(b, N);
+    float* dy = sc.alloc<float>((size_t)rows * N);
+    float* part = sc.alloc<float>(MLP_PART_FLOATS);
+    int* ctr = sc.alloc<int>(MLP_FWD_COUNTERS);
+    if (!sc.ok || hipMemset(ctr, 0, MLP_FWD_COUNTERS * sizeof(int)) != hipSuccess) return L3_ENOMEM;
+    mlp_dense_fwd(dx, di, K, dw, db, dy, rows, K, N, relu, part, ctr, sc.s);
+    sc.get(y, dy, (size_t)rows * N);
+    return sc.status();
+}
+
+extern "C" int l3_op_mlp_dense_bwd_x(int device, const float* dy, const float* w, const float* h, int rows, int K, int N, float* dx) {
+    const int rc = mlp_op_check("l3_op_mlp_dense_bwd_x", device, dy && w && dx, rows, K, N, nullptr, rows);
+    if (rc != L3_OK) return rc;
+    Scope sc(device);
+    const float* ddy = sc.put(dy, (size_t)rows * N);
+    const float* dw = sc.put(w, (size_t)K * N);
+    const float* dh = h ? sc.put(h, (size_t)rows * K) : nullptr;
+    float* ddx = sc.alloc<float>((size_t)rows * K);
+    if (!sc.ok) return L3_ENOMEM;
+    mlp_dense_bwd_x(ddy, dw, dh, ddx, rows, K, N, sc.s);
+    sc.get(dx, ddx, (size_t)rows * K);
+    return sc.status();
+}
+
+namespace {
+int mlp_wgrad_op(int device, const float* x, int64_t n_x, const int32_t* idx, int rows, int K, int N, const float* dy, float* dw,
+                 float* db, float* w, float* b, float* mw, float* vw, float* mb, float* vb, float wd, float lr_t, float* w2_out) {
+    const bool adam = w != nullptr;
+    const char* name = adam ? "l3_op_mlp_wgrad_adam" : "l3_op_mlp_wgrad";
+    const bool ptrs = x && dy && (adam ? (b && mw && vw && mb && vb) : (dw && db));
+    const int rc = mlp_op_check(name, device, ptrs, rows, K, N, idx, n_x);
+    if (rc != L3_OK) return rc;
+    Scope sc(device);
+    MlpWgrad a{};
+    a.nl = 1, a.rows = rows, a.adam = adam ? 1 : 0;
+    a.l2x2 = 2.f * wd, a.lr_t = lr_t, a.b1 = 0.9f, a.b2 = 0.999f, a.eps = 1e-8f, a.wd = wd;
+    MlpWgLayer& L = a.L[0];
+    L.x = sc.put(x, (size_t)n_x * K), L.idx = idx ? sc.put(idx, rows) : nullptr, L.ldx = K;
+    L.dy = sc.put(dy, (size_t)rows * N), L.K = K, L.N = N;
+    const size_t nw = (size_t)K * N;
+    if (adam) {
+        L.w = sc.put(w, nw), L.mw = sc.put(mw, nw), L.vw = sc.put(vw, nw);
+        L.b = sc.put(b, N), L.mb = sc.put(mb, N), L.vb = sc.put(vb, N);
+    } else {
+        L.dw = sc.alloc<float>(nw), L.db = sc.alloc<float>(N);
+    }
+    float* w2part = sc.alloc<float>(mlp_wgrad_tiles(a));
+    int* ctr = sc.alloc<int>(1);
+    a.w2out = sc.alloc<float>(1);
+    if (!sc.ok || hipMemset(ctr, 0, sizeof(int)) != hipSuccess) return L3_ENOMEM;
+    mlp_wgrad(a, w2part, ctr, sc.s);
+    if (adam) {
+        sc.get(w, L.w, nw), sc.get(mw, L.mw, nw), sc.get(vw, L.vw, nw);
+        sc.get(b, L.b, N), sc.get(mb, L.mb, N), sc.get(vb, L.vb, N);
+        if (w2_out) sc.get(w2_out, a.w2out, 1);
+    } else {
+        sc.get(dw, L.dw, nw), sc.get(db, L.db, N);
+    }
+    return sc.status();
+}
+}  // namespace
+
+extern "C" int l3_op_mlp_wgrad(int device, const float* x, int64_t n_x, const int32_t* idx, int rows, int K, int N, const float* dy,
+                               float* dw, float* db) {
+    if (!dw || !db) {
+        set_op_error("l3_op_mlp_wgrad: NULL output");
+        return L3_EINVAL;
+    }
+    return mlp_wgrad_op(device, x, n_x, idx, rows, K, N, dy, dw, db, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f,
+                        nullptr);
+}
+
+extern "C" int l3_op_mlp_wgrad_adam(int device, const float* x, int64_t n_x, const int32_t* idx, int rows, int K, int N,
+                                    const float* dy, float* w, float* b, float* mw, float* vw, float* mb, float* vb,
+                                    float weight_decay, float lr_t, float* w2_out) {
+    if (!w) {
+        set_op_error("l3_op_mlp_wgrad_adam: NULL w");
+        return L3_EINVAL;
+    }
+    return mlp_wgrad_op(device, x, n_x, idx, rows, K, N, dy, nullptr, nullptr, w, b, mw, vw, mb, vb, weight_decay, lr_t, w2_out);
+}
+
+extern "C" int l3_op_mlp_softmax_ce(int device, const float* z, const int32_t* labels, int rows, int C, float gscale, float* probs,
+                                    float* dz, float* ce, float* correct) {
+    int rc = mlp_op_check("l3_op_mlp_softmax_ce", device, z && labels, rows, 1, C, nullptr, rows);
+    if (rc == L3_OK && (C < 2 || C > MLP_MAX_CLASSES)) {
+        set_op_error("l3_op_mlp_softmax_ce: class count must be in [2, 64]");
+        rc = L3_EINVAL;
+    }
+    for (int i = 0; rc == L3_OK && i < rows; ++i)
+        if (labels[i] < 0 || labels[i] >= C) {
+            set_op_error("l3_op_mlp_softmax_ce: labels[" + std::to_string(i) + "] outside [0, C)");
+            rc = L3_EINVAL;
+        }
+    if (rc != L3_OK) return rc;
+    Scope sc(device);
+    const size_t n = (size_t)rows * C;
+    const float* dzin = sc.put(z, n);
+    const int* dl = sc.put(labels, rows);
+    float* dp = probs ? sc.alloc<float>(n) : nullptr;
+    float* ddz = dz ? sc.alloc<float>(n) : nullptr;
+    float* dce = ce ? sc.alloc<float>(rows) : nullptr;
+    float* dco = correct ? sc.alloc<float>(rows) : nullptr;
+    if (!sc.ok) return L3_ENOMEM;
+    mlp_softmax_ce(dzin, dl, nullptr, rows, C, gscale, dp, ddz, dce, dco, sc.s);
+    if (probs) sc.get(probs, dp, n);
+    if (dz) sc.get(dz, ddz, n);
+    if (ce) sc.get(ce, dce, rows);
+    if (correct) sc.get(correct, dco, rows);
+    return sc.status();
+}
+
+extern "C" int l3_op_adam(int device, float* p, const float* g, float* m, float* v, int64_t n, int64_t n_l2, float l2x2, float lr_t) {
+    const int rc = mlp_op_check("l3_op_adam", device, p && g && m && v && n_l2 >= 0 && n_l2 <= n, 1, 1, 1, nullptr, n > 0 ? 1 : 0);
+    if (rc != L3_OK || n <= 0) {
+        if (rc == L3_OK) set_op_error("l3_op_adam: n <= 0");
+        return rc != L3_OK ? rc : L3_EINVAL;
+    }
+    Scope sc(device);
+    float* dp = sc.put(p, n);
+    const float* dg = sc.put(g, n);
+    float* dm = sc.put(m, n);
+    float* dv = sc.put(v, n);
+    if (!sc.ok) return L3_ENOMEM;
+    adam_step(dp, dg, dm, dv, n, n_l2, l2x2, lr_t, 0.9f, 0.999f, 1e-8f, 1.f, sc.s);
+    sc.get(p, dp, n), sc.get(m, dm, n), sc.get(v, dv, n);
+    return sc.status();
+}

@@ -208,3 +208,48 @@ def load_weights(path, table, model_type, wrapper=False, report=None):
                 raise ValueError('shape mismatch for %s: file %s has %s, model expects %s' % (p, w, arr.shape, shapes[p]))
             out[p] = arr
     return out
+
+
+# ---- flat Dense models (the downstream MLP classifier, classifier/train.py:230-257) ----------------------------------------------
+def save_dense_weights(path, weights, input_name='input_1'):
+    """keras-2.0.9 `save_weights` of a Sequential-like stack of Dense layers: groups input_1 (no weights), dense_1 .. dense_n,
+    each holding dense_i/kernel:0 (in, out) and dense_i/bias:0; `weights` in get_weights() order (kernel, bias per layer)."""
+    if len(weights) % 2:
+        raise ValueError('expected kernel / bias pairs, got %d arrays' % len(weights))
+    root = h5lite.Group()
+    names = [input_name] + ['dense_%d' % (i + 1) for i in range(len(weights) // 2)]
+    root.attrs['layer_names'] = np.array([n.encode('utf8') for n in names])
+    root.attrs['backend'] = b'tensorflow'
+    root.attrs['keras_version'] = b'2.0.9'
+    g = root.create_group(input_name)
+    g.attrs['weight_names'] = np.zeros((0,), np.float64)
+    for i, name in enumerate(names[1:]):
+        g = root.create_group(name)
+        wnames = ['%s/kernel:0' % name, '%s/bias:0' % name]
+        g.attrs['weight_names'] = np.array([w.encode('utf8') for w in wnames])
+        for w, arr in zip(wnames, weights[2 * i:2 * i + 2]):
+            g.create_dataset(w, np.asarray(arr, dtype=np.float32))
+    h5lite.write_file(path, root)
+
+
+def load_dense_weights(path):
+    """-> [kernel, bias, ...] of every layer group with weights, in the file's layer order (keras `load_weights` by topology)"""
+    root = h5lite.read_file(path)
+    if 'layer_names' not in root.attrs:
+        raise ValueError('%s is not a keras weight file (no layer_names attribute)' % path)
+    out = []
+    for ln in np.atleast_1d(root.attrs['layer_names']):
+        ln = ln.decode('utf8') if isinstance(ln, bytes) else str(ln)
+        g = root.children.get(ln)
+        if g is None:
+            raise ValueError('layer group "%s" missing in %s' % (ln, path))
+        wn = g.attrs.get('weight_names')
+        if wn is None or np.asarray(wn).dtype.kind != 'S':
+            continue
+        names = [n.decode('utf8') for n in np.atleast_1d(wn)]
+        by_kind = {n.split('/')[-1].split(':')[0]: n for n in names}
+        for kind in ('kernel', 'bias'):
+            if kind not in by_kind:
+                raise ValueError('layer "%s" of %s has no %s' % (ln, path, kind))
+            out.append(np.asarray(g[by_kind[kind]], dtype=np.float32))
+    return out

@@ -1,0 +1,234 @@
+"""Fold reading and preprocessing of the downstream sound-classification sets (UrbanSound8K, ESC-50, DCASE 2013): the
+reference's data/usc/folds.py:16-112 and data/usc/features.py:52-150,243-253, restated without scipy and sklearn.
+
+Quirks kept on purpose:
+  * feature files are read in `os.listdir` order, and `filenames` lists every file of the fold, skipped ones included;
+  * the US8K augmented-file skip ('_' in the name) applies to the valid and test folds only: get_train_folds reads with
+    augment=True;
+  * the summary statistics are min, max, median, mean, var, skew, excess kurtosis (scipy.stats defaults, bias=True);
+  * the scalers use sklearn's arithmetic: population variance, and a zero variance / zero range scales by 1;
+  * the training rows are shuffled (np.random.permutation, the global NumPy state) after standardisation.
+"""
+import os
+
+import numpy as np
+
+DATASET_NUM_FOLDS = {'us8k': 10, 'esc50': 5, 'dcase2013': 2}
+
+
+def load_feature_file(feature_filepath):
+    """One feature file -> (X, y): X the frames (or one vector), y an int when the file holds a single label for the clip,
+    else the array as stored (data/usc/folds.py:16-21)."""
+    with np.load(feature_filepath) as npz:
+        frames, label = npz['X'], npz['y']
+    if isinstance(label, np.ndarray) and label.ndim == 0:
+        label = int(label)
+    return frames, label
+
+
+def _is_augmented_us8k(fold_dir, name):
+    # US8K's augmented copies carry '_' in their file names (data/usc/folds.py:35-37); only the training folds read them
+    return 'us8k' in fold_dir and '_' in name
+
+
+def _row_ranges(counts):
+    """[[start, end), ...] of consecutive blocks of the given sizes"""
+    ends = np.cumsum(np.asarray(counts, dtype=np.int64))
+    return np.stack((ends - np.asarray(counts, dtype=np.int64), ends), axis=1)
+
+
+def get_fold(feature_dir, fold_idx, augment=False):
+    """Fold `fold_idx` (0-based, directory fold<fold_idx + 1>) -> {'features', 'labels', 'file_idxs', 'filenames'}
+    (data/usc/folds.py:24-62).  Files in os.listdir order; 'filenames' lists the whole directory, skipped files included."""
+    fold_dir = os.path.join(feature_dir, 'fold%d' % (fold_idx + 1))
+    names = os.listdir(fold_dir)
+    wanted = [n for n in names if augment or not _is_augmented_us8k(fold_dir, n)]
+    loaded = [load_feature_file(os.path.join(fold_dir, n)) for n in wanted]
+    frames = [x for x, _ in loaded]
+    labels = [lab for _, lab in loaded]
+    per_file = isinstance(labels[0], int) or np.ndim(labels[0]) == 0
+    return {
+        'features': np.vstack(frames),
+        'labels': np.array(labels) if per_file else np.concatenate(labels),
+        'file_idxs': _row_ranges([x.shape[0] if x.ndim > 1 else 1 for x in frames]),
+        'filenames': names,
+    }
+
+
+def get_valid_fold_idx(test_fold_idx, num_folds):
+    """the fold before the test fold, wrapping around (data/usc/folds.py:78-79)"""
+    return (test_fold_idx + num_folds - 1) % num_folds
+
+
+def get_train_folds(feature_dir, test_fold_idx, num_folds, valid=True):
+    """Every fold but the test fold (and the validation fold when `valid`), augmented files included, stacked; each fold's
+    file_idxs continue after the rows of the folds before it (data/usc/folds.py:82-112)."""
+    held_out = {test_fold_idx}
+    if valid:
+        held_out.add(get_valid_fold_idx(test_fold_idx, num_folds))
+    folds = [get_fold(feature_dir, i, augment=True) for i in range(num_folds) if i not in held_out]
+    if not folds:
+        # dcase2013 has two folds: a test and a validation fold leave none (the reference fails inside np.vstack)
+        raise ValueError('No training fold left: {} folds, test fold {}, validation fold held out: {}; use the parameter '
+                         'search without a validation fold'.format(num_folds, test_fold_idx + 1, valid))
+    first_row = np.cumsum([0] + [f['features'].shape[0] for f in folds[:-1]])
+    return {
+        'features': np.vstack([f['features'] for f in folds]),
+        'labels': np.concatenate([f['labels'] for f in folds]),
+        'file_idxs': np.vstack([f['file_idxs'] + off for f, off in zip(folds, first_row)]),
+        'filenames': [name for f in folds for name in f['filenames']],
+    }
+
+
+def get_split(feature_dir, test_fold_idx, dataset_name, valid=True):
+    """-> (train, valid or None, test) for one cross-validation fold (data/usc/folds.py:65-75)"""
+    num_folds = DATASET_NUM_FOLDS.get(dataset_name)
+    if num_folds is None:
+        raise ValueError('unknown dataset {!r}: one of {}'.format(dataset_name, ', '.join(sorted(DATASET_NUM_FOLDS))))
+    train = get_train_folds(feature_dir, test_fold_idx, num_folds, valid=valid)
+    held = get_fold(feature_dir, get_valid_fold_idx(test_fold_idx, num_folds)) if valid else None
+    return train, held, get_fold(feature_dir, test_fold_idx)
+
+
+# ---- scalers with sklearn.preprocessing's arithmetic ----------------------------------------------------------------------------
+def _handle_zeros(scale):
+    scale = np.array(scale, copy=True)
+    scale[scale == 0.0] = 1.0
+    return scale
+
+
+class StandardScaler(object):
+    """sklearn.preprocessing.StandardScaler(): mean_, var_ (population), scale_ = sqrt(var_) with 0 -> 1."""
+
+    def fit(self, X):
+        X = np.asarray(X)
+        self.mean_ = X.mean(axis=0, dtype=np.float64)
+        self.var_ = X.var(axis=0, dtype=np.float64)
+        self.scale_ = _handle_zeros(np.sqrt(self.var_))
+        self.n_samples_seen_ = X.shape[0]
+        return self
+
+    def transform(self, X):
+        X = np.array(X, dtype=np.result_type(np.asarray(X).dtype, np.float32), copy=True)
+        X -= self.mean_          # in place, in the input's float type, as sklearn does
+        X /= self.scale_
+        return X
+
+    def fit_transform(self, X):
+        return self.fit(X).transform(X)
+
+
+class MinMaxScaler(object):
+    """sklearn.preprocessing.MinMaxScaler(feature_range=(0, 1)): X * scale_ + min_, a zero range scaling by 1."""
+
+    def __init__(self, feature_range=(0, 1)):
+        self.feature_range = feature_range
+
+    def fit(self, X):
+        X = np.asarray(X)
+        self.data_min_ = np.min(X, axis=0)
+        self.data_max_ = np.max(X, axis=0)
+        self.data_range_ = self.data_max_ - self.data_min_
+        lo, hi = self.feature_range
+        self.scale_ = (hi - lo) / _handle_zeros(self.data_range_)
+        self.min_ = lo - self.data_min_ * self.scale_
+        return self
+
+    def transform(self, X):
+        X = np.array(X, copy=True)
+        X *= self.scale_
+        X += self.min_
+        return X
+
+    def fit_transform(self, X):
+        return self.fit(X).transform(X)
+
+
+# ---- data/usc/features.py ---------------------------------------------------------------------------------------------------
+def sample_non_overlap_file(X, chunk_size=10):
+    """every chunk_size-th frame, starting with the first (data/usc/features.py:52-57)"""
+    return np.asarray(X)[::chunk_size]
+
+
+def remove_data_overlap(data, chunk_size=10):
+    """In place: keep every chunk_size-th frame of each file and renumber file_idxs (data/usc/features.py:60-73)."""
+    kept = [sample_non_overlap_file(data['features'][s:e], chunk_size) for s, e in data['file_idxs']]
+    data['file_idxs'] = _row_ranges([len(k) for k in kept])
+    data['features'] = np.vstack(kept)
+
+
+def compute_stats_features(embeddings):
+    """min, max, median, mean, var, skew, excess kurtosis over axis 0 (scipy.stats.skew / kurtosis with bias=True)"""
+    x = np.asarray(embeddings)
+    mean = np.mean(x, axis=0)
+    var = np.var(x, axis=0)
+    d = x.astype(np.float64) - x.mean(axis=0, dtype=np.float64)
+    m2 = (d ** 2).mean(axis=0)
+    m3 = (d ** 3).mean(axis=0)
+    m4 = (d ** 4).mean(axis=0)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        # a constant column (m2 == 0 up to rounding): skew 0 and kurtosis -3, as the scipy of the reference's era returned
+        # (scipy >= 1.9 returns NaN there)
+        zero = m2 <= (np.finfo(np.float64).resolution * x.mean(axis=0, dtype=np.float64)) ** 2
+        skew = np.where(zero, 0.0, m3 / m2 ** 1.5)
+        kurt = np.where(zero, -3.0, m4 / m2 ** 2 - 3.0)
+    return np.concatenate((np.min(x, axis=0), np.max(x, axis=0), np.median(x, axis=0), mean, var,
+                           skew.astype(mean.dtype), kurt.astype(mean.dtype)))
+
+
+def framewise_to_stats(data):
+    """In place: one row of summary statistics per file, file i owning row i (data/usc/features.py:76-85)."""
+    rows = [compute_stats_features(data['features'][s:e]) for s, e in data['file_idxs']]
+    data['features'] = np.vstack(rows)
+    data['file_idxs'] = _row_ranges(np.ones(len(rows), dtype=np.int64))
+
+
+def expand_framewise_labels(data):
+    """In place: each file's label repeated once per frame of the file (data/usc/features.py:88-94)."""
+    spans = [e - s for s, e in data['file_idxs']]
+    n = min(len(spans), len(data['labels']))
+    data['labels'] = np.repeat(np.asarray(data['labels'])[:n], spans[:n], axis=0)
+
+
+def _present(*splits):
+    return [d for d in splits if d]
+
+
+def preprocess_split_data(train_data, valid_data, test_data, feature_mode='framewise', non_overlap=False,
+                          non_overlap_chunk_size=10, use_min_max=False):
+    """data/usc/features.py:97-150, in place on the splits (valid_data may be None) -> (min-max scaler, standardiser).
+
+    Order: thin overlapping frames; min-max scaling (fitted on train, when asked); per-frame labels or per-file statistics;
+    standardisation fitted on train; then one np.random.permutation of the training rows (the global NumPy state), after which
+    train_data['file_idxs'] is a list holding, per file, the new positions of its rows."""
+    if feature_mode not in ('framewise', 'stats'):
+        raise ValueError("feature_mode must be 'framewise' or 'stats', not {!r}".format(feature_mode))
+    everything = _present(train_data, valid_data, test_data)
+    if non_overlap:
+        for d in everything:
+            remove_data_overlap(d, chunk_size=non_overlap_chunk_size)
+
+    unit_range = MinMaxScaler()
+    if use_min_max:
+        unit_range.fit(train_data['features'])
+        for d in everything:
+            d['features'] = unit_range.transform(d['features'])
+
+    if feature_mode == 'stats':
+        for d in everything:
+            framewise_to_stats(d)
+    else:
+        for d in _present(train_data, valid_data):       # the test split keeps one label per file
+            expand_framewise_labels(d)
+
+    stdizer = StandardScaler().fit(train_data['features'])
+    for d in everything:
+        d['features'] = stdizer.transform(d['features'])
+
+    order = np.random.permutation(len(train_data['labels']))
+    new_position = np.empty_like(order)
+    new_position[order] = np.arange(order.size)
+    train_data['features'] = train_data['features'][order]
+    train_data['labels'] = train_data['labels'][order]
+    train_data['file_idxs'] = [new_position[s:e] for s, e in train_data['file_idxs']]
+    return unit_range, stdizer
