@@ -241,6 +241,25 @@ int64_t l3_embed_dim(const l3_engine *e, int vision, int pool_h, int pool_w);
  * lo < 0, lo > hi or hi > n_samples, a bad pooling size, or a model without an audio embedding layer (tiny_L3). */
 int l3_embed_audio_frames(l3_engine *e, const float *samples, int64_t n_samples, const int64_t *table,
                           int64_t n_frames, int pool_h, int pool_w, float *out);
+/* load_audio's resampling + get_l3_frames_uniform -- data/usc/features.py:18-28 (resampy.resample(data, sr_orig, sr), filter
+ * 'kaiser_best') and :256-306: l3_embed_audio_frames on samples the device produces from native-rate clips.
+ * native: n_native floats, the clips at their own rates back to back, uploaded once.  clips: n_clips rows of 6 int64
+ * {x_off, L, sr_orig, t0, n_out, y_off}: outputs [t0, t0 + n_out) of the 48 kHz version of the L samples at native[x_off ..)
+ * go to samples[y_off ..) of a device buffer of n_samples floats, which `table` (n_frames x {start, lo, hi}, as above) frames.
+ * One launch of the resample kernel (csrc/resample.hip) covers every row, mixed rates included; a row with sr_orig == 48000
+ * is copied, not filtered (the reference skips resampy then).  The engine keeps the filter tables between calls and uploads
+ * them again only for a new window scale or another half_window.  Output t of a clip sits at the exact time t * sr_orig / 48000
+ * (resampy accumulates the time in an f64 register: DESIGN.md section 8).  half_window: the filter's n_window-entry half window
+ * (resampy's interp_win, e.g. l3embedding_amd/resample.py kaiser_best), num_table entries per zero crossing; the library scales
+ * it by the ratio when downsampling and takes its differences, as resampy does.  Samples no row writes are zero.
+ * L3_EINVAL (message in l3_last_error) for a NULL pointer, a rate <= 0 or above 2^24, (L + 1) * max(rate) >= 2^62, a
+ * native range outside the upload, an output range past int(L * 48000 / sr_orig) (or an output length < 1, resampy's
+ * ValueError), a destination outside the buffer, a bad frame table, a bad pooling size, or a model without an audio
+ * embedding layer. */
+int l3_embed_audio_clips_resampled(l3_engine *e, const float *native, int64_t n_native, const int64_t *clips,
+                                   int64_t n_clips, const double *half_window, int64_t n_window, int num_table,
+                                   int64_t n_samples, const int64_t *table, int64_t n_frames, int pool_h, int pool_w,
+                                   float *out);
 
 /* Diagnostics / parity taps. */
 int l3_get_activation(l3_engine *e, const char *name, float *dst, int64_t numel); /* e.g. "audio_model/frontend", "vision_model/conv2d_1" */
@@ -317,6 +336,16 @@ int l3_op_frontend(int device, int model_type, const float *audio, int n, int db
 /* The frame gather of l3_embed_audio_frames on its own: frames (n_frames, 48000) from samples + table as above (parity tests). */
 int l3_op_gather_frames(int device, const float *samples, int64_t n_samples, const int64_t *table,
                         int64_t n_frames, float *frames);
+/* resampy.resample(x, sr_orig, sr_new, filter=...)[t0 : t0 + n_out] -- data/usc/features.py:25-26 -- for one clip of n_in
+ * samples, on the device (csrc/resample.hip, exact output times as above).  Always filters, equal rates included, as resampy
+ * does.  L3_EINVAL for rates <= 0, int(n_in * sr_new / sr_orig) < 1, or a range past that length. */
+int l3_op_resample(int device, const float *x, int64_t n_in, int64_t sr_orig, int64_t sr_new, const double *half_window,
+                   int64_t n_window, int num_table, int64_t t0, int64_t n_out, float *y);
+/* The resample launch of l3_embed_audio_clips_resampled on its own: clip rows as there, any sr_new, into y (n_samples floats,
+ * zero where no row writes); copy_equal != 0 copies rows with sr_orig == sr_new. */
+int l3_op_resample_clips(int device, const float *x, int64_t n_in, const int64_t *clips, int64_t n_clips, int64_t sr_new,
+                         const double *half_window, int64_t n_window, int num_table, int64_t n_samples, int copy_equal,
+                         float *y);
 /* keras BatchNormalization batch moments (vision_model.py:124-187, audio_model.py:370-433) from the partial sums the
  * convolution epilogues leave: nblk rows of [sum, sum of squares][c] about pivot[c] over `rows` elements per channel.
  * Runs the engine's second reduction stage on a buffer of exactly nblk rows; L3_EINVAL if it wrote past them. */

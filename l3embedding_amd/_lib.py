@@ -103,6 +103,9 @@ SIGNATURES = {
     'l3_embed_dim': (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     'l3_embed_audio_frames': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                         C.c_void_p]),
+    'l3_embed_audio_clips_resampled': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                 C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                                 C.c_void_p]),
     'l3_get_activation': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     'l3_activation_numel': (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
     'l3_sync': (C.c_int, [C.c_void_p]),
@@ -124,6 +127,10 @@ SIGNATURES = {
     'l3_op_maxpool_bwd': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9),
     'l3_op_frontend': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'l3_op_gather_frames': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_op_resample': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
+                                 C.c_int64, C.c_int64, C.c_void_p]),
+    'l3_op_resample_clips': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                       C.c_int, C.c_int64, C.c_int, C.c_void_p]),
     'l3_op_bn_stats_from_partials': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_float,
                                                C.c_void_p, C.c_void_p]),
     'l3_op_preprocess': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -484,6 +491,27 @@ class Engine(object):
               self.h)
         return out
 
+    def embed_audio_clips_resampled(self, native, clips, half_window, num_table, n_samples, table, pool, out=None):
+        """l3_embed_audio_clips_resampled: native (n,) float32 (clips at their own rates back to back), clips (n_clips, 6) int64
+        {x_off, L, sr_orig, t0, n_out, y_off}, half_window (n_window,) float64 with num_table entries per zero crossing,
+        n_samples the 48 kHz buffer the rows fill, table (n_frames, 3) int64 {start, lo, hi} over it -> (n_frames, D)
+        embeddings, written into `out` when given (C-contiguous float32)."""
+        x = np.ascontiguousarray(native, dtype=np.float32).reshape(-1)
+        c = np.ascontiguousarray(clips, dtype=np.int64).reshape(-1, 6)
+        w = np.ascontiguousarray(half_window, dtype=np.float64).reshape(-1)
+        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 3)
+        d = self.lib.l3_embed_dim(self.h, 0, pool[0], pool[1])
+        if out is None:
+            out = np.empty((t.shape[0], max(d, 0)), np.float32)
+        elif out.dtype != np.float32 or not out.flags['C_CONTIGUOUS'] or out.shape != (t.shape[0], d):
+            raise ValueError('out must be a C-contiguous float32 array of shape %s' % ((t.shape[0], d),))
+        if x.size == 0:
+            x = np.zeros(1, np.float32)[:0]
+        check(self.lib.l3_embed_audio_clips_resampled(self.h, _ptr(x), x.size, _ptr(c), c.shape[0], _ptr(w), w.size,
+                                                      int(num_table), int(n_samples), _ptr(t), t.shape[0], pool[0], pool[1],
+                                                      _ptr(out)), self.h)
+        return out
+
     def embed_vision(self, video, pool=(7, 7)):
         v = _f32(video)
         d = self.lib.l3_embed_dim(self.h, 1, pool[0], pool[1])
@@ -652,6 +680,33 @@ def op_gather_frames(samples, table, device=0):
         s = np.zeros(1, np.float32)[:0]
     out = np.empty((t.shape[0], 48000), np.float32)
     check(lib.l3_op_gather_frames(device, _ptr(s), s.size, _ptr(t), t.shape[0], _ptr(out)))
+    return out
+
+
+def op_resample(x, sr_orig, sr_new, half_window, num_table, t0=0, n_out=None, device=0):
+    """l3_op_resample: outputs [t0, t0 + n_out) of resampy.resample(x, sr_orig, sr_new) with the given half window (float32);
+    n_out defaults to the rest of the output."""
+    lib = load()
+    a = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    w = np.ascontiguousarray(half_window, dtype=np.float64).reshape(-1)
+    if n_out is None:
+        n_out = max(0, int(a.size * (float(sr_new) / sr_orig)) - int(t0)) if sr_orig > 0 else 0
+    out = np.empty(max(int(n_out), 0), np.float32)
+    check(lib.l3_op_resample(device, _ptr(a), a.size, int(sr_orig), int(sr_new), _ptr(w), w.size, int(num_table), int(t0),
+                             int(n_out), _ptr(out)))
+    return out
+
+
+def op_resample_clips(x, clips, sr_new, half_window, num_table, n_samples, copy_equal=False, device=0):
+    """l3_op_resample_clips: one launch over clip rows (n_clips, 6) int64 {x_off, L, sr_orig, t0, n_out, y_off} of x into a
+    buffer of n_samples float32 (zero where no row writes)."""
+    lib = load()
+    a = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    c = np.ascontiguousarray(clips, dtype=np.int64).reshape(-1, 6)
+    w = np.ascontiguousarray(half_window, dtype=np.float64).reshape(-1)
+    out = np.empty(int(n_samples), np.float32)
+    check(lib.l3_op_resample_clips(device, _ptr(a), a.size, _ptr(c), c.shape[0], int(sr_new), _ptr(w), w.size, int(num_table),
+                                   int(n_samples), 1 if copy_equal else 0, _ptr(out)))
     return out
 
 

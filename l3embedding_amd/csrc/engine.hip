@@ -212,6 +212,14 @@ struct l3_engine {
     float* clip_samples = nullptr;
     int64_t* clip_table = nullptr;
     size_t clip_samples_cap = 0, clip_table_cap = 0;
+    // l3_embed_audio_clips_resampled: the native-rate clips, their descriptors, the block table and the filter tables
+    float* rs_native = nullptr;
+    l3::ResampleClip* rs_clips = nullptr;
+    int64_t* rs_blocks = nullptr;
+    double* rs_tabs = nullptr;
+    size_t rs_native_cap = 0, rs_clips_cap = 0, rs_blocks_cap = 0, rs_tabs_cap = 0;
+    l3::ResampleTables rs_tables;               // host tables, kept across calls; rs_tabs holds generation rs_tabs_gen of them
+    uint64_t rs_tabs_gen = ~(uint64_t)0;
     bool last_training = false;
     bool fwd_done = false;
 
@@ -2694,6 +2702,72 @@ int l3_embed_audio_frames(l3_engine* e, const float* samples, int64_t n_samples,
     if ((rc = dev_grow_t(e, &e->clip_table, &e->clip_table_cap, (size_t)n_frames * 3))) return rc;
     if (n_samples > 0)
         HIPCHK(e, hipMemcpyAsync(e->clip_samples, samples, (size_t)n_samples * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->clip_table, table, (size_t)n_frames * 3 * 8, hipMemcpyHostToDevice, e->stream));
+    EmbedSource src;
+    src.samples = e->clip_samples;
+    src.table = e->clip_table;
+    return embed_rows(e, false, src, n_frames, pool_h, pool_w, D, out);
+}
+
+int l3_embed_audio_clips_resampled(l3_engine* e, const float* native, int64_t n_native, const int64_t* clips, int64_t n_clips,
+                                   const double* half_window, int64_t n_window, int num_table, int64_t n_samples,
+                                   const int64_t* table, int64_t n_frames, int pool_h, int pool_w, float* out) {
+    if (!e) return L3_EINVAL;
+    if (!native || !clips || !half_window || !table || !out) {
+        e->err = "l3_embed_audio_clips_resampled: native, clips, half_window, table and out must not be NULL";
+        return L3_EINVAL;
+    }
+    if (n_native < 0 || n_clips < 0 || n_samples < 0 || n_frames < 0) {
+        e->err = "l3_embed_audio_clips_resampled: n_native, n_clips, n_samples and n_frames must be >= 0";
+        return L3_EINVAL;
+    }
+    int64_t D = 0;
+    int rc = embed_check(e, false, pool_h, pool_w, &D);
+    if (rc) return rc;
+    int64_t bad = 0;
+    if (const char* why = resample_clips_error(clips, n_clips, n_native, AUDIO_T, n_window, num_table, n_samples, true, &bad)) {
+        e->err = std::string("l3_embed_audio_clips_resampled: ") + (bad >= 0 ? "clip " + std::to_string(bad) + ": " : std::string()) + why;
+        return L3_EINVAL;
+    }
+    if (const char* why = frame_table_error(table, n_frames, n_samples, &bad)) {
+        e->err = std::string("l3_embed_audio_clips_resampled: frame ") + std::to_string(bad) + ": " + why;
+        return L3_EINVAL;
+    }
+    if (n_frames == 0) return L3_OK;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    l3::ResamplePlan p;
+    // every return below waits for the stream first: the copies enqueued from p and e->rs_tables must have read them
+    struct WaitOnExit {
+        hipStream_t s;
+        ~WaitOnExit() { (void)l3::stream_wait(s); }
+    } wait_on_exit{e->stream};
+    resample_plan(clips, n_clips, AUDIO_T, half_window, n_window, true, &e->rs_tables, &p);
+    const std::vector<double>& tabs = e->rs_tables.tables;
+    const int64_t n_blocks = (int64_t)p.blocks.size() / 2;
+    if ((rc = dev_grow_t(e, &e->rs_native, &e->rs_native_cap, (size_t)(n_native > 0 ? n_native : 1)))) return rc;
+    if ((rc = dev_grow_t(e, &e->rs_clips, &e->rs_clips_cap, p.clips.size() + 1))) return rc;
+    if ((rc = dev_grow_t(e, &e->rs_blocks, &e->rs_blocks_cap, p.blocks.size() + 2))) return rc;
+    if (tabs.size() + 2 > e->rs_tabs_cap) e->rs_tabs_gen = ~(uint64_t)0;          // a new device buffer holds nothing yet
+    if ((rc = dev_grow_t(e, &e->rs_tabs, &e->rs_tabs_cap, tabs.size() + 2))) return rc;
+    if ((rc = dev_grow_t(e, &e->clip_samples, &e->clip_samples_cap, (size_t)(n_samples > 0 ? n_samples : 1)))) return rc;
+    if ((rc = dev_grow_t(e, &e->clip_table, &e->clip_table_cap, (size_t)n_frames * 3))) return rc;
+    if (n_native > 0)
+        HIPCHK(e, hipMemcpyAsync(e->rs_native, native, (size_t)n_native * 4, hipMemcpyHostToDevice, e->stream));
+    if (!p.clips.empty())
+        HIPCHK(e, hipMemcpyAsync(e->rs_clips, p.clips.data(), p.clips.size() * sizeof(l3::ResampleClip), hipMemcpyHostToDevice,
+                                 e->stream));
+    if (n_blocks > 0)
+        HIPCHK(e, hipMemcpyAsync(e->rs_blocks, p.blocks.data(), p.blocks.size() * 8, hipMemcpyHostToDevice, e->stream));
+    if (!tabs.empty() && e->rs_tabs_gen != e->rs_tables.generation) {         // only a new window scale or window uploads
+        e->rs_tabs_gen = ~(uint64_t)0;
+        HIPCHK(e, hipMemcpyAsync(e->rs_tabs, tabs.data(), tabs.size() * 8, hipMemcpyHostToDevice, e->stream));
+        e->rs_tabs_gen = e->rs_tables.generation;
+    }
+    // samples no clip row writes read as zeros (the frame table only reads inside the clips' ranges)
+    if (n_samples > 0) HIPCHK(e, hipMemsetAsync(e->clip_samples, 0, (size_t)n_samples * 4, e->stream));
+    if (n_blocks > 0)
+        resample_launch(e->rs_native, e->rs_clips, e->rs_blocks, n_blocks, e->rs_tabs, (int)n_window, num_table, e->clip_samples,
+                        e->stream);
     HIPCHK(e, hipMemcpyAsync(e->clip_table, table, (size_t)n_frames * 3 * 8, hipMemcpyHostToDevice, e->stream));
     EmbedSource src;
     src.samples = e->clip_samples;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 namespace l3 {
 
@@ -290,6 +291,35 @@ inline const char* frame_table_error(const int64_t* table, int64_t n_frames, int
     }
     return nullptr;
 }
+
+// resampling of whole clips (resample.hip; resampy.resample, data/usc/features.py:25-26).  A caller's clip row is RESAMPLE_ROW int64
+// {x_off, L, sr_orig, t0, n_out, y_off}: outputs [t0, t0 + n_out) of the L native samples at x[x_off ..) go to y[y_off ..).
+constexpr int RESAMPLE_ROW = 6;
+struct ResampleClip {
+    int64_t x_off, L, sr_o, sr_n, t0, n_out, y_off;
+    int64_t table;          // first (win, delta) pair of the clip's filter table; -1: copy (sr_o == sr_n under copy_equal)
+};
+struct ResamplePlan {
+    std::vector<ResampleClip> clips;
+    std::vector<int64_t> blocks;        // per 256-output block: {clip, first output}
+};
+// The filter tables of one half window, one per window scale met so far: an engine keeps them across calls and uploads them
+// again only when `generation` moved (a new scale, or another window, which drops the old tables).
+struct ResampleTables {
+    std::vector<double> window;         // the half window they were built from
+    std::vector<double> keys;           // window scale of each table: 1 (upsampling) or the ratio
+    std::vector<double> tables;         // interleaved (win, delta), window.size() pairs per key
+    uint64_t generation = 0;
+};
+int64_t resample_out_len(int64_t L, int64_t sr_o, int64_t sr_n);     // int(L * (float(sr_n) / sr_o)), resampy's output length
+// host-side check of the clip rows against an upload of n_native samples and an output buffer of n_samples: nullptr or what is wrong
+// (*bad: the row, -1 for an argument).  copy_equal: rows with sr_orig == sr_new are copied (load_audio skips resampy for them).
+const char* resample_clips_error(const int64_t* clips, int64_t n_clips, int64_t n_native, int64_t sr_new, int64_t n_window,
+                                 int num_table, int64_t n_samples, bool copy_equal, int64_t* bad);
+void resample_plan(const int64_t* clips, int64_t n_clips, int64_t sr_new, const double* half_window, int64_t n_window,
+                   bool copy_equal, ResampleTables* tabs, ResamplePlan* p);
+void resample_launch(const float* x, const ResampleClip* clips, const int64_t* blocks, int64_t n_blocks, const double* tabs,
+                     int nwin, int num_table, float* y, hipStream_t s);
 
 // head: dense + softmax + categorical cross-entropy
 void dense_fwd(const float* x, const float* w, const float* b, float* y, int B, int K, int N, int relu,

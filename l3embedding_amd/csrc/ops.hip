@@ -498,6 +498,50 @@ int l3_op_gather_frames(int device, const float* samples, int64_t n_samples, con
     return sc.status();
 }
 
+static int op_resample(const char* name, int device, const float* x, int64_t n_in, const int64_t* clips, int64_t n_clips,
+                       int64_t sr_new, const double* half_window, int64_t n_window, int num_table, int64_t n_samples, bool copy_equal,
+                       float* y) {
+    if (!x || !clips || !half_window || !y || n_in < 0 || n_clips < 0 || n_samples < 0) {
+        set_op_error(std::string(name) + ": NULL pointer or negative count");
+        return L3_EINVAL;
+    }
+    int64_t bad = 0;
+    if (const char* why = resample_clips_error(clips, n_clips, n_in, sr_new, n_window, num_table, n_samples, copy_equal, &bad)) {
+        set_op_error(std::string(name) + ": " + (bad >= 0 ? "clip " + std::to_string(bad) + ": " : std::string()) + why);
+        return L3_EINVAL;
+    }
+    Scope sc(device);
+    if (!sc.ok) {
+        set_op_error(std::string(name) + ": HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)");
+        return L3_EHIP;
+    }
+    ResamplePlan p;
+    ResampleTables tabs;
+    resample_plan(clips, n_clips, sr_new, half_window, n_window, copy_equal, &tabs, &p);
+    const float* d_x = sc.put(x, (size_t)n_in);
+    const ResampleClip* d_c = sc.put(p.clips.data(), p.clips.size());
+    const int64_t* d_b = sc.put(p.blocks.data(), p.blocks.size());
+    const double* d_t = sc.put(tabs.tables.data(), tabs.tables.size());
+    float* d_y = sc.alloc<float>((size_t)n_samples);
+    if (!sc.ok) return L3_ENOMEM;
+    if (n_samples > 0 && hipMemset(d_y, 0, (size_t)n_samples * 4) != hipSuccess) return L3_EHIP;
+    resample_launch(d_x, d_c, d_b, (int64_t)p.blocks.size() / 2, d_t, (int)n_window, num_table, d_y, sc.s);
+    sc.get(y, d_y, (size_t)n_samples);
+    return sc.status();
+}
+
+int l3_op_resample(int device, const float* x, int64_t n_in, int64_t sr_orig, int64_t sr_new, const double* half_window,
+                   int64_t n_window, int num_table, int64_t t0, int64_t n_out, float* y) {
+    const int64_t row[RESAMPLE_ROW] = {0, n_in, sr_orig, t0, n_out, 0};
+    return op_resample("l3_op_resample", device, x, n_in, row, 1, sr_new, half_window, n_window, num_table, n_out, false, y);
+}
+
+int l3_op_resample_clips(int device, const float* x, int64_t n_in, const int64_t* clips, int64_t n_clips, int64_t sr_new,
+                         const double* half_window, int64_t n_window, int num_table, int64_t n_samples, int copy_equal, float* y) {
+    return op_resample("l3_op_resample_clips", device, x, n_in, clips, n_clips, sr_new, half_window, n_window, num_table, n_samples,
+                       copy_equal != 0, y);
+}
+
 int l3_op_frontend(int device, int model_type, const float* audio, int n, int db_max_scope, float* out) {
     // runs the engine's own front-end path on a throw-away engine of batch n
     l3_config cfg{};

@@ -1,10 +1,12 @@
 """Audio embeddings of whole clips -- data/usc/features.py:18-28,256-306 (load_audio, get_l3_frames_uniform).
 
 The framing rule lives here and only here: `frame_table` turns clip lengths into one (start, lo, hi) row per 1-second
-frame, and the C side (l3_embed_audio_frames, csrc/clips.hip) only follows the table on the GPU.  Resampling and
-non-PCM16 files are out of scope: decode / resample with any library and pass the array.
+frame, and the C side (l3_embed_audio_frames, csrc/clips.hip) only follows the table on the GPU.  load_audio keeps its
+PCM16-at-48-kHz contract; read_wav / read_audio are the reference's load_audio in full: any PCM or IEEE-float WAV file, resampled
+on the GPU (resample.py, csrc/resample.hip) when its rate is not the one asked for.
 """
 import os
+import struct
 import wave
 
 import numpy as np
@@ -66,6 +68,81 @@ def load_audio(path, sr):
                          % (path, rate, sr))
     pcm = np.frombuffer(raw, dtype='<i2').reshape(-1, nch)
     return (pcm.astype(np.float32) / np.float32(32768)).mean(axis=-1)
+
+
+# WAVE format tags (mmreg.h) that read_wav names when it refuses them
+_WAVE_FORMATS = {0x0001: 'PCM', 0x0002: 'MS ADPCM', 0x0003: 'IEEE float', 0x0006: 'A-law', 0x0007: 'mu-law',
+                 0x0011: 'IMA ADPCM', 0x0031: 'GSM 6.10', 0x0050: 'MPEG', 0x0055: 'MPEG Layer 3', 0xFFFE: 'extensible'}
+
+
+def _wave_format_name(tag):
+    return '%s (format tag 0x%04x)' % (_WAVE_FORMATS.get(tag, 'unknown'), tag)
+
+
+def read_wav(path):
+    """(samples, rate): a WAV file as sf.read(path, dtype='float32', always_2d=True) reads it, then the float32 mean over the
+    channels (data/usc/features.py:22-23), without soundfile.  The RIFF chunks are parsed here, with libsndfile's conversions
+    to float32 [3P]: 8-bit unsigned PCM (u - 128) / 128; 16-, 24- and 32-bit PCM float32(v) * 2^-(bits - 1); IEEE float 32 as
+    stored, 64 cast to float32; WAVE_FORMAT_EXTENSIBLE with a PCM or float sub-format the same.  Any other encoding (ADPCM,
+    A-law, mu-law, MPEG, ...) or a malformed file raises ValueError naming it."""
+    with open(str(path), 'rb') as fh:
+        raw = fh.read()
+    if len(raw) < 12 or raw[0:4] != b'RIFF' or raw[8:12] != b'WAVE':
+        raise ValueError('%s: not a RIFF WAVE file' % (path,))
+    fmt, data, pos = None, None, 12
+    while pos + 8 <= len(raw):
+        cid, size = raw[pos:pos + 4], struct.unpack('<I', raw[pos + 4:pos + 8])[0]
+        body = raw[pos + 8:pos + 8 + size]          # a data chunk whose size runs past the end of the file is cut there
+        if cid == b'fmt ' and fmt is None:
+            fmt = body
+        elif cid == b'data' and data is None:
+            data = body
+        pos += 8 + size + (size & 1)
+    if fmt is None or len(fmt) < 16:
+        raise ValueError('%s: WAV file without a valid fmt chunk' % (path,))
+    if data is None:
+        raise ValueError('%s: WAV file without a data chunk' % (path,))
+    tag, nch, rate, _, block, bits = struct.unpack('<HHIIHH', fmt[:16])
+    if tag == 0xFFFE:
+        if len(fmt) < 40:
+            raise ValueError('%s: WAVE_FORMAT_EXTENSIBLE fmt chunk of %d bytes' % (path, len(fmt)))
+        sub = struct.unpack('<H', fmt[24:26])[0]
+        if sub not in (1, 3):
+            raise ValueError('%s: unsupported WAV encoding: extensible with sub-format %s' % (path, _wave_format_name(sub)))
+        tag = sub
+    if tag not in (1, 3):
+        raise ValueError('%s: unsupported WAV encoding: %s' % (path, _wave_format_name(tag)))
+    if nch < 1 or rate < 1:
+        raise ValueError('%s: %d channels at %d Hz' % (path, nch, rate))
+    width = (bits + 7) // 8
+    if (tag == 1 and width not in (1, 2, 3, 4)) or (tag == 3 and width not in (4, 8)) or block != width * nch:
+        raise ValueError('%s: unsupported WAV encoding: %s with %d bits per sample, block of %d bytes'
+                         % (path, _wave_format_name(tag), bits, block))
+    n = len(data) // block
+    b = np.frombuffer(data, dtype=np.uint8, count=n * block)
+    if tag == 3:
+        x = b.view('<f4' if width == 4 else '<f8').astype(np.float32)
+    elif width == 1:
+        x = (b.astype(np.float32) - np.float32(128)) / np.float32(128)
+    elif width == 2:
+        x = b.view('<i2').astype(np.float32) * np.float32(2.0 ** -15)
+    elif width == 3:
+        v = b.reshape(-1, 3).astype(np.int32)
+        v = (v[:, 0] | (v[:, 1] << 8) | (v[:, 2] << 16)) << 8 >> 8          # sign-extend the 24-bit little-endian value
+        x = v.astype(np.float32) * np.float32(2.0 ** -23)
+    else:
+        x = b.view('<i4').astype(np.float32) * np.float32(2.0 ** -31)
+    return x.reshape(n, nch).mean(axis=-1), int(rate)
+
+
+def read_audio(path, sr, device=0):
+    """data/usc/features.py:18-28 (load_audio) in full: read_wav, then, when the file's rate is not `sr`, resampy.resample(data,
+    sr_orig, sr) on the GPU (resample.resample, filter 'kaiser_best').  Returns float32 samples at `sr`."""
+    from .resample import resample
+    data, sr_orig = read_wav(path)
+    if sr_orig != sr:
+        data = resample(data, sr_orig, sr, device=device)
+    return data
 
 
 def get_l3_frames_uniform(audio, l3embedding_model, hop_size=0.1, sr=48000):

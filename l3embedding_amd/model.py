@@ -747,14 +747,19 @@ class EmbeddingModel(object):
     CLIP_CALL_FRAMES = 4096
     CLIP_CALL_SAMPLES = 1 << 26
 
-    def predict_clips(self, clips, hop_length, batch_size=32):
+    def predict_clips(self, clips, hop_length, batch_size=32, rates=None):
         """get_l3_frames_uniform's framing + predict for many clips at once (data/usc/features.py:276-306): clips is a
         sequence of 1-D float32 arrays at 48 kHz, hop_length the hop in samples.  Returns one (n_i, D) array per clip, n_i
         from features.frame_table.  The engine is chosen as predict chooses it (the model's current one, else batch
         min(batch_size, frames)).  Each clip is sent to the device once and cut into frames there.  Under
         db_max_scope = 'sample' the frames of consecutive clips share engine batches; under 'batch' (the dB maximum over
         an engine batch, kapre 0.1.3.1) every clip starts a new engine batch, so the batches are those of one predict call
-        per clip."""
+        per clip.
+
+        rates: clip i's sample rate (whole Hz) when the clips are not all at 48 kHz.  Each clip is then resampled to 48 kHz on
+        the device as load_audio resamples it (resampy 'kaiser_best', features.py:25-26; a clip at 48 kHz is taken as it is),
+        and the 48 kHz lengths are framed and packed exactly as above: the result equals predict_clips on the clips resampled
+        by resample.resample.  A clip is uploaded at its own rate, once per call its frames reach."""
         from .features import frame_table
         if self.embedding_type != 'audio':
             raise TypeError('predict_clips needs an audio embedding model')
@@ -763,6 +768,15 @@ class EmbeddingModel(object):
             if c.ndim != 1:
                 raise ValueError('every clip must be a 1-D array (got shape %s)' % (c.shape,))
         lengths = np.array([c.size for c in clips], np.int64)
+        if rates is not None:
+            from .resample import check_rates, get_filter, output_length
+            win, num_table = get_filter('kaiser_best')
+            rates = [check_rates(r, 48000)[0] for r in np.asarray(rates).reshape(-1).tolist()]
+            if len(rates) != len(clips):
+                raise ValueError('rates must give one rate per clip (%d rates, %d clips)' % (len(rates), len(clips)))
+            native = lengths
+            lengths = np.array([n if r == 48000 else output_length(int(n), r, 48000) for n, r in zip(native.tolist(), rates)],
+                               np.int64)
         table, counts = frame_table(lengths, hop_length)
         if not clips:
             return []
@@ -802,7 +816,11 @@ class EmbeddingModel(object):
             t[:, 0] = rows[r0:r1, 0] - base
             t[:, 1] = a[r0:r1] - base
             t[:, 2] = np.maximum(np.minimum(rows[r0:r1, 0] + 48000, rows[r0:r1, 2]), a[r0:r1]) - base
-            e.embed_audio_frames(_clip_span(clips, offs, base, top), t, self.pool, out=out[r0:r1])
+            if rates is None:
+                e.embed_audio_frames(_clip_span(clips, offs, base, top), t, self.pool, out=out[r0:r1])
+            else:
+                x, descs = _resample_rows(clips, rates, offs, lengths, base, top)
+                e.embed_audio_clips_resampled(x, descs, win, num_table, top - base, t, self.pool, out=out[r0:r1])
             r0 = r1
         return [out[row0[i]:row0[i] + counts[i]] for i in range(len(clips))]
 
@@ -827,6 +845,24 @@ def _clip_span(clips, offs, base, top):
     if len(pieces) == 1:
         return pieces[0]
     return np.concatenate(pieces) if pieces else np.zeros(0, np.float32)
+
+
+def _resample_rows(clips, rates, offs, lengths, base, top):
+    """The native samples and clip rows {x_off, L, sr_orig, t0, n_out, y_off} (l3_embed_audio_clips_resampled) that fill samples
+    [base, top) of the 48 kHz clips laid back to back (offs, lengths: their first sample and length at 48 kHz).  Every clip the
+    span reaches is uploaded whole: the filter reads up to 64 zero crossings beyond the outputs, and a clip is uploaded once per
+    call anyway unless it spans calls."""
+    i = int(np.searchsorted(offs + lengths, base, side='right'))
+    rows, pieces, pos = [], [], 0
+    while i < len(clips) and offs[i] < top:
+        lo, hi = max(base, int(offs[i])) - int(offs[i]), min(top, int(offs[i] + lengths[i])) - int(offs[i])
+        if hi > lo:
+            rows.append((pos, clips[i].size, rates[i], lo, hi - lo, int(offs[i]) + lo - base))
+            pieces.append(clips[i])
+            pos += clips[i].size
+        i += 1
+    x = np.concatenate(pieces) if len(pieces) > 1 else (pieces[0] if pieces else np.zeros(0, np.float32))
+    return x, np.array(rows, np.int64).reshape(-1, 6)
 
 
 # ---------------------------------------------------------------------------------------------------
