@@ -186,8 +186,9 @@ def amplitude_to_decibel(x, scope='sample', amin=1e-10, dynamic_range=80.0):
     return np.maximum(log_spec, np.asarray(-dynamic_range, dtype=x.dtype))
 
 
-def frontend_forward(kind, audio, consts=None, db_max_scope='sample', dtype=np.float64):
-    """audio (B,1,48000) -> (B, n_freq|n_mels, n_frames, 1)."""
+def frontend_forward(kind, audio, consts=None, db_max_scope='sample', dtype=np.float64, amin=1e-10):
+    """audio (B,1,48000) -> (B, n_freq|n_mels, n_frames, 1).  `amin` is kapre's default; tests vary it only to
+    show that their bounds reject a wrong floor."""
     cfg = FRONTENDS[kind]
     if consts is None:
         consts = frontend_constants(kind)
@@ -205,7 +206,7 @@ def frontend_forward(kind, audio, consts=None, db_max_scope='sample', dtype=np.f
         p = np.power(np.sqrt(p), np.asarray(cfg['power'], dtype=dtype))
     out = np.transpose(p, (0, 2, 1))[..., None]             # (B, freq, time, 1)
     if cfg['db']:
-        out = amplitude_to_decibel(out, scope=db_max_scope)
+        out = amplitude_to_decibel(out, scope=db_max_scope, amin=amin)
     if cfg['loglambda']:
         # audio_model.py:43  tf.log(tf.maximum(x, 1e-12)) / 5.0
         out = np.log(np.maximum(out, np.asarray(1e-12, dtype=dtype))) / np.asarray(5.0, dtype=dtype)
@@ -844,17 +845,40 @@ AUDIO_POOLING = {
 }
 
 
-def embed_audio(model_type, P, audio, pooling_type='original', dtype=np.float64, db_max_scope='sample'):
-    """MaxPooling2D(pool, padding='same') on the *conv output* of
-    audio_embedding_layer (before its BN/ReLU), inference-mode BN, then Flatten."""
+def audio_embedding_map(model_type, P, audio, dtype=np.float64, db_max_scope='sample', rows=None, bn_training=False,
+                        amin=1e-10):
+    """The conv output of audio_embedding_layer (before its BN/ReLU), NHWC, for the rows `rows` of the batch `audio`
+    (every row when None).  The front-end runs on every row given, so a 'batch'-scope dB maximum is the whole batch's;
+    the tower runs one row at a time and only on `rows`, so a row's value does not depend on which other rows are asked
+    for: rows=[r] is row r of the full call bit for bit.  `bn_training` (BatchNorm on the batch moments of `rows`) and
+    `amin` are wrong meanings, there for the tests' negative controls."""
     spec = model_spec(model_type)
-    ph, pw = AUDIO_POOLING[model_type][pooling_type]
     consts = {k.rsplit('/', 1)[1]: v for k, v in P.items() if '/' + spec['frontend_name'] + '/' in k}
-    fe = frontend_forward(spec['frontend'], audio, consts, db_max_scope, dtype)
-    taps = {}
-    _tower_forward('audio_model', spec['audio'], fe, P, False, taps)
-    y, _ = maxpool_fwd(taps['audio_embedding_layer'], ph, pw, ph, pw, 'same')
+    fe = frontend_forward(spec['frontend'], audio, consts, db_max_scope, dtype, amin=amin)
+    rows = np.arange(fe.shape[0]) if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)
+    ops = spec['audio']
+    ops = ops[:[k for k, op in enumerate(ops) if op[0] == 'conv' and op[1] == 'audio_embedding_layer'][0] + 1]
+    groups = [rows] if bn_training else [rows[i:i + 1] for i in range(len(rows))]
+    maps = []
+    for g in groups:
+        taps = {}
+        _tower_forward('audio_model', ops, fe[g], P, bn_training, taps)
+        maps.append(taps['audio_embedding_layer'])
+    return np.concatenate(maps)
+
+
+def pool_embedding(emb_map, pool):
+    """MaxPooling2D(pool, padding='same') then Flatten in Keras's (H, W, C) order."""
+    y, _ = maxpool_fwd(emb_map, pool[0], pool[1], pool[0], pool[1], 'same')
     return y.reshape(y.shape[0], -1)
+
+
+def embed_audio(model_type, P, audio, pooling_type='original', dtype=np.float64, db_max_scope='sample', rows=None):
+    """MaxPooling2D(pool, padding='same') on the *conv output* of
+    audio_embedding_layer (before its BN/ReLU), inference-mode BN, then Flatten.
+    `rows`: embed only these rows of the batch (audio_embedding_map)."""
+    emb = audio_embedding_map(model_type, P, audio, dtype, db_max_scope, rows)
+    return pool_embedding(emb, AUDIO_POOLING[model_type][pooling_type])
 
 
 def embed_vision(model_type, P, video, dtype=np.float64):

@@ -286,6 +286,30 @@ def test_embedding_dims():
     assert o.embed_audio('cnn_L3_melspec2', P, a, 'short', np.float32).shape == (1, 512)
 
 
+@pytest.mark.parametrize('scope', ['sample', 'batch'])
+def test_embedding_of_chosen_rows_equals_the_full_call(scope):
+    """embed_audio(rows=r) -- front-end on every row (the 'batch'-scope dB maximum is the whole batch's), tower on rows r
+    only -- is rows r of the full call bit for bit, and the full call is the whole-batch tower of the training graph."""
+    mt = 'cnn_L3_melspec1'
+    P, _ = perturbed(mt, 5)
+    a = np.random.RandomState(3).uniform(-1, 1, (3, 1, 48000)).astype(np.float32)
+    a[1] *= 0.01                                        # 40 dB quieter: the scope changes this row
+    full = {p: o.embed_audio(mt, P, a, p, np.float32, scope) for p in ('original', 'short')}
+    emb = o.audio_embedding_map(mt, P, a, np.float32, scope, rows=[2, 1])
+    for p, pool in o.AUDIO_POOLING[mt].items():
+        part = o.pool_embedding(emb, pool)
+        assert part.shape == (2, full[p].shape[1]) and np.array_equal(part, full[p][[2, 1]]), p
+        assert np.array_equal(o.embed_audio(mt, P, a, p, np.float32, scope, rows=[1]), full[p][[1]]), p
+    spec = o.model_spec(mt)
+    fe = o.frontend_forward(spec['frontend'], a, None, scope, np.float32)
+    taps = {}
+    o._tower_forward('audio_model', spec['audio'], fe, P, False, taps)
+    ref = o.pool_embedding(taps['audio_embedding_layer'], o.AUDIO_POOLING[mt]['original'])
+    assert np.abs(full['original'] - ref).max() <= 1e-5 * np.abs(ref).max()
+    other = o.embed_audio(mt, P, a, 'original', np.float32, 'batch' if scope == 'sample' else 'sample', rows=[1])
+    assert np.abs(other - full['original'][[1]]).max() > 1e-2 * np.abs(ref).max()
+
+
 def test_torch_cpu_baseline_step_matches_oracle():
     """bench.py's CPU baseline (oracle/torch_cpu.py, fp32 autograd) does the same training step as the
     NumPy oracle: same loss before the update and after one Adam step."""
