@@ -186,7 +186,8 @@ int l3_step_results_wait(l3_engine *e, int slot, float *loss, float *acc);
  * gradient arena, issued by the library itself:
  *   l3_comm_unique_id   rank 0 obtains the 128-byte ncclUniqueId and ships it to the other ranks by any
  *                       means the host has (file, TCP store, MPI); no engine needed
- *   l3_comm_init        ncclCommInitRank for this engine's GPU (collective over all ranks)
+ *   l3_comm_init        ncclCommInitRank for this engine's GPU (collective over all ranks); on any failure
+ *                       (L3_ECOMM / L3_EHIP / L3_ENOMEM) no communicator is left: it may be called again
  *   l3_step_dp          one training step on the resident batch: as each gradient bucket completes
  *                       (head, vision block 4..1, audio block 4..1) its ncclAllReduce is enqueued on the
  *                       communicator's own HIP stream behind an event, while backward continues on the
@@ -220,7 +221,8 @@ int l3_bucket_range(const l3_engine *e, int bucket, int64_t *offset, int64_t *nu
  * itself; l3_config.dp_moving, training_utils.py:141-157): after l3_step_forward(e, 1), l3_bn_stats_pack_dev packs this rank's
  * batch means / variances (`numel` floats, engine stream) -> the caller all-gathers them into the buffer
  * l3_bn_stats_replicas_dev returns (world x numel floats, rank-major) -> the next l3_step_update applies the `world` replica
- * updates in rank order instead of the rank's own single one. */
+ * updates in rank order instead of the rank's own single one.  l3_bn_stats_replicas_dev refuses (L3_ESTATE, nothing armed) unless a
+ * training forward is current and l3_bn_stats_pack_dev ran behind it. */
 int l3_bn_stats_pack_dev(l3_engine *e, void **send_dev, int64_t *numel);
 int l3_bn_stats_replicas_dev(l3_engine *e, int world, void **gathered_dev);
 

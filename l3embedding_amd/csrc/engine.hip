@@ -234,6 +234,7 @@ struct l3_engine {
     // every rank's, and how many replica updates the next l3_step_update applies from the latter (0: the rank's own, once)
     float *bn_send = nullptr, *bn_gathered = nullptr;
     int bn_pack_floats = 0, bn_gathered_world = 0, bn_replicas_armed = 0;
+    bool bn_packed = false;     // l3_bn_stats_pack_dev ran behind the current forward (l3_bn_stats_replicas_dev arms only then)
     // l3_comm_timing: hipEvents around every bucket's all-reduce (communicator stream) and at "backward done" / "last collective done"
     bool comm_timing = false;
     std::vector<hipEvent_t> ev_ct0, ev_ct1;
@@ -2099,6 +2100,7 @@ int l3_step_forward(l3_engine* e, int training) {
     HIPCHK(e, hipSetDevice(e->cfg.device));
     e->bucket_ready = -1;       // a step that was abandoned between a backward bucket and its reduce must not leave its flag to the next
     e->bn_replicas_armed = 0;   // ... nor the replicas' statistics it had gathered: they are armed behind THIS forward or not at all
+    e->bn_packed = false;
     if (training) {
         // At most two training steps are queued: a caller that enqueues a long run of steps without reading anything (bench.py)
         // otherwise runs into the runtime's own limit, where the HIP launch path SPINS until the GPU has caught up -- measured with
@@ -2197,14 +2199,8 @@ int l3_comm_unique_id(void* id128) {
     return L3_OK;
 }
 
-int l3_comm_init(l3_engine* e, const void* id128, int world, int rank) {
-    if (!e || !id128) return L3_EINVAL;
-    if (e->comm) {
-        e->err = "l3_comm_init: communicator already initialised";
-        return L3_ESTATE;
-    }
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    if (l3::comm_create(id128, world, rank, e->cfg.device, &e->comm, &e->err)) return L3_ECOMM;
+// l3_comm_init behind comm_create: the communicator's events and scratch, then the ranks' agreement on the protocol
+static int comm_init_after_create(l3_engine* e) {
     comm_release_events(e);
     e->ev_bucket.assign(e->buckets.size(), nullptr);
     for (auto& ev : e->ev_bucket) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -2216,27 +2212,41 @@ int l3_comm_init(l3_engine* e, const void* id128, int world, int rank) {
     // compare what they decided (max of x and of -x over the ranks): a rank that serialised its towers, another model, another
     // dp_moving or another precision on one rank would otherwise hang or corrupt silently at the first step.
     e->dp_order_alt = e->side != nullptr && e->overlap && !(l3_knob("L3_DP_ARENA_ORDER") && atoi(l3_knob("L3_DP_ARENA_ORDER")) == 1);
-    {
-        const double mine[4] = {e->dp_order_alt ? 1.0 : 0.0, (double)e->buckets.size(), (double)e->cfg.dp_moving,
-                                (double)(e->cfg.model_type * 2 + e->cfg.dtype)};
-        double v[8];
-        for (int i = 0; i < 4; ++i) {
-            v[i] = mine[i];
-            v[4 + i] = -mine[i];
-        }
-        if ((rc = l3_comm_allreduce_host(e, v, 8, 1))) return rc;
-        for (int i = 0; i < 4; ++i)
-            if (v[i] != mine[i] || v[4 + i] != -mine[i]) {
-                static const char* what[4] = {"the bucket order on the wire (l3_set_tower_overlap / L3_TWO_STREAMS differ)", "the number of gradient buckets",
-                                              "l3_config.dp_moving", "l3_config.model_type / dtype"};
-                e->err = std::string("l3_comm_init: the ranks disagree on ") + what[i];
-                l3::comm_destroy(e->comm);
-                e->comm = nullptr;
-                comm_release_events(e);
-                return L3_ECOMM;
-            }
+    const double mine[4] = {e->dp_order_alt ? 1.0 : 0.0, (double)e->buckets.size(), (double)e->cfg.dp_moving,
+                            (double)(e->cfg.model_type * 2 + e->cfg.dtype)};
+    double v[8];
+    for (int i = 0; i < 4; ++i) {
+        v[i] = mine[i];
+        v[4 + i] = -mine[i];
     }
+    if ((rc = l3_comm_allreduce_host(e, v, 8, 1))) return rc;
+    for (int i = 0; i < 4; ++i)
+        if (v[i] != mine[i] || v[4 + i] != -mine[i]) {
+            static const char* what[4] = {"the bucket order on the wire (l3_set_tower_overlap / L3_TWO_STREAMS differ)", "the number of gradient buckets",
+                                          "l3_config.dp_moving", "l3_config.model_type / dtype"};
+            e->err = std::string("l3_comm_init: the ranks disagree on ") + what[i];
+            return L3_ECOMM;
+        }
     return L3_OK;
+}
+
+int l3_comm_init(l3_engine* e, const void* id128, int world, int rank) {
+    if (!e || !id128) return L3_EINVAL;
+    if (e->comm) {
+        e->err = "l3_comm_init: communicator already initialised";
+        return L3_ESTATE;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    if (l3::comm_create(id128, world, rank, e->cfg.device, &e->comm, &e->err)) return L3_ECOMM;
+    // whatever fails behind comm_create (an event, the scratch buffer, the agreement all-reduce, a disagreement) leaves no
+    // communicator: a half-built one would answer a retry with "already initialised" and let l3_step_dp run on it
+    const int rc = comm_init_after_create(e);
+    if (rc) {
+        l3::comm_destroy(e->comm);
+        e->comm = nullptr;
+        comm_release_events(e);
+    }
+    return rc;
 }
 
 int l3_comm_destroy(l3_engine* e) {
@@ -2389,6 +2399,7 @@ int l3_bn_stats_pack_dev(l3_engine* e, void** send_dev, int64_t* numel) {
     }
     int rc = bn_stats_pack(e, 1);
     if (rc) return rc;
+    e->bn_packed = true;
     *send_dev = e->bn_send;
     *numel = e->bn_pack_floats;
     return L3_OK;
@@ -2396,6 +2407,13 @@ int l3_bn_stats_pack_dev(l3_engine* e, void** send_dev, int64_t* numel) {
 
 int l3_bn_stats_replicas_dev(l3_engine* e, int world, void** gathered_dev) {
     if (!e || !gathered_dev || world < 1) return L3_EINVAL;
+    // the `world` updates it arms are applied by the next l3_step_update: only behind a training forward whose statistics this rank
+    // has packed (what the caller gathers), never from whatever the buffer held before
+    if (!e->fwd_done || !e->last_training || !e->bn_packed) {
+        e->bn_replicas_armed = 0;
+        e->err = "l3_bn_stats_replicas_dev: no packed training forward (l3_step_forward(e, 1), then l3_bn_stats_pack_dev)";
+        return L3_ESTATE;
+    }
     HIPCHK(e, hipSetDevice(e->cfg.device));
     int rc = ensure_bn_table(e);
     if (rc) return rc;
