@@ -410,6 +410,51 @@ int l3_op_mlp_softmax_ce(int device, const float *z, const int32_t *labels, int 
 /* The engine's Adam kernel (keras 2.0.9 + L2 gradient 2 * l2 * p on the first n_l2 elements) on its own: p, m, v in/out. */
 int l3_op_adam(int device, float *p, const float *g, float *m, float *v, int64_t n, int64_t n_l2, float l2x2, float lr_t);
 
+/* ---- Downstream SVM classifier (classifier/train.py:79-166) ------------------------------------------------------------------
+ * train_svm's sklearn.svm.SVC (libsvm's C-SVC) on the GPU: the binary problems of one-vs-one and of probability estimates solved
+ * together by decomposition (working sets of q variables, libsvm's WSS3 inside each), kernel values in fp32 on the fp32 matrix
+ * cores, alpha and the gradient in float64.  Deterministic (no float atomics).  The multiclass shell (pairs, probability
+ * estimates, votes) is Python (classifier.py).  Errors: l3_last_error(NULL) gives the message. */
+#define L3_SVM_LINEAR 0     /* u.v                                  (libsvm kernel_type order) */
+#define L3_SVM_POLY 1       /* (gamma u.v + coef0)^degree */
+#define L3_SVM_RBF 2        /* exp(-gamma |u - v|^2), |u|^2 + |v|^2 - 2 u.v clamped at 0 */
+#define L3_SVM_SIGMOID 3    /* tanh(gamma u.v + coef0) */
+#define L3_SVM_DEFAULT_WS 64          /* working-set size q when l3_svm_fit is given 0 */
+#define L3_SVM_LOCAL_REL 0.1          /* a local solve stops at max(tol, 0.1 x its first gap) */
+typedef struct l3_svm_kernel {
+    int32_t kind, degree;
+    double gamma, coef0;
+} l3_svm_kernel;
+typedef struct l3_svm l3_svm;
+int l3_svm_create(int device, l3_svm **m);
+void l3_svm_destroy(l3_svm *m);
+/* The training matrix X (n, D) float32, copied to the device once and kept for every later fit (the grid search over C of
+ * train_param_search refits on the same rows).  The labels travel with the problems, as signs. */
+int l3_svm_set_data(l3_svm *m, const float *X, int64_t n, int D);
+/* SVC.fit's libsvm svm_train_one, for n_prob binary problems at once (svm.cpp Solver::Solve with WSS3, shrinking off).  Problem p
+ * holds entries [prob_off[p], prob_off[p + 1]) of rows (indices into the set_data matrix) and signs (+1 / -1); alpha_out (one per
+ * entry), rho_out (libsvm's rho: decision = sum y alpha K - rho), updates_out (local SMO updates), outer_out (outer iterations)
+ * and gap_out (the last m(alpha) - M(alpha) seen; < tol when converged) per problem; the last three may be NULL.  max_iter caps
+ * the updates per problem (-1: libsvm's max(10^7, 100 l)); q is the working-set size (0: L3_SVM_DEFAULT_WS; even, <= 128).
+ * Every launch covers all problems still active; the host waits once per outer iteration. */
+int l3_svm_fit(l3_svm *m, const l3_svm_kernel *k, double C, double tol, int64_t max_iter, int n_prob, const int64_t *prob_off,
+               const int32_t *rows, const int8_t *signs, int q, double *alpha_out, double *rho_out, int64_t *updates_out,
+               int32_t *outer_out, double *gap_out);
+/* svm_predict_values (svm.cpp) of n rows, one fused launch per block of rows: dec_out (n, n_class (n_class - 1) / 2) in libsvm's
+ * pair order (0,1), (0,2), ..., positive for the first class of the pair.  Rows come as a host matrix X (n, D) or as x_idx into the
+ * set_data matrix; support vectors likewise as SV (n_sv, D) or sv_idx.  Support vectors are grouped by class: class c owns
+ * [sv_start[c], sv_start[c + 1]); coef is libsvm's sv_coef (n_class - 1, n_sv), rho one per pair.  2 <= n_class <= 64. */
+int l3_svm_decision(l3_svm *m, const l3_svm_kernel *k, const float *X, const int32_t *x_idx, int64_t n, int D, const float *SV,
+                    const int32_t *sv_idx, int64_t n_sv, int n_class, const int64_t *sv_start, const double *coef,
+                    const double *rho, double *dec_out);
+/* Operators on their own (host buffers; parity tests).  kernel rows: out (na, nb) = k(x[a_idx[w]], x[b_idx[t]]), fp32. */
+int l3_op_svm_kernel_rows(int device, const l3_svm_kernel *k, const float *x, int64_t n_x, int D, const int32_t *a_idx, int na,
+                          const int32_t *b_idx, int nb, float *out);
+/* one local SMO solve of the q-variable problem (q <= 128): block K (q, q), signs y, alpha in/out, gradient grad at alpha; stops
+ * at a gap below max(eps, local_rel x the first gap), when no pair can move, or after max_updates (<= 0: no cap) updates. */
+int l3_op_svm_smo(int device, const float *K, const int8_t *y, int q, double C, double eps, double local_rel, int64_t max_updates,
+                  double *alpha, const double *grad, int64_t *updates_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,18 @@ SIGNATURES = {
                              + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p]),
     'l3_op_mlp_softmax_ce': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 4),
     'l3_op_adam': (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_float, C.c_float]),
+    # downstream SVM classifier (csrc/svm.hip)
+    'l3_svm_create': (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    'l3_svm_destroy': (None, [C.c_void_p]),
+    'l3_svm_set_data': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
+    'l3_svm_fit': (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int64, C.c_int] + [C.c_void_p] * 3
+                   + [C.c_int] + [C.c_void_p] * 5),
+    'l3_svm_decision': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_int64, C.c_int] + [C.c_void_p] * 4),
+    'l3_op_svm_kernel_rows': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_int, C.c_void_p]),
+    'l3_op_svm_smo': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -865,3 +877,105 @@ def op_adam(p, g, m, v, n_l2, l2x2, lr_t, device=0):
     g = _f32(g).ravel()
     check(load().l3_op_adam(device, _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.size, int(n_l2), float(l2x2), float(lr_t)))
     return p, m, v
+
+
+# ---- downstream SVM classifier (classifier/train.py:79-166; csrc/svm.hip) ---------------------------------------------------------
+SVM_KERNELS = {'linear': 0, 'poly': 1, 'rbf': 2, 'sigmoid': 3}     # L3_SVM_* (libsvm's kernel_type order)
+SVM_MAX_CLASSES = 64
+SVM_MAX_WS = 128
+
+
+class SvmKernel(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('degree', C.c_int32), ('gamma', C.c_double), ('coef0', C.c_double)]
+
+
+def svm_kernel(kernel, gamma=0.0, coef0=0.0, degree=3):
+    if kernel not in SVM_KERNELS:
+        raise ValueError('kernel must be one of %s, not %r' % (sorted(SVM_KERNELS), kernel))
+    return SvmKernel(SVM_KERNELS[kernel], int(degree), float(gamma), float(coef0))
+
+
+class SVM(object):
+    """RAII wrapper over an l3_svm handle: the resident training matrix and the batched binary solver on one device."""
+
+    def __init__(self, device=0):
+        self.lib = load()
+        h = C.c_void_p()
+        check(self.lib.l3_svm_create(int(device), C.byref(h)), None)
+        self.h = h
+        self.n = self.D = 0
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_svm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_data(self, X):
+        x = _f32(X)
+        check(self.lib.l3_svm_set_data(self.h, _ptr(x), x.shape[0], x.shape[1]))
+        self.n, self.D = x.shape
+
+    def fit(self, kernel, problems, cost=1.0, tol=1e-3, max_iter=-1, q=0):
+        """problems: list of (rows, signs) over the set_data rows.  -> (alphas (list of float64 arrays), rho (P,),
+        updates (P,), outer iterations (P,), last gaps (P,))"""
+        rows = [np.ascontiguousarray(r, np.int32) for r, _ in problems]
+        off = np.zeros(len(rows) + 1, np.int64)
+        off[1:] = np.cumsum([r.size for r in rows])
+        r_all = np.concatenate(rows) if rows else np.zeros(0, np.int32)
+        s_all = np.concatenate([np.asarray(s, np.int8) for _, s in problems]) if rows else np.zeros(0, np.int8)
+        P = len(rows)
+        alpha, rho = np.empty(int(off[-1]), np.float64), np.empty(P, np.float64)
+        upd, outer, gap = np.empty(P, np.int64), np.empty(P, np.int32), np.empty(P, np.float64)
+        check(self.lib.l3_svm_fit(self.h, C.byref(kernel), float(cost), float(tol), int(max_iter), P, _ptr(off), _ptr(r_all),
+                                  _ptr(s_all), int(q), _ptr(alpha), _ptr(rho), _ptr(upd), _ptr(outer), _ptr(gap)))
+        return [alpha[off[p]:off[p + 1]] for p in range(P)], rho, upd, outer, gap
+
+    def decision(self, kernel, sv_start, coef, rho, X=None, x_idx=None, SV=None, sv_idx=None):
+        """libsvm's pairwise decision values (n, n_class (n_class - 1) / 2) of host rows X or resident rows x_idx, against
+        support vectors SV (host) or sv_idx (resident), grouped by class as sv_start says."""
+        cs = np.ascontiguousarray(sv_start, np.int64)
+        ncls = cs.size - 1
+        cf = np.ascontiguousarray(coef, np.float64).reshape(ncls - 1, -1)
+        rh = np.ascontiguousarray(rho, np.float64).reshape(-1)
+        x, xi = _f32(X), _i32(x_idx)
+        sv, si = _f32(SV), _i32(sv_idx)
+        n = x.shape[0] if x is not None else xi.size
+        D = x.shape[1] if x is not None else (sv.shape[1] if sv is not None else self.D)
+        if sv is not None and sv.size == 0:
+            sv = np.zeros((1, D), np.float32)
+        if si is not None and si.size == 0:
+            si = np.zeros(1, np.int32)
+        out = np.empty((n, ncls * (ncls - 1) // 2), np.float64)
+        if n == 0:
+            return out
+        check(self.lib.l3_svm_decision(self.h, C.byref(kernel), _ptr(x), _ptr(xi), n, int(D), _ptr(sv), _ptr(si), int(cs[-1]), ncls,
+                                       _ptr(cs), _ptr(cf), _ptr(rh), _ptr(out)))
+        return out
+
+
+def op_svm_kernel_rows(x, a_idx, b_idx, kernel='rbf', gamma=0.0, coef0=0.0, degree=3, device=0):
+    """(len(a_idx), len(b_idx)) float32: k(x[a], x[b]) through the solver's kernel-row launch"""
+    x, a, b = _f32(x), _i32(a_idx), _i32(b_idx)
+    out = np.empty((a.size, b.size), np.float32)
+    kp = svm_kernel(kernel, gamma, coef0, degree)
+    check(load().l3_op_svm_kernel_rows(device, C.byref(kp), _ptr(x), x.shape[0], x.shape[1], _ptr(a), a.size, _ptr(b), b.size,
+                                       _ptr(out)))
+    return out
+
+
+def op_svm_smo(K, y, alpha, grad, cost=1.0, eps=1e-3, local_rel=0.0, max_updates=-1, device=0):
+    """one local SMO solve on the GPU (box [0, cost]) -> (alpha, updates)"""
+    K = _f32(K)
+    y = np.ascontiguousarray(y, np.int8)
+    a = np.array(alpha, np.float64, copy=True)
+    g = np.ascontiguousarray(grad, np.float64)
+    u = np.zeros(1, np.int64)
+    check(load().l3_op_svm_smo(device, _ptr(K), _ptr(y), y.size, float(cost), float(eps), float(local_rel), int(max_updates), _ptr(a),
+                               _ptr(g), _ptr(u)))
+    return a, int(u[0])

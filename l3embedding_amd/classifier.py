@@ -7,7 +7,10 @@ it.  Deviations from the reference, all deliberate:
     are not reproducible); the Glorot initialisation is seeded with random_state too;
   * the random start delay and the Google Sheets logging of train() are skipped; config.json has git_commit None;
   * the scalers are pickled with `pickle` (the reference uses sklearn's joblib; these are NumPy restatements, usc.py);
-  * SVM, random forest and StratifiedShuffleSplit (sklearn on the host) are not built: they raise.
+  * the random forest and StratifiedShuffleSplit (sklearn on the host) are not built: they raise;
+  * the SVM (train_svm, classifier/train.py:79-166) trains on the GPU (svm.py, csrc/svm.hip); its probability estimates draw the
+    cross-validation fold permutation from np.random.RandomState(random_state) as the MLP's shuffle does (libsvm uses rand()),
+    and the model is pickled with `pickle` (the reference uses joblib).  train() still runs only the MLP.
 """
 import datetime
 import getpass
@@ -20,6 +23,7 @@ from itertools import product
 import numpy as np
 
 from . import _lib, callbacks, kerasfile
+from .svm import SVC, hinge_loss  # noqa: F401  (re-exported: the reference imports them into classifier/train.py)
 from .usc import get_split, preprocess_split_data
 
 LOGGER = logging.getLogger('classifier')
@@ -30,7 +34,8 @@ DATASET_NUM_CLASSES = {
     'dcase2013': 10,
 }
 
-ONLY_MLP = 'only the mlp classifier is built (model_type {!r}: the SVM and random forest are sklearn on the host, with no GPU path)'
+ONLY_MLP = ('only the mlp classifier is built (model_type {!r}: the fold driver runs the MLP alone; classifier.train_svm trains '
+            'the SVM on the GPU, and the random forest is not built)')
 NO_SSS = ('the parameter search without a validation fold needs sklearn\'s StratifiedShuffleSplit, which is not built: '
           'search on the validation fold instead')
 
@@ -275,6 +280,35 @@ def train_mlp(train_data, valid_data, test_data, model_dir, batch_size=64, num_e
         per_file = _file_predictions(model.predict(test_data['features']), test_data['file_idxs'])
         test_metrics = compute_metrics(test_data['labels'], per_file, num_classes=num_classes)
     return model, train_metrics, valid_metrics, test_metrics
+
+
+def train_svm(train_data, valid_data, test_data, model_dir, C=1.0, kernel='rbf', num_classes=10, tol=0.001, max_iterations=-1,
+              verbose=False, random_state=12345678, **kwargs):
+    """classifier/train.py:79-166 -> (model, train_metrics, valid_metrics, test_metrics): SVC(C, kernel, tol, max_iter,
+    probability=True, random_state) fitted on the GPU and pickled to model_dir/model.pkl; 'loss' is sklearn's hinge loss of the
+    (ovr) decision values; the test set is classified per file as the argmax of the mean of its frames' predict_proba."""
+    features, labels = train_data['features'], train_data['labels']
+    clf = SVC(C=C, probability=True, kernel=kernel, max_iter=max_iterations, tol=tol, random_state=random_state, verbose=verbose)
+    LOGGER.debug('Fitting model to data...')
+    clf.fit(features, labels)
+    LOGGER.info('Saving model...')
+    _dump(os.path.join(model_dir, 'model.pkl'), clf)
+
+    classes = np.arange(num_classes)
+    train_metrics = compute_metrics(labels, clf.predict(features), num_classes=num_classes)
+    train_metrics['loss'] = hinge_loss(labels, clf.decision_function(features), labels=classes)
+    LOGGER.info('Train - hinge loss: %s, acc: %s', train_metrics['loss'], train_metrics['accuracy'])
+    valid_metrics = {}
+    if valid_data:
+        vx, vy = valid_data['features'], valid_data['labels']
+        valid_metrics = compute_metrics(vy, clf.predict(vx), num_classes=num_classes)
+        valid_metrics['loss'] = hinge_loss(vy, clf.decision_function(vx), labels=classes)
+        LOGGER.info('Valid - hinge loss: %s, acc: %s', valid_metrics['loss'], valid_metrics['accuracy'])
+    test_metrics = {}
+    if test_data:
+        per_file = _file_predictions(clf.predict_proba(test_data['features']), test_data['file_idxs'])
+        test_metrics = compute_metrics(test_data['labels'], per_file, num_classes=num_classes)
+    return clf, train_metrics, valid_metrics, test_metrics
 
 
 def train_param_search(train_data, valid_data, test_data, model_dir, train_func, search_space, valid_ratio=0.15,

@@ -1,6 +1,6 @@
 """Command line of the reference's 06_train_classifier.py (same flags, same defaults: 06_train_classifier.py:5-203) driving
-l3embedding_amd.classifier.train().  Only the MLP is built: `-mt svm` (the default, as in the reference) and `-mt rf` fail at
-once, and so does `-psnv` (it needs sklearn's StratifiedShuffleSplit).
+l3embedding_amd.classifier.train().  The fold driver runs the MLP alone: `-mt svm` (the default, as in the reference; the SVM
+itself is classifier.train_svm) and `-mt rf` fail at once, and so does `-psnv` (it needs sklearn's StratifiedShuffleSplit).
 
     python -m l3embedding_amd.cli_classifier -mt mlp -e 150 -lr 1e-4 -wd 1e-5 <features_dir> <output_dir> <fold_num>
 """
@@ -27,11 +27,11 @@ _OPTIONS = [
      'after the search keep the chosen run instead of retraining on train + validation'),
     ('-lr', '--learning-rate', 'learning_rate', dict(type=float, default=1e-4), 'MLP: Adam learning rate'),
     ('-wd', '--weight-decay', 'weight_decay', dict(type=float, default=1e-5), 'MLP: L2 factor on the three kernels'),
-    ('-npf', '--norm-penalty-factor', 'C', dict(type=float, default=1.0), 'SVM only (not built): C'),
-    ('-sct', '--svm-conv-tolerance', 'tol', dict(type=float, default=0.00001), 'SVM only (not built): tolerance'),
-    ('-smi', '--svm-max-iterations', 'max_iterations', dict(type=int, default=-1), 'SVM only (not built): iteration cap'),
+    ('-npf', '--norm-penalty-factor', 'C', dict(type=float, default=1.0), 'SVM only (classifier.train_svm): C'),
+    ('-sct', '--svm-conv-tolerance', 'tol', dict(type=float, default=0.00001), 'SVM only (classifier.train_svm): tolerance'),
+    ('-smi', '--svm-max-iterations', 'max_iterations', dict(type=int, default=-1), 'SVM only (classifier.train_svm): iteration cap'),
     ('-skt', '--svm-kernel-type', 'kernel', dict(type=str, default='rbf', choices=['rbf', 'sigmoid', 'linear', 'poly']),
-     'SVM only (not built): kernel'),
+     'SVM only (classifier.train_svm): kernel'),
     ('-rfne', '--rf-num-estimators', 'n_estimators', dict(type=int, default=100), 'random forest only (not built): trees'),
     ('-gsid', '--gsheet-id', 'gsheet_id', dict(type=str), 'accepted and ignored (no spreadsheet logging)'),
     ('-gdan', '--google-dev-app-name', 'google_dev_app_name', dict(type=str), 'accepted and ignored'),

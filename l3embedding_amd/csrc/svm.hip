@@ -1,0 +1,961 @@
+// svm.hip -- the reference's SVM sound classifier (classifier/train.py:79-166: sklearn.svm.SVC, i.e. libsvm's C-SVC) trained and
+// evaluated on the GPU, and the l3_svm handle of the C ABI.
+//
+// Training is decomposition in the ThunderSVM style, batched over every binary problem of a fit (one-vs-one pairs and the
+// cross-validation sub-problems of probability estimates).  One outer iteration is four launches on one stream:
+//   svm_select   one workgroup per problem: m(alpha) - M(alpha) for the stopping test; q / 2 violators from the top of I_up and
+//                q / 2 from the bottom of I_low by -y grad (the working set)
+//   svm_rows     K[w, t] = k(x[ws_w], x[idx_t]) for every working-set row against the problem's rows: gathered fp32 rows on the
+//                fp32 matrix cores (v_mfma_f32_32x32x2_f32), the kernel function applied in the epilogue
+//   svm_smo      one workgroup per problem solves the q-variable sub-problem with libsvm's second-order pair selection (WSS3)
+//                on the q x q block held in LDS; alpha and grad in float64
+//   svm_grad     grad_t += sum_s dalpha_s y_s y_t K[s, t] in float64 from the rows svm_rows wrote
+// then one host synchronisation for all problems (which are still active).  Prediction is one fused launch per class block:
+// K(X_test, SV) tiles in registers times the class's dual coefficients, the n_test x n_SV kernel matrix never reaching HBM.
+// No float atomics anywhere: the same inputs give bit-identical results.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/l3hip.h"
+#include "device_common.h"
+#include "kernels.h"
+
+namespace l3 {
+namespace {
+
+constexpr int SVM_QMAX = 128;          // working-set cap: the q x q fp32 block is 64 KiB of LDS
+constexpr int SVM_MAX_CLASSES = 64;
+constexpr double SVM_TAU = 1e-12;      // libsvm's TAU: the curvature used where K_ii + K_jj - 2 K_ij <= 0 (sigmoid is not PSD)
+
+__device__ __forceinline__ int mfma_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+
+struct SvmKern {
+    int kind, degree;
+    float gamma, coef0;
+};
+
+// libsvm's powi: repeated squaring (the same products for an integer degree)
+__device__ __forceinline__ float powi_f(float base, int times) {
+    float tmp = base, ret = 1.f;
+    for (int t = times; t > 0; t /= 2) {
+        if (t % 2 == 1) ret *= tmp;
+        tmp = tmp * tmp;
+    }
+    return ret;
+}
+
+__device__ __forceinline__ float kfun(const SvmKern& k, float dot, float xx, float yy) {
+    switch (k.kind) {
+        case L3_SVM_POLY: return powi_f(k.gamma * dot + k.coef0, k.degree);
+        case L3_SVM_RBF: return expf(-k.gamma * fmaxf(xx + yy - 2.f * dot, 0.f));
+        case L3_SVM_SIGMOID: return tanhf(k.gamma * dot + k.coef0);
+        default: return dot;
+    }
+}
+
+// ---- squared row norms (rbf), summed in float64 ------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void svm_norms_kernel(const float* x, int64_t n, int D, float* xx) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const float* xr = x + row * D;
+    double s = 0.0;
+    for (int k = lane; k < D; k += 64) s += (double)xr[k] * (double)xr[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) xx[row] = (float)s;
+}
+
+// ---- kernel rows ---------------------------------------------------------------------------------------------------------------
+// One wave per (problem, 32-column tile); the wave runs the problem's rows in groups of four 32-row tiles, so every column row
+// it loads feeds up to 128 rows.  Step of 8 k: lane (r, h) holds x[row r][k0 + 4h + j] (one float4 of each row) and MFMA j sums
+// k0 + j and k0 + 4 + j, as mlp_fwd_kernel does.
+struct SvmRowsArgs {
+    const float* x;              // resident rows (n_x, D)
+    const float* xx;             // their squared norms
+    const int* ridx;             // problem p's rows: ridx + p * rstride, nrows[p] of them (or nrows_all when nrows is NULL)
+    const int* nrows;
+    const int* cidx;             // problem p's columns: cidx[col_off[p] .. col_off[p + 1])
+    const int64_t* col_off;
+    const int64_t* tile_off;     // prefix of ceil(columns / 32) per problem
+    const int* active;           // may be NULL
+    float* out;                  // problem p: out + rstride * col_off[p], row w at w * columns + t
+    int P, rstride, nrows_all, D, vec;
+    SvmKern k;
+};
+
+__global__ __launch_bounds__(256) void svm_rows_kernel(SvmRowsArgs a) {
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int64_t wv = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wv >= a.tile_off[a.P]) return;
+    int lo = 0, hi = a.P - 1;                 // the problem whose tiles hold wv
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.tile_off[mid] <= wv) lo = mid; else hi = mid - 1;
+    }
+    const int p = lo;
+    if (a.active && !a.active[p]) return;
+    const int nr = a.nrows ? a.nrows[p] : a.nrows_all;
+    if (nr <= 0) return;
+    const int64_t c0 = a.col_off[p];
+    const int ncol = (int)(a.col_off[p + 1] - c0);
+    const int col = (int)(wv - a.tile_off[p]) * 32 + r;
+    const bool cv = col < ncol;
+    const int cg = cv ? a.cidx[c0 + col] : 0;
+    const float* xc = a.x + (int64_t)cg * a.D;
+    const float ycn = cv ? a.xx[cg] : 0.f;
+    const int* rows = a.ridx + (int64_t)p * a.rstride;
+    float* out = a.out + (int64_t)a.rstride * c0;
+    for (int g0 = 0; g0 < nr; g0 += 128) {
+        const int nt = min(4, (nr - g0 + 31) >> 5);
+        const float* xr[4];
+        bool rv[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int w = g0 + t * 32 + r;
+            rv[t] = t < nt && w < nr;
+            xr[t] = a.x + (rv[t] ? (int64_t)rows[w] * a.D : 0);
+        }
+        f32x16 acc[4] = {};
+        for (int k0 = 0; k0 < a.D; k0 += 8) {
+            const int kk = k0 + 4 * h;
+            float bv[4];
+            if (a.vec && kk + 4 <= a.D) {
+                const float4 qv = cv ? *reinterpret_cast<const float4*>(xc + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+                bv[0] = qv.x, bv[1] = qv.y, bv[2] = qv.z, bv[3] = qv.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) bv[j] = (cv && kk + j < a.D) ? xc[kk + j] : 0.f;
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (t >= nt) break;
+                float av[4];
+                if (a.vec && kk + 4 <= a.D) {
+                    const float4 qv = rv[t] ? *reinterpret_cast<const float4*>(xr[t] + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    av[0] = qv.x, av[1] = qv.y, av[2] = qv.z, av[3] = qv.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) av[j] = (rv[t] && kk + j < a.D) ? xr[t][kk + j] : 0.f;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc[t], 0, 0, 0);
+            }
+        }
+        if (!cv) continue;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (t >= nt) break;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int w = g0 + t * 32 + mfma_row(i, h);
+                if (w < nr) out[(int64_t)w * ncol + col] = kfun(a.k, acc[t][i], a.xx[rows[w]], ycn);
+            }
+        }
+    }
+}
+
+// ---- block reductions (argmax with a deterministic tie rule) -------------------------------------------------------------
+// (v, i) beats (w, j) when v > w, or v == w and i > j (libsvm's ">=" scans keep the LAST index of a tie)
+__device__ __forceinline__ void argmax_pair(double& v, int& i, double w, int j) {
+    if (w > v || (w == v && j > i)) v = w, i = j;
+}
+template <int NT>
+__device__ void block_argmax(double& v, int& i, double* sv, int* si) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double w = __shfl_xor(v, o);
+        const int j = __shfl_xor(i, o);
+        argmax_pair(v, i, w, j);
+    }
+    const int wid = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sv[wid] = v, si[wid] = i;
+    __syncthreads();
+    v = sv[0], i = si[0];
+    for (int k = 1; k < NT / 64; ++k) argmax_pair(v, i, sv[k], si[k]);
+}
+
+// ---- working-set selection -------------------------------------------------------------------------------------------------
+struct SvmState {
+    const float* x;
+    const int64_t* off;          // problem p's entries: [off[p], off[p + 1])
+    const int* idx;              // global row of each entry
+    const signed char* y;        // +1 / -1
+    double *alpha, *grad;
+    int *wsl, *wsg, *nws;        // per problem: q local / global working-set rows, their count
+    double* dal;                 // per problem: q alpha changes of the last local solve
+    int* active;
+    long long* updates;          // local SMO updates so far
+    int* outer;
+    double *gap, *rho;
+    float* krow;                 // problem p: q * off[p], row w at w * n_p + t
+    const int64_t *tile32, *tile256;
+    double C, tol, local_rel;
+    long long max_updates;       // per problem (-1: libsvm's cap, resolved on the host)
+    int P, q, outer_cap;
+};
+
+__device__ __forceinline__ bool in_up(signed char y, double a, double C) { return y > 0 ? a < C : a > 0.0; }
+__device__ __forceinline__ bool in_low(signed char y, double a, double C) { return y > 0 ? a > 0.0 : a < C; }
+
+constexpr int SEL_NT = 512;
+__global__ __launch_bounds__(SEL_NT) void svm_select_kernel(SvmState s) {
+    __shared__ double sv[SEL_NT / 64];
+    __shared__ int si[SEL_NT / 64];
+    __shared__ int ups[SVM_QMAX / 2], lows[SVM_QMAX / 2];
+    const int p = blockIdx.x;
+    if (!s.active[p]) return;
+    const int64_t off = s.off[p];
+    const int n = (int)(s.off[p + 1] - off);
+    const double* G = s.grad + off;
+    const double* A = s.alpha + off;
+    const signed char* Y = s.y + off;
+    const int half = s.q / 2;
+    // picks leave in the order (key desc, index asc) for I_up and (key asc, index asc) for I_low; the previous pick bounds the next
+    double pu = INFINITY, pl = -INFINITY;
+    int pui = -1, pli = -1, nu = 0, nl = 0;
+    for (int rnd = 0; rnd < half; ++rnd) {
+        double bu = -INFINITY, bl = -INFINITY;       // bl holds -key so that both sides reduce as argmax
+        int bui = -1, bli = -1;
+        for (int t = threadIdx.x; t < n; t += SEL_NT) {
+            const signed char yt = Y[t];
+            const double a = A[t], key = -(double)yt * G[t];
+            if (pui != -2 && in_up(yt, a, s.C) && (key < pu || (key == pu && t > pui)))
+                if (bui < 0 || key > bu || (key == bu && t < bui)) bu = key, bui = t;
+            if (pli != -2 && in_low(yt, a, s.C) && (key > pl || (key == pl && t > pli)))
+                if (bli < 0 || -key > bl || (-key == bl && t < bli)) bl = -key, bli = t;
+        }
+        // argmax_pair prefers the larger index on equal keys; the scan above kept the smaller, so reduce on -index
+        int nbu = bui < 0 ? INT_MIN : -bui, nbl = bli < 0 ? INT_MIN : -bli;
+        if (bui < 0) bu = -INFINITY;
+        if (bli < 0) bl = -INFINITY;
+        block_argmax<SEL_NT>(bu, nbu, sv, si);
+        block_argmax<SEL_NT>(bl, nbl, sv, si);
+        bui = nbu == INT_MIN ? -1 : -nbu;
+        bli = nbl == INT_MIN ? -1 : -nbl;
+        if (rnd == 0) {
+            const double gap = (bui < 0 || bli < 0) ? -INFINITY : bu + bl;     // m(alpha) - M(alpha)
+            const bool capped = s.updates[p] >= s.max_updates || s.outer[p] >= s.outer_cap;
+            if (gap < s.tol || capped) {
+                if (threadIdx.x == 0) s.active[p] = 0, s.gap[p] = gap, s.nws[p] = 0;
+                return;
+            }
+            if (threadIdx.x == 0) s.gap[p] = gap;
+        }
+        if (threadIdx.x == 0) {
+            if (bui >= 0) ups[nu] = bui;
+            if (bli >= 0) lows[nl] = bli;
+        }
+        nu += bui >= 0, nl += bli >= 0;
+        if (bui >= 0) pu = bu, pui = bui; else pui = -2;        // -2: that side is exhausted
+        if (bli >= 0) pl = -bl, pli = bli; else pli = -2;
+        if (pui == -2 && pli == -2) break;
+        __syncthreads();
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        // the union of both lists (a free variable may sit in both)
+        int* wl = s.wsl + (int64_t)p * s.q;
+        int* wg = s.wsg + (int64_t)p * s.q;
+        int c = 0;
+        for (int i = 0; i < nu; ++i) wl[c++] = ups[i];
+        for (int i = 0; i < nl; ++i) {
+            bool dup = false;
+            for (int j = 0; j < nu; ++j) dup |= ups[j] == lows[i];
+            if (!dup) wl[c++] = lows[i];
+        }
+        for (int i = 0; i < c; ++i) wg[i] = s.idx[off + wl[i]];
+        s.nws[p] = c;
+        s.outer[p] += 1;
+    }
+}
+
+// ---- local SMO: one workgroup per problem, one thread per working-set variable --------------------------------------------------
+// libsvm's Solver::select_working_set (WSS3) and its two-variable update, on the q x q block in LDS.  The solve stops when the
+// local gap falls below max(eps, local_rel * first local gap), when no pair can move, or at the update cap.
+struct SvmSmoArgs {
+    const float* K;               // problem p's rows: K + koff, ld n_p (or the q x q block itself for the operator)
+    const int64_t* off;
+    const int* wsl;
+    const int* nws;
+    const signed char* y;
+    double *alpha;                // in / out
+    const double* grad;
+    double* dal;                  // out: alpha change per variable
+    long long* updates;           // in / out, per problem
+    int* active;                  // may be NULL (operator)
+    double C, eps, local_rel;
+    long long max_updates;
+    int q, ldk_is_n;
+};
+
+constexpr int SMO_NT = SVM_QMAX;
+__global__ __launch_bounds__(SMO_NT) void svm_smo_kernel(SvmSmoArgs a) {
+    __shared__ float Kb[SVM_QMAX * SVM_QMAX];
+    __shared__ double sv[SMO_NT / 64], Av[SVM_QMAX];
+    __shared__ int si[SMO_NT / 64];
+    __shared__ double upd_a[2], gij[2];
+    const int p = blockIdx.x;
+    if (a.active && !a.active[p]) return;
+    const int nw = a.nws[p];
+    if (nw <= 0) return;
+    const int64_t off = a.off[p];
+    const int n = (int)(a.off[p + 1] - off);
+    const int ld = a.ldk_is_n ? n : nw;
+    const float* Kp = a.K + (int64_t)a.q * off;
+    const int* wl = a.wsl + (int64_t)p * a.q;
+    for (int e = threadIdx.x; e < nw * nw; e += SMO_NT) {
+        const int w = e / nw, v = e - w * nw;
+        Kb[w * SVM_QMAX + v] = Kp[(int64_t)w * ld + wl[v]];
+    }
+    const int k = threadIdx.x;
+    const bool kv = k < nw;
+    const int lk = kv ? wl[k] : 0;
+    const signed char yk = kv ? a.y[off + lk] : 1;
+    const double a0 = kv ? a.alpha[off + lk] : 0.0;
+    double ak = a0, gk = kv ? a.grad[off + lk] : 0.0;
+    if (kv) Av[k] = ak;
+    __syncthreads();
+    const double Ckk = kv ? (double)Kb[k * SVM_QMAX + k] : 0.0;
+    const long long cap = a.max_updates - a.updates[p];
+    long long upd = 0;
+    double local_eps = a.eps;
+    for (int it = 0;; ++it) {
+        // i = argmax over I_up of -y G
+        double vi = (kv && in_up(yk, ak, a.C)) ? -(double)yk * gk : -INFINITY;
+        int ii = (kv && in_up(yk, ak, a.C)) ? k : -1;
+        block_argmax<SMO_NT>(vi, ii, sv, si);
+        const double Gmax = vi;
+        // j: Gmax2 = max over I_low of y G; the second-order choice among I_low with grad_diff > 0
+        double g2 = (kv && in_low(yk, ak, a.C)) ? (double)yk * gk : -INFINITY;
+        int g2i = (kv && in_low(yk, ak, a.C)) ? k : -1;
+        double ob = -INFINITY;      // -obj_diff, as argmax
+        int oj = -1;
+        if (ii >= 0 && kv && in_low(yk, ak, a.C)) {
+            const double gd = Gmax + (double)yk * gk;
+            if (gd > 0.0) {
+                double quad = (double)Kb[ii * SVM_QMAX + ii] + Ckk - 2.0 * (double)Kb[ii * SVM_QMAX + k];
+                if (!(quad > 0.0)) quad = SVM_TAU;
+                ob = gd * gd / quad, oj = k;
+            }
+        }
+        block_argmax<SMO_NT>(g2, g2i, sv, si);
+        block_argmax<SMO_NT>(ob, oj, sv, si);
+        const double gap = (ii < 0 || g2i < 0) ? -INFINITY : Gmax + g2;
+        if (it == 0) local_eps = fmax(a.eps, a.local_rel * gap);
+        if (ii < 0 || oj < 0 || gap < local_eps || upd >= cap) break;
+        const int i = ii, j = oj;
+        // the two gradients the update reads, from their owners; then libsvm's two-variable update (Solver::Solve) by thread 0
+        if (k == i) gij[0] = gk;
+        if (k == j) gij[1] = gk;
+        __syncthreads();
+        if (k == 0) {
+            const double Kii = Kb[i * SVM_QMAX + i], Kjj = Kb[j * SVM_QMAX + j], Kij = Kb[i * SVM_QMAX + j];
+            const signed char yi = a.y[off + wl[i]], yj = a.y[off + wl[j]];
+            const double Gi = gij[0], Gj = gij[1];
+            double ai = Av[i], aj = Av[j];
+            const double C = a.C;
+            if (yi != yj) {
+                double quad = Kii + Kjj + 2.0 * (-(Kij));       // QD_i + QD_j + 2 Q_ij, Q_ij = y_i y_j K_ij = -K_ij
+                if (quad <= 0.0) quad = SVM_TAU;
+                const double delta = (-Gi - Gj) / quad;
+                const double diff = ai - aj;
+                ai += delta;
+                aj += delta;
+                if (diff > 0) {
+                    if (aj < 0) aj = 0, ai = diff;
+                } else {
+                    if (ai < 0) ai = 0, aj = -diff;
+                }
+                if (diff > 0.0) {        // C_i - C_j = 0
+                    if (ai > C) ai = C, aj = C - diff;
+                } else {
+                    if (aj > C) aj = C, ai = C + diff;
+                }
+            } else {
+                double quad = Kii + Kjj - 2.0 * Kij;
+                if (quad <= 0.0) quad = SVM_TAU;
+                const double delta = (Gi - Gj) / quad;
+                const double sum = ai + aj;
+                ai -= delta;
+                aj += delta;
+                if (sum > C) {
+                    if (ai > C) ai = C, aj = sum - C;
+                } else {
+                    if (aj < 0) aj = 0, ai = sum;
+                }
+                if (sum > C) {
+                    if (aj > C) aj = C, ai = sum - C;
+                } else {
+                    if (ai < 0) ai = 0, aj = sum;
+                }
+            }
+            upd_a[0] = ai - Av[i];
+            upd_a[1] = aj - Av[j];
+            Av[i] = ai, Av[j] = aj;
+        }
+        __syncthreads();
+        if (kv) {
+            const double di = upd_a[0], dj = upd_a[1];
+            const signed char yi = a.y[off + wl[i]], yj = a.y[off + wl[j]];
+            const double qki = (double)(yk * yi) * (double)Kb[k * SVM_QMAX + i];
+            const double qkj = (double)(yk * yj) * (double)Kb[k * SVM_QMAX + j];
+            gk += qki * di + qkj * dj;
+            ak = Av[k];
+        }
+        ++upd;
+        __syncthreads();
+    }
+    if (kv) {
+        a.alpha[off + lk] = ak;
+        a.dal[(int64_t)p * a.q + k] = ak - a0;
+    }
+    if (k == 0) {
+        a.updates[p] += upd;
+        if (upd == 0 && a.active) a.active[p] = 0;      // no pair can move: the problem stalls (its gap stays >= tol)
+    }
+}
+
+// ---- gradient update: grad_t += y_t sum_s dalpha_s y_s K[s, t] --------------------------------------------------------------------
+__global__ __launch_bounds__(256) void svm_grad_kernel(SvmState s) {
+    __shared__ double dy[SVM_QMAX];
+    const int64_t b = blockIdx.x;
+    if (b >= s.tile256[s.P]) return;
+    int lo = 0, hi = s.P - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (s.tile256[mid] <= b) lo = mid; else hi = mid - 1;
+    }
+    const int p = lo;
+    if (!s.active[p]) return;
+    const int nw = s.nws[p];
+    const int64_t off = s.off[p];
+    const int n = (int)(s.off[p + 1] - off);
+    if (threadIdx.x < nw)
+        dy[threadIdx.x] = s.dal[(int64_t)p * s.q + threadIdx.x] * (double)s.y[off + s.wsl[(int64_t)p * s.q + threadIdx.x]];
+    __syncthreads();
+    const int t = (int)(b - s.tile256[p]) * 256 + threadIdx.x;
+    if (t >= n) return;
+    const float* Kp = s.krow + (int64_t)s.q * off;
+    double acc = 0.0;
+    for (int w = 0; w < nw; ++w) {
+        const double d = dy[w];
+        if (d != 0.0) acc += d * (double)Kp[(int64_t)w * n + t];
+    }
+    s.grad[off + t] += (double)s.y[off + t] * acc;
+}
+
+// ---- start state and libsvm's rho -----------------------------------------------------------------------------------------------
+__global__ void svm_init_kernel(SvmState s, int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < total) s.alpha[i] = 0.0, s.grad[i] = -1.0;
+    if (i < s.P) s.active[i] = 1, s.updates[i] = 0, s.outer[i] = 0, s.nws[i] = 0, s.gap[i] = INFINITY;
+}
+
+// Solver::calculate_rho: the mean of y G over free variables, else the middle of [lb, ub]
+__global__ __launch_bounds__(256) void svm_rho_kernel(SvmState s) {
+    __shared__ double red[3][4];
+    __shared__ long long cnt[4];
+    const int p = blockIdx.x;
+    const int64_t off = s.off[p];
+    const int n = (int)(s.off[p + 1] - off);
+    double ub = INFINITY, lb = -INFINITY, sum = 0.0;
+    long long nf = 0;
+    for (int t = threadIdx.x; t < n; t += 256) {
+        const signed char yt = s.y[off + t];
+        const double a = s.alpha[off + t], yG = (double)yt * s.grad[off + t];
+        if (a >= s.C) {
+            if (yt < 0) ub = fmin(ub, yG); else lb = fmax(lb, yG);
+        } else if (a <= 0.0) {
+            if (yt > 0) ub = fmin(ub, yG); else lb = fmax(lb, yG);
+        } else {
+            ++nf;
+            sum += yG;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ub = fmin(ub, __shfl_xor(ub, o));
+        lb = fmax(lb, __shfl_xor(lb, o));
+        sum += __shfl_xor(sum, o);
+        nf += __shfl_xor(nf, o);
+    }
+    const int wid = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) red[0][wid] = ub, red[1][wid] = lb, red[2][wid] = sum, cnt[wid] = nf;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ub = red[0][0], lb = red[1][0], sum = red[2][0], nf = cnt[0];
+        for (int w = 1; w < 4; ++w) ub = fmin(ub, red[0][w]), lb = fmax(lb, red[1][w]), sum += red[2][w], nf += cnt[w];
+        s.rho[p] = nf > 0 ? sum / (double)nf : (ub + lb) / 2.0;
+    }
+}
+
+// ---- fused decision values --------------------------------------------------------------------------------------------------
+// One single-wave workgroup per (32 test rows, class c): K(x_test, SV) tiles of class c's support vectors on the matrix cores, the kernel function
+// in registers, then S[m, c, r] = sum over the class's SVs of K * coef[r, sv] (float64) for r < R = n_class - 1.  The tile goes
+// through LDS to meet the coefficients; the kernel matrix is never written out.
+struct SvmDecArgs {
+    const float *xt, *xtn;         // test rows / their squared norms, indexed through xidx (NULL: identity)
+    const int* xidx;
+    const float *sv, *svn;         // support vectors / norms, through svidx (NULL: identity)
+    const int* svidx;
+    const int64_t* cs;             // class c's SVs: [cs[c], cs[c + 1])
+    const double* coef;            // (R, n_sv)
+    double* S;                     // (n, n_class, R)
+    int64_t n, n_sv;
+    int D, ncls, vec;
+    SvmKern k;
+};
+
+__global__ __launch_bounds__(64) void svm_decision_kernel(SvmDecArgs a) {
+    extern __shared__ unsigned char smem[];
+    const int R = a.ncls - 1;
+    const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+    float* T = reinterpret_cast<float*>(smem);
+    double* Sacc = reinterpret_cast<double*>(smem + 32 * 33 * sizeof(float));
+    const int64_t row_tiles = (a.n + 31) >> 5;
+    const int64_t wv = blockIdx.x;
+    if (wv >= row_tiles * a.ncls) return;
+    const int c = (int)(wv % a.ncls);
+    const int64_t rt = wv / a.ncls;
+    const int64_t m = rt * 32 + r;
+    const bool mv = m < a.n;
+    const int64_t mg = mv ? (a.xidx ? a.xidx[m] : m) : 0;
+    const float* xr = a.xt + mg * a.D;
+    for (int e = lane; e < 32 * R; e += 64) Sacc[e] = 0.0;
+    const int64_t s0 = a.cs[c], s1 = a.cs[c + 1];
+    for (int64_t sb = s0; sb < s1; sb += 32) {
+        const int64_t sidx = sb + r;
+        const bool sv_ok = sidx < s1;
+        const int64_t sg = sv_ok ? (a.svidx ? a.svidx[sidx] : sidx) : 0;
+        const float* svr = a.sv + sg * a.D;
+        f32x16 acc = {};
+        for (int k0 = 0; k0 < a.D; k0 += 8) {
+            const int kk = k0 + 4 * h;
+            float av[4], bv[4];
+            if (a.vec && kk + 4 <= a.D) {
+                const float4 qa = mv ? *reinterpret_cast<const float4*>(xr + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 qb = sv_ok ? *reinterpret_cast<const float4*>(svr + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+                av[0] = qa.x, av[1] = qa.y, av[2] = qa.z, av[3] = qa.w;
+                bv[0] = qb.x, bv[1] = qb.y, bv[2] = qb.z, bv[3] = qb.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    av[j] = (mv && kk + j < a.D) ? xr[kk + j] : 0.f;
+                    bv[j] = (sv_ok && kk + j < a.D) ? svr[kk + j] : 0.f;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
+        }
+        // lane (r, h) holds column r (an SV) of rows mfma_row(i, h): kernel function, then the tile to LDS as T[row][sv]
+        const float ysn = sv_ok ? a.svn[sg] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int row = mfma_row(i, h);
+            const int64_t mr = rt * 32 + row;
+            float kvv = 0.f;
+            if (sv_ok && mr < a.n) kvv = kfun(a.k, acc[i], a.xtn[a.xidx ? a.xidx[mr] : mr], ysn);
+            T[row * 33 + r] = kvv;
+        }
+        __syncthreads();
+        const int ns = (int)min<int64_t>(32, s1 - sb);
+        for (int e = lane; e < 32 * R; e += 64) {
+            const int rr = e >> 5, row = e & 31;
+            const double* cf = a.coef + (int64_t)rr * a.n_sv + sb;
+            double s = Sacc[e];
+            for (int j = 0; j < ns; ++j) s += (double)T[row * 33 + j] * cf[j];
+            Sacc[e] = s;
+        }
+        __syncthreads();
+    }
+    for (int e = lane; e < 32 * R; e += 64) {
+        const int rr = e >> 5, row = e & 31;
+        const int64_t mr = rt * 32 + row;
+        if (mr < a.n) a.S[(mr * a.ncls + c) * R + rr] = Sacc[e];
+    }
+}
+
+// pair (i, j), i < j: S[m, i, j - 1] + S[m, j, i] - rho_ij (libsvm's svm_predict_values)
+__global__ void svm_pairs_kernel(const double* S, const double* rho, int64_t n, int ncls, double* dec) {
+    const int P = ncls * (ncls - 1) / 2, R = ncls - 1;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * P) return;
+    const int64_t m = e / P;
+    int p = (int)(e - m * P), i = 0;
+    while (p >= ncls - 1 - i) p -= ncls - 1 - i, ++i;
+    const int j = i + 1 + p;
+    const int pp = (int)(e - m * P);
+    dec[e] = S[(m * ncls + i) * R + (j - 1)] + S[(m * ncls + j) * R + i] - rho[pp];
+}
+
+}  // namespace
+}  // namespace l3
+
+// ================================================================================================================================
+// l3_svm: the resident training matrix and the batched solver (include/l3hip.h)
+// ================================================================================================================================
+using namespace l3;
+
+struct l3_svm {
+    int device = 0;
+    hipStream_t s = nullptr;
+    float *x = nullptr, *xx = nullptr;
+    int64_t n = 0;
+    int D = 0;
+};
+
+namespace {
+int fail(int code, const std::string& msg) {
+    set_op_error(msg);
+    return code;
+}
+
+// device buffers of one call, freed on every return path
+struct Bufs {
+    std::vector<void*> p;
+    bool ok = true;
+    template <class T>
+    T* alloc(int64_t count) {
+        void* q = nullptr;
+        if (hipMalloc(&q, (size_t)(count > 0 ? count : 1) * sizeof(T)) != hipSuccess) {
+            ok = false;
+            return nullptr;
+        }
+        p.push_back(q);
+        return static_cast<T*>(q);
+    }
+    template <class T>
+    T* put(const T* src, int64_t count, hipStream_t s) {
+        T* d = alloc<T>(count);
+        if (d && count > 0 && hipMemcpyAsync(d, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice, s) != hipSuccess) ok = false;
+        return d;
+    }
+    ~Bufs() {
+        for (void* q : p) (void)hipFree(q);
+    }
+};
+
+bool kern_ok(const l3_svm_kernel* kp, std::string* why) {
+    if (!kp) return *why = "kernel parameters are NULL", false;
+    if (kp->kind < L3_SVM_LINEAR || kp->kind > L3_SVM_SIGMOID) return *why = "unknown kernel", false;
+    if (kp->kind == L3_SVM_POLY && (kp->degree < 0 || kp->degree > 64)) return *why = "poly degree must be in [0, 64]", false;
+    if (!std::isfinite(kp->gamma) || !std::isfinite(kp->coef0)) return *why = "gamma and coef0 must be finite", false;
+    return true;
+}
+SvmKern to_kern(const l3_svm_kernel* kp) { return SvmKern{kp->kind, kp->degree, (float)kp->gamma, (float)kp->coef0}; }
+
+bool device_ok(int device) {
+    int nd = 0;
+    return hipGetDeviceCount(&nd) == hipSuccess && device >= 0 && device < nd && hipSetDevice(device) == hipSuccess;
+}
+
+void launch_norms(const float* x, int64_t n, int D, float* xx, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(svm_norms_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, x, n, D, xx);
+}
+
+int vec_ok(const float* x, int D) { return (D % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) ? 1 : 0; }
+
+// the decision values of n rows (given on the device) in blocks bounded by the S scratch
+int decision_dev(hipStream_t s, const float* xt, const float* xtn, const int* xidx, int64_t n, const float* sv, const float* svn,
+                 const int* svidx, int64_t n_sv, int D, int ncls, const int64_t* cs_d, const double* coef_d, const double* rho_d,
+                 const SvmKern& k, double* S, int64_t rows_blk, double* dec_d) {
+    const int R = ncls - 1, P = ncls * R / 2;
+    const size_t lds = 32 * 33 * sizeof(float) + (size_t)32 * R * sizeof(double);
+    for (int64_t r0 = 0; r0 < n; r0 += rows_blk) {
+        const int64_t rows = std::min(rows_blk, n - r0);
+        SvmDecArgs a{};
+        a.xt = xidx ? xt : xt + r0 * D, a.xtn = xidx ? xtn : xtn + r0, a.xidx = xidx ? xidx + r0 : nullptr;
+        a.sv = sv, a.svn = svn, a.svidx = svidx, a.cs = cs_d, a.coef = coef_d, a.S = S, a.n = rows, a.n_sv = n_sv;
+        a.D = D, a.ncls = ncls, a.k = k;
+        a.vec = vec_ok(sv, D) & vec_ok(xt, D);
+        const int64_t waves = ((rows + 31) / 32) * ncls;
+        hipLaunchKernelGGL(svm_decision_kernel, dim3((unsigned)waves), dim3(64), lds, s, a);
+        const int64_t e = rows * P;
+        hipLaunchKernelGGL(svm_pairs_kernel, dim3((unsigned)((e + 255) / 256)), dim3(256), 0, s, S, rho_d, rows, ncls, dec_d + r0 * P);
+    }
+    return hipGetLastError() == hipSuccess ? L3_OK : fail(L3_EHIP, "l3_svm: decision launch failed");
+}
+
+int64_t prefix_tiles(const std::vector<int64_t>& off, int per, std::vector<int64_t>* tiles) {
+    const size_t P = off.size() - 1;
+    tiles->assign(P + 1, 0);
+    for (size_t p = 0; p < P; ++p) (*tiles)[p + 1] = (*tiles)[p] + (off[p + 1] - off[p] + per - 1) / per;
+    return (*tiles)[P];
+}
+}  // namespace
+
+extern "C" {
+
+int l3_svm_create(int device, l3_svm** out) {
+    if (!out) return fail(L3_EINVAL, "l3_svm_create: out is NULL");
+    *out = nullptr;
+    if (!device_ok(device))
+        return fail(L3_EHIP, "l3_svm_create: HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)");
+    l3_svm* m = new l3_svm();
+    m->device = device;
+    if (hipStreamCreateWithFlags(&m->s, hipStreamNonBlocking) != hipSuccess) {
+        delete m;
+        return fail(L3_EHIP, "l3_svm_create: stream creation failed");
+    }
+    *out = m;
+    return L3_OK;
+}
+
+void l3_svm_destroy(l3_svm* m) {
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    if (m->s) (void)hipStreamSynchronize(m->s);
+    if (m->x) (void)hipFree(m->x);
+    if (m->xx) (void)hipFree(m->xx);
+    if (m->s) (void)hipStreamDestroy(m->s);
+    delete m;
+}
+
+int l3_svm_set_data(l3_svm* m, const float* X, int64_t n, int D) {
+    if (!m || !X) return fail(L3_EINVAL, "l3_svm_set_data: NULL argument");
+    if (n <= 0 || n > INT32_MAX || D <= 0 || D > (1 << 24)) return fail(L3_EINVAL, "l3_svm_set_data: need 1 <= n < 2^31, 1 <= D <= 2^24");
+    (void)hipSetDevice(m->device);
+    (void)hipStreamSynchronize(m->s);
+    if (m->x) (void)hipFree(m->x), m->x = nullptr;
+    if (m->xx) (void)hipFree(m->xx), m->xx = nullptr;
+    m->n = 0;
+    if (hipMalloc(&m->x, (size_t)n * D * sizeof(float)) != hipSuccess || hipMalloc(&m->xx, (size_t)n * sizeof(float)) != hipSuccess)
+        return fail(L3_ENOMEM, "l3_svm_set_data: device allocation of " + std::to_string(n * D * 4) + " bytes failed");
+    if (hipMemcpyAsync(m->x, X, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, m->s) != hipSuccess)
+        return fail(L3_EHIP, "l3_svm_set_data: copy to the device failed");
+    launch_norms(m->x, n, D, m->xx, m->s);
+    if (hipStreamSynchronize(m->s) != hipSuccess) return fail(L3_EHIP, "l3_svm_set_data: HIP error");
+    m->n = n, m->D = D;
+    return L3_OK;
+}
+
+int l3_svm_fit(l3_svm* m, const l3_svm_kernel* kp, double C, double tol, int64_t max_iter, int n_prob, const int64_t* prob_off,
+               const int32_t* rows, const int8_t* signs, int q, double* alpha_out, double* rho_out, int64_t* updates_out,
+               int32_t* outer_out, double* gap_out) {
+    std::string why;
+    if (!m || !prob_off || !rows || !signs || !alpha_out || !rho_out) return fail(L3_EINVAL, "l3_svm_fit: NULL argument");
+    if (!kern_ok(kp, &why)) return fail(L3_EINVAL, "l3_svm_fit: " + why);
+    if (m->n <= 0) return fail(L3_ESTATE, "l3_svm_fit: no training data (l3_svm_set_data)");
+    if (!(C > 0.0) || !std::isfinite(C) || !(tol > 0.0)) return fail(L3_EINVAL, "l3_svm_fit: need C > 0 and tol > 0");
+    if (n_prob <= 0) return fail(L3_EINVAL, "l3_svm_fit: no problems");
+    if (q == 0) q = L3_SVM_DEFAULT_WS;
+    if (q < 2 || q > SVM_QMAX || (q & 1)) return fail(L3_EINVAL, "l3_svm_fit: working-set size must be even, in [2, 128]");
+    if (prob_off[0] != 0) return fail(L3_EINVAL, "l3_svm_fit: prob_off[0] must be 0");
+    for (int p = 0; p < n_prob; ++p)
+        if (prob_off[p + 1] - prob_off[p] < 2) return fail(L3_EINVAL, "l3_svm_fit: problem " + std::to_string(p) + " has < 2 rows");
+    const int64_t total = prob_off[n_prob];
+    for (int64_t i = 0; i < total; ++i) {
+        if (rows[i] < 0 || rows[i] >= m->n) return fail(L3_EINVAL, "l3_svm_fit: rows[" + std::to_string(i) + "] outside [0, n)");
+        if (signs[i] != 1 && signs[i] != -1) return fail(L3_EINVAL, "l3_svm_fit: signs must be +1 or -1");
+    }
+    (void)hipSetDevice(m->device);
+    const std::vector<int64_t> off(prob_off, prob_off + n_prob + 1);
+    std::vector<int64_t> t32, t256;
+    const int64_t n32 = prefix_tiles(off, 32, &t32), n256 = prefix_tiles(off, 256, &t256);
+    Bufs b;
+    SvmState st{};
+    st.x = m->x;
+    st.off = b.put(off.data(), n_prob + 1, m->s);
+    st.idx = b.put(rows, total, m->s);
+    st.y = reinterpret_cast<const signed char*>(b.put(signs, total, m->s));
+    st.alpha = b.alloc<double>(total), st.grad = b.alloc<double>(total);
+    st.wsl = b.alloc<int>((int64_t)n_prob * q), st.wsg = b.alloc<int>((int64_t)n_prob * q), st.nws = b.alloc<int>(n_prob);
+    st.dal = b.alloc<double>((int64_t)n_prob * q);
+    st.active = b.alloc<int>(n_prob), st.updates = b.alloc<long long>(n_prob), st.outer = b.alloc<int>(n_prob);
+    st.gap = b.alloc<double>(n_prob), st.rho = b.alloc<double>(n_prob);
+    st.krow = b.alloc<float>(total * q);
+    st.tile32 = b.put(t32.data(), n_prob + 1, m->s), st.tile256 = b.put(t256.data(), n_prob + 1, m->s);
+    if (!b.ok) return fail(L3_ENOMEM, "l3_svm_fit: device allocation failed (" + std::to_string(total * q * 4) + " bytes of kernel rows)");
+    st.C = C, st.tol = tol, st.local_rel = L3_SVM_LOCAL_REL, st.P = n_prob, st.q = q;
+    // libsvm's cap when max_iter is -1: max(10^7, 100 l) updates; the largest problem sets it for all
+    int64_t nmax = 0;
+    for (int p = 0; p < n_prob; ++p) nmax = std::max(nmax, off[p + 1] - off[p]);
+    st.max_updates = max_iter > 0 ? max_iter : std::max<int64_t>(10000000, 100 * nmax);
+    st.outer_cap = 1 << 24;
+    hipLaunchKernelGGL(svm_init_kernel, dim3((unsigned)((std::max<int64_t>(total, n_prob) + 255) / 256)), dim3(256), 0, m->s, st,
+                       total);
+    SvmRowsArgs ra{};
+    ra.x = m->x, ra.xx = m->xx, ra.ridx = st.wsg, ra.nrows = st.nws, ra.cidx = st.idx, ra.col_off = st.off, ra.tile_off = st.tile32;
+    ra.active = st.active, ra.out = st.krow, ra.P = n_prob, ra.rstride = q, ra.D = m->D, ra.vec = vec_ok(m->x, m->D), ra.k = to_kern(kp);
+    SvmSmoArgs sa{};
+    sa.K = st.krow, sa.off = st.off, sa.wsl = st.wsl, sa.nws = st.nws, sa.y = st.y, sa.alpha = st.alpha, sa.grad = st.grad;
+    sa.dal = st.dal, sa.updates = st.updates, sa.active = st.active, sa.C = C, sa.eps = tol, sa.local_rel = L3_SVM_LOCAL_REL;
+    sa.max_updates = st.max_updates, sa.q = q, sa.ldk_is_n = 1;
+    std::vector<int> act(n_prob);
+    for (;;) {
+        hipLaunchKernelGGL(svm_select_kernel, dim3(n_prob), dim3(SEL_NT), 0, m->s, st);
+        hipLaunchKernelGGL(svm_rows_kernel, dim3((unsigned)((n32 + 3) / 4)), dim3(256), 0, m->s, ra);
+        hipLaunchKernelGGL(svm_smo_kernel, dim3(n_prob), dim3(SMO_NT), 0, m->s, sa);
+        hipLaunchKernelGGL(svm_grad_kernel, dim3((unsigned)n256), dim3(256), 0, m->s, st);
+        if (hipGetLastError() != hipSuccess) return fail(L3_EHIP, "l3_svm_fit: launch failed");
+        // the one synchronisation of the outer iteration, for all problems
+        if (hipMemcpyAsync(act.data(), st.active, n_prob * sizeof(int), hipMemcpyDeviceToHost, m->s) != hipSuccess ||
+            hipStreamSynchronize(m->s) != hipSuccess)
+            return fail(L3_EHIP, "l3_svm_fit: HIP error in the solver");
+        bool any = false;
+        for (int p = 0; p < n_prob; ++p) any |= act[p] != 0;
+        if (!any) break;
+    }
+    hipLaunchKernelGGL(svm_rho_kernel, dim3(n_prob), dim3(256), 0, m->s, st);
+    std::vector<long long> upd(n_prob);
+    if (hipMemcpyAsync(alpha_out, st.alpha, total * sizeof(double), hipMemcpyDeviceToHost, m->s) != hipSuccess ||
+        hipMemcpyAsync(rho_out, st.rho, n_prob * sizeof(double), hipMemcpyDeviceToHost, m->s) != hipSuccess ||
+        hipMemcpyAsync(upd.data(), st.updates, n_prob * sizeof(long long), hipMemcpyDeviceToHost, m->s) != hipSuccess ||
+        (outer_out && hipMemcpyAsync(outer_out, st.outer, n_prob * sizeof(int), hipMemcpyDeviceToHost, m->s) != hipSuccess) ||
+        (gap_out && hipMemcpyAsync(gap_out, st.gap, n_prob * sizeof(double), hipMemcpyDeviceToHost, m->s) != hipSuccess) ||
+        hipStreamSynchronize(m->s) != hipSuccess)
+        return fail(L3_EHIP, "l3_svm_fit: copy from the device failed");
+    if (updates_out)
+        for (int p = 0; p < n_prob; ++p) updates_out[p] = upd[p];
+    return L3_OK;
+}
+
+int l3_svm_decision(l3_svm* m, const l3_svm_kernel* kp, const float* X, const int32_t* x_idx, int64_t n, int D, const float* SV,
+                    const int32_t* sv_idx, int64_t n_sv, int n_class, const int64_t* sv_start, const double* coef, const double* rho,
+                    double* dec_out) {
+    std::string why;
+    if (!m || !sv_start || !coef || !rho || !dec_out || n <= 0) return fail(L3_EINVAL, "l3_svm_decision: NULL argument or n <= 0");
+    if (!kern_ok(kp, &why)) return fail(L3_EINVAL, "l3_svm_decision: " + why);
+    if (n_class < 2 || n_class > SVM_MAX_CLASSES) return fail(L3_EINVAL, "l3_svm_decision: class count must be in [2, 64]");
+    if ((!X) == (!x_idx) || (!SV) == (!sv_idx)) return fail(L3_EINVAL, "l3_svm_decision: give rows either as a matrix or as indices");
+    if ((x_idx || sv_idx) && (m->n <= 0 || D != m->D)) return fail(L3_ESTATE, "l3_svm_decision: indices need the resident matrix of D columns");
+    if (D <= 0 || D > (1 << 24) || n_sv < 0 || n > INT32_MAX) return fail(L3_EINVAL, "l3_svm_decision: bad sizes");
+    if (sv_start[0] != 0 || sv_start[n_class] != n_sv) return fail(L3_EINVAL, "l3_svm_decision: sv_start must run from 0 to n_sv");
+    for (int c = 0; c < n_class; ++c)
+        if (sv_start[c + 1] < sv_start[c]) return fail(L3_EINVAL, "l3_svm_decision: sv_start must not decrease");
+    if (x_idx)
+        for (int64_t i = 0; i < n; ++i)
+            if (x_idx[i] < 0 || x_idx[i] >= m->n) return fail(L3_EINVAL, "l3_svm_decision: x_idx outside [0, n)");
+    if (sv_idx)
+        for (int64_t i = 0; i < n_sv; ++i)
+            if (sv_idx[i] < 0 || sv_idx[i] >= m->n) return fail(L3_EINVAL, "l3_svm_decision: sv_idx outside [0, n)");
+    (void)hipSetDevice(m->device);
+    const int R = n_class - 1, P = n_class * R / 2;
+    int64_t rows_blk = std::min<int64_t>({65536, (int64_t(64) << 20) / D, (int64_t(32) << 20) / ((int64_t)n_class * R)});
+    rows_blk = std::max<int64_t>(32, rows_blk & ~int64_t(31));
+    Bufs b;
+    const float *sv = m->x, *svn = m->xx;
+    const int* svi = nullptr;
+    if (SV) {
+        float* d = b.put(SV, n_sv * D, m->s);
+        float* dn = b.alloc<float>(n_sv);
+        if (b.ok) launch_norms(d, n_sv, D, dn, m->s);
+        sv = d, svn = dn;
+    } else {
+        svi = b.put(sv_idx, n_sv, m->s);
+    }
+    const int64_t* cs = b.put(sv_start, n_class + 1, m->s);
+    const double* cf = b.put(coef, (int64_t)R * n_sv, m->s);
+    const double* rh = b.put(rho, P, m->s);
+    double* S = b.alloc<double>(std::min(rows_blk, n) * n_class * R);
+    double* dec = b.alloc<double>(n * P);
+    if (!b.ok) return fail(L3_ENOMEM, "l3_svm_decision: device allocation failed");
+    const SvmKern k = to_kern(kp);
+    int rc = L3_OK;
+    if (x_idx) {
+        const int* xi = b.put(x_idx, n, m->s);
+        if (!b.ok) return fail(L3_ENOMEM, "l3_svm_decision: device allocation failed");
+        rc = decision_dev(m->s, m->x, m->xx, xi, n, sv, svn, svi, n_sv, D, n_class, cs, cf, rh, k, S, rows_blk, dec);
+    } else {
+        // host rows staged in blocks
+        const int64_t blk = std::min(rows_blk, n);
+        float* xt = b.alloc<float>(blk * D);
+        float* xtn = b.alloc<float>(blk);
+        if (!b.ok) return fail(L3_ENOMEM, "l3_svm_decision: device allocation failed");
+        for (int64_t r0 = 0; r0 < n && rc == L3_OK; r0 += blk) {
+            const int64_t rows = std::min(blk, n - r0);
+            if (hipMemcpyAsync(xt, X + r0 * D, (size_t)rows * D * sizeof(float), hipMemcpyHostToDevice, m->s) != hipSuccess)
+                return fail(L3_EHIP, "l3_svm_decision: copy to the device failed");
+            launch_norms(xt, rows, D, xtn, m->s);
+            rc = decision_dev(m->s, xt, xtn, nullptr, rows, sv, svn, svi, n_sv, D, n_class, cs, cf, rh, k, S, rows_blk, dec + r0 * P);
+        }
+    }
+    if (rc != L3_OK) return rc;
+    if (hipMemcpyAsync(dec_out, dec, (size_t)n * P * sizeof(double), hipMemcpyDeviceToHost, m->s) != hipSuccess ||
+        hipStreamSynchronize(m->s) != hipSuccess)
+        return fail(L3_EHIP, "l3_svm_decision: HIP error");
+    return L3_OK;
+}
+
+int l3_op_svm_kernel_rows(int device, const l3_svm_kernel* kp, const float* x, int64_t n_x, int D, const int32_t* a_idx, int na,
+                          const int32_t* b_idx, int nb, float* out) {
+    std::string why;
+    if (!x || !a_idx || !b_idx || !out || n_x <= 0 || na <= 0 || nb <= 0 || D <= 0 || D > (1 << 24))
+        return fail(L3_EINVAL, "l3_op_svm_kernel_rows: NULL pointer or non-positive size");
+    if (!kern_ok(kp, &why)) return fail(L3_EINVAL, "l3_op_svm_kernel_rows: " + why);
+    for (int i = 0; i < na; ++i)
+        if (a_idx[i] < 0 || a_idx[i] >= n_x) return fail(L3_EINVAL, "l3_op_svm_kernel_rows: a_idx outside [0, n_x)");
+    for (int i = 0; i < nb; ++i)
+        if (b_idx[i] < 0 || b_idx[i] >= n_x) return fail(L3_EINVAL, "l3_op_svm_kernel_rows: b_idx outside [0, n_x)");
+    if (!device_ok(device)) return fail(L3_EHIP, "l3_op_svm_kernel_rows: HIP device not available (libl3hip needs an AMD GPU)");
+    Bufs b;
+    hipStream_t s = nullptr;
+    const float* dx = b.put(x, n_x * D, s);
+    float* dxx = b.alloc<float>(n_x);
+    const int* da = b.put(a_idx, na, s);
+    const int* db = b.put(b_idx, nb, s);
+    const int64_t off[2] = {0, nb}, tiles[2] = {0, (nb + 31) / 32};
+    const int64_t* doff = b.put(off, 2, s);
+    const int64_t* dt = b.put(tiles, 2, s);
+    float* dout = b.alloc<float>((int64_t)na * nb);
+    if (!b.ok) return fail(L3_ENOMEM, "l3_op_svm_kernel_rows: device allocation failed");
+    launch_norms(dx, n_x, D, dxx, s);
+    SvmRowsArgs ra{};
+    ra.x = dx, ra.xx = dxx, ra.ridx = da, ra.nrows = nullptr, ra.nrows_all = na, ra.cidx = db, ra.col_off = doff, ra.tile_off = dt;
+    ra.active = nullptr, ra.out = dout, ra.P = 1, ra.rstride = na, ra.D = D, ra.vec = vec_ok(dx, D), ra.k = to_kern(kp);
+    hipLaunchKernelGGL(svm_rows_kernel, dim3((unsigned)((tiles[1] + 3) / 4)), dim3(256), 0, s, ra);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(out, dout, (size_t)na * nb * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return fail(L3_EHIP, "l3_op_svm_kernel_rows: HIP error");
+    return L3_OK;
+}
+
+int l3_op_svm_smo(int device, const float* K, const int8_t* y, int q, double C, double eps, double local_rel, int64_t max_updates,
+                  double* alpha, const double* grad, int64_t* updates_out) {
+    if (!K || !y || !alpha || !grad || q < 2 || q > SVM_QMAX) return fail(L3_EINVAL, "l3_op_svm_smo: NULL pointer or q outside [2, 128]");
+    if (!(C > 0.0) || !(eps > 0.0) || !(local_rel >= 0.0)) return fail(L3_EINVAL, "l3_op_svm_smo: need C > 0, eps > 0, local_rel >= 0");
+    for (int i = 0; i < q; ++i) {
+        if (y[i] != 1 && y[i] != -1) return fail(L3_EINVAL, "l3_op_svm_smo: y must be +1 or -1");
+        if (!(alpha[i] >= 0.0 && alpha[i] <= C)) return fail(L3_EINVAL, "l3_op_svm_smo: alpha outside [0, C]");
+    }
+    if (!device_ok(device)) return fail(L3_EHIP, "l3_op_svm_smo: HIP device not available (libl3hip needs an AMD GPU)");
+    Bufs b;
+    hipStream_t s = nullptr;
+    std::vector<int> wl(q);
+    for (int i = 0; i < q; ++i) wl[i] = i;
+    const int64_t off[2] = {0, q};
+    const long long zero = 0;
+    SvmSmoArgs sa{};
+    sa.K = b.put(K, (int64_t)q * q, s);
+    sa.off = b.put(off, 2, s);
+    sa.wsl = b.put(wl.data(), q, s);
+    sa.nws = b.put(&q, 1, s);
+    sa.y = reinterpret_cast<const signed char*>(b.put(y, q, s));
+    double* da = b.put(alpha, q, s);
+    sa.alpha = da;
+    sa.grad = b.put(grad, q, s);
+    sa.dal = b.alloc<double>(q);
+    long long* du = b.put(&zero, 1, s);
+    sa.updates = du;
+    if (!b.ok) return fail(L3_ENOMEM, "l3_op_svm_smo: device allocation failed");
+    sa.active = nullptr, sa.C = C, sa.eps = eps, sa.local_rel = local_rel;
+    sa.max_updates = max_updates > 0 ? max_updates : (long long)1 << 62;
+    sa.q = q, sa.ldk_is_n = 1;
+    hipLaunchKernelGGL(svm_smo_kernel, dim3(1), dim3(SMO_NT), 0, s, sa);
+    long long u = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(alpha, da, q * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(&u, du, sizeof(u), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return fail(L3_EHIP, "l3_op_svm_smo: HIP error");
+    if (updates_out) *updates_out = u;
+    return L3_OK;
+}
+
+}  // extern "C"

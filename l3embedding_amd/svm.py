@@ -1,0 +1,354 @@
+"""The reference's SVM sound classifier (classifier/train.py:79-166): sklearn.svm.SVC of scikit-learn 0.19.0, i.e. libsvm's C-SVC,
+trained and evaluated on the GPU through the l3_svm handle of libl3hip (csrc/svm.hip).
+
+Here are the multiclass shell and probability estimates of libsvm's svm_train / svm_predict_probability (svm.cpp): one-vs-one
+pairs, support vectors grouped by class with the (C - 1, n_SV) coefficient matrix, the vote, Platt scaling fitted on 5-fold
+cross-validation decision values, and pairwise coupling.  Every binary problem (the pairs and their cross-validation
+sub-problems) goes through the GPU solver in one batched call; the sigmoid fit and the coupling stay on the host in NumPy.
+
+Deviations from sklearn 0.19 / libsvm, all deliberate:
+  * the cross-validation fold permutation of probability estimates is drawn from np.random.RandomState(random_state) (libsvm
+    uses the C library's rand()), as the MLP's epoch shuffle is;
+  * the solver is decomposition with working sets of q variables (libsvm's WSS3 inside each), without libsvm's shrinking heuristic
+    or kernel cache; kernel values are fp32 (libsvm also stores them as float), alpha and the gradient float64.  The solution meets
+    the same stopping test m(alpha) - M(alpha) < tol, so it agrees with libsvm's to the accuracy tol allows, not bit for bit;
+  * max_iter caps the local SMO updates per problem (the closest analogue of libsvm's iteration count);
+  * class_weight, sample weights, shrinking and cache_size are not built.
+"""
+import logging
+
+import numpy as np
+
+from . import _lib
+
+LOGGER = logging.getLogger('classifier')
+
+NR_FOLD = 5
+MIN_PROB = 1e-7
+
+
+# ---- libsvm's probability estimates (svm.cpp), float64 on the host -----------------------------------------------------------
+def _sigmoid_loss(dec, t, A, B):
+    f = dec * A + B
+    pos = f >= 0
+    out = np.empty_like(f)
+    out[pos] = t[pos] * f[pos] + np.log(1 + np.exp(-f[pos]))
+    out[~pos] = (t[~pos] - 1) * f[~pos] + np.log(1 + np.exp(f[~pos]))
+    return out.sum()
+
+
+def sigmoid_train(dec, labels):
+    """svm.cpp sigmoid_train: Platt's sigmoid fitted with the Newton method and backtracking of Lin, Lin and Weng. -> (A, B)"""
+    dec = np.asarray(dec, np.float64)
+    labels = np.asarray(labels)
+    prior1 = float((labels > 0).sum())
+    prior0 = float(labels.size - prior1)
+    max_iter, min_step, sigma, eps = 100, 1e-10, 1e-12, 1e-5
+    t = np.where(labels > 0, (prior1 + 1.0) / (prior1 + 2.0), 1 / (prior0 + 2.0))
+    A, B = 0.0, np.log((prior0 + 1.0) / (prior1 + 1.0))
+    fval = _sigmoid_loss(dec, t, A, B)
+    for _ in range(max_iter):
+        f = dec * A + B
+        e = np.exp(-np.abs(f))
+        # p = 1 / (1 + exp(f)), q = 1 - p, in the branch that keeps exp's argument <= 0
+        p = np.where(f >= 0, e / (1.0 + e), 1.0 / (1.0 + e))
+        q = np.where(f >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+        d2 = p * q
+        h11 = sigma + (dec * dec * d2).sum()
+        h22 = sigma + d2.sum()
+        h21 = (dec * d2).sum()
+        d1 = t - p
+        g1, g2 = (dec * d1).sum(), d1.sum()
+        if abs(g1) < eps and abs(g2) < eps:
+            break
+        det = h11 * h22 - h21 * h21
+        dA = -(h22 * g1 - h21 * g2) / det
+        dB = -(-h21 * g1 + h11 * g2) / det
+        gd = g1 * dA + g2 * dB
+        step = 1.0
+        while step >= min_step:
+            nA, nB = A + step * dA, B + step * dB
+            nf = _sigmoid_loss(dec, t, nA, nB)
+            if nf < fval + 0.0001 * step * gd:
+                A, B, fval = nA, nB, nf
+                break
+            step /= 2.0
+        if step < min_step:
+            LOGGER.info('Line search fails in two-class probability estimates')
+            break
+    return A, B
+
+
+def sigmoid_predict(dec, A, B):
+    """svm.cpp sigmoid_predict, elementwise"""
+    f = np.asarray(dec, np.float64) * A + B
+    e = np.exp(-np.abs(f))
+    return np.where(f >= 0, e / (1.0 + e), 1.0 / (1.0 + e))
+
+
+def multiclass_probability(r):
+    """svm.cpp multiclass_probability (method 2 of Wu, Lin and Weng), for every row at once: r (n, k, k) pairwise probabilities
+    r[i, j] = P(i | i or j) -> (n, k).  Each row iterates until its own stopping test, as libsvm does per row."""
+    r = np.asarray(r, np.float64)
+    n, k = r.shape[:2]
+    Q = np.empty((n, k, k))
+    for t in range(k):
+        others = [j for j in range(k) if j != t]
+        Q[:, t, t] = (r[:, others, t] ** 2).sum(axis=1) if others else 0.0
+        for j in others:
+            Q[:, t, j] = -r[:, j, t] * r[:, t, j]
+    p = np.full((n, k), 1.0 / k)
+    eps = 0.005 / k
+    live = np.arange(n)
+    for _ in range(max(100, k)):
+        if live.size == 0:
+            break
+        Ql, pl = Q[live], p[live]
+        Qp = np.einsum('ntj,nj->nt', Ql, pl)
+        pQp = (pl * Qp).sum(axis=1)
+        go = np.abs(Qp - pQp[:, None]).max(axis=1) >= eps
+        live, Ql, pl, Qp, pQp = live[go], Ql[go], pl[go], Qp[go], pQp[go]
+        for t in range(k):
+            diff = (-Qp[:, t] + pQp) / Ql[:, t, t]
+            pl[:, t] += diff
+            pQp = (pQp + diff * (diff * Ql[:, t, t] + 2 * Qp[:, t])) / (1 + diff) / (1 + diff)
+            Qp = (Qp + diff[:, None] * Ql[:, t, :]) / (1 + diff)[:, None]
+            pl /= (1 + diff)[:, None]
+        p[live] = pl
+    return p
+
+
+def ovr_decision_function(predictions, confidences, n_classes):
+    """sklearn 0.19 sklearn.utils.multiclass._ovr_decision_function: votes + sum of confidences / (3 (|sum| + 1))"""
+    n = predictions.shape[0]
+    votes = np.zeros((n, n_classes))
+    conf = np.zeros((n, n_classes))
+    k = 0
+    for i in range(n_classes):
+        for j in range(i + 1, n_classes):
+            conf[:, i] -= confidences[:, k]
+            conf[:, j] += confidences[:, k]
+            votes[predictions[:, k] == 0, i] += 1
+            votes[predictions[:, k] == 1, j] += 1
+            k += 1
+    return votes + conf / (3 * (np.abs(conf) + 1))
+
+
+def hinge_loss(y_true, pred_decision, labels=None):
+    """sklearn 0.19 sklearn.metrics.hinge_loss: the multiclass margin is the true class's decision value minus the largest other
+    one (Crammer-Singer); with two classes, y in {-1, +1} (the larger label +1) times the one decision value."""
+    y_true = np.asarray(y_true).reshape(-1)
+    pred = np.asarray(pred_decision, np.float64)
+    present = np.unique(y_true)
+    if present.size > 2:
+        if labels is None and pred.ndim > 1 and present.size != pred.shape[1]:
+            raise ValueError('Please include all labels in y_true or pass labels as third argument')
+        lab = np.unique(present if labels is None else np.asarray(labels))
+        if not np.all(np.isin(y_true, lab)):
+            raise ValueError('y_true contains labels not in labels')
+        yi = np.searchsorted(lab, y_true)
+        rows = np.arange(y_true.size)
+        margin = pred[rows, yi].copy()
+        others = pred.copy()
+        others[rows, yi] = -np.inf
+        margin -= others.max(axis=1)
+    else:
+        pred = pred.reshape(-1)
+        if pred.size != y_true.size:
+            raise ValueError('pred_decision should hold one value per sample')
+        y = np.where(y_true == present[-1], 1.0, -1.0) if present.size == 2 else -np.ones(y_true.size)
+        margin = y * pred
+    losses = 1 - margin
+    losses[losses <= 0] = 0
+    return float(np.mean(losses))
+
+
+# ---- SVC -------------------------------------------------------------------------------------------------------------------------
+class SVC(object):
+    """sklearn 0.19.0's sklearn.svm.SVC (C-SVC) on the GPU: fit / predict / decision_function / predict_proba and sklearn's
+    fitted attributes (classes_, support_, support_vectors_, n_support_, dual_coef_, intercept_, probA_, probB_).  The fitted
+    model pickles without its device handle and predicts again after unpickling."""
+
+    def __init__(self, C=1.0, kernel='rbf', degree=3, gamma='auto', coef0=0.0, tol=1e-3, max_iter=-1, probability=False,
+                 random_state=None, verbose=False, decision_function_shape='ovr', device=0, ws_size=0):
+        self.C, self.kernel, self.degree, self.gamma, self.coef0 = C, kernel, degree, gamma, coef0
+        self.tol, self.max_iter, self.probability, self.random_state = tol, max_iter, probability, random_state
+        self.verbose, self.decision_function_shape, self.device, self.ws_size = verbose, decision_function_shape, device, ws_size
+        self._h = None
+
+    # pickling: everything but the device handle
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state['_h'] = None
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+
+    def _handle(self):
+        if self._h is None:
+            self._h = _lib.SVM(self.device)
+        return self._h
+
+    def _kernel(self):
+        return _lib.svm_kernel(self.kernel, self._gamma, self.coef0, self.degree)
+
+    def fit(self, X, y):
+        X = np.ascontiguousarray(X, np.float32)
+        y = np.asarray(y).reshape(-1)
+        if X.ndim != 2 or X.shape[0] != y.size:
+            raise ValueError('X must be (n_samples, n_features) with one label per row')
+        if not self.C > 0:
+            raise ValueError('C <= 0')
+        if self.kernel not in _lib.SVM_KERNELS:
+            raise ValueError('kernel must be one of %s' % sorted(_lib.SVM_KERNELS))
+        self.classes_, yenc = np.unique(y, return_inverse=True)
+        nc = self.classes_.size
+        if nc < 2:
+            raise ValueError('The number of classes has to be greater than one; got %d' % nc)
+        if nc > _lib.SVM_MAX_CLASSES:
+            raise ValueError('at most %d classes are built' % _lib.SVM_MAX_CLASSES)
+        self.shape_fit_ = X.shape
+        self._gamma = 1.0 / X.shape[1] if self.gamma == 'auto' else float(self.gamma)
+        h = self._handle()
+        h.set_data(X)
+        kp = self._kernel()
+        groups = [np.flatnonzero(yenc == c).astype(np.int32) for c in range(nc)]
+        pairs = [(i, j) for i in range(nc) for j in range(i + 1, nc)]
+        problems = [(np.concatenate((groups[i], groups[j])),
+                     np.concatenate((np.ones(groups[i].size, np.int8), -np.ones(groups[j].size, np.int8)))) for i, j in pairs]
+        cv = []                      # (pair, held-out positions in the pair's rows, sub-problem number or a fixed value)
+        sub = []
+        if self.probability:
+            rs = np.random.RandomState(self.random_state)
+            for p, (rows, signs) in enumerate(problems):
+                l = rows.size
+                perm = rs.permutation(l)
+                for f in range(NR_FOLD):
+                    begin, end = f * l // NR_FOLD, (f + 1) * l // NR_FOLD
+                    train_pos = np.concatenate((perm[:begin], perm[end:]))
+                    npos = int((signs[train_pos] > 0).sum())
+                    nneg = train_pos.size - npos
+                    if npos == 0 or nneg == 0:      # libsvm's fixed decision values for a fold with one class (or none)
+                        cv.append((p, perm[begin:end], 0.0 if npos == nneg else (1.0 if npos else -1.0)))
+                    else:
+                        cv.append((p, perm[begin:end], len(problems) + len(sub)))
+                        sub.append((rows[train_pos], signs[train_pos]))
+        alphas, rho, updates, outer, gaps = h.fit(kp, problems + sub, cost=self.C, tol=self.tol, max_iter=self.max_iter,
+                                                  q=self.ws_size)
+        self.n_iter_ = updates[:len(problems)].copy()
+        self.n_outer_ = outer[:len(problems)].copy()
+        if self.max_iter is not None and self.max_iter > 0 and np.any(updates >= self.max_iter):
+            LOGGER.warning('Solver terminated early (max_iter=%d).  Consider pre-processing your data with StandardScaler or '
+                           'MinMaxScaler.', self.max_iter)
+        self._build_model(X, groups, pairs, problems, alphas, rho)
+        if self.probability:
+            self.probA_, self.probB_ = self._platt(h, kp, problems, sub, cv, alphas, rho)
+        else:
+            self.probA_ = self.probB_ = np.empty(0)
+        return self
+
+    def _build_model(self, X, groups, pairs, problems, alphas, rho):
+        """svm.cpp svm_train's multiclass model: support vectors grouped by class, sv_coef (C - 1, n_SV), rho per pair"""
+        nc = len(groups)
+        nonzero = np.zeros(X.shape[0], bool)
+        for (rows, _), a in zip(problems, alphas):
+            nonzero[rows[a > 0]] = True
+        sv_of = [g[nonzero[g]] for g in groups]
+        self.n_support_ = np.array([s.size for s in sv_of], np.int32)
+        self.support_ = np.concatenate(sv_of).astype(np.int32)
+        self.support_vectors_ = X[self.support_]
+        start = np.concatenate(([0], np.cumsum(self.n_support_)))
+        pos = np.full(X.shape[0], -1, np.int64)
+        pos[self.support_] = np.arange(self.support_.size)
+        coef = np.zeros((nc - 1, self.support_.size))
+        for (i, j), (rows, signs), a in zip(pairs, problems, alphas):
+            ya = signs * a
+            nz = a > 0
+            ri, rj = rows[:groups[i].size], rows[groups[i].size:]
+            mi, mj = nz[:groups[i].size], nz[groups[i].size:]
+            coef[j - 1, pos[ri[mi]]] = ya[:groups[i].size][mi]
+            coef[i, pos[rj[mj]]] = ya[groups[i].size:][mj]
+        self._sv_start = start.astype(np.int64)
+        self._dual_coef_ = coef
+        self._intercept_ = -np.asarray(rho[:len(pairs)], np.float64)
+        self.dual_coef_, self.intercept_ = coef.copy(), self._intercept_.copy()
+        if nc == 2:                 # sklearn flips the binary model so that positive means classes_[1]
+            self.dual_coef_, self.intercept_ = -self.dual_coef_, -self.intercept_
+
+    def _platt(self, h, kp, problems, sub, cv, alphas, rho):
+        """svm_binary_svc_probability for every pair: decision values of the held-out folds (GPU), then sigmoid_train"""
+        allp = problems + sub
+        decs = [np.empty(rows.size) for rows, _ in problems]
+        for p, held, job in cv:
+            if isinstance(job, float):
+                decs[p][held] = job
+                continue
+            rows, signs = allp[job]
+            a = alphas[job]
+            nz = a > 0
+            pos, neg = nz & (signs > 0), nz & (signs < 0)
+            sv = np.concatenate((rows[pos], rows[neg]))
+            coef = np.concatenate((a[pos], -a[neg]))[None, :]
+            cs = np.array([0, pos.sum(), pos.sum() + neg.sum()], np.int64)
+            decs[p][held] = h.decision(kp, cs, coef, [rho[job]], x_idx=problems[p][0][held], sv_idx=sv)[:, 0]
+        A, B = np.empty(len(problems)), np.empty(len(problems))
+        for p, (rows, signs) in enumerate(problems):
+            A[p], B[p] = sigmoid_train(decs[p], signs)
+        return A, B
+
+    def _check_fitted(self):
+        if not hasattr(self, 'support_'):
+            raise ValueError('This SVC instance is not fitted yet')
+
+    def _ovo(self, X):
+        """libsvm's pairwise decision values (n, P): positive for the first class of the pair"""
+        self._check_fitted()
+        X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2 or X.shape[1] != self.shape_fit_[1]:
+            raise ValueError('X has %s features per sample; expecting %d' % (X.shape[1:], self.shape_fit_[1]))
+        return self._handle().decision(self._kernel(), self._sv_start, self._dual_coef_, -self._intercept_, X=X,
+                                       SV=self.support_vectors_)
+
+    def decision_function(self, X):
+        dec = self._ovo(X)
+        nc = self.classes_.size
+        if nc == 2:
+            return -dec.ravel()
+        if self.decision_function_shape == 'ovr':
+            return ovr_decision_function(dec < 0, -dec, nc)
+        return dec
+
+    def predict(self, X):
+        """libsvm's one-vs-one vote, ties to the lower class"""
+        dec = self._ovo(X)
+        nc = self.classes_.size
+        votes = np.zeros((dec.shape[0], nc), np.int64)
+        k = 0
+        for i in range(nc):
+            for j in range(i + 1, nc):
+                win = dec[:, k] > 0
+                votes[win, i] += 1
+                votes[~win, j] += 1
+                k += 1
+        return self.classes_[votes.argmax(axis=1)]
+
+    def predict_proba(self, X):
+        """svm_predict_probability: sigmoid_predict of each pair's decision value, clipped to [1e-7, 1 - 1e-7], then coupled"""
+        if not self.probability:
+            raise AttributeError('predict_proba is not available when probability=False')
+        return pairwise_coupling(self._ovo(X), self.probA_, self.probB_, self.classes_.size)
+
+
+def pairwise_coupling(dec, probA, probB, n_classes):
+    """libsvm's svm_predict_probability from the pairwise decision values (n, P) and Platt's (A, B) per pair -> (n, C)"""
+    dec = np.asarray(dec, np.float64).reshape(-1, n_classes * (n_classes - 1) // 2)
+    n = dec.shape[0]
+    r = np.zeros((n, n_classes, n_classes))
+    k = 0
+    for i in range(n_classes):
+        for j in range(i + 1, n_classes):
+            pij = np.clip(sigmoid_predict(dec[:, k], probA[k], probB[k]), MIN_PROB, 1 - MIN_PROB)
+            r[:, i, j], r[:, j, i] = pij, 1 - pij
+            k += 1
+    return multiclass_probability(r)
