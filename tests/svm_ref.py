@@ -26,6 +26,72 @@ def kernel_matrix(A, B, kind, gamma, coef0=0.0, degree=3):
     raise ValueError(kind)
 
 
+def dk_ddot(kind, K, dot, gamma, coef0=0.0, degree=3):
+    """|dK / d(u.v)| in float64: how far a rounding of the dot product moves the kernel value"""
+    if kind == 'linear':
+        return np.ones_like(K)
+    if kind == 'poly':
+        if degree == 0:
+            return np.zeros_like(K)
+        return np.abs(degree * gamma * (gamma * dot + coef0) ** (degree - 1))
+    if kind == 'rbf':
+        return 2 * gamma * K
+    return gamma * (1 - K * K)
+
+
+def kernel_rows_bound(A, B, kind, gamma, coef0=0.0, degree=3):
+    """-> (K, bK): the float64 kernel matrix and the project's bound on an fp32 MFMA kernel row against it (the comment above
+    test_svm_gpu.py: test_kernel_rows_match_float64): 2.5e-7 sqrt(D) |dK/d dot| S + 1e-6 |K| + 1e-7, S = sum |u_k v_k| (rbf:
+    + |u|^2 + |v|^2)"""
+    A = np.asarray(A, np.float64)
+    B = np.asarray(B, np.float64)
+    K = kernel_matrix(A, B, kind, gamma, coef0, degree)
+    S = np.abs(A) @ np.abs(B).T
+    if kind == 'rbf':
+        S = S + (A * A).sum(1)[:, None] + (B * B).sum(1)[None, :]
+    bK = 2.5e-7 * np.sqrt(A.shape[1]) * dk_ddot(kind, K, A @ B.T, gamma, coef0, degree) * S + 1e-6 * np.abs(K) + 1e-7
+    return K, bK
+
+
+def pair_index(i, j, nc):
+    """the column of pair (i, j), i < j, in libsvm's order (0, 1), (0, 2), ..., (1, 2), ..."""
+    return i * nc - i * (i + 1) // 2 + (j - i - 1)
+
+
+def ovo_decision_bound(Xt, SV, n_support, coef, rho, kind, gamma, coef0=0.0, degree=3):
+    """ovo_decision and the bound on fp32 kernel values summed in float64 against it, per element: sum_s |coef_s| bK[m, s] over
+    the pair's two classes' support vectors + 1e-12 (sum_s |coef_s K[m, s]| + |rho|).  -> (dec, bound), both (n, P)"""
+    K, bK = kernel_rows_bound(Xt, SV, kind, gamma, coef0, degree)
+    coef = np.asarray(coef, np.float64).reshape(len(n_support) - 1, -1)
+    absK, absc = np.abs(K), np.abs(coef)
+    start = np.concatenate(([0], np.cumsum(n_support))).astype(np.int64)
+    nc = len(n_support)
+    dec = np.empty((K.shape[0], nc * (nc - 1) // 2))
+    bound = np.empty_like(dec)
+    p = 0
+    for i in range(nc):
+        for j in range(i + 1, nc):
+            si, sj = slice(start[i], start[i + 1]), slice(start[j], start[j + 1])
+            dec[:, p] = K[:, si] @ coef[j - 1, si] + K[:, sj] @ coef[i, sj] - rho[p]
+            bound[:, p] = (bK[:, si] @ absc[j - 1, si] + bK[:, sj] @ absc[i, sj]
+                           + 1e-12 * (absK[:, si] @ absc[j - 1, si] + absK[:, sj] @ absc[i, sj] + abs(rho[p])))
+            p += 1
+    return dec, bound
+
+
+def ovo_vote(dec, nc):
+    """libsvm's one-vs-one vote over decision values (n, P): the class index with the most wins, ties to the lower class"""
+    votes = np.zeros((dec.shape[0], nc), np.int64)
+    p = 0
+    for i in range(nc):
+        for j in range(i + 1, nc):
+            win = dec[:, p] > 0
+            votes[win, i] += 1
+            votes[~win, j] += 1
+            p += 1
+    return votes.argmax(axis=1)
+
+
 def solve(K, y, C, eps, alpha=None, G=None, max_updates=None, local_rel=0.0):
     """libsvm Solver::Solve (C-SVC, Cp = Cn = C, no shrinking) on the kernel matrix K of the problem's rows, y in {+1, -1}:
     min 1/2 a^T Q a - e^T a, Q = y y^T K, 0 <= a <= C, y^T a = 0.  Starts from alpha / G (default 0 / -1).  Stops when
