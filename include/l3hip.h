@@ -455,6 +455,65 @@ int l3_op_svm_kernel_rows(int device, const l3_svm_kernel *k, const float *x, in
 int l3_op_svm_smo(int device, const float *K, const int8_t *y, int q, double C, double eps, double local_rel, int64_t max_updates,
                   double *alpha, const double *grad, int64_t *updates_out);
 
+/* ---- VGGish baseline features (data/usc/features.py:166-240) --------------------------------------------------------------------
+ * extract_vggish_embedding / get_vggish_frames_uniform on the GPU, inference only, fp32: load_audio's resampling to 16 kHz and the
+ * zero pad to 15600 samples (features.py:170-181), the log-mel front-end (vggish/mel_features.py:71-97,114-218 with the
+ * parameters of vggish/vggish_input.py:25-29), the examples (vggish_input.py:64-75), the network (vggish/vggish_slim.py:66-99)
+ * and the postprocessor (vggish/vggish_postprocess.py:51-94).  A handle separate from l3_engine: it owns its weights, its
+ * activation buffers for `batch` examples and one stream; calls on one handle are not re-entrant.  Deterministic (no float
+ * atomics).  Errors: l3_last_error(NULL) gives the message. */
+#define L3_VGGISH_DEFAULT_BATCH 128   /* examples per pass when l3_vggish_create is given 0: fc1 reads its 201 MB of weights once
+                                         per pass whatever the batch, so a larger pass spreads that read over more examples (where
+                                         the read stops bounding fc1 is not measured) */
+#define L3_VGGISH_MAX_BATCH 1024
+#define L3_VGGISH_CONV_DIRECT 3       /* l3_vggish_set_conv: the implicit-GEMM convolution instead of a Winograd form */
+#define L3_VGGISH_RAW 0               /* the embedding after fc2's ReLU (vggish_slim.py:96-99) */
+#define L3_VGGISH_PCA 1               /* Postprocessor.postprocess(quantize=False): pca (e - means) clipped to [-2, 2] */
+#define L3_VGGISH_QUANTIZED 2         /* quantize=True: (x + 2) * (255 / 4) truncated to an integer in [0, 255], as float32 */
+typedef struct l3_vggish l3_vggish;
+int l3_vggish_create(int device, int batch, l3_vggish **out);
+void l3_vggish_destroy(l3_vggish *v);
+int l3_vggish_batch(const l3_vggish *v);
+/* fp32 algorithm of the five 3x3 convolutions behind the first: L3_VGGISH_CONV_DIRECT (the default), L3_FP32_CONV_F4X4 or
+ * L3_FP32_CONV_F2X2.  The default is the implicit GEMM because it sums the 9 Cin products of an output directly, the arithmetic the
+ * parity bounds of this path are stated in; the two Winograd forms issue 4x / 2.25x fewer multiplies at the rounding error the
+ * l3_config.fp32_conv comment above gives for them.  Their speed and error on these maps are not measured yet. */
+int l3_vggish_set_conv(l3_vggish *v, int fp32_conv);
+/* One tensor by its TF variable name (vggish_slim.py:66-99 scopes): vggish/conv1/weights (3,3,1,64) HWIO, vggish/conv1/biases,
+ * vggish/conv2/..., vggish/conv3/conv3_1/..., vggish/conv3/conv3_2/..., vggish/conv4/conv4_1/..., vggish/conv4/conv4_2/...,
+ * vggish/fc1/fc1_1/weights (12288, 4096) (in, out), vggish/fc1/fc1_2/..., vggish/fc2/weights (4096, 128), vggish/fc2/biases.
+ * L3_EINVAL for another name or element count. */
+int l3_vggish_set_weight(l3_vggish *v, const char *name, const float *src, int64_t numel);
+/* vggish_pca_params.npz: pca_eigen_vectors (128, 128) row major and pca_means (128) */
+int l3_vggish_set_pca(l3_vggish *v, const float *pca_matrix, const float *pca_means);
+/* extract_vggish_embedding for many files at once.  native / clips / half_window / n_window / num_table / n_samples as in
+ * l3_embed_audio_clips_resampled, at 16 kHz: row {x_off, L, sr_orig, t0, n_out, y_off} writes outputs [t0, t0 + n_out) of the 16 kHz
+ * version of a clip to a zeroed device buffer of n_samples floats (a row at 16 kHz is copied); y_off carries the left pad of a
+ * short clip.  segments: n_segments rows {offset, length} of that buffer, one per (padded) clip; each gets 1 + (length - 400) / 160
+ * log-mel rows, computed once, laid back to back in segment order.  example_rows: the first log-mel row of each example (96 rows
+ * inside one segment).  The examples run through the network in passes of the handle's batch; out (n_examples, 128) float32 in
+ * the form `postprocess` names.  One device-to-host copy and one host wait per call.  L3_ESTATE if a weight (or, for a
+ * postprocessed form, the PCA parameters) was never set; L3_EINVAL for a bad row, segment or example. */
+int l3_vggish_embed_clips_resampled(l3_vggish *v, const float *native, int64_t n_native, const int64_t *clips, int64_t n_clips,
+                                    const double *half_window, int64_t n_window, int num_table, int64_t n_samples,
+                                    const int64_t *segments, int64_t n_segments, const int64_t *example_rows, int64_t n_examples,
+                                    int postprocess, float *out);
+/* Operators of that path on their own (host buffers; parity tests).  Log-mel of segments {offset, length} of x (n floats):
+ * out (rows, 64), rows = sum of 1 + (length - 400) / 160 (a segment shorter than 400 gives none). */
+int l3_op_vggish_logmel(int device, const float *x, int64_t n, const int64_t *segments, int64_t n_segments, float *out);
+/* the first convolution with the example gather, bias, ReLU and 2x2 max pool fused: y (n_examples, 48, 32, 64) */
+int l3_op_vggish_conv1(int device, const float *logmel, int64_t n_rows, const int64_t *example_rows, int64_t n_examples,
+                       const float *w, const float *b, float *y);
+/* the BatchNorm-free convolution tail: y = relu(x + b) (pool 0) or its 2x2 / stride-2 maximum (pool 1: h, wd even); c % 4 == 0 */
+int l3_op_vggish_bias_relu(int device, const float *x, const float *b, float *y, int n, int h, int wd, int c, int pool);
+/* one of the five wide convolutions as the handle runs it under `fp32_conv` (l3_vggish_set_conv), with that tail: x (n, h, wd, cin),
+ * w (3, 3, cin, cout) HWIO, y (n, h, wd, cout) or pooled */
+int l3_op_vggish_conv(int device, int fp32_conv, const float *x, const float *w, const float *b, float *y, int n, int h, int wd,
+                      int cin, int cout, int pool);
+/* the postprocessor: emb (n, 128) -> out (n, 128), quantize 0 / 1 */
+int l3_op_vggish_postprocess(int device, const float *emb, int64_t n, const float *pca_matrix, const float *pca_means,
+                             int quantize, float *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,21 @@ SIGNATURES = {
                                         C.c_int, C.c_void_p]),
     'l3_op_svm_smo': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    # VGGish baseline features (csrc/vggish.hip)
+    'l3_vggish_create': (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    'l3_vggish_destroy': (None, [C.c_void_p]),
+    'l3_vggish_batch': (C.c_int, [C.c_void_p]),
+    'l3_vggish_set_conv': (C.c_int, [C.c_void_p, C.c_int]),
+    'l3_vggish_set_weight': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    'l3_vggish_set_pca': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_vggish_embed_clips_resampled': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                  C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
+                                                  C.c_void_p]),
+    'l3_op_vggish_logmel': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_op_vggish_conv1': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_op_vggish_bias_relu': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5),
+    'l3_op_vggish_postprocess': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'l3_op_vggish_conv': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6),
 }
 
 
@@ -979,3 +994,109 @@ def op_svm_smo(K, y, alpha, grad, cost=1.0, eps=1e-3, local_rel=0.0, max_updates
     check(load().l3_op_svm_smo(device, _ptr(K), _ptr(y), y.size, float(cost), float(eps), float(local_rel), int(max_updates), _ptr(a),
                                _ptr(g), _ptr(u)))
     return a, int(u[0])
+
+
+# ---- VGGish baseline features (csrc/vggish.hip; data/usc/features.py:166-240) -----------------------------------------------------
+VGGISH_CONV = {'f4x4': 0, 'f2x2': 1, 'direct': 3}
+VGGISH_POSTPROCESS = {'raw': 0, 'pca': 1, 'quantized': 2}
+
+
+def _i64(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int64)
+
+
+class VGGish(object):
+    """RAII wrapper over an l3_vggish handle: the network's weights and the activation buffers of one example batch."""
+
+    def __init__(self, batch=0, device=0):
+        self.lib = load()
+        h = C.c_void_p()
+        check(self.lib.l3_vggish_create(int(device), int(batch), C.byref(h)), None)
+        self.h = h
+        self.batch = int(self.lib.l3_vggish_batch(h))
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_vggish_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_conv(self, algo):
+        check(self.lib.l3_vggish_set_conv(self.h, VGGISH_CONV[algo]))
+
+    def set_weight(self, name, value):
+        a = _f32(value)
+        check(self.lib.l3_vggish_set_weight(self.h, name.encode(), _ptr(a), a.size))
+
+    def set_pca(self, pca_matrix, pca_means):
+        m, mu = _f32(pca_matrix), _f32(np.asarray(pca_means).reshape(-1))
+        if m.shape != (128, 128) or mu.shape != (128,):
+            raise ValueError('PCA parameters must be (128, 128) and (128,), got %s and %s' % (m.shape, mu.shape))
+        check(self.lib.l3_vggish_set_pca(self.h, _ptr(m), _ptr(mu)))
+
+    def embed_clips_resampled(self, native, clips, half_window, num_table, n_samples, segments, example_rows, postprocess='quantized'):
+        """native: the clips at their own rates back to back; clips (n, 6) int64 rows {x_off, L, sr_orig, t0, n_out, y_off} into a
+        16 kHz buffer of n_samples; segments (n, 2) int64 {offset, length} of that buffer; example_rows: first log-mel row of each
+        example -> (n_examples, 128) float32"""
+        x, c, w = _f32(native).reshape(-1), _i64(clips).reshape(-1, 6), np.ascontiguousarray(half_window, np.float64).reshape(-1)
+        sg, ex = _i64(segments).reshape(-1, 2), _i64(example_rows).reshape(-1)
+        out = np.empty((ex.size, 128), np.float32)
+        check(self.lib.l3_vggish_embed_clips_resampled(self.h, _ptr(x), x.size, _ptr(c), c.shape[0], _ptr(w), w.size, int(num_table),
+                                                       int(n_samples), _ptr(sg), sg.shape[0], _ptr(ex), ex.size,
+                                                       VGGISH_POSTPROCESS[postprocess], _ptr(out)))
+        return out
+
+
+def vggish_logmel_rows(lengths):
+    """log-mel rows of segments of these lengths: 1 + (n - 400) // 160, none below 400 samples"""
+    n = np.asarray(lengths, np.int64)
+    return np.where(n < 400, 0, 1 + (np.maximum(n, 400) - 400) // 160)
+
+
+def op_vggish_logmel(x, segments=None, device=0):
+    """(rows, 64) float32 log-mel of x, or of its segments {offset, length} back to back"""
+    x = _f32(x).reshape(-1)
+    sg = _i64([[0, x.size]] if segments is None else segments).reshape(-1, 2)
+    out = np.empty((int(vggish_logmel_rows(sg[:, 1]).sum()), 64), np.float32)
+    check(load().l3_op_vggish_logmel(device, _ptr(x), x.size, _ptr(sg), sg.shape[0], _ptr(out)))
+    return out
+
+
+def op_vggish_conv1(logmel, example_rows, w, b, device=0):
+    lm, ex, w, b = _f32(logmel), _i64(example_rows).reshape(-1), _f32(w), _f32(b)
+    assert lm.ndim == 2 and lm.shape[1] == 64 and w.size == 9 * 64 and b.size == 64
+    y = np.empty((ex.size, 48, 32, 64), np.float32)
+    check(load().l3_op_vggish_conv1(device, _ptr(lm), lm.shape[0], _ptr(ex), ex.size, _ptr(w), _ptr(b), _ptr(y)))
+    return y
+
+
+def op_vggish_bias_relu(x, b, pool, device=0):
+    x, b = _f32(x), _f32(b)
+    n, h, w, c = x.shape
+    y = np.empty((n, h // 2, w // 2, c) if pool else x.shape, np.float32)
+    check(load().l3_op_vggish_bias_relu(device, _ptr(x), _ptr(b), _ptr(y), n, h, w, c, 1 if pool else 0))
+    return y
+
+
+def op_vggish_conv(x, w, b, pool, algo, device=0):
+    """one wide VGGish convolution as the handle runs it under `algo` ('f4x4', 'f2x2', 'direct') + bias, ReLU (+ 2x2 pool)"""
+    x, w, b = _f32(x), _f32(w), _f32(b)
+    n, h, wd, cin = x.shape
+    cout = w.shape[3]
+    y = np.empty((n, h // 2, wd // 2, cout) if pool else (n, h, wd, cout), np.float32)
+    check(load().l3_op_vggish_conv(device, VGGISH_CONV[algo], _ptr(x), _ptr(w), _ptr(b), _ptr(y), n, h, wd, cin, cout,
+                                   1 if pool else 0))
+    return y
+
+
+def op_vggish_postprocess(emb, pca_matrix, pca_means, quantize=True, device=0):
+    e, m, mu = _f32(emb), _f32(pca_matrix), _f32(np.asarray(pca_means).reshape(-1))
+    assert e.ndim == 2 and e.shape[1] == 128 and m.shape == (128, 128) and mu.shape == (128,)
+    out = np.empty_like(e)
+    check(load().l3_op_vggish_postprocess(device, _ptr(e), e.shape[0], _ptr(m), _ptr(mu), 1 if quantize else 0, _ptr(out)))
+    return out

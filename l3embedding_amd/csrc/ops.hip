@@ -12,6 +12,7 @@
 #include "kernels.h"
 #include "knobs.h"
 #include "mlp.h"
+#include "vggish.h"
 
 namespace {
 using namespace l3;
@@ -724,5 +725,140 @@ extern "C" int l3_op_adam(int device, float* p, const float* g, float* m, float*
     if (!sc.ok) return L3_ENOMEM;
     adam_step(dp, dg, dm, dv, n, n_l2, l2x2, lr_t, 0.9f, 0.999f, 1e-8f, 1.f, sc.s);
     sc.get(p, dp, n), sc.get(m, dm, n), sc.get(v, dv, n);
+    return sc.status();
+}
+
+// ---- VGGish operators (vggish.hip; data/usc/features.py:166-240) -------------------------------------------------------------
+namespace {
+int vggish_op_device(const char* name, Scope& sc, int device) {
+    if (sc.ok) return L3_OK;
+    set_op_error(std::string(name) + ": HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)");
+    return L3_EHIP;
+}
+}  // namespace
+
+extern "C" int l3_op_vggish_logmel(int device, const float* x, int64_t n, const int64_t* segments, int64_t n_segments, float* out) {
+    if (!x || !segments || !out || n < 0 || n_segments < 0) {
+        set_op_error("l3_op_vggish_logmel: NULL pointer or negative count");
+        return L3_EINVAL;
+    }
+    for (int64_t i = 0; i < n_segments; ++i) {
+        const int64_t off = segments[2 * i], len = segments[2 * i + 1];
+        if (off < 0 || len < 0 || off > n || len > n - off) {
+            set_op_error("l3_op_vggish_logmel: segment " + std::to_string(i) + " outside x");
+            return L3_EINVAL;
+        }
+    }
+    std::vector<int64_t> blocks;
+    const int64_t rows = vggish_logmel_blocks(segments, n_segments, &blocks, nullptr);
+    if (rows == 0) return L3_OK;
+    Scope sc(device);
+    if (int rc = vggish_op_device("l3_op_vggish_logmel", sc, device)) return rc;
+    std::vector<float> dft, mel;
+    vggish_host_dft(&dft);
+    vggish_host_mel(&mel);
+    const float* d_x = sc.put(x, (size_t)n);
+    const int64_t* d_b = sc.put(blocks.data(), blocks.size());
+    const float* d_dft = sc.put(dft.data(), dft.size());
+    const float* d_mel = sc.put(mel.data(), mel.size());
+    float* d_o = sc.alloc<float>((size_t)rows * VG_MELS);
+    if (!sc.ok) return L3_ENOMEM;
+    vggish_logmel(d_x, d_b, (int64_t)blocks.size() / 3, d_dft, d_mel, d_o, sc.s);
+    sc.get(out, d_o, (size_t)rows * VG_MELS);
+    return sc.status();
+}
+
+extern "C" int l3_op_vggish_conv1(int device, const float* logmel, int64_t n_rows, const int64_t* example_rows, int64_t n_examples,
+                                  const float* w, const float* b, float* y) {
+    if (!logmel || !example_rows || !w || !b || !y || n_rows < 0 || n_examples < 0 || n_examples > (1 << 20)) {
+        set_op_error("l3_op_vggish_conv1: NULL pointer or bad count");
+        return L3_EINVAL;
+    }
+    for (int64_t e = 0; e < n_examples; ++e)
+        if (example_rows[e] < 0 || example_rows[e] + VG_ROWS > n_rows) {
+            set_op_error("l3_op_vggish_conv1: example " + std::to_string(e) + " outside the log-mel rows");
+            return L3_EINVAL;
+        }
+    if (n_examples == 0) return L3_OK;
+    Scope sc(device);
+    if (int rc = vggish_op_device("l3_op_vggish_conv1", sc, device)) return rc;
+    const float* d_l = sc.put(logmel, (size_t)n_rows * VG_MELS);
+    const int64_t* d_e = sc.put(example_rows, (size_t)n_examples);
+    const float* d_w = sc.put(w, 9 * 64);
+    const float* d_b = sc.put(b, 64);
+    const size_t ny = (size_t)n_examples * (VG_ROWS / 2) * (VG_MELS / 2) * 64;
+    float* d_y = sc.alloc<float>(ny);
+    if (!sc.ok) return L3_ENOMEM;
+    vggish_conv1(d_l, d_e, d_w, d_b, d_y, (int)n_examples, sc.s);
+    sc.get(y, d_y, ny);
+    return sc.status();
+}
+
+extern "C" int l3_op_vggish_bias_relu(int device, const float* x, const float* b, float* y, int n, int h, int wd, int c, int pool) {
+    if (!x || !b || !y || n <= 0 || h <= 0 || wd <= 0 || c <= 0 || c % 4 != 0 || (pool && (h % 2 != 0 || wd % 2 != 0))) {
+        set_op_error("l3_op_vggish_bias_relu: NULL pointer, c not a multiple of 4, or an odd map under the pool");
+        return L3_EINVAL;
+    }
+    Scope sc(device);
+    if (int rc = vggish_op_device("l3_op_vggish_bias_relu", sc, device)) return rc;
+    const size_t nx = (size_t)n * h * wd * c, ny = pool ? nx / 4 : nx;
+    const float* d_x = sc.put(x, nx);
+    const float* d_b = sc.put(b, (size_t)c);
+    float* d_y = sc.alloc<float>(ny);
+    if (!sc.ok) return L3_ENOMEM;
+    vggish_bias_relu(d_x, d_b, d_y, n, h, wd, c, pool ? 1 : 0, sc.s);
+    sc.get(y, d_y, ny);
+    return sc.status();
+}
+
+extern "C" int l3_op_vggish_postprocess(int device, const float* emb, int64_t n, const float* pca_matrix, const float* pca_means,
+                                        int quantize, float* out) {
+    if (!emb || !pca_matrix || !pca_means || !out || n <= 0 || n > (1 << 24)) {
+        set_op_error("l3_op_vggish_postprocess: NULL pointer or bad count");
+        return L3_EINVAL;
+    }
+    Scope sc(device);
+    if (int rc = vggish_op_device("l3_op_vggish_postprocess", sc, device)) return rc;
+    std::vector<float> t((size_t)VG_EMB * VG_EMB);
+    for (int j = 0; j < VG_EMB; ++j)
+        for (int k = 0; k < VG_EMB; ++k) t[(size_t)k * VG_EMB + j] = pca_matrix[(size_t)j * VG_EMB + k];
+    const float* d_e = sc.put(emb, (size_t)n * VG_EMB);
+    const float* d_p = sc.put(t.data(), t.size());
+    const float* d_m = sc.put(pca_means, (size_t)VG_EMB);
+    float* d_o = sc.alloc<float>((size_t)n * VG_EMB);
+    if (!sc.ok) return L3_ENOMEM;
+    vggish_postprocess(d_e, d_p, d_m, d_o, (int)n, quantize ? 1 : 0, sc.s);
+    sc.get(out, d_o, (size_t)n * VG_EMB);
+    return sc.status();
+}
+
+// one of the five wide convolutions as the handle runs it: conv_fwd without bias under `fp32_conv` (a Winograd form where
+// conv_wino_ok, else the implicit GEMM), then the bias + ReLU (+ pool) tail
+extern "C" int l3_op_vggish_conv(int device, int fp32_conv, const float* x, const float* w, const float* b, float* y, int n, int h,
+                                 int wd, int cin, int cout, int pool) {
+    if (!x || !w || !b || !y || n <= 0 || h <= 0 || wd <= 0 || cin <= 0 || cout <= 0 || cout % 4 != 0 ||
+        (pool && (h % 2 != 0 || wd % 2 != 0)) ||
+        (fp32_conv != L3_FP32_CONV_F4X4 && fp32_conv != L3_FP32_CONV_F2X2 && fp32_conv != L3_VGGISH_CONV_DIRECT)) {
+        set_op_error("l3_op_vggish_conv: NULL pointer, bad size, cout not a multiple of 4, an odd map under the pool, or a bad fp32_conv");
+        return L3_EINVAL;
+    }
+    Scope sc(device);
+    if (int rc = vggish_op_device("l3_op_vggish_conv", sc, device)) return rc;
+    ConvGeom g{n, h, wd, cin, h, wd, cout, 3, 3, 1, 1};
+    g.solo = 1;
+    g.f2x2 = fp32_conv == L3_FP32_CONV_F2X2 ? 1 : 0;
+    const bool wino = fp32_conv != L3_VGGISH_CONV_DIRECT && conv_wino_ok(g);
+    const size_t nx = (size_t)n * h * wd * cin, nc = (size_t)n * h * wd * cout, ny = pool ? nc / 4 : nc;
+    const float* d_x = sc.put(x, nx);
+    const float* d_w = sc.put(w, (size_t)9 * cin * cout);
+    const float* d_b = sc.put(b, (size_t)cout);
+    float* d_u = wino ? sc.alloc<float>(conv_wino_floats(g)) : nullptr;
+    float* d_c = sc.alloc<float>(nc);
+    float* d_y = sc.alloc<float>(ny);
+    if (!sc.ok) return L3_ENOMEM;
+    if (wino) conv_wino_transform_weights(d_w, d_u, g, false, sc.s);
+    conv_fwd(d_x, d_w, nullptr, d_c, g, sc.s, d_u);
+    vggish_bias_relu(d_c, d_b, d_y, n, h, wd, cout, pool ? 1 : 0, sc.s);
+    sc.get(y, d_y, ny);
     return sc.status();
 }

@@ -1,4 +1,5 @@
-"""Audio embeddings of whole clips -- data/usc/features.py:18-28,256-306 (load_audio, get_l3_frames_uniform).
+"""Audio embeddings of whole clips -- data/usc/features.py:18-28,224-240,256-323 (load_audio, get_vggish_frames_uniform,
+get_l3_frames_uniform, compute_file_features).
 
 The framing rule lives here and only here: `frame_table` turns clip lengths into one (start, lo, hi) row per 1-second
 frame, and the C side (l3_embed_audio_frames, csrc/clips.hip) only follows the table on the GPU.  load_audio keeps its
@@ -161,3 +162,26 @@ def get_l3_frames_uniform(audio, l3embedding_model, hop_size=0.1, sr=48000):
     if audio.ndim != 1:
         raise ValueError('audio must be 1-D (got shape %s)' % (audio.shape,))
     return l3embedding_model.predict_clips([audio], int(hop_size * sr))[0]
+
+
+def get_vggish_frames_uniform(audio_path, hop_size=0.1, vggish_model=None):
+    """features.py:224-240: the VGGish features of an audio file, one 128-vector per 0.96-second example every hop_size seconds
+    (vggish.extract_vggish_embedding with frame_hop_sec=hop_size).  vggish_model: a vggish.VGGishModel to use instead of the one
+    read from the default resources directory."""
+    from .vggish import extract_vggish_embedding
+    return extract_vggish_embedding(audio_path, frame_hop_sec=hop_size, vggish_model=vggish_model)
+
+
+def compute_file_features(path, feature_type, l3embedding_model=None, **feature_args):
+    """features.py:309-323: the features of one file, 'l3' or 'vggish' (feature_args: hop_size; vggish_model for 'vggish')"""
+    if feature_type == 'l3':
+        if not l3embedding_model:
+            raise ValueError('Must provide L3 embedding model to use {} features'.format(feature_type))
+        hop_size = feature_args.get('hop_size', 0.1)
+        file_features = get_l3_frames_uniform(read_audio(path, FRAME_LENGTH), l3embedding_model, hop_size=hop_size)
+    elif feature_type == 'vggish':
+        hop_size = feature_args.get('hop_size', 0.1)
+        file_features = get_vggish_frames_uniform(path, hop_size=hop_size, vggish_model=feature_args.get('vggish_model'))
+    else:
+        raise ValueError('Invalid feature type: {}'.format(feature_type))
+    return file_features

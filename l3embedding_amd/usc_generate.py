@@ -1,5 +1,6 @@
 """Embedding feature folds of the downstream sound-classification sets -- the reference's data/usc/us8k.py, esc50.py and
-dcase2013.py generation (driven by 05_generate_embedding_samples.py), restated for the GPU pipeline.
+dcase2013.py generation (driven by 05_generate_embedding_samples.py), restated for the GPU pipeline.  features='vggish' with a
+vggish_model (vggish.VGGishModel) writes the VGGish baseline's features into the same layout.
 
 Per fold k (counted from 1): <output_dir>/fold<k>/<basename>.npz with X the (n_frames, D) embeddings of the file and y its class
 index, written with np.savez_compressed -- the layout usc.get_fold reads.  A file whose .npz exists already is skipped.  What
@@ -68,17 +69,20 @@ def _fold_dirs(data_dir, output_dir, fold_idx):
     return os.path.join(data_dir, 'fold{}'.format(fold_idx + 1)), out
 
 
-def _check_features(features, l3embedding_model):
+def _check_features(features, l3embedding_model, vggish_model=None):
+    if features == 'vggish' and vggish_model:
+        return
     if features != 'l3':
-        raise ValueError('Invalid feature type: {} (only l3 features are built)'.format(features))
+        raise ValueError('Invalid feature type: {} (l3, or vggish with a vggish_model)'.format(features))
     if not l3embedding_model:
         raise ValueError('Must provide L3 embedding model to use {} features'.format(features))
 
 
-def embed_files(jobs, l3embedding_model, hop_size=0.1, **_):
+def embed_files(jobs, l3embedding_model, hop_size=0.1, features='l3', vggish_model=None, **_):
     """jobs: (audio_path, output_path, label) in order.  Files whose output exists, or is the output of an earlier job, are
     skipped, mp3 files are skipped with an error log; the rest are read (features.read_wav), embedded in batches of many files
-    by one predict_clips(..., rates=...) call each, and written as <output_path> {X, y}.  Returns the output paths written."""
+    by one predict_clips(..., rates=...) call each, and written as <output_path> {X, y}.  features='vggish': the batches go to
+    vggish_model.predict_clips(clips, rates, hop_size=...) (vggish.VGGishModel) instead.  Returns the output paths written."""
     hop_length = int(hop_size * SR)
     todo, claimed = [], set()
     for audio_path, output_path, label in jobs:
@@ -102,7 +106,10 @@ def embed_files(jobs, l3embedding_model, hop_size=0.1, **_):
             batch.append(todo[i])
             total += x.size
             i += 1
-        embeddings = l3embedding_model.predict_clips(clips, hop_length, rates=rates)
+        if features == 'vggish':
+            embeddings = vggish_model.predict_clips(clips, rates, hop_size=hop_size)
+        else:
+            embeddings = l3embedding_model.predict_clips(clips, hop_length, rates=rates)
         for (audio_path, output_path, label), X in zip(batch, embeddings):
             np.savez_compressed(output_path, X=X, y=label)
             LOGGER.debug('Processed {}'.format(audio_path))
@@ -111,9 +118,9 @@ def embed_files(jobs, l3embedding_model, hop_size=0.1, **_):
 
 
 def generate_us8k_fold_data(metadata, data_dir, fold_idx, output_dir, l3embedding_model=None, features='l3',
-                            random_state=12345678, **feature_args):
+                            random_state=12345678, vggish_model=None, **feature_args):
     """us8k.py:70-134 for one fold (fold_idx counted from 0); metadata as load_us8k_metadata returns it, or the CSV's path"""
-    _check_features(features, l3embedding_model)
+    _check_features(features, l3embedding_model, vggish_model)
     if isinstance(metadata, str):
         metadata = load_us8k_metadata(metadata)
     _seed_fold(random_state, fold_idx)
@@ -123,28 +130,29 @@ def generate_us8k_fold_data(metadata, data_dir, fold_idx, output_dir, l3embeddin
         for var_path in us8k_variants(audio_fold_dir, fname):
             basename = os.path.splitext(os.path.basename(var_path))[0]
             jobs.append((var_path, os.path.join(out, basename + '.npz'), example_metadata['classID']))
-    return embed_files(jobs, l3embedding_model, **feature_args)
+    return embed_files(jobs, l3embedding_model, features=features, vggish_model=vggish_model, **feature_args)
 
 
 def generate_us8k_folds(metadata_path, data_dir, output_dir, l3embedding_model=None, features='l3', random_state=12345678,
-                        **feature_args):
+                        vggish_model=None, **feature_args):
     LOGGER.info('Generating all folds.')
     metadata = load_us8k_metadata(metadata_path)
     for fold_idx in range(NUM_FOLDS['us8k']):
         generate_us8k_fold_data(metadata, data_dir, fold_idx, output_dir, l3embedding_model=l3embedding_model,
-                                features=features, random_state=random_state, **feature_args)
+                                features=features, random_state=random_state, vggish_model=vggish_model, **feature_args)
 
 
-def _generate_listed_fold(data_dir, fold_idx, output_dir, label_of, l3embedding_model, features, random_state, feature_args):
+def _generate_listed_fold(data_dir, fold_idx, output_dir, label_of, l3embedding_model, features, random_state, vggish_model,
+                          feature_args):
     # esc50.py:25-51 / dcase2013.py:38-64: every entry of the fold directory, in glob order
-    _check_features(features, l3embedding_model)
+    _check_features(features, l3embedding_model, vggish_model)
     _seed_fold(random_state, fold_idx)
     audio_fold_dir, out = _fold_dirs(data_dir, output_dir, fold_idx)
     jobs = []
     for f in glob.glob(audio_fold_dir + '/*'):
         basename = os.path.splitext(os.path.basename(f))[0]
         jobs.append((f, os.path.join(out, basename + '.npz'), label_of(basename)))
-    return embed_files(jobs, l3embedding_model, **feature_args)
+    return embed_files(jobs, l3embedding_model, features=features, vggish_model=vggish_model, **feature_args)
 
 
 def esc50_label(basename):
@@ -156,25 +164,26 @@ def dcase2013_label(basename):
 
 
 def generate_esc50_fold_data(data_dir, fold_idx, output_dir, l3embedding_model=None, features='l3', random_state=12345678,
-                             **feature_args):
+                             vggish_model=None, **feature_args):
     return _generate_listed_fold(data_dir, fold_idx, output_dir, esc50_label, l3embedding_model, features, random_state,
-                                 feature_args)
+                                 vggish_model, feature_args)
 
 
-def generate_esc50_folds(data_dir, output_dir, l3embedding_model=None, features='l3', random_state=12345678, **feature_args):
+def generate_esc50_folds(data_dir, output_dir, l3embedding_model=None, features='l3', random_state=12345678, vggish_model=None,
+                         **feature_args):
     for fold_idx in range(NUM_FOLDS['esc50']):
         generate_esc50_fold_data(data_dir, fold_idx, output_dir, l3embedding_model=l3embedding_model, features=features,
-                                 random_state=random_state, **feature_args)
+                                 random_state=random_state, vggish_model=vggish_model, **feature_args)
 
 
 def generate_dcase2013_fold_data(data_dir, fold_idx, output_dir, l3embedding_model=None, features='l3', random_state=12345678,
-                                 **feature_args):
+                                 vggish_model=None, **feature_args):
     return _generate_listed_fold(data_dir, fold_idx, output_dir, dcase2013_label, l3embedding_model, features, random_state,
-                                 feature_args)
+                                 vggish_model, feature_args)
 
 
 def generate_dcase2013_folds(data_dir, output_dir, l3embedding_model=None, features='l3', random_state=12345678,
-                             **feature_args):
+                             vggish_model=None, **feature_args):
     for fold_idx in range(NUM_FOLDS['dcase2013']):
         generate_dcase2013_fold_data(data_dir, fold_idx, output_dir, l3embedding_model=l3embedding_model, features=features,
-                                     random_state=random_state, **feature_args)
+                                     random_state=random_state, vggish_model=vggish_model, **feature_args)
