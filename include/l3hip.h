@@ -409,6 +409,35 @@ int l3_op_mlp_softmax_ce(int device, const float *z, const int32_t *labels, int 
                          float *ce, float *correct);
 /* The engine's Adam kernel (keras 2.0.9 + L2 gradient 2 * l2 * p on the first n_l2 elements) on its own: p, m, v in/out. */
 int l3_op_adam(int device, float *p, const float *g, float *m, float *v, int64_t n, int64_t n_l2, float l2x2, float lr_t);
+/* The same kernel with every scalar the engine passes: beta_1, beta_2, epsilon and the gradient scale (g * gscale before the L2
+ * term; l3_step_update's grad_scale). */
+int l3_op_adam_scaled(int device, float *p, const float *g, float *m, float *v, int64_t n, int64_t n_l2, float l2x2, float lr_t,
+                      float b1, float b2, float eps, float gscale);
+
+/* Operators of the engine's head, loss and update on their own (host buffers; parity tests).  Each runs the launcher the engine
+ * calls.  y (B, N) = x (B, K) . w (K, N) + b, ReLU when relu != 0.  L3_EINVAL when the launch's dynamic LDS, (K + 8 N) * 4 bytes,
+ * is above the 64 KiB a launch may ask for without a function attribute. */
+int l3_op_head_dense_fwd(int device, const float *x, const float *w, const float *b, float *y, int B, int K, int N, int relu);
+/* dw (K, N) = x^T . dy, db (N) = column sums of dy, dx (B, K) = dy . w^T (no ReLU mask); same limit on N * 4 bytes. */
+int l3_op_head_dense_bwd(int device, const float *x, const float *w, const float *dy, float *dw, float *db, float *dx, int B,
+                         int K, int N);
+/* The engine's two-class softmax + keras categorical_crossentropy: logits (B, 2), labels (B, 2) float32 (one-hot or soft) ->
+ * probs (B, 2), dlogits (B, 2) = gscale * d(sum of the losses) / dlogits, stats[0] = sum of the losses, stats[1] = correct rows. */
+int l3_op_softmax_ce2(int device, const float *logits, const float *labels, int B, float gscale, float *probs, float *dlogits,
+                      float *stats);
+/* out[i] = sum of the squares of base[off[i] .. off[i] + n[i]) (base holds n_base floats).  multi 1: the one-call form for up to
+ * 24 ranges; multi 0: one single-range call per range, the engine's fallback above 24 regularised tensors. */
+int l3_op_sumsq(int device, const float *base, int64_t n_base, const int64_t *off, const int64_t *n, int count, int multi,
+                float *out);
+/* One launch of the moving-average update of every BatchNormalization statistic over a table of `entries` vectors of c[i]
+ * channels.  moving, biased (in/out) and batch hold entry i at slot_off[i] (slot_off[i + 1] - slot_off[i] >= c[i]; n_slots floats in
+ * all); the table's packed offsets are the running sum of c, as the engine builds them.  gathered NULL: one update from batch.
+ * Else `replicas` updates in order, replica r's statistic i at gathered[r * stride + packed offset of i] (n_gathered floats).
+ * `step` = updates applied once the call is done.  packed (in/out, n_packed floats >= sum of c) receives bn_moving_pack's output
+ * of the same table. */
+int l3_op_bn_moving_update(int device, int entries, const int32_t *c, const int64_t *slot_off, int64_t n_slots, float *moving,
+                           float *biased, const float *batch, const float *gathered, int64_t n_gathered, int replicas,
+                           int64_t stride, float momentum, int zero_debias, int64_t step, float *packed, int64_t n_packed);
 
 /* ---- Downstream SVM classifier (classifier/train.py:79-166) ------------------------------------------------------------------
  * train_svm's sklearn.svm.SVC (libsvm's C-SVC) on the GPU: the binary problems of one-vs-one and of probability estimates solved

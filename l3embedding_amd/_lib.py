@@ -152,6 +152,14 @@ SIGNATURES = {
                              + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p]),
     'l3_op_mlp_softmax_ce': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 4),
     'l3_op_adam': (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_float, C.c_float]),
+    'l3_op_adam_scaled': (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int64] + [C.c_float] * 6),
+    # head / loss / L2 sums / BatchNorm moving averages on their own (csrc/elementwise.hip)
+    'l3_op_head_dense_fwd': (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 4),
+    'l3_op_head_dense_bwd': (C.c_int, [C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 3),
+    'l3_op_softmax_ce2': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 3),
+    'l3_op_sumsq': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'l3_op_bn_moving_update': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+                               + [C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
     # downstream SVM classifier (csrc/svm.hip)
     'l3_svm_create': (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     'l3_svm_destroy': (None, [C.c_void_p]),
@@ -892,6 +900,70 @@ def op_adam(p, g, m, v, n_l2, l2x2, lr_t, device=0):
     g = _f32(g).ravel()
     check(load().l3_op_adam(device, _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.size, int(n_l2), float(l2x2), float(lr_t)))
     return p, m, v
+
+
+def op_adam_scaled(p, g, m, v, n_l2, l2x2, lr_t, b1=0.9, b2=0.999, eps=1e-8, gscale=1.0, device=0):
+    """The engine's Adam kernel with every scalar of its launch (g * gscale before the L2 term) -> (p, m, v)"""
+    p, m, v = [np.array(a, np.float32, copy=True).ravel() for a in (p, m, v)]
+    g = _f32(g).ravel()
+    check(load().l3_op_adam_scaled(device, _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.size, int(n_l2), float(l2x2), float(lr_t),
+                                   float(b1), float(b2), float(eps), float(gscale)))
+    return p, m, v
+
+
+# ---- the engine's head, loss, L2 sums and BatchNorm moving averages on their own (csrc/elementwise.hip) ---------------------------
+def op_head_dense_fwd(x, w, b, relu, device=0):
+    """y (B, N) = x (B, K) . w (K, N) + b, ReLU when `relu`: the engine's dense_fwd launch"""
+    x, w, b = _f32(x), _f32(w), _f32(b)
+    (B, K), N = x.shape, w.shape[1]
+    assert w.shape == (K, N) and b.shape == (N,)
+    y = np.empty((B, N), np.float32)
+    check(load().l3_op_head_dense_fwd(device, _ptr(x), _ptr(w), _ptr(b), _ptr(y), B, K, N, int(bool(relu))))
+    return y
+
+
+def op_head_dense_bwd(x, w, dy, device=0):
+    """-> dw (K, N), db (N), dx (B, K): the engine's dense_bwd_w and dense_bwd_x launches"""
+    x, w, dy = _f32(x), _f32(w), _f32(dy)
+    (B, K), N = x.shape, w.shape[1]
+    assert w.shape == (K, N) and dy.shape == (B, N)
+    dw, db, dx = np.empty((K, N), np.float32), np.empty(N, np.float32), np.empty((B, K), np.float32)
+    check(load().l3_op_head_dense_bwd(device, _ptr(x), _ptr(w), _ptr(dy), _ptr(dw), _ptr(db), _ptr(dx), B, K, N))
+    return dw, db, dx
+
+
+def op_softmax_ce2(logits, labels, gscale, device=0):
+    """The engine's two-class loss: logits, float labels (B, 2) -> probs, dlogits, sum of the losses, correct rows"""
+    z, t = _f32(logits), _f32(labels)
+    assert z.ndim == 2 and z.shape[1] == 2 and t.shape == z.shape
+    probs, dz, stats = np.empty_like(z), np.empty_like(z), np.empty(2, np.float32)
+    check(load().l3_op_softmax_ce2(device, _ptr(z), _ptr(t), z.shape[0], float(gscale), _ptr(probs), _ptr(dz), _ptr(stats)))
+    return probs, dz, stats[0], stats[1]
+
+
+def op_sumsq(base, off, n, multi, device=0):
+    """Sums of squares of the ranges [off[i], off[i] + n[i]) of `base`: one sumsq_multi call (multi) or one sumsq call each"""
+    base, off, n = _f32(base).ravel(), _i64(off).ravel(), _i64(n).ravel()
+    assert off.size == n.size
+    out = np.empty(off.size, np.float32)
+    check(load().l3_op_sumsq(device, _ptr(base), base.size, _ptr(off), _ptr(n), off.size, int(bool(multi)), _ptr(out)))
+    return out
+
+
+def op_bn_moving_update(c, slot_off, moving, biased, batch, momentum, zero_debias, step, gathered=None, replicas=1, stride=0,
+                        packed=None, device=0):
+    """One bn_moving_update_all launch over a table of len(c) statistics (entry i: c[i] channels at slot_off[i] of moving /
+    biased / batch), and bn_moving_pack of the same table into `packed` -> (moving, biased, packed), copies."""
+    c, slot_off = _i32(c).ravel(), _i64(slot_off).ravel()
+    moving, biased = [np.array(a, np.float32, copy=True).ravel() for a in (moving, biased)]
+    batch = _f32(batch).ravel()
+    assert c.size == slot_off.size and moving.size == biased.size == batch.size
+    packed = np.zeros(int(c.sum()), np.float32) if packed is None else np.array(packed, np.float32, copy=True).ravel()
+    g = None if gathered is None else _f32(gathered).ravel()
+    check(load().l3_op_bn_moving_update(device, c.size, _ptr(c), _ptr(slot_off), moving.size, _ptr(moving), _ptr(biased),
+                                        _ptr(batch), _ptr(g), 0 if g is None else g.size, int(replicas), int(stride),
+                                        float(momentum), int(bool(zero_debias)), int(step), _ptr(packed), packed.size))
+    return moving, biased, packed
 
 
 # ---- downstream SVM classifier (classifier/train.py:79-166; csrc/svm.hip) ---------------------------------------------------------

@@ -728,6 +728,176 @@ extern "C" int l3_op_adam(int device, float* p, const float* g, float* m, float*
     return sc.status();
 }
 
+extern "C" int l3_op_adam_scaled(int device, float* p, const float* g, float* m, float* v, int64_t n, int64_t n_l2, float l2x2,
+                                 float lr_t, float b1, float b2, float eps, float gscale) {
+    const int rc = mlp_op_check("l3_op_adam_scaled", device, p && g && m && v && n_l2 >= 0 && n_l2 <= n, 1, 1, 1, nullptr, n > 0 ? 1 : 0);
+    if (rc != L3_OK || n <= 0) {
+        if (rc == L3_OK) set_op_error("l3_op_adam_scaled: n <= 0");
+        return rc != L3_OK ? rc : L3_EINVAL;
+    }
+    Scope sc(device);
+    float* dp = sc.put(p, n);
+    const float* dg = sc.put(g, n);
+    float* dm = sc.put(m, n);
+    float* dv = sc.put(v, n);
+    if (!sc.ok) return L3_ENOMEM;
+    adam_step(dp, dg, dm, dv, n, n_l2, l2x2, lr_t, b1, b2, eps, gscale, sc.s);
+    sc.get(p, dp, n), sc.get(m, dm, n), sc.get(v, dv, n);
+    return sc.status();
+}
+
+// ---- head, loss, L2 sums and BatchNorm moving averages on their own (elementwise.hip; model.py:25-31, train.py:270-284) ----------
+namespace {
+constexpr size_t HEAD_MAX_DYN_LDS = 64 * 1024;      // dynamic LDS of a launch that sets no function attribute
+int head_op_check(const char* name, int device, bool ptrs_ok, int B, int K, int N, size_t lds_bytes) {
+    if (ptrs_ok && B > 0 && K > 0 && N > 0 && lds_bytes > HEAD_MAX_DYN_LDS) {
+        set_op_error(std::string(name) + ": K / N need " + std::to_string(lds_bytes) + " bytes of dynamic LDS, above the 65536 of a plain launch");
+        return L3_EINVAL;
+    }
+    return mlp_op_check(name, device, ptrs_ok, B, K, N, nullptr, B);
+}
+}  // namespace
+
+extern "C" int l3_op_head_dense_fwd(int device, const float* x, const float* w, const float* b, float* y, int B, int K, int N,
+                                    int relu) {
+    const int rc = head_op_check("l3_op_head_dense_fwd", device, x && w && b && y, B, K, N, ((size_t)K + 8 * (size_t)N) * 4);
+    if (rc != L3_OK) return rc;
+    Scope sc(device);
+    const float* dx = sc.put(x, (size_t)B * K);
+    const float* dw = sc.put(w, (size_t)K * N);
+    const float* db = sc.put(b, (size_t)N);
+    float* dy = sc.alloc<float>((size_t)B * N);
+    if (!sc.ok) return L3_ENOMEM;
+    dense_fwd(dx, dw, db, dy, B, K, N, relu ? 1 : 0, sc.s);
+    sc.get(y, dy, (size_t)B * N);
+    return sc.status();
+}
+
+extern "C" int l3_op_head_dense_bwd(int device, const float* x, const float* w, const float* dy, float* dw, float* db, float* dx,
+                                    int B, int K, int N) {
+    const int rc = head_op_check("l3_op_head_dense_bwd", device, x && w && dy && dw && db && dx, B, K, N, (size_t)N * 4);
+    if (rc != L3_OK) return rc;
+    Scope sc(device);
+    const float* d_x = sc.put(x, (size_t)B * K);
+    const float* d_w = sc.put(w, (size_t)K * N);
+    const float* d_dy = sc.put(dy, (size_t)B * N);
+    float* d_dw = sc.alloc<float>((size_t)K * N);
+    float* d_db = sc.alloc<float>((size_t)N);
+    float* d_dx = sc.alloc<float>((size_t)B * K);
+    if (!sc.ok) return L3_ENOMEM;
+    dense_bwd_w(d_x, d_dy, d_dw, d_db, B, K, N, sc.s);
+    dense_bwd_x(d_dy, d_w, d_dx, B, K, N, sc.s);
+    sc.get(dw, d_dw, (size_t)K * N);
+    sc.get(db, d_db, (size_t)N);
+    sc.get(dx, d_dx, (size_t)B * K);
+    return sc.status();
+}
+
+extern "C" int l3_op_softmax_ce2(int device, const float* logits, const float* labels, int B, float gscale, float* probs,
+                                 float* dlogits, float* stats) {
+    const int rc = mlp_op_check("l3_op_softmax_ce2", device, logits && labels && probs && dlogits && stats, B, 1, 2, nullptr, B);
+    if (rc != L3_OK) return rc;
+    Scope sc(device);
+    const float* d_z = sc.put(logits, (size_t)B * 2);
+    const float* d_t = sc.put(labels, (size_t)B * 2);
+    float* d_p = sc.alloc<float>((size_t)B * 2);
+    float* d_g = sc.alloc<float>((size_t)B * 2);
+    float* d_s = sc.alloc<float>(2);
+    if (!sc.ok) return L3_ENOMEM;
+    softmax_ce(d_z, d_t, d_p, d_g, d_s, B, gscale, sc.s);
+    sc.get(probs, d_p, (size_t)B * 2);
+    sc.get(dlogits, d_g, (size_t)B * 2);
+    sc.get(stats, d_s, 2);
+    return sc.status();
+}
+
+extern "C" int l3_op_sumsq(int device, const float* base, int64_t n_base, const int64_t* off, const int64_t* n, int count,
+                           int multi, float* out) {
+    if (!base || !off || !n || !out || n_base <= 0 || count <= 0 || (multi && count > SUMSQ_MAX_SEGS)) {
+        set_op_error("l3_op_sumsq: NULL pointer, empty base, or a range count outside [1, " +
+                     std::string(multi ? std::to_string(SUMSQ_MAX_SEGS) : "inf") + "]");
+        return L3_EINVAL;
+    }
+    for (int i = 0; i < count; ++i)
+        if (off[i] < 0 || n[i] < 0 || off[i] > n_base || n[i] > n_base - off[i]) {
+            set_op_error("l3_op_sumsq: range " + std::to_string(i) + " outside base");
+            return L3_EINVAL;
+        }
+    const int rc = mlp_op_check("l3_op_sumsq", device, true, 1, 1, 1, nullptr, 1);
+    if (rc != L3_OK) return rc;
+    Scope sc(device);
+    const float* d_b = sc.put(base, (size_t)n_base);
+    float* d_o = sc.alloc<float>((size_t)count);
+    float* d_s = sc.alloc<float>(multi ? (size_t)SUMSQ_MAX_SEGS * SUMSQ_BLOCKS : sumsq_scratch_floats(n_base));
+    if (!sc.ok) return L3_ENOMEM;
+    if (multi) {
+        SumsqSegs segs{};
+        for (int i = 0; i < count; ++i) {
+            segs.off[i] = off[i];
+            segs.n[i] = n[i];
+        }
+        segs.count = count;
+        sumsq_multi(d_b, segs, d_o, d_s, sc.s);
+    } else {
+        for (int i = 0; i < count; ++i) sumsq(d_b + off[i], n[i], d_o + i, d_s, sc.s);
+    }
+    sc.get(out, d_o, (size_t)count);
+    return sc.status();
+}
+
+extern "C" int l3_op_bn_moving_update(int device, int entries, const int32_t* c, const int64_t* slot_off, int64_t n_slots,
+                                      float* moving, float* biased, const float* batch, const float* gathered, int64_t n_gathered,
+                                      int replicas, int64_t stride, float momentum, int zero_debias, int64_t step, float* packed,
+                                      int64_t n_packed) {
+    const char* name = "l3_op_bn_moving_update";
+    if (!c || !slot_off || !moving || !biased || !batch || !packed || entries <= 0 || entries > 65535 || n_slots <= 0 || step < 1) {
+        set_op_error(std::string(name) + ": NULL pointer, entry count outside [1, 65535] or step < 1");
+        return L3_EINVAL;
+    }
+    int64_t total = 0;
+    int max_c = 0;
+    for (int i = 0; i < entries; ++i) {
+        const int64_t end = i + 1 < entries ? slot_off[i + 1] : n_slots;
+        if (c[i] <= 0 || slot_off[i] < 0 || slot_off[i] > end || c[i] > end - slot_off[i] || end > n_slots) {
+            set_op_error(std::string(name) + ": entry " + std::to_string(i) + " does not fit its slot");
+            return L3_EINVAL;
+        }
+        total += c[i];
+        max_c = c[i] > max_c ? c[i] : max_c;
+    }
+    if (total > n_packed || total > INT32_MAX) {
+        set_op_error(std::string(name) + ": packed holds fewer floats than the channel counts add up to");
+        return L3_EINVAL;
+    }
+    if (gathered && (replicas < 1 || stride < total || n_gathered < (int64_t)(replicas - 1) * stride + total)) {
+        set_op_error(std::string(name) + ": gathered needs replicas >= 1, stride >= the packed size and (replicas - 1) * stride + "
+                     "the packed size floats");
+        return L3_EINVAL;
+    }
+    const int rc = mlp_op_check(name, device, true, 1, 1, 1, nullptr, 1);
+    if (rc != L3_OK) return rc;
+    Scope sc(device);
+    float* d_m = sc.put(moving, (size_t)n_slots);
+    float* d_b = sc.put(biased, (size_t)n_slots);
+    const float* d_v = sc.put(batch, (size_t)n_slots);
+    const float* d_g = gathered ? sc.put(gathered, (size_t)n_gathered) : nullptr;
+    float* d_p = sc.put(packed, (size_t)n_packed);
+    std::vector<BnMovingEntry> tab;
+    int off = 0;
+    for (int i = 0; i < entries; ++i) {
+        tab.push_back(BnMovingEntry{d_m + slot_off[i], d_b + slot_off[i], d_v + slot_off[i], c[i], off});
+        off += c[i];
+    }
+    const BnMovingEntry* d_t = sc.put(tab.data(), tab.size());
+    if (!sc.ok) return L3_ENOMEM;
+    bn_moving_pack(d_t, entries, max_c, d_p, sc.s);
+    bn_moving_update_all(d_t, entries, max_c, momentum, zero_debias ? 1 : 0, step, sc.s, d_g, replicas, stride);
+    sc.get(moving, d_m, (size_t)n_slots);
+    sc.get(biased, d_b, (size_t)n_slots);
+    sc.get(packed, d_p, (size_t)n_packed);
+    return sc.status();
+}
+
 // ---- VGGish operators (vggish.hip; data/usc/features.py:166-240) -------------------------------------------------------------
 namespace {
 int vggish_op_device(const char* name, Scope& sc, int device) {
