@@ -154,6 +154,28 @@ int l3_upload_batch_raw(l3_engine *e, const uint8_t *video_u8, const int16_t *au
  * starts.  Keras' fit_generator keeps batches queued ahead of the device the same way
  * (train.py:408-414, max_queue_size=10). */
 int l3_stage_batch_raw(l3_engine *e, const uint8_t *video_u8, const int16_t *audio_i16, const int32_t *labels_i32);
+/* Training-set augmentation (02_generate_samples.py --augment; data/avc/sample.py:24-69,117-166,169-283), one record per sample.
+ * The draws are the caller's (l3embedding_amd/augment.py draw_params keeps the reference's order of random calls); the library
+ * applies them.  start_x is the crop's first ROW and start_y its first COLUMN, the reference's names (sample.py:181-191). */
+typedef struct l3_augment_params {
+    int32_t start_x, start_y;   /* sample_cropped_frame, sample.py:182: 0 <= start_x <= H - 224, 0 <= start_y <= W - 224 */
+    int32_t flip;               /* horiz_flip, sample.py:59-69,244-247 */
+    int32_t sat_first;          /* 1: saturation then brightness (sample.py:253-262); 0: brightness first (sample.py:264-273) */
+    float saturation;           /* adjust_saturation's factor, sample.py:24-38 */
+    float brightness;           /* adjust_brightness's delta on the [0, 1] image, sample.py:41-56 */
+} l3_augment_params;
+/* l3_upload_batch_raw / l3_stage_batch_raw with the batch augmented in the pass that scales it: the kernels of
+ * l3_op_augment_video / l3_op_augment_audio run in place of the plain scaling ones, on the engine's 224 x 224 frames (so
+ * start_x = start_y = 0) and 48000-sample rows.  params: B records; u: B draws of random() in [0, 1), the audio gain's
+ * (sample.py:156).  Labels are unchanged.  The staged variant sends the records over the copy stream with the batch; staged
+ * plain and augmented batches may follow each other in any order.  L3_EINVAL for a NULL pointer or a non-zero crop start. */
+int l3_upload_batch_raw_aug(l3_engine *e, const uint8_t *video_u8, const int16_t *audio_i16, const int32_t *labels_i32,
+                            const l3_augment_params *params, const double *u);
+int l3_stage_batch_raw_aug(l3_engine *e, const uint8_t *video_u8, const int16_t *audio_i16, const int32_t *labels_i32,
+                           const l3_augment_params *params, const double *u);
+/* The audio gains (sample.py:156,162 'gain') of the batch the engine holds -- the last one uploaded, or staged and adopted by a
+ * step -- B doubles.  Waits for the device: for tests and metadata.  L3_ESTATE if that batch was not augmented. */
+int l3_batch_gains(l3_engine *e, double *gains);
 /* Staged step on the resident batch, so the host can overlap the gradient
  * all-reduce with backward (buckets complete head -> block4 -> ... -> block1):
  *   l3_step_forward          forward + loss + head backward          (bucket 0 ready)
@@ -355,6 +377,19 @@ int l3_op_bn_stats_from_partials(int device, const float *part, int nblk, int c,
                                  float eps, float *mean, float *var);
 int l3_op_preprocess(int device, const uint8_t *video_u8, int64_t nv, float *video,
                      const int16_t *audio_i16, int64_t na, float *audio);
+/* sample_one_frame(augment=True) after the frame has been chosen (data/avc/sample.py:235-281): crop to 224 x 224 at
+ * (start_x, start_y), flip, img_as_float, saturation and brightness in the record's order, img_as_ubyte.  u8: n frames
+ * (h, w, 3) with h, w >= 224.  out_u8 (n, 224, 224, 3) is the stored byte; out_f32 is l3_op_preprocess of it, bit for bit;
+ * either may be NULL.  float64 arithmetic along skimage's own sequence of operations: the bytes are the original's.
+ * L3_EINVAL (message in l3_last_error(NULL)) for a crop outside the frame. */
+int l3_op_augment_video(int device, const uint8_t *u8, int n, int h, int w, const l3_augment_params *params,
+                        uint8_t *out_u8, float *out_f32);
+/* sample_one_second(augment=True) after the second has been cut (data/avc/sample.py:146-162): per row of t samples,
+ * gain = 1 + (-0.1 + (min(0.1, 32768 / peak - 1) + 0.1) * u[row]) in float64 (random.uniform's own arithmetic; 0.1 for a silent
+ * row), out = (int16) trunc(x * gain) as numpy's astype(int16) converts it -- bit-exact with the original.
+ * out_i16 (n, t); out_f32 is l3_op_preprocess of it; either may be NULL.  gains: n doubles, always written. */
+int l3_op_augment_audio(int device, const int16_t *i16, int n, int t, const double *u, int16_t *out_i16, float *out_f32,
+                        double *gains);
 
 /* ---- Downstream MLP classifier (classifier/train.py:230-391) ------------------------------------------------------------------
  * construct_mlp_model (train.py:230-257): Dense(512, relu) -> Dense(128, relu) -> Dense(C, softmax), kernel_regularizer

@@ -15,10 +15,10 @@ LIBPATH = os.path.join(LIBDIR, 'libl3hip.so')
 # F(2x2,3x3) = l3_config.fp32_conv F2X2 + the dispatch, F(3x3,2x2) weight gradient, direct implicit GEMM for the DFT and every
 # geometry Winograd does not take), mixed precision (halo forward / data gradient, transpose-read weight gradient, the dispatch +
 # fp32-tensor entry points), first layers, BatchNorm / pool, head / loss / Adam, front-end, clip framing, resampling, engine, operator
-# entry points, RCCL, the downstream MLP and SVM classifiers, the VGGish baseline features.
+# entry points, RCCL, the downstream MLP and SVM classifiers, the VGGish baseline features, training-set augmentation.
 SOURCES = ['conv.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_bf16.hip', 'conv_bf16_halo.hip', 'conv_wgrad_bf16.hip', 'conv_wgrad_wino.hip',
            'conv_first.hip', 'elementwise.hip', 'bn_fused.hip', 'frontend.hip', 'clips.hip', 'resample.hip', 'engine.hip', 'ops.hip',
-           'comm.hip', 'mlp.hip', 'svm.hip', 'vggish.hip']
+           'comm.hip', 'mlp.hip', 'svm.hip', 'vggish.hip', 'augment.hip']
 # Measured-and-rejected kernel variants (split-bf16 fp32 convolutions, flat-tile MODE 5, tap-split bf16 weight gradient; round 6: the
 # filter-in-registers 64-channel halo kernel, the split-bf16 first convolution): records of negative results (profiles/r05_bx6_ablations.txt,
 # r05_bf16_conv_notes.txt, r06_halo64_regfilter.txt, r06_first_conv_mfma.txt), NOT product paths.  L3_BUILD_EXPERIMENTS=1 compiles them

@@ -80,6 +80,9 @@ SIGNATURES = {
     'l3_upload_batch_raw': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'l3_tower_step': (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     'l3_stage_batch_raw': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_upload_batch_raw_aug': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_stage_batch_raw_aug': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_batch_gains': (C.c_int, [C.c_void_p, C.c_void_p]),
     'l3_step_forward': (C.c_int, [C.c_void_p, C.c_int]),
     'l3_step_bucket_count': (C.c_int, [C.c_void_p]),
     'l3_step_backward_bucket': (C.c_int, [C.c_void_p, C.c_int]),
@@ -134,6 +137,8 @@ SIGNATURES = {
     'l3_op_bn_stats_from_partials': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_float,
                                                C.c_void_p, C.c_void_p]),
     'l3_op_preprocess': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_op_augment_video': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_op_augment_audio': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # downstream MLP classifier (csrc/mlp.hip)
     'l3_mlp_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.POINTER(C.c_void_p)]),
     'l3_mlp_destroy': (None, [C.c_void_p]),
@@ -403,6 +408,34 @@ class Engine(object):
         a = np.ascontiguousarray(audio_i16, dtype=np.int16)
         l = np.ascontiguousarray(labels_i32, dtype=np.int32)
         check(self.lib.l3_stage_batch_raw(self.h, _ptr(v), _ptr(a), _ptr(l)), self.h)
+
+    def _aug_args(self, params, u):
+        p, g = augment_records(params), np.ascontiguousarray(u, dtype=np.float64)
+        if len(p) != self.batch or len(g) != self.batch:
+            raise ValueError('%d augmentation records and %d gain draws for a batch of %d' % (len(p), len(g), self.batch))
+        return p, g
+
+    def upload_batch_raw_aug(self, video_u8, audio_i16, labels_i32, params, u):
+        """upload_batch_raw with the batch augmented on the way (data/avc/sample.py:146-162,241-281)."""
+        v = np.ascontiguousarray(video_u8, dtype=np.uint8)
+        a = np.ascontiguousarray(audio_i16, dtype=np.int16)
+        l = np.ascontiguousarray(labels_i32, dtype=np.int32)
+        p, g = self._aug_args(params, u)
+        check(self.lib.l3_upload_batch_raw_aug(self.h, _ptr(v), _ptr(a), _ptr(l), _ptr(p), _ptr(g)), self.h)
+
+    def stage_batch_raw_aug(self, video_u8, audio_i16, labels_i32, params, u):
+        """stage_batch_raw with the records; the adopting step augments the batch in place of scaling it."""
+        v = np.ascontiguousarray(video_u8, dtype=np.uint8)
+        a = np.ascontiguousarray(audio_i16, dtype=np.int16)
+        l = np.ascontiguousarray(labels_i32, dtype=np.int32)
+        p, g = self._aug_args(params, u)
+        check(self.lib.l3_stage_batch_raw_aug(self.h, _ptr(v), _ptr(a), _ptr(l), _ptr(p), _ptr(g)), self.h)
+
+    def batch_gains(self):
+        """Audio gains of the augmented batch the engine holds (waits for the device)."""
+        out = np.empty(self.batch, np.float64)
+        check(self.lib.l3_batch_gains(self.h, _ptr(out)), self.h)
+        return out
 
     def tower_step(self, tower, backward=True):
         """One tower alone ('vision' | 'audio') on the resident batch: training-mode forward (+ backward
@@ -754,6 +787,54 @@ def op_preprocess(video_u8=None, audio_i16=None, device=0):
     check(lib.l3_op_preprocess(device, _ptr(v), 0 if v is None else v.size, _ptr(vo),
                                _ptr(a), 0 if a is None else a.size, _ptr(ao)))
     return vo, ao
+
+
+# l3_augment_params of include/l3hip.h
+AUGMENT_RECORD = np.dtype([('start_x', np.int32), ('start_y', np.int32), ('flip', np.int32), ('sat_first', np.int32),
+                           ('saturation', np.float32), ('brightness', np.float32)])
+
+
+def augment_records(params):
+    """The fields of l3_augment_params out of any structured array that has them, packed as the library reads them."""
+    params = np.asarray(params)
+    rec = np.empty(params.shape, AUGMENT_RECORD)
+    for name in AUGMENT_RECORD.names:
+        rec[name] = params[name]
+    return rec
+
+
+def op_augment_video(video_u8, params, out='u8', device=0):
+    """(N, H, W, 3) uint8 frames -> (N, 224, 224, 3) augmented: out = 'u8' the stored byte, 'f32' the engine's float, 'both'."""
+    lib = load()
+    v = np.ascontiguousarray(video_u8, dtype=np.uint8)
+    if v.ndim != 4 or v.shape[3] != 3:
+        raise ValueError('frames must be (N, H, W, 3), got %r' % (v.shape,))
+    p = augment_records(params)
+    if p.shape != (v.shape[0],):
+        raise ValueError('%d frames but %r augmentation records' % (v.shape[0], p.shape))
+    n, h, w = v.shape[:3]
+    o8 = np.empty((n, 224, 224, 3), np.uint8) if out in ('u8', 'both') else None
+    of = np.empty((n, 224, 224, 3), np.float32) if out in ('f32', 'both') else None
+    if o8 is None and of is None:
+        raise ValueError("out must be 'u8', 'f32' or 'both'")
+    check(lib.l3_op_augment_video(device, _ptr(v), n, h, w, _ptr(p), _ptr(o8), _ptr(of)))
+    return (o8, of) if out == 'both' else (o8 if of is None else of)
+
+
+def op_augment_audio(audio_i16, u, out='i16', device=0):
+    """(N, T) int16 rows and the draws u (N,) -> (augmented rows, gains): out = 'i16', 'f32' or 'both'."""
+    lib = load()
+    a = np.ascontiguousarray(audio_i16, dtype=np.int16)
+    g = np.ascontiguousarray(u, dtype=np.float64)
+    if a.ndim != 2 or g.shape != (a.shape[0],):
+        raise ValueError('rows must be (N, T) with one draw each, got %r and %r' % (a.shape, g.shape))
+    oi = np.empty(a.shape, np.int16) if out in ('i16', 'both') else None
+    of = np.empty(a.shape, np.float32) if out in ('f32', 'both') else None
+    if oi is None and of is None:
+        raise ValueError("out must be 'i16', 'f32' or 'both'")
+    gains = np.empty(a.shape[0], np.float64)
+    check(lib.l3_op_augment_audio(device, _ptr(a), a.shape[0], a.shape[1], _ptr(g), _ptr(oi), _ptr(of), _ptr(gains)))
+    return ((oi, of) if out == 'both' else (oi if of is None else of)), gains
 
 
 # ---- downstream MLP classifier (classifier/train.py:230-391; csrc/mlp.hip) ---------------------------------------------------------

@@ -200,6 +200,11 @@ struct l3_engine {
     bool ev_step_set[2] = {false, false};
     int64_t steps_enqueued = 0;
     bool staged = false, adopted_once = false;
+    // l3_upload_batch_raw_aug / l3_stage_batch_raw_aug: the records and draws of the current and of the staged batch, the gains of
+    // the current one (allocated by the first augmented batch)
+    l3::AugmentParams *aug_params = nullptr, *nxt_aug_params = nullptr;
+    double *aug_u = nullptr, *nxt_aug_u = nullptr, *aug_gains = nullptr;
+    bool staged_aug = false, gains_valid = false;
     // head
     int nv = 0, na = 0, head = 0;
     int p_w1 = -1, p_b1 = -1, p_w2 = -1, p_b2 = -1;
@@ -1707,6 +1712,7 @@ int read_results(l3_engine* e, float* loss, float* acc, float* probs, float* log
 int upload_inputs(l3_engine* e, const float* video, const float* audio, const float* labels) {
     const int B = e->B;
     e->staged = false;      // an explicit upload supersedes a staged batch
+    e->gains_valid = false;
     if (video) HIPCHK(e, hipMemcpyAsync(e->video, video, (size_t)B * 224 * 224 * 3 * 4, hipMemcpyHostToDevice, e->stream));
     if (audio) HIPCHK(e, hipMemcpyAsync(e->audio, audio, (size_t)B * AUDIO_T * 4, hipMemcpyHostToDevice, e->stream));
     if (labels) HIPCHK(e, hipMemcpyAsync(e->labels, labels, (size_t)B * 2 * 4, hipMemcpyHostToDevice, e->stream));
@@ -2039,6 +2045,7 @@ int l3_upload_batch_raw(l3_engine* e, const uint8_t* video_u8, const int16_t* au
     HIPCHK(e, hipSetDevice(e->cfg.device));
     const int B = e->B;
     e->staged = false;      // an explicit upload supersedes a staged batch
+    e->gains_valid = false;
     if (video_u8) {
         HIPCHK(e, hipMemcpyAsync(e->raw_video, video_u8, (size_t)B * 224 * 224 * 3, hipMemcpyHostToDevice, e->stream));
         preprocess_video(e->raw_video, e->video, (int64_t)B * 224 * 224 * 3, e->stream);
@@ -2055,9 +2062,55 @@ int l3_upload_batch_raw(l3_engine* e, const uint8_t* video_u8, const int16_t* au
     return L3_OK;
 }
 
-int l3_stage_batch_raw(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32) {
-    if (!e || !video_u8 || !audio_i16 || !labels_i32) return L3_EINVAL;
+// the device buffers of the augmentation records; the engine's frames are already 224 x 224, so a record must not move the crop
+static int aug_prepare(l3_engine* e, const l3_augment_params* params, const double* u) {
+    if (!params || !u) {
+        e->err = "augmented batch without its parameter records or gain draws";
+        return L3_EINVAL;
+    }
+    for (int i = 0; i < e->B; ++i)
+        if (params[i].start_x != 0 || params[i].start_y != 0) {
+            e->err = "augmentation record " + std::to_string(i) + ": the engine's frames are 224 x 224, the crop must start at (0, 0)";
+            return L3_EINVAL;
+        }
+    if (e->aug_gains) return L3_OK;
+    int rc;
+    const size_t B = (size_t)e->B;
+    if ((rc = dev_alloc_t(e, &e->aug_params, B))) return rc;
+    if ((rc = dev_alloc_t(e, &e->nxt_aug_params, B))) return rc;
+    if ((rc = dev_alloc_t(e, &e->aug_u, B))) return rc;
+    if ((rc = dev_alloc_t(e, &e->nxt_aug_u, B))) return rc;
+    return dev_alloc_t(e, &e->aug_gains, B);
+}
+
+// data/avc/sample.py:146-162,241-281 on the batch, in the pass that l3_upload_batch_raw spends on train.py:186,189
+int l3_upload_batch_raw_aug(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
+                            const l3_augment_params* params, const double* u) {
+    if (!e) return L3_EINVAL;
+    if (!video_u8 || !audio_i16 || !labels_i32) {
+        e->err = "l3_upload_batch_raw_aug: NULL batch pointer";
+        return L3_EINVAL;
+    }
     HIPCHK(e, hipSetDevice(e->cfg.device));
+    int rc = aug_prepare(e, params, u);
+    if (rc) return rc;
+    const int B = e->B;
+    e->staged = false;      // an explicit upload supersedes a staged batch
+    HIPCHK(e, hipMemcpyAsync(e->aug_params, params, (size_t)B * sizeof(l3::AugmentParams), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->aug_u, u, (size_t)B * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->raw_video, video_u8, (size_t)B * 224 * 224 * 3, hipMemcpyHostToDevice, e->stream));
+    augment_video(e->raw_video, B, 224, 224, e->aug_params, nullptr, e->video, e->stream);
+    HIPCHK(e, hipMemcpyAsync(e->raw_audio, audio_i16, (size_t)B * AUDIO_T * 2, hipMemcpyHostToDevice, e->stream));
+    augment_audio(e->raw_audio, B, AUDIO_T, e->aug_u, nullptr, e->audio, e->aug_gains, e->stream);
+    HIPCHK(e, hipMemcpyAsync(e->raw_labels, labels_i32, (size_t)B * 2 * 4, hipMemcpyHostToDevice, e->stream));
+    labels_onehot(e->raw_labels, e->labels, (int64_t)B * 2, e->stream);
+    HIPCHK(e, l3::stream_wait(e->stream));
+    e->gains_valid = true;
+    return L3_OK;
+}
+
+static int stage_batch(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
+                       const l3_augment_params* params, const double* u) {
     const int B = e->B;
     if (!e->copy_stream) {
         HIPCHK(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
@@ -2075,9 +2128,33 @@ int l3_stage_batch_raw(l3_engine* e, const uint8_t* video_u8, const int16_t* aud
     HIPCHK(e, hipMemcpyAsync(e->nxt_video, video_u8, (size_t)B * 224 * 224 * 3, hipMemcpyHostToDevice, e->copy_stream));
     HIPCHK(e, hipMemcpyAsync(e->nxt_audio, audio_i16, (size_t)B * AUDIO_T * 2, hipMemcpyHostToDevice, e->copy_stream));
     HIPCHK(e, hipMemcpyAsync(e->nxt_labels, labels_i32, (size_t)B * 2 * 4, hipMemcpyHostToDevice, e->copy_stream));
+    if (params) {
+        HIPCHK(e, hipMemcpyAsync(e->nxt_aug_params, params, (size_t)B * sizeof(l3::AugmentParams), hipMemcpyHostToDevice, e->copy_stream));
+        HIPCHK(e, hipMemcpyAsync(e->nxt_aug_u, u, (size_t)B * sizeof(double), hipMemcpyHostToDevice, e->copy_stream));
+    }
     HIPCHK(e, hipEventRecord(e->ev_staged, e->copy_stream));
     e->staged = true;
+    e->staged_aug = params != nullptr;
     return L3_OK;
+}
+
+int l3_stage_batch_raw(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32) {
+    if (!e || !video_u8 || !audio_i16 || !labels_i32) return L3_EINVAL;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    return stage_batch(e, video_u8, audio_i16, labels_i32, nullptr, nullptr);
+}
+
+int l3_stage_batch_raw_aug(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
+                           const l3_augment_params* params, const double* u) {
+    if (!e) return L3_EINVAL;
+    if (!video_u8 || !audio_i16 || !labels_i32) {
+        e->err = "l3_stage_batch_raw_aug: NULL batch pointer";
+        return L3_EINVAL;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    int rc = aug_prepare(e, params, u);
+    if (rc) return rc;
+    return stage_batch(e, video_u8, audio_i16, labels_i32, params, u);
 }
 
 // a staged batch becomes the current one: in stream order behind the previous step, which still read
@@ -2086,12 +2163,30 @@ static int adopt_staged(l3_engine* e) {
     if (!e->staged) return L3_OK;
     const int B = e->B;
     HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_staged, 0));
-    preprocess_video(e->nxt_video, e->video, (int64_t)B * 224 * 224 * 3, e->stream);
-    preprocess_audio(e->nxt_audio, e->audio, (int64_t)B * AUDIO_T, e->stream);
+    if (e->staged_aug) {
+        augment_video(e->nxt_video, B, 224, 224, e->nxt_aug_params, nullptr, e->video, e->stream);
+        augment_audio(e->nxt_audio, B, AUDIO_T, e->nxt_aug_u, nullptr, e->audio, e->aug_gains, e->stream);
+    } else {
+        preprocess_video(e->nxt_video, e->video, (int64_t)B * 224 * 224 * 3, e->stream);
+        preprocess_audio(e->nxt_audio, e->audio, (int64_t)B * AUDIO_T, e->stream);
+    }
+    e->gains_valid = e->staged_aug;
     labels_onehot(e->nxt_labels, e->labels, (int64_t)B * 2, e->stream);
     HIPCHK(e, hipEventRecord(e->ev_adopted, e->stream));
     e->adopted_once = true;
     e->staged = false;
+    return L3_OK;
+}
+
+int l3_batch_gains(l3_engine* e, double* gains) {
+    if (!e || !gains) return L3_EINVAL;
+    if (!e->gains_valid) {
+        e->err = "l3_batch_gains: the current batch was not augmented";
+        return L3_ESTATE;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, l3::stream_wait(e->stream));
+    HIPCHK(e, hipMemcpy(gains, e->aug_gains, (size_t)e->B * sizeof(double), hipMemcpyDeviceToHost));
     return L3_OK;
 }
 

@@ -240,6 +240,22 @@ void preprocess_video(const uint8_t* u8, float* out, int64_t n, hipStream_t s);
 void preprocess_audio(const int16_t* pcm, float* out, int64_t n, hipStream_t s);
 void labels_onehot(const int32_t* lab, float* out, int64_t n, hipStream_t s);
 
+// training-set augmentation (data/avc/sample.py:24-69,117-166,169-283; csrc/augment.hip).  One record per sample, the layout of
+// l3_augment_params (include/l3hip.h).
+struct AugmentParams {
+    int32_t start_x, start_y, flip, sat_first;      // crop row / column, mirror the columns, saturation before brightness
+    float saturation, brightness;                   // factor on S of HSV; delta added to the [0, 1] image
+};
+constexpr int AUG_CROP = 224;
+// u8 [N, H, W, 3] -> crop, flip, colour ops, quantise: out_u8 and / or out_f32 [N, 224, 224, 3] (out_f32 = preprocess_video of out_u8).
+// The caller has checked every record against (H, W); u8 is 4-byte aligned.
+void augment_video(const uint8_t* u8, int N, int H, int W, const AugmentParams* params, uint8_t* out_u8, float* out_f32,
+                   hipStream_t s);
+// int16 [N, T] and the uniform draws u[N] -> gain from the row's own peak, applied in double: out_i16 and / or out_f32
+// (= preprocess_audio of out_i16), and gains[N].  The rows are 2-byte aligned at least; 16-byte rows take the vector path.
+void augment_audio(const int16_t* pcm, int N, int T, const double* u, int16_t* out_i16, float* out_f32, double* gains,
+                   hipStream_t s);
+
 // audio front-end (kapre Spectrogram / Melspectrogram)
 struct FrontendCfg {
     int n_dft, n_hop, pad_left, n_frames, n_freq, n_mels;   // n_freq = n_dft/2+1

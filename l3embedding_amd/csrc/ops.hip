@@ -470,6 +470,57 @@ int l3_op_preprocess(int device, const uint8_t* video_u8, int64_t nv, float* vid
     return sc.status();
 }
 
+static_assert(sizeof(l3_augment_params) == sizeof(AugmentParams) && sizeof(AugmentParams) == 24, "one record layout on both sides");
+
+int l3_op_augment_video(int device, const uint8_t* u8, int n, int h, int w, const l3_augment_params* params, uint8_t* out_u8,
+                        float* out_f32) {
+    if (!u8 || !params || (!out_u8 && !out_f32) || n <= 0 || h < AUG_CROP || w < AUG_CROP) {
+        set_op_error("l3_op_augment_video: NULL pointer, n <= 0 or a frame smaller than 224 x 224");
+        return L3_EINVAL;
+    }
+    for (int i = 0; i < n; ++i)
+        if (params[i].start_x < 0 || params[i].start_x > h - AUG_CROP || params[i].start_y < 0 || params[i].start_y > w - AUG_CROP) {
+            set_op_error("l3_op_augment_video: record " + std::to_string(i) + ": crop start (" + std::to_string(params[i].start_x) +
+                         ", " + std::to_string(params[i].start_y) + ") outside a " + std::to_string(h) + " x " + std::to_string(w) +
+                         " frame");
+            return L3_EINVAL;
+        }
+    Scope sc(device);
+    if (!sc.ok) return L3_EHIP;
+    const size_t n_out = (size_t)n * AUG_CROP * AUG_CROP * 3;
+    uint8_t* d_in = sc.put(u8, (size_t)n * h * w * 3);
+    AugmentParams* d_par = sc.put(reinterpret_cast<const AugmentParams*>(params), (size_t)n);
+    uint8_t* d_u8 = out_u8 ? sc.alloc<uint8_t>(n_out) : nullptr;
+    float* d_f32 = out_f32 ? sc.alloc<float>(n_out) : nullptr;
+    if (!sc.ok) return L3_ENOMEM;
+    augment_video(d_in, n, h, w, d_par, d_u8, d_f32, sc.s);
+    if (out_u8) sc.get(out_u8, d_u8, n_out);
+    if (out_f32) sc.get(out_f32, d_f32, n_out);
+    return sc.status();
+}
+
+int l3_op_augment_audio(int device, const int16_t* i16, int n, int t, const double* u, int16_t* out_i16, float* out_f32,
+                        double* gains) {
+    if (!i16 || !u || !gains || (!out_i16 && !out_f32) || n <= 0 || t <= 0) {
+        set_op_error("l3_op_augment_audio: NULL pointer or an empty batch");
+        return L3_EINVAL;
+    }
+    Scope sc(device);
+    if (!sc.ok) return L3_EHIP;
+    const size_t cnt = (size_t)n * t;
+    int16_t* d_in = sc.put(i16, cnt);
+    double* d_u = sc.put(u, (size_t)n);
+    double* d_g = sc.alloc<double>((size_t)n);
+    int16_t* d_i16 = out_i16 ? sc.alloc<int16_t>(cnt) : nullptr;
+    float* d_f32 = out_f32 ? sc.alloc<float>(cnt) : nullptr;
+    if (!sc.ok) return L3_ENOMEM;
+    augment_audio(d_in, n, t, d_u, d_i16, d_f32, d_g, sc.s);
+    if (out_i16) sc.get(out_i16, d_i16, cnt);
+    if (out_f32) sc.get(out_f32, d_f32, cnt);
+    sc.get(gains, d_g, (size_t)n);
+    return sc.status();
+}
+
 int l3_op_gather_frames(int device, const float* samples, int64_t n_samples, const int64_t* table, int64_t n_frames,
                         float* frames) {
     if (!samples || !table || !frames || n_samples < 0 || n_frames < 0) {

@@ -415,6 +415,15 @@ class L3Model(object):
         lo, hi = get_slice_bounds(len(v), self.replicas, dist.get_rank())
         return v[lo:hi], a[lo:hi], (None if y is None else y[lo:hi]), len(v)
 
+    def _split_augment(self, x):
+        """This rank's rows of the augmentation parameters a training batch carries (augment.AugmentedInputs; None for a plain
+        batch).  The rows are those of the global batch, cut with the bounds `_split` cuts the arrays with."""
+        params = getattr(x, 'augment', None)
+        if params is None or self.replicas <= 1:
+            return params
+        lo, hi = get_slice_bounds(len(params), self.replicas, self._dist().get_rank())
+        return params[lo:hi]
+
     @staticmethod
     def _is_raw(v, a):
         """uint8 frames + int16 PCM as stored in the HDF5 blobs (data/avc/sample.py:371-377)."""
@@ -436,6 +445,10 @@ class L3Model(object):
             raise RuntimeError('You must compile a model before training/testing. Use `model.compile(optimizer, loss)`.')
         v, a, l, gb = self._split(x, y)
         raw = self._is_raw(v, a)
+        aug = self._split_augment(x)
+        if aug is not None and not raw:
+            raise ValueError('only raw batches (uint8 video, int16 audio) can be augmented: the arithmetic of '
+                             'data/avc/sample.py is defined on the stored dtypes')
         dp = self.replicas > 1
         e = self._ensure_engine(len(v), global_batch=gb if dp else 0)
         if dp and e._trainer is None:
@@ -447,7 +460,9 @@ class L3Model(object):
             else:
                 e._trainer = DataParallelTrainer(e, self.device, self.replicas, self._dist().get_rank(), stream=self._tstream)
         if not staged:
-            if raw:      # stored dtypes straight to the GPU; train.py:186,189 scaling happens there, bit-exact
+            if aug is not None:      # ... and augmented in that same pass (data/avc/sample.py:146-162,241-281)
+                e.upload_batch_raw_aug(v, a, np.asarray(l).astype(np.int32), aug, aug['u_gain'])
+            elif raw:      # stored dtypes straight to the GPU; train.py:186,189 scaling happens there, bit-exact
                 e.upload_batch_raw(v, a, np.asarray(l).astype(np.int32))
             else:
                 e.upload_batch(v, a, l)
@@ -485,7 +500,11 @@ class L3Model(object):
         v, a, l, _ = self._split(x, y)
         if len(v) != n_local or not self._is_raw(v, a):
             return False
-        e.stage_batch_raw(v, a, np.asarray(l).astype(np.int32))
+        aug = self._split_augment(x)
+        if aug is not None:
+            e.stage_batch_raw_aug(v, a, np.asarray(l).astype(np.int32), aug, aug['u_gain'])
+        else:
+            e.stage_batch_raw(v, a, np.asarray(l).astype(np.int32))
         return True
 
     def _finish_train(self):

@@ -125,7 +125,33 @@ def train(train_data_dir, validation_data_dir, output_dir,
     """Train an AVC model (train.py:218-421).  With `gpus > 1` this is one rank of a
     `torch.distributed` job (one process per GPU): every rank trains on its shard of each batch, rank 0
     owns the run directory."""
-    call_args = dict(locals())
+    return _train(**locals())
+
+
+def train_augmented(train_data_dir, validation_data_dir, output_dir, augment_random_state=20180123, **train_args):
+    """`train()` on un-augmented blobs with every training batch augmented on the GPU as 02_generate_samples.py --augment
+    augments a sample (data/avc/sample.py:146-162,241-281; `augment`), a fresh draw per batch from
+    random.Random(augment_random_state).  Validation batches are not augmented.  `train_args`: the keyword arguments of
+    `train()`.  config.json also records `augment` and `augment_random_state`."""
+    import inspect
+    from .augment import AugmentingFeed
+    args = {k: v.default for k, v in inspect.signature(train).parameters.items() if v.default is not inspect.Parameter.empty}
+    unknown = sorted(set(train_args) - set(args))
+    if unknown:
+        raise TypeError('train_augmented() got unexpected keyword arguments: %s' % ', '.join(unknown))
+    args.update(train_args)
+    return _train(train_data_dir, validation_data_dir, output_dir, **args,
+                  wrap_train_feed=lambda batches: AugmentingFeed(batches, augment_random_state),
+                  extra_config=dict(augment=True, augment_random_state=augment_random_state))
+
+
+def _train(train_data_dir, validation_data_dir, output_dir, num_epochs, train_epoch_size, validation_epoch_size,
+           train_batch_size, validation_batch_size, model_type, random_state, learning_rate, verbose, checkpoint_interval,
+           log_path, disable_logging, gpus, continue_model_dir, gsheet_id, google_dev_app_name,
+           wrap_train_feed=None, extra_config=None):
+    """The body of `train()`.  wrap_train_feed: a wrapper around the generator of training batches (train_augmented);
+    extra_config: entries added to config.json."""
+    call_args = {k: v for k, v in locals().items() if k not in ('wrap_train_feed', 'extra_config')}
     if not disable_logging and log_path:
         handler = logging.FileHandler(log_path)
         handler.setFormatter(logging.Formatter('%(asctime)s - %(name)s - %(levelname)s - %(message)s'))
@@ -155,7 +181,7 @@ def train(train_data_dir, validation_data_dir, output_dir,
     LOGGER.info('Model files can be found in "%s"', model_dir)
 
     config = dict(call_args, username=getpass.getuser(), model_id=model_id, model_dir=model_dir, git_commit=_git_commit(),
-                  backend='libl3hip (MI355X)')
+                  backend='libl3hip (MI355X)', **(extra_config or {}))
     LOGGER.info('Training with the following arguments: %s', config)
     if writes:
         with open(os.path.join(model_dir, ARTEFACTS['config']), 'w') as fh:
@@ -181,10 +207,12 @@ def train(train_data_dir, validation_data_dir, output_dir,
     val_feed = blobfeed.RestartingFeed(
         lambda: blobfeed.BlobFeed(validation_data_dir, validation_batch_size, random_state, **shard), validation_epoch_size)
 
+    train_batches = blobfeed.as_model_inputs(train_feed, train_batch_size, sharded=bool(shard))
+    if wrap_train_feed is not None:
+        train_batches = wrap_train_feed(train_batches)
     LOGGER.info('Fitting model...')
     try:
-        history = m.fit_generator(blobfeed.as_model_inputs(train_feed, train_batch_size, sharded=bool(shard)),
-                                  train_epoch_size, num_epochs,
+        history = m.fit_generator(train_batches, train_epoch_size, num_epochs,
                                   validation_data=blobfeed.as_model_inputs(val_feed, validation_batch_size, sharded=bool(shard)),
                                   validation_steps=validation_epoch_size, callbacks=callbacks,
                                   verbose=1 if verbose else 2, initial_epoch=first_epoch)
