@@ -20,6 +20,9 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
+// C/D map of the 32x32 f32 MFMA: register i of lane l holds row (i & 3) + 8 (i >> 2) + 4 (l >> 5), column l & 31
+__device__ __forceinline__ int mfma_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+
 // Bijective XCD-aware remap: the hardware places workgroup b on XCD b % 8; give every XCD a contiguous
 // range of logical tiles so neighbouring tiles (shared halo rows, shared filter slice) hit the same
 // private L2.

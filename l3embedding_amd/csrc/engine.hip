@@ -152,7 +152,7 @@ struct l3_engine {
     BnMovingEntry* bn_table = nullptr;    // do_update: every BatchNormalization's moving mean / variance triple
     int bn_table_n = 0, bn_table_max_c = 0;
     std::string err;
-    std::vector<void*> allocs;
+    l3::DeviceBufs bufs;          // every device buffer of the engine (freed by l3_destroy, in its place among the streams)
 
     std::vector<Param> params;            // keras get_weights order
     std::map<std::string, int> pindex;
@@ -217,14 +217,7 @@ struct l3_engine {
     float* clip_samples = nullptr;
     int64_t* clip_table = nullptr;
     size_t clip_samples_cap = 0, clip_table_cap = 0;
-    // l3_embed_audio_clips_resampled: the native-rate clips, their descriptors, the block table and the filter tables
-    float* rs_native = nullptr;
-    l3::ResampleClip* rs_clips = nullptr;
-    int64_t* rs_blocks = nullptr;
-    double* rs_tabs = nullptr;
-    size_t rs_native_cap = 0, rs_clips_cap = 0, rs_blocks_cap = 0, rs_tabs_cap = 0;
-    l3::ResampleTables rs_tables;               // host tables, kept across calls; rs_tabs holds generation rs_tabs_gen of them
-    uint64_t rs_tabs_gen = ~(uint64_t)0;
+    l3::ResampleStage resample;         // l3_embed_audio_clips_resampled: native-rate clips -> clip_samples
     bool last_training = false;
     bool fwd_done = false;
 
@@ -270,37 +263,20 @@ namespace {
         }                                                                                     \
     } while (0)
 
-int dev_alloc(l3_engine* e, void** p, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    hipError_t st = hipMalloc(p, bytes);
-    if (st != hipSuccess) {
-        e->err = "hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(st);
-        return L3_ENOMEM;
-    }
-    e->allocs.push_back(*p);
-    return L3_OK;
-}
+// every allocation failure of the engine reads "hipMalloc(bytes): ..." in l3_last_error
 template <class T>
 int dev_alloc_t(l3_engine* e, T** p, size_t count) {
-    return dev_alloc(e, reinterpret_cast<void**>(p), count * sizeof(T));
+    if ((*p = e->bufs.alloc<T>(count)) != nullptr) return L3_OK;
+    e->err = "hipMalloc(" + std::to_string(l3::DeviceBufs::bytes_of<T>(count)) + "): " + hipGetErrorString(hipGetLastError());
+    return L3_ENOMEM;
 }
 // a buffer that grows on demand: the old one is freed (hipFree waits for the device) when `count` exceeds `*cap`
 template <class T>
 int dev_grow_t(l3_engine* e, T** p, size_t* cap, size_t count) {
     if (count <= *cap) return L3_OK;
-    if (*p != nullptr) {
-        for (auto it = e->allocs.begin(); it != e->allocs.end(); ++it)
-            if (*it == (void*)*p) {
-                e->allocs.erase(it);
-                break;
-            }
-        (void)hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-    }
-    int rc = dev_alloc_t(e, p, count);
-    if (rc == L3_OK) *cap = count;
-    return rc;
+    if (e->bufs.grow(p, cap, count)) return L3_OK;
+    e->err = "hipMalloc(" + std::to_string(l3::DeviceBufs::bytes_of<T>(count)) + "): " + hipGetErrorString(hipGetLastError());
+    return L3_ENOMEM;
 }
 
 // ---- TF padding helpers ---------------------------------------------------------------------
@@ -1640,11 +1616,10 @@ int ensure_bn_table(l3_engine* e) {
             }
     e->bn_table_n = (int)tab.size();
     e->bn_pack_floats = off;
-    void* dev = nullptr;
-    HIPCHK(e, hipMalloc(&dev, (tab.size() + 1) * sizeof(BnMovingEntry)));
-    e->allocs.push_back(dev);
+    BnMovingEntry* dev = nullptr;
+    if (int rc = dev_alloc_t(e, &dev, tab.size() + 1)) return rc;
     HIPCHK(e, hipMemcpy(dev, tab.data(), tab.size() * sizeof(BnMovingEntry), hipMemcpyHostToDevice));
-    e->bn_table = (BnMovingEntry*)dev;
+    e->bn_table = dev;
     return L3_OK;
 }
 
@@ -1655,7 +1630,7 @@ int bn_stats_pack(l3_engine* e, int world) {
     if (e->bn_pack_floats == 0) return L3_OK;
     if (e->bn_send == nullptr && (rc = dev_alloc_t(e, &e->bn_send, (size_t)e->bn_pack_floats))) return rc;
     if (e->bn_gathered_world < world) {
-        if ((rc = dev_alloc_t(e, &e->bn_gathered, (size_t)e->bn_pack_floats * world))) return rc;      // (the smaller one stays in e->allocs)
+        if ((rc = dev_alloc_t(e, &e->bn_gathered, (size_t)e->bn_pack_floats * world))) return rc;      // (the smaller one stays with e->bufs)
         e->bn_gathered_world = world;
     }
     bn_moving_pack(e->bn_table, e->bn_table_n, e->bn_table_max_c, e->bn_send, e->stream);
@@ -1820,7 +1795,7 @@ int l3_create(const l3_config* cfg, uint64_t seed, l3_engine** out) {
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= cfg->device) {
-        g_create_error = "l3_create: HIP device " + std::to_string(cfg->device) + " not available (libl3hip needs an AMD GPU)";
+        g_create_error = l3::no_gpu_message("l3_create", cfg->device);
         return L3_EHIP;
     }
     l3_engine* e = new l3_engine();
@@ -1891,7 +1866,7 @@ void l3_destroy(l3_engine* e) {
     for (auto ev : e->ev_step)
         if (ev) (void)hipEventDestroy(ev);
     if (e->res_host) (void)hipHostFree(e->res_host);
-    for (void* p : e->allocs) (void)hipFree(p);
+    e->bufs.clear();
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
     for (auto& r : e->prof_recs) {
         (void)hipEventDestroy(r.a);
@@ -2848,39 +2823,11 @@ int l3_embed_audio_clips_resampled(l3_engine* e, const float* native, int64_t n_
     }
     if (n_frames == 0) return L3_OK;
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    l3::ResamplePlan p;
-    // every return below waits for the stream first: the copies enqueued from p and e->rs_tables must have read them
-    struct WaitOnExit {
-        hipStream_t s;
-        ~WaitOnExit() { (void)l3::stream_wait(s); }
-    } wait_on_exit{e->stream};
-    resample_plan(clips, n_clips, AUDIO_T, half_window, n_window, true, &e->rs_tables, &p);
-    const std::vector<double>& tabs = e->rs_tables.tables;
-    const int64_t n_blocks = (int64_t)p.blocks.size() / 2;
-    if ((rc = dev_grow_t(e, &e->rs_native, &e->rs_native_cap, (size_t)(n_native > 0 ? n_native : 1)))) return rc;
-    if ((rc = dev_grow_t(e, &e->rs_clips, &e->rs_clips_cap, p.clips.size() + 1))) return rc;
-    if ((rc = dev_grow_t(e, &e->rs_blocks, &e->rs_blocks_cap, p.blocks.size() + 2))) return rc;
-    if (tabs.size() + 2 > e->rs_tabs_cap) e->rs_tabs_gen = ~(uint64_t)0;          // a new device buffer holds nothing yet
-    if ((rc = dev_grow_t(e, &e->rs_tabs, &e->rs_tabs_cap, tabs.size() + 2))) return rc;
     if ((rc = dev_grow_t(e, &e->clip_samples, &e->clip_samples_cap, (size_t)(n_samples > 0 ? n_samples : 1)))) return rc;
     if ((rc = dev_grow_t(e, &e->clip_table, &e->clip_table_cap, (size_t)n_frames * 3))) return rc;
-    if (n_native > 0)
-        HIPCHK(e, hipMemcpyAsync(e->rs_native, native, (size_t)n_native * 4, hipMemcpyHostToDevice, e->stream));
-    if (!p.clips.empty())
-        HIPCHK(e, hipMemcpyAsync(e->rs_clips, p.clips.data(), p.clips.size() * sizeof(l3::ResampleClip), hipMemcpyHostToDevice,
-                                 e->stream));
-    if (n_blocks > 0)
-        HIPCHK(e, hipMemcpyAsync(e->rs_blocks, p.blocks.data(), p.blocks.size() * 8, hipMemcpyHostToDevice, e->stream));
-    if (!tabs.empty() && e->rs_tabs_gen != e->rs_tables.generation) {         // only a new window scale or window uploads
-        e->rs_tabs_gen = ~(uint64_t)0;
-        HIPCHK(e, hipMemcpyAsync(e->rs_tabs, tabs.data(), tabs.size() * 8, hipMemcpyHostToDevice, e->stream));
-        e->rs_tabs_gen = e->rs_tables.generation;
-    }
-    // samples no clip row writes read as zeros (the frame table only reads inside the clips' ranges)
-    if (n_samples > 0) HIPCHK(e, hipMemsetAsync(e->clip_samples, 0, (size_t)n_samples * 4, e->stream));
-    if (n_blocks > 0)
-        resample_launch(e->rs_native, e->rs_clips, e->rs_blocks, n_blocks, e->rs_tabs, (int)n_window, num_table, e->clip_samples,
-                        e->stream);
+    if ((rc = e->resample.run(native, n_native, clips, n_clips, AUDIO_T, half_window, n_window, num_table, true, e->clip_samples,
+                              n_samples, e->stream, &e->err)))
+        return rc;
     HIPCHK(e, hipMemcpyAsync(e->clip_table, table, (size_t)n_frames * 3 * 8, hipMemcpyHostToDevice, e->stream));
     EmbedSource src;
     src.samples = e->clip_samples;
@@ -2930,10 +2877,7 @@ int l3_get_activation(l3_engine* e, const char* name, float* dst, int64_t numel)
         if (t->d_bf16) {
             std::vector<uint16_t> h((size_t)numel);
             HIPCHK(e, hipMemcpy(h.data(), src, (size_t)numel * 2, hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < numel; ++i) {
-                const uint32_t u = (uint32_t)h[(size_t)i] << 16;
-                memcpy(dst + i, &u, 4);
-            }
+            l3::widen_bf16(dst, h.data(), (size_t)numel);
             return L3_OK;
         }
     }

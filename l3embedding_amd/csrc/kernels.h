@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "host_common.h"
+
 namespace l3 {
 
 struct ConvGeom {
@@ -293,7 +295,6 @@ void db_normalize(float* x, float* smax, int B, int64_t per_sample, int batch_sc
 // frames of whole clips (clips.hip; data/usc/features.py:276-300): out row r (T floats) = samples[start_r + j] where
 // lo_r <= start_r + j < hi_r, else 0; table = rows x {start, lo, hi}; rows >= n_real are zeroed
 void gather_frames(const float* samples, const int64_t* table, float* out, int rows, int n_real, int T, hipStream_t s);
-void set_op_error(const std::string& msg);       // engine.hip: l3_last_error(NULL) of an operator entry point
 // host-side check of such a table against a buffer of n_samples: nullptr if every row is valid, else what is wrong
 inline const char* frame_table_error(const int64_t* table, int64_t n_frames, int64_t n_samples, int64_t* bad_row) {
     const int64_t lim = (int64_t)1 << 62;          // start + j never overflows
@@ -332,10 +333,28 @@ int64_t resample_out_len(int64_t L, int64_t sr_o, int64_t sr_n);     // int(L * 
 // (*bad: the row, -1 for an argument).  copy_equal: rows with sr_orig == sr_new are copied (load_audio skips resampy for them).
 const char* resample_clips_error(const int64_t* clips, int64_t n_clips, int64_t n_native, int64_t sr_new, int64_t n_window,
                                  int num_table, int64_t n_samples, bool copy_equal, int64_t* bad);
-void resample_plan(const int64_t* clips, int64_t n_clips, int64_t sr_new, const double* half_window, int64_t n_window,
-                   bool copy_equal, ResampleTables* tabs, ResamplePlan* p);
-void resample_launch(const float* x, const ResampleClip* clips, const int64_t* blocks, int64_t n_blocks, const double* tabs,
-                     int nwin, int num_table, float* y, hipStream_t s);
+// The whole path from native-rate clips on the host to resampled samples on the device, for every caller of it (the engine, the
+// VGGish handle, the operator): it owns the host tables, the device copies of the native samples, the clip descriptors, the block
+// table and the filter tables, and knows which generation of the tables the device holds.
+struct ResampleStage {
+    // Plans the rows (checked by the caller: resample_clips_error), grows the buffers, uploads, zero-fills d_out[0, n_samples)
+    // and launches on s.  The tables go up again only when their generation moved or their device buffer is new.  The stream has
+    // consumed every host vector of the plan before this returns, on every path (it is waited for after the uploads, before the
+    // launch).  Returns L3_OK, L3_ENOMEM or L3_EHIP with the reason in *err; the device must be current.
+    int run(const float* native, int64_t n_native, const int64_t* clips, int64_t n_clips, int64_t sr_new,
+            const double* half_window, int64_t n_window, int num_table, bool copy_equal, float* d_out, int64_t n_samples,
+            hipStream_t s, std::string* err);
+
+private:
+    ResampleTables tabs;                // kept across calls
+    DeviceBufs bufs;
+    float* d_native = nullptr;
+    ResampleClip* d_clips = nullptr;
+    int64_t* d_blocks = nullptr;
+    double* d_tabs = nullptr;
+    size_t cap_native = 0, cap_clips = 0, cap_blocks = 0, cap_tabs = 0;
+    uint64_t tabs_on_device = ~(uint64_t)0;          // generation of `tabs` that d_tabs holds
+};
 
 // head: dense + softmax + categorical cross-entropy
 void dense_fwd(const float* x, const float* w, const float* b, float* y, int B, int K, int N, int relu,

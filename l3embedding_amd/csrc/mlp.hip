@@ -22,9 +22,6 @@
 
 namespace l3 {
 
-// C/D map of the 32x32 f32 MFMA: register i of lane l holds row (i & 3) + 8 (i >> 2) + 4 (l >> 5), column l & 31
-__device__ __forceinline__ int mfma_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -388,28 +385,10 @@ struct l3_mlp {
     double* acc = nullptr;
     float *xtr = nullptr, *xva = nullptr;
     int64_t ntr = 0, nva = 0, perm_cap = 0, xin_rows = 0;
-    std::vector<void*> owned;
+    DeviceBufs bufs;
 };
 
 namespace {
-int fail(int code, const std::string& msg) {
-    set_op_error(msg);
-    return code;
-}
-template <class T>
-bool dev_alloc(l3_mlp* m, T** p, int64_t count) {
-    void* q = nullptr;
-    if (hipMalloc(&q, (size_t)(count > 0 ? count : 1) * sizeof(T)) != hipSuccess) return false;
-    m->owned.push_back(q);
-    *p = static_cast<T*>(q);
-    return true;
-}
-void dev_free(l3_mlp* m, void* q) {
-    if (!q) return;
-    for (auto& o : m->owned)
-        if (o == q) o = nullptr;
-    (void)hipFree(q);
-}
 float* W(l3_mlp* m, int i) { return m->p + m->off[i]; }
 
 void forward(l3_mlp* m, const float* x, const int* idx, int rows) {
@@ -463,9 +442,7 @@ int l3_mlp_create(int device, int D, int C, int batch, float weight_decay, uint6
     if (C < 2 || C > MLP_MAX_CLASSES) return fail(L3_EINVAL, "l3_mlp_create: class count must be in [2, 64]");
     if (batch <= 0 || batch > MLP_MAX_BATCH) return fail(L3_EINVAL, "l3_mlp_create: batch must be in [1, 4096]");
     if (!(weight_decay >= 0.f)) return fail(L3_EINVAL, "l3_mlp_create: weight_decay must be >= 0");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n || hipSetDevice(device) != hipSuccess)
-        return fail(L3_EHIP, "l3_mlp_create: HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)");
+    if (!device_ok(device)) return fail(L3_EHIP, no_gpu_message("l3_mlp_create", device));
     l3_mlp* m = new l3_mlp();
     m->device = device, m->D = D, m->C = C, m->B = batch, m->wd = weight_decay;
     const int64_t shape[6][2] = {{D, MLP_H1}, {MLP_H1, 1}, {MLP_H1, MLP_H2}, {MLP_H2, 1}, {MLP_H2, C}, {C, 1}};
@@ -483,15 +460,18 @@ int l3_mlp_create(int device, int D, int C, int batch, float weight_decay, uint6
         total_wg = mlp_wgrad_tiles(a);
     }
     m->xin_rows = std::max<int64_t>(32, std::min<int64_t>(MLP_EVAL_ROWS, MLP_PREDICT_FLOATS / D) & ~31);
-    const bool ok = hipStreamCreateWithFlags(&m->s, hipStreamNonBlocking) == hipSuccess && dev_alloc(m, &m->p, m->nparam) &&
-                    dev_alloc(m, &m->m, m->nparam) && dev_alloc(m, &m->v, m->nparam) && dev_alloc(m, &m->h1, (int64_t)rows * MLP_H1) &&
-                    dev_alloc(m, &m->h2, (int64_t)rows * MLP_H2) && dev_alloc(m, &m->z, (int64_t)rows * C) &&
-                    dev_alloc(m, &m->dz, (int64_t)rows * C) && dev_alloc(m, &m->dh1, (int64_t)batch * MLP_H1) &&
-                    dev_alloc(m, &m->dh2, (int64_t)batch * MLP_H2) && dev_alloc(m, &m->part, MLP_PART_FLOATS) &&
-                    dev_alloc(m, &m->w2part, total_wg) && dev_alloc(m, &m->ce, rows) && dev_alloc(m, &m->correct, rows) &&
-                    dev_alloc(m, &m->sq, 4) && dev_alloc(m, &m->sq_scratch, SUMSQ_MAX_SEGS * SUMSQ_BLOCKS) &&
-                    dev_alloc(m, &m->ctr, MLP_FWD_COUNTERS + 1) && dev_alloc(m, &m->yzero, rows) && dev_alloc(m, &m->acc, 2) &&
-                    dev_alloc(m, &m->xin, m->xin_rows * D);
+    DeviceBufs& b = m->bufs;
+    const size_t np = (size_t)m->nparam;
+    m->p = b.alloc<float>(np), m->m = b.alloc<float>(np), m->v = b.alloc<float>(np);
+    m->h1 = b.alloc<float>((size_t)rows * MLP_H1), m->h2 = b.alloc<float>((size_t)rows * MLP_H2);
+    m->z = b.alloc<float>((size_t)rows * C), m->dz = b.alloc<float>((size_t)rows * C);
+    m->dh1 = b.alloc<float>((size_t)batch * MLP_H1), m->dh2 = b.alloc<float>((size_t)batch * MLP_H2);
+    m->part = b.alloc<float>(MLP_PART_FLOATS), m->w2part = b.alloc<float>(total_wg);
+    m->ce = b.alloc<float>(rows), m->correct = b.alloc<float>(rows);
+    m->sq = b.alloc<float>(4), m->sq_scratch = b.alloc<float>(SUMSQ_MAX_SEGS * SUMSQ_BLOCKS);
+    m->ctr = b.alloc<int>(MLP_FWD_COUNTERS + 1), m->yzero = b.alloc<int>(rows), m->acc = b.alloc<double>(2);
+    m->xin = b.alloc<float>((size_t)(m->xin_rows * D));
+    const bool ok = b.ok() && hipStreamCreateWithFlags(&m->s, hipStreamNonBlocking) == hipSuccess;
     if (!ok) {
         l3_mlp_destroy(m);
         return fail(L3_ENOMEM, "l3_mlp_create: device allocation failed");
@@ -523,8 +503,6 @@ void l3_mlp_destroy(l3_mlp* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->s) (void)hipStreamSynchronize(m->s);
-    for (void* q : m->owned)
-        if (q) (void)hipFree(q);
     if (m->s) (void)hipStreamDestroy(m->s);
     delete m;
 }
@@ -555,10 +533,13 @@ int l3_mlp_set_data(l3_mlp* m, const float* X_train, const int32_t* y_train, int
                                        " outside [0, " + std::to_string(m->C) + ")");
     (void)hipSetDevice(m->device);
     (void)hipStreamSynchronize(m->s);
-    for (void* q : {(void*)m->xtr, (void*)m->xva, (void*)m->ytr, (void*)m->yva, (void*)m->perm}) dev_free(m, q);
+    for (void* q : {(void*)m->xtr, (void*)m->xva, (void*)m->ytr, (void*)m->yva, (void*)m->perm}) m->bufs.release(q);
     m->xtr = m->xva = nullptr, m->ytr = m->yva = m->perm = nullptr, m->ntr = m->nva = 0;
-    if (!dev_alloc(m, &m->xtr, n_train * m->D) || !dev_alloc(m, &m->ytr, n_train) || !dev_alloc(m, &m->perm, n_train) ||
-        !dev_alloc(m, &m->xva, std::max<int64_t>(1, n_valid) * m->D) || !dev_alloc(m, &m->yva, std::max<int64_t>(1, n_valid)))
+    const size_t nva = (size_t)std::max<int64_t>(1, n_valid);
+    m->xtr = m->bufs.alloc<float>((size_t)(n_train * m->D)), m->ytr = m->bufs.alloc<int>((size_t)n_train);
+    m->perm = m->bufs.alloc<int>((size_t)n_train);
+    m->xva = m->bufs.alloc<float>(nva * m->D), m->yva = m->bufs.alloc<int>(nva);
+    if (!m->xtr || !m->ytr || !m->perm || !m->xva || !m->yva)
         return fail(L3_ENOMEM, "l3_mlp_set_data: device allocation of " + std::to_string(bytes) + " bytes failed");
     if (hipMemcpyAsync(m->xtr, X_train, n_train * m->D * sizeof(float), hipMemcpyHostToDevice, m->s) != hipSuccess ||
         hipMemcpyAsync(m->ytr, y_train, n_train * sizeof(int32_t), hipMemcpyHostToDevice, m->s) != hipSuccess ||

@@ -18,26 +18,16 @@ namespace {
 using namespace l3;
 
 struct Scope {
-    std::vector<void*> bufs;
+    DeviceBufs bufs;
     hipStream_t s = nullptr;
     bool ok = true;
-    explicit Scope(int device) {
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n <= device || hipSetDevice(device) != hipSuccess) ok = false;
-    }
-    ~Scope() {
-        (void)hipDeviceSynchronize();
-        for (void* p : bufs) (void)hipFree(p);
-    }
+    explicit Scope(int device) : ok(device_ok(device)) {}
+    ~Scope() { (void)hipDeviceSynchronize(); }          // before bufs frees
     template <class T>
     T* alloc(size_t count) {
-        void* p = nullptr;
-        if (hipMalloc(&p, (count ? count : 4) * sizeof(T)) != hipSuccess) {
-            ok = false;
-            return nullptr;
-        }
-        bufs.push_back(p);
-        return static_cast<T*>(p);
+        T* p = bufs.alloc<T>(count);
+        if (!p) ok = false;
+        return p;
     }
     template <class T>
     T* put(const T* host, size_t count) {
@@ -122,10 +112,7 @@ int l3_op_conv2d_fwd_dt(int device, int dtype, const float* x, const float* w, c
                           reinterpret_cast<float*>(yb), g, sc.s, true, nullptr, 0, true);
             std::vector<uint16_t> hy(ny);
             sc.get(hy.data(), yb, ny);
-            for (size_t i = 0; i < ny; ++i) {
-                const uint32_t u = (uint32_t)hy[i] << 16;
-                memcpy(y + i, &u, 4);
-            }
+            widen_bf16(y, hy.data(), ny);
             return sc.status();
         }
         conv_bf16_fwd(reinterpret_cast<const float*>(xb), reinterpret_cast<const float*>(wb), db, dy, g, sc.s, true);
@@ -142,10 +129,7 @@ int l3_op_conv2d_fwd_dt(int device, int dtype, const float* x, const float* w, c
             conv_first_fwd(dx, dw, db, yb, g, sc.s, nullptr, 0, true);
             std::vector<uint16_t> hy(ny);
             sc.get(hy.data(), yb, ny);
-            for (size_t i = 0; i < ny; ++i) {
-                const uint32_t u = (uint32_t)hy[i] << 16;
-                memcpy(y + i, &u, 4);
-            }
+            widen_bf16(y, hy.data(), ny);
             return sc.status();
         }
         conv_first_fwd(dx, dw, db, dy, g, sc.s);
@@ -206,10 +190,7 @@ int l3_op_conv2d_bwd_dt(int device, int dtype, const float* x, const float* w, c
                           reinterpret_cast<float*>(dxb), dg, sc.s, true, nullptr, 0, true);
             std::vector<uint16_t> hx(nx);
             sc.get(hx.data(), dxb, nx);
-            for (size_t i = 0; i < nx; ++i) {
-                const uint32_t u = (uint32_t)hx[i] << 16;
-                memcpy(dx + i, &u, 4);
-            }
+            widen_bf16(dx, hx.data(), nx);
         } else {
             conv_bf16_fwd(reinterpret_cast<const float*>(gb), reinterpret_cast<const float*>(wb), nullptr, d_dx, dg, sc.s, true);
             sc.get(dx, d_dx, nx);
@@ -534,7 +515,7 @@ int l3_op_gather_frames(int device, const float* samples, int64_t n_samples, con
     }
     Scope sc(device);
     if (!sc.ok) {
-        set_op_error("l3_op_gather_frames: HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)");
+        set_op_error(no_gpu_message("l3_op_gather_frames", device));
         return L3_EHIP;
     }
     constexpr int T = 48000;
@@ -564,20 +545,17 @@ static int op_resample(const char* name, int device, const float* x, int64_t n_i
     }
     Scope sc(device);
     if (!sc.ok) {
-        set_op_error(std::string(name) + ": HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)");
+        set_op_error(no_gpu_message(name, device));
         return L3_EHIP;
     }
-    ResamplePlan p;
-    ResampleTables tabs;
-    resample_plan(clips, n_clips, sr_new, half_window, n_window, copy_equal, &tabs, &p);
-    const float* d_x = sc.put(x, (size_t)n_in);
-    const ResampleClip* d_c = sc.put(p.clips.data(), p.clips.size());
-    const int64_t* d_b = sc.put(p.blocks.data(), p.blocks.size());
-    const double* d_t = sc.put(tabs.tables.data(), tabs.tables.size());
     float* d_y = sc.alloc<float>((size_t)n_samples);
     if (!sc.ok) return L3_ENOMEM;
-    if (n_samples > 0 && hipMemset(d_y, 0, (size_t)n_samples * 4) != hipSuccess) return L3_EHIP;
-    resample_launch(d_x, d_c, d_b, (int64_t)p.blocks.size() / 2, d_t, (int)n_window, num_table, d_y, sc.s);
+    ResampleStage stage;          // lives for the call: sc.get below waits for the device before it goes
+    std::string why;
+    if (const int rc = stage.run(x, n_in, clips, n_clips, sr_new, half_window, n_window, num_table, copy_equal, d_y, n_samples, sc.s, &why)) {
+        set_op_error(std::string(name) + ": " + why);
+        return rc;
+    }
     sc.get(y, d_y, (size_t)n_samples);
     return sc.status();
 }
@@ -633,9 +611,8 @@ int mlp_op_check(const char* name, int device, bool ptrs_ok, int rows, int K, in
             set_op_error(std::string(name) + ": idx[" + std::to_string(i) + "] outside [0, n_x)");
             return L3_EINVAL;
         }
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= device || device < 0) {
-        set_op_error(std::string(name) + ": HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)");
+    if (!device_ok(device)) {
+        set_op_error(no_gpu_message(name, device));
         return L3_EHIP;
     }
     return L3_OK;
@@ -953,7 +930,7 @@ extern "C" int l3_op_bn_moving_update(int device, int entries, const int32_t* c,
 namespace {
 int vggish_op_device(const char* name, Scope& sc, int device) {
     if (sc.ok) return L3_OK;
-    set_op_error(std::string(name) + ": HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)");
+    set_op_error(no_gpu_message(name, device));
     return L3_EHIP;
 }
 }  // namespace

@@ -10,7 +10,9 @@
 // this file: the weights and the sums must round as NumPy's float64 arithmetic rounds them (tests/resample_ref.py).
 #include <cstring>
 
+#include "../../include/l3hip.h"
 #include "kernels.h"
+#include "knobs.h"
 
 #pragma clang fp contract(off)
 
@@ -103,6 +105,7 @@ const char* resample_clips_error(const int64_t* clips, int64_t n_clips, int64_t 
     return nullptr;
 }
 
+namespace {
 void resample_plan(const int64_t* clips, int64_t n_clips, int64_t sr_new, const double* half_window, int64_t n_window,
                    bool copy_equal, ResampleTables* tabs, ResamplePlan* p) {
     p->clips.clear();
@@ -151,6 +154,46 @@ void resample_launch(const float* x, const ResampleClip* clips, const int64_t* b
         hipLaunchKernelGGL(resample_kernel, dim3((unsigned)nb), dim3(256), 0, s, x, clips, blocks + 2 * b0,
                            reinterpret_cast<const double2*>(tabs), nwin, num_table, y);
     }
+}
+
+}  // namespace
+
+int ResampleStage::run(const float* native, int64_t n_native, const int64_t* clips, int64_t n_clips, int64_t sr_new,
+                       const double* half_window, int64_t n_window, int num_table, bool copy_equal, float* d_out, int64_t n_samples,
+                       hipStream_t s, std::string* err) {
+    ResamplePlan plan;
+    resample_plan(clips, n_clips, sr_new, half_window, n_window, copy_equal, &tabs, &plan);
+    bufs.grow(&d_native, &cap_native, (size_t)n_native);
+    bufs.grow(&d_clips, &cap_clips, plan.clips.size());
+    bufs.grow(&d_blocks, &cap_blocks, plan.blocks.size());
+    if (bufs.grow(&d_tabs, &cap_tabs, tabs.tables.size())) tabs_on_device = ~(uint64_t)0;      // a new buffer holds nothing yet
+    if (!d_native || !d_clips || !d_blocks || !d_tabs) {
+        *err = "hipMalloc of the resampling buffers failed";
+        return L3_ENOMEM;
+    }
+    auto up = [s](void* dst, const void* src, size_t bytes) {
+        return bytes == 0 ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+    };
+    const bool new_tabs = tabs_on_device != tabs.generation;          // only a new window scale or another window uploads
+    tabs_on_device = ~(uint64_t)0;
+    hipError_t st = up(d_native, native, (size_t)n_native * sizeof(float));
+    if (st == hipSuccess) st = up(d_clips, plan.clips.data(), plan.clips.size() * sizeof(ResampleClip));
+    if (st == hipSuccess) st = up(d_blocks, plan.blocks.data(), plan.blocks.size() * sizeof(int64_t));
+    if (st == hipSuccess && new_tabs) st = up(d_tabs, tabs.tables.data(), tabs.tables.size() * sizeof(double));
+    // the copies read `plan`, which ends with this call, and `tabs`, which the next call may rebuild: none is left in flight
+    const hipError_t waited = stream_wait(s);
+    if (st != hipSuccess || waited != hipSuccess) {
+        *err = std::string("resampling upload: ") + hipGetErrorString(st != hipSuccess ? st : waited);
+        return L3_EHIP;
+    }
+    tabs_on_device = tabs.generation;
+    // samples no clip row writes read as zeros
+    if (n_samples > 0 && (st = hipMemsetAsync(d_out, 0, (size_t)n_samples * sizeof(float), s)) != hipSuccess) {
+        *err = std::string("resampling zero-fill: ") + hipGetErrorString(st);
+        return L3_EHIP;
+    }
+    resample_launch(d_native, d_clips, d_blocks, (int64_t)plan.blocks.size() / 2, d_tabs, (int)n_window, num_table, d_out, s);
+    return L3_OK;
 }
 
 }  // namespace l3

@@ -32,7 +32,6 @@ constexpr int SVM_QMAX = 128;          // working-set cap: the q x q fp32 block 
 constexpr int SVM_MAX_CLASSES = 64;
 constexpr double SVM_TAU = 1e-12;      // libsvm's TAU: the curvature used where K_ii + K_jj - 2 K_ij <= 0 (sigmoid is not PSD)
 
-__device__ __forceinline__ int mfma_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
 struct SvmKern {
     int kind, degree;
@@ -606,42 +605,13 @@ using namespace l3;
 struct l3_svm {
     int device = 0;
     hipStream_t s = nullptr;
+    DeviceBufs bufs;          // owns x and xx
     float *x = nullptr, *xx = nullptr;
     int64_t n = 0;
     int D = 0;
 };
 
 namespace {
-int fail(int code, const std::string& msg) {
-    set_op_error(msg);
-    return code;
-}
-
-// device buffers of one call, freed on every return path
-struct Bufs {
-    std::vector<void*> p;
-    bool ok = true;
-    template <class T>
-    T* alloc(int64_t count) {
-        void* q = nullptr;
-        if (hipMalloc(&q, (size_t)(count > 0 ? count : 1) * sizeof(T)) != hipSuccess) {
-            ok = false;
-            return nullptr;
-        }
-        p.push_back(q);
-        return static_cast<T*>(q);
-    }
-    template <class T>
-    T* put(const T* src, int64_t count, hipStream_t s) {
-        T* d = alloc<T>(count);
-        if (d && count > 0 && hipMemcpyAsync(d, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice, s) != hipSuccess) ok = false;
-        return d;
-    }
-    ~Bufs() {
-        for (void* q : p) (void)hipFree(q);
-    }
-};
-
 bool kern_ok(const l3_svm_kernel* kp, std::string* why) {
     if (!kp) return *why = "kernel parameters are NULL", false;
     if (kp->kind < L3_SVM_LINEAR || kp->kind > L3_SVM_SIGMOID) return *why = "unknown kernel", false;
@@ -650,11 +620,6 @@ bool kern_ok(const l3_svm_kernel* kp, std::string* why) {
     return true;
 }
 SvmKern to_kern(const l3_svm_kernel* kp) { return SvmKern{kp->kind, kp->degree, (float)kp->gamma, (float)kp->coef0}; }
-
-bool device_ok(int device) {
-    int nd = 0;
-    return hipGetDeviceCount(&nd) == hipSuccess && device >= 0 && device < nd && hipSetDevice(device) == hipSuccess;
-}
 
 void launch_norms(const float* x, int64_t n, int D, float* xx, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(svm_norms_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, x, n, D, xx);
@@ -697,7 +662,7 @@ int l3_svm_create(int device, l3_svm** out) {
     if (!out) return fail(L3_EINVAL, "l3_svm_create: out is NULL");
     *out = nullptr;
     if (!device_ok(device))
-        return fail(L3_EHIP, "l3_svm_create: HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)");
+        return fail(L3_EHIP, no_gpu_message("l3_svm_create", device));
     l3_svm* m = new l3_svm();
     m->device = device;
     if (hipStreamCreateWithFlags(&m->s, hipStreamNonBlocking) != hipSuccess) {
@@ -712,8 +677,6 @@ void l3_svm_destroy(l3_svm* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->s) (void)hipStreamSynchronize(m->s);
-    if (m->x) (void)hipFree(m->x);
-    if (m->xx) (void)hipFree(m->xx);
     if (m->s) (void)hipStreamDestroy(m->s);
     delete m;
 }
@@ -723,10 +686,9 @@ int l3_svm_set_data(l3_svm* m, const float* X, int64_t n, int D) {
     if (n <= 0 || n > INT32_MAX || D <= 0 || D > (1 << 24)) return fail(L3_EINVAL, "l3_svm_set_data: need 1 <= n < 2^31, 1 <= D <= 2^24");
     (void)hipSetDevice(m->device);
     (void)hipStreamSynchronize(m->s);
-    if (m->x) (void)hipFree(m->x), m->x = nullptr;
-    if (m->xx) (void)hipFree(m->xx), m->xx = nullptr;
-    m->n = 0;
-    if (hipMalloc(&m->x, (size_t)n * D * sizeof(float)) != hipSuccess || hipMalloc(&m->xx, (size_t)n * sizeof(float)) != hipSuccess)
+    m->bufs.release(m->x), m->bufs.release(m->xx);
+    m->x = m->xx = nullptr, m->n = 0;
+    if (!(m->x = m->bufs.alloc<float>((size_t)n * D)) || !(m->xx = m->bufs.alloc<float>((size_t)n)))
         return fail(L3_ENOMEM, "l3_svm_set_data: device allocation of " + std::to_string(n * D * 4) + " bytes failed");
     if (hipMemcpyAsync(m->x, X, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, m->s) != hipSuccess)
         return fail(L3_EHIP, "l3_svm_set_data: copy to the device failed");
@@ -759,7 +721,7 @@ int l3_svm_fit(l3_svm* m, const l3_svm_kernel* kp, double C, double tol, int64_t
     const std::vector<int64_t> off(prob_off, prob_off + n_prob + 1);
     std::vector<int64_t> t32, t256;
     const int64_t n32 = prefix_tiles(off, 32, &t32), n256 = prefix_tiles(off, 256, &t256);
-    Bufs b;
+    DeviceBufs b;
     SvmState st{};
     st.x = m->x;
     st.off = b.put(off.data(), n_prob + 1, m->s);
@@ -772,7 +734,7 @@ int l3_svm_fit(l3_svm* m, const l3_svm_kernel* kp, double C, double tol, int64_t
     st.gap = b.alloc<double>(n_prob), st.rho = b.alloc<double>(n_prob);
     st.krow = b.alloc<float>(total * q);
     st.tile32 = b.put(t32.data(), n_prob + 1, m->s), st.tile256 = b.put(t256.data(), n_prob + 1, m->s);
-    if (!b.ok) return fail(L3_ENOMEM, "l3_svm_fit: device allocation failed (" + std::to_string(total * q * 4) + " bytes of kernel rows)");
+    if (!b.ok()) return fail(L3_ENOMEM, "l3_svm_fit: device allocation failed (" + std::to_string(total * q * 4) + " bytes of kernel rows)");
     st.C = C, st.tol = tol, st.local_rel = L3_SVM_LOCAL_REL, st.P = n_prob, st.q = q;
     // libsvm's cap when max_iter is -1: max(10^7, 100 l) updates; the largest problem sets it for all
     int64_t nmax = 0;
@@ -840,13 +802,13 @@ int l3_svm_decision(l3_svm* m, const l3_svm_kernel* kp, const float* X, const in
     const int R = n_class - 1, P = n_class * R / 2;
     int64_t rows_blk = std::min<int64_t>({65536, (int64_t(64) << 20) / D, (int64_t(32) << 20) / ((int64_t)n_class * R)});
     rows_blk = std::max<int64_t>(32, rows_blk & ~int64_t(31));
-    Bufs b;
+    DeviceBufs b;
     const float *sv = m->x, *svn = m->xx;
     const int* svi = nullptr;
     if (SV) {
         float* d = b.put(SV, n_sv * D, m->s);
         float* dn = b.alloc<float>(n_sv);
-        if (b.ok) launch_norms(d, n_sv, D, dn, m->s);
+        if (b.ok()) launch_norms(d, n_sv, D, dn, m->s);
         sv = d, svn = dn;
     } else {
         svi = b.put(sv_idx, n_sv, m->s);
@@ -856,19 +818,19 @@ int l3_svm_decision(l3_svm* m, const l3_svm_kernel* kp, const float* X, const in
     const double* rh = b.put(rho, P, m->s);
     double* S = b.alloc<double>(std::min(rows_blk, n) * n_class * R);
     double* dec = b.alloc<double>(n * P);
-    if (!b.ok) return fail(L3_ENOMEM, "l3_svm_decision: device allocation failed");
+    if (!b.ok()) return fail(L3_ENOMEM, "l3_svm_decision: device allocation failed");
     const SvmKern k = to_kern(kp);
     int rc = L3_OK;
     if (x_idx) {
         const int* xi = b.put(x_idx, n, m->s);
-        if (!b.ok) return fail(L3_ENOMEM, "l3_svm_decision: device allocation failed");
+        if (!b.ok()) return fail(L3_ENOMEM, "l3_svm_decision: device allocation failed");
         rc = decision_dev(m->s, m->x, m->xx, xi, n, sv, svn, svi, n_sv, D, n_class, cs, cf, rh, k, S, rows_blk, dec);
     } else {
         // host rows staged in blocks
         const int64_t blk = std::min(rows_blk, n);
         float* xt = b.alloc<float>(blk * D);
         float* xtn = b.alloc<float>(blk);
-        if (!b.ok) return fail(L3_ENOMEM, "l3_svm_decision: device allocation failed");
+        if (!b.ok()) return fail(L3_ENOMEM, "l3_svm_decision: device allocation failed");
         for (int64_t r0 = 0; r0 < n && rc == L3_OK; r0 += blk) {
             const int64_t rows = std::min(blk, n - r0);
             if (hipMemcpyAsync(xt, X + r0 * D, (size_t)rows * D * sizeof(float), hipMemcpyHostToDevice, m->s) != hipSuccess)
@@ -895,7 +857,7 @@ int l3_op_svm_kernel_rows(int device, const l3_svm_kernel* kp, const float* x, i
     for (int i = 0; i < nb; ++i)
         if (b_idx[i] < 0 || b_idx[i] >= n_x) return fail(L3_EINVAL, "l3_op_svm_kernel_rows: b_idx outside [0, n_x)");
     if (!device_ok(device)) return fail(L3_EHIP, "l3_op_svm_kernel_rows: HIP device not available (libl3hip needs an AMD GPU)");
-    Bufs b;
+    DeviceBufs b;
     hipStream_t s = nullptr;
     const float* dx = b.put(x, n_x * D, s);
     float* dxx = b.alloc<float>(n_x);
@@ -905,7 +867,7 @@ int l3_op_svm_kernel_rows(int device, const l3_svm_kernel* kp, const float* x, i
     const int64_t* doff = b.put(off, 2, s);
     const int64_t* dt = b.put(tiles, 2, s);
     float* dout = b.alloc<float>((int64_t)na * nb);
-    if (!b.ok) return fail(L3_ENOMEM, "l3_op_svm_kernel_rows: device allocation failed");
+    if (!b.ok()) return fail(L3_ENOMEM, "l3_op_svm_kernel_rows: device allocation failed");
     launch_norms(dx, n_x, D, dxx, s);
     SvmRowsArgs ra{};
     ra.x = dx, ra.xx = dxx, ra.ridx = da, ra.nrows = nullptr, ra.nrows_all = na, ra.cidx = db, ra.col_off = doff, ra.tile_off = dt;
@@ -927,7 +889,7 @@ int l3_op_svm_smo(int device, const float* K, const int8_t* y, int q, double C, 
         if (!(alpha[i] >= 0.0 && alpha[i] <= C)) return fail(L3_EINVAL, "l3_op_svm_smo: alpha outside [0, C]");
     }
     if (!device_ok(device)) return fail(L3_EHIP, "l3_op_svm_smo: HIP device not available (libl3hip needs an AMD GPU)");
-    Bufs b;
+    DeviceBufs b;
     hipStream_t s = nullptr;
     std::vector<int> wl(q);
     for (int i = 0; i < q; ++i) wl[i] = i;
@@ -945,7 +907,7 @@ int l3_op_svm_smo(int device, const float* K, const int8_t* y, int q, double C, 
     sa.dal = b.alloc<double>(q);
     long long* du = b.put(&zero, 1, s);
     sa.updates = du;
-    if (!b.ok) return fail(L3_ENOMEM, "l3_op_svm_smo: device allocation failed");
+    if (!b.ok()) return fail(L3_ENOMEM, "l3_op_svm_smo: device allocation failed");
     sa.active = nullptr, sa.C = C, sa.eps = eps, sa.local_rel = local_rel;
     sa.max_updates = max_updates > 0 ? max_updates : (long long)1 << 62;
     sa.q = q, sa.ldk_is_n = 1;

@@ -44,7 +44,6 @@ constexpr int LM_KCHUNK = 50;                                         // product
 static_assert(VG_WIN % LM_KCHUNK == 0 && LM_KCHUNK % 2 == 0, "whole chunks of MFMA steps");
 
 __device__ __forceinline__ int lm_idx(int s) { return s + (s >> 5); }
-__device__ __forceinline__ int vg_mfma_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
 __global__ __launch_bounds__(256) void vggish_logmel_kernel(const float* x, const int64_t* blocks, const float* dft,
                                                             const float* mel, float* out) {
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(256) void vggish_logmel_kernel(const float* x, cons
             im += pi;
         }
 #pragma unroll
-        for (int i = 0; i < 16; ++i) mag[vg_mfma_row(i, h) * LM_MAG_LD + nb * 32 + r] = sqrtf(re[i] * re[i] + im[i] * im[i]);
+        for (int i = 0; i < 16; ++i) mag[mfma_row(i, h) * LM_MAG_LD + nb * 32 + r] = sqrtf(re[i] * re[i] + im[i] * im[i]);
     }
     __syncthreads();
     if (wave >= 2) return;
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(256) void vggish_logmel_kernel(const float* x, cons
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-        const int row = vg_mfma_row(i, h);
+        const int row = mfma_row(i, h);
         if (row < nv) out[(out_row + row) * VG_MELS + wave * 32 + r] = logf(acc[i] + 0.01f);
     }
 }
@@ -288,39 +287,15 @@ struct l3_vggish {
     float *dft = nullptr, *mel = nullptr, *pca_t = nullptr, *means = nullptr;
     float *act[2] = {}, *part = nullptr;
     int* ctr = nullptr;
-    // grow-only buffers of a call
-    void* buf[8] = {};
-    size_t cap[8] = {};
-    ResampleTables tabs;
-    uint64_t tabs_uploaded = 0;
-    double* tabs_dev = nullptr;
-    size_t tabs_cap = 0;
+    // grow-only buffers of a call, with their capacities in elements
+    float *d_16k = nullptr, *d_logmel = nullptr, *d_out = nullptr;
+    int64_t *d_lblocks = nullptr, *d_ex = nullptr;
+    size_t cap_16k = 0, cap_logmel = 0, cap_out = 0, cap_lblocks = 0, cap_ex = 0;
+    ResampleStage resample;
+    DeviceBufs bufs;          // owns every pointer above
 };
 
 namespace {
-int fail(int code, const std::string& msg) {
-    set_op_error(msg);
-    return code;
-}
-
-bool dev_ok(int device) {
-    int n = 0;
-    return device >= 0 && hipGetDeviceCount(&n) == hipSuccess && device < n && hipSetDevice(device) == hipSuccess;
-}
-
-template <class T>
-T* grow(l3_vggish* v, int slot, size_t count) {
-    const size_t need = std::max<size_t>(count, 1) * sizeof(T);
-    if (v->cap[slot] < need) {
-        if (v->buf[slot]) (void)hipFree(v->buf[slot]);
-        v->buf[slot] = nullptr;
-        v->cap[slot] = 0;
-        if (hipMalloc(&v->buf[slot], need) != hipSuccess) return nullptr;
-        v->cap[slot] = need;
-    }
-    return static_cast<T*>(v->buf[slot]);
-}
-
 ConvGeom layer_geom(const l3_vggish* v, const VgLayer& L, int n) {
     ConvGeom g{n, L.H, L.W, L.Cin, L.H, L.W, L.Cout, 3, 3, 1, 1};
     g.solo = 1;
@@ -370,29 +345,27 @@ int l3_vggish_create(int device, int batch, l3_vggish** out) {
     if (batch == 0) batch = L3_VGGISH_DEFAULT_BATCH;
     if (batch < 1 || batch > L3_VGGISH_MAX_BATCH)
         return fail(L3_EINVAL, "l3_vggish_create: batch must be in [1, " + std::to_string(L3_VGGISH_MAX_BATCH) + "]");
-    if (!dev_ok(device))
-        return fail(L3_EHIP, "l3_vggish_create: HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)");
+    if (!device_ok(device)) return fail(L3_EHIP, no_gpu_message("l3_vggish_create", device));
     l3_vggish* v = new l3_vggish();
     v->device = device;
     v->batch = batch;
-    bool ok = hipStreamCreate(&v->s) == hipSuccess;
-    for (int l = 0; l < 9 && ok; ++l) {
+    DeviceBufs& dev = v->bufs;
+    for (int l = 0; l < 9; ++l) {
         const VgLayer& L = VG_LAYERS[l];
-        ok = hipMalloc((void**)&v->w[l], layer_w_numel(L) * 4) == hipSuccess && hipMalloc((void**)&v->b[l], (size_t)L.Cout * 4) == hipSuccess;
-        if (ok && l >= 1 && l <= 5) ok = hipMalloc((void**)&v->u[l], (size_t)36 * L.Cin * L.Cout * 4) == hipSuccess;
+        v->w[l] = dev.alloc<float>((size_t)layer_w_numel(L)), v->b[l] = dev.alloc<float>((size_t)L.Cout);
+        if (l >= 1 && l <= 5) v->u[l] = dev.alloc<float>((size_t)36 * L.Cin * L.Cout);
     }
     std::vector<float> dft, mel;
     vggish_host_dft(&dft);
     vggish_host_mel(&mel);
-    ok = ok && hipMalloc((void**)&v->dft, dft.size() * 4) == hipSuccess && hipMalloc((void**)&v->mel, mel.size() * 4) == hipSuccess &&
-         hipMalloc((void**)&v->pca_t, VG_EMB * VG_EMB * 4) == hipSuccess && hipMalloc((void**)&v->means, VG_EMB * 4) == hipSuccess &&
-         hipMalloc((void**)&v->act[0], (size_t)batch * VG_ACT_FLOATS * 4) == hipSuccess &&
-         hipMalloc((void**)&v->act[1], (size_t)batch * VG_ACT_FLOATS * 4) == hipSuccess &&
-         hipMalloc((void**)&v->part, (size_t)MLP_PART_FLOATS * 4) == hipSuccess &&
-         hipMalloc((void**)&v->ctr, (size_t)MLP_FWD_COUNTERS * 4) == hipSuccess &&
-         hipMemset(v->ctr, 0, (size_t)MLP_FWD_COUNTERS * 4) == hipSuccess &&
-         hipMemcpy(v->dft, dft.data(), dft.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(v->mel, mel.data(), mel.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+    v->dft = dev.alloc<float>(dft.size()), v->mel = dev.alloc<float>(mel.size());
+    v->pca_t = dev.alloc<float>(VG_EMB * VG_EMB), v->means = dev.alloc<float>(VG_EMB);
+    v->act[0] = dev.alloc<float>((size_t)batch * VG_ACT_FLOATS), v->act[1] = dev.alloc<float>((size_t)batch * VG_ACT_FLOATS);
+    v->part = dev.alloc<float>((size_t)MLP_PART_FLOATS), v->ctr = dev.alloc<int>((size_t)MLP_FWD_COUNTERS);
+    const bool ok = dev.ok() && hipStreamCreate(&v->s) == hipSuccess &&
+                    hipMemset(v->ctr, 0, (size_t)MLP_FWD_COUNTERS * 4) == hipSuccess &&
+                    hipMemcpy(v->dft, dft.data(), dft.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(v->mel, mel.data(), mel.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {
         l3_vggish_destroy(v);
         return fail(L3_ENOMEM, "l3_vggish_create: device allocation failed");
@@ -405,16 +378,6 @@ void l3_vggish_destroy(l3_vggish* v) {
     if (!v) return;
     (void)hipSetDevice(v->device);
     if (v->s) (void)hipStreamSynchronize(v->s);
-    for (int l = 0; l < 9; ++l) {
-        if (v->w[l]) (void)hipFree(v->w[l]);
-        if (v->b[l]) (void)hipFree(v->b[l]);
-        if (v->u[l]) (void)hipFree(v->u[l]);
-    }
-    void* rest[] = {v->dft, v->mel, v->pca_t, v->means, v->act[0], v->act[1], v->part, v->ctr, v->tabs_dev};
-    for (void* p : rest)
-        if (p) (void)hipFree(p);
-    for (void* p : v->buf)
-        if (p) (void)hipFree(p);
     if (v->s) (void)hipStreamDestroy(v->s);
     delete v;
 }
@@ -499,45 +462,24 @@ int l3_vggish_embed_clips_resampled(l3_vggish* v, const float* native, int64_t n
     if (n_examples == 0) return L3_OK;
     if (hipSetDevice(v->device) != hipSuccess) return fail(L3_EHIP, std::string(me) + "hipSetDevice failed");
 
-    ResamplePlan plan;
-    resample_plan(clips, n_clips, VG_SR, half_window, n_window, true, &v->tabs, &plan);
-    float* d_native = grow<float>(v, 0, (size_t)n_native);
-    float* d_16k = grow<float>(v, 1, (size_t)n_samples);
-    ResampleClip* d_clips = grow<ResampleClip>(v, 2, plan.clips.size());
-    int64_t* d_rblocks = grow<int64_t>(v, 3, plan.blocks.size());
-    int64_t* d_lblocks = grow<int64_t>(v, 4, blocks.size());
-    float* d_logmel = grow<float>(v, 5, (size_t)rows * VG_MELS);
-    int64_t* d_ex = grow<int64_t>(v, 6, (size_t)n_examples);
-    float* d_out = grow<float>(v, 7, (size_t)n_examples * VG_EMB + (size_t)v->batch * VG_EMB);      // + one batch of raw embeddings
-    if (!d_native || !d_16k || !d_clips || !d_rblocks || !d_lblocks || !d_logmel || !d_ex || !d_out)
-        return fail(L3_ENOMEM, std::string(me) + "device allocation failed");
-    if (v->tabs_uploaded != v->tabs.generation || !v->tabs_dev) {
-        const size_t need = std::max<size_t>(v->tabs.tables.size(), 1) * sizeof(double);
-        if (hipStreamSynchronize(v->s) != hipSuccess) return fail(L3_EHIP, std::string(me) + "stream error");
-        if (v->tabs_cap < need) {
-            if (v->tabs_dev) (void)hipFree(v->tabs_dev);
-            v->tabs_dev = nullptr;
-            v->tabs_cap = 0;
-            if (hipMalloc((void**)&v->tabs_dev, need) != hipSuccess) return fail(L3_ENOMEM, std::string(me) + "device allocation failed");
-            v->tabs_cap = need;
-        }
-        if (!v->tabs.tables.empty() &&
-            hipMemcpy(v->tabs_dev, v->tabs.tables.data(), v->tabs.tables.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-            return fail(L3_EHIP, std::string(me) + "filter table upload failed");
-        v->tabs_uploaded = v->tabs.generation;
-    }
-    bool ok = hipMemcpyAsync(d_native, native, (size_t)n_native * 4, hipMemcpyHostToDevice, v->s) == hipSuccess &&
-              hipMemcpyAsync(d_clips, plan.clips.data(), plan.clips.size() * sizeof(ResampleClip), hipMemcpyHostToDevice, v->s) == hipSuccess &&
-              hipMemcpyAsync(d_rblocks, plan.blocks.data(), plan.blocks.size() * 8, hipMemcpyHostToDevice, v->s) == hipSuccess &&
-              hipMemcpyAsync(d_lblocks, blocks.data(), blocks.size() * 8, hipMemcpyHostToDevice, v->s) == hipSuccess &&
-              hipMemcpyAsync(d_ex, example_rows, (size_t)n_examples * 8, hipMemcpyHostToDevice, v->s) == hipSuccess &&
-              hipMemsetAsync(d_16k, 0, std::max<size_t>((size_t)n_samples, 1) * 4, v->s) == hipSuccess;
-    if (!ok) {
-        (void)hipStreamSynchronize(v->s);          // the staged host vectors go out of scope
+    DeviceBufs& dev = v->bufs;
+    dev.grow(&v->d_16k, &v->cap_16k, (size_t)n_samples);
+    dev.grow(&v->d_lblocks, &v->cap_lblocks, blocks.size());
+    dev.grow(&v->d_logmel, &v->cap_logmel, (size_t)rows * VG_MELS);
+    dev.grow(&v->d_ex, &v->cap_ex, (size_t)n_examples);
+    dev.grow(&v->d_out, &v->cap_out, (size_t)n_examples * VG_EMB + (size_t)v->batch * VG_EMB);      // + one batch of raw embeddings
+    float *d_16k = v->d_16k, *d_logmel = v->d_logmel, *d_out = v->d_out;
+    int64_t *d_lblocks = v->d_lblocks, *d_ex = v->d_ex;
+    if (!d_16k || !d_lblocks || !d_logmel || !d_ex || !d_out) return fail(L3_ENOMEM, std::string(me) + "device allocation failed");
+    std::string why;
+    if (const int rc = v->resample.run(native, n_native, clips, n_clips, VG_SR, half_window, n_window, num_table, true, d_16k,
+                                       n_samples, v->s, &why))
+        return fail(rc, std::string(me) + why);
+    if (hipMemcpyAsync(d_lblocks, blocks.data(), blocks.size() * 8, hipMemcpyHostToDevice, v->s) != hipSuccess ||
+        hipMemcpyAsync(d_ex, example_rows, (size_t)n_examples * 8, hipMemcpyHostToDevice, v->s) != hipSuccess) {
+        (void)stream_wait(v->s);          // `blocks` goes out of scope
         return fail(L3_EHIP, std::string(me) + "upload failed");
     }
-    // the host vectors of the asynchronous copies above are pageable: HIP stages them before returning
-    resample_launch(d_native, d_clips, d_rblocks, (int64_t)plan.blocks.size() / 2, v->tabs_dev, (int)n_window, num_table, d_16k, v->s);
     vggish_logmel(d_16k, d_lblocks, (int64_t)blocks.size() / 3, v->dft, v->mel, d_logmel, v->s);
     float* d_emb = d_out + (size_t)n_examples * VG_EMB;
     for (int64_t e0 = 0; e0 < n_examples; e0 += v->batch) {

@@ -170,6 +170,37 @@ def test_fit_is_deterministic(gpu_required):
         assert np.array_equal(a, b)
 
 
+def test_set_data_again_on_one_handle_equals_a_fresh_handle(gpu_required):
+    """set_data frees the resident matrix and its norms and allocates new ones: a larger set, then a smaller one, on the same
+    handle; the solver and the decision values over the resident rows are those of a fresh handle, bit for bit.  D = 20 is no
+    multiple of 4 (the scalar loads of the kernel rows)."""
+    kern = _lib.svm_kernel('rbf', 1.0 / 20)
+    kept = _lib.SVM()
+    for n, seed in ((64, 5), (300, 6), (40, 7)):
+        X, y = _clusters(n, 20, 3, seed)
+        groups = [np.flatnonzero(y == c).astype(np.int32) for c in range(3)]
+        problems = [(np.concatenate((groups[i], groups[j])),
+                     np.concatenate((np.ones(groups[i].size), -np.ones(groups[j].size))).astype(np.int8))
+                    for i in range(3) for j in range(i + 1, 3)]
+        sv_idx = np.concatenate(groups)
+        sv_start = np.concatenate([[0], np.cumsum([g.size for g in groups])])
+        r = np.random.RandomState(seed)
+        coef, rho = r.randn(2, n), r.randn(3)
+        out = []
+        for h in (kept, _lib.SVM()):
+            h.set_data(X)
+            assert (h.n, h.D) == (n, 20)
+            alphas, rho_fit = h.fit(kern, problems)[:2]
+            out.append((np.concatenate(alphas), rho_fit,
+                        h.decision(kern, sv_start, coef, rho, x_idx=np.arange(n, dtype=np.int32), sv_idx=sv_idx),
+                        h.decision(kern, sv_start, coef, rho, X=X[::-1], sv_idx=sv_idx)))
+            if h is not kept:
+                h.close()
+        for a, b in zip(*out):
+            assert a.size and np.isfinite(a).all() and np.array_equal(a, b), n
+    kept.close()
+
+
 def test_pickles_without_handle_and_predicts_again(gpu_required, tmp_path):
     z = _fixture('c4')
     m = SVC(probability=True, gamma='auto', random_state=1).fit(z['X'], z['y'])

@@ -263,3 +263,34 @@ def test_missing_weight_is_an_error_not_a_fallback(gpu_required):
     with pytest.raises(_lib.L3Error, match='no VGGish variable named'):
         net.set_weight('vggish/conv9/weights', np.zeros(4, np.float32))
     net.close()
+
+
+def test_handle_filter_tables_follow_the_window_and_the_buffers(gpu_required):
+    # the handle keeps its filter tables and its per-call buffers across calls: another half window must not meet the old
+    # tables, and a buffer reallocated for a longer call (or for one more table) must not pass for an uploaded one
+    weights = _CHAIN_REF.get('weights') or ref.he_weights(3)
+    win, nt = resample.kaiser_best()
+    short, long_, other = ref.varied_clips(21, [int(1.2 * 44100), 3 * int(1.2 * 44100), int(1.2 * 22050)])
+
+    def embed(net, x, sr, w):
+        n16 = resample.output_length(x.size, sr, 16000)
+        pads, rows, _ = vggish.example_table([n16], 0.96)
+        return net.embed_clips_resampled(x, [[0, x.size, sr, 0, n16, int(pads[0, 0])]], w, nt, int(pads[0, 1]), [[0, int(pads[0, 1])]],
+                                         rows, 'raw')
+
+    kept = vggish.VGGishModel(weights=weights, batch=4)
+    calls = [(short, 44100, win), (short, 44100, 0.5 * win), (short, 44100, win),
+             (long_, 44100, win),               # three times as long: every per-call buffer is reallocated
+             (other, 22050, win),               # one more window scale: the table buffer grows
+             (short, 44100, win)]
+    got = []
+    for x, sr, w in calls:
+        fresh = vggish.VGGishModel(weights=weights, batch=4)
+        got.append(embed(kept.net, x, sr, w))
+        want = embed(fresh.net, x, sr, w)
+        fresh.close()
+        assert got[-1].shape[0] >= 1 and np.array_equal(got[-1], want), (x.size, sr, float(w[0]))
+    kept.close()
+    assert not np.array_equal(got[0], got[1])              # the window matters to the output: stale tables would show
+    assert np.array_equal(got[0], got[2]) and np.array_equal(got[0], got[5])
+    assert got[3].shape[0] > got[0].shape[0]
