@@ -609,11 +609,15 @@ __global__ __launch_bounds__(256) void conv_dgrad_small_kernel(const float* dy, 
     }
 }
 
-// true if handled (3x3 'same', stride 1, 64 filters, 1 or 3 input channels)
+// 3x3 'same', stride 1, 64 filters, 1 or 3 input channels
+bool conv_dgrad_small_ok(const ConvGeom& g) {
+    return g.KH == 3 && g.KW == 3 && g.padT == 1 && g.padL == 1 && g.Cout == 64 && g.Ho == g.H && g.Wo == g.W &&
+           (g.Cin == 1 || g.Cin == 3);
+}
+
+// true if handled
 bool conv_dgrad_small(const float* dy, const float* w, float* dx, const ConvGeom& g, hipStream_t s) {
-    if (!(g.KH == 3 && g.KW == 3 && g.padT == 1 && g.padL == 1 && g.Cout == 64 && g.Ho == g.H && g.Wo == g.W &&
-          (g.Cin == 1 || g.Cin == 3)))
-        return false;
+    if (!conv_dgrad_small_ok(g)) return false;
     const int strip = 32;
     const int strips = (g.W + strip - 1) / strip;
     const int waves = g.N * g.H * strips;

@@ -66,6 +66,31 @@ struct Param {
     float* g = nullptr;   // device grad (trainable only)
 };
 
+// The kernel path of one tower op, resolved by plan_tower() at the head of a pass and only executed by tower_forward() /
+// tower_backward_block().  Flops are the issued ones (-1: the algorithmic count), bytes the algorithmic HBM traffic of the launch.
+enum ConvFwd { CF_BF16_STORED, CF_BF16_CAST, CF_FIRST, CF_FP32 };      // bf16 MFMA (operands stored bf16 / cast at fetch), FMA first layer, conv_fwd
+enum ConvWgrad { WG_AUG, WG_AUG_DEFERRED, WG_BF16_STORED, WG_BF16_CAST, WG_FP32 };      // augmented first layer (dY formed from the deferred BatchNorm), ...
+enum ConvDgrad { DG_NONE, DG_SMALL, DG_BF16_STORED, DG_BF16_CAST, DG_WINO, DG_FLIPPED };
+struct ConvPlan {
+    ConvFwd fwd = CF_FP32;
+    bool wino_filter = false;    // the forward filter is transformed into the Winograd domain first and conv_fwd is given it
+    int stat_mode = 0;           // > 0: the epilogue leaves the BatchNorm statistic partials of op.bn_follow (1 output, 2 relu(output))
+    ConvWgrad wgrad = WG_FP32;
+    bool colsum = false;         // the bias gradient is a launch of its own
+    ConvDgrad dgrad = DG_NONE;
+    int bwd_bn = -1;             // >= 0: the data gradient's epilogue leaves this BatchNorm's backward reduction partials (BnBwdFuse)
+    double fwd_executed = -1.0, fwd_bytes = 0.0, wg_executed = -1.0, wg_bytes = 0.0, dg_executed = -1.0, dg_bytes = 0.0;
+};
+enum BnStats { BS_PARTIALS, BS_FAST, BS_PLAIN, BS_MOVING };
+enum BnBwd { BB_BY_FIRST_CONV, BB_FAST_POOLED, BB_FAST, BB_FAST_DEFERRED, BB_PLAIN };      // (training) the first conv produces it, ...
+struct BnPlan {
+    BnStats stats = BS_MOVING;
+    int stat_blocks = 0;         // BS_PARTIALS: blocks the producing conv leaves in the statistics scratch
+    BnBwd bwd = BB_PLAIN;
+    int bwd_blocks = 0;          // > 0: reduction partial blocks the consuming conv's data gradient leaves (ConvPlan::bwd_bn)
+    double fwd_bytes = 0.0, bwd_bytes = 0.0;
+};
+
 struct Op {
     OpKind kind;
     std::string name;
@@ -87,17 +112,14 @@ struct Op {
     // by nothing but the first conv's weight gradient): it leaves its backward coefficients and conv_first_wgrad forms dY itself
     bool defer_apply = false;    // (bn op)
     int bn_defer = -1;           // (conv op) that BatchNorm
-    const float* apply_coeffs = nullptr;   // (bn op) bn_bwd_fast_coeffs of its last backward
     float *xaug = nullptr, *gaug = nullptr;
     ConvGeom ageom{};
     int bn_follow = -1;          // (conv op) BatchNorm op that consumes this conv's output (through a fused pre-ReLU)
-    int stats_nblk = 0;          // (bn op) > 0: the producing conv left this many statistic partial blocks
     bool need_dx = true;
     int dy_to_bn = -1;           // (conv op) BatchNorm op whose output (directly, or through the 2x2 pool folded into it) this conv
                                  // reads: its data gradient can leave that BatchNorm's backward reduction partials (kernels.h
                                  // BnBwdFuse; a pooled BatchNorm stands in with its winner tensor `xwin`)
     float* xwin = nullptr;       // (bn op with a folded pool, training) the input element that won each pool window
-    int bwd_part_blocks = 0;     // (bn op) > 0: partial blocks left in the statistics scratch by the consumer's data gradient
     // bn
     int p_gamma = -1, p_beta = -1, p_mmean = -1, p_mvar = -1;
     bool fused_relu = false;
@@ -110,6 +132,9 @@ struct Op {
     float *biased_mean = nullptr, *biased_var = nullptr;
     // pool
     PoolGeom pg{};
+    // what this pass runs for the op (plan_tower)
+    ConvPlan cp{};
+    BnPlan bp{};
 };
 
 struct Tower {
@@ -118,6 +143,7 @@ struct Tower {
     std::vector<Op> ops;
     int nblocks = 0;
     int emb_conv_op = -1;   // '<x>_embedding_layer'
+    bool training = false;  // of the pass plan_tower last resolved
 };
 
 struct FrontendDef {
@@ -147,6 +173,7 @@ struct l3_engine {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     float *red_scratch2 = nullptr, *wg_scratch2 = nullptr;
     float *stat_scratch = nullptr, *stat_scratch2 = nullptr;   // conv-epilogue BN partials (per stream)
+    size_t stat_max = 0;          // floats of each: plan_tower holds every block count it hands out against it
     float* w4_tail = nullptr;     // scratch of the F(4x4,3x3) channel-slice tail of solo launches (l3_tower_step, l3_embed_*: one stream)
     bool overlap = true;          // l3_set_tower_overlap
     BnMovingEntry* bn_table = nullptr;    // do_update: every BatchNormalization's moving mean / variance triple
@@ -277,14 +304,6 @@ int dev_grow_t(l3_engine* e, T** p, size_t* cap, size_t count) {
     if (e->bufs.grow(p, cap, count)) return L3_OK;
     e->err = "hipMalloc(" + std::to_string(l3::DeviceBufs::bytes_of<T>(count)) + "): " + hipGetErrorString(hipGetLastError());
     return L3_ENOMEM;
-}
-
-// ---- TF padding helpers ---------------------------------------------------------------------
-void tf_same(int n, int k, int s, int* out, int* before) {
-    *out = (n + s - 1) / s;
-    int total = (*out - 1) * s + k - n;
-    if (total < 0) total = 0;
-    *before = total / 2;
 }
 
 // ---- profiling ----------------------------------------------------------------------------------
@@ -611,7 +630,7 @@ int build_ledger(l3_engine* e) {
             if (op.kind == OP_CONV || op.kind == OP_BN) any = true;
         }
     }
-    const int bnbwd_fuse = l3_knob("L3_BNBWD_FUSE") ? atoi(l3_knob("L3_BNBWD_FUSE")) : 1;      // read per engine: the tests switch it
+    const int bnbwd_fuse = knob_int("L3_BNBWD_FUSE", 1);      // read per engine: the tests switch it
     if (bnbwd_fuse)
         for (Tower* tw : {&e->vis, &e->aud})
             for (size_t i = 0; i < tw->ops.size(); ++i) {
@@ -624,7 +643,7 @@ int build_ledger(l3_engine* e) {
                         cv.dy_to_bn = (int)j;
                 }
             }
-    static const int first_fused = l3_knob("L3_FIRST_FUSED") ? atoi(l3_knob("L3_FIRST_FUSED")) : 1;
+    static const int first_fused = knob_int("L3_FIRST_FUSED", 1);
     if (first_fused)
         for (Tower* tw : {&e->vis, &e->aud})
             for (size_t i = 1; i < tw->ops.size(); ++i) {
@@ -680,7 +699,7 @@ int build_ledger(l3_engine* e) {
                 tw->ops[i + 1].fused_into_bn = true;
             }
         }
-    const int first_wg_fuse = l3_knob("L3_FIRST_WG_FUSE") ? atoi(l3_knob("L3_FIRST_WG_FUSE")) : 1;
+    const int first_wg_fuse = knob_int("L3_FIRST_WG_FUSE", 1);
     if (first_wg_fuse)
         for (Tower* tw : {&e->vis, &e->aud})
             for (auto& cv : tw->ops) {
@@ -695,7 +714,7 @@ int build_ledger(l3_engine* e) {
     // BN -> ReLU -> MaxPool 2x2 -> conv: the gradient that conv's data gradient writes is the POOLED one; with the window winners
     // kept by the forward pass (Op::xwin) the BatchNorm's backward reduction is the same sum at pooled resolution, so it too can
     // ride in the data gradient's epilogue (dy_to_bn; the pooled BatchNorms are known only now)
-    const int pooled_fuse = l3_knob("L3_BNBWD_FUSE_POOLED") ? atoi(l3_knob("L3_BNBWD_FUSE_POOLED")) : 1;      // read per engine
+    const int pooled_fuse = knob_int("L3_BNBWD_FUSE_POOLED", 1);      // read per engine
     if (bnbwd_fuse && pooled_fuse)
         for (Tower* tw : {&e->vis, &e->aud})
             for (size_t i = 0; i < tw->ops.size(); ++i) {
@@ -788,7 +807,7 @@ int rebuild_consts(l3_engine* e) {
     // kapre's kernels are w[n] cos / -w[n] sin with a symmetric (periodic Hann) window: real[n] == real[N-n],
     // imag[n] == -imag[N-n], imag[0] == imag[N/2] == 0.  Then the DFT folds into two GEMMs of half the depth.
     // Loaded weight files could hold anything, so check; otherwise keep the full-depth form.
-    static const int allow_fold = l3_knob("L3_DFT_FOLD") ? atoi(l3_knob("L3_DFT_FOLD")) : 1;
+    static const int allow_fold = knob_int("L3_DFT_FOLD", 1);
     FrontendCfg& fw = e->fcfg;
     const int N = f.n_dft, H = N / 2;
     bool sym = allow_fold && N % 2 == 0 && (size_t)(fw.ke + fw.ko) * fw.nc <= (size_t)f.n_dft * f.ncols_pad;
@@ -806,7 +825,7 @@ int rebuild_consts(l3_engine* e) {
     // the transform is then KNOWN to be window x DFT and runs factored, 2048 = 32 x 64 (frontend.hip dft_*).  Anything else -- a file
     // with retrained or edited kernels -- keeps the GEMM against the kernels as given.  L3_DFT_FACTORED=0: never (A/B, tests).
     {
-        const int want = l3_knob("L3_DFT_FACTORED") ? atoi(l3_knob("L3_DFT_FACTORED")) : 1;        // read per rebuild: the tests switch it
+        const int want = knob_int("L3_DFT_FACTORED", 1);        // read per rebuild: the tests switch it
         bool stock = want && N == 2048 && e->dft_y != nullptr;
         if (stock) {
             std::vector<float> r0, i0;
@@ -1017,9 +1036,9 @@ int alloc_everything(l3_engine* e, uint64_t seed) {
     if ((rc = dev_alloc_t(e, &e->l2part, 64))) return rc;
     HIPCHK(e, hipMemset(e->l2part, 0, 64 * 4));
     // mixed precision: which tensors live in HBM as bfloat16
-    static const int bf16_storage = l3_knob("L3_BF16_STORAGE") ? atoi(l3_knob("L3_BF16_STORAGE")) : 1;
-    static const int bf16_out = l3_knob("L3_BF16_CONV_OUT") ? atoi(l3_knob("L3_BF16_CONV_OUT")) : 1;
-    static const int bf16_dgrad_out = l3_knob("L3_BF16_DGRAD_OUT") ? atoi(l3_knob("L3_BF16_DGRAD_OUT")) : 1;
+    static const int bf16_storage = knob_int("L3_BF16_STORAGE", 1);
+    static const int bf16_out = knob_int("L3_BF16_CONV_OUT", 1);
+    static const int bf16_dgrad_out = knob_int("L3_BF16_DGRAD_OUT", 1);
     if (e->cfg.dtype == L3_DTYPE_BF16 && bf16_storage)
         for (Tower* tw : {&e->vis, &e->aud})
             for (size_t ci = 0; ci < tw->ops.size(); ++ci) {
@@ -1056,7 +1075,8 @@ int alloc_everything(l3_engine* e, uint64_t seed) {
             }
     auto t_floats = [](const Tensor& t, bool bf16) { return bf16 ? (size_t)(t.numel() + 1) / 2 : (size_t)t.numel(); };
     // activations
-    size_t red_max = 1024, wg_max = 16, stat_max = 0;
+    size_t red_max = 1024, wg_max = 16;
+    size_t& stat_max = e->stat_max;
     for (int ti = 0; ti < 2; ++ti) {
         Tower& tw = ti == 0 ? e->vis : e->aud;
         tw.t[0].d = ti == 0 ? e->video : nullptr;
@@ -1164,7 +1184,7 @@ int run_frontend(l3_engine* e) {
         // -> GEMM (K = 2 N2: the length-N2 complex DFTs over n2, bins k2 < N2 / 2) ; 5.2x fewer multiplies than the folded GEMMs
         const int N1 = f.N1, N2 = f.N2;
         // L3_DFT_FACTORED=2 (debug knob): the two-GEMM form below instead of the one-kernel form (A/B, tests)
-        const int form = l3_knob("L3_DFT_FACTORED") ? atoi(l3_knob("L3_DFT_FACTORED")) : 1;
+        const int form = knob_int("L3_DFT_FACTORED", 1);
         if (form != 2 && f.n_mels > 0 && N1 == 32 && N2 == 64) {
             const double m1 = (double)M * N2, m2 = (double)M * N1;
             ProfScope ps(e, F_FRONTEND, 2.0 * M * (double)f.n_dft * 2.0 * f.n_freq + 2.0 * M * (double)f.n_freq * f.n_mels, nullptr,
@@ -1221,89 +1241,176 @@ int run_frontend(l3_engine* e) {
 static inline double act_bytes(const Tensor& t) { return (double)t.numel() * (t.d_bf16 ? 2.0 : 4.0); }
 static inline double grad_bytes(const Tensor& t) { return (double)t.numel() * (t.g_bf16 ? 2.0 : 4.0); }
 
-void tower_forward(l3_engine* e, Tower& tw, bool training) {
+// Resolves, for one pass over a tower, which kernel path every convolution and BatchNorm takes (Op::cp, Op::bp): the only place that
+// asks the kernels' predicates, the engine's dtype and the per-call debug knobs (L3_WINO4, L3_CONV_FIRST, L3_BF16_HALO: the kernels
+// read them per launch, so a plan holds for the pass it was resolved for -- a forward and the backward behind it).  Also the
+// per-pass launch settings of every convolution: ConvGeom::solo is 1 while the tower runs on its own (l3_tower_step, l3_embed_*),
+// 0 in the two-tower step (kernels.h).
+int plan_tower(l3_engine* e, Tower& tw, bool training, int solo) {
+    static const int epi_stats = knob_int("L3_EPILOGUE_STATS", 1);
+    const bool bf16 = e->cfg.dtype == L3_DTYPE_BF16;
+    tw.training = training;
+    // a block count handed to a BatchNorm must fit the statistics scratch alloc_everything sized over every path
+    auto fits = [&](const Op& cv, int blocks, int C) {
+        if ((size_t)blocks * 2 * C <= e->stat_max) return true;
+        e->err = cv.name + ": " + std::to_string(blocks) + " partial blocks of " + std::to_string(C) + " channels exceed the statistics scratch (" +
+                 std::to_string(e->stat_max) + " floats)";
+        return false;
+    };
+    // (BatchNorm behind the first conv) writes neither dx nor the bias gradient: conv_first_wgrad forms them (FirstWgFuse; both
+    // tensors fp32 or both bfloat16-stored)
+    auto defers = [&](const Op& bn) {
+        return training && bn.defer_apply && bn.fuse_pool < 0 && bn_fast_ok(tw.t[bn.in].C) && tw.t[bn.in].d_bf16 == tw.t[bn.out].g_bf16;
+    };
+    for (auto& op : tw.ops) op.bp = BnPlan{};
+    for (auto& op : tw.ops) {
+        if (op.kind != OP_CONV) continue;
+        op.geom.solo = op.dgeom.solo = solo;
+        // while a communicator exists its collectives may hold CUs beside any launch of the step: tile blocks through work counters
+        op.geom.dynamic = op.dgeom.dynamic = e->comm != nullptr ? 1 : 0;
+        // the channel-slice tail of a solo F(4x4,3x3) launch writes into the engine's own scratch (freed with the engine).  Only
+        // there: the one buffer serves one stream.  The two-tower step never splits tails in the product; when a test forces it
+        // (L3_W4_TAIL=2) its two streams must not share a buffer, so they fall back to the per-(device, stream) pool.
+        float* ts = solo ? e->w4_tail : nullptr;
+        op.geom.tail_scratch = op.dgeom.tail_scratch = ts;
+        op.geom.tail_scratch_bytes = op.dgeom.tail_scratch_bytes = ts ? conv_wino4_tail_scratch_bytes() : 0;
+
+        const Tensor &x = tw.t[op.in], &y = tw.t[op.out];
+        const double wbytes = (double)e->params[op.p_kernel].numel * 4.0;
+        ConvPlan& p = op.cp = ConvPlan{};
+        // forward.  Training: the epilogue also leaves the batch-norm statistic partials of its output
+        const bool mp = bf16 && conv_bf16_ok(op.geom);      // mixed precision: bf16 operands, fp32 accumulate (conv_bf16.hip)
+        p.fwd = mp ? (x.d_bf16 ? CF_BF16_STORED : CF_BF16_CAST) : conv_first_ok(op.geom) ? CF_FIRST : CF_FP32;
+        p.wino_filter = op.wino_uf && !mp;
+        p.fwd_executed = p.wino_filter ? conv_wino_executed_flops(op.geom) : -1.0;
+        p.fwd_bytes = act_bytes(x) + act_bytes(y) + wbytes;
+        const int nblk = p.fwd == CF_BF16_STORED ? conv_bf16_stat_blocks(op.geom)
+                         : p.fwd == CF_FIRST     ? conv_first_stat_blocks(op.geom)
+                         : p.fwd == CF_FP32 && p.wino_filter ? conv_wino_stat_blocks(op.geom) : 0;
+        if (epi_stats && training && op.bn_follow >= 0 && e->stat_max > 0 && nblk > 0) {
+            if (!fits(op, nblk, op.geom.Cout)) return L3_ESTATE;
+            p.stat_mode = tw.ops[op.bn_follow].prerelu ? 2 : 1;
+            tw.ops[op.bn_follow].bp.stat_blocks = nblk;
+        }
+        // backward
+        if (training && op.in_bn >= 0) {
+            // [x^, 1]; + dY, or the conv output and the gradient behind its BatchNorm
+            const Op* fb = op.bn_defer >= 0 && defers(tw.ops[op.bn_defer]) ? &tw.ops[op.bn_defer] : nullptr;
+            p.wgrad = fb ? WG_AUG_DEFERRED : WG_AUG;
+            p.wg_bytes = (double)x.rows() * op.ageom.Cin * 4.0 + (fb ? act_bytes(tw.t[fb->in]) + grad_bytes(tw.t[fb->out]) : grad_bytes(y));
+            continue;       // gamma / beta / bias gradients come with it, and nothing trainable lies in front
+        }
+        const bool wbf = bf16 && conv_wgrad_bf16_ok(op.geom);
+        p.wgrad = !wbf ? WG_FP32 : x.d_bf16 && y.g_bf16 ? WG_BF16_STORED : WG_BF16_CAST;
+        p.wg_executed = conv_wgrad_executed_flops(op.geom, wbf);
+        p.wg_bytes = act_bytes(x) + grad_bytes(y) + wbytes;
+        p.colsum = !op.bias_by_bn;
+        if (!op.need_dx) continue;
+        const bool dbf = bf16 && conv_bf16_ok(op.dgeom);
+        p.dgrad = conv_dgrad_small_ok(op.geom) ? DG_SMALL
+                  : dbf                        ? (y.g_bf16 ? DG_BF16_STORED : DG_BF16_CAST)
+                  : op.wino_ud                 ? DG_WINO : DG_FLIPPED;
+        p.dg_executed = op.wino_ud && !dbf ? conv_wino_executed_flops(op.dgeom) : -1.0;
+        p.dg_bytes = grad_bytes(y) + grad_bytes(x) + wbytes;
+        // the gradient this launch writes is dL/dy of the BatchNorm(+ReLU) in front of the conv (through the 2x2 pool folded into
+        // it: over the window winners): the epilogue leaves that BatchNorm's backward reduction partials -- the halo kernel on
+        // bf16-stored tensors, the Winograd kernels on fp32 ones
+        Op* bn = training && op.dy_to_bn >= 0 && e->stat_max > 0 ? &tw.ops[op.dy_to_bn] : nullptr;
+        if (bn != nullptr && bn->fuse_pool >= 0 && (bn->xwin == nullptr || x.batch_stride != (int64_t)x.H * x.W * x.C)) bn = nullptr;
+        if (bn == nullptr) continue;
+        const bool bx = tw.t[bn->in].d_bf16;
+        int blocks = -1;
+        if (p.dgrad == DG_BF16_STORED && x.g_bf16 && bx && conv_bf16_halo_ok(op.dgeom)) blocks = conv_bf16_stat_blocks(op.dgeom);
+        if (p.dgrad == DG_WINO && !x.g_bf16 && !bx && conv_wino_ok(op.dgeom)) blocks = conv_wino_stat_blocks(op.dgeom);
+        if (blocks < 0) continue;
+        if (!fits(op, blocks, op.dgeom.Cout)) return L3_ESTATE;
+        p.bwd_bn = op.dy_to_bn;
+        bn->bp.bwd_blocks = blocks;
+    }
+    for (auto& op : tw.ops) {
+        if (op.kind != OP_BN) continue;
+        const Tensor &x = tw.t[op.in], &y = tw.t[op.out];
+        const Tensor& out = op.fuse_pool >= 0 ? tw.t[tw.ops[op.fuse_pool].out] : y;       // what it writes / whose gradient it reads
+        BnPlan& p = op.bp;
+        p.stats = !training ? BS_MOVING : p.stat_blocks > 0 ? BS_PARTIALS : op.prerelu || x.d_bf16 ? BS_FAST : BS_PLAIN;
+        p.bwd = training && op.fused_first ? BB_BY_FIRST_CONV : !bn_fast_ok(x.C) ? BB_PLAIN : op.fuse_pool >= 0 ? BB_FAST_POOLED
+                : defers(op) ? BB_FAST_DEFERRED : BB_FAST;
+        // statistics: the conv epilogue's partials, or one pass over x; then x -> y (or -> the pooled tensor, + the window winners)
+        p.fwd_bytes = (!training ? 0.0 : p.stat_blocks > 0 ? (double)p.stat_blocks * 2 * x.C * 4 : act_bytes(x)) + act_bytes(x) + act_bytes(out);
+        if (p.bwd == BB_BY_FIRST_CONV) p.fwd_bytes += act_bytes(x) + (double)x.rows() * (&op + 1)->ageom.Cin * 4.0;       // + [x^, 1]
+        if (op.fuse_pool >= 0 && training && op.xwin != nullptr) p.fwd_bytes += (double)out.numel() * (x.d_bf16 ? 2.0 : 4.0);
+        // reduction over (x, dy) -- or the data gradient's epilogue partials --, then (x, dy) -> dx unless deferred
+        p.bwd_bytes = p.bwd == BB_PLAIN ? 2.0 * (act_bytes(x) + grad_bytes(y)) + grad_bytes(x)
+                                        : (p.bwd_blocks > 0 ? (double)p.bwd_blocks * 2 * x.C * 4 : act_bytes(x) + grad_bytes(out)) +
+                                              (p.bwd == BB_FAST_DEFERRED ? 0.0 : act_bytes(x) + grad_bytes(out) + grad_bytes(x));
+    }
+    return L3_OK;
+}
+
+void tower_forward(l3_engine* e, Tower& tw) {
+    const bool training = tw.training;
     for (auto& op : tw.ops) {
         Tensor& x = tw.t[op.in];
         Tensor& y = tw.t[op.out];
         switch (op.kind) {
             case OP_CONV: {
-                const bool mp = e->cfg.dtype == L3_DTYPE_BF16 && conv_bf16_ok(op.geom);
-                ProfScope ps(e, F_CONV_FWD, conv_flops(op.geom), op.name.c_str(),
-                             op.wino_uf && !mp ? conv_wino_executed_flops(op.geom) : -1.0);
-                ps.bytes(act_bytes(x) + act_bytes(y) + (double)e->params[op.p_kernel].numel * 4.0);
-                // training: the Winograd epilogue also leaves the batch-norm statistic partials of its output
-                static const int epi_stats = l3_knob("L3_EPILOGUE_STATS") ? atoi(l3_knob("L3_EPILOGUE_STATS")) : 1;
-                if (op.wino_uf && !mp)
-                    conv_wino_transform_weights(e->params[op.p_kernel].d, op.wino_uf, op.geom, false, e->stream);
-                if (mp) {
-                    // mixed precision: bf16 operands, fp32 accumulate (conv_bf16.hip)
-                    if (x.d_bf16)
-                        conv_weights_bf16(e->params[op.p_kernel].d, op.wflip, op.kh, op.kw, x.C, op.cout, true, e->stream);
-                    else
-                        conv_flip_weights(e->params[op.p_kernel].d, op.wflip, op.kh, op.kw, x.C, op.cout, e->stream);
-                    const bool mstats = epi_stats && training && x.d_bf16 && op.bn_follow >= 0 && e->stat_scratch != nullptr;
-                    conv_bf16_fwd(x.d, op.wflip, e->params[op.p_bias].d, y.d, op.geom, e->stream, x.d_bf16,
-                                  mstats ? e->stat_scratch : nullptr, mstats ? (tw.ops[op.bn_follow].prerelu ? 2 : 1) : 0,
-                                  y.d_bf16);
-                    if (op.bn_follow >= 0) tw.ops[op.bn_follow].stats_nblk = mstats ? conv_bf16_stat_blocks(op.geom) : 0;
-                    break;
+                const ConvPlan& p = op.cp;
+                const float *w = e->params[op.p_kernel].d, *bias = e->params[op.p_bias].d;
+                float* part = p.stat_mode ? e->stat_scratch : nullptr;
+                ProfScope ps(e, F_CONV_FWD, conv_flops(op.geom), op.name.c_str(), p.fwd_executed);
+                ps.bytes(p.fwd_bytes);
+                if (p.wino_filter) conv_wino_transform_weights(w, op.wino_uf, op.geom, false, e->stream);
+                switch (p.fwd) {
+                    case CF_BF16_STORED:
+                        conv_weights_bf16(w, op.wflip, op.kh, op.kw, x.C, op.cout, true, e->stream);
+                        conv_bf16_fwd(x.d, op.wflip, bias, y.d, op.geom, e->stream, true, part, p.stat_mode, y.d_bf16);
+                        break;
+                    case CF_BF16_CAST:
+                        conv_flip_weights(w, op.wflip, op.kh, op.kw, x.C, op.cout, e->stream);
+                        conv_bf16_fwd(x.d, op.wflip, bias, y.d, op.geom, e->stream);
+                        break;
+                    case CF_FIRST:      // FMA kernel with the statistics (and, bf16 engines, the bf16 store) fused
+                        conv_first_fwd(x.d, w, bias, y.d, op.geom, e->stream, part, p.stat_mode, y.d_bf16);
+                        break;
+                    case CF_FP32:
+                        conv_fwd(x.d, w, bias, y.d, op.geom, e->stream, p.wino_filter ? op.wino_uf : nullptr, part, p.stat_mode);
+                        break;
                 }
-                if (conv_first_ok(op.geom)) {
-                    // first conv of the tower: FMA kernel with the statistics (and, bf16 engines, the bf16 store) fused
-                    const bool fstats = epi_stats && training && op.bn_follow >= 0 && e->stat_scratch != nullptr;
-                    conv_first_fwd(x.d, e->params[op.p_kernel].d, e->params[op.p_bias].d, y.d, op.geom, e->stream,
-                                   fstats ? e->stat_scratch : nullptr, fstats ? (tw.ops[op.bn_follow].prerelu ? 2 : 1) : 0,
-                                   y.d_bf16);
-                    if (op.bn_follow >= 0) tw.ops[op.bn_follow].stats_nblk = fstats ? conv_first_stat_blocks(op.geom) : 0;
-                    break;
-                }
-                const bool stats = epi_stats && training && op.wino_uf && op.bn_follow >= 0 && e->stat_scratch != nullptr &&
-                                   conv_wino_stat_blocks(op.geom) > 0;
-                conv_fwd(x.d, e->params[op.p_kernel].d, e->params[op.p_bias].d, y.d, op.geom, e->stream, op.wino_uf,
-                         stats ? e->stat_scratch : nullptr, stats ? (tw.ops[op.bn_follow].prerelu ? 2 : 1) : 0);
-                if (op.bn_follow >= 0) tw.ops[op.bn_follow].stats_nblk = stats ? conv_wino_stat_blocks(op.geom) : 0;
                 break;
             }
             case OP_BN: {
+                const BnPlan& p = op.bp;
                 ProfScope ps(e, F_ELEMWISE, 0.0);
-                {       // statistics: the conv epilogue's partials, or one pass over x; then x -> y (or -> the pooled tensor)
-                    double by = !training ? 0.0 : op.stats_nblk > 0 ? (double)op.stats_nblk * 2 * x.C * 4 : act_bytes(x);
-                    if (training && op.fused_first) by += act_bytes(x) + (double)x.rows() * (&op + 1)->ageom.Cin * 4.0;
-                    if (op.fuse_pool >= 0) {
-                        const Tensor& p = tw.t[tw.ops[op.fuse_pool].out];
-                        by += act_bytes(x) + act_bytes(p) + (training && op.xwin != nullptr ? (double)p.numel() * (x.d_bf16 ? 2.0 : 4.0) : 0.0);
-                    } else {
-                        by += act_bytes(x) + act_bytes(y);
-                    }
-                    ps.bytes(by);
-                }
+                ps.bytes(p.fwd_bytes);
                 const float* gamma = e->params[op.p_gamma].d;
                 const float* beta = e->params[op.p_beta].d;
-                const int mode = op.prerelu ? 2 : (op.fused_relu ? 1 : 0);
-                if (training && op.stats_nblk > 0)
-                    bn_stats_from_partials(e->stat_scratch, op.stats_nblk, e->params[op.bias_param].d, gamma, beta, op.mean,
-                                           op.var, op.scale, op.shift, x.rows(), x.C, BN_EPS, op.prerelu ? 1 : 0, e->stream);
-                else if (training && (op.prerelu || x.d_bf16))
-                    bn_stats_fast(x.d, gamma, beta, op.mean, op.var, op.scale, op.shift, e->red_scratch, x.rows(), x.C,
-                                  BN_EPS, op.prerelu ? 1 : 0, e->stream, x.d_bf16 ? 1 : 0);
-                else if (training)
-                    bn_stats(x.d, gamma, beta, op.mean, op.var, op.scale, op.shift, e->red_scratch, x.rows(), x.C,
-                             BN_EPS, e->stream);
-                else
-                    bn_scale_shift(gamma, beta, e->params[op.p_mmean].d, e->params[op.p_mvar].d, op.scale,
-                                   op.shift, x.C, BN_EPS, e->stream);
-                if (training && op.fused_first) {
-                    const Op& cv = *(&op + 1);          // the first conv follows its input BatchNorm directly
-                    bn_xhat_ones(x.d, op.mean, op.var, BN_EPS, cv.xaug, x.rows(), x.C, e->stream);
+                switch (p.stats) {
+                    case BS_PARTIALS:
+                        bn_stats_from_partials(e->stat_scratch, p.stat_blocks, e->params[op.bias_param].d, gamma, beta, op.mean, op.var,
+                                               op.scale, op.shift, x.rows(), x.C, BN_EPS, op.prerelu ? 1 : 0, e->stream);
+                        break;
+                    case BS_FAST:
+                        bn_stats_fast(x.d, gamma, beta, op.mean, op.var, op.scale, op.shift, e->red_scratch, x.rows(), x.C, BN_EPS,
+                                      op.prerelu ? 1 : 0, e->stream, x.d_bf16 ? 1 : 0);
+                        break;
+                    case BS_PLAIN:
+                        bn_stats(x.d, gamma, beta, op.mean, op.var, op.scale, op.shift, e->red_scratch, x.rows(), x.C, BN_EPS, e->stream);
+                        break;
+                    case BS_MOVING:
+                        bn_scale_shift(gamma, beta, e->params[op.p_mmean].d, e->params[op.p_mvar].d, op.scale, op.shift, x.C, BN_EPS,
+                                       e->stream);
+                        break;
                 }
-                if (op.fuse_pool >= 0) {
-                    const Op& pl = tw.ops[op.fuse_pool];
-                    Tensor& p = tw.t[pl.out];
-                    bn_relu_pool2_fwd(x.d, op.scale, op.shift, p.d, x.N, x.H, x.W, x.C, p.H, p.W, p.batch_stride,
-                                      mode, e->stream, p.d_bf16 ? 1 : 0, x.d_bf16 ? 1 : 0, training ? (void*)op.xwin : nullptr);
+                // the first conv follows its input BatchNorm directly and takes [x^, 1]
+                if (p.bwd == BB_BY_FIRST_CONV) bn_xhat_ones(x.d, op.mean, op.var, BN_EPS, (&op + 1)->xaug, x.rows(), x.C, e->stream);
+                if (op.fuse_pool >= 0) {      // the apply form follows the tensors' storage, fixed at creation
+                    Tensor& pl = tw.t[tw.ops[op.fuse_pool].out];
+                    bn_relu_pool2_fwd(x.d, op.scale, op.shift, pl.d, x.N, x.H, x.W, x.C, pl.H, pl.W, pl.batch_stride,
+                                      op.prerelu ? 2 : (op.fused_relu ? 1 : 0), e->stream, pl.d_bf16 ? 1 : 0, x.d_bf16 ? 1 : 0,
+                                      training ? (void*)op.xwin : nullptr);
                 } else if (y.d_bf16 || x.d_bf16) {
-                    bn_apply_fast(x.d, op.scale, op.shift, y.d, x.rows(), x.C, op.fused_relu ? 1 : 0, e->stream,
-                                  y.d_bf16 ? 1 : 0, x.d_bf16 ? 1 : 0);
+                    bn_apply_fast(x.d, op.scale, op.shift, y.d, x.rows(), x.C, op.fused_relu ? 1 : 0, e->stream, y.d_bf16 ? 1 : 0,
+                                  x.d_bf16 ? 1 : 0);
                 } else {
                     bn_apply(x.d, op.scale, op.shift, y.d, x.rows(), x.C, op.fused_relu ? 1 : 0, e->stream);
                 }
@@ -1328,7 +1435,14 @@ void tower_forward(l3_engine* e, Tower& tw, bool training) {
     }
 }
 
-void tower_backward_block(l3_engine* e, Tower& tw, int block, bool training) {
+// the BatchNorm(+ReLU) whose backward reduction a data gradient's epilogue leaves (ConvPlan::bwd_bn): a pooled BatchNorm stands in
+// with its winner tensor
+BnBwdFuse bn_bwd_fuse(const Tower& tw, const Op& bn) {
+    return BnBwdFuse{bn.fuse_pool >= 0 ? bn.xwin : tw.t[bn.in].d, bn.scale, bn.shift, bn.mean, bn.var, BN_EPS, bn.fused_relu ? 1 : 0};
+}
+
+void tower_backward_block(l3_engine* e, Tower& tw, int block) {
+    const bool training = tw.training;
     for (int oi = (int)tw.ops.size() - 1; oi >= 0; --oi) {
         Op& op = tw.ops[oi];
         if (op.block != block) continue;
@@ -1350,155 +1464,99 @@ void tower_backward_block(l3_engine* e, Tower& tw, int block, bool training) {
                 break;
             }
             case OP_BN: {
-                if (training && op.fused_first) break;      // gamma/beta gradients came from first_conv_grads
+                const BnPlan& p = op.bp;
+                if (p.bwd == BB_BY_FIRST_CONV) break;      // gamma/beta gradients come from first_conv_grads
                 ProfScope ps(e, F_ELEMWISE, 0.0);
+                ps.bytes(p.bwd_bytes);
                 const float* mean = training ? op.mean : e->params[op.p_mmean].d;
                 const float* var = training ? op.var : e->params[op.p_mvar].d;
-                if (bn_fast_ok(x.C)) {
-                    float* dbias = op.bias_param >= 0 ? e->params[op.bias_param].g : nullptr;
-                    {       // reduction over (x, dy) -- or the data gradient's epilogue partials --, then (x, dy) -> dx unless deferred
-                        const double dyb = op.fuse_pool >= 0 ? grad_bytes(tw.t[tw.ops[op.fuse_pool].out]) : grad_bytes(y);
-                        const bool defer0 = op.fuse_pool < 0 && training && op.defer_apply && x.d_bf16 == y.g_bf16;
-                        double by = op.bwd_part_blocks > 0 ? (double)op.bwd_part_blocks * 2 * x.C * 4 : act_bytes(x) + dyb;
-                        if (!defer0) by += act_bytes(x) + dyb + grad_bytes(x);
-                        ps.bytes(by);
-                    }
-                    if (op.fuse_pool >= 0) {
-                        const Tensor& p = tw.t[tw.ops[op.fuse_pool].out];
-                        bn_bwd_fast(x.d, op.scale, op.shift, mean, var, e->params[op.p_gamma].d, p.g, 1, x.N, x.H,
-                                    x.W, x.C, p.H, p.W, p.batch_stride, x.g, e->params[op.p_gamma].g,
-                                    e->params[op.p_beta].g, dbias, e->red_scratch, BN_EPS, op.prerelu ? 2 : 1,
-                                    training ? 1 : 0, e->stream, x.g_bf16 ? 1 : 0, x.d_bf16 ? 1 : 0, p.g_bf16 ? 1 : 0,
-                                    op.bwd_part_blocks > 0 ? e->stat_scratch : nullptr, op.bwd_part_blocks);
-                        op.bwd_part_blocks = 0;
-                    } else {
-                        // dx and the bias gradient: conv_first_wgrad (FirstWgFuse; both tensors fp32 or both bfloat16-stored)
-                        const bool defer = training && op.defer_apply && x.d_bf16 == y.g_bf16;
-                        op.apply_coeffs = defer ? bn_bwd_fast_coeffs(e->red_scratch, x.C) : nullptr;
-                        bn_bwd_fast(x.d, op.scale, op.shift, mean, var, e->params[op.p_gamma].d, y.g, 0, x.N, x.H,
-                                    x.W, x.C, x.H, x.W, (int64_t)x.H * x.W * x.C, defer ? nullptr : x.g, e->params[op.p_gamma].g,
-                                    e->params[op.p_beta].g, defer ? nullptr : dbias, e->red_scratch, BN_EPS, op.fused_relu ? 1 : 0,
-                                    training ? 1 : 0, e->stream, x.g_bf16 ? 1 : 0, x.d_bf16 ? 1 : 0, y.g_bf16 ? 1 : 0,
-                                    op.bwd_part_blocks > 0 ? e->stat_scratch : nullptr, op.bwd_part_blocks);
-                        op.bwd_part_blocks = 0;
-                    }
+                const float* gamma = e->params[op.p_gamma].d;
+                float *dgamma = e->params[op.p_gamma].g, *dbeta = e->params[op.p_beta].g;
+                if (p.bwd == BB_PLAIN) {
+                    bn_bwd(x.d, y.d, y.g, gamma, mean, var, x.g, dgamma, dbeta, e->red_scratch, x.rows(), x.C, BN_EPS, op.fused_relu ? 1 : 0,
+                           training ? 1 : 0, e->stream);
                     break;
                 }
-                ps.bytes(2.0 * (act_bytes(x) + grad_bytes(y)) + grad_bytes(x));
-                bn_bwd(x.d, y.d, y.g, e->params[op.p_gamma].d, mean, var, x.g, e->params[op.p_gamma].g,
-                       e->params[op.p_beta].g, e->red_scratch, x.rows(), x.C, BN_EPS, op.fused_relu ? 1 : 0,
-                       training ? 1 : 0, e->stream);
+                // pooled: dy is the gradient at the pooled output.  deferred: dx and the bias gradient are left to conv_first_wgrad
+                const bool pooled = p.bwd == BB_FAST_POOLED, defer = p.bwd == BB_FAST_DEFERRED;
+                const Tensor& dy = pooled ? tw.t[tw.ops[op.fuse_pool].out] : y;
+                bn_bwd_fast(x.d, op.scale, op.shift, mean, var, gamma, dy.g, pooled ? 1 : 0, x.N, x.H, x.W, x.C, dy.H, dy.W,
+                            pooled ? dy.batch_stride : (int64_t)x.H * x.W * x.C, defer ? nullptr : x.g, dgamma, dbeta,
+                            defer ? nullptr : op.bias_param >= 0 ? e->params[op.bias_param].g : nullptr, e->red_scratch, BN_EPS,
+                            pooled ? (op.prerelu ? 2 : 1) : (op.fused_relu ? 1 : 0), training ? 1 : 0, e->stream, x.g_bf16 ? 1 : 0,
+                            x.d_bf16 ? 1 : 0, dy.g_bf16 ? 1 : 0, p.bwd_blocks > 0 ? e->stat_scratch : nullptr, p.bwd_blocks);
                 break;
             }
             case OP_CONV: {
-                if (training && op.in_bn >= 0) {
+                const ConvPlan& p = op.cp;
+                const float* w = e->params[op.p_kernel].d;
+                if (p.wgrad == WG_AUG || p.wgrad == WG_AUG_DEFERRED) {
                     ProfScope ps(e, F_CONV_WGRAD, conv_flops(op.geom), op.name.c_str());
-                    ps.bytes((double)x.rows() * op.ageom.Cin * 4.0);       // [x^, 1]; + dY, or the conv output and the gradient behind its BatchNorm
+                    ps.bytes(p.wg_bytes);
                     const Op& bn = tw.ops[op.in_bn];
-                    const Op* fb = op.bn_defer >= 0 && tw.ops[op.bn_defer].apply_coeffs != nullptr ? &tw.ops[op.bn_defer] : nullptr;
-                    if (fb != nullptr) {
-                        // the BatchNorm behind this conv left coefficients, not dY: formed inside the weight-gradient kernel from the
-                        // conv's stored output and the gradient behind the BatchNorm; the bias gradient is the ones-channel row
-                        const Tensor &bi = tw.t[fb->in], &bo = tw.t[fb->out];
-                        const int C = op.cout;
-                        const FirstWgFuse f{bi.d, bo.g, fb->scale, fb->shift, fb->apply_coeffs, fb->apply_coeffs + C,
-                                            fb->apply_coeffs + 2 * C, fb->fused_relu ? 1 : 0, bi.d_bf16 ? 1 : 0};
-                        ps.bytes(act_bytes(bi) + grad_bytes(bo));
+                    if (p.wgrad == WG_AUG_DEFERRED) {
+                        // the BatchNorm behind this conv left coefficients (in the scratch of its bn_bwd_fast), not dY: formed inside the
+                        // weight-gradient kernel from the conv's stored output and the gradient behind the BatchNorm; the bias gradient
+                        // is the ones-channel row
+                        const Op& fb = tw.ops[op.bn_defer];
+                        const Tensor &bi = tw.t[fb.in], &bo = tw.t[fb.out];
+                        const float* co = bn_bwd_fast_coeffs(e->red_scratch, op.cout);
+                        const FirstWgFuse f{bi.d, bo.g, fb.scale, fb.shift, co, co + op.cout, co + 2 * op.cout, fb.fused_relu ? 1 : 0,
+                                            bi.d_bf16 ? 1 : 0};
                         conv_wgrad(op.xaug, nullptr, op.gaug, e->wg_scratch, op.ageom, e->stream, false, false, &f);
                     } else {
-                        ps.bytes(grad_bytes(y));
                         conv_wgrad(op.xaug, y.g, op.gaug, e->wg_scratch, op.ageom, e->stream);
                     }
-                    first_conv_grads(op.gaug, e->params[op.p_kernel].d, e->params[bn.p_gamma].d, e->params[bn.p_beta].d,
-                                     e->params[op.p_kernel].g, e->params[bn.p_gamma].g, e->params[bn.p_beta].g,
-                                     op.bias_by_bn && fb == nullptr ? nullptr : e->params[op.p_bias].g, op.kh * op.kw, x.C, op.cout,
+                    first_conv_grads(op.gaug, w, e->params[bn.p_gamma].d, e->params[bn.p_beta].d, e->params[op.p_kernel].g,
+                                     e->params[bn.p_gamma].g, e->params[bn.p_beta].g,
+                                     op.bias_by_bn && p.wgrad == WG_AUG ? nullptr : e->params[op.p_bias].g, op.kh * op.kw, x.C, op.cout,
                                      e->stream);
                     break;
                 }
                 {
-                    const bool wbf = e->cfg.dtype == L3_DTYPE_BF16 && conv_wgrad_bf16_ok(op.geom);
-                    ProfScope ps(e, F_CONV_WGRAD, conv_flops(op.geom), op.name.c_str(), conv_wgrad_executed_flops(op.geom, wbf));
-                    ps.bytes(act_bytes(x) + grad_bytes(y) + (double)e->params[op.p_kernel].numel * 4.0);
-                    conv_wgrad(x.d, y.g, e->params[op.p_kernel].g, e->wg_scratch, op.geom, e->stream,
-                               e->cfg.dtype == L3_DTYPE_BF16 && conv_wgrad_bf16_ok(op.geom), x.d_bf16 && y.g_bf16);
+                    ProfScope ps(e, F_CONV_WGRAD, conv_flops(op.geom), op.name.c_str(), p.wg_executed);
+                    ps.bytes(p.wg_bytes);
+                    conv_wgrad(x.d, y.g, e->params[op.p_kernel].g, e->wg_scratch, op.geom, e->stream, p.wgrad != WG_FP32,
+                               p.wgrad == WG_BF16_STORED);
                 }
-                if (!op.bias_by_bn) {
+                if (p.colsum) {
                     ProfScope ps(e, F_ELEMWISE, 0.0);
                     ps.bytes(grad_bytes(y));
                     colsum(y.g, e->params[op.p_bias].g, e->red_scratch, y.rows(), y.C, e->stream);
                 }
-                if (op.need_dx) {
-                    ProfScope ps(e, F_CONV_DGRAD, conv_flops(op.geom), op.name.c_str(),
-                                 op.wino_ud && !(e->cfg.dtype == L3_DTYPE_BF16 && conv_bf16_ok(op.dgeom))
-                                     ? conv_wino_executed_flops(op.dgeom)
-                                     : -1.0);
-                    ps.bytes(grad_bytes(y) + grad_bytes(x) + (double)e->params[op.p_kernel].numel * 4.0);
-                    if (!conv_dgrad_small(y.g, e->params[op.p_kernel].d, x.g, op.geom, e->stream)) {
-                        if (e->cfg.dtype == L3_DTYPE_BF16 && conv_bf16_ok(op.dgeom)) {
-                            if (y.g_bf16) {      // filter cast once into the (now free) forward-operand buffer
-                                conv_weights_bf16(e->params[op.p_kernel].d, op.wflip, op.kh, op.kw, x.C, op.cout, false,
-                                                  e->stream);
-                                // (BatchNorm-backward partials in the epilogue as in the fp32 branch below; bf16-stored tensors)
-                                Op* bn = training && op.dy_to_bn >= 0 && e->stat_scratch != nullptr && x.g_bf16 &&
-                                                 conv_bf16_halo_ok(op.dgeom) && tw.t[tw.ops[op.dy_to_bn].in].d_bf16
-                                             ? &tw.ops[op.dy_to_bn]
-                                             : nullptr;
-                                if (bn != nullptr && bn->fuse_pool >= 0 && (bn->xwin == nullptr || x.batch_stride != (int64_t)x.H * x.W * x.C))
-                                    bn = nullptr;
-                                if (bn != nullptr) {
-                                    const BnBwdFuse bb{bn->fuse_pool >= 0 ? bn->xwin : tw.t[bn->in].d, bn->scale, bn->shift, bn->mean, bn->var,
-                                                       BN_EPS, bn->fused_relu ? 1 : 0};
-                                    conv_bf16_fwd(y.g, op.wflip, nullptr, x.g, op.dgeom, e->stream, true, e->stat_scratch, 0, true, &bb);
-                                    bn->bwd_part_blocks = conv_bf16_stat_blocks(op.dgeom);
-                                } else {
-                                    conv_bf16_fwd(y.g, op.wflip, nullptr, x.g, op.dgeom, e->stream, true, nullptr, 0, x.g_bf16);
-                                }
-                            } else {
-                                conv_bf16_fwd(y.g, e->params[op.p_kernel].d, nullptr, x.g, op.dgeom, e->stream);
-                            }
-                        } else if (op.wino_ud) {
-                            conv_wino_transform_weights(e->params[op.p_kernel].d, op.wino_ud, op.dgeom, true, e->stream);
-                            // the gradient this launch writes is dL/dy of the BatchNorm(+ReLU) in front of the conv: leave
-                            // that BatchNorm's backward reduction partials in the epilogue (fp32 tensors only)
-                            Op* bn = training && op.dy_to_bn >= 0 && e->stat_scratch != nullptr && !x.g_bf16 ? &tw.ops[op.dy_to_bn] : nullptr;
-                            if (bn != nullptr && bn->fuse_pool >= 0 && (bn->xwin == nullptr || x.batch_stride != (int64_t)x.H * x.W * x.C))
-                                bn = nullptr;
-                            if (bn != nullptr && !tw.t[bn->in].d_bf16 && conv_wino_ok(op.dgeom)) {
-                                const BnBwdFuse bb{bn->fuse_pool >= 0 ? bn->xwin : tw.t[bn->in].d, bn->scale, bn->shift, bn->mean, bn->var,
-                                                   BN_EPS, bn->fused_relu ? 1 : 0};
-                                conv_fwd(y.g, nullptr, nullptr, x.g, op.dgeom, e->stream, op.wino_ud, e->stat_scratch, 0, &bb);
-                                bn->bwd_part_blocks = conv_wino_stat_blocks(op.dgeom);
-                            } else {
-                                conv_fwd(y.g, nullptr, nullptr, x.g, op.dgeom, e->stream, op.wino_ud);
-                            }
-                        } else {
-                            conv_flip_weights(e->params[op.p_kernel].d, op.wflip, op.kh, op.kw, x.C, op.cout, e->stream);
-                            conv_fwd(y.g, op.wflip, nullptr, x.g, op.dgeom, e->stream);
-                        }
-                    }
+                if (p.dgrad == DG_NONE) break;
+                ProfScope ps(e, F_CONV_DGRAD, conv_flops(op.geom), op.name.c_str(), p.dg_executed);
+                ps.bytes(p.dg_bytes);
+                BnBwdFuse bb{};
+                if (p.bwd_bn >= 0) bb = bn_bwd_fuse(tw, tw.ops[p.bwd_bn]);
+                const BnBwdFuse* fuse = p.bwd_bn >= 0 ? &bb : nullptr;
+                float* part = p.bwd_bn >= 0 ? e->stat_scratch : nullptr;
+                switch (p.dgrad) {
+                    case DG_SMALL:
+                        (void)conv_dgrad_small(y.g, w, x.g, op.geom, e->stream);
+                        break;
+                    case DG_BF16_STORED:       // filter cast once into the (now free) forward-operand buffer
+                        conv_weights_bf16(w, op.wflip, op.kh, op.kw, x.C, op.cout, false, e->stream);
+                        conv_bf16_fwd(y.g, op.wflip, nullptr, x.g, op.dgeom, e->stream, true, part, 0, x.g_bf16, fuse);
+                        break;
+                    case DG_BF16_CAST:
+                        conv_bf16_fwd(y.g, w, nullptr, x.g, op.dgeom, e->stream);
+                        break;
+                    case DG_WINO:
+                        conv_wino_transform_weights(w, op.wino_ud, op.dgeom, true, e->stream);
+                        conv_fwd(y.g, nullptr, nullptr, x.g, op.dgeom, e->stream, op.wino_ud, part, 0, fuse);
+                        break;
+                    case DG_FLIPPED:
+                        conv_flip_weights(w, op.wflip, op.kh, op.kw, x.C, op.cout, e->stream);
+                        conv_fwd(y.g, op.wflip, nullptr, x.g, op.dgeom, e->stream);
+                        break;
+                    case DG_NONE: break;
                 }
                 break;
             }
             default: break;
         }
     }
-}
-
-// ConvGeom::solo of every convolution of a tower: 1 while the tower runs on its own (l3_tower_step, l3_embed_*), 0 in the
-// two-tower step (kernels.h)
-void set_solo(l3_engine* e, Tower& tw, int v) {
-    for (auto& op : tw.ops)
-        if (op.kind == OP_CONV) {
-            op.geom.solo = op.dgeom.solo = v;
-            // while a communicator exists its collectives may hold CUs beside any launch of the step: tile blocks through work counters
-            op.geom.dynamic = op.dgeom.dynamic = e->comm != nullptr ? 1 : 0;
-            // the channel-slice tail of a solo F(4x4,3x3) launch writes into the engine's own scratch (freed with the engine).  Only
-            // there: the one buffer serves one stream.  The two-tower step never splits tails in the product; when a test forces it
-            // (L3_W4_TAIL=2) its two streams must not share a buffer, so they fall back to the per-(device, stream) pool.
-            float* ts = v ? e->w4_tail : nullptr;
-            op.geom.tail_scratch = op.dgeom.tail_scratch = ts;
-            op.geom.tail_scratch_bytes = op.dgeom.tail_scratch_bytes = ts ? conv_wino4_tail_scratch_bytes() : 0;
-        }
 }
 
 // The L2 penalty's sums of squares (kernel_regularizer of every Conv2D / Dense kernel, l3embedding/audio_model.py:372-377,
@@ -1524,8 +1582,8 @@ void l2_sums(l3_engine* e) {
 
 int forward_all(l3_engine* e, bool training) {
     int rc;
-    set_solo(e, e->vis, 0);
-    set_solo(e, e->aud, 0);
+    e->fwd_done = false;      // the plans below belong to this pass: no backward of an earlier one may run under them
+    if ((rc = plan_tower(e, e->vis, training, 0)) || (rc = plan_tower(e, e->aud, training, 0))) return rc;
     if (e->side && e->overlap) {
         HIPCHK(e, hipEventRecord(e->ev_fork, e->stream));
         HIPCHK(e, hipStreamWaitEvent(e->side, e->ev_fork, 0));
@@ -1533,16 +1591,16 @@ int forward_all(l3_engine* e, bool training) {
         {
             SideScope sd(e);
             if ((rc = run_frontend(e))) return rc;
-            tower_forward(e, e->aud, training);
+            tower_forward(e, e->aud);
             HIPCHK(e, hipEventRecord(e->ev_join, e->stream));
         }
-        tower_forward(e, e->vis, training);
+        tower_forward(e, e->vis);
         HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_join, 0));
     } else {
         l2_sums(e);
         if ((rc = run_frontend(e))) return rc;
-        tower_forward(e, e->vis, training);
-        tower_forward(e, e->aud, training);
+        tower_forward(e, e->vis);
+        tower_forward(e, e->aud);
     }
     ProfScope ps(e, F_HEAD, 0.0);
     const int D = e->nv + e->na;
@@ -1576,11 +1634,11 @@ int backward_bucket(l3_engine* e, int bucket, bool join = true) {
         return L3_EINVAL;
     }
     if (bucket <= nbv) {
-        tower_backward_block(e, e->vis, nbv - bucket, e->last_training);
+        tower_backward_block(e, e->vis, nbv - bucket);
     } else if (e->side && e->overlap) {
         {
             SideScope sd(e);
-            tower_backward_block(e, e->aud, nba - (bucket - nbv), e->last_training);
+            tower_backward_block(e, e->aud, nba - (bucket - nbv));
             HIPCHK(e, hipEventRecord(e->ev_join, e->stream));
             // data-parallel step: the bucket is final HERE, on the side stream -- its all-reduce may start now, whatever the vision
             // tower still has queued on the main stream (round 3 recorded the event on the main stream behind the join: an audio
@@ -1595,7 +1653,7 @@ int backward_bucket(l3_engine* e, int bucket, bool join = true) {
         // block wait for this one; its update waits for the communicator stream, which has waited for every bucket's event)
         if (join) HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_join, 0));
     } else {
-        tower_backward_block(e, e->aud, nba - (bucket - nbv), e->last_training);
+        tower_backward_block(e, e->aud, nba - (bucket - nbv));
     }
     return L3_OK;
 }
@@ -1819,7 +1877,7 @@ int l3_create(const l3_config* cfg, uint64_t seed, l3_engine** out) {
         }
         e->own_stream = true;
     }
-    static const int two_streams = l3_knob("L3_TWO_STREAMS") ? atoi(l3_knob("L3_TWO_STREAMS")) : 1;
+    static const int two_streams = knob_int("L3_TWO_STREAMS", 1);
     if (two_streams) {
         if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -2196,13 +2254,13 @@ int l3_tower_step(l3_engine* e, int tower, int backward) {
     if (rc) return rc;
     Tower& tw = tower == 0 ? e->vis : e->aud;
     if (tower == 1 && (rc = run_frontend(e))) return rc;
-    set_solo(e, tw, 1);
-    tower_forward(e, tw, true);
+    if ((rc = plan_tower(e, tw, true, 1))) return rc;
+    tower_forward(e, tw);
     if (backward) {
         // stand-in loss = mean of the tower output: d loss / d out = 1 / (B * width)
         const int width = tower == 0 ? e->nv : e->na;
         fill(e->dh0, 1.0f / ((float)e->B * (float)width), (int64_t)e->B * (e->nv + e->na), e->stream);
-        for (int b = tw.nblocks - 1; b >= 0; --b) tower_backward_block(e, tw, b, true);
+        for (int b = tw.nblocks - 1; b >= 0; --b) tower_backward_block(e, tw, b);
     }
     e->fwd_done = false;
     HIPCHK(e, hipGetLastError());
@@ -2281,7 +2339,7 @@ static int comm_init_after_create(l3_engine* e) {
     // sequence of ncclAllReduce / ncclAllGather calls.  It is decided HERE, once, from this rank's configuration, and the ranks
     // compare what they decided (max of x and of -x over the ranks): a rank that serialised its towers, another model, another
     // dp_moving or another precision on one rank would otherwise hang or corrupt silently at the first step.
-    e->dp_order_alt = e->side != nullptr && e->overlap && !(l3_knob("L3_DP_ARENA_ORDER") && atoi(l3_knob("L3_DP_ARENA_ORDER")) == 1);
+    e->dp_order_alt = e->side != nullptr && e->overlap && knob_int("L3_DP_ARENA_ORDER", 0) != 1;
     const double mine[4] = {e->dp_order_alt ? 1.0 : 0.0, (double)e->buckets.size(), (double)e->cfg.dp_moving,
                             (double)(e->cfg.model_type * 2 + e->cfg.dtype)};
     double v[8];
@@ -2734,8 +2792,8 @@ static int embed_rows(l3_engine* e, bool vision, const EmbedSource& src, int64_t
             rc = run_frontend(e);
             if (rc) return rc;
         }
-        set_solo(e, tw, 1);
-        tower_forward(e, tw, false);
+        if ((rc = plan_tower(e, tw, false, 1))) return rc;
+        tower_forward(e, tw);
         maxpool_fwd(t.d, e->emb_out + (size_t)(s0 - f0) * D, pg, e->stream);
         if (s0 + cnt == n || s0 + 2 * B - f0 > cap_rows) {
             HIPCHK(e, hipMemcpyAsync(out + (size_t)f0 * D, e->emb_out, (size_t)(s0 + cnt - f0) * D * 4, hipMemcpyDeviceToHost, e->stream));

@@ -28,6 +28,14 @@ inline std::string no_gpu_message(const char* fn, int device) {
     return std::string(fn) + ": HIP device " + std::to_string(device) + " not available (libl3hip needs an AMD GPU)";
 }
 
+// TensorFlow 'SAME' padding: output length and the padding in front, for n inputs, window k, stride s
+inline void tf_same(int n, int k, int s, int* out, int* before) {
+    *out = (n + s - 1) / s;
+    int total = (*out - 1) * s + k - n;
+    if (total < 0) total = 0;
+    *before = total / 2;
+}
+
 // bfloat16 storage read back as the float of the same value
 inline void widen_bf16(float* dst, const uint16_t* src, size_t n) {
     for (size_t i = 0; i < n; ++i) {

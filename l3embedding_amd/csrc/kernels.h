@@ -69,7 +69,8 @@ void conv_wino_fwd(const float* x, const float* u, const float* bias, float* y, 
 int conv_wino_stat_blocks(const ConvGeom& g);          // partial blocks the Winograd kernel writes (0: not eligible)
 int conv_wino_stat_blocks_max(const ConvGeom& g);      // over F(2x2,3x3) / F(4x4,3x3): for sizing the partial scratch
 // data gradient of a first-layer conv (Cin in {1,3}, 64 filters, 3x3 'same'); g is the FORWARD
-// geometry, w the forward filter.  Returns false (nothing launched) for other shapes.
+// geometry, w the forward filter.  Returns false (nothing launched) for other shapes: those conv_dgrad_small_ok(g) refuses.
+bool conv_dgrad_small_ok(const ConvGeom& g);
 bool conv_dgrad_small(const float* dy, const float* w, float* dx, const ConvGeom& g, hipStream_t s);
 // wt[kh][kw][co][ci] = w[KH-1-kh][KW-1-kw][ci][co]  (dgrad filter)
 void conv_flip_weights(const float* w, float* wt, int KH, int KW, int Cin, int Cout, hipStream_t s);

@@ -48,13 +48,6 @@ struct Scope {
     }
 };
 
-void tf_same(int n, int k, int s, int* out, int* before) {
-    *out = (n + s - 1) / s;
-    int total = (*out - 1) * s + k - n;
-    if (total < 0) total = 0;
-    *before = total / 2;
-}
-
 ConvGeom make_geom(int n, int h, int w, int cin, int cout, int kh, int kw, int same) {
     ConvGeom g{n, h, w, cin, 0, 0, cout, kh, kw, 0, 0};
     if (same) {
