@@ -578,6 +578,59 @@ int l3_op_vggish_conv(int device, int fp32_conv, const float *x, const float *w,
 int l3_op_vggish_postprocess(int device, const float *emb, int64_t n, const float *pca_matrix, const float *pca_means,
                              int quantize, float *out);
 
+/* ---- Fold preprocessing of the downstream classifier (data/usc/features.py:52-150,243-253) -------------------------------------
+ * preprocess_split_data's passes over the (n, D) feature matrix on the GPU: the row selection of remove_data_overlap (:60-73) and of
+ * the final shuffle (:143-148), MinMaxScaler's fit and transform (:107-113), compute_stats_features per file (:76-85,243-253) and
+ * StandardScaler's fit and transform (:131-141).  A handle separate from l3_engine, l3_mlp and l3_svm: it owns ONE float32 row-major
+ * matrix on one device and one stream; every operation replaces that matrix and has finished when the call returns; calls on one
+ * handle are not re-entrant.  Every D-sized piece of scaler arithmetic (ranges, scales, square roots, the zero rule of sklearn's
+ * _handle_zeros) stays with the caller.  Deterministic: no float atomics, and the sums over rows run over fixed chunks of
+ * L3_FEAT_CHUNK_ROWS rows whose partial results are added in chunk order, whatever the launch geometry.  NaN inputs are out of
+ * contract (the extrema and the median order values as finite floats; -0.0 sorts below +0.0).  Errors: l3_last_error(NULL). */
+#define L3_FEAT_CHUNK_ROWS 256        /* rows per partial sum of l3_feat_minmax / l3_feat_moments */
+#define L3_FEAT_STATS_LDS_ROWS 64     /* l3_feat_file_stats keeps a file of up to this many rows in LDS; longer files are re-read
+                                         from global memory by the same kernel */
+typedef struct l3_feat l3_feat;
+/* X (n, D) float32 row major, copied to the device once.  1 <= n <= 2^31 - 1, 1 <= D <= 2^21 (any D, not only multiples of 4). */
+int l3_feat_create(int device, const float *X, int64_t n, int64_t D, l3_feat **f);
+void l3_feat_destroy(l3_feat *f);
+int l3_feat_shape(const l3_feat *f, int64_t *n, int64_t *D);
+/* rows [lo, hi) -> dst ((hi - lo), D) */
+int l3_feat_download(l3_feat *f, int64_t lo, int64_t hi, float *dst);
+/* X <- X[rows]: n_out >= 1 host indices, each in [0, n) (else L3_EINVAL, and the matrix stays as it was).  The caller builds the
+ * table -- every chunk_size-th row of each file, or the shuffle's permutation -- and the device moves the rows. */
+int l3_feat_gather(l3_feat *f, const int64_t *rows, int64_t n_out);
+/* np.min / np.max(X, axis=0), D floats each, exact */
+int l3_feat_minmax(l3_feat *f, float *min_out, float *max_out);
+/* MinMaxScaler.transform's `X *= scale_; X += min_` on a float32 matrix: x <- fl32(fl32(x * scale[j]) + shift[j]), two float32
+ * roundings, never a fused multiply-add */
+int l3_feat_affine32(l3_feat *f, const float *scale, const float *shift);
+/* X.mean(axis=0, dtype=float64) and X.var(axis=0, dtype=float64) (population variance), D doubles each: two passes, the second over
+ * fl64(x) - mean.  NumPy adds the rows one after the other; here each chunk of L3_FEAT_CHUNK_ROWS rows is added in row order and
+ * the chunks' sums in chunk order, so the results agree to the rounding error of two float64 sums of n terms, and
+ * two calls give the same bits. */
+int l3_feat_moments(l3_feat *f, double *mean_out, double *var_out);
+/* StandardScaler.transform's in-place `X -= mean_; X /= scale_` on a float32 matrix with float64 operands:
+ * x <- fl32(fl64(fl32(fl64(x) - mean[j])) / scale[j]), each step computed in float64 and rounded to float32 */
+int l3_feat_standardize(l3_feat *f, const double *mean, const double *scale);
+/* framewise_to_stats: X <- (n_files, 7 D), row i = compute_stats_features(X[s_i:e_i]) for file_idxs[i] = {s_i, e_i} (int64 pairs,
+ * 0 <= s_i < e_i <= n; 7 D <= 2^21).  Per column, in blocks of D: min, max (exact); median (the middle element, or fl32(fl32(a + b) / 2) of the
+ * two middle ones; a bitwise radix select, linear in the file's rows); mean (float32 sum in row order / fl32(F)); var (float32 sum
+ * in row order of fl32(x - mean)^2, / fl32(F)); skew and excess kurtosis with scipy's bias=True defaults: float64 mean in row order,
+ * d = fl64(x) - mean, m2 m3 m4 the row-order float64 means of d^2 d^3 d^4, skew 0 and kurtosis -3 where
+ * m2 <= (1e-15 * mean)^2, else m3 / m2^1.5 and m4 / m2^2 - 3, cast to float32.  The first five blocks are NumPy's bits;
+ * the last two differ from NumPy by the roundings of d * d * d against pow(d, 3). */
+int l3_feat_file_stats(l3_feat *f, const int64_t *file_idxs, int64_t n_files);
+
+/* l3_mlp_set_data from device matrices: rows [lo, hi) of `train` and rows [vlo, vhi) of `valid` (NULL or vlo == vhi: none; it may be
+ * the same handle as `train`) are copied device to device, on the MLP's stream, into the MLP's own resident matrices; the l3_feat
+ * handles may be destroyed afterwards.  y / yv: host class indices, one per copied row.  Checks and error codes as l3_mlp_set_data;
+ * also L3_EINVAL for a handle on another device or of another width than the MLP's D. */
+int l3_mlp_set_data_dev(l3_mlp *m, const l3_feat *train, int64_t lo, int64_t hi, const int32_t *y, const l3_feat *valid, int64_t vlo,
+                        int64_t vhi, const int32_t *yv);
+/* l3_mlp_predict of rows [lo, hi) of a device matrix, in l3_mlp_predict's row blocks without its staging copy: the same bits */
+int l3_mlp_predict_dev(l3_mlp *m, const l3_feat *x, int64_t lo, int64_t hi, float *probs_out);
+
 #ifdef __cplusplus
 }
 #endif

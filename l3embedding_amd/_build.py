@@ -15,10 +15,11 @@ LIBPATH = os.path.join(LIBDIR, 'libl3hip.so')
 # F(2x2,3x3) = l3_config.fp32_conv F2X2 + the dispatch, F(3x3,2x2) weight gradient, direct implicit GEMM for the DFT and every
 # geometry Winograd does not take), mixed precision (halo forward / data gradient, transpose-read weight gradient, the dispatch +
 # fp32-tensor entry points), first layers, BatchNorm / pool, head / loss / Adam, front-end, clip framing, resampling, engine, operator
-# entry points, RCCL, the downstream MLP and SVM classifiers, the VGGish baseline features, training-set augmentation.
+# entry points, RCCL, the downstream MLP and SVM classifiers, the VGGish baseline features, training-set augmentation, the
+# classifier's fold preprocessing.
 SOURCES = ['conv.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_bf16.hip', 'conv_bf16_halo.hip', 'conv_wgrad_bf16.hip', 'conv_wgrad_wino.hip',
            'conv_first.hip', 'elementwise.hip', 'bn_fused.hip', 'frontend.hip', 'clips.hip', 'resample.hip', 'engine.hip', 'ops.hip',
-           'comm.hip', 'mlp.hip', 'svm.hip', 'vggish.hip', 'augment.hip']
+           'comm.hip', 'mlp.hip', 'svm.hip', 'vggish.hip', 'augment.hip', 'featprep.hip']
 # Measured-and-rejected kernel variants (split-bf16 fp32 convolutions, flat-tile MODE 5, tap-split bf16 weight gradient; round 6: the
 # filter-in-registers 64-channel halo kernel, the split-bf16 first convolution): records of negative results (profiles/r05_bx6_ablations.txt,
 # r05_bf16_conv_notes.txt, r06_halo64_regfilter.txt, r06_first_conv_mfma.txt), NOT product paths.  L3_BUILD_EXPERIMENTS=1 compiles them
@@ -32,8 +33,10 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC'] + (['-DL3_EXPERI
 # conv_first.hip: the weight gradient's 32 / 48 accumulator registers in arch VGPRs (-amdgpu-mfma-vgpr-form): left to choose, the
 # compiler kept them half in AGPRs and permuted the whole set through v_accvgpr_read / _write at every loop end (16 of 79 VALU
 # instructions per 4-pixel unit, round 6)
+# featprep.hip: its contract counts float32 / float64 roundings (NumPy's in-place scaler arithmetic), so no multiply and add may
+# be contracted into a fused multiply-add
 FILE_FLAGS = {'conv_wino4.hip': ['-fno-slp-vectorize'], 'conv_wino_bx6.hip': ['-fno-slp-vectorize'], 'conv_wgrad_bx6.hip': ['-fno-slp-vectorize'],
-              'conv_first.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}
+              'conv_first.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'featprep.hip': ['-ffp-contract=off']}
 
 
 def _headers():

@@ -192,6 +192,20 @@ SIGNATURES = {
     'l3_op_vggish_bias_relu': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5),
     'l3_op_vggish_postprocess': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'l3_op_vggish_conv': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6),
+    # fold preprocessing of the classifier (csrc/featprep.hip) and its hand-off to the MLP (csrc/mlp.hip)
+    'l3_feat_create': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    'l3_feat_destroy': (None, [C.c_void_p]),
+    'l3_feat_shape': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'l3_feat_download': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'l3_feat_gather': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_feat_minmax': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_feat_affine32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_feat_moments': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_feat_standardize': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_feat_file_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_mlp_set_data_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                      C.c_void_p]),
+    'l3_mlp_predict_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
 }
 
 
@@ -921,6 +935,107 @@ class MLP(object):
         if x.shape[0]:
             check(self.lib.l3_mlp_predict(self.h, _ptr(x), x.shape[0], _ptr(out)))
         return out
+
+    def set_data_dev(self, train, lo, hi, y_train, valid=None, vlo=0, vhi=0, y_valid=None):
+        """set_data from rows [lo, hi) of the Features `train` and rows [vlo, vhi) of `valid` (may be `train` itself), copied
+        device to device; the Features may be closed afterwards"""
+        yt = _i32(y_train)
+        yv = _i32(y_valid) if valid is not None and vhi > vlo else None
+        if yt.shape != (hi - lo,) or (yv is not None and yv.shape != (vhi - vlo,)):
+            raise ValueError('one label per copied row is needed')
+        check(self.lib.l3_mlp_set_data_dev(self.h, train.h, int(lo), int(hi), _ptr(yt), None if yv is None else valid.h,
+                                           int(vlo), int(vhi), _ptr(yv)))
+        self.n_train, self.n_valid = int(hi - lo), 0 if yv is None else int(vhi - vlo)
+
+    def predict_dev(self, feat, lo=0, hi=None):
+        """predict of rows [lo, hi) of the Features `feat`, without a trip through the host"""
+        hi = feat.shape[0] if hi is None else hi
+        out = np.empty((max(0, hi - lo), self.C), np.float32)
+        if hi > lo:
+            check(self.lib.l3_mlp_predict_dev(self.h, feat.h, int(lo), int(hi), _ptr(out)))
+        return out
+
+
+# ---- fold preprocessing of the classifier (data/usc/features.py:52-150,243-253; csrc/featprep.hip) ---------------------------------
+FEAT_CHUNK_ROWS = 256          # L3_FEAT_CHUNK_ROWS
+FEAT_STATS_LDS_ROWS = 64       # L3_FEAT_STATS_LDS_ROWS
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+class Features(object):
+    """RAII wrapper over an l3_feat handle: one float32 (n, D) matrix on one device, replaced by each operation."""
+
+    def __init__(self, X, device=0):
+        self.lib = load()
+        X = np.asarray(X)
+        if X.dtype != np.float32 or X.ndim != 2:
+            raise ValueError('a 2-d float32 matrix is needed, not %s of %d dimensions' % (X.dtype, X.ndim))
+        x = np.ascontiguousarray(X)
+        h = C.c_void_p()
+        check(self.lib.l3_feat_create(int(device), _ptr(x), x.shape[0], x.shape[1], C.byref(h)), None)
+        self.h = h
+        self.device = int(device)
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_feat_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def shape(self):
+        n, d = C.c_int64(), C.c_int64()
+        check(self.lib.l3_feat_shape(self.h, C.byref(n), C.byref(d)))
+        return (n.value, d.value)
+
+    def download(self, lo=0, hi=None):
+        n, d = self.shape
+        hi = n if hi is None else hi
+        out = np.empty((max(0, hi - lo), d), np.float32)
+        check(self.lib.l3_feat_download(self.h, int(lo), int(hi), _ptr(out)))
+        return out
+
+    def gather(self, rows):
+        r = _i64(rows)
+        check(self.lib.l3_feat_gather(self.h, _ptr(r), r.size))
+
+    def minmax(self):
+        d = self.shape[1]
+        lo, hi = np.empty(d, np.float32), np.empty(d, np.float32)
+        check(self.lib.l3_feat_minmax(self.h, _ptr(lo), _ptr(hi)))
+        return lo, hi
+
+    def affine32(self, scale, shift):
+        a, b = _f32(scale), _f32(shift)
+        if a.shape != (self.shape[1],) or b.shape != a.shape:
+            raise ValueError('scale and shift need one entry per column')
+        check(self.lib.l3_feat_affine32(self.h, _ptr(a), _ptr(b)))
+
+    def moments(self):
+        d = self.shape[1]
+        mean, var = np.empty(d, np.float64), np.empty(d, np.float64)
+        check(self.lib.l3_feat_moments(self.h, _ptr(mean), _ptr(var)))
+        return mean, var
+
+    def standardize(self, mean, scale):
+        a, b = _f64(mean), _f64(scale)
+        if a.shape != (self.shape[1],) or b.shape != a.shape:
+            raise ValueError('mean and scale need one entry per column')
+        check(self.lib.l3_feat_standardize(self.h, _ptr(a), _ptr(b)))
+
+    def file_stats(self, file_idxs):
+        f = _i64(file_idxs)
+        if f.ndim != 2 or f.shape[1] != 2:
+            raise ValueError('file_idxs must be (n_files, 2) row ranges')
+        check(self.lib.l3_feat_file_stats(self.h, _ptr(f), f.shape[0]))
 
 
 def op_mlp_dense_fwd(x, w, b, idx=None, relu=True, device=0):

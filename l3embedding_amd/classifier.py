@@ -24,7 +24,7 @@ import numpy as np
 
 from . import _lib, callbacks, kerasfile
 from .svm import SVC, hinge_loss  # noqa: F401  (re-exported: the reference imports them into classifier/train.py)
-from .usc import get_split, preprocess_split_data
+from .usc import DeviceFeatures, get_split, preprocess_split_data
 
 LOGGER = logging.getLogger('classifier')
 
@@ -147,12 +147,19 @@ class MLPModel(object):
         self.set_weights(kerasfile.load_dense_weights(filepath))
 
     def predict(self, x, batch_size=None, verbose=0):
-        return self._handle(self._h.batch if self._h is not None else 64).predict(x)
+        h = self._handle(self._h.batch if self._h is not None else 64)
+        return h.predict_dev(x.handle) if isinstance(x, DeviceFeatures) else h.predict(x)
 
     def fit(self, x, y, batch_size=64, epochs=1, verbose=0, callbacks=None, validation_split=0.0, validation_data=None,
             shuffle=True, random_state=None):
         """keras Model.fit with shuffle=True: y one-hot (n, C); validation_split takes the LAST fraction of x before any
-        shuffling (split_at = int(n * (1 - validation_split))).  -> {'loss': [...], 'acc': [...], 'val_loss': ..., 'val_acc': ...}"""
+        shuffling (split_at = int(n * (1 - validation_split))).  -> {'loss': [...], 'acc': [...], 'val_loss': ..., 'val_acc': ...}
+
+        x (and the validation features) may be usc.DeviceFeatures: their rows are then copied on the device into the model's
+        own matrices, validation_split slicing by row range."""
+        if isinstance(x, DeviceFeatures):
+            return self._fit(*self._set_data_dev(x, y, int(batch_size), validation_split, validation_data), batch_size=batch_size,
+                             epochs=epochs, verbose=verbose, callbacks=callbacks, shuffle=shuffle, random_state=random_state)
         x = np.asarray(x, np.float32)
         labels = np.argmax(np.asarray(y), axis=1).astype(np.int32)
         if validation_data is not None:
@@ -166,23 +173,47 @@ class MLPModel(object):
             vx = vy = None
         h = self._handle(int(batch_size))
         h.set_data(x, labels, vx, vy)
+        return self._fit(h, len(x), vx is not None, batch_size=batch_size, epochs=epochs, verbose=verbose, callbacks=callbacks,
+                         shuffle=shuffle, random_state=random_state)
+
+    def _set_data_dev(self, x, y, batch_size, validation_split, validation_data):
+        """fit's data set-up for DeviceFeatures -> (handle, training rows, whether there is validation data)"""
+        labels = np.argmax(np.asarray(y), axis=1).astype(np.int32)
+        n = len(x)
+        valid, vlo, vhi, vy = None, 0, 0, None
+        if validation_data is not None:
+            vx = validation_data[0]
+            if not isinstance(vx, DeviceFeatures):
+                vx = DeviceFeatures(np.asarray(vx, np.float32), x.device)
+            valid, vhi = vx.handle, len(vx)
+            vy = np.argmax(np.asarray(validation_data[1]), axis=1).astype(np.int32)
+        elif validation_split and 0.0 < validation_split < 1.0:
+            split_at = int(n * (1.0 - validation_split))
+            valid, vlo, vhi, vy = x.handle, split_at, n, labels[split_at:]
+            n, labels = split_at, labels[:split_at]
+        h = self._handle(batch_size)
+        h.set_data_dev(x.handle, 0, n, labels, valid, vlo, vhi, vy)
+        return h, n, vy is not None
+
+    def _fit(self, h, n_train, with_valid, batch_size, epochs, verbose, callbacks, shuffle, random_state):
+        """the epochs of fit over the data the handle holds"""
         rs = np.random.RandomState(random_state)
         cbs = list(callbacks or [])
         for cb in cbs:
             cb.set_model(self)
-            cb.set_params({'epochs': epochs, 'batch_size': batch_size, 'samples': len(x)})
+            cb.set_params({'epochs': epochs, 'batch_size': batch_size, 'samples': n_train})
         history = {}
         self.stop_training = False
         for cb in cbs:
             cb.on_train_begin()
-        steps = -(-len(x) // int(batch_size))
+        steps = -(-n_train // int(batch_size))
         for epoch in range(int(epochs)):
             for cb in cbs:
                 cb.on_epoch_begin(epoch)
-            perm = rs.permutation(len(x)) if shuffle else np.arange(len(x))
+            perm = rs.permutation(n_train) if shuffle else np.arange(n_train)
             logs = h.epoch(perm, self.lr, self.iterations)
             self.iterations += steps
-            if vx is None:
+            if not with_valid:
                 logs = {k: logs[k] for k in ('loss', 'acc')}
             for k, v in logs.items():
                 history.setdefault(k, []).append(v)
@@ -287,6 +318,7 @@ def train_svm(train_data, valid_data, test_data, model_dir, C=1.0, kernel='rbf',
     """classifier/train.py:79-166 -> (model, train_metrics, valid_metrics, test_metrics): SVC(C, kernel, tol, max_iter,
     probability=True, random_state) fitted on the GPU and pickled to model_dir/model.pkl; 'loss' is sklearn's hinge loss of the
     (ovr) decision values; the test set is classified per file as the argmax of the mean of its frames' predict_proba."""
+    train_data, valid_data, test_data = (_on_host(d) for d in (train_data, valid_data, test_data))
     features, labels = train_data['features'], train_data['labels']
     clf = SVC(C=C, probability=True, kernel=kernel, max_iter=max_iterations, tol=tol, random_state=random_state, verbose=verbose)
     LOGGER.debug('Fitting model to data...')
@@ -309,6 +341,13 @@ def train_svm(train_data, valid_data, test_data, model_dir, C=1.0, kernel='rbf',
         per_file = _file_predictions(clf.predict_proba(test_data['features']), test_data['file_idxs'])
         test_metrics = compute_metrics(test_data['labels'], per_file, num_classes=num_classes)
     return clf, train_metrics, valid_metrics, test_metrics
+
+
+def _on_host(data):
+    """the split with its features as a NumPy array (downloaded if preprocess_split_data left them on the device)"""
+    if data and isinstance(data['features'], DeviceFeatures):
+        data = dict(data, features=data['features'].to_host())
+    return data
 
 
 def train_param_search(train_data, valid_data, test_data, model_dir, train_func, search_space, valid_ratio=0.15,
@@ -361,11 +400,13 @@ def _dump(path, obj):
 def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='framewise', train_batch_size=64, patience=20,
           random_state=20171021, parameter_search=False, parameter_search_valid_fold=True, parameter_search_valid_ratio=0.15,
           parameter_search_train_with_valid=False, gsheet_id=None, google_dev_app_name=None, verbose=False, non_overlap=False,
-          non_overlap_chunk_size=10, use_min_max=False, **model_args):
+          non_overlap_chunk_size=10, use_min_max=False, preprocess_device=None, **model_args):
     """classifier/train.py:495-709 for model_type='mlp': one cross-validation fold (fold_num is 1-based) of the features under
     `features_dir` (its path names the dataset after 'features/'), written to
     <output_dir>/classifier/<features desc>/<mode>/<overlap>/<min-max>/mlp/fold<N>/<timestamp>/: config.json,
     min_max_scaler.pkl, stdizer.pkl, model.h5, history_checkpoint.pkl, history_csvlog.csv, results.pkl.
+    preprocess_device: a GPU index preprocesses the folds on that GPU (usc.preprocess_split_data(device=...)) and, without a
+    parameter search, hands them to the MLP there; config.json names it only when it is set.
     -> that directory."""
     if model_type != 'mlp':
         raise ValueError(ONLY_MLP.format(model_type))
@@ -394,6 +435,8 @@ def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='fr
                     feature_mode=feature_mode, train_batch_size=train_batch_size, patience=patience, non_overlap=non_overlap,
                     non_overlap_chunk_size=non_overlap_chunk_size, random_state=random_state, verbose=verbose,
                     git_commit=None, gsheet_id=gsheet_id, google_dev_app_name=google_dev_app_name)
+    if preprocess_device is not None:
+        settings['preprocess_device'] = preprocess_device
     settings.update(model_args)
     with open(os.path.join(model_dir, 'config.json'), 'w') as fh:
         json.dump(settings, fh)
@@ -402,13 +445,15 @@ def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='fr
     LOGGER.info('Fold %d of %s: loading and preprocessing', fold_num, dataset)
     splits = get_split(features_dir, fold_num - 1, dataset, valid=with_valid_fold)
     scalers = preprocess_split_data(*splits, feature_mode=feature_mode, non_overlap=non_overlap,
-                                    non_overlap_chunk_size=int(non_overlap_chunk_size), use_min_max=use_min_max)
+                                    non_overlap_chunk_size=int(non_overlap_chunk_size), use_min_max=use_min_max,
+                                    device=preprocess_device)
     for name, scaler in zip(('min_max_scaler.pkl', 'stdizer.pkl'), scalers):
         _dump(os.path.join(model_dir, name), scaler)
 
     common = dict(batch_size=train_batch_size, patience=patience, random_state=random_state,
                   num_classes=DATASET_NUM_CLASSES[dataset], verbose=verbose)
     if parameter_search:
+        splits = tuple(_on_host(d) for d in splits)          # one download; the search then runs as on the host
         grid = {'learning_rate': [1e-5, 1e-4, 1e-3], 'weight_decay': [1e-5, 1e-4, 1e-3]}
         outcome = train_param_search(*splits, model_dir, train_func=train_mlp, search_space=grid,
                                      valid_ratio=parameter_search_valid_ratio,

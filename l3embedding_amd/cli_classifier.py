@@ -47,6 +47,9 @@ _OPTIONS = [
     ('-nocs', '--non-overlap-chunk-size', 'non_overlap_chunk_size', dict(default=10), 'n of --non-overlap'),
     ('-umm', '--use-min-max', 'use_min_max', dict(action='store_true', default=False),
      'scale features to [0, 1] (fitted on the training rows) before standardising'),
+    # not a flag of 06_train_classifier.py: the folds are preprocessed on this GPU and handed to the MLP there
+    ('-ppd', '--preprocess-device', 'preprocess_device', dict(type=int, default=None),
+     'preprocess the folds on this GPU instead of in NumPy on the host'),
 ]
 _POSITIONALS = [
     ('features_dir', str, 'directory holding fold1 .. foldN of .npz feature files; its path names the dataset after features/'),

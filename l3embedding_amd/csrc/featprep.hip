@@ -1,0 +1,462 @@
+// featprep.hip -- fold preprocessing of the downstream classifier on the GPU (data/usc/features.py:52-150,243-253): the l3_feat
+// handle of the C ABI and its kernels.  Every kernel streams the (n, D) matrix with columns across lanes (consecutive lanes read
+// consecutive floats, four per lane when D % 4 == 0) and rows along the loop; all of them are bound by HBM.
+//
+//   feat_gather        X[rows] -> a new matrix            (remove_data_overlap :60-73, the shuffle :143-148)
+//   feat_colreduce     per chunk of L3_FEAT_CHUNK_ROWS rows: column min / max, float64 sum, float64 sum of (x - mean)^2
+//   feat_combine       the chunks' partial results, in chunk order
+//   feat_affine32      x * scale + shift, two float32 roundings             (MinMaxScaler.transform)
+//   feat_standardize   (x - mean) / scale through float64, two float32 roundings (StandardScaler.transform)
+//   feat_file_stats    compute_stats_features of every file (:243-253)
+//
+// The arithmetic whose roundings are part of the contract is written with the __f*_rn / __d*_rn intrinsics, which the compiler
+// never contracts into a fused multiply-add; the file is also built with -ffp-contract=off (_build.py).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "../../include/l3hip.h"
+#include "featprep.h"
+
+namespace l3 {
+namespace {
+
+constexpr int CHUNK = L3_FEAT_CHUNK_ROWS;
+constexpr int LDS_ROWS = L3_FEAT_STATS_LDS_ROWS;
+constexpr int ELEM_BLOCK = 256;          // threads of an elementwise block
+constexpr int ELEM_VECS = 4096;          // lane-sized pieces one elementwise block handles (whole rows)
+
+// V floats of one lane: one dword, or four when the row length allows it
+template <int V>
+struct Vec;
+template <>
+struct Vec<1> {
+    float v[1];
+    __device__ static Vec load(const float* p) { return Vec{{*p}}; }
+    __device__ void store(float* p) const { *p = v[0]; }
+};
+template <>
+struct Vec<4> {
+    float v[4];
+    __device__ static Vec load(const float* p) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        return Vec{{q.x, q.y, q.z, q.w}};
+    }
+    __device__ void store(float* p) const { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+};
+
+// ---- elementwise: a block owns `rows_per_block` whole rows, a contiguous span of the matrix ---------------------------------------
+// op 0: gather (src row rows[r]); op 1: affine32 (a = scale, b = shift, float32); op 2: standardize (ma = mean, mb = scale, float64)
+template <int V, int OP>
+__global__ __launch_bounds__(ELEM_BLOCK) void feat_elementwise_kernel(const float* x, float* y, int64_t n,
+                                                                     int Dv, int rows_per_block, const int64_t* __restrict__ rows,
+                                                                     const float* __restrict__ a, const float* __restrict__ b,
+                                                                     const double* __restrict__ ma, const double* __restrict__ mb) {
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+    const int nr = (int)min((int64_t)rows_per_block, n - r0);
+    const int span = nr * Dv;
+    const int64_t D = (int64_t)Dv * V;
+    for (int e = threadIdx.x; e < span; e += ELEM_BLOCK) {
+        const int r = e / Dv, cv = e - r * Dv;
+        const int c = cv * V;
+        const int64_t dst = (r0 + r) * D + c;
+        if (OP == 0) {
+            Vec<V>::load(x + rows[r0 + r] * D + c).store(y + dst);
+        } else {
+            Vec<V> q = Vec<V>::load(x + dst);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                if (OP == 1) {
+                    q.v[j] = __fadd_rn(__fmul_rn(q.v[j], a[c + j]), b[c + j]);
+                } else {
+                    const float t = (float)__dsub_rn((double)q.v[j], ma[c + j]);
+                    q.v[j] = (float)__ddiv_rn((double)t, mb[c + j]);
+                }
+            }
+            q.store(y + dst);
+        }
+    }
+}
+
+// ---- column reductions over one chunk of rows: one wave per (chunk, 64 lanes of columns) ------------------------------------------
+// MODE 0: p0 = min, p1 = max (float); MODE 1: d0 = float64 sum in row order; MODE 2: d0 = float64 sum of (fl64(x) - mean)^2
+template <int V, int MODE>
+__global__ __launch_bounds__(64) void feat_colreduce_kernel(const float* __restrict__ x, int64_t n, int64_t D, const double* __restrict__ mean,
+                                                           float* __restrict__ p0, float* __restrict__ p1, double* __restrict__ d0) {
+    const int64_t c = ((int64_t)blockIdx.y * 64 + threadIdx.x) * V;
+    if (c >= D) return;
+    const int64_t r0 = (int64_t)blockIdx.x * CHUNK;
+    const int nr = (int)min((int64_t)CHUNK, n - r0);
+    const float* p = x + r0 * D + c;
+    float lo[V], hi[V];
+    double acc[V], mu[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        lo[j] = INFINITY, hi[j] = -INFINITY, acc[j] = 0.0;
+        mu[j] = MODE == 2 ? mean[c + j] : 0.0;
+    }
+#pragma unroll 8
+    for (int r = 0; r < nr; ++r) {
+        const Vec<V> q = Vec<V>::load(p + (int64_t)r * D);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            if (MODE == 0) {
+                lo[j] = fminf(lo[j], q.v[j]);
+                hi[j] = fmaxf(hi[j], q.v[j]);
+            } else if (MODE == 1) {
+                acc[j] = __dadd_rn(acc[j], (double)q.v[j]);
+            } else {
+                const double d = __dsub_rn((double)q.v[j], mu[j]);
+                acc[j] = __dadd_rn(acc[j], __dmul_rn(d, d));
+            }
+        }
+    }
+    const int64_t o = (int64_t)blockIdx.x * D + c;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        if (MODE == 0)
+            p0[o + j] = lo[j], p1[o + j] = hi[j];
+        else
+            d0[o + j] = acc[j];
+    }
+}
+
+// the chunks' partial results of one column, in chunk order.  MODE 0: min / max; else out = sum / n
+template <int MODE>
+__global__ __launch_bounds__(256) void feat_combine_kernel(int64_t chunks, int64_t D, int64_t n, const float* __restrict__ p0,
+                                                          const float* __restrict__ p1, const double* __restrict__ d0,
+                                                          float* __restrict__ out0, float* __restrict__ out1, double* __restrict__ dout) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= D) return;
+    if (MODE == 0) {
+        float lo = INFINITY, hi = -INFINITY;
+        for (int64_t k = 0; k < chunks; ++k) {
+            lo = fminf(lo, p0[k * D + c]);
+            hi = fmaxf(hi, p1[k * D + c]);
+        }
+        out0[c] = lo, out1[c] = hi;
+    } else {
+        double s = 0.0;
+        for (int64_t k = 0; k < chunks; ++k) s = __dadd_rn(s, d0[k * D + c]);
+        dout[c] = __ddiv_rn(s, (double)n);
+    }
+}
+
+// ---- compute_stats_features: one wave per (file, 64 columns), a lane per column ---------------------------------------------------
+// order-preserving image of a float's bits (NaN out of contract)
+__device__ __forceinline__ uint32_t ordered_bits(float v) {
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float from_ordered_bits(uint32_t u) {
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+__global__ __launch_bounds__(64) void feat_file_stats_kernel(const float* __restrict__ x, int64_t D, const int64_t* __restrict__ files,
+                                                            float* __restrict__ out) {
+    __shared__ float slab[LDS_ROWS * 64];
+    const int lane = threadIdx.x;
+    const int64_t c = (int64_t)blockIdx.y * 64 + lane;
+    if (c >= D) return;          // a lane touches its own LDS column only: no barrier anywhere in this kernel
+    const int64_t s = files[2 * blockIdx.x], e = files[2 * blockIdx.x + 1];
+    const int F = (int)(e - s);
+    const bool in_lds = F <= LDS_ROWS;          // the same for the whole block
+    const float* col = x + s * D + c;
+    auto at = [&](int r) { return in_lds ? slab[r * 64 + lane] : col[(int64_t)r * D]; };
+
+    // pass 1, in row order: extrema, the float32 and float64 sums; the file goes to LDS if it fits
+    float lo = INFINITY, hi = -INFINITY, sum32 = 0.f;
+    double sum64 = 0.0;
+#pragma unroll 4
+    for (int r = 0; r < F; ++r) {
+        const float v = col[(int64_t)r * D];
+        if (in_lds) slab[r * 64 + lane] = v;
+        lo = fminf(lo, v), hi = fmaxf(hi, v);
+        sum32 = __fadd_rn(sum32, v);
+        sum64 = __dadd_rn(sum64, (double)v);
+    }
+    const float fF = (float)F;
+    const float mean32 = __fdiv_rn(sum32, fF);
+    const double mean64 = __ddiv_rn(sum64, (double)F);
+
+    // pass 2, in row order: the float32 variance and the float64 central moments
+    float v32 = 0.f;
+    double s2 = 0.0, s3 = 0.0, s4 = 0.0;
+    for (int r = 0; r < F; ++r) {
+        const float v = at(r);
+        const float t = __fsub_rn(v, mean32);
+        v32 = __fadd_rn(v32, __fmul_rn(t, t));
+        const double d = __dsub_rn((double)v, mean64);
+        const double d2 = __dmul_rn(d, d);
+        s2 = __dadd_rn(s2, d2);
+        s3 = __dadd_rn(s3, __dmul_rn(d2, d));
+        s4 = __dadd_rn(s4, __dmul_rn(d2, d2));
+    }
+    const float var32 = __fdiv_rn(v32, fF);
+    const double m2 = __ddiv_rn(s2, (double)F), m3 = __ddiv_rn(s3, (double)F), m4 = __ddiv_rn(s4, (double)F);
+    const double thr = __dmul_rn(1e-15, mean64);          // np.finfo(np.float64).resolution * mean
+    const bool zero = m2 <= __dmul_rn(thr, thr);
+    const float skew = zero ? 0.f : (float)__ddiv_rn(m3, __dmul_rn(m2, __dsqrt_rn(m2)));
+    const float kurt = zero ? -3.f : (float)__dsub_rn(__ddiv_rn(m4, __dmul_rn(m2, m2)), 3.0);
+
+    // median: the element of rank k = (F - 1) / 2 by a bitwise radix select (32 counting passes), then for even F the next one up
+    const int k = (F - 1) >> 1;
+    uint32_t prefix = 0, mask = 0;
+    int rank = k;
+    for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t b = 1u << bit;
+        int zeros = 0;
+        for (int r = 0; r < F; ++r) {
+            const uint32_t u = ordered_bits(at(r));
+            zeros += ((u & mask) == prefix && !(u & b)) ? 1 : 0;
+        }
+        if (rank >= zeros) rank -= zeros, prefix |= b;
+        mask |= b;
+    }
+    float median = from_ordered_bits(prefix);
+    if (!(F & 1)) {
+        // rank k + 1: the same value if it occurs more than once past rank k, else the smallest value above it
+        int not_above = 0;
+        uint32_t next = 0xffffffffu;
+        for (int r = 0; r < F; ++r) {
+            const uint32_t u = ordered_bits(at(r));
+            if (u <= prefix)
+                ++not_above;
+            else
+                next = min(next, u);
+        }
+        const float upper = not_above >= k + 2 ? median : from_ordered_bits(next);
+        median = __fdiv_rn(__fadd_rn(median, upper), 2.f);
+    }
+
+    float* o = out + (int64_t)blockIdx.x * 7 * D + c;
+    o[0] = lo, o[D] = hi, o[2 * D] = median, o[3 * D] = mean32, o[4 * D] = var32, o[5 * D] = skew, o[6 * D] = kurt;
+}
+
+// ---- launchers ------------------------------------------------------------------------------------------------------------------
+bool vec4(const l3_feat* f) { return f->D % 4 == 0; }          // hipMalloc'ed base, rows of a multiple of 16 bytes
+
+template <int OP>
+void launch_elementwise(const l3_feat* f, const float* x, float* y, int64_t n_rows, const int64_t* rows, const float* a, const float* b,
+                        const double* ma, const double* mb) {
+    const int V = vec4(f) ? 4 : 1;
+    const int Dv = (int)(f->D / V);
+    const int rpb = std::max(1, ELEM_VECS / Dv);
+    const dim3 grid((unsigned)((n_rows + rpb - 1) / rpb));
+    if (V == 4)
+        hipLaunchKernelGGL((feat_elementwise_kernel<4, OP>), grid, dim3(ELEM_BLOCK), 0, f->s, x, y, n_rows, Dv, rpb, rows, a, b, ma, mb);
+    else
+        hipLaunchKernelGGL((feat_elementwise_kernel<1, OP>), grid, dim3(ELEM_BLOCK), 0, f->s, x, y, n_rows, Dv, rpb, rows, a, b, ma, mb);
+}
+
+int64_t chunks_of(const l3_feat* f) { return (f->n + CHUNK - 1) / CHUNK; }
+
+template <int MODE>
+void launch_colreduce(const l3_feat* f, const double* mean, float* p0, float* p1, double* d0) {
+    const int V = vec4(f) ? 4 : 1;
+    const dim3 grid((unsigned)chunks_of(f), (unsigned)((f->D / V + 63) / 64));
+    if (V == 4)
+        hipLaunchKernelGGL((feat_colreduce_kernel<4, MODE>), grid, dim3(64), 0, f->s, f->x, f->n, f->D, mean, p0, p1, d0);
+    else
+        hipLaunchKernelGGL((feat_colreduce_kernel<1, MODE>), grid, dim3(64), 0, f->s, f->x, f->n, f->D, mean, p0, p1, d0);
+}
+
+template <int MODE>
+void launch_combine(const l3_feat* f, const float* p0, const float* p1, const double* d0, float* out0, float* out1, double* dout) {
+    hipLaunchKernelGGL((feat_combine_kernel<MODE>), dim3((unsigned)((f->D + 255) / 256)), dim3(256), 0, f->s, chunks_of(f), f->D, f->n, p0,
+                       p1, d0, out0, out1, dout);
+}
+
+// the stream has finished and no launch failed
+bool finished(l3_feat* f) { return hipStreamSynchronize(f->s) == hipSuccess && hipGetLastError() == hipSuccess; }
+
+// the handle's matrix becomes `y` of n rows of D floats
+void adopt(l3_feat* f, float* y, int64_t n, int64_t D) {
+    f->bufs.release(f->x);
+    f->x = y, f->n = n, f->D = D;
+}
+
+int enter(l3_feat* f, bool args_ok, const char* fn) {
+    if (!f || !args_ok) return fail(L3_EINVAL, std::string(fn) + ": NULL argument");
+    if (hipSetDevice(f->device) != hipSuccess) return fail(L3_EHIP, no_gpu_message(fn, f->device));
+    return L3_OK;
+}
+
+}  // namespace
+}  // namespace l3
+
+using namespace l3;
+
+extern "C" {
+
+int l3_feat_create(int device, const float* X, int64_t n, int64_t D, l3_feat** out) {
+    if (!out) return fail(L3_EINVAL, "l3_feat_create: out is NULL");
+    *out = nullptr;
+    if (!X || n < 1 || n > INT32_MAX || D < 1 || D > (1 << 21))
+        return fail(L3_EINVAL, "l3_feat_create: need X, 1 <= n <= 2^31 - 1 rows and 1 <= D <= 2^21 columns");
+    if (!device_ok(device)) return fail(L3_EHIP, no_gpu_message("l3_feat_create", device));
+    l3_feat* f = new l3_feat();
+    f->device = device, f->n = n, f->D = D;
+    f->x = f->bufs.alloc<float>((size_t)(n * D));
+    if (!f->x || hipStreamCreateWithFlags(&f->s, hipStreamNonBlocking) != hipSuccess) {
+        l3_feat_destroy(f);
+        return fail(L3_ENOMEM, "l3_feat_create: device allocation of " + std::to_string(n * D * 4) + " bytes failed");
+    }
+    if (hipMemcpyAsync(f->x, X, (size_t)(n * D) * sizeof(float), hipMemcpyHostToDevice, f->s) != hipSuccess || !finished(f)) {
+        l3_feat_destroy(f);
+        return fail(L3_EHIP, "l3_feat_create: copy to the device failed");
+    }
+    *out = f;
+    return L3_OK;
+}
+
+void l3_feat_destroy(l3_feat* f) {
+    if (!f) return;
+    (void)hipSetDevice(f->device);
+    if (f->s) (void)hipStreamSynchronize(f->s);
+    if (f->s) (void)hipStreamDestroy(f->s);
+    delete f;
+}
+
+int l3_feat_shape(const l3_feat* f, int64_t* n, int64_t* D) {
+    if (!f || !n || !D) return fail(L3_EINVAL, "l3_feat_shape: NULL argument");
+    *n = f->n, *D = f->D;
+    return L3_OK;
+}
+
+int l3_feat_download(l3_feat* f, int64_t lo, int64_t hi, float* dst) {
+    const int rc = enter(f, dst != nullptr, "l3_feat_download");
+    if (rc != L3_OK) return rc;
+    if (lo < 0 || hi < lo || hi > f->n) return fail(L3_EINVAL, "l3_feat_download: rows [lo, hi) outside the matrix");
+    if (hi == lo) return L3_OK;
+    if (hipMemcpyAsync(dst, f->x + lo * f->D, (size_t)((hi - lo) * f->D) * sizeof(float), hipMemcpyDeviceToHost, f->s) != hipSuccess ||
+        !finished(f))
+        return fail(L3_EHIP, "l3_feat_download: copy from the device failed");
+    return L3_OK;
+}
+
+int l3_feat_gather(l3_feat* f, const int64_t* rows, int64_t n_out) {
+    const int rc = enter(f, rows != nullptr, "l3_feat_gather");
+    if (rc != L3_OK) return rc;
+    if (n_out < 1 || n_out > INT32_MAX) return fail(L3_EINVAL, "l3_feat_gather: need 1 <= n_out <= 2^31 - 1 rows");
+    for (int64_t i = 0; i < n_out; ++i)
+        if (rows[i] < 0 || rows[i] >= f->n)
+            return fail(L3_EINVAL, "l3_feat_gather: rows[" + std::to_string(i) + "] = " + std::to_string(rows[i]) + " outside [0, " +
+                                       std::to_string(f->n) + ")");
+    float* y = f->bufs.alloc<float>((size_t)(n_out * f->D));
+    int64_t* drows = f->bufs.put(rows, (size_t)n_out, f->s);
+    if (!y || !drows) {
+        f->bufs.release(y), f->bufs.release(drows);
+        return fail(L3_ENOMEM, "l3_feat_gather: device allocation failed");
+    }
+    launch_elementwise<0>(f, f->x, y, n_out, drows, nullptr, nullptr, nullptr, nullptr);
+    const bool ok = finished(f);
+    f->bufs.release(drows);
+    if (!ok) {
+        f->bufs.release(y);
+        return fail(L3_EHIP, "l3_feat_gather: HIP error");
+    }
+    adopt(f, y, n_out, f->D);
+    return L3_OK;
+}
+
+int l3_feat_minmax(l3_feat* f, float* min_out, float* max_out) {
+    const int rc = enter(f, min_out && max_out, "l3_feat_minmax");
+    if (rc != L3_OK) return rc;
+    const size_t part = (size_t)(chunks_of(f) * f->D);
+    float *p0 = f->bufs.alloc<float>(part), *p1 = f->bufs.alloc<float>(part), *o = f->bufs.alloc<float>((size_t)(2 * f->D));
+    int out = L3_OK;
+    if (!p0 || !p1 || !o) {
+        out = fail(L3_ENOMEM, "l3_feat_minmax: device allocation failed");
+    } else {
+        launch_colreduce<0>(f, nullptr, p0, p1, nullptr);
+        launch_combine<0>(f, p0, p1, nullptr, o, o + f->D, nullptr);
+        if (hipMemcpyAsync(min_out, o, f->D * sizeof(float), hipMemcpyDeviceToHost, f->s) != hipSuccess ||
+            hipMemcpyAsync(max_out, o + f->D, f->D * sizeof(float), hipMemcpyDeviceToHost, f->s) != hipSuccess || !finished(f))
+            out = fail(L3_EHIP, "l3_feat_minmax: HIP error");
+    }
+    f->bufs.release(p0), f->bufs.release(p1), f->bufs.release(o);
+    return out;
+}
+
+int l3_feat_affine32(l3_feat* f, const float* scale, const float* shift) {
+    const int rc = enter(f, scale && shift, "l3_feat_affine32");
+    if (rc != L3_OK) return rc;
+    float *a = f->bufs.put(scale, (size_t)f->D, f->s), *b = f->bufs.put(shift, (size_t)f->D, f->s);
+    int out = L3_OK;
+    if (!a || !b) {
+        out = fail(L3_ENOMEM, "l3_feat_affine32: device allocation failed");
+    } else {
+        launch_elementwise<1>(f, f->x, f->x, f->n, nullptr, a, b, nullptr, nullptr);
+        if (!finished(f)) out = fail(L3_EHIP, "l3_feat_affine32: HIP error");
+    }
+    f->bufs.release(a), f->bufs.release(b);
+    return out;
+}
+
+int l3_feat_moments(l3_feat* f, double* mean_out, double* var_out) {
+    const int rc = enter(f, mean_out && var_out, "l3_feat_moments");
+    if (rc != L3_OK) return rc;
+    double *part = f->bufs.alloc<double>((size_t)(chunks_of(f) * f->D)), *o = f->bufs.alloc<double>((size_t)(2 * f->D));
+    int out = L3_OK;
+    if (!part || !o) {
+        out = fail(L3_ENOMEM, "l3_feat_moments: device allocation failed");
+    } else {
+        launch_colreduce<1>(f, nullptr, nullptr, nullptr, part);
+        launch_combine<1>(f, nullptr, nullptr, part, nullptr, nullptr, o);
+        launch_colreduce<2>(f, o, nullptr, nullptr, part);
+        launch_combine<2>(f, nullptr, nullptr, part, nullptr, nullptr, o + f->D);
+        if (hipMemcpyAsync(mean_out, o, f->D * sizeof(double), hipMemcpyDeviceToHost, f->s) != hipSuccess ||
+            hipMemcpyAsync(var_out, o + f->D, f->D * sizeof(double), hipMemcpyDeviceToHost, f->s) != hipSuccess || !finished(f))
+            out = fail(L3_EHIP, "l3_feat_moments: HIP error");
+    }
+    f->bufs.release(part), f->bufs.release(o);
+    return out;
+}
+
+int l3_feat_standardize(l3_feat* f, const double* mean, const double* scale) {
+    const int rc = enter(f, mean && scale, "l3_feat_standardize");
+    if (rc != L3_OK) return rc;
+    double *a = f->bufs.put(mean, (size_t)f->D, f->s), *b = f->bufs.put(scale, (size_t)f->D, f->s);
+    int out = L3_OK;
+    if (!a || !b) {
+        out = fail(L3_ENOMEM, "l3_feat_standardize: device allocation failed");
+    } else {
+        launch_elementwise<2>(f, f->x, f->x, f->n, nullptr, nullptr, nullptr, a, b);
+        if (!finished(f)) out = fail(L3_EHIP, "l3_feat_standardize: HIP error");
+    }
+    f->bufs.release(a), f->bufs.release(b);
+    return out;
+}
+
+int l3_feat_file_stats(l3_feat* f, const int64_t* file_idxs, int64_t n_files) {
+    const int rc = enter(f, file_idxs != nullptr, "l3_feat_file_stats");
+    if (rc != L3_OK) return rc;
+    if (n_files < 1 || n_files > INT32_MAX) return fail(L3_EINVAL, "l3_feat_file_stats: need 1 <= n_files <= 2^31 - 1");
+    if (7 * f->D > (1 << 21)) return fail(L3_EINVAL, "l3_feat_file_stats: 7 D exceeds the 2^21 columns of a matrix");
+    for (int64_t i = 0; i < n_files; ++i) {
+        const int64_t s = file_idxs[2 * i], e = file_idxs[2 * i + 1];
+        if (s < 0 || e <= s || e > f->n)
+            return fail(L3_EINVAL, "l3_feat_file_stats: file " + std::to_string(i) + " = [" + std::to_string(s) + ", " +
+                                       std::to_string(e) + ") is empty or outside [0, " + std::to_string(f->n) + ")");
+    }
+    float* y = f->bufs.alloc<float>((size_t)(n_files * 7 * f->D));
+    int64_t* files = f->bufs.put(file_idxs, (size_t)(2 * n_files), f->s);
+    if (!y || !files) {
+        f->bufs.release(y), f->bufs.release(files);
+        return fail(L3_ENOMEM, "l3_feat_file_stats: device allocation failed");
+    }
+    hipLaunchKernelGGL(feat_file_stats_kernel, dim3((unsigned)n_files, (unsigned)((f->D + 63) / 64)), dim3(64), 0, f->s, f->x, f->D, files,
+                       y);
+    const bool ok = finished(f);
+    f->bufs.release(files);
+    if (!ok) {
+        f->bufs.release(y);
+        return fail(L3_EHIP, "l3_feat_file_stats: HIP error");
+    }
+    adopt(f, y, n_files, 7 * f->D);
+    return L3_OK;
+}
+
+}  // extern "C"

@@ -17,6 +17,7 @@
 
 #include "../../include/l3hip.h"
 #include "device_common.h"
+#include "featprep.h"
 #include "kernels.h"
 #include "mlp.h"
 
@@ -431,6 +432,46 @@ int l2_term(l3_mlp* m, double* out) {
     *out = (double)(m->wd * ((sq[0] + sq[1]) + sq[2]));
     return L3_OK;
 }
+
+// l3_mlp_set_data / l3_mlp_set_data_dev: the features come from host memory or from another buffer of this device (`kind`)
+int set_data(l3_mlp* m, const char* fn, const float* X_train, const int32_t* y_train, int64_t n_train, const float* X_valid,
+             const int32_t* y_valid, int64_t n_valid, hipMemcpyKind kind) {
+    const std::string name(fn);
+    if (!m) return fail(L3_EINVAL, name + ": NULL handle");
+    if (n_train <= 0 || !X_train || !y_train) return fail(L3_EINVAL, name + ": need n_train > 0 rows and their labels");
+    if (n_valid < 0 || (n_valid > 0 && (!X_valid || !y_valid))) return fail(L3_EINVAL, name + ": bad validation set");
+    if (n_train > INT32_MAX || n_valid > INT32_MAX) return fail(L3_EINVAL, name + ": more than 2^31 - 1 rows");
+    const int64_t bytes = (n_train + n_valid) * (int64_t)m->D * 4;
+    if ((n_train + n_valid) > MLP_MAX_DATA_BYTES / ((int64_t)m->D * 4))
+        return fail(L3_ENOMEM, name + ": " + std::to_string(bytes) + " bytes of features exceed the 64 GiB cap");
+    for (int64_t i = 0; i < n_train; ++i)
+        if (y_train[i] < 0 || y_train[i] >= m->C)
+            return fail(L3_EINVAL, name + ": y_train[" + std::to_string(i) + "] = " + std::to_string(y_train[i]) +
+                                       " outside [0, " + std::to_string(m->C) + ")");
+    for (int64_t i = 0; i < n_valid; ++i)
+        if (y_valid[i] < 0 || y_valid[i] >= m->C)
+            return fail(L3_EINVAL, name + ": y_valid[" + std::to_string(i) + "] = " + std::to_string(y_valid[i]) +
+                                       " outside [0, " + std::to_string(m->C) + ")");
+    (void)hipSetDevice(m->device);
+    (void)hipStreamSynchronize(m->s);
+    for (void* q : {(void*)m->xtr, (void*)m->xva, (void*)m->ytr, (void*)m->yva, (void*)m->perm}) m->bufs.release(q);
+    m->xtr = m->xva = nullptr, m->ytr = m->yva = m->perm = nullptr, m->ntr = m->nva = 0;
+    const size_t nva = (size_t)std::max<int64_t>(1, n_valid);
+    m->xtr = m->bufs.alloc<float>((size_t)(n_train * m->D)), m->ytr = m->bufs.alloc<int>((size_t)n_train);
+    m->perm = m->bufs.alloc<int>((size_t)n_train);
+    m->xva = m->bufs.alloc<float>(nva * m->D), m->yva = m->bufs.alloc<int>(nva);
+    if (!m->xtr || !m->ytr || !m->perm || !m->xva || !m->yva)
+        return fail(L3_ENOMEM, name + ": device allocation of " + std::to_string(bytes) + " bytes failed");
+    if (hipMemcpyAsync(m->xtr, X_train, n_train * m->D * sizeof(float), kind, m->s) != hipSuccess ||
+        hipMemcpyAsync(m->ytr, y_train, n_train * sizeof(int32_t), hipMemcpyHostToDevice, m->s) != hipSuccess ||
+        (n_valid > 0 &&
+         (hipMemcpyAsync(m->xva, X_valid, n_valid * m->D * sizeof(float), kind, m->s) != hipSuccess ||
+          hipMemcpyAsync(m->yva, y_valid, n_valid * sizeof(int32_t), hipMemcpyHostToDevice, m->s) != hipSuccess)) ||
+        hipStreamSynchronize(m->s) != hipSuccess)
+        return fail(L3_EHIP, name + ": copy to the device failed");
+    m->ntr = n_train, m->nva = n_valid;
+    return L3_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -516,40 +557,21 @@ int64_t l3_mlp_param_count(const l3_mlp* m) {
 
 int l3_mlp_set_data(l3_mlp* m, const float* X_train, const int32_t* y_train, int64_t n_train, const float* X_valid,
                     const int32_t* y_valid, int64_t n_valid) {
-    if (!m) return fail(L3_EINVAL, "l3_mlp_set_data: NULL handle");
-    if (n_train <= 0 || !X_train || !y_train) return fail(L3_EINVAL, "l3_mlp_set_data: need n_train > 0 rows and their labels");
-    if (n_valid < 0 || (n_valid > 0 && (!X_valid || !y_valid))) return fail(L3_EINVAL, "l3_mlp_set_data: bad validation set");
-    if (n_train > INT32_MAX || n_valid > INT32_MAX) return fail(L3_EINVAL, "l3_mlp_set_data: more than 2^31 - 1 rows");
-    const int64_t bytes = (n_train + n_valid) * (int64_t)m->D * 4;
-    if ((n_train + n_valid) > MLP_MAX_DATA_BYTES / ((int64_t)m->D * 4))
-        return fail(L3_ENOMEM, "l3_mlp_set_data: " + std::to_string(bytes) + " bytes of features exceed the 64 GiB cap");
-    for (int64_t i = 0; i < n_train; ++i)
-        if (y_train[i] < 0 || y_train[i] >= m->C)
-            return fail(L3_EINVAL, "l3_mlp_set_data: y_train[" + std::to_string(i) + "] = " + std::to_string(y_train[i]) +
-                                       " outside [0, " + std::to_string(m->C) + ")");
-    for (int64_t i = 0; i < n_valid; ++i)
-        if (y_valid[i] < 0 || y_valid[i] >= m->C)
-            return fail(L3_EINVAL, "l3_mlp_set_data: y_valid[" + std::to_string(i) + "] = " + std::to_string(y_valid[i]) +
-                                       " outside [0, " + std::to_string(m->C) + ")");
-    (void)hipSetDevice(m->device);
-    (void)hipStreamSynchronize(m->s);
-    for (void* q : {(void*)m->xtr, (void*)m->xva, (void*)m->ytr, (void*)m->yva, (void*)m->perm}) m->bufs.release(q);
-    m->xtr = m->xva = nullptr, m->ytr = m->yva = m->perm = nullptr, m->ntr = m->nva = 0;
-    const size_t nva = (size_t)std::max<int64_t>(1, n_valid);
-    m->xtr = m->bufs.alloc<float>((size_t)(n_train * m->D)), m->ytr = m->bufs.alloc<int>((size_t)n_train);
-    m->perm = m->bufs.alloc<int>((size_t)n_train);
-    m->xva = m->bufs.alloc<float>(nva * m->D), m->yva = m->bufs.alloc<int>(nva);
-    if (!m->xtr || !m->ytr || !m->perm || !m->xva || !m->yva)
-        return fail(L3_ENOMEM, "l3_mlp_set_data: device allocation of " + std::to_string(bytes) + " bytes failed");
-    if (hipMemcpyAsync(m->xtr, X_train, n_train * m->D * sizeof(float), hipMemcpyHostToDevice, m->s) != hipSuccess ||
-        hipMemcpyAsync(m->ytr, y_train, n_train * sizeof(int32_t), hipMemcpyHostToDevice, m->s) != hipSuccess ||
-        (n_valid > 0 &&
-         (hipMemcpyAsync(m->xva, X_valid, n_valid * m->D * sizeof(float), hipMemcpyHostToDevice, m->s) != hipSuccess ||
-          hipMemcpyAsync(m->yva, y_valid, n_valid * sizeof(int32_t), hipMemcpyHostToDevice, m->s) != hipSuccess)) ||
-        hipStreamSynchronize(m->s) != hipSuccess)
-        return fail(L3_EHIP, "l3_mlp_set_data: copy to the device failed");
-    m->ntr = n_train, m->nva = n_valid;
-    return L3_OK;
+    return set_data(m, "l3_mlp_set_data", X_train, y_train, n_train, X_valid, y_valid, n_valid, hipMemcpyHostToDevice);
+}
+
+int l3_mlp_set_data_dev(l3_mlp* m, const l3_feat* train, int64_t lo, int64_t hi, const int32_t* y, const l3_feat* valid, int64_t vlo,
+                        int64_t vhi, const int32_t* yv) {
+    if (!m || !train) return fail(L3_EINVAL, "l3_mlp_set_data_dev: NULL handle");
+    if (vhi == vlo) valid = nullptr;
+    for (const l3_feat* f : {train, valid})
+        if (f && (f->device != m->device || f->D != m->D))
+            return fail(L3_EINVAL, "l3_mlp_set_data_dev: the feature matrix is on another device or not " + std::to_string(m->D) +
+                                       " columns wide");
+    if (lo < 0 || hi < lo || hi > train->n || (valid && (vlo < 0 || vhi < vlo || vhi > valid->n)))
+        return fail(L3_EINVAL, "l3_mlp_set_data_dev: a row range lies outside its matrix");
+    return set_data(m, "l3_mlp_set_data_dev", train->x + lo * m->D, y, hi - lo, valid ? valid->x + vlo * m->D : nullptr, yv,
+                    valid ? vhi - vlo : 0, hipMemcpyDeviceToDevice);
 }
 
 int l3_mlp_epoch(l3_mlp* m, const int32_t* perm, float lr, int64_t t0, double* stats_out) {
@@ -615,6 +637,24 @@ int l3_mlp_predict(l3_mlp* m, const float* X, int64_t n, float* probs_out) {
         if (hipMemcpyAsync(m->xin, X + r0 * m->D, rows * m->D * sizeof(float), hipMemcpyHostToDevice, m->s) != hipSuccess)
             return fail(L3_EHIP, "l3_mlp_predict: copy to the device failed");
         const int rc = evaluate(m, m->xin, nullptr, rows, &sc, &sk, probs_out + r0 * m->C);
+        if (rc != L3_OK) return rc;
+    }
+    return L3_OK;
+}
+
+int l3_mlp_predict_dev(l3_mlp* m, const l3_feat* x, int64_t lo, int64_t hi, float* probs_out) {
+    if (!m || !x || !probs_out || hi <= lo) return fail(L3_EINVAL, "l3_mlp_predict_dev: NULL argument or no rows");
+    if (x->device != m->device || x->D != m->D)
+        return fail(L3_EINVAL, "l3_mlp_predict_dev: the feature matrix is on another device or not " + std::to_string(m->D) +
+                                   " columns wide");
+    if (lo < 0 || hi > x->n) return fail(L3_EINVAL, "l3_mlp_predict_dev: rows [lo, hi) outside the matrix");
+    (void)hipSetDevice(m->device);
+    const int64_t n = hi - lo;
+    // l3_mlp_predict's row blocks, so that every forward launch has its shape (and its split-K order)
+    for (int64_t r0 = 0; r0 < n; r0 += m->xin_rows) {
+        const int64_t rows = std::min(m->xin_rows, n - r0);
+        double sc, sk;
+        const int rc = evaluate(m, x->x + (lo + r0) * m->D, nullptr, rows, &sc, &sk, probs_out + r0 * m->C);
         if (rc != L3_OK) return rc;
     }
     return L3_OK;

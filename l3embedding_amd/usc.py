@@ -8,10 +8,15 @@ Quirks kept on purpose:
   * the summary statistics are min, max, median, mean, var, skew, excess kurtosis (scipy.stats defaults, bias=True);
   * the scalers use sklearn's arithmetic: population variance, and a zero variance / zero range scales by 1;
   * the training rows are shuffled (np.random.permutation, the global NumPy state) after standardisation.
+
+preprocess_split_data(..., device=<index>) runs the passes over the (n, D) matrices on the GPU (csrc/featprep.hip):
+the splits' 'features' become DeviceFeatures, which classifier.MLPModel takes without a trip through the host.
 """
 import os
 
 import numpy as np
+
+from . import _lib
 
 DATASET_NUM_FOLDS = {'us8k': 10, 'esc50': 5, 'dcase2013': 2}
 
@@ -102,10 +107,13 @@ class StandardScaler(object):
 
     def fit(self, X):
         X = np.asarray(X)
-        self.mean_ = X.mean(axis=0, dtype=np.float64)
-        self.var_ = X.var(axis=0, dtype=np.float64)
+        return self._fitted(X.mean(axis=0, dtype=np.float64), X.var(axis=0, dtype=np.float64), X.shape[0])
+
+    def _fitted(self, mean, var, n):
+        self.mean_ = mean
+        self.var_ = var
         self.scale_ = _handle_zeros(np.sqrt(self.var_))
-        self.n_samples_seen_ = X.shape[0]
+        self.n_samples_seen_ = n
         return self
 
     def transform(self, X):
@@ -126,8 +134,11 @@ class MinMaxScaler(object):
 
     def fit(self, X):
         X = np.asarray(X)
-        self.data_min_ = np.min(X, axis=0)
-        self.data_max_ = np.max(X, axis=0)
+        return self._fitted(np.min(X, axis=0), np.max(X, axis=0))
+
+    def _fitted(self, data_min, data_max):
+        self.data_min_ = data_min
+        self.data_max_ = data_max
         self.data_range_ = self.data_max_ - self.data_min_
         lo, hi = self.feature_range
         self.scale_ = (hi - lo) / _handle_zeros(self.data_range_)
@@ -194,15 +205,104 @@ def _present(*splits):
     return [d for d in splits if d]
 
 
+def _require_float32(X):
+    if X.dtype != np.float32:
+        raise ValueError('the device path preprocesses float32 features; these are {} (there is no silent conversion: cast '
+                         'them, or preprocess on the host with device=None)'.format(X.dtype))
+
+
+class DeviceFeatures(object):
+    """A split's feature matrix on the GPU (an l3_feat handle, _lib.Features): what preprocess_split_data(device=...) leaves in
+    data['features'].  It holds no host copy; to_host() / rows() download."""
+
+    def __init__(self, X, device=0):
+        X = np.asarray(X)
+        _require_float32(X)
+        self.device = int(device)
+        self.handle = _lib.Features(X if X.ndim == 2 else X.reshape(len(X), -1), device=self.device)
+
+    @property
+    def shape(self):
+        return self.handle.shape
+
+    def __len__(self):
+        return self.shape[0]
+
+    def rows(self, lo, hi):
+        """rows [lo, hi) as a NumPy array"""
+        return self.handle.download(lo, hi)
+
+    def to_host(self):
+        return self.handle.download()
+
+    def close(self):
+        self.handle.close()
+
+
+def non_overlap_rows(file_idxs, chunk_size=10):
+    """remove_data_overlap as an index table: the rows it keeps, in order, and the renumbered file_idxs"""
+    kept = [np.arange(s, e, chunk_size, dtype=np.int64) for s, e in file_idxs]
+    return np.concatenate(kept), _row_ranges([len(k) for k in kept])
+
+
+def _preprocess_on_device(train_data, valid_data, test_data, feature_mode, non_overlap, chunk_size, use_min_max, device):
+    """preprocess_split_data's stages in its order with the (n, D) passes on the GPU; labels, file_idxs, the D-sized scaler
+    arithmetic and the draw of the permutation stay on the host, in the host path's own expressions"""
+    everything = _present(train_data, valid_data, test_data)
+    for d in everything:          # before anything is uploaded or replaced
+        _require_float32(np.asarray(d['features']))
+    for d in everything:
+        d['features'] = DeviceFeatures(d['features'], device)
+    feats = [d['features'].handle for d in everything]
+    if non_overlap:
+        for d, f in zip(everything, feats):
+            rows, d['file_idxs'] = non_overlap_rows(d['file_idxs'], chunk_size)
+            f.gather(rows)
+
+    unit_range = MinMaxScaler()
+    if use_min_max:
+        unit_range._fitted(*train_data['features'].handle.minmax())
+        for f in feats:
+            f.affine32(unit_range.scale_, unit_range.min_)
+
+    if feature_mode == 'stats':
+        for d, f in zip(everything, feats):
+            f.file_stats(d['file_idxs'])
+            d['file_idxs'] = _row_ranges(np.ones(len(d['file_idxs']), dtype=np.int64))
+    else:
+        for d in _present(train_data, valid_data):
+            expand_framewise_labels(d)
+
+    mean, var = train_data['features'].handle.moments()
+    stdizer = StandardScaler()._fitted(mean, var, len(train_data['features']))
+    for f in feats:
+        f.standardize(stdizer.mean_, stdizer.scale_)
+
+    order = np.random.permutation(len(train_data['labels']))
+    new_position = np.empty_like(order)
+    new_position[order] = np.arange(order.size)
+    train_data['features'].handle.gather(order)
+    train_data['labels'] = train_data['labels'][order]
+    train_data['file_idxs'] = [new_position[s:e] for s, e in train_data['file_idxs']]
+    return unit_range, stdizer
+
+
 def preprocess_split_data(train_data, valid_data, test_data, feature_mode='framewise', non_overlap=False,
-                          non_overlap_chunk_size=10, use_min_max=False):
+                          non_overlap_chunk_size=10, use_min_max=False, device=None):
     """data/usc/features.py:97-150, in place on the splits (valid_data may be None) -> (min-max scaler, standardiser).
 
     Order: thin overlapping frames; min-max scaling (fitted on train, when asked); per-frame labels or per-file statistics;
     standardisation fitted on train; then one np.random.permutation of the training rows (the global NumPy state), after which
-    train_data['file_idxs'] is a list holding, per file, the new positions of its rows."""
+    train_data['file_idxs'] is a list holding, per file, the new positions of its rows.
+
+    device: None runs everything in NumPy on the host.  A GPU index runs the same stages with the passes over the feature
+    matrices on that GPU (float32 features only): every split's 'features' is then a DeviceFeatures, min-max scaled values are
+    the host path's bits, and the standardiser's mean_ / var_ agree with the host's to the rounding of a float64 sum."""
     if feature_mode not in ('framewise', 'stats'):
         raise ValueError("feature_mode must be 'framewise' or 'stats', not {!r}".format(feature_mode))
+    if device is not None:
+        return _preprocess_on_device(train_data, valid_data, test_data, feature_mode, non_overlap, non_overlap_chunk_size,
+                                     use_min_max, device)
     everything = _present(train_data, valid_data, test_data)
     if non_overlap:
         for d in everything:
