@@ -518,6 +518,42 @@ int l3_op_svm_kernel_rows(int device, const l3_svm_kernel *k, const float *x, in
  * at a gap below max(eps, local_rel x the first gap), when no pair can move, or after max_updates (<= 0: no cap) updates. */
 int l3_op_svm_smo(int device, const float *K, const int8_t *y, int q, double C, double eps, double local_rel, int64_t max_updates,
                   double *alpha, const double *grad, int64_t *updates_out);
+/* Scoring a fitted model on the device (csrc/svm_eval.hip): what train_svm reports after the fit (classifier/train.py:134-166:
+ * clf.predict, clf.decision_function -> hinge_loss, clf.predict_proba -> the per-file argmax of the mean) without the pair decisions
+ * leaving the device.  All of it float64, rounded operation by operation, deterministic.  struct l3_feat: the device matrix of
+ * "Fold preprocessing" below. */
+/* l3_svm_set_data from rows [lo, hi) of a device matrix (preprocess_split_data's output, features.py:52-150): one copy on the SVM's
+ * stream, then the norms; the l3_feat may be destroyed afterwards.  L3_EINVAL for a handle on another device or a bad or empty range. */
+int l3_svm_set_data_dev(l3_svm *m, const struct l3_feat *f, int64_t lo, int64_t hi);
+/* out (n, D) = rows idx of the resident matrix: SVC.support_vectors_ (sklearn svm/base.py: the rows libsvm copies out of a fit)
+ * when the fit came from the device */
+int l3_svm_get_rows(l3_svm *m, const int32_t *idx, int64_t n, float *out);
+/* The model svm_predict_values / svm_predict_probability read (svm.cpp svm_model), resident until the next set_model: the kernel, the
+ * support vectors as a host matrix SV (n_sv, D) or as sv_idx into the resident matrix (their rows are copied, so the model
+ * outlives the matrix), sv_start / coef / rho as in l3_svm_decision, and Platt's probA / probB per pair (both or neither; NULL: a
+ * model without probability estimates).  Everything is copied once, with the norms.  Argument checks as l3_svm_decision. */
+int l3_svm_set_model(l3_svm *m, const l3_svm_kernel *k, const float *SV, const int32_t *sv_idx, int64_t n_sv, int D, int n_class,
+                     const int64_t *sv_start, const double *coef, const double *rho, const double *probA, const double *probB);
+/* One scoring pass over n rows with the resident model (train.py:134-166).  Rows: exactly one of a host matrix X (n, D), x_idx (n)
+ * into the resident matrix, or rows [lo, hi) of a device matrix (n = hi - lo), else L3_EINVAL; a host matrix is staged in
+ * l3_svm_decision's row blocks.  labels (n) host class indices in [0, n_class) or NULL; files (n_files, 2) int64 row ranges, each
+ * non-empty and inside [0, n), or NULL.  Every output may be NULL (not wanted): pred (n) the one-vs-one vote, ties to the lower class
+ * (svm.cpp svm_predict_values); ovr (n, n_class) sklearn 0.19's _ovr_decision_function(dec < 0, -dec), or (n) = -dec for two
+ * classes; hinge_sum the sum of sklearn's hinge_loss terms (needs labels; the caller divides by n; chunks of 256 rows added in row
+ * order, then the chunk sums in chunk order); proba (n, n_class) svm_predict_probability; file_proba (n_files, n_class) the mean of a
+ * file's rows in row order and file_pred its argmax, ties to the lower class (train.py:158-163).  Per row block: decision values,
+ * pairs, tail, coupling; the file means after the last block; proba stays on the device unless asked for.  One host wait per call.
+ * L3_ESTATE without a model, or when a probability output is asked of a model set without probA / probB. */
+int l3_svm_score(l3_svm *m, const float *X, const int32_t *x_idx, const struct l3_feat *feat, int64_t lo, int64_t hi, int64_t n,
+                 int D, const int32_t *labels, const int64_t *files, int64_t n_files, int32_t *pred_out, double *ovr_out,
+                 double *hinge_sum_out, double *proba_out, double *file_proba_out, int32_t *file_pred_out);
+/* The kernels behind l3_svm_score on a host block of pair decisions dec (n, P), no kernel evaluation in front (parity tests).
+ * The outputs of l3_svm_score, plus pair_proba (n, P): sigmoid_predict (svm.cpp) of each decision clipped to [1e-7, 1 - 1e-7], and
+ * iters (n): the sweeps multiclass_probability (svm.cpp) made for the row, max(100, n_class) at its cap. */
+int l3_op_svm_tail(int device, const double *dec, int64_t n, int n_class, const double *probA, const double *probB,
+                   const int32_t *labels, const int64_t *files, int64_t n_files, int32_t *pred_out, double *ovr_out,
+                   double *hinge_sum_out, double *pair_proba_out, double *proba_out, double *file_proba_out, int32_t *file_pred_out,
+                   int32_t *iters_out);
 
 /* ---- VGGish baseline features (data/usc/features.py:166-240) --------------------------------------------------------------------
  * extract_vggish_embedding / get_vggish_frames_uniform on the GPU, inference only, fp32: load_audio's resampling to 16 kHz and the

@@ -177,6 +177,14 @@ SIGNATURES = {
                                         C.c_int, C.c_void_p]),
     'l3_op_svm_smo': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ... its scoring (csrc/svm_eval.hip)
+    'l3_svm_set_data_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    'l3_svm_get_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_svm_set_model': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    'l3_svm_score': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
+                               C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
+    'l3_op_svm_tail': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+                       + [C.c_void_p] * 8),
     # VGGish baseline features (csrc/vggish.hip)
     'l3_vggish_create': (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     'l3_vggish_destroy': (None, [C.c_void_p]),
@@ -1178,6 +1186,33 @@ def svm_kernel(kernel, gamma=0.0, coef0=0.0, degree=3):
     return SvmKernel(SVM_KERNELS[kernel], int(degree), float(gamma), float(coef0))
 
 
+def _svm_score_io(n, ncls, labels, files, outputs, extra):
+    """labels and file ranges as the C ABI takes them, the output arrays `outputs` names and the pointer list of l3_svm_score
+    (`extra` = ('pair_proba', 'iters'): of l3_op_svm_tail), NULL where an output is not wanted"""
+    lab = None if labels is None else _i32(labels).reshape(-1)
+    if lab is not None and lab.size != n:
+        raise ValueError('one label per row is needed')
+    fl = None if files is None else _i64(files).reshape(-1, 2)
+    nf = 0 if fl is None else fl.shape[0]
+    P = ncls * (ncls - 1) // 2
+    shapes = {'pred': ((n,), np.int32), 'ovr': ((n,) if ncls == 2 else (n, ncls), np.float64), 'hinge_sum': ((1,), np.float64),
+              'pair_proba': ((n, P), np.float64), 'proba': ((n, ncls), np.float64), 'file_proba': ((nf, ncls), np.float64),
+              'file_pred': ((nf,), np.int32), 'iters': ((n,), np.int32)}
+    order = [k for k in ('pred', 'ovr', 'hinge_sum', 'pair_proba', 'proba', 'file_proba', 'file_pred', 'iters')
+             if k in extra or k not in ('pair_proba', 'iters')]
+    unknown = set(outputs) - set(order)
+    if unknown:
+        raise ValueError('unknown outputs %s' % sorted(unknown))
+    out = {k: np.empty(*shapes[k]) for k in outputs}
+    return lab, fl, out, [_ptr(out.get(k)) for k in order]
+
+
+def _svm_score_result(out):
+    if 'hinge_sum' in out:
+        out['hinge_sum'] = float(out['hinge_sum'][0])
+    return out
+
+
 class SVM(object):
     """RAII wrapper over an l3_svm handle: the resident training matrix and the batched binary solver on one device."""
 
@@ -1241,6 +1276,65 @@ class SVM(object):
                                        _ptr(cs), _ptr(cf), _ptr(rh), _ptr(out)))
         return out
 
+    def set_data_dev(self, feat, lo=0, hi=None):
+        """set_data from rows [lo, hi) of the Features `feat`, copied device to device; it may be closed afterwards"""
+        n, d = feat.shape
+        hi = n if hi is None else hi
+        check(self.lib.l3_svm_set_data_dev(self.h, feat.h, int(lo), int(hi)))
+        self.n, self.D = int(hi - lo), int(d)
+
+    def get_rows(self, idx):
+        """rows idx of the resident matrix -> (len(idx), D) float32"""
+        i = _i32(idx).reshape(-1)
+        out = np.empty((i.size, self.D), np.float32)
+        if i.size:
+            check(self.lib.l3_svm_get_rows(self.h, _ptr(i), i.size, _ptr(out)))
+        return out
+
+    def set_model(self, kernel, sv_start, coef, rho, SV=None, sv_idx=None, probA=None, probB=None):
+        """the resident model of score(): arguments as decision(), and Platt's (A, B) per pair or neither"""
+        cs = np.ascontiguousarray(sv_start, np.int64)
+        ncls = cs.size - 1
+        cf = np.ascontiguousarray(coef, np.float64).reshape(ncls - 1, -1)
+        rh = np.ascontiguousarray(rho, np.float64).reshape(-1)
+        if rh.size != ncls * (ncls - 1) // 2 or cf.shape[1] != cs[-1]:
+            raise ValueError('coef must be (n_class - 1, n_sv) and rho one per pair')
+        sv, si = _f32(SV), _i32(sv_idx)
+        D = sv.shape[1] if sv is not None else self.D
+        if sv is not None and sv.size == 0:
+            sv = np.zeros((1, D), np.float32)
+        if si is not None and si.size == 0:
+            si = np.zeros(1, np.int32)
+        pa = None if probA is None else _f64(probA).reshape(-1)
+        pb = None if probB is None else _f64(probB).reshape(-1)
+        if (pa is None) != (pb is None) or (pa is not None and (pa.size != rh.size or pb.size != rh.size)):
+            raise ValueError('probA and probB come together, one entry per pair')
+        check(self.lib.l3_svm_set_model(self.h, C.byref(kernel), _ptr(sv), _ptr(si), int(cs[-1]), int(D), ncls, _ptr(cs), _ptr(cf),
+                                        _ptr(rh), _ptr(pa), _ptr(pb)))
+        self.model_classes, self.model_D = ncls, int(D)
+
+    def score(self, X=None, x_idx=None, feat=None, lo=0, hi=None, labels=None, files=None,
+              outputs=('pred', 'ovr', 'hinge_sum', 'proba', 'file_proba', 'file_pred')):
+        """one scoring pass with the resident model over host rows X, resident rows x_idx or rows [lo, hi) of the Features `feat`
+        -> dict of the named outputs (l3_svm_score)"""
+        if (X is not None) + (x_idx is not None) + (feat is not None) != 1:
+            raise ValueError('give rows as exactly one of X, x_idx or feat')
+        if not getattr(self, 'model_classes', 0):
+            raise L3Error('l3_svm_score: no model (set_model)')
+        ncls = self.model_classes
+        x, xi = _f32(X), _i32(x_idx)
+        if feat is not None:
+            hi = feat.shape[0] if hi is None else hi
+            n, D = int(hi - lo), self.model_D
+        else:
+            n = x.shape[0] if x is not None else xi.size
+            D = x.shape[1] if x is not None else self.D
+            lo = hi = 0
+        lab, fl, out, ptrs = _svm_score_io(n, ncls, labels, files, outputs, ())
+        check(self.lib.l3_svm_score(self.h, _ptr(x), _ptr(xi), None if feat is None else feat.h, int(lo), int(hi), n, int(D), _ptr(lab),
+                                    _ptr(fl), 0 if fl is None else fl.shape[0], *ptrs))
+        return _svm_score_result(out)
+
 
 def op_svm_kernel_rows(x, a_idx, b_idx, kernel='rbf', gamma=0.0, coef0=0.0, degree=3, device=0):
     """(len(a_idx), len(b_idx)) float32: k(x[a], x[b]) through the solver's kernel-row launch"""
@@ -1262,6 +1356,23 @@ def op_svm_smo(K, y, alpha, grad, cost=1.0, eps=1e-3, local_rel=0.0, max_updates
     check(load().l3_op_svm_smo(device, _ptr(K), _ptr(y), y.size, float(cost), float(eps), float(local_rel), int(max_updates), _ptr(a),
                                _ptr(g), _ptr(u)))
     return a, int(u[0])
+
+
+def op_svm_tail(dec, n_classes, probA=None, probB=None, labels=None, files=None,
+                outputs=('pred', 'ovr', 'hinge_sum', 'pair_proba', 'proba', 'file_proba', 'file_pred', 'iters'), device=0):
+    """the scoring kernels (csrc/svm_eval.hip) on a host block of pair decisions (n, P) -> dict of the named outputs"""
+    ncls = int(n_classes)
+    P = ncls * (ncls - 1) // 2
+    dec = _f64(dec).reshape(-1, P)
+    n = dec.shape[0]
+    pa = None if probA is None else _f64(probA).reshape(-1)
+    pb = None if probB is None else _f64(probB).reshape(-1)
+    if (pa is not None and pa.size != P) or (pb is not None and pb.size != P):
+        raise ValueError('probA and probB hold one entry per pair')
+    lab, fl, out, ptrs = _svm_score_io(n, ncls, labels, files, outputs, ('pair_proba', 'iters'))
+    check(load().l3_op_svm_tail(int(device), _ptr(dec), n, ncls, _ptr(pa), _ptr(pb), _ptr(lab), _ptr(fl),
+                                0 if fl is None else fl.shape[0], *ptrs))
+    return _svm_score_result(out)
 
 
 # ---- VGGish baseline features (csrc/vggish.hip; data/usc/features.py:166-240) -----------------------------------------------------

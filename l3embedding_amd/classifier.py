@@ -314,10 +314,17 @@ def train_mlp(train_data, valid_data, test_data, model_dir, batch_size=64, num_e
 
 
 def train_svm(train_data, valid_data, test_data, model_dir, C=1.0, kernel='rbf', num_classes=10, tol=0.001, max_iterations=-1,
-              verbose=False, random_state=12345678, **kwargs):
+              verbose=False, random_state=12345678, evaluate_on_device=False, **kwargs):
     """classifier/train.py:79-166 -> (model, train_metrics, valid_metrics, test_metrics): SVC(C, kernel, tol, max_iter,
     probability=True, random_state) fitted on the GPU and pickled to model_dir/model.pkl; 'loss' is sklearn's hinge loss of the
-    (ovr) decision values; the test set is classified per file as the argmax of the mean of its frames' predict_proba."""
+    (ovr) decision values; the test set is classified per file as the argmax of the mean of its frames' predict_proba.
+    evaluate_on_device: the splits stay as they are (usc.DeviceFeatures are not downloaded) and each is scored by one
+    SVC.evaluate on the GPU; the same four values come back.  That path reads the classes off the fitted model (clf.classes_)
+    where the default one passes labels=np.arange(num_classes) to hinge_loss: the two agree when every class of
+    range(num_classes) occurs in the training split, and a validation label the training split lacks is a ValueError there."""
+    if evaluate_on_device:
+        return _train_svm_on_device(train_data, valid_data, test_data, model_dir, C, kernel, num_classes, tol, max_iterations,
+                                    verbose, random_state)
     train_data, valid_data, test_data = (_on_host(d) for d in (train_data, valid_data, test_data))
     features, labels = train_data['features'], train_data['labels']
     clf = SVC(C=C, probability=True, kernel=kernel, max_iter=max_iterations, tol=tol, random_state=random_state, verbose=verbose)
@@ -341,6 +348,33 @@ def train_svm(train_data, valid_data, test_data, model_dir, C=1.0, kernel='rbf',
         per_file = _file_predictions(clf.predict_proba(test_data['features']), test_data['file_idxs'])
         test_metrics = compute_metrics(test_data['labels'], per_file, num_classes=num_classes)
     return clf, train_metrics, valid_metrics, test_metrics
+
+
+def _train_svm_on_device(train_data, valid_data, test_data, model_dir, C, kernel, num_classes, tol, max_iterations, verbose,
+                         random_state):
+    """train_svm with the fit from the split as it is and one SVC.evaluate per split: predictions and the hinge loss of the train
+    and validation rows (no (n, C) array returns), the per-file classes of the test set"""
+    clf = SVC(C=C, probability=True, kernel=kernel, max_iter=max_iterations, tol=tol, random_state=random_state, verbose=verbose)
+    LOGGER.debug('Fitting model to data...')
+    clf.fit(train_data['features'], train_data['labels'])
+    LOGGER.info('Saving model...')
+    _dump(os.path.join(model_dir, 'model.pkl'), clf)
+
+    metrics = []
+    for name, data in (('Train', train_data), ('Valid', valid_data)):
+        if not data:
+            metrics.append({})
+            continue
+        got = clf.evaluate(data['features'], y=data['labels'], outputs=('predict', 'hinge_loss'))
+        m = compute_metrics(data['labels'], got['predict'], num_classes=num_classes)
+        m['loss'] = got['hinge_loss']
+        LOGGER.info('%s - hinge loss: %s, acc: %s', name, m['loss'], m['accuracy'])
+        metrics.append(m)
+    test_metrics = {}
+    if test_data:
+        per_file = clf.evaluate(test_data['features'], file_idxs=test_data['file_idxs'], outputs=('file_predict',))['file_predict']
+        test_metrics = compute_metrics(test_data['labels'], per_file, num_classes=num_classes)
+    return clf, metrics[0], metrics[1], test_metrics
 
 
 def _on_host(data):

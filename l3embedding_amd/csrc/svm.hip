@@ -23,7 +23,9 @@
 
 #include "../../include/l3hip.h"
 #include "device_common.h"
+#include "featprep.h"
 #include "kernels.h"
+#include "svm_eval.h"
 
 namespace l3 {
 namespace {
@@ -594,6 +596,14 @@ __global__ void svm_pairs_kernel(const double* S, const double* rho, int64_t n, 
     dec[e] = S[(m * ncls + i) * R + (j - 1)] + S[(m * ncls + j) * R + i] - rho[pp];
 }
 
+// out (n, D) = x[idx]: the support vectors of a resident model, and the rows l3_svm_get_rows downloads
+__global__ void svm_gather_rows_kernel(const float* x, const int* idx, int64_t n, int D, float* out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * D) return;
+    const int64_t r = e / D;
+    out[e] = x[(int64_t)idx[r] * D + (e - r * D)];
+}
+
 }  // namespace
 }  // namespace l3
 
@@ -609,6 +619,15 @@ struct l3_svm {
     float *x = nullptr, *xx = nullptr;
     int64_t n = 0;
     int D = 0;
+    // the resident model of l3_svm_set_model (mbufs owns it): support vectors with their norms, grouped by class
+    DeviceBufs mbufs;
+    bool has_model = false, has_prob = false;
+    SvmKern mk{};
+    float *msv = nullptr, *msvn = nullptr;
+    int64_t* mcs = nullptr;
+    double *mcoef = nullptr, *mrho = nullptr, *mA = nullptr, *mB = nullptr;
+    int64_t m_nsv = 0;
+    int m_ncls = 0, mD = 0;
 };
 
 namespace {
@@ -843,6 +862,201 @@ int l3_svm_decision(l3_svm* m, const l3_svm_kernel* kp, const float* X, const in
     if (hipMemcpyAsync(dec_out, dec, (size_t)n * P * sizeof(double), hipMemcpyDeviceToHost, m->s) != hipSuccess ||
         hipStreamSynchronize(m->s) != hipSuccess)
         return fail(L3_EHIP, "l3_svm_decision: HIP error");
+    return L3_OK;
+}
+
+int l3_svm_set_data_dev(l3_svm* m, const l3_feat* f, int64_t lo, int64_t hi) {
+    if (!m || !f) return fail(L3_EINVAL, "l3_svm_set_data_dev: NULL handle");
+    if (f->device != m->device) return fail(L3_EINVAL, "l3_svm_set_data_dev: the feature matrix is on another device");
+    if (lo < 0 || hi <= lo || hi > f->n) return fail(L3_EINVAL, "l3_svm_set_data_dev: rows [lo, hi) lie outside the matrix or are none");
+    const int64_t n = hi - lo;
+    if (n > INT32_MAX || f->D <= 0 || f->D > (1 << 24)) return fail(L3_EINVAL, "l3_svm_set_data_dev: need 1 <= n < 2^31, 1 <= D <= 2^24");
+    const int D = (int)f->D;
+    (void)hipSetDevice(m->device);
+    (void)hipStreamSynchronize(m->s);
+    m->bufs.release(m->x), m->bufs.release(m->xx);
+    m->x = m->xx = nullptr, m->n = 0;
+    if (!(m->x = m->bufs.alloc<float>((size_t)n * D)) || !(m->xx = m->bufs.alloc<float>((size_t)n)))
+        return fail(L3_ENOMEM, "l3_svm_set_data_dev: device allocation of " + std::to_string(n * D * 4) + " bytes failed");
+    if (hipMemcpyAsync(m->x, f->x + lo * D, (size_t)n * D * sizeof(float), hipMemcpyDeviceToDevice, m->s) != hipSuccess)
+        return fail(L3_EHIP, "l3_svm_set_data_dev: copy on the device failed");
+    launch_norms(m->x, n, D, m->xx, m->s);
+    if (hipStreamSynchronize(m->s) != hipSuccess) return fail(L3_EHIP, "l3_svm_set_data_dev: HIP error");
+    m->n = n, m->D = D;
+    return L3_OK;
+}
+
+int l3_svm_get_rows(l3_svm* m, const int32_t* idx, int64_t n, float* out) {
+    if (!m || !idx || !out || n <= 0) return fail(L3_EINVAL, "l3_svm_get_rows: NULL argument or n <= 0");
+    if (m->n <= 0) return fail(L3_ESTATE, "l3_svm_get_rows: no resident matrix (l3_svm_set_data)");
+    for (int64_t i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= m->n) return fail(L3_EINVAL, "l3_svm_get_rows: idx[" + std::to_string(i) + "] outside [0, n)");
+    (void)hipSetDevice(m->device);
+    DeviceBufs b;
+    const int* di = b.put(idx, n, m->s);
+    float* d = b.alloc<float>((size_t)n * m->D);
+    if (!b.ok()) return fail(L3_ENOMEM, "l3_svm_get_rows: device allocation failed");
+    const int64_t e = n * m->D;
+    hipLaunchKernelGGL(svm_gather_rows_kernel, dim3((unsigned)((e + 255) / 256)), dim3(256), 0, m->s, m->x, di, n, m->D, d);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, d, (size_t)e * sizeof(float), hipMemcpyDeviceToHost, m->s) != hipSuccess ||
+        hipStreamSynchronize(m->s) != hipSuccess)
+        return fail(L3_EHIP, "l3_svm_get_rows: HIP error");
+    return L3_OK;
+}
+
+int l3_svm_set_model(l3_svm* m, const l3_svm_kernel* kp, const float* SV, const int32_t* sv_idx, int64_t n_sv, int D, int n_class,
+                     const int64_t* sv_start, const double* coef, const double* rho, const double* probA, const double* probB) {
+    std::string why;
+    if (!m || !sv_start || !coef || !rho) return fail(L3_EINVAL, "l3_svm_set_model: NULL argument");
+    if (!kern_ok(kp, &why)) return fail(L3_EINVAL, "l3_svm_set_model: " + why);
+    if (n_class < 2 || n_class > SVM_MAX_CLASSES) return fail(L3_EINVAL, "l3_svm_set_model: class count must be in [2, 64]");
+    if ((!SV) == (!sv_idx)) return fail(L3_EINVAL, "l3_svm_set_model: give support vectors either as a matrix or as indices");
+    if ((!probA) != (!probB)) return fail(L3_EINVAL, "l3_svm_set_model: probA and probB come together");
+    if (sv_idx && (m->n <= 0 || D != m->D)) return fail(L3_ESTATE, "l3_svm_set_model: indices need the resident matrix of D columns");
+    if (D <= 0 || D > (1 << 24) || n_sv < 0 || n_sv > INT32_MAX) return fail(L3_EINVAL, "l3_svm_set_model: bad sizes");
+    if (sv_start[0] != 0 || sv_start[n_class] != n_sv) return fail(L3_EINVAL, "l3_svm_set_model: sv_start must run from 0 to n_sv");
+    for (int c = 0; c < n_class; ++c)
+        if (sv_start[c + 1] < sv_start[c]) return fail(L3_EINVAL, "l3_svm_set_model: sv_start must not decrease");
+    if (sv_idx)
+        for (int64_t i = 0; i < n_sv; ++i)
+            if (sv_idx[i] < 0 || sv_idx[i] >= m->n) return fail(L3_EINVAL, "l3_svm_set_model: sv_idx outside [0, n)");
+    (void)hipSetDevice(m->device);
+    (void)hipStreamSynchronize(m->s);
+    m->mbufs.clear();
+    m->has_model = m->has_prob = false;
+    DeviceBufs& b = m->mbufs;
+    const int R = n_class - 1, P = n_class * R / 2;
+    DeviceBufs tmp;
+    if (SV) {
+        m->msv = b.put(SV, (size_t)n_sv * D, m->s);
+    } else {
+        m->msv = b.alloc<float>((size_t)n_sv * D);
+        const int* di = tmp.put(sv_idx, n_sv, m->s);
+        const int64_t e = n_sv * D;
+        if (b.ok() && tmp.ok() && e > 0)
+            hipLaunchKernelGGL(svm_gather_rows_kernel, dim3((unsigned)((e + 255) / 256)), dim3(256), 0, m->s, m->x, di, n_sv, D, m->msv);
+    }
+    m->msvn = b.alloc<float>((size_t)n_sv);
+    m->mcs = b.put(sv_start, n_class + 1, m->s);
+    m->mcoef = b.put(coef, (size_t)R * n_sv, m->s);
+    m->mrho = b.put(rho, P, m->s);
+    m->mA = probA ? b.put(probA, P, m->s) : nullptr;
+    m->mB = probB ? b.put(probB, P, m->s) : nullptr;
+    // the pointers, not b.ok(): mbufs lives as long as the handle, and a failure it once met must not fail every later model
+    if (!m->msv || !m->msvn || !m->mcs || !m->mcoef || !m->mrho || (probA && (!m->mA || !m->mB)) || !tmp.ok()) {
+        (void)hipStreamSynchronize(m->s);
+        b.clear();
+        return fail(L3_ENOMEM, "l3_svm_set_model: device allocation failed");
+    }
+    launch_norms(m->msv, n_sv, D, m->msvn, m->s);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(m->s) != hipSuccess) {
+        b.clear();
+        return fail(L3_EHIP, "l3_svm_set_model: HIP error");
+    }
+    m->mk = to_kern(kp), m->m_nsv = n_sv, m->m_ncls = n_class, m->mD = D;
+    m->has_model = true, m->has_prob = probA != nullptr;
+    return L3_OK;
+}
+
+int l3_svm_score(l3_svm* m, const float* X, const int32_t* x_idx, const l3_feat* feat, int64_t lo, int64_t hi, int64_t n, int D,
+                 const int32_t* labels, const int64_t* files, int64_t n_files, int32_t* pred_out, double* ovr_out,
+                 double* hinge_sum_out, double* proba_out, double* file_proba_out, int32_t* file_pred_out) {
+    if (!m) return fail(L3_EINVAL, "l3_svm_score: NULL handle");
+    if ((X != nullptr) + (x_idx != nullptr) + (feat != nullptr) != 1)
+        return fail(L3_EINVAL, "l3_svm_score: give rows as exactly one of a matrix, indices or a device matrix");
+    if (!m->has_model) return fail(L3_ESTATE, "l3_svm_score: no model (l3_svm_set_model)");
+    const bool want_files = file_proba_out || file_pred_out;
+    const bool want_prob = proba_out || want_files;
+    if (want_prob && !m->has_prob) return fail(L3_ESTATE, "l3_svm_score: the model was set without probA / probB");
+    if (feat) {
+        if (feat->device != m->device || feat->D != m->mD)
+            return fail(L3_EINVAL, "l3_svm_score: the feature matrix is on another device or not " + std::to_string(m->mD) +
+                                       " columns wide");
+        if (lo < 0 || hi <= lo || hi > feat->n || n != hi - lo)
+            return fail(L3_EINVAL, "l3_svm_score: rows [lo, hi) lie outside the matrix, are none, or are not n");
+        D = m->mD;
+    }
+    if (n <= 0 || n > INT32_MAX || D != m->mD) return fail(L3_EINVAL, "l3_svm_score: need 1 <= n < 2^31 rows of the model's width");
+    if (x_idx) {
+        if (m->n <= 0 || m->D != D) return fail(L3_ESTATE, "l3_svm_score: indices need the resident matrix of D columns");
+        for (int64_t i = 0; i < n; ++i)
+            if (x_idx[i] < 0 || x_idx[i] >= m->n) return fail(L3_EINVAL, "l3_svm_score: x_idx outside [0, n)");
+    }
+    const int C = m->m_ncls, R = C - 1, P = C * R / 2;
+    if (hinge_sum_out && !labels) return fail(L3_EINVAL, "l3_svm_score: the hinge loss needs labels");
+    if (labels)
+        for (int64_t i = 0; i < n; ++i)
+            if (labels[i] < 0 || labels[i] >= C) return fail(L3_EINVAL, "l3_svm_score: labels[" + std::to_string(i) + "] outside [0, C)");
+    if (want_files) {
+        if (!files || n_files <= 0) return fail(L3_EINVAL, "l3_svm_score: file outputs need file ranges");
+        for (int64_t f = 0; f < n_files; ++f)
+            if (files[2 * f] < 0 || files[2 * f] >= files[2 * f + 1] || files[2 * f + 1] > n)
+                return fail(L3_EINVAL, "l3_svm_score: file " + std::to_string(f) + " is empty or outside [0, n)");
+    }
+    (void)hipSetDevice(m->device);
+    // l3_svm_decision's row blocks, so that every decision launch has its shape
+    int64_t rows_blk = std::min<int64_t>({65536, (int64_t(64) << 20) / D, (int64_t(32) << 20) / ((int64_t)C * R)});
+    rows_blk = std::max<int64_t>(32, rows_blk & ~int64_t(31));
+    const int64_t blk = std::min(rows_blk, n);
+    const int ovr_w = C == 2 ? 1 : C;
+    const int64_t chunks = (n + SVM_HINGE_CHUNK - 1) / SVM_HINGE_CHUNK;
+    DeviceBufs b;
+    hipStream_t s = m->s;
+    double* S = b.alloc<double>((size_t)blk * C * R);
+    double* dec = b.alloc<double>((size_t)blk * P);
+    float* xt = X ? b.alloc<float>((size_t)blk * D) : nullptr;
+    float* xtn = x_idx ? nullptr : b.alloc<float>((size_t)blk);
+    const int* xi = x_idx ? b.put(x_idx, n, s) : nullptr;
+    const int* d_lab = hinge_sum_out ? b.put(labels, n, s) : nullptr;
+    const int64_t* d_files = want_files ? b.put(files, 2 * n_files, s) : nullptr;
+    int* d_pred = pred_out ? b.alloc<int>(n) : nullptr;
+    double* d_ovr = ovr_out ? b.alloc<double>((size_t)n * ovr_w) : nullptr;
+    double* d_hinge = hinge_sum_out ? b.alloc<double>(n) : nullptr;
+    double* d_part = hinge_sum_out ? b.alloc<double>(chunks + 1) : nullptr;
+    double* d_pp = want_prob ? b.alloc<double>((size_t)blk * P) : nullptr;
+    double* d_proba = want_prob ? b.alloc<double>((size_t)n * C) : nullptr;
+    double* d_fp = file_proba_out ? b.alloc<double>((size_t)n_files * C) : nullptr;
+    int* d_fpred = file_pred_out ? b.alloc<int>(n_files) : nullptr;
+    if (!b.ok()) return fail(L3_ENOMEM, "l3_svm_score: device allocation failed");
+    for (int64_t r0 = 0; r0 < n; r0 += blk) {
+        const int64_t rows = std::min(blk, n - r0);
+        int rc;
+        if (x_idx) {
+            rc = decision_dev(s, m->x, m->xx, xi + r0, rows, m->msv, m->msvn, nullptr, m->m_nsv, D, C, m->mcs, m->mcoef, m->mrho, m->mk,
+                              S, rows_blk, dec);
+        } else {
+            const float* xb = feat ? feat->x + (lo + r0) * D : xt;
+            if (X && hipMemcpyAsync(xt, X + r0 * D, (size_t)rows * D * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) {
+                (void)hipStreamSynchronize(s);          // copies from the caller's buffers are still queued
+                return fail(L3_EHIP, "l3_svm_score: copy to the device failed");
+            }
+            launch_norms(xb, rows, D, xtn, s);
+            rc = decision_dev(s, xb, xtn, nullptr, rows, m->msv, m->msvn, nullptr, m->m_nsv, D, C, m->mcs, m->mcoef, m->mrho, m->mk, S,
+                              rows_blk, dec);
+        }
+        if (rc != L3_OK) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        svm_tail(s, dec, rows, C, want_prob ? m->mA : nullptr, want_prob ? m->mB : nullptr, d_lab ? d_lab + r0 : nullptr,
+                 d_pred ? d_pred + r0 : nullptr, d_ovr ? d_ovr + r0 * ovr_w : nullptr, d_hinge ? d_hinge + r0 : nullptr, d_pp);
+        if (want_prob) svm_coupling(s, d_pp, rows, C, d_proba + r0 * C, nullptr);
+    }
+    if (want_files) svm_file_mean(s, d_proba, C, d_files, n_files, d_fp, d_fpred);
+    if (hinge_sum_out) svm_hinge_sum(s, d_hinge, n, d_part, d_part + chunks);
+    bool ok = hipGetLastError() == hipSuccess;
+    auto get = [&](void* dst, const void* src, size_t bytes) {
+        if (dst && ok) ok = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
+    };
+    get(pred_out, d_pred, (size_t)n * sizeof(int));
+    get(ovr_out, d_ovr, (size_t)n * ovr_w * sizeof(double));
+    get(hinge_sum_out, d_part ? d_part + chunks : nullptr, sizeof(double));
+    get(proba_out, d_proba, (size_t)n * C * sizeof(double));
+    get(file_proba_out, d_fp, (size_t)n_files * C * sizeof(double));
+    get(file_pred_out, d_fpred, (size_t)n_files * sizeof(int));
+    // the one host wait of the call
+    const bool done = hipStreamSynchronize(s) == hipSuccess;
+    if (!ok || !done) return fail(L3_EHIP, "l3_svm_score: HIP error");
     return L3_OK;
 }
 

@@ -4,7 +4,10 @@ trained and evaluated on the GPU through the l3_svm handle of libl3hip (csrc/svm
 Here are the multiclass shell and probability estimates of libsvm's svm_train / svm_predict_probability (svm.cpp): one-vs-one
 pairs, support vectors grouped by class with the (C - 1, n_SV) coefficient matrix, the vote, Platt scaling fitted on 5-fold
 cross-validation decision values, and pairwise coupling.  Every binary problem (the pairs and their cross-validation
-sub-problems) goes through the GPU solver in one batched call; the sigmoid fit and the coupling stay on the host in NumPy.
+sub-problems) goes through the GPU solver in one batched call; the sigmoid fit stays on the host in NumPy.  predict,
+decision_function and predict_proba of NumPy rows vote and couple on the host in NumPy; SVC.evaluate scores a split in one pass on
+the GPU (csrc/svm_eval.hip: vote, ovr values, hinge loss, Platt probabilities, coupling, per-file means) and takes
+usc.DeviceFeatures as it is, as fit does.
 
 Deviations from sklearn 0.19 / libsvm, all deliberate:
   * the cross-validation fold permutation of probability estimates is drawn from np.random.RandomState(random_state) (libsvm
@@ -20,11 +23,13 @@ import logging
 import numpy as np
 
 from . import _lib
+from .usc import DeviceFeatures
 
 LOGGER = logging.getLogger('classifier')
 
 NR_FOLD = 5
 MIN_PROB = 1e-7
+EVALUATE_OUTPUTS = ('predict', 'decision_function', 'hinge_loss', 'predict_proba', 'file_proba', 'file_predict')
 
 
 # ---- libsvm's probability estimates (svm.cpp), float64 on the host -----------------------------------------------------------
@@ -180,6 +185,7 @@ class SVC(object):
     def __getstate__(self):
         state = dict(self.__dict__)
         state['_h'] = None
+        state['_model_set'] = state['_resident'] = False
         return state
 
     def __setstate__(self, state):
@@ -194,9 +200,12 @@ class SVC(object):
         return _lib.svm_kernel(self.kernel, self._gamma, self.coef0, self.degree)
 
     def fit(self, X, y):
-        X = np.ascontiguousarray(X, np.float32)
+        """X: NumPy rows, or a usc.DeviceFeatures, which is copied on the device (no download; the solver sees the same bits)"""
+        on_device = isinstance(X, DeviceFeatures)
+        if not on_device:
+            X = np.ascontiguousarray(X, np.float32)
         y = np.asarray(y).reshape(-1)
-        if X.ndim != 2 or X.shape[0] != y.size:
+        if len(X.shape) != 2 or X.shape[0] != y.size:
             raise ValueError('X must be (n_samples, n_features) with one label per row')
         if not self.C > 0:
             raise ValueError('C <= 0')
@@ -208,10 +217,14 @@ class SVC(object):
             raise ValueError('The number of classes has to be greater than one; got %d' % nc)
         if nc > _lib.SVM_MAX_CLASSES:
             raise ValueError('at most %d classes are built' % _lib.SVM_MAX_CLASSES)
-        self.shape_fit_ = X.shape
+        self.shape_fit_ = tuple(X.shape)
         self._gamma = 1.0 / X.shape[1] if self.gamma == 'auto' else float(self.gamma)
+        self._model_set = self._resident = False
         h = self._handle()
-        h.set_data(X)
+        if on_device:
+            h.set_data_dev(X.handle)
+        else:
+            h.set_data(X)
         kp = self._kernel()
         groups = [np.flatnonzero(yenc == c).astype(np.int32) for c in range(nc)]
         pairs = [(i, j) for i in range(nc) for j in range(i + 1, nc)]
@@ -241,25 +254,26 @@ class SVC(object):
         if self.max_iter is not None and self.max_iter > 0 and np.any(updates >= self.max_iter):
             LOGGER.warning('Solver terminated early (max_iter=%d).  Consider pre-processing your data with StandardScaler or '
                            'MinMaxScaler.', self.max_iter)
-        self._build_model(X, groups, pairs, problems, alphas, rho)
+        self._build_model(h.get_rows if on_device else X.__getitem__, y.size, groups, pairs, problems, alphas, rho)
         if self.probability:
             self.probA_, self.probB_ = self._platt(h, kp, problems, sub, cv, alphas, rho)
         else:
             self.probA_ = self.probB_ = np.empty(0)
+        self._resident = True          # the support vectors are rows support_ of this handle's matrix
         return self
 
-    def _build_model(self, X, groups, pairs, problems, alphas, rho):
+    def _build_model(self, rows_of, n_rows, groups, pairs, problems, alphas, rho):
         """svm.cpp svm_train's multiclass model: support vectors grouped by class, sv_coef (C - 1, n_SV), rho per pair"""
         nc = len(groups)
-        nonzero = np.zeros(X.shape[0], bool)
+        nonzero = np.zeros(n_rows, bool)
         for (rows, _), a in zip(problems, alphas):
             nonzero[rows[a > 0]] = True
         sv_of = [g[nonzero[g]] for g in groups]
         self.n_support_ = np.array([s.size for s in sv_of], np.int32)
         self.support_ = np.concatenate(sv_of).astype(np.int32)
-        self.support_vectors_ = X[self.support_]
+        self.support_vectors_ = rows_of(self.support_)
         start = np.concatenate(([0], np.cumsum(self.n_support_)))
-        pos = np.full(X.shape[0], -1, np.int64)
+        pos = np.full(n_rows, -1, np.int64)
         pos[self.support_] = np.arange(self.support_.size)
         coef = np.zeros((nc - 1, self.support_.size))
         for (i, j), (rows, signs), a in zip(pairs, problems, alphas):
@@ -310,7 +324,73 @@ class SVC(object):
         return self._handle().decision(self._kernel(), self._sv_start, self._dual_coef_, -self._intercept_, X=X,
                                        SV=self.support_vectors_)
 
+    def _ensure_model(self):
+        """the resident model of evaluate: set once per fitted model, and again after unpickling"""
+        h = self._handle()
+        if not getattr(self, '_model_set', False):
+            prob = dict(probA=self.probA_, probB=self.probB_) if self.probability else {}
+            sv = dict(sv_idx=self.support_) if getattr(self, '_resident', False) else dict(SV=self.support_vectors_)
+            h.set_model(self._kernel(), self._sv_start, self._dual_coef_, -self._intercept_, **dict(sv, **prob))
+            self._model_set = True
+        return h
+
+    def evaluate(self, X, y=None, file_idxs=None, outputs=('predict',)):
+        """One scoring pass on the GPU over X (NumPy rows or a usc.DeviceFeatures) -> dict of what `outputs` names, and nothing
+        else is computed or downloaded: 'predict' (n) as classes_, 'decision_function' (n, C) sklearn's ovr values ((n) for two
+        classes), 'hinge_loss' (sklearn's, of y against those values), 'predict_proba' (n, C), 'file_proba' (n_files, C) the mean
+        of the rows [s, e) of each file_idxs entry and 'file_predict' its argmax as classes_."""
+        self._check_fitted()
+        outputs = tuple(outputs)
+        unknown = set(outputs) - set(EVALUATE_OUTPUTS)
+        if unknown:
+            raise ValueError('unknown outputs %s; choose from %s' % (sorted(unknown), list(EVALUATE_OUTPUTS)))
+        if 'hinge_loss' in outputs and y is None:
+            raise ValueError("'hinge_loss' needs the labels y")
+        files = None
+        if 'file_proba' in outputs or 'file_predict' in outputs:
+            if file_idxs is None:
+                raise ValueError("'file_proba' and 'file_predict' need file_idxs")
+            files = np.asarray(file_idxs, np.int64).reshape(-1, 2)
+        if not self.probability and set(outputs) & {'predict_proba', 'file_proba', 'file_predict'}:
+            raise ValueError('probability outputs are not available when probability=False')
+        nc = self.classes_.size
+        if 'decision_function' in outputs and nc > 2 and self.decision_function_shape != 'ovr':
+            raise ValueError("evaluate gives sklearn's ovr decision values only; the pair decisions stay on the device")
+        on_device = isinstance(X, DeviceFeatures)
+        if not on_device:
+            X = np.ascontiguousarray(X, np.float32)
+        if len(X.shape) != 2 or X.shape[1] != self.shape_fit_[1]:
+            raise ValueError('X has %s features per sample; expecting %d' % (tuple(X.shape[1:]), self.shape_fit_[1]))
+        n = X.shape[0]
+        labels = None
+        if 'hinge_loss' in outputs:
+            y = np.asarray(y).reshape(-1)
+            if y.size != n:
+                raise ValueError('one label per row is needed')
+            labels = np.clip(np.searchsorted(self.classes_, y), 0, nc - 1)
+            if not np.array_equal(self.classes_[labels], y):
+                raise ValueError('y contains labels not in classes_')
+        if files is not None and (files.size == 0 or files.min() < 0 or files.max() > n or np.any(files[:, 0] >= files[:, 1])):
+            raise ValueError('file_idxs must be non-empty row ranges inside [0, n)')
+        names = {'predict': 'pred', 'decision_function': 'ovr', 'hinge_loss': 'hinge_sum', 'predict_proba': 'proba',
+                 'file_proba': 'file_proba', 'file_predict': 'file_pred'}
+        if n == 0:
+            raise ValueError('no rows to evaluate')
+        h = self._ensure_model()
+        got = h.score(labels=labels, files=files, outputs=tuple(names[k] for k in outputs),
+                      **(dict(feat=X.handle) if on_device else dict(X=X)))
+        out = {k: got[names[k]] for k in outputs}
+        if 'predict' in out:
+            out['predict'] = self.classes_[out['predict']]
+        if 'file_predict' in out:
+            out['file_predict'] = self.classes_[out['file_predict']]
+        if 'hinge_loss' in out:
+            out['hinge_loss'] = out['hinge_loss'] / n
+        return out
+
     def decision_function(self, X):
+        if isinstance(X, DeviceFeatures):
+            return self.evaluate(X, outputs=('decision_function',))['decision_function']
         dec = self._ovo(X)
         nc = self.classes_.size
         if nc == 2:
@@ -321,6 +401,8 @@ class SVC(object):
 
     def predict(self, X):
         """libsvm's one-vs-one vote, ties to the lower class"""
+        if isinstance(X, DeviceFeatures):
+            return self.evaluate(X, outputs=('predict',))['predict']
         dec = self._ovo(X)
         nc = self.classes_.size
         votes = np.zeros((dec.shape[0], nc), np.int64)
@@ -337,6 +419,8 @@ class SVC(object):
         """svm_predict_probability: sigmoid_predict of each pair's decision value, clipped to [1e-7, 1 - 1e-7], then coupled"""
         if not self.probability:
             raise AttributeError('predict_proba is not available when probability=False')
+        if isinstance(X, DeviceFeatures):
+            return self.evaluate(X, outputs=('predict_proba',))['predict_proba']
         return pairwise_coupling(self._ovo(X), self.probA_, self.probB_, self.classes_.size)
 
 
