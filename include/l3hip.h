@@ -504,6 +504,23 @@ int l3_svm_set_data(l3_svm *m, const float *X, int64_t n, int D);
 int l3_svm_fit(l3_svm *m, const l3_svm_kernel *k, double C, double tol, int64_t max_iter, int n_prob, const int64_t *prob_off,
                const int32_t *rows, const int8_t *signs, int q, double *alpha_out, double *rho_out, int64_t *updates_out,
                int32_t *outer_out, double *gap_out);
+/* l3_svm_fit with one box bound per problem, C[p] for problem p (each finite and > 0, else L3_EINVAL): the grid of a parameter
+ * search over C goes through one call, every cost's pair problems and cross-validation sub-problems side by side.  A problem's
+ * result does not depend on what else is in the batch, with one exception that l3_svm_fit shares: the update cap of max_iter = -1
+ * is max(10^7, 100 x the largest problem of the batch).  l3_svm_fit is this call with its scalar broadcast. */
+int l3_svm_fit_costs(l3_svm *m, const l3_svm_kernel *k, const double *C, double tol, int64_t max_iter, int n_prob,
+                     const int64_t *prob_off, const int32_t *rows, const int8_t *signs, int q, double *alpha_out, double *rho_out,
+                     int64_t *updates_out, int32_t *outer_out, double *gap_out);
+/* svm_binary_svc_probability's held-out decision values (svm.cpp) for n_jobs binary models in one launch and one host wait.  Job j
+ * scores the resident rows held_rows[held_off[j] .. held_off[j + 1]) against the support vectors sv_rows[sv_off[j] .. sv_off[j + 1])
+ * (resident rows too): the positives first, the negatives from sv_off[j] + sv_neg[j]; coef holds one coefficient per support vector
+ * (y alpha), rho one value per job.  dec_out holds one value per held-out row, in the order of held_rows, bit-equal to
+ * l3_svm_decision(x_idx = the job's held-out rows, sv_idx = its support vectors, n_class = 2).  A job may have no support vectors on
+ * either side (none at all: dec = -rho) and no held-out rows (it is skipped).  L3_EINVAL for a row outside [0, n), a decreasing
+ * offset or an sv_neg outside its job. */
+int l3_svm_cv_decision(l3_svm *m, const l3_svm_kernel *k, int n_jobs, const int64_t *held_off, const int32_t *held_rows,
+                       const int64_t *sv_off, const int64_t *sv_neg, const int32_t *sv_rows, const double *coef, const double *rho,
+                       double *dec_out);
 /* svm_predict_values (svm.cpp) of n rows, one fused launch per block of rows: dec_out (n, n_class (n_class - 1) / 2) in libsvm's
  * pair order (0,1), (0,2), ..., positive for the first class of the pair.  Rows come as a host matrix X (n, D) or as x_idx into the
  * set_data matrix; support vectors likewise as SV (n_sv, D) or sv_idx.  Support vectors are grouped by class: class c owns
@@ -554,6 +571,13 @@ int l3_op_svm_tail(int device, const double *dec, int64_t n, int n_class, const 
                    const int32_t *labels, const int64_t *files, int64_t n_files, int32_t *pred_out, double *ovr_out,
                    double *hinge_sum_out, double *pair_proba_out, double *proba_out, double *file_proba_out, int32_t *file_pred_out,
                    int32_t *iters_out);
+/* svm.cpp sigmoid_train (Platt's A, B by Newton's method with backtracking; Lin, Lin and Weng) for n_jobs pairs in one launch, one
+ * workgroup per job: job j fits dec[off[j] .. off[j + 1]) (at least one row, finite) against signs (+1 / -1) there.  Float64
+ * throughout; every sum over a job's rows is reduced in a fixed order (strided partials per thread, then a tree), so a job's
+ * result does not depend on the batch it is in.  iters_out (may be NULL): the Newton iterations made, i.e. sigmoid_train's `iter`
+ * when it stopped (100 at the cap). */
+int l3_op_svm_sigmoid_train(int device, int n_jobs, const int64_t *off, const double *dec, const int8_t *signs, double *A_out,
+                            double *B_out, int32_t *iters_out);
 
 /* ---- VGGish baseline features (data/usc/features.py:166-240) --------------------------------------------------------------------
  * extract_vggish_embedding / get_vggish_frames_uniform on the GPU, inference only, fp32: load_audio's resampling to 16 kHz and the

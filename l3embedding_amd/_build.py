@@ -16,7 +16,7 @@ LIBPATH = os.path.join(LIBDIR, 'libl3hip.so')
 # geometry Winograd does not take), mixed precision (halo forward / data gradient, transpose-read weight gradient, the dispatch +
 # fp32-tensor entry points), first layers, BatchNorm / pool, head / loss / Adam, front-end, clip framing, resampling, engine, operator
 # entry points, RCCL, the downstream MLP and SVM classifiers, the VGGish baseline features, training-set augmentation, the
-# classifier's fold preprocessing, the SVM's scoring.
+# classifier's fold preprocessing, the SVM's scoring and sigmoid fits.
 SOURCES = ['conv.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_bf16.hip', 'conv_bf16_halo.hip', 'conv_wgrad_bf16.hip', 'conv_wgrad_wino.hip',
            'conv_first.hip', 'elementwise.hip', 'bn_fused.hip', 'frontend.hip', 'clips.hip', 'resample.hip', 'engine.hip', 'ops.hip',
            'comm.hip', 'mlp.hip', 'svm.hip', 'vggish.hip', 'augment.hip', 'featprep.hip', 'svm_eval.hip']

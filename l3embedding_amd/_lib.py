@@ -171,6 +171,10 @@ SIGNATURES = {
     'l3_svm_set_data': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
     'l3_svm_fit': (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int64, C.c_int] + [C.c_void_p] * 3
                    + [C.c_int] + [C.c_void_p] * 5),
+    'l3_svm_fit_costs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int] + [C.c_void_p] * 3
+                         + [C.c_int] + [C.c_void_p] * 5),
+    'l3_svm_cv_decision': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8),
+    'l3_op_svm_sigmoid_train': (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 6),
     'l3_svm_decision': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_int64, C.c_int] + [C.c_void_p] * 4),
     'l3_op_svm_kernel_rows': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -1240,8 +1244,8 @@ class SVM(object):
         self.n, self.D = x.shape
 
     def fit(self, kernel, problems, cost=1.0, tol=1e-3, max_iter=-1, q=0):
-        """problems: list of (rows, signs) over the set_data rows.  -> (alphas (list of float64 arrays), rho (P,),
-        updates (P,), outer iterations (P,), last gaps (P,))"""
+        """problems: list of (rows, signs) over the set_data rows; cost: the box bound C, one for all or one per problem.
+        -> (alphas (list of float64 arrays), rho (P,), updates (P,), outer iterations (P,), last gaps (P,))"""
         rows = [np.ascontiguousarray(r, np.int32) for r, _ in problems]
         off = np.zeros(len(rows) + 1, np.int64)
         off[1:] = np.cumsum([r.size for r in rows])
@@ -1250,9 +1254,40 @@ class SVM(object):
         P = len(rows)
         alpha, rho = np.empty(int(off[-1]), np.float64), np.empty(P, np.float64)
         upd, outer, gap = np.empty(P, np.int64), np.empty(P, np.int32), np.empty(P, np.float64)
-        check(self.lib.l3_svm_fit(self.h, C.byref(kernel), float(cost), float(tol), int(max_iter), P, _ptr(off), _ptr(r_all),
-                                  _ptr(s_all), int(q), _ptr(alpha), _ptr(rho), _ptr(upd), _ptr(outer), _ptr(gap)))
+        tail = (float(tol), int(max_iter), P, _ptr(off), _ptr(r_all), _ptr(s_all), int(q), _ptr(alpha), _ptr(rho), _ptr(upd),
+                _ptr(outer), _ptr(gap))
+        if np.ndim(cost) == 0:
+            check(self.lib.l3_svm_fit(self.h, C.byref(kernel), float(cost), *tail))
+        else:
+            costs = _f64(cost).reshape(-1)
+            if costs.size != P:
+                raise ValueError('cost must be a scalar or hold one value per problem (%d), not %d' % (P, costs.size))
+            check(self.lib.l3_svm_fit_costs(self.h, C.byref(kernel), _ptr(costs), *tail))
         return [alpha[off[p]:off[p + 1]] for p in range(P)], rho, upd, outer, gap
+
+    def cv_decision(self, kernel, jobs):
+        """the held-out decision values of binary models, all in one launch (l3_svm_cv_decision).  jobs: a list of
+        (held, sv, n_pos, coef, rho): resident rows to score, resident rows of the support vectors (the n_pos positives first),
+        one coefficient per support vector, the model's rho.  -> a list of float64 arrays, one value per held-out row"""
+        J = len(jobs)
+        if J == 0:
+            return []
+        held = [_i32(j[0]).reshape(-1) for j in jobs]
+        sv = [_i32(j[1]).reshape(-1) for j in jobs]
+        coef = [_f64(j[3]).reshape(-1) for j in jobs]
+        if any(c.size != v.size for c, v in zip(coef, sv)):
+            raise ValueError('one coefficient per support vector is needed')
+        hoff, soff = np.zeros(J + 1, np.int64), np.zeros(J + 1, np.int64)
+        hoff[1:] = np.cumsum([a.size for a in held])
+        soff[1:] = np.cumsum([a.size for a in sv])
+        neg = _i64([int(j[2]) for j in jobs])
+        rho = _f64([float(j[4]) for j in jobs])
+        # a buffer of at least one element, so that no pointer is NULL when every job is empty on that side
+        cat = lambda parts, dt: np.concatenate(parts + [np.zeros(1, dt)])
+        out = np.empty(int(hoff[-1]) + 1, np.float64)
+        check(self.lib.l3_svm_cv_decision(self.h, C.byref(kernel), J, _ptr(hoff), _ptr(cat(held, np.int32)), _ptr(soff), _ptr(neg),
+                                          _ptr(cat(sv, np.int32)), _ptr(cat(coef, np.float64)), _ptr(rho), _ptr(out)))
+        return [out[hoff[j]:hoff[j + 1]] for j in range(J)]
 
     def decision(self, kernel, sv_start, coef, rho, X=None, x_idx=None, SV=None, sv_idx=None):
         """libsvm's pairwise decision values (n, n_class (n_class - 1) / 2) of host rows X or resident rows x_idx, against
@@ -1356,6 +1391,24 @@ def op_svm_smo(K, y, alpha, grad, cost=1.0, eps=1e-3, local_rel=0.0, max_updates
     check(load().l3_op_svm_smo(device, _ptr(K), _ptr(y), y.size, float(cost), float(eps), float(local_rel), int(max_updates), _ptr(a),
                                _ptr(g), _ptr(u)))
     return a, int(u[0])
+
+
+def svm_sigmoid_train(device, decs, signs):
+    """svm.cpp sigmoid_train for every (decision values, +1 / -1 labels) pair of the two lists in one launch
+    (l3_op_svm_sigmoid_train) -> (A, B, iters), one entry per pair"""
+    decs = [_f64(d).reshape(-1) for d in decs]
+    signs = [np.ascontiguousarray(v, np.int8).reshape(-1) for v in signs]
+    J = len(decs)
+    if len(signs) != J or any(d.size != v.size for d, v in zip(decs, signs)):
+        raise ValueError('one label per decision value is needed')
+    A, B, it = np.empty(J), np.empty(J), np.empty(J, np.int32)
+    if J == 0:
+        return A, B, it
+    off = np.zeros(J + 1, np.int64)
+    off[1:] = np.cumsum([d.size for d in decs])
+    check(load().l3_op_svm_sigmoid_train(int(device), J, _ptr(off), _ptr(np.concatenate(decs)), _ptr(np.concatenate(signs)),
+                                         _ptr(A), _ptr(B), _ptr(it)))
+    return A, B, it
 
 
 def op_svm_tail(dec, n_classes, probA=None, probB=None, labels=None, files=None,

@@ -10,7 +10,9 @@ it.  Deviations from the reference, all deliberate:
   * the random forest and StratifiedShuffleSplit (sklearn on the host) are not built: they raise;
   * the SVM (train_svm, classifier/train.py:79-166) trains on the GPU (svm.py, csrc/svm.hip); its probability estimates draw the
     cross-validation fold permutation from np.random.RandomState(random_state) as the MLP's shuffle does (libsvm uses rand()),
-    and the model is pickled with `pickle` (the reference uses joblib).  train() still runs only the MLP.
+    and the model is pickled with `pickle` (the reference uses joblib).  train() still runs only the MLP; train_svm_fold is
+    the reference's train(model_type='svm'), and train_svm_search its parameter search over C with the whole grid fitted in
+    one pass on the GPU (svm.fit_grid).
 """
 import datetime
 import getpass
@@ -23,6 +25,7 @@ from itertools import product
 import numpy as np
 
 from . import _lib, callbacks, kerasfile
+from . import svm as _svm
 from .svm import SVC, hinge_loss  # noqa: F401  (re-exported: the reference imports them into classifier/train.py)
 from .usc import DeviceFeatures, get_split, preprocess_split_data
 
@@ -359,7 +362,11 @@ def _train_svm_on_device(train_data, valid_data, test_data, model_dir, C, kernel
     clf.fit(train_data['features'], train_data['labels'])
     LOGGER.info('Saving model...')
     _dump(os.path.join(model_dir, 'model.pkl'), clf)
+    return (clf,) + _svm_metrics_on_device(clf, train_data, valid_data, test_data, num_classes)
 
+
+def _svm_metrics_on_device(clf, train_data, valid_data, test_data, num_classes):
+    """-> (train_metrics, valid_metrics, test_metrics) of a fitted SVC, one SVC.evaluate per split"""
     metrics = []
     for name, data in (('Train', train_data), ('Valid', valid_data)):
         if not data:
@@ -374,7 +381,7 @@ def _train_svm_on_device(train_data, valid_data, test_data, model_dir, C, kernel
     if test_data:
         per_file = clf.evaluate(test_data['features'], file_idxs=test_data['file_idxs'], outputs=('file_predict',))['file_predict']
         test_metrics = compute_metrics(test_data['labels'], per_file, num_classes=num_classes)
-    return clf, metrics[0], metrics[1], test_metrics
+    return metrics[0], metrics[1], test_metrics
 
 
 def _on_host(data):
@@ -419,6 +426,52 @@ def train_param_search(train_data, valid_data, test_data, model_dir, train_func,
     return model, train_metrics, valid_metrics, test_metrics
 
 
+SVM_SEARCH_CS = (0.1, 1, 10, 100, 1000)        # classifier/train.py:609
+
+
+def train_svm_search(train_data, valid_data, test_data, model_dir, Cs=SVM_SEARCH_CS, train_with_valid=False, platt='device', C=None,
+                     kernel='rbf', num_classes=10, tol=0.001, max_iterations=-1, verbose=False, random_state=12345678,
+                     max_entries=None, **kwargs):
+    """train_param_search(..., train_func=train_svm, search_space={'C': Cs}, evaluate_on_device=True) with the grid fitted in one
+    pass: one svm.fit_grid over the training split (NumPy rows or usc.DeviceFeatures, resident once), one SVC.evaluate per split
+    and model, the cost with the best validation accuracy (the first one on ties), and with train_with_valid the retrain on
+    train + valid shuffled together (merged on the host, np.random.permutation as there).  -> the same tuple (model, train_metrics,
+    valid_metrics, test_metrics) with the same search records.  platt: svm.fit_grid's ('host': Platt's sigmoids as SVC.fit
+    fits them, so every number equals that of the separate fits).  model_dir/model.pkl holds the returned model (the loop over
+    train_svm leaves the one it fitted last there).  C is ignored (the search sets it); the other arguments are train_svm's."""
+    if not valid_data:
+        raise ValueError(NO_SSS)
+    Cs = list(Cs)
+    params = dict(probability=True, kernel=kernel, max_iter=max_iterations, tol=tol, random_state=random_state, verbose=verbose)
+    LOGGER.info('Fitting the grid C = %s', Cs)
+    models = _svm.fit_grid(train_data['features'], train_data['labels'], Cs, platt=platt, max_entries=max_entries, **params)
+    runs = []                       # (point, model, train metrics, valid metrics, test metrics)
+    for c, clf in zip(Cs, models):
+        LOGGER.info('Search point %s', {'C': c})
+        runs.append(((c,), clf) + _svm_metrics_on_device(clf, train_data, valid_data, test_data, num_classes))
+    chosen = runs[int(np.argmax([run[3]['accuracy'] for run in runs]))]
+    point = chosen[0]
+    LOGGER.info('Chosen %s (validation accuracy %s)', {'C': point[0]}, chosen[3]['accuracy'])
+
+    if train_with_valid:
+        train_data, valid_data = _on_host(train_data), _on_host(valid_data)
+        merged_labels = np.concatenate((train_data['labels'], valid_data['labels']))
+        mix = np.random.permutation(merged_labels.size)
+        merged = {'features': np.vstack((train_data['features'], valid_data['features']))[mix], 'labels': merged_labels[mix]}
+        model = _svm.fit_grid(merged['features'], merged['labels'], [point[0]], platt=platt, max_entries=max_entries, **params)[0]
+        train_metrics, _, test_metrics = _svm_metrics_on_device(model, merged, None, test_data, num_classes)
+    else:
+        model, train_metrics, test_metrics = chosen[1], dict(chosen[2]), chosen[4]
+    LOGGER.info('Saving model...')
+    _dump(os.path.join(model_dir, 'model.pkl'), model)
+
+    search_record = {'search_params': ['C'], 'search_params_best_values': point}
+    train_metrics.update(search_record, search={run[0]: run[2] for run in runs})
+    valid_metrics = dict(chosen[3])
+    valid_metrics.update(search_record, search={run[0]: run[3] for run in runs})
+    return model, train_metrics, valid_metrics, test_metrics
+
+
 def _dataset_of(features_dir):
     """'.../features/us8k/l3/...' -> ('us8k', 'us8k/l3/...'): the path after the last 'features/' and its first part"""
     at = features_dir.rindex('features')
@@ -431,23 +484,12 @@ def _dump(path, obj):
         pk.dump(obj, fh, protocol=pk.HIGHEST_PROTOCOL)
 
 
-def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='framewise', train_batch_size=64, patience=20,
-          random_state=20171021, parameter_search=False, parameter_search_valid_fold=True, parameter_search_valid_ratio=0.15,
-          parameter_search_train_with_valid=False, gsheet_id=None, google_dev_app_name=None, verbose=False, non_overlap=False,
-          non_overlap_chunk_size=10, use_min_max=False, preprocess_device=None, **model_args):
-    """classifier/train.py:495-709 for model_type='mlp': one cross-validation fold (fold_num is 1-based) of the features under
-    `features_dir` (its path names the dataset after 'features/'), written to
-    <output_dir>/classifier/<features desc>/<mode>/<overlap>/<min-max>/mlp/fold<N>/<timestamp>/: config.json,
-    min_max_scaler.pkl, stdizer.pkl, model.h5, history_checkpoint.pkl, history_csvlog.csv, results.pkl.
-    preprocess_device: a GPU index preprocesses the folds on that GPU (usc.preprocess_split_data(device=...)) and, without a
-    parameter search, hands them to the MLP there; config.json names it only when it is set.
-    -> that directory."""
-    if model_type != 'mlp':
-        raise ValueError(ONLY_MLP.format(model_type))
-    if parameter_search and not parameter_search_valid_fold:
-        raise ValueError(NO_SSS)
-    if gsheet_id:
-        LOGGER.warning('Google Sheets logging is not built; gsheet_id ignored')
+def _start_fold(features_dir, output_dir, fold_num, model_type, feature_mode, train_batch_size, patience, random_state,
+                parameter_search, parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid,
+                gsheet_id, google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device,
+                model_args):
+    """what a fold of any model type begins with (classifier/train.py:495-603): the run's directory, config.json, the fold's
+    splits preprocessed, the two scalers pickled -> (model_dir, dataset, splits)"""
     dataset, desc = _dataset_of(features_dir)
     if dataset not in DATASET_NUM_CLASSES:
         raise ValueError('the features directory must name a dataset right after "features/" (one of {})'.format(
@@ -484,6 +526,31 @@ def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='fr
     for name, scaler in zip(('min_max_scaler.pkl', 'stdizer.pkl'), scalers):
         _dump(os.path.join(model_dir, name), scaler)
 
+    return model_dir, dataset, splits
+
+
+def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='framewise', train_batch_size=64, patience=20,
+          random_state=20171021, parameter_search=False, parameter_search_valid_fold=True, parameter_search_valid_ratio=0.15,
+          parameter_search_train_with_valid=False, gsheet_id=None, google_dev_app_name=None, verbose=False, non_overlap=False,
+          non_overlap_chunk_size=10, use_min_max=False, preprocess_device=None, **model_args):
+    """classifier/train.py:495-709 for model_type='mlp': one cross-validation fold (fold_num is 1-based) of the features under
+    `features_dir` (its path names the dataset after 'features/'), written to
+    <output_dir>/classifier/<features desc>/<mode>/<overlap>/<min-max>/mlp/fold<N>/<timestamp>/: config.json,
+    min_max_scaler.pkl, stdizer.pkl, model.h5, history_checkpoint.pkl, history_csvlog.csv, results.pkl.
+    preprocess_device: a GPU index preprocesses the folds on that GPU (usc.preprocess_split_data(device=...)) and, without a
+    parameter search, hands them to the MLP there; config.json names it only when it is set.
+    -> that directory."""
+    if model_type != 'mlp':
+        raise ValueError(ONLY_MLP.format(model_type))
+    if parameter_search and not parameter_search_valid_fold:
+        raise ValueError(NO_SSS)
+    if gsheet_id:
+        LOGGER.warning('Google Sheets logging is not built; gsheet_id ignored')
+    model_dir, dataset, splits = _start_fold(
+        features_dir, output_dir, fold_num, model_type, feature_mode, train_batch_size, patience, random_state, parameter_search,
+        parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id, google_dev_app_name,
+        verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args)
+
     common = dict(batch_size=train_batch_size, patience=patience, random_state=random_state,
                   num_classes=DATASET_NUM_CLASSES[dataset], verbose=verbose)
     if parameter_search:
@@ -494,6 +561,38 @@ def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='fr
                                      train_with_valid=parameter_search_train_with_valid, **dict(common, **model_args))
     else:
         outcome = train_mlp(*splits, model_dir, **dict(common, **model_args))
+    _, train_metrics, valid_metrics, test_metrics = outcome
+    _dump(os.path.join(model_dir, 'results.pkl'), {'train': train_metrics, 'valid': valid_metrics, 'test': test_metrics})
+    LOGGER.info('Fold %d done: results in %s', fold_num, model_dir)
+    return model_dir
+
+
+def train_svm_fold(features_dir, output_dir, fold_num, feature_mode='framewise', train_batch_size=64, patience=20,
+                   random_state=20171021, parameter_search=False, parameter_search_valid_fold=True,
+                   parameter_search_valid_ratio=0.15, parameter_search_train_with_valid=False, gsheet_id=None,
+                   google_dev_app_name=None, verbose=False, non_overlap=False, non_overlap_chunk_size=10, use_min_max=False,
+                   preprocess_device=None, platt='device', **model_args):
+    """classifier/train.py:495-709 for model_type='svm': one cross-validation fold as train() runs it for the MLP, written to
+    <output_dir>/classifier/<features desc>/<mode>/<overlap>/<min-max>/svm/fold<N>/<timestamp>/: config.json, min_max_scaler.pkl,
+    stdizer.pkl, model.pkl, results.pkl.  preprocess_device: a GPU index preprocesses the folds on that GPU and the SVM is
+    fitted and scored from the splits there (nothing is downloaded but the results); config.json names it only when it is set.
+    parameter_search: train_svm_search over C = 0.1 ... 1000 (platt: its sigmoid fit, 'device' or 'host'); else one train_svm with
+    model_args (C, kernel, tol, max_iterations).  train_batch_size and patience are recorded as the reference records them; the
+    SVM does not use them.  -> that directory."""
+    if parameter_search and not parameter_search_valid_fold:
+        raise ValueError(NO_SSS)
+    if gsheet_id:
+        LOGGER.warning('Google Sheets logging is not built; gsheet_id ignored')
+    model_dir, dataset, splits = _start_fold(
+        features_dir, output_dir, fold_num, 'svm', feature_mode, train_batch_size, patience, random_state, parameter_search,
+        parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id, google_dev_app_name,
+        verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args)
+    common = dict(random_state=random_state, num_classes=DATASET_NUM_CLASSES[dataset], verbose=verbose)
+    if parameter_search:
+        outcome = train_svm_search(*splits, model_dir, train_with_valid=parameter_search_train_with_valid, platt=platt,
+                                   **dict(common, **model_args))
+    else:
+        outcome = train_svm(*splits, model_dir, evaluate_on_device=True, **dict(common, **model_args))
     _, train_metrics, valid_metrics, test_metrics = outcome
     _dump(os.path.join(model_dir, 'results.pkl'), {'train': train_metrics, 'valid': valid_metrics, 'test': test_metrics})
     LOGGER.info('Fold %d done: results in %s', fold_num, model_dir)

@@ -12,6 +12,9 @@
 //   svm_grad     grad_t += sum_s dalpha_s y_s y_t K[s, t] in float64 from the rows svm_rows wrote
 // then one host synchronisation for all problems (which are still active).  Prediction is one fused launch per class block:
 // K(X_test, SV) tiles in registers times the class's dual coefficients, the n_test x n_SV kernel matrix never reaching HBM.
+// Every problem carries its own box bound C (l3_svm_fit_costs), so the grid of a parameter search over C is one batch.  The held-out
+// decision values of probability estimates come from one launch for all cross-validation sub-problems (svm_cv_decision_kernel: one
+// wave per sub-problem and 32 held-out rows, the arithmetic of the prediction launch at two classes).
 // No float atomics anywhere: the same inputs give bit-identical results.
 #include <hip/hip_runtime.h>
 
@@ -197,7 +200,8 @@ struct SvmState {
     double *gap, *rho;
     float* krow;                 // problem p: q * off[p], row w at w * n_p + t
     const int64_t *tile32, *tile256;
-    double C, tol, local_rel;
+    const double* C;             // the box bound of each problem
+    double tol, local_rel;
     long long max_updates;       // per problem (-1: libsvm's cap, resolved on the host)
     int P, q, outer_cap;
 };
@@ -221,15 +225,16 @@ __global__ __launch_bounds__(SEL_NT) void svm_select_kernel(SvmState s) {
     // picks leave in the order (key desc, index asc) for I_up and (key asc, index asc) for I_low; the previous pick bounds the next
     double pu = INFINITY, pl = -INFINITY;
     int pui = -1, pli = -1, nu = 0, nl = 0;
+    const double Cp = s.C[p];
     for (int rnd = 0; rnd < half; ++rnd) {
         double bu = -INFINITY, bl = -INFINITY;       // bl holds -key so that both sides reduce as argmax
         int bui = -1, bli = -1;
         for (int t = threadIdx.x; t < n; t += SEL_NT) {
             const signed char yt = Y[t];
             const double a = A[t], key = -(double)yt * G[t];
-            if (pui != -2 && in_up(yt, a, s.C) && (key < pu || (key == pu && t > pui)))
+            if (pui != -2 && in_up(yt, a, Cp) && (key < pu || (key == pu && t > pui)))
                 if (bui < 0 || key > bu || (key == bu && t < bui)) bu = key, bui = t;
-            if (pli != -2 && in_low(yt, a, s.C) && (key > pl || (key == pl && t > pli)))
+            if (pli != -2 && in_low(yt, a, Cp) && (key > pl || (key == pl && t > pli)))
                 if (bli < 0 || -key > bl || (-key == bl && t < bli)) bl = -key, bli = t;
         }
         // argmax_pair prefers the larger index on equal keys; the scan above kept the smaller, so reduce on -index
@@ -291,7 +296,8 @@ struct SvmSmoArgs {
     double* dal;                  // out: alpha change per variable
     long long* updates;           // in / out, per problem
     int* active;                  // may be NULL (operator)
-    double C, eps, local_rel;
+    const double* C;              // the box bound of each problem
+    double eps, local_rel;
     long long max_updates;
     int q, ldk_is_n;
 };
@@ -324,21 +330,22 @@ __global__ __launch_bounds__(SMO_NT) void svm_smo_kernel(SvmSmoArgs a) {
     if (kv) Av[k] = ak;
     __syncthreads();
     const double Ckk = kv ? (double)Kb[k * SVM_QMAX + k] : 0.0;
+    const double Cp = a.C[p];
     const long long cap = a.max_updates - a.updates[p];
     long long upd = 0;
     double local_eps = a.eps;
     for (int it = 0;; ++it) {
         // i = argmax over I_up of -y G
-        double vi = (kv && in_up(yk, ak, a.C)) ? -(double)yk * gk : -INFINITY;
-        int ii = (kv && in_up(yk, ak, a.C)) ? k : -1;
+        double vi = (kv && in_up(yk, ak, Cp)) ? -(double)yk * gk : -INFINITY;
+        int ii = (kv && in_up(yk, ak, Cp)) ? k : -1;
         block_argmax<SMO_NT>(vi, ii, sv, si);
         const double Gmax = vi;
         // j: Gmax2 = max over I_low of y G; the second-order choice among I_low with grad_diff > 0
-        double g2 = (kv && in_low(yk, ak, a.C)) ? (double)yk * gk : -INFINITY;
-        int g2i = (kv && in_low(yk, ak, a.C)) ? k : -1;
+        double g2 = (kv && in_low(yk, ak, Cp)) ? (double)yk * gk : -INFINITY;
+        int g2i = (kv && in_low(yk, ak, Cp)) ? k : -1;
         double ob = -INFINITY;      // -obj_diff, as argmax
         int oj = -1;
-        if (ii >= 0 && kv && in_low(yk, ak, a.C)) {
+        if (ii >= 0 && kv && in_low(yk, ak, Cp)) {
             const double gd = Gmax + (double)yk * gk;
             if (gd > 0.0) {
                 double quad = (double)Kb[ii * SVM_QMAX + ii] + Ckk - 2.0 * (double)Kb[ii * SVM_QMAX + k];
@@ -361,7 +368,7 @@ __global__ __launch_bounds__(SMO_NT) void svm_smo_kernel(SvmSmoArgs a) {
             const signed char yi = a.y[off + wl[i]], yj = a.y[off + wl[j]];
             const double Gi = gij[0], Gj = gij[1];
             double ai = Av[i], aj = Av[j];
-            const double C = a.C;
+            const double C = Cp;
             if (yi != yj) {
                 double quad = Kii + Kjj + 2.0 * (-(Kij));       // QD_i + QD_j + 2 Q_ij, Q_ij = y_i y_j K_ij = -K_ij
                 if (quad <= 0.0) quad = SVM_TAU;
@@ -466,12 +473,13 @@ __global__ __launch_bounds__(256) void svm_rho_kernel(SvmState s) {
     const int p = blockIdx.x;
     const int64_t off = s.off[p];
     const int n = (int)(s.off[p + 1] - off);
+    const double Cp = s.C[p];
     double ub = INFINITY, lb = -INFINITY, sum = 0.0;
     long long nf = 0;
     for (int t = threadIdx.x; t < n; t += 256) {
         const signed char yt = s.y[off + t];
         const double a = s.alpha[off + t], yG = (double)yt * s.grad[off + t];
-        if (a >= s.C) {
+        if (a >= Cp) {
             if (yt < 0) ub = fmin(ub, yG); else lb = fmax(lb, yG);
         } else if (a <= 0.0) {
             if (yt > 0) ub = fmin(ub, yG); else lb = fmax(lb, yG);
@@ -594,6 +602,100 @@ __global__ void svm_pairs_kernel(const double* S, const double* rho, int64_t n, 
     const int j = i + 1 + p;
     const int pp = (int)(e - m * P);
     dec[e] = S[(m * ncls + i) * R + (j - 1)] + S[(m * ncls + j) * R + i] - rho[pp];
+}
+
+// ---- held-out decision values of many binary models in one launch -------------------------------------------------------------
+// Job j is one binary model (a cross-validation sub-problem of probability estimates) scored on its held-out rows.  One wave per
+// (job, 32 held-out rows), found through the prefix of tiles as svm_rows_kernel finds its problem.  The arithmetic is
+// svm_decision_kernel followed by svm_pairs_kernel at two classes: the same 32 x 32 tiles and k-steps, the same kfun, the positives'
+// and the negatives' sums each in float64 in support-vector order (tiles start at each side's first support vector), then
+// S_pos + S_neg - rho.  Every row is an index into the resident matrix.
+struct SvmCvArgs {
+    const float *x, *xx;           // the resident rows and their squared norms
+    const int64_t* held_off;       // job j's held-out rows: held[held_off[j] .. held_off[j + 1])
+    const int* held;
+    const int64_t* sv_off;         // its support vectors: sv[sv_off[j] .. sv_off[j + 1]), the negatives from sv_off[j] + sv_neg[j]
+    const int64_t* sv_neg;
+    const int* sv;
+    const double* coef;            // one per support vector
+    const double* rho;             // one per job
+    const int64_t* tile_off;       // prefix of ceil(held-out rows / 32) per job
+    double* dec;                   // one per held-out row
+    int64_t tile0;                 // the first tile of this launch
+    int J, D, vec;
+    SvmKern k;
+};
+
+__global__ __launch_bounds__(64) void svm_cv_decision_kernel(SvmCvArgs a) {
+    __shared__ float T[32 * 33];
+    const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+    const int64_t wv = a.tile0 + blockIdx.x;
+    if (wv >= a.tile_off[a.J]) return;
+    int lo = 0, hi = a.J - 1;                 // the job whose tiles hold wv (a job without held-out rows owns none)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.tile_off[mid] <= wv) lo = mid; else hi = mid - 1;
+    }
+    const int j = lo;
+    const int64_t h0 = a.held_off[j];
+    const int64_t n = a.held_off[j + 1] - h0;
+    const int64_t rt = wv - a.tile_off[j];
+    const int* held = a.held + h0;
+    const int64_t m = rt * 32 + r;
+    const bool mv = m < n;
+    const int64_t mg = mv ? held[m] : 0;
+    const float* xr = a.x + mg * a.D;
+    double side[2] = {0.0, 0.0};              // lanes 0 .. 31: row `lane` of the tile
+    for (int c = 0; c < 2; ++c) {
+        const int64_t s0 = c == 0 ? a.sv_off[j] : a.sv_off[j] + a.sv_neg[j];
+        const int64_t s1 = c == 0 ? a.sv_off[j] + a.sv_neg[j] : a.sv_off[j + 1];
+        double acc64 = 0.0;
+        for (int64_t sb = s0; sb < s1; sb += 32) {
+            const int64_t sidx = sb + r;
+            const bool sv_ok = sidx < s1;
+            const int64_t sg = sv_ok ? a.sv[sidx] : 0;
+            const float* svr = a.x + sg * a.D;
+            f32x16 acc = {};
+            for (int k0 = 0; k0 < a.D; k0 += 8) {
+                const int kk = k0 + 4 * h;
+                float av[4], bv[4];
+                if (a.vec && kk + 4 <= a.D) {
+                    const float4 qa = mv ? *reinterpret_cast<const float4*>(xr + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    const float4 qb = sv_ok ? *reinterpret_cast<const float4*>(svr + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    av[0] = qa.x, av[1] = qa.y, av[2] = qa.z, av[3] = qa.w;
+                    bv[0] = qb.x, bv[1] = qb.y, bv[2] = qb.z, bv[3] = qb.w;
+                } else {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        av[t] = (mv && kk + t < a.D) ? xr[kk + t] : 0.f;
+                        bv[t] = (sv_ok && kk + t < a.D) ? svr[kk + t] : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bv[t], acc, 0, 0, 0);
+            }
+            const float ysn = sv_ok ? a.xx[sg] : 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int row = mfma_row(i, h);
+                const int64_t mr = rt * 32 + row;
+                float kvv = 0.f;
+                if (sv_ok && mr < n) kvv = kfun(a.k, acc[i], a.xx[held[mr]], ysn);
+                T[row * 33 + r] = kvv;
+            }
+            __syncthreads();
+            const int ns = (int)min<int64_t>(32, s1 - sb);
+            if (lane < 32) {
+                const double* cf = a.coef + sb;
+                double s = acc64;
+                for (int t = 0; t < ns; ++t) s += (double)T[lane * 33 + t] * cf[t];
+                acc64 = s;
+            }
+            __syncthreads();
+        }
+        side[c] = acc64;
+    }
+    if (lane < 32 && rt * 32 + lane < n) a.dec[h0 + rt * 32 + lane] = side[0] + side[1] - a.rho[j];
 }
 
 // out (n, D) = x[idx]: the support vectors of a resident model, and the rows l3_svm_get_rows downloads
@@ -720,12 +822,23 @@ int l3_svm_set_data(l3_svm* m, const float* X, int64_t n, int D) {
 int l3_svm_fit(l3_svm* m, const l3_svm_kernel* kp, double C, double tol, int64_t max_iter, int n_prob, const int64_t* prob_off,
                const int32_t* rows, const int8_t* signs, int q, double* alpha_out, double* rho_out, int64_t* updates_out,
                int32_t* outer_out, double* gap_out) {
+    if (n_prob <= 0) return fail(L3_EINVAL, "l3_svm_fit: no problems");
+    const std::vector<double> costs((size_t)n_prob, C);
+    return l3_svm_fit_costs(m, kp, costs.data(), tol, max_iter, n_prob, prob_off, rows, signs, q, alpha_out, rho_out, updates_out,
+                            outer_out, gap_out);
+}
+
+int l3_svm_fit_costs(l3_svm* m, const l3_svm_kernel* kp, const double* C, double tol, int64_t max_iter, int n_prob,
+                     const int64_t* prob_off, const int32_t* rows, const int8_t* signs, int q, double* alpha_out, double* rho_out,
+                     int64_t* updates_out, int32_t* outer_out, double* gap_out) {
     std::string why;
-    if (!m || !prob_off || !rows || !signs || !alpha_out || !rho_out) return fail(L3_EINVAL, "l3_svm_fit: NULL argument");
+    if (!m || !C || !prob_off || !rows || !signs || !alpha_out || !rho_out) return fail(L3_EINVAL, "l3_svm_fit: NULL argument");
     if (!kern_ok(kp, &why)) return fail(L3_EINVAL, "l3_svm_fit: " + why);
     if (m->n <= 0) return fail(L3_ESTATE, "l3_svm_fit: no training data (l3_svm_set_data)");
-    if (!(C > 0.0) || !std::isfinite(C) || !(tol > 0.0)) return fail(L3_EINVAL, "l3_svm_fit: need C > 0 and tol > 0");
     if (n_prob <= 0) return fail(L3_EINVAL, "l3_svm_fit: no problems");
+    if (!(tol > 0.0)) return fail(L3_EINVAL, "l3_svm_fit: need C > 0 and tol > 0");
+    for (int p = 0; p < n_prob; ++p)
+        if (!(C[p] > 0.0) || !std::isfinite(C[p])) return fail(L3_EINVAL, "l3_svm_fit: need C > 0 and tol > 0");
     if (q == 0) q = L3_SVM_DEFAULT_WS;
     if (q < 2 || q > SVM_QMAX || (q & 1)) return fail(L3_EINVAL, "l3_svm_fit: working-set size must be even, in [2, 128]");
     if (prob_off[0] != 0) return fail(L3_EINVAL, "l3_svm_fit: prob_off[0] must be 0");
@@ -753,8 +866,9 @@ int l3_svm_fit(l3_svm* m, const l3_svm_kernel* kp, double C, double tol, int64_t
     st.gap = b.alloc<double>(n_prob), st.rho = b.alloc<double>(n_prob);
     st.krow = b.alloc<float>(total * q);
     st.tile32 = b.put(t32.data(), n_prob + 1, m->s), st.tile256 = b.put(t256.data(), n_prob + 1, m->s);
+    st.C = b.put(C, n_prob, m->s);
     if (!b.ok()) return fail(L3_ENOMEM, "l3_svm_fit: device allocation failed (" + std::to_string(total * q * 4) + " bytes of kernel rows)");
-    st.C = C, st.tol = tol, st.local_rel = L3_SVM_LOCAL_REL, st.P = n_prob, st.q = q;
+    st.tol = tol, st.local_rel = L3_SVM_LOCAL_REL, st.P = n_prob, st.q = q;
     // libsvm's cap when max_iter is -1: max(10^7, 100 l) updates; the largest problem sets it for all
     int64_t nmax = 0;
     for (int p = 0; p < n_prob; ++p) nmax = std::max(nmax, off[p + 1] - off[p]);
@@ -767,7 +881,7 @@ int l3_svm_fit(l3_svm* m, const l3_svm_kernel* kp, double C, double tol, int64_t
     ra.active = st.active, ra.out = st.krow, ra.P = n_prob, ra.rstride = q, ra.D = m->D, ra.vec = vec_ok(m->x, m->D), ra.k = to_kern(kp);
     SvmSmoArgs sa{};
     sa.K = st.krow, sa.off = st.off, sa.wsl = st.wsl, sa.nws = st.nws, sa.y = st.y, sa.alpha = st.alpha, sa.grad = st.grad;
-    sa.dal = st.dal, sa.updates = st.updates, sa.active = st.active, sa.C = C, sa.eps = tol, sa.local_rel = L3_SVM_LOCAL_REL;
+    sa.dal = st.dal, sa.updates = st.updates, sa.active = st.active, sa.C = st.C, sa.eps = tol, sa.local_rel = L3_SVM_LOCAL_REL;
     sa.max_updates = st.max_updates, sa.q = q, sa.ldk_is_n = 1;
     std::vector<int> act(n_prob);
     for (;;) {
@@ -862,6 +976,61 @@ int l3_svm_decision(l3_svm* m, const l3_svm_kernel* kp, const float* X, const in
     if (hipMemcpyAsync(dec_out, dec, (size_t)n * P * sizeof(double), hipMemcpyDeviceToHost, m->s) != hipSuccess ||
         hipStreamSynchronize(m->s) != hipSuccess)
         return fail(L3_EHIP, "l3_svm_decision: HIP error");
+    return L3_OK;
+}
+
+int l3_svm_cv_decision(l3_svm* m, const l3_svm_kernel* kp, int n_jobs, const int64_t* held_off, const int32_t* held_rows,
+                       const int64_t* sv_off, const int64_t* sv_neg, const int32_t* sv_rows, const double* coef, const double* rho,
+                       double* dec_out) {
+    std::string why;
+    if (!m || !held_off || !held_rows || !sv_off || !sv_neg || !sv_rows || !coef || !rho || !dec_out)
+        return fail(L3_EINVAL, "l3_svm_cv_decision: NULL argument");
+    if (!kern_ok(kp, &why)) return fail(L3_EINVAL, "l3_svm_cv_decision: " + why);
+    if (m->n <= 0) return fail(L3_ESTATE, "l3_svm_cv_decision: no resident matrix (l3_svm_set_data)");
+    if (n_jobs <= 0) return fail(L3_EINVAL, "l3_svm_cv_decision: no jobs");
+    if (held_off[0] != 0 || sv_off[0] != 0) return fail(L3_EINVAL, "l3_svm_cv_decision: held_off[0] and sv_off[0] must be 0");
+    for (int j = 0; j < n_jobs; ++j) {
+        if (held_off[j + 1] < held_off[j] || sv_off[j + 1] < sv_off[j])
+            return fail(L3_EINVAL, "l3_svm_cv_decision: offsets of job " + std::to_string(j) + " decrease");
+        if (sv_neg[j] < 0 || sv_neg[j] > sv_off[j + 1] - sv_off[j])
+            return fail(L3_EINVAL, "l3_svm_cv_decision: sv_neg of job " + std::to_string(j) + " lies outside its support vectors");
+    }
+    const int64_t n_held = held_off[n_jobs], n_sv = sv_off[n_jobs];
+    for (int64_t i = 0; i < n_held; ++i)
+        if (held_rows[i] < 0 || held_rows[i] >= m->n)
+            return fail(L3_EINVAL, "l3_svm_cv_decision: held_rows[" + std::to_string(i) + "] outside [0, n)");
+    for (int64_t i = 0; i < n_sv; ++i)
+        if (sv_rows[i] < 0 || sv_rows[i] >= m->n)
+            return fail(L3_EINVAL, "l3_svm_cv_decision: sv_rows[" + std::to_string(i) + "] outside [0, n)");
+    if (n_held == 0) return L3_OK;
+    (void)hipSetDevice(m->device);
+    const std::vector<int64_t> hoff(held_off, held_off + n_jobs + 1);
+    std::vector<int64_t> tiles;
+    const int64_t n_tiles = prefix_tiles(hoff, 32, &tiles);
+    DeviceBufs b;
+    SvmCvArgs a{};
+    a.x = m->x, a.xx = m->xx;
+    a.held_off = b.put(held_off, n_jobs + 1, m->s), a.held = b.put(held_rows, n_held, m->s);
+    a.sv_off = b.put(sv_off, n_jobs + 1, m->s), a.sv_neg = b.put(sv_neg, n_jobs, m->s), a.sv = b.put(sv_rows, n_sv, m->s);
+    a.coef = b.put(coef, n_sv, m->s), a.rho = b.put(rho, n_jobs, m->s);
+    a.tile_off = b.put(tiles.data(), n_jobs + 1, m->s);
+    a.dec = b.alloc<double>(n_held);
+    if (!b.ok()) {
+        (void)hipStreamSynchronize(m->s);       // copies from the caller's buffers may still be queued
+        return fail(L3_ENOMEM, "l3_svm_cv_decision: device allocation failed");
+    }
+    a.J = n_jobs, a.D = m->D, a.vec = vec_ok(m->x, m->D), a.k = to_kern(kp);
+    // one launch; more only where the tiles outnumber a grid dimension
+    const int64_t grid_max = 0x7fffffff;
+    for (int64_t t0 = 0; t0 < n_tiles; t0 += grid_max) {
+        a.tile0 = t0;
+        hipLaunchKernelGGL(svm_cv_decision_kernel, dim3((unsigned)std::min(grid_max, n_tiles - t0)), dim3(64), 0, m->s, a);
+    }
+    const bool ok = hipGetLastError() == hipSuccess &&
+                    hipMemcpyAsync(dec_out, a.dec, (size_t)n_held * sizeof(double), hipMemcpyDeviceToHost, m->s) == hipSuccess;
+    // the one host wait of the call
+    const bool done = hipStreamSynchronize(m->s) == hipSuccess;
+    if (!ok || !done) return fail(L3_EHIP, "l3_svm_cv_decision: HIP error");
     return L3_OK;
 }
 
@@ -1121,8 +1290,9 @@ int l3_op_svm_smo(int device, const float* K, const int8_t* y, int q, double C, 
     sa.dal = b.alloc<double>(q);
     long long* du = b.put(&zero, 1, s);
     sa.updates = du;
+    sa.C = b.put(&C, 1, s);
     if (!b.ok()) return fail(L3_ENOMEM, "l3_op_svm_smo: device allocation failed");
-    sa.active = nullptr, sa.C = C, sa.eps = eps, sa.local_rel = local_rel;
+    sa.active = nullptr, sa.eps = eps, sa.local_rel = local_rel;
     sa.max_updates = max_updates > 0 ? max_updates : (long long)1 << 62;
     sa.q = q, sa.ldk_is_n = 1;
     hipLaunchKernelGGL(svm_smo_kernel, dim3(1), dim3(SMO_NT), 0, s, sa);

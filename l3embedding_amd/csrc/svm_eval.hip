@@ -7,6 +7,7 @@
 //                          multiclass_probability operation for operation (tests/svm_ref.multiclass_probability is its restatement)
 //   svm_file_mean_kernel   one wave per file: the row-order float64 sum of its rows' probabilities / count, argmax to the lower class
 //   svm_chunk_sum_kernel   the hinge terms of a call in chunks of 256 rows in row order, then the chunk sums in chunk order
+//   svm_sigmoid_train_kernel   svm.cpp sigmoid_train (Platt's A, B) of every pair of a fit at once, one workgroup per pair
 // Everything is float64 and rounded operation by operation (no contraction), no float atomics: the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 
@@ -218,6 +219,113 @@ __global__ void svm_chunk_sum_kernel(const double* in, int64_t n, int64_t chunk,
     out[b] = sum;
 }
 
+// ---- svm.cpp sigmoid_train for many pairs at once -------------------------------------------------------------------------------
+// One workgroup per job (a pair's cross-validation decision values and its +1 / -1 labels).  Every sum over the rows (the five of
+// the Newton step, the objective of the line search, the count of positives) is taken as thread t's partial over rows t, t + NT, ...
+// in row order and then a tree over the NT partials in LDS: a fixed order, so a job's result does not depend on the batch around it.
+// The scalar part (priors, targets, the start point, sigma = 1e-12, the |g| < 1e-5 stop, the backtracking down to 1e-10, 100
+// iterations at most) is svm.cpp's, evaluated by every thread on the same reduced values.
+constexpr int SIG_NT = 256;
+
+// sums of v[0 .. N) over the workgroup -> every thread; red holds N * SIG_NT doubles
+template <int N>
+__device__ __forceinline__ void sig_block_sum(double (&v)[N], double* red) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < N; ++i) red[i * SIG_NT + t] = v[i];
+    __syncthreads();
+    for (int o = SIG_NT / 2; o > 0; o >>= 1) {
+        if (t < o) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) red[i * SIG_NT + t] = red[i * SIG_NT + t] + red[i * SIG_NT + t + o];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = red[i * SIG_NT];
+    __syncthreads();
+}
+
+// svm.cpp sigmoid_train's objective at (A, B)
+__device__ __forceinline__ double sig_objective(const double* dec, const signed char* y, int l, double hi, double lo, double A,
+                                                double B, double* red) {
+    double f[1] = {0.0};
+    for (int i = threadIdx.x; i < l; i += SIG_NT) {
+        const double t = y[i] > 0 ? hi : lo;
+        const double fApB = dec[i] * A + B;
+        if (fApB >= 0.0)
+            f[0] += t * fApB + log(1.0 + exp(-fApB));
+        else
+            f[0] += (t - 1.0) * fApB + log(1.0 + exp(fApB));
+    }
+    sig_block_sum<1>(f, red);
+    return f[0];
+}
+
+__global__ __launch_bounds__(SIG_NT) void svm_sigmoid_train_kernel(const int64_t* off, const double* dec_all, const signed char* y_all,
+                                                                   double* A_out, double* B_out, int* iters_out) {
+    __shared__ double red[5 * SIG_NT];
+    const int job = blockIdx.x;
+    const int64_t o = off[job];
+    const int l = (int)(off[job + 1] - o);
+    const double* dec = dec_all + o;
+    const signed char* y = y_all + o;
+    const int max_iter = 100;
+    const double min_step = 1e-10, sigma = 1e-12, eps = 1e-5;
+    double cnt[1] = {0.0};
+    for (int i = threadIdx.x; i < l; i += SIG_NT) cnt[0] += y[i] > 0 ? 1.0 : 0.0;
+    sig_block_sum<1>(cnt, red);
+    const double prior1 = cnt[0], prior0 = (double)l - prior1;
+    const double hi = (prior1 + 1.0) / (prior1 + 2.0), lo = 1.0 / (prior0 + 2.0);
+    double A = 0.0, B = log((prior0 + 1.0) / (prior1 + 1.0));
+    double fval = sig_objective(dec, y, l, hi, lo, A, B, red);
+    int iter = 0;
+    for (; iter < max_iter; ++iter) {
+        double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};        // h11, h22, h21, g1, g2
+        for (int i = threadIdx.x; i < l; i += SIG_NT) {
+            const double d = dec[i];
+            const double fApB = d * A + B;
+            double p, q;
+            if (fApB >= 0.0) {
+                p = exp(-fApB) / (1.0 + exp(-fApB));
+                q = 1.0 / (1.0 + exp(-fApB));
+            } else {
+                p = 1.0 / (1.0 + exp(fApB));
+                q = exp(fApB) / (1.0 + exp(fApB));
+            }
+            const double d2 = p * q;
+            v[0] += d * d * d2;
+            v[1] += d2;
+            v[2] += d * d2;
+            const double d1 = (y[i] > 0 ? hi : lo) - p;
+            v[3] += d * d1;
+            v[4] += d1;
+        }
+        sig_block_sum<5>(v, red);
+        const double h11 = sigma + v[0], h22 = sigma + v[1], h21 = v[2], g1 = v[3], g2 = v[4];
+        if (fabs(g1) < eps && fabs(g2) < eps) break;
+        const double det = h11 * h22 - h21 * h21;
+        const double dA = -(h22 * g1 - h21 * g2) / det;
+        const double dB = -(-h21 * g1 + h11 * g2) / det;
+        const double gd = g1 * dA + g2 * dB;
+        double step = 1.0;
+        while (step >= min_step) {
+            const double nA = A + step * dA, nB = B + step * dB;
+            const double nf = sig_objective(dec, y, l, hi, lo, nA, nB, red);
+            if (nf < fval + 0.0001 * step * gd) {
+                A = nA, B = nB, fval = nf;
+                break;
+            }
+            step = step / 2.0;
+        }
+        if (step < min_step) break;        // the line search failed
+    }
+    if (threadIdx.x == 0) {
+        A_out[job] = A, B_out[job] = B;
+        if (iters_out) iters_out[job] = iter;
+    }
+}
+
 }  // namespace
 
 void svm_tail(hipStream_t s, const double* dec, int64_t rows, int C, const double* A, const double* B, const int* labels, int* pred,
@@ -311,5 +419,44 @@ extern "C" int l3_op_svm_tail(int device, const double* dec, int64_t n, int n_cl
     // the wait also covers the copies still queued from the caller's buffers when something above failed
     const bool done = hipStreamSynchronize(s) == hipSuccess;
     if (!ok || !done) return fail(L3_EHIP, "l3_op_svm_tail: HIP error");
+    return L3_OK;
+}
+
+extern "C" int l3_op_svm_sigmoid_train(int device, int n_jobs, const int64_t* off, const double* dec, const int8_t* signs,
+                                       double* A_out, double* B_out, int32_t* iters_out) {
+    if (!off || !dec || !signs || !A_out || !B_out || n_jobs <= 0)
+        return fail(L3_EINVAL, "l3_op_svm_sigmoid_train: NULL argument or no jobs");
+    if (off[0] != 0) return fail(L3_EINVAL, "l3_op_svm_sigmoid_train: off[0] must be 0");
+    for (int j = 0; j < n_jobs; ++j)
+        if (off[j + 1] <= off[j] || off[j + 1] - off[j] > INT32_MAX)
+            return fail(L3_EINVAL, "l3_op_svm_sigmoid_train: job " + std::to_string(j) + " needs 1 <= rows < 2^31");
+    const int64_t total = off[n_jobs];
+    for (int64_t i = 0; i < total; ++i) {
+        if (signs[i] != 1 && signs[i] != -1) return fail(L3_EINVAL, "l3_op_svm_sigmoid_train: signs must be +1 or -1");
+        if (!std::isfinite(dec[i])) return fail(L3_EINVAL, "l3_op_svm_sigmoid_train: decision values must be finite");
+    }
+    if (!device_ok(device)) return fail(L3_EHIP, no_gpu_message("l3_op_svm_sigmoid_train", device));
+    DeviceBufs b;
+    hipStream_t s = nullptr;
+    const int64_t* d_off = b.put(off, n_jobs + 1, s);
+    const double* d_dec = b.put(dec, total, s);
+    const signed char* d_y = reinterpret_cast<const signed char*>(b.put(signs, total, s));
+    double* d_A = b.alloc<double>(n_jobs);
+    double* d_B = b.alloc<double>(n_jobs);
+    int* d_it = b.alloc<int>(n_jobs);
+    if (!b.ok()) {
+        (void)hipStreamSynchronize(s);
+        return fail(L3_ENOMEM, "l3_op_svm_sigmoid_train: device allocation failed");
+    }
+    hipLaunchKernelGGL(svm_sigmoid_train_kernel, dim3((unsigned)n_jobs), dim3(SIG_NT), 0, s, d_off, d_dec, d_y, d_A, d_B, d_it);
+    bool ok = hipGetLastError() == hipSuccess;
+    auto get = [&](void* dst, const void* src, size_t bytes) {
+        if (dst && ok) ok = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
+    };
+    get(A_out, d_A, n_jobs * sizeof(double));
+    get(B_out, d_B, n_jobs * sizeof(double));
+    get(iters_out, d_it, n_jobs * sizeof(int));
+    const bool done = hipStreamSynchronize(s) == hipSuccess;
+    if (!ok || !done) return fail(L3_EHIP, "l3_op_svm_sigmoid_train: HIP error");
     return L3_OK;
 }

@@ -4,7 +4,9 @@ trained and evaluated on the GPU through the l3_svm handle of libl3hip (csrc/svm
 Here are the multiclass shell and probability estimates of libsvm's svm_train / svm_predict_probability (svm.cpp): one-vs-one
 pairs, support vectors grouped by class with the (C - 1, n_SV) coefficient matrix, the vote, Platt scaling fitted on 5-fold
 cross-validation decision values, and pairwise coupling.  Every binary problem (the pairs and their cross-validation
-sub-problems) goes through the GPU solver in one batched call; the sigmoid fit stays on the host in NumPy.  predict,
+sub-problems) goes through the GPU solver in one batched call; the sigmoid fit stays on the host in NumPy.  fit_grid fits the
+models of a grid over C in one pass: one solver call with a cost per problem, one launch for the held-out decision values of
+every cross-validation sub-problem, one for the sigmoid fits of every pair and cost (csrc/svm_eval.hip).  predict,
 decision_function and predict_proba of NumPy rows vote and couple on the host in NumPy; SVC.evaluate scores a split in one pass on
 the GPU (csrc/svm_eval.hip: vote, ovr values, hinge loss, Platt probabilities, coupling, per-file means) and takes
 usc.DeviceFeatures as it is, as fit does.
@@ -168,6 +170,68 @@ def hinge_loss(y_true, pred_decision, labels=None):
     return float(np.mean(losses))
 
 
+# ---- the problems of a fit: what SVC.fit and fit_grid assemble alike ---------------------------------------------------------------
+def _check_rows(X, y):
+    """-> (X as fit takes it, y flat, whether X is a usc.DeviceFeatures)"""
+    on_device = isinstance(X, DeviceFeatures)
+    if not on_device:
+        X = np.ascontiguousarray(X, np.float32)
+    y = np.asarray(y).reshape(-1)
+    if len(X.shape) != 2 or X.shape[0] != y.size:
+        raise ValueError('X must be (n_samples, n_features) with one label per row')
+    return X, y, on_device
+
+
+def _encode_classes(y):
+    classes, yenc = np.unique(y, return_inverse=True)
+    if classes.size < 2:
+        raise ValueError('The number of classes has to be greater than one; got %d' % classes.size)
+    if classes.size > _lib.SVM_MAX_CLASSES:
+        raise ValueError('at most %d classes are built' % _lib.SVM_MAX_CLASSES)
+    return classes, yenc
+
+
+def pair_problems(yenc, nc):
+    """libsvm's one-vs-one problems -> (groups: the rows of each class, pairs (i, j), problems: (rows, signs) per pair with class i
+    first and +1)"""
+    groups = [np.flatnonzero(yenc == c).astype(np.int32) for c in range(nc)]
+    pairs = [(i, j) for i in range(nc) for j in range(i + 1, nc)]
+    problems = [(np.concatenate((groups[i], groups[j])),
+                 np.concatenate((np.ones(groups[i].size, np.int8), -np.ones(groups[j].size, np.int8)))) for i, j in pairs]
+    return groups, pairs, problems
+
+
+def cv_problems(problems, random_state):
+    """svm_binary_svc_probability's 5 folds of every pair, the permutations drawn from np.random.RandomState(random_state) pair after
+    pair -> (cv, sub): cv lists (pair, held-out positions in the pair's rows, job), job being a sub-problem as its number in
+    problems + sub, or libsvm's fixed decision value (a float) for a fold whose training part holds one class or none; sub lists
+    the sub-problems (rows, signs)"""
+    cv, sub = [], []
+    rs = np.random.RandomState(random_state)
+    for p, (rows, signs) in enumerate(problems):
+        l = rows.size
+        perm = rs.permutation(l)
+        for f in range(NR_FOLD):
+            begin, end = f * l // NR_FOLD, (f + 1) * l // NR_FOLD
+            train_pos = np.concatenate((perm[:begin], perm[end:]))
+            npos = int((signs[train_pos] > 0).sum())
+            nneg = train_pos.size - npos
+            if npos == 0 or nneg == 0:      # libsvm's fixed decision values for a fold with one class (or none)
+                cv.append((p, perm[begin:end], 0.0 if npos == nneg else (1.0 if npos else -1.0)))
+            else:
+                cv.append((p, perm[begin:end], len(problems) + len(sub)))
+                sub.append((rows[train_pos], signs[train_pos]))
+    return cv, sub
+
+
+def _binary_model(rows, signs, a):
+    """a solved binary problem as the decision launches take it -> (support-vector rows, positives first; their count of positives;
+    the coefficients y alpha)"""
+    nz = a > 0
+    pos, neg = nz & (signs > 0), nz & (signs < 0)
+    return np.concatenate((rows[pos], rows[neg])), int(pos.sum()), np.concatenate((a[pos], -a[neg]))
+
+
 # ---- SVC -------------------------------------------------------------------------------------------------------------------------
 class SVC(object):
     """sklearn 0.19.0's sklearn.svm.SVC (C-SVC) on the GPU: fit / predict / decision_function / predict_proba and sklearn's
@@ -184,7 +248,7 @@ class SVC(object):
     # pickling: everything but the device handle
     def __getstate__(self):
         state = dict(self.__dict__)
-        state['_h'] = None
+        state['_h'] = state['_key'] = None
         state['_model_set'] = state['_resident'] = False
         return state
 
@@ -201,22 +265,13 @@ class SVC(object):
 
     def fit(self, X, y):
         """X: NumPy rows, or a usc.DeviceFeatures, which is copied on the device (no download; the solver sees the same bits)"""
-        on_device = isinstance(X, DeviceFeatures)
-        if not on_device:
-            X = np.ascontiguousarray(X, np.float32)
-        y = np.asarray(y).reshape(-1)
-        if len(X.shape) != 2 or X.shape[0] != y.size:
-            raise ValueError('X must be (n_samples, n_features) with one label per row')
+        X, y, on_device = _check_rows(X, y)
         if not self.C > 0:
             raise ValueError('C <= 0')
         if self.kernel not in _lib.SVM_KERNELS:
             raise ValueError('kernel must be one of %s' % sorted(_lib.SVM_KERNELS))
-        self.classes_, yenc = np.unique(y, return_inverse=True)
+        self.classes_, yenc = _encode_classes(y)
         nc = self.classes_.size
-        if nc < 2:
-            raise ValueError('The number of classes has to be greater than one; got %d' % nc)
-        if nc > _lib.SVM_MAX_CLASSES:
-            raise ValueError('at most %d classes are built' % _lib.SVM_MAX_CLASSES)
         self.shape_fit_ = tuple(X.shape)
         self._gamma = 1.0 / X.shape[1] if self.gamma == 'auto' else float(self.gamma)
         self._model_set = self._resident = False
@@ -226,34 +281,12 @@ class SVC(object):
         else:
             h.set_data(X)
         kp = self._kernel()
-        groups = [np.flatnonzero(yenc == c).astype(np.int32) for c in range(nc)]
-        pairs = [(i, j) for i in range(nc) for j in range(i + 1, nc)]
-        problems = [(np.concatenate((groups[i], groups[j])),
-                     np.concatenate((np.ones(groups[i].size, np.int8), -np.ones(groups[j].size, np.int8)))) for i, j in pairs]
-        cv = []                      # (pair, held-out positions in the pair's rows, sub-problem number or a fixed value)
-        sub = []
-        if self.probability:
-            rs = np.random.RandomState(self.random_state)
-            for p, (rows, signs) in enumerate(problems):
-                l = rows.size
-                perm = rs.permutation(l)
-                for f in range(NR_FOLD):
-                    begin, end = f * l // NR_FOLD, (f + 1) * l // NR_FOLD
-                    train_pos = np.concatenate((perm[:begin], perm[end:]))
-                    npos = int((signs[train_pos] > 0).sum())
-                    nneg = train_pos.size - npos
-                    if npos == 0 or nneg == 0:      # libsvm's fixed decision values for a fold with one class (or none)
-                        cv.append((p, perm[begin:end], 0.0 if npos == nneg else (1.0 if npos else -1.0)))
-                    else:
-                        cv.append((p, perm[begin:end], len(problems) + len(sub)))
-                        sub.append((rows[train_pos], signs[train_pos]))
+        groups, pairs, problems = pair_problems(yenc, nc)
+        # cv: (pair, held-out positions in the pair's rows, sub-problem number or a fixed value)
+        cv, sub = cv_problems(problems, self.random_state) if self.probability else ([], [])
         alphas, rho, updates, outer, gaps = h.fit(kp, problems + sub, cost=self.C, tol=self.tol, max_iter=self.max_iter,
                                                   q=self.ws_size)
-        self.n_iter_ = updates[:len(problems)].copy()
-        self.n_outer_ = outer[:len(problems)].copy()
-        if self.max_iter is not None and self.max_iter > 0 and np.any(updates >= self.max_iter):
-            LOGGER.warning('Solver terminated early (max_iter=%d).  Consider pre-processing your data with StandardScaler or '
-                           'MinMaxScaler.', self.max_iter)
+        self._solved(updates, outer, len(problems))
         self._build_model(h.get_rows if on_device else X.__getitem__, y.size, groups, pairs, problems, alphas, rho)
         if self.probability:
             self.probA_, self.probB_ = self._platt(h, kp, problems, sub, cv, alphas, rho)
@@ -261,6 +294,14 @@ class SVC(object):
             self.probA_ = self.probB_ = np.empty(0)
         self._resident = True          # the support vectors are rows support_ of this handle's matrix
         return self
+
+    def _solved(self, updates, outer, n_pairs):
+        """the solver's counts of this model's problems (the pairs first)"""
+        self.n_iter_ = updates[:n_pairs].copy()
+        self.n_outer_ = outer[:n_pairs].copy()
+        if self.max_iter is not None and self.max_iter > 0 and np.any(updates >= self.max_iter):
+            LOGGER.warning('Solver terminated early (max_iter=%d).  Consider pre-processing your data with StandardScaler or '
+                           'MinMaxScaler.', self.max_iter)
 
     def _build_model(self, rows_of, n_rows, groups, pairs, problems, alphas, rho):
         """svm.cpp svm_train's multiclass model: support vectors grouped by class, sv_coef (C - 1, n_SV), rho per pair"""
@@ -298,14 +339,9 @@ class SVC(object):
             if isinstance(job, float):
                 decs[p][held] = job
                 continue
-            rows, signs = allp[job]
-            a = alphas[job]
-            nz = a > 0
-            pos, neg = nz & (signs > 0), nz & (signs < 0)
-            sv = np.concatenate((rows[pos], rows[neg]))
-            coef = np.concatenate((a[pos], -a[neg]))[None, :]
-            cs = np.array([0, pos.sum(), pos.sum() + neg.sum()], np.int64)
-            decs[p][held] = h.decision(kp, cs, coef, [rho[job]], x_idx=problems[p][0][held], sv_idx=sv)[:, 0]
+            sv, npos, coef = _binary_model(allp[job][0], allp[job][1], alphas[job])
+            cs = np.array([0, npos, sv.size], np.int64)
+            decs[p][held] = h.decision(kp, cs, coef[None, :], [rho[job]], x_idx=problems[p][0][held], sv_idx=sv)[:, 0]
         A, B = np.empty(len(problems)), np.empty(len(problems))
         for p, (rows, signs) in enumerate(problems):
             A[p], B[p] = sigmoid_train(decs[p], signs)
@@ -327,12 +363,20 @@ class SVC(object):
     def _ensure_model(self):
         """the resident model of evaluate: set once per fitted model, and again after unpickling"""
         h = self._handle()
-        if not getattr(self, '_model_set', False):
+        # models fitted together (fit_grid) share one handle, which holds one model at a time: the handle names its owner
+        if not getattr(self, '_model_set', False) or getattr(h, 'model_owner', None) is not self._owner_key():
             prob = dict(probA=self.probA_, probB=self.probB_) if self.probability else {}
             sv = dict(sv_idx=self.support_) if getattr(self, '_resident', False) else dict(SV=self.support_vectors_)
             h.set_model(self._kernel(), self._sv_start, self._dual_coef_, -self._intercept_, **dict(sv, **prob))
             self._model_set = True
+            h.model_owner = self._owner_key()
         return h
+
+    def _owner_key(self):
+        """what a shared handle remembers of the object whose model it holds (not the object: no reference cycle)"""
+        if self.__dict__.get('_key') is None:
+            self._key = object()
+        return self._key
 
     def evaluate(self, X, y=None, file_idxs=None, outputs=('predict',)):
         """One scoring pass on the GPU over X (NumPy rows or a usc.DeviceFeatures) -> dict of what `outputs` names, and nothing
@@ -436,3 +480,130 @@ def pairwise_coupling(dec, probA, probB, n_classes):
             r[:, i, j], r[:, j, i] = pij, 1 - pij
             k += 1
     return multiclass_probability(r)
+
+
+# ---- the grid over C in one pass -----------------------------------------------------------------------------------------------
+PLATT_MODES = ('device', 'host')
+
+
+def grid_problems(yenc, nc, Cs, probability, random_state):
+    """what fit_grid solves: per cost, the problems SVC(C=c, random_state=random_state).fit assembles (pair_problems, cv_problems)
+    -> (groups, pairs, problems, folds): folds holds one (cv, sub) per cost.  A fixed random_state gives every cost the same folds,
+    as separate fits would draw them; None draws anew for every cost, as separate fits would."""
+    groups, pairs, problems = pair_problems(yenc, nc)
+    folds = []
+    for _ in Cs:
+        if not probability:
+            folds.append(([], []))
+        elif folds and random_state is not None and not isinstance(random_state, np.random.RandomState):
+            folds.append(folds[0])
+        else:
+            folds.append(cv_problems(problems, random_state))
+    return groups, pairs, problems, folds
+
+
+def _cost_batches(entries, budget):
+    """consecutive costs per solver call: as many as keep the call's entries (rows over all its problems) within the budget, one
+    at least -> list of index lists"""
+    batches, used = [], 0
+    for g, e in enumerate(entries):
+        if not batches or (budget is not None and used + e > budget):
+            batches.append([])
+            used = 0
+        batches[-1].append(g)
+        used += e
+    return batches
+
+
+def fit_grid(X, y, Cs, platt='device', max_entries=None, keep_cv_decisions=False, **svc_params):
+    """SVC(C=c, **svc_params).fit(X, y) for every c of Cs in one pass -> the fitted models, in the order of Cs.
+
+    X (NumPy rows or a usc.DeviceFeatures) becomes resident once.  The pair problems and the cross-validation sub-problems of every
+    cost are solved side by side in one solver call (_lib.SVM.fit with one cost per problem), the held-out decision values of every
+    sub-problem come from one launch (_lib.SVM.cv_decision), and Platt's sigmoids of every pair and cost are fitted in one more
+    (_lib.svm_sigmoid_train; platt='device').  platt='host' fits them with sigmoid_train in NumPy instead, pair by pair, as SVC.fit
+    does.  The solver attributes (support_, dual_coef_, intercept_, n_iter_, ...) are those of the separate fits bit for bit, since
+    a problem's solution does not depend on its batch; so are probA_ / probB_ with platt='host'; with platt='device' they differ
+    by the order of the float64 sums of the sigmoid fit.  One exception, which SVC.fit shares across its own problems: with
+    max_iter=-1 the update cap is max(10^7, 100 x the largest problem), the same for every cost here.
+
+    max_entries: a budget on the rows over all problems of one solver call (its kernel-row scratch is 4 q bytes per entry); the
+    costs then go through several calls, a whole cost at a time, and the models do not depend on the split.
+
+    keep_cv_decisions: each model keeps the cross-validation decision values its sigmoids were fitted on as cv_decisions_ (one
+    array per pair, in the order of the pair's rows).
+
+    The models share one device handle (and its resident matrix); the handle holds the model evaluate() last used."""
+    Cs = [float(c) for c in Cs]
+    if not Cs:
+        raise ValueError('Cs is empty')
+    if any(not c > 0 or not np.isfinite(c) for c in Cs):
+        raise ValueError('C <= 0')
+    if platt not in PLATT_MODES:
+        raise ValueError('platt must be one of %s, not %r' % (list(PLATT_MODES), platt))
+    if 'C' in svc_params:
+        raise ValueError('the costs come as Cs, not as C')
+    models = [SVC(C=c, **svc_params) for c in Cs]
+    m0 = models[0]
+    X, y, on_device = _check_rows(X, y)
+    if m0.kernel not in _lib.SVM_KERNELS:
+        raise ValueError('kernel must be one of %s' % sorted(_lib.SVM_KERNELS))
+    classes, yenc = _encode_classes(y)
+    nc = classes.size
+    h = _lib.SVM(m0.device)
+    if on_device:
+        h.set_data_dev(X.handle)
+    else:
+        h.set_data(X)
+    for m in models:
+        m.classes_, m.shape_fit_ = classes, tuple(X.shape)
+        m._gamma = 1.0 / X.shape[1] if m.gamma == 'auto' else float(m.gamma)
+        m._model_set = m._resident = False
+        m._h = h
+    kp = m0._kernel()
+    groups, pairs, problems, folds = grid_problems(yenc, nc, Cs, m0.probability, m0.random_state)
+    n_pairs = len(problems)
+    per_cost = [problems + sub for _, sub in folds]
+    entries = [sum(rows.size for rows, _ in allp) for allp in per_cost]
+    solved = [None] * len(Cs)                   # per cost: (alphas, rho) over problems + sub
+    for batch in _cost_batches(entries, max_entries):
+        probs = [pr for g in batch for pr in per_cost[g]]
+        costs = np.concatenate([np.full(len(per_cost[g]), Cs[g]) for g in batch])
+        alphas, rho, updates, outer, _ = h.fit(kp, probs, cost=costs, tol=m0.tol, max_iter=m0.max_iter, q=m0.ws_size)
+        at = 0
+        for g in batch:
+            n = len(per_cost[g])
+            solved[g] = (alphas[at:at + n], rho[at:at + n])
+            models[g]._solved(updates[at:at + n], outer[at:at + n], n_pairs)
+            at += n
+    rows_of = h.get_rows if on_device else X.__getitem__
+    for m, (alphas, rho) in zip(models, solved):
+        m._build_model(rows_of, y.size, groups, pairs, problems, alphas, rho)
+        m.probA_ = m.probB_ = np.empty(0)
+        m._resident = True
+    if m0.probability:
+        # every sub-problem of every cost scored on its held-out rows in one launch
+        jobs, where = [], []
+        decs = [[np.empty(rows.size) for rows, _ in problems] for _ in Cs]
+        for g, ((cv, _), (alphas, rho)) in enumerate(zip(folds, solved)):
+            for p, held, job in cv:
+                if isinstance(job, float):
+                    decs[g][p][held] = job
+                    continue
+                sv, npos, coef = _binary_model(per_cost[g][job][0], per_cost[g][job][1], alphas[job])
+                jobs.append((problems[p][0][held], sv, npos, coef, rho[job]))
+                where.append((g, p, held))
+        for (g, p, held), dec in zip(where, h.cv_decision(kp, jobs)):
+            decs[g][p][held] = dec
+        if keep_cv_decisions:
+            for g, m in enumerate(models):
+                m.cv_decisions_ = decs[g]
+        if platt == 'device':
+            A, B, _ = _lib.svm_sigmoid_train(m0.device, [d for dg in decs for d in dg], [signs for _ in Cs for _, signs in problems])
+            for g, m in enumerate(models):
+                m.probA_, m.probB_ = A[g * n_pairs:(g + 1) * n_pairs].copy(), B[g * n_pairs:(g + 1) * n_pairs].copy()
+        else:
+            for g, m in enumerate(models):
+                fitted = [sigmoid_train(decs[g][p], signs) for p, (_, signs) in enumerate(problems)]
+                m.probA_, m.probB_ = np.array([a for a, _ in fitted], np.float64), np.array([b for _, b in fitted], np.float64)
+    return models
