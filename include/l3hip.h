@@ -657,6 +657,18 @@ void l3_feat_destroy(l3_feat *f);
 int l3_feat_shape(const l3_feat *f, int64_t *n, int64_t *D);
 /* rows [lo, hi) -> dst ((hi - lo), D) */
 int l3_feat_download(l3_feat *f, int64_t lo, int64_t hi, float *dst);
+/* A new handle on `device` whose matrix is the rows [lo, hi) of each segment's source, in segment order, copied device to device by
+ * ONE kernel launch (the np.vstack of get_fold and get_train_folds, data/usc/folds.py:24-112, for folds that already are on the
+ * device).  The sources are only read and stay as they are; a source may occur in any number of segments; a segment with lo == hi
+ * contributes nothing.  L3_EINVAL, with a message that names the segment, *out untouched and nothing allocated on the device: a NULL
+ * source, a source on another device, a source of another width D than segment 0's, lo / hi outside the source, n_segs < 1, a total
+ * of 0 rows or of more than 2^31 - 1.  Rows move as 16-byte accesses wherever a segment's first source and output addresses are both
+ * 16-byte aligned (always when D % 4 == 0) and as 4-byte accesses otherwise; the result is the same bits either way.
+ * Ordering: the copy runs on the new handle's stream and has finished when the call returns.  It relies on every l3_feat call having
+ * finished on its handle's stream when it returns, so the sources hold their final values at entry; each source's stream is
+ * synchronised before the launch all the same.  As for every l3_feat call, no other call may run on a source meanwhile. */
+typedef struct { const l3_feat *src; int64_t lo, hi; } l3_feat_segment;   /* rows [lo, hi) of src */
+int l3_feat_assemble(int device, const l3_feat_segment *segs, int64_t n_segs, l3_feat **out);
 /* X <- X[rows]: n_out >= 1 host indices, each in [0, n) (else L3_EINVAL, and the matrix stays as it was).  The caller builds the
  * table -- every chunk_size-th row of each file, or the shuffle's permutation -- and the device moves the rows. */
 int l3_feat_gather(l3_feat *f, const int64_t *rows, int64_t n_out);

@@ -209,6 +209,7 @@ SIGNATURES = {
     'l3_feat_destroy': (None, [C.c_void_p]),
     'l3_feat_shape': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'l3_feat_download': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'l3_feat_assemble': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     'l3_feat_gather': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     'l3_feat_minmax': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'l3_feat_affine32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -990,6 +991,26 @@ class Features(object):
         check(self.lib.l3_feat_create(int(device), _ptr(x), x.shape[0], x.shape[1], C.byref(h)), None)
         self.h = h
         self.device = int(device)
+
+    SEGMENT = np.dtype([('src', np.uintp), ('lo', np.int64), ('hi', np.int64)])          # l3_feat_segment
+
+    @classmethod
+    def assemble(cls, segments, device=0):
+        """A new Features whose rows are the rows [lo, hi) of each (Features, lo, hi) of `segments`, in order, copied on the device
+        by one kernel (l3_feat_assemble).  The sources stay as they are."""
+        segments = list(segments)
+        table = np.zeros(len(segments), cls.SEGMENT)
+        for i, (src, lo, hi) in enumerate(segments):
+            if not isinstance(src, cls) or not src.h:
+                raise ValueError('segment %d: the source must be an open Features' % i)
+            table[i] = (src.h.value, int(lo), int(hi))
+        self = cls.__new__(cls)
+        self.lib = load()
+        h = C.c_void_p()
+        check(self.lib.l3_feat_assemble(int(device), _ptr(table), len(segments), C.byref(h)), None)
+        self.h = h
+        self.device = int(device)
+        return self
 
     def close(self):
         if getattr(self, 'h', None):

@@ -8,6 +8,8 @@ it.  Deviations from the reference, all deliberate:
   * the random start delay and the Google Sheets logging of train() are skipped; config.json has git_commit None;
   * the scalers are pickled with `pickle` (the reference uses sklearn's joblib; these are NumPy restatements, usc.py);
   * the random forest and StratifiedShuffleSplit (sklearn on the host) are not built: they raise;
+  * cross_validate runs every fold of a dataset in one call from folds read once (usc.FoldBank) and summarises them with
+    aggregate_metrics (classifier/metrics.py:49-78); the reference runs one job per fold;
   * the SVM (train_svm, classifier/train.py:79-166) trains on the GPU (svm.py, csrc/svm.hip); its probability estimates draw the
     cross-validation fold permutation from np.random.RandomState(random_state) as the MLP's shuffle does (libsvm uses rand()),
     and the model is pickled with `pickle` (the reference uses joblib).  train() still runs only the MLP; train_svm_fold is
@@ -27,7 +29,7 @@ import numpy as np
 from . import _lib, callbacks, kerasfile
 from . import svm as _svm
 from .svm import SVC, hinge_loss  # noqa: F401  (re-exported: the reference imports them into classifier/train.py)
-from .usc import DeviceFeatures, get_split, preprocess_split_data
+from .usc import DeviceFeatures, FoldBank, get_split, preprocess_split_data
 
 LOGGER = logging.getLogger('classifier')
 
@@ -263,6 +265,19 @@ def compute_metrics(y, pred, num_classes=10):
     return {'accuracy': hit.mean(), 'class_accuracy': per_class, 'average_class_accuracy': np.mean(per_class)}
 
 
+def aggregate_metrics(fold_metrics):
+    """classifier/metrics.py:49-78: the folds' values of every key of the FIRST fold's metrics -> {key: {'mean', 'var', 'min',
+    '25_%ile', '75_%ile', 'median', 'max'}}, each as NumPy gives it over the list of the folds' values (a list-valued metric such
+    as class_accuracy is reduced over all its entries)."""
+    keys = list(fold_metrics[0].keys())
+    out = {}
+    for k in keys:
+        values = [fold[k] for fold in fold_metrics]
+        out[k] = {'mean': np.mean(values), 'var': np.var(values), 'min': np.min(values), '25_%ile': np.percentile(values, 25),
+                  '75_%ile': np.percentile(values, 75), 'median': np.median(values), 'max': np.max(values)}
+    return out
+
+
 def _series_metrics(series, at):
     """loss / accuracy at the checkpoint epoch and their whole histories, from a MetricCallback's two series"""
     loss, acc = series
@@ -435,7 +450,8 @@ def train_svm_search(train_data, valid_data, test_data, model_dir, Cs=SVM_SEARCH
     """train_param_search(..., train_func=train_svm, search_space={'C': Cs}, evaluate_on_device=True) with the grid fitted in one
     pass: one svm.fit_grid over the training split (NumPy rows or usc.DeviceFeatures, resident once), one SVC.evaluate per split
     and model, the cost with the best validation accuracy (the first one on ties), and with train_with_valid the retrain on
-    train + valid shuffled together (merged on the host, np.random.permutation as there).  -> the same tuple (model, train_metrics,
+    train + valid shuffled together (np.random.permutation as there; two usc.DeviceFeatures on one GPU are merged and shuffled
+    there, anything else on the host: the same bits).  -> the same tuple (model, train_metrics,
     valid_metrics, test_metrics) with the same search records.  platt: svm.fit_grid's ('host': Platt's sigmoids as SVC.fit
     fits them, so every number equals that of the separate fits).  model_dir/model.pkl holds the returned model (the loop over
     train_svm leaves the one it fitted last there).  C is ignored (the search sets it); the other arguments are train_svm's."""
@@ -454,12 +470,26 @@ def train_svm_search(train_data, valid_data, test_data, model_dir, Cs=SVM_SEARCH
     LOGGER.info('Chosen %s (validation accuracy %s)', {'C': point[0]}, chosen[3]['accuracy'])
 
     if train_with_valid:
-        train_data, valid_data = _on_host(train_data), _on_host(valid_data)
         merged_labels = np.concatenate((train_data['labels'], valid_data['labels']))
         mix = np.random.permutation(merged_labels.size)
-        merged = {'features': np.vstack((train_data['features'], valid_data['features']))[mix], 'labels': merged_labels[mix]}
-        model = _svm.fit_grid(merged['features'], merged['labels'], [point[0]], platt=platt, max_entries=max_entries, **params)[0]
-        train_metrics, _, test_metrics = _svm_metrics_on_device(model, merged, None, test_data, num_classes)
+        tx, vx = train_data['features'], valid_data['features']
+        resident = isinstance(tx, DeviceFeatures) and isinstance(vx, DeviceFeatures) and tx.device == vx.device
+        if resident:          # vstack((train, valid))[mix] where the two splits are: one copy kernel, one gather
+            stacked = DeviceFeatures.assemble([(tx, 0, len(tx)), (vx, 0, len(vx))], device=tx.device)
+            try:
+                stacked.handle.gather(mix)
+            except Exception:
+                stacked.close()
+                raise
+        else:
+            stacked = np.vstack((_on_host(train_data)['features'], _on_host(valid_data)['features']))[mix]
+        merged = {'features': stacked, 'labels': merged_labels[mix]}
+        try:
+            model = _svm.fit_grid(merged['features'], merged['labels'], [point[0]], platt=platt, max_entries=max_entries, **params)[0]
+            train_metrics, _, test_metrics = _svm_metrics_on_device(model, merged, None, test_data, num_classes)
+        finally:
+            if resident:
+                stacked.close()
     else:
         model, train_metrics, test_metrics = chosen[1], dict(chosen[2]), chosen[4]
     LOGGER.info('Saving model...')
@@ -479,6 +509,11 @@ def _dataset_of(features_dir):
     return desc.split('/')[0], desc
 
 
+def _model_id(desc, feature_mode, non_overlap, use_min_max, model_type):
+    return os.path.join(desc, feature_mode, 'non-overlap' if non_overlap else 'overlap', 'min-max' if use_min_max else 'no-min-max',
+                        model_type)
+
+
 def _dump(path, obj):
     with open(path, 'wb') as fh:
         pk.dump(obj, fh, protocol=pk.HIGHEST_PROTOCOL)
@@ -487,17 +522,16 @@ def _dump(path, obj):
 def _start_fold(features_dir, output_dir, fold_num, model_type, feature_mode, train_batch_size, patience, random_state,
                 parameter_search, parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid,
                 gsheet_id, google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device,
-                model_args):
+                model_args, splits=None):
     """what a fold of any model type begins with (classifier/train.py:495-603): the run's directory, config.json, the fold's
-    splits preprocessed, the two scalers pickled -> (model_dir, dataset, splits)"""
+    splits preprocessed, the two scalers pickled -> (model_dir, dataset, splits).  splits: a function of (with_valid_fold) that
+    gives the fold's (train, valid or None, test) in place of usc.get_split (cross_validate's come from its FoldBank)."""
     dataset, desc = _dataset_of(features_dir)
     if dataset not in DATASET_NUM_CLASSES:
         raise ValueError('the features directory must name a dataset right after "features/" (one of {})'.format(
             ', '.join(sorted(DATASET_NUM_CLASSES))))
 
-    variant = [feature_mode, 'non-overlap' if non_overlap else 'overlap', 'min-max' if use_min_max else 'no-min-max',
-               model_type]
-    model_id = os.path.join(desc, *variant)
+    model_id = _model_id(desc, feature_mode, non_overlap, use_min_max, model_type)
     stamp = datetime.datetime.now().strftime('%Y%m%d%H%M%S')
     model_dir = os.path.join(output_dir, 'classifier', model_id, 'fold%d' % fold_num, stamp)
     os.makedirs(model_dir, exist_ok=True)
@@ -519,7 +553,7 @@ def _start_fold(features_dir, output_dir, fold_num, model_type, feature_mode, tr
 
     with_valid_fold = parameter_search_valid_fold or not parameter_search
     LOGGER.info('Fold %d of %s: loading and preprocessing', fold_num, dataset)
-    splits = get_split(features_dir, fold_num - 1, dataset, valid=with_valid_fold)
+    splits = splits(with_valid_fold) if splits else get_split(features_dir, fold_num - 1, dataset, valid=with_valid_fold)
     scalers = preprocess_split_data(*splits, feature_mode=feature_mode, non_overlap=non_overlap,
                                     non_overlap_chunk_size=int(non_overlap_chunk_size), use_min_max=use_min_max,
                                     device=preprocess_device)
@@ -542,25 +576,43 @@ def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='fr
     -> that directory."""
     if model_type != 'mlp':
         raise ValueError(ONLY_MLP.format(model_type))
+    return _mlp_fold(None, features_dir, output_dir, fold_num, feature_mode, train_batch_size, patience, random_state, parameter_search,
+                     parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id,
+                     google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args)
+
+
+def _close_splits(splits):
+    for d in splits:
+        if d and isinstance(d.get('features'), DeviceFeatures):
+            d['features'].close()
+
+
+def _mlp_fold(splits, features_dir, output_dir, fold_num, feature_mode, train_batch_size, patience, random_state, parameter_search,
+              parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id,
+              google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args):
+    """train()'s fold; `splits` as _start_fold takes them -> the fold's directory"""
     if parameter_search and not parameter_search_valid_fold:
         raise ValueError(NO_SSS)
     if gsheet_id:
         LOGGER.warning('Google Sheets logging is not built; gsheet_id ignored')
     model_dir, dataset, splits = _start_fold(
-        features_dir, output_dir, fold_num, model_type, feature_mode, train_batch_size, patience, random_state, parameter_search,
+        features_dir, output_dir, fold_num, 'mlp', feature_mode, train_batch_size, patience, random_state, parameter_search,
         parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id, google_dev_app_name,
-        verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args)
+        verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args, splits=splits)
 
     common = dict(batch_size=train_batch_size, patience=patience, random_state=random_state,
                   num_classes=DATASET_NUM_CLASSES[dataset], verbose=verbose)
-    if parameter_search:
-        splits = tuple(_on_host(d) for d in splits)          # one download; the search then runs as on the host
-        grid = {'learning_rate': [1e-5, 1e-4, 1e-3], 'weight_decay': [1e-5, 1e-4, 1e-3]}
-        outcome = train_param_search(*splits, model_dir, train_func=train_mlp, search_space=grid,
-                                     valid_ratio=parameter_search_valid_ratio,
-                                     train_with_valid=parameter_search_train_with_valid, **dict(common, **model_args))
-    else:
-        outcome = train_mlp(*splits, model_dir, **dict(common, **model_args))
+    try:
+        if parameter_search:
+            on_host = tuple(_on_host(d) for d in splits)          # one download; the search then runs as on the host
+            grid = {'learning_rate': [1e-5, 1e-4, 1e-3], 'weight_decay': [1e-5, 1e-4, 1e-3]}
+            outcome = train_param_search(*on_host, model_dir, train_func=train_mlp, search_space=grid,
+                                         valid_ratio=parameter_search_valid_ratio,
+                                         train_with_valid=parameter_search_train_with_valid, **dict(common, **model_args))
+        else:
+            outcome = train_mlp(*splits, model_dir, **dict(common, **model_args))
+    finally:
+        _close_splits(splits)
     _, train_metrics, valid_metrics, test_metrics = outcome
     _dump(os.path.join(model_dir, 'results.pkl'), {'train': train_metrics, 'valid': valid_metrics, 'test': test_metrics})
     LOGGER.info('Fold %d done: results in %s', fold_num, model_dir)
@@ -579,6 +631,15 @@ def train_svm_fold(features_dir, output_dir, fold_num, feature_mode='framewise',
     parameter_search: train_svm_search over C = 0.1 ... 1000 (platt: its sigmoid fit, 'device' or 'host'); else one train_svm with
     model_args (C, kernel, tol, max_iterations).  train_batch_size and patience are recorded as the reference records them; the
     SVM does not use them.  -> that directory."""
+    return _svm_fold(None, features_dir, output_dir, fold_num, feature_mode, train_batch_size, patience, random_state, parameter_search,
+                     parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id,
+                     google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, platt, model_args)
+
+
+def _svm_fold(splits, features_dir, output_dir, fold_num, feature_mode, train_batch_size, patience, random_state, parameter_search,
+              parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id,
+              google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, platt, model_args):
+    """train_svm_fold()'s fold; `splits` as _start_fold takes them -> the fold's directory"""
     if parameter_search and not parameter_search_valid_fold:
         raise ValueError(NO_SSS)
     if gsheet_id:
@@ -586,14 +647,117 @@ def train_svm_fold(features_dir, output_dir, fold_num, feature_mode='framewise',
     model_dir, dataset, splits = _start_fold(
         features_dir, output_dir, fold_num, 'svm', feature_mode, train_batch_size, patience, random_state, parameter_search,
         parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id, google_dev_app_name,
-        verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args)
+        verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args, splits=splits)
     common = dict(random_state=random_state, num_classes=DATASET_NUM_CLASSES[dataset], verbose=verbose)
-    if parameter_search:
-        outcome = train_svm_search(*splits, model_dir, train_with_valid=parameter_search_train_with_valid, platt=platt,
-                                   **dict(common, **model_args))
-    else:
-        outcome = train_svm(*splits, model_dir, evaluate_on_device=True, **dict(common, **model_args))
+    try:
+        if parameter_search:
+            outcome = train_svm_search(*splits, model_dir, train_with_valid=parameter_search_train_with_valid, platt=platt,
+                                       **dict(common, **model_args))
+        else:
+            outcome = train_svm(*splits, model_dir, evaluate_on_device=True, **dict(common, **model_args))
+    finally:
+        _close_splits(splits)
     _, train_metrics, valid_metrics, test_metrics = outcome
     _dump(os.path.join(model_dir, 'results.pkl'), {'train': train_metrics, 'valid': valid_metrics, 'test': test_metrics})
     LOGGER.info('Fold %d done: results in %s', fold_num, model_dir)
     return model_dir
+
+
+# what a fold's metrics hold besides numbers and lists of numbers with one entry per class: the per-epoch histories (their length
+# differs from fold to fold under early stopping) and the parameter search's records
+NOT_AGGREGATED = ('loss_history', 'accuracy_history', 'search', 'search_params', 'search_params_best_values')
+
+
+def _aggregated_part(fold_metrics):
+    """aggregate_metrics over the keys of the first fold that hold a number or a list of numbers and are not in NOT_AGGREGATED"""
+    def numeric(v):
+        a = np.asarray(v)
+        return a.ndim <= 1 and a.size > 0 and a.dtype.kind in 'biuf'
+    keys = [k for k, v in fold_metrics[0].items() if k not in NOT_AGGREGATED and numeric(v)]
+    return aggregate_metrics([{k: fold[k] for k in keys} for fold in fold_metrics]) if keys else {}
+
+
+def _jsonable(v):
+    """NumPy scalars and arrays as Python numbers and lists, tuples as lists, every dictionary key as a string"""
+    if isinstance(v, dict):
+        return {k if isinstance(k, str) else str(k): _jsonable(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_jsonable(x) for x in v]
+    if isinstance(v, np.ndarray):
+        return _jsonable(v.tolist())
+    if isinstance(v, np.generic):
+        return v.item()
+    return v
+
+
+def cross_validate(features_dir, output_dir, model_type='svm', folds=None, fold_seed=None, preprocess_device=0,
+                   feature_mode='framewise', train_batch_size=64, patience=20, random_state=20171021, parameter_search=False,
+                   parameter_search_valid_fold=True, parameter_search_valid_ratio=0.15, parameter_search_train_with_valid=False,
+                   gsheet_id=None, google_dev_app_name=None, verbose=False, non_overlap=False, non_overlap_chunk_size=10,
+                   use_min_max=False, platt='device', **model_args):
+    """Every fold of a dataset in one run: what one train(model_type='mlp') or train_svm_fold (model_type='svm'; 'rf' raises as in
+    train) call per fold does -- the same per-fold directories and files, from the same arguments -- with the feature files read
+    and uploaded once (usc.FoldBank on preprocess_device; None keeps the folds and their preprocessing on the host) and every
+    fold's splits put together from them on the GPU, bit for bit the matrices usc.get_split stacks.
+
+    folds: the test folds to run, 1-based; None runs all of the dataset's.  fold_seed: an int seeds NumPy's global state
+    (np.random.seed) before each fold, so that fold k equals a separate per-fold call made after np.random.seed(fold_seed); None
+    leaves the global state alone, and the folds draw their shuffles one after the other from it.  platt: train_svm_fold's.
+    A fold's splits are closed before the next fold's are assembled.
+
+    Afterwards <output_dir>/classifier/<model_id>/cross_validation/<timestamp>/results.pkl and results.json hold
+    {'folds': the fold numbers, 'fold_dirs': their directories, 'train' / 'valid' / 'test': the list of the folds' metrics as
+    their results.pkl holds them, 'aggregate': {'train', 'valid', 'test'}: aggregate_metrics over the folds of every key whose
+    value is a number or a list of numbers}.  Not aggregated (NOT_AGGREGATED): loss_history and accuracy_history, whose lengths
+    differ between folds, and the search records search, search_params and search_params_best_values.  In results.json NumPy
+    values are plain numbers and the search's tuple keys are strings.  -> that directory."""
+    if model_type not in ('mlp', 'svm'):
+        raise ValueError(ONLY_MLP.format(model_type))
+    dataset, desc = _dataset_of(features_dir)
+    if dataset not in DATASET_NUM_CLASSES:
+        raise ValueError('the features directory must name a dataset right after "features/" (one of {})'.format(
+            ', '.join(sorted(DATASET_NUM_CLASSES))))
+    if parameter_search and not parameter_search_valid_fold:
+        raise ValueError(NO_SSS)
+    fold_args = (feature_mode, train_batch_size, patience, random_state, parameter_search, parameter_search_valid_fold,
+                 parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id, google_dev_app_name, verbose, non_overlap,
+                 non_overlap_chunk_size, use_min_max, preprocess_device)
+    fold_dirs = []
+    with FoldBank(features_dir, dataset, device=preprocess_device) as bank:
+        folds = list(range(1, bank.num_folds + 1)) if folds is None else [int(f) for f in folds]
+        for fold_num in folds:
+            if not 1 <= fold_num <= bank.num_folds:
+                raise ValueError('fold {} of {} ({} folds, counted from 1)'.format(fold_num, dataset, bank.num_folds))
+        for fold_num in folds:
+            made = []
+
+            def splits(with_valid_fold, fold_num=fold_num, made=made):
+                made.extend(bank.split(fold_num - 1, valid=with_valid_fold))
+                return tuple(made)
+            if fold_seed is not None:
+                np.random.seed(fold_seed)
+            try:
+                if model_type == 'mlp':
+                    fold_dirs.append(_mlp_fold(splits, features_dir, output_dir, fold_num, *fold_args, model_args))
+                else:
+                    fold_dirs.append(_svm_fold(splits, features_dir, output_dir, fold_num, *fold_args, platt, model_args))
+            finally:
+                _close_splits(made)          # also after a failure between the assembly and the fold's own clean-up
+
+    results = {'folds': folds, 'fold_dirs': fold_dirs}
+    per_fold = []
+    for d in fold_dirs:
+        with open(os.path.join(d, 'results.pkl'), 'rb') as fh:
+            per_fold.append(pk.load(fh))
+    for part in ('train', 'valid', 'test'):
+        results[part] = [r[part] for r in per_fold]
+    results['aggregate'] = {part: _aggregated_part(results[part]) for part in ('train', 'valid', 'test')}
+
+    out_dir = os.path.join(output_dir, 'classifier', _model_id(desc, feature_mode, non_overlap, use_min_max, model_type), 'cross_validation',
+                           datetime.datetime.now().strftime('%Y%m%d%H%M%S'))
+    os.makedirs(out_dir, exist_ok=True)
+    _dump(os.path.join(out_dir, 'results.pkl'), results)
+    with open(os.path.join(out_dir, 'results.json'), 'w') as fh:
+        json.dump(_jsonable(results), fh)
+    LOGGER.info('Cross-validation of %d folds done: results in %s', len(folds), out_dir)
+    return out_dir

@@ -8,6 +8,7 @@
 //   feat_affine32      x * scale + shift, two float32 roundings             (MinMaxScaler.transform)
 //   feat_standardize   (x - mean) / scale through float64, two float32 roundings (StandardScaler.transform)
 //   feat_file_stats    compute_stats_features of every file (:243-253)
+//   feat_assemble      row ranges of other matrices -> a new matrix  (the np.vstack of data/usc/folds.py:24-112)
 //
 // The arithmetic whose roundings are part of the contract is written with the __f*_rn / __d*_rn intrinsics, which the compiler
 // never contracts into a fused multiply-add; the file is also built with -ffp-contract=off (_build.py).
@@ -15,8 +16,10 @@
 
 #include <algorithm>
 #include <string>
+#include <vector>
 
 #include "../../include/l3hip.h"
+#include "feat_assemble.h"
 #include "featprep.h"
 
 namespace l3 {
@@ -234,6 +237,56 @@ __global__ __launch_bounds__(64) void feat_file_stats_kernel(const float* __rest
     o[0] = lo, o[D] = hi, o[2 * D] = median, o[3 * D] = mean32, o[4 * D] = var32, o[5 * D] = skew, o[6 * D] = kurt;
 }
 
+// ---- assembly: the output rows in spans of `rows_per_wave`, one wave per span ----------------------------------------------------------
+// table[s] = {address of segment s's first source row, its first output row}, S entries and the sentinel {nullptr, n}: segment s
+// owns the output rows [table[s].first, table[s + 1].first), none of them empty.  A wave finds the segment of its first row by
+// bisection and walks on from there; inside a segment source and destination are both contiguous, so the piece of a segment that
+// falls into the span is one flat copy: four floats per lane where both ends are 16-byte aligned (then a tail of fewer than
+// four), one float per lane otherwise.  Everything is read once and written once: non-temporal.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int ASM_BLOCK = 256;           // four waves
+constexpr int ASM_WAVE_FLOATS = 4096;    // what one wave moves when rows are shorter than that (16 KiB)
+
+__global__ __launch_bounds__(ASM_BLOCK) void feat_assemble_kernel(const AssembleEntry* __restrict__ table, int64_t S, float* __restrict__ y,
+                                                                 int64_t n, int64_t D, int rows_per_wave) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * (ASM_BLOCK / 64) + (threadIdx.x >> 6);
+    const int64_t r0 = wave * rows_per_wave;
+    if (r0 >= n) return;
+    const int64_t r1 = min(n, r0 + rows_per_wave);
+    // the last s in [0, S) with table[s].first <= r0 (table[0].first == 0)
+    int64_t s = 0, hi = S;
+    while (hi - s > 1) {
+        const int64_t mid = (s + hi) >> 1;
+        if (table[mid].first <= r0)
+            s = mid;
+        else
+            hi = mid;
+    }
+    int64_t r = r0;
+    while (r < r1) {
+        const int64_t first = table[s].first, next = table[s + 1].first;          // s + 1 <= S: the sentinel
+        const int64_t e = min(r1, next);
+        const float* src = table[s].src + (r - first) * D;
+        float* dst = y + r * D;
+        const int len = (int)((e - r) * D);          // <= max(ASM_WAVE_FLOATS, D) <= 2^21
+        if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
+            const int nv = len >> 2;
+#pragma unroll 4
+            for (int i = lane; i < nv; i += 64)
+                __builtin_nontemporal_store(__builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src) + i),
+                                            reinterpret_cast<f32x4*>(dst) + i);
+            const int t = (nv << 2) + lane;
+            if (t < len) __builtin_nontemporal_store(__builtin_nontemporal_load(src + t), dst + t);
+        } else {
+#pragma unroll 4
+            for (int i = lane; i < len; i += 64) __builtin_nontemporal_store(__builtin_nontemporal_load(src + i), dst + i);
+        }
+        r = e;
+        ++s;
+    }
+}
+
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
 bool vec4(const l3_feat* f) { return f->D % 4 == 0; }          // hipMalloc'ed base, rows of a multiple of 16 bytes
 
@@ -333,6 +386,49 @@ int l3_feat_download(l3_feat* f, int64_t lo, int64_t hi, float* dst) {
     if (hipMemcpyAsync(dst, f->x + lo * f->D, (size_t)((hi - lo) * f->D) * sizeof(float), hipMemcpyDeviceToHost, f->s) != hipSuccess ||
         !finished(f))
         return fail(L3_EHIP, "l3_feat_download: copy from the device failed");
+    return L3_OK;
+}
+
+int l3_feat_assemble(int device, const l3_feat_segment* segs, int64_t n_segs, l3_feat** out) {
+    if (!out) return fail(L3_EINVAL, "l3_feat_assemble: out is NULL");
+    std::vector<FeatSegView> views;
+    for (int64_t i = 0; segs && i < n_segs; ++i) {
+        const l3_feat* g = segs[i].src;
+        views.push_back(g ? FeatSegView{true, g->device, g->n, g->D, g->x, segs[i].lo, segs[i].hi}
+                          : FeatSegView{false, 0, 0, 0, nullptr, segs[i].lo, segs[i].hi});
+    }
+    AssemblePlan plan;
+    std::string err;
+    if (!plan_assemble(device, views.data(), segs ? n_segs : 0, &plan, &err)) return fail(L3_EINVAL, err);
+    if (!device_ok(device)) return fail(L3_EHIP, no_gpu_message("l3_feat_assemble", device));
+    // whatever a source's stream still holds comes first (every l3_feat call has finished when it returns, so this waits for nothing
+    // unless the caller runs a call on a source from another thread, which the handle's contract forbids anyway)
+    const l3_feat* seen = nullptr;
+    for (int64_t i = 0; i < n_segs; ++i)
+        if (segs[i].src != seen) {
+            seen = segs[i].src;
+            if (hipStreamSynchronize(seen->s) != hipSuccess) return fail(L3_EHIP, "l3_feat_assemble: a source's stream failed");
+        }
+    l3_feat* f = new l3_feat();
+    f->device = device, f->n = plan.rows, f->D = plan.D;
+    f->x = f->bufs.alloc<float>((size_t)(plan.rows * plan.D));
+    AssembleEntry* table = nullptr;
+    if (f->x && hipStreamCreateWithFlags(&f->s, hipStreamNonBlocking) == hipSuccess) table = f->bufs.put(plan.table.data(), plan.table.size(), f->s);
+    if (!table) {
+        l3_feat_destroy(f);
+        return fail(L3_ENOMEM, "l3_feat_assemble: device allocation of " + std::to_string(plan.rows * plan.D * 4) + " bytes failed");
+    }
+    const int rpw = (int)std::max<int64_t>(1, ASM_WAVE_FLOATS / plan.D);
+    const int64_t waves = (plan.rows + rpw - 1) / rpw, per_block = ASM_BLOCK / 64;
+    hipLaunchKernelGGL(feat_assemble_kernel, dim3((unsigned)((waves + per_block - 1) / per_block)), dim3(ASM_BLOCK), 0, f->s, table,
+                       (int64_t)plan.table.size() - 1, f->x, plan.rows, plan.D, rpw);
+    const bool ok = finished(f);
+    f->bufs.release(table);
+    if (!ok) {
+        l3_feat_destroy(f);
+        return fail(L3_EHIP, "l3_feat_assemble: HIP error");
+    }
+    *out = f;
     return L3_OK;
 }
 

@@ -11,6 +11,9 @@ Quirks kept on purpose:
 
 preprocess_split_data(..., device=<index>) runs the passes over the (n, D) matrices on the GPU (csrc/featprep.hip):
 the splits' 'features' become DeviceFeatures, which classifier.MLPModel takes without a trip through the host.
+
+FoldBank reads every fold of a dataset once and puts the splits of any cross-validation fold together from them, on the GPU by one
+copy kernel per split (l3_feat_assemble): what classifier.cross_validate runs on.
 """
 import os
 
@@ -65,6 +68,12 @@ def get_valid_fold_idx(test_fold_idx, num_folds):
     return (test_fold_idx + num_folds - 1) % num_folds
 
 
+def _no_training_fold(num_folds, test_fold_idx, valid):
+    # dcase2013 has two folds: a test and a validation fold leave none (the reference fails inside np.vstack)
+    return ValueError('No training fold left: {} folds, test fold {}, validation fold held out: {}; use the parameter '
+                      'search without a validation fold'.format(num_folds, test_fold_idx + 1, valid))
+
+
 def get_train_folds(feature_dir, test_fold_idx, num_folds, valid=True):
     """Every fold but the test fold (and the validation fold when `valid`), augmented files included, stacked; each fold's
     file_idxs continue after the rows of the folds before it (data/usc/folds.py:82-112)."""
@@ -73,9 +82,7 @@ def get_train_folds(feature_dir, test_fold_idx, num_folds, valid=True):
         held_out.add(get_valid_fold_idx(test_fold_idx, num_folds))
     folds = [get_fold(feature_dir, i, augment=True) for i in range(num_folds) if i not in held_out]
     if not folds:
-        # dcase2013 has two folds: a test and a validation fold leave none (the reference fails inside np.vstack)
-        raise ValueError('No training fold left: {} folds, test fold {}, validation fold held out: {}; use the parameter '
-                         'search without a validation fold'.format(num_folds, test_fold_idx + 1, valid))
+        raise _no_training_fold(num_folds, test_fold_idx, valid)
     first_row = np.cumsum([0] + [f['features'].shape[0] for f in folds[:-1]])
     return {
         'features': np.vstack([f['features'] for f in folds]),
@@ -85,14 +92,132 @@ def get_train_folds(feature_dir, test_fold_idx, num_folds, valid=True):
     }
 
 
-def get_split(feature_dir, test_fold_idx, dataset_name, valid=True):
-    """-> (train, valid or None, test) for one cross-validation fold (data/usc/folds.py:65-75)"""
+def _num_folds(dataset_name):
     num_folds = DATASET_NUM_FOLDS.get(dataset_name)
     if num_folds is None:
         raise ValueError('unknown dataset {!r}: one of {}'.format(dataset_name, ', '.join(sorted(DATASET_NUM_FOLDS))))
+    return num_folds
+
+
+def get_split(feature_dir, test_fold_idx, dataset_name, valid=True):
+    """-> (train, valid or None, test) for one cross-validation fold (data/usc/folds.py:65-75)"""
+    num_folds = _num_folds(dataset_name)
     train = get_train_folds(feature_dir, test_fold_idx, num_folds, valid=valid)
     held = get_fold(feature_dir, get_valid_fold_idx(test_fold_idx, num_folds)) if valid else None
     return train, held, get_fold(feature_dir, test_fold_idx)
+
+
+class FoldBank(object):
+    """Every fold of a dataset read once and kept, so that the splits of all cross-validation folds come from one pass over the
+    files: split() gives what get_split gives, with 'features' put together from the kept folds -- on GPU `device` by one copy
+    kernel per split (DeviceFeatures.assemble; the download has the bits of get_split's array), or with device=None in NumPy.
+
+    Per fold it keeps what get_fold(..., augment=True) reads: the rows of all files in os.listdir order (one DeviceFeatures, or
+    one array), and on the host each file's label, its row range, the directory listing and which files are US8K augmented
+    copies.  A validation or test fold leaves those copies out, so it is put together from the other files' row ranges and its
+    file_idxs are numbered as get_fold(augment=False) numbers them.
+
+    Memory: the bank holds the dataset once and a split assembled from it holds up to all of it again; close the splits'
+    DeviceFeatures when a fold is done, and the bank (close(), or a with block) at the end."""
+
+    def __init__(self, feature_dir, dataset_name, device=0):
+        self.feature_dir, self.dataset_name = feature_dir, dataset_name
+        self.device = None if device is None else int(device)
+        self.num_folds = _num_folds(dataset_name)
+        self.folds = []
+        try:
+            for i in range(self.num_folds):
+                self.folds.append(self._read_fold(i))
+        except Exception:
+            self.close()
+            raise
+
+    def _read_fold(self, fold_idx):
+        fold_dir = os.path.join(self.feature_dir, 'fold%d' % (fold_idx + 1))
+        names = os.listdir(fold_dir)
+        loaded = [load_feature_file(os.path.join(fold_dir, n)) for n in names]
+        frames = [x for x, _ in loaded]
+        features = np.vstack(frames)
+        if self.device is not None:
+            features = DeviceFeatures(features, self.device)
+        return {
+            'features': features,
+            'labels': [lab for _, lab in loaded],
+            'file_idxs': _row_ranges([x.shape[0] if x.ndim > 1 else 1 for x in frames]),
+            'filenames': names,
+            'augmented': np.array([_is_augmented_us8k(fold_dir, n) for n in names], dtype=bool),
+        }
+
+    @staticmethod
+    def _labels(labels):
+        # get_fold's rule, decided by the first file it reads
+        per_file = isinstance(labels[0], int) or np.ndim(labels[0]) == 0
+        return np.array(labels) if per_file else np.concatenate(labels)
+
+    def _segments(self, fold_idx, augment):
+        """-> (row ranges of the fold's matrix that make up the part, its labels, its file_idxs)"""
+        fold = self.folds[fold_idx]
+        keep = np.ones(len(fold['filenames']), dtype=bool) if augment else ~fold['augmented']
+        ranges = fold['file_idxs'][keep]
+        labels = self._labels([lab for lab, k in zip(fold['labels'], keep) if k])
+        # neighbouring files are one range
+        starts = np.flatnonzero(np.r_[True, ranges[1:, 0] != ranges[:-1, 1]])
+        runs = [(int(ranges[a, 0]), int(ranges[b - 1, 1])) for a, b in zip(starts, np.r_[starts[1:], len(ranges)])]
+        return [(fold['features'], lo, hi) for lo, hi in runs], labels, _row_ranges(ranges[:, 1] - ranges[:, 0])
+
+    def _assemble(self, segments):
+        if self.device is not None:
+            return DeviceFeatures.assemble(segments, device=self.device)
+        return np.concatenate([x[lo:hi] for x, lo, hi in segments])
+
+    def split(self, test_fold_idx, valid=True):
+        """-> (train, valid or None, test) as get_split(feature_dir, test_fold_idx, dataset_name, valid) returns them; 'features' is a
+        new DeviceFeatures (a new array with device=None) that the caller owns"""
+        self._open()
+        held_out = {test_fold_idx}
+        if valid:
+            held_out.add(get_valid_fold_idx(test_fold_idx, self.num_folds))
+        train_folds = [i for i in range(self.num_folds) if i not in held_out]
+        if not train_folds:
+            raise _no_training_fold(self.num_folds, test_fold_idx, valid)
+        held_folds = ([get_valid_fold_idx(test_fold_idx, self.num_folds)] if valid else []) + [test_fold_idx]
+        train_parts = [self._segments(i, True) for i in train_folds]
+        first_row = np.cumsum([0] + [int(idxs[-1, 1]) for _, _, idxs in train_parts[:-1]])
+        splits = [{
+            'labels': np.concatenate([labels for _, labels, _ in train_parts]),
+            'file_idxs': np.vstack([idxs + off for (_, _, idxs), off in zip(train_parts, first_row)]),
+            'filenames': [name for i in train_folds for name in self.folds[i]['filenames']],
+        }]
+        segments = [[seg for segs, _, _ in train_parts for seg in segs]]
+        for i in held_folds:
+            segs, labels, idxs = self._segments(i, False)
+            splits.append({'labels': labels, 'file_idxs': idxs, 'filenames': list(self.folds[i]['filenames'])})
+            segments.append(segs)
+        try:
+            for d, segs in zip(splits, segments):
+                d['features'] = self._assemble(segs)
+        except Exception:
+            for d in splits:          # what was assembled before the failure; the bank itself is untouched
+                if isinstance(d.get('features'), DeviceFeatures):
+                    d['features'].close()
+            raise
+        return (splits[0], splits[1], splits[2]) if valid else (splits[0], None, splits[1])
+
+    def _open(self):
+        if self.folds is None:
+            raise ValueError('the FoldBank is closed')
+
+    def close(self):
+        for fold in self.folds or []:
+            if isinstance(fold['features'], DeviceFeatures):
+                fold['features'].close()
+        self.folds = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 # ---- scalers with sklearn.preprocessing's arithmetic ----------------------------------------------------------------------------
@@ -221,6 +346,19 @@ class DeviceFeatures(object):
         self.device = int(device)
         self.handle = _lib.Features(X if X.ndim == 2 else X.reshape(len(X), -1), device=self.device)
 
+    @classmethod
+    def from_handle(cls, handle):
+        """the DeviceFeatures that owns an existing _lib.Features"""
+        self = cls.__new__(cls)
+        self.device, self.handle = handle.device, handle
+        return self
+
+    @classmethod
+    def assemble(cls, segments, device=0):
+        """a new matrix on `device` from the rows [lo, hi) of each (DeviceFeatures, lo, hi), in order, copied there by one kernel
+        (_lib.Features.assemble); the sources stay as they are"""
+        return cls.from_handle(_lib.Features.assemble([(f.handle, lo, hi) for f, lo, hi in segments], device=device))
+
     @property
     def shape(self):
         return self.handle.shape
@@ -250,9 +388,15 @@ def _preprocess_on_device(train_data, valid_data, test_data, feature_mode, non_o
     arithmetic and the draw of the permutation stay on the host, in the host path's own expressions"""
     everything = _present(train_data, valid_data, test_data)
     for d in everything:          # before anything is uploaded or replaced
-        _require_float32(np.asarray(d['features']))
-    for d in everything:
-        d['features'] = DeviceFeatures(d['features'], device)
+        if isinstance(d['features'], DeviceFeatures):
+            if d['features'].device != int(device):
+                raise ValueError('a split\'s features are on device {}, the preprocessing runs on device {}'.format(
+                    d['features'].device, device))
+        else:
+            _require_float32(np.asarray(d['features']))
+    for d in everything:          # a resident split (FoldBank.split) is preprocessed where it is
+        if not isinstance(d['features'], DeviceFeatures):
+            d['features'] = DeviceFeatures(d['features'], device)
     feats = [d['features'].handle for d in everything]
     if non_overlap:
         for d, f in zip(everything, feats):
@@ -296,7 +440,8 @@ def preprocess_split_data(train_data, valid_data, test_data, feature_mode='frame
     train_data['file_idxs'] is a list holding, per file, the new positions of its rows.
 
     device: None runs everything in NumPy on the host.  A GPU index runs the same stages with the passes over the feature
-    matrices on that GPU (float32 features only): every split's 'features' is then a DeviceFeatures, min-max scaled values are
+    matrices on that GPU (float32 features only; NumPy arrays are uploaded, DeviceFeatures on that GPU -- FoldBank.split -- are
+    used where they are, and one on another GPU is a ValueError): every split's 'features' is then a DeviceFeatures, min-max scaled values are
     the host path's bits, and the standardiser's mean_ / var_ agree with the host's to the rounding of a float64 sum."""
     if feature_mode not in ('framewise', 'stats'):
         raise ValueError("feature_mode must be 'framewise' or 'stats', not {!r}".format(feature_mode))
@@ -304,6 +449,8 @@ def preprocess_split_data(train_data, valid_data, test_data, feature_mode='frame
         return _preprocess_on_device(train_data, valid_data, test_data, feature_mode, non_overlap, non_overlap_chunk_size,
                                      use_min_max, device)
     everything = _present(train_data, valid_data, test_data)
+    if any(isinstance(d['features'], DeviceFeatures) for d in everything):
+        raise ValueError('a split\'s features are on a GPU (DeviceFeatures) and device is None: name the device, or download them')
     if non_overlap:
         for d in everything:
             remove_data_overlap(d, chunk_size=non_overlap_chunk_size)
