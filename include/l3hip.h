@@ -642,8 +642,8 @@ int l3_op_vggish_postprocess(int device, const float *emb, int64_t n, const floa
  * preprocess_split_data's passes over the (n, D) feature matrix on the GPU: the row selection of remove_data_overlap (:60-73) and of
  * the final shuffle (:143-148), MinMaxScaler's fit and transform (:107-113), compute_stats_features per file (:76-85,243-253) and
  * StandardScaler's fit and transform (:131-141).  A handle separate from l3_engine, l3_mlp and l3_svm: it owns ONE float32 row-major
- * matrix on one device and one stream; every operation replaces that matrix and has finished when the call returns; calls on one
- * handle are not re-entrant.  Every D-sized piece of scaler arithmetic (ranges, scales, square roots, the zero rule of sklearn's
+ * matrix on one device and one stream; every operation replaces that matrix (l3_feat_assemble and l3_feat_split only read their
+ * sources and make new handles) and has finished when the call returns; calls on one handle are not re-entrant.  Every D-sized piece of scaler arithmetic (ranges, scales, square roots, the zero rule of sklearn's
  * _handle_zeros) stays with the caller.  Deterministic: no float atomics, and the sums over rows run over fixed chunks of
  * L3_FEAT_CHUNK_ROWS rows whose partial results are added in chunk order, whatever the launch geometry.  NaN inputs are out of
  * contract (the extrema and the median order values as finite floats; -0.0 sorts below +0.0).  Errors: l3_last_error(NULL). */
@@ -672,6 +672,19 @@ int l3_feat_assemble(int device, const l3_feat_segment *segs, int64_t n_segs, l3
 /* X <- X[rows]: n_out >= 1 host indices, each in [0, n) (else L3_EINVAL, and the matrix stays as it was).  The caller builds the
  * table -- every chunk_size-th row of each file, or the shuffle's permutation -- and the device moves the rows. */
 int l3_feat_gather(l3_feat *f, const int64_t *rows, int64_t n_out);
+/* src[rows_a] and src[rows_b] as NumPy's integer indexing gives them, as two NEW handles on src's device, written by ONE kernel launch
+ * (train_param_search's cut of the training rows into a search part and a validation part, classifier/train.py:416-423).  src is
+ * only read: it keeps its matrix and stays usable.  n_a >= 1; n_b == 0 with rows_b and out_b both NULL is a plain out-of-place take.
+ * Host int64 indices in any order, repeats allowed; each output has at most 2^31 - 1 rows.  L3_EINVAL, with *out_a and *out_b
+ * untouched and nothing allocated on the device: an index outside [0, n) (the message names the table and the position, as in
+ * "rows_b[3] = 9 outside [0, 9)"), n_a < 1, a missing src / rows_a / out_a, or n_b that does not match rows_b and out_b (both NULL
+ * for 0, both given otherwise).  The two tables go to the device once, in one buffer; output rows are cut into spans of about 4096
+ * floats, one wave per span; a row moves as 16-byte accesses when D % 4 == 0 and as 4-byte accesses otherwise, the same bits
+ * either way; no atomics, deterministic.
+ * Ordering as l3_feat_assemble's: src's stream is synchronised first, each new handle gets a stream of its own, and both outputs
+ * have finished when the call returns. */
+int l3_feat_split(const l3_feat *src, const int64_t *rows_a, int64_t n_a, const int64_t *rows_b, int64_t n_b, l3_feat **out_a,
+                  l3_feat **out_b);
 /* np.min / np.max(X, axis=0), D floats each, exact */
 int l3_feat_minmax(l3_feat *f, float *min_out, float *max_out);
 /* MinMaxScaler.transform's `X *= scale_; X += min_` on a float32 matrix: x <- fl32(fl32(x * scale[j]) + shift[j]), two float32

@@ -211,6 +211,7 @@ SIGNATURES = {
     'l3_feat_download': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     'l3_feat_assemble': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     'l3_feat_gather': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_feat_split': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     'l3_feat_minmax': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'l3_feat_affine32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'l3_feat_moments': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1039,6 +1040,22 @@ class Features(object):
     def gather(self, rows):
         r = _i64(rows)
         check(self.lib.l3_feat_gather(self.h, _ptr(r), r.size))
+
+    def split(self, rows_a, rows_b=None):
+        """X[rows_a] and X[rows_b] as two new Features on this device, written by one kernel (l3_feat_split); this matrix stays as
+        it is.  rows_b None (or empty): a plain out-of-place take -> (Features, None)."""
+        a = _i64(rows_a).reshape(-1)
+        b = None if rows_b is None else _i64(rows_b).reshape(-1)
+        if b is not None and b.size == 0:
+            b = None
+        out = []
+        for _ in range(1 if b is None else 2):
+            part = type(self).__new__(type(self))
+            part.lib, part.h, part.device = self.lib, C.c_void_p(), self.device
+            out.append(part)
+        check(self.lib.l3_feat_split(self.h, _ptr(a), a.size, _ptr(b), 0 if b is None else b.size, C.byref(out[0].h),
+                                     C.byref(out[1].h) if b is not None else None))
+        return out[0], (out[1] if b is not None else None)
 
     def minmax(self):
         d = self.shape[1]

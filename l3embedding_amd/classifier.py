@@ -7,7 +7,11 @@ it.  Deviations from the reference, all deliberate:
     are not reproducible); the Glorot initialisation is seeded with random_state too;
   * the random start delay and the Google Sheets logging of train() are skipped; config.json has git_commit None;
   * the scalers are pickled with `pickle` (the reference uses sklearn's joblib; these are NumPy restatements, usc.py);
-  * the random forest and StratifiedShuffleSplit (sklearn on the host) are not built: they raise;
+  * the random forest (sklearn on the host) is not built: it raises;
+  * the parameter search without a validation fold (train_param_search :408-423, :470-479) cuts the training rows with
+    usc.stratified_shuffle_split, a NumPy restatement of sklearn's StratifiedShuffleSplit, and only when the caller gives the
+    split's seed (split_random_state / parameter_search_split_seed; the reference passes none, so its split differs from run to
+    run): without a seed it raises as before.  Rows on the GPU are cut there (DeviceFeatures.split, one kernel) and stay there;
   * cross_validate runs every fold of a dataset in one call from folds read once (usc.FoldBank) and summarises them with
     aggregate_metrics (classifier/metrics.py:49-78); the reference runs one job per fold;
   * the SVM (train_svm, classifier/train.py:79-166) trains on the GPU (svm.py, csrc/svm.hip); its probability estimates draw the
@@ -29,7 +33,7 @@ import numpy as np
 from . import _lib, callbacks, kerasfile
 from . import svm as _svm
 from .svm import SVC, hinge_loss  # noqa: F401  (re-exported: the reference imports them into classifier/train.py)
-from .usc import DeviceFeatures, FoldBank, get_split, preprocess_split_data
+from .usc import DeviceFeatures, FoldBank, get_split, preprocess_split_data, stratified_shuffle_split
 
 LOGGER = logging.getLogger('classifier')
 
@@ -406,27 +410,57 @@ def _on_host(data):
     return data
 
 
+def _cut_for_search(train_data, valid_ratio, split_random_state):
+    """classifier/train.py:412-423 -> (search part, validation part), {'features', 'labels'} each: the training rows cut by
+    usc.stratified_shuffle_split(labels, valid_ratio, split_random_state).  A DeviceFeatures is cut on its GPU by one
+    DeviceFeatures.split into two new ones (the caller closes them: _close_splits), a NumPy array by indexing: the same bits."""
+    labels = np.asarray(train_data['labels'])
+    train_idx, valid_idx = stratified_shuffle_split(labels, valid_ratio, split_random_state)
+    features = train_data['features']
+    if isinstance(features, DeviceFeatures):
+        kept, held = features.split(train_idx, valid_idx)
+    else:
+        kept, held = features[train_idx], features[valid_idx]
+    return {'features': kept, 'labels': labels[train_idx]}, {'features': held, 'labels': labels[valid_idx]}
+
+
 def train_param_search(train_data, valid_data, test_data, model_dir, train_func, search_space, valid_ratio=0.15,
-                       train_with_valid=True, **kwargs):
-    """classifier/train.py:394-492 on the validation-fold path: train_func once per point of the grid (the product of the
-    search_space values, in key order), keep the point with the best validation accuracy (the first one on ties), then either
-    retrain on train + valid shuffled together with no validation data (train_with_valid) or keep that run.  Without a
-    validation fold the reference splits with sklearn's StratifiedShuffleSplit, which is not built."""
+                       train_with_valid=True, split_random_state=None, **kwargs):
+    """classifier/train.py:394-492: train_func once per point of the grid (the product of the search_space values, in key
+    order), keep the point with the best validation accuracy (the first one on ties), then either retrain with no validation
+    data (train_with_valid) or keep that run.  With a validation fold the search runs on (train, valid) and the retrain on the two
+    shuffled together.  Without one (valid_data None) the reference cuts valid_ratio of the training rows off with sklearn's
+    StratifiedShuffleSplit: split_random_state, an int, is the seed of that cut (_cut_for_search), the search runs on its two
+    parts, the retrain on the whole of train_data as it is, and the parts are closed at the end; None refuses (NO_SSS)."""
+    cut = ()
     if not valid_data:
-        raise ValueError(NO_SSS)
+        if split_random_state is None:
+            raise ValueError(NO_SSS)
+        cut = _cut_for_search(train_data, valid_ratio, split_random_state)
+    try:
+        return _param_search(train_data, valid_data, test_data, model_dir, train_func, search_space, train_with_valid, cut, kwargs)
+    finally:
+        _close_splits(cut)
+
+
+def _param_search(train_data, valid_data, test_data, model_dir, train_func, search_space, train_with_valid, cut, kwargs):
+    """train_param_search on (train_data, valid_data), or on the two parts of `cut` when it is not empty"""
+    search_train, search_valid = cut or (train_data, valid_data)
     names = list(search_space)
     runs = []                       # (point, model, train metrics, valid metrics, test metrics)
     for point in product(*(search_space[n] for n in names)):
         LOGGER.info('Search point %s', dict(zip(names, point)))
         kwargs.update(zip(names, point))
-        runs.append((point,) + tuple(train_func(train_data, valid_data, test_data, model_dir, **kwargs)))
+        runs.append((point,) + tuple(train_func(search_train, search_valid, test_data, model_dir, **kwargs)))
     accuracies = [run[3]['accuracy'] for run in runs]
     chosen = runs[int(np.argmax(accuracies))]
     point = chosen[0]
     LOGGER.info('Chosen %s (validation accuracy %s)', dict(zip(names, point)), chosen[3]['accuracy'])
     kwargs.update(zip(names, point))
 
-    if train_with_valid:
+    if train_with_valid and cut:          # :471-474: the entire training set, neither merged nor shuffled
+        model, train_metrics, _, test_metrics = train_func(train_data, None, test_data, model_dir, **kwargs)
+    elif train_with_valid:
         merged_labels = np.concatenate((train_data['labels'], valid_data['labels']))
         mix = np.random.permutation(merged_labels.size)
         merged = {'features': np.vstack((train_data['features'], valid_data['features']))[mix], 'labels': merged_labels[mix]}
@@ -446,7 +480,7 @@ SVM_SEARCH_CS = (0.1, 1, 10, 100, 1000)        # classifier/train.py:609
 
 def train_svm_search(train_data, valid_data, test_data, model_dir, Cs=SVM_SEARCH_CS, train_with_valid=False, platt='device', C=None,
                      kernel='rbf', num_classes=10, tol=0.001, max_iterations=-1, verbose=False, random_state=12345678,
-                     max_entries=None, **kwargs):
+                     max_entries=None, valid_ratio=0.15, split_random_state=None, **kwargs):
     """train_param_search(..., train_func=train_svm, search_space={'C': Cs}, evaluate_on_device=True) with the grid fitted in one
     pass: one svm.fit_grid over the training split (NumPy rows or usc.DeviceFeatures, resident once), one SVC.evaluate per split
     and model, the cost with the best validation accuracy (the first one on ties), and with train_with_valid the retrain on
@@ -454,22 +488,40 @@ def train_svm_search(train_data, valid_data, test_data, model_dir, Cs=SVM_SEARCH
     there, anything else on the host: the same bits).  -> the same tuple (model, train_metrics,
     valid_metrics, test_metrics) with the same search records.  platt: svm.fit_grid's ('host': Platt's sigmoids as SVC.fit
     fits them, so every number equals that of the separate fits).  model_dir/model.pkl holds the returned model (the loop over
-    train_svm leaves the one it fitted last there).  C is ignored (the search sets it); the other arguments are train_svm's."""
+    train_svm leaves the one it fitted last there).  C is ignored (the search sets it); the other arguments are train_svm's.
+    Without a validation fold (valid_data None): train_param_search's cut of valid_ratio of the training rows, seeded by
+    split_random_state (None refuses, NO_SSS); the grid is fitted and scored on its two parts, and train_with_valid refits the
+    chosen cost on the whole of train_data as it is."""
+    cut = ()
     if not valid_data:
-        raise ValueError(NO_SSS)
-    Cs = list(Cs)
-    params = dict(probability=True, kernel=kernel, max_iter=max_iterations, tol=tol, random_state=random_state, verbose=verbose)
+        if split_random_state is None:
+            raise ValueError(NO_SSS)
+        cut = _cut_for_search(train_data, valid_ratio, split_random_state)
+    try:
+        return _svm_search(train_data, valid_data, test_data, model_dir, list(Cs), train_with_valid, platt, num_classes, max_entries, cut,
+                           dict(probability=True, kernel=kernel, max_iter=max_iterations, tol=tol, random_state=random_state,
+                                verbose=verbose))
+    finally:
+        _close_splits(cut)
+
+
+def _svm_search(train_data, valid_data, test_data, model_dir, Cs, train_with_valid, platt, num_classes, max_entries, cut, params):
+    """train_svm_search on (train_data, valid_data), or on the two parts of `cut` when it is not empty"""
+    search_train, search_valid = cut or (train_data, valid_data)
     LOGGER.info('Fitting the grid C = %s', Cs)
-    models = _svm.fit_grid(train_data['features'], train_data['labels'], Cs, platt=platt, max_entries=max_entries, **params)
+    models = _svm.fit_grid(search_train['features'], search_train['labels'], Cs, platt=platt, max_entries=max_entries, **params)
     runs = []                       # (point, model, train metrics, valid metrics, test metrics)
     for c, clf in zip(Cs, models):
         LOGGER.info('Search point %s', {'C': c})
-        runs.append(((c,), clf) + _svm_metrics_on_device(clf, train_data, valid_data, test_data, num_classes))
+        runs.append(((c,), clf) + _svm_metrics_on_device(clf, search_train, search_valid, test_data, num_classes))
     chosen = runs[int(np.argmax([run[3]['accuracy'] for run in runs]))]
     point = chosen[0]
     LOGGER.info('Chosen %s (validation accuracy %s)', {'C': point[0]}, chosen[3]['accuracy'])
 
-    if train_with_valid:
+    if train_with_valid and cut:          # classifier/train.py:471-474: the entire training set, neither merged nor shuffled
+        model = _svm.fit_grid(train_data['features'], train_data['labels'], [point[0]], platt=platt, max_entries=max_entries, **params)[0]
+        train_metrics, _, test_metrics = _svm_metrics_on_device(model, train_data, None, test_data, num_classes)
+    elif train_with_valid:
         merged_labels = np.concatenate((train_data['labels'], valid_data['labels']))
         mix = np.random.permutation(merged_labels.size)
         tx, vx = train_data['features'], valid_data['features']
@@ -522,7 +574,7 @@ def _dump(path, obj):
 def _start_fold(features_dir, output_dir, fold_num, model_type, feature_mode, train_batch_size, patience, random_state,
                 parameter_search, parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid,
                 gsheet_id, google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device,
-                model_args, splits=None):
+                model_args, splits=None, parameter_search_split_seed=None):
     """what a fold of any model type begins with (classifier/train.py:495-603): the run's directory, config.json, the fold's
     splits preprocessed, the two scalers pickled -> (model_dir, dataset, splits).  splits: a function of (with_valid_fold) that
     gives the fold's (train, valid or None, test) in place of usc.get_split (cross_validate's come from its FoldBank)."""
@@ -547,6 +599,8 @@ def _start_fold(features_dir, output_dir, fold_num, model_type, feature_mode, tr
                     git_commit=None, gsheet_id=gsheet_id, google_dev_app_name=google_dev_app_name)
     if preprocess_device is not None:
         settings['preprocess_device'] = preprocess_device
+    if parameter_search_split_seed is not None:
+        settings['parameter_search_split_seed'] = parameter_search_split_seed
     settings.update(model_args)
     with open(os.path.join(model_dir, 'config.json'), 'w') as fh:
         json.dump(settings, fh)
@@ -566,19 +620,24 @@ def _start_fold(features_dir, output_dir, fold_num, model_type, feature_mode, tr
 def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='framewise', train_batch_size=64, patience=20,
           random_state=20171021, parameter_search=False, parameter_search_valid_fold=True, parameter_search_valid_ratio=0.15,
           parameter_search_train_with_valid=False, gsheet_id=None, google_dev_app_name=None, verbose=False, non_overlap=False,
-          non_overlap_chunk_size=10, use_min_max=False, preprocess_device=None, **model_args):
+          non_overlap_chunk_size=10, use_min_max=False, preprocess_device=None, parameter_search_split_seed=None, **model_args):
     """classifier/train.py:495-709 for model_type='mlp': one cross-validation fold (fold_num is 1-based) of the features under
     `features_dir` (its path names the dataset after 'features/'), written to
     <output_dir>/classifier/<features desc>/<mode>/<overlap>/<min-max>/mlp/fold<N>/<timestamp>/: config.json,
     min_max_scaler.pkl, stdizer.pkl, model.h5, history_checkpoint.pkl, history_csvlog.csv, results.pkl.
     preprocess_device: a GPU index preprocesses the folds on that GPU (usc.preprocess_split_data(device=...)) and, without a
     parameter search, hands them to the MLP there; config.json names it only when it is set.
+    parameter_search_split_seed: an int lets parameter_search=True, parameter_search_valid_fold=False run: the search is made on a
+    stratified cut of parameter_search_valid_ratio of the training rows, drawn from this seed (train_param_search's
+    split_random_state), and with preprocess_device the rows stay on the GPU through the cut and every run of the grid; None
+    refuses that mode (NO_SSS).  config.json names it only when it is set.
     -> that directory."""
     if model_type != 'mlp':
         raise ValueError(ONLY_MLP.format(model_type))
     return _mlp_fold(None, features_dir, output_dir, fold_num, feature_mode, train_batch_size, patience, random_state, parameter_search,
                      parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id,
-                     google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args)
+                     google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args,
+                     parameter_search_split_seed=parameter_search_split_seed)
 
 
 def _close_splits(splits):
@@ -589,26 +648,32 @@ def _close_splits(splits):
 
 def _mlp_fold(splits, features_dir, output_dir, fold_num, feature_mode, train_batch_size, patience, random_state, parameter_search,
               parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id,
-              google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args):
+              google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args,
+              parameter_search_split_seed=None):
     """train()'s fold; `splits` as _start_fold takes them -> the fold's directory"""
-    if parameter_search and not parameter_search_valid_fold:
+    without_valid_fold = parameter_search and not parameter_search_valid_fold
+    if without_valid_fold and parameter_search_split_seed is None:
         raise ValueError(NO_SSS)
     if gsheet_id:
         LOGGER.warning('Google Sheets logging is not built; gsheet_id ignored')
     model_dir, dataset, splits = _start_fold(
         features_dir, output_dir, fold_num, 'mlp', feature_mode, train_batch_size, patience, random_state, parameter_search,
         parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id, google_dev_app_name,
-        verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args, splits=splits)
+        verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args, splits=splits,
+        parameter_search_split_seed=parameter_search_split_seed)
 
     common = dict(batch_size=train_batch_size, patience=patience, random_state=random_state,
                   num_classes=DATASET_NUM_CLASSES[dataset], verbose=verbose)
     try:
         if parameter_search:
-            on_host = tuple(_on_host(d) for d in splits)          # one download; the search then runs as on the host
             grid = {'learning_rate': [1e-5, 1e-4, 1e-3], 'weight_decay': [1e-5, 1e-4, 1e-3]}
-            outcome = train_param_search(*on_host, model_dir, train_func=train_mlp, search_space=grid,
+            if without_valid_fold:          # the splits stay where they are: train_mlp takes DeviceFeatures as it does without a search
+                searched, seed = splits, dict(split_random_state=parameter_search_split_seed)
+            else:                           # one download; the search then runs as on the host
+                searched, seed = tuple(_on_host(d) for d in splits), {}
+            outcome = train_param_search(*searched, model_dir, train_func=train_mlp, search_space=grid,
                                          valid_ratio=parameter_search_valid_ratio,
-                                         train_with_valid=parameter_search_train_with_valid, **dict(common, **model_args))
+                                         train_with_valid=parameter_search_train_with_valid, **dict(common, **model_args), **seed)
         else:
             outcome = train_mlp(*splits, model_dir, **dict(common, **model_args))
     finally:
@@ -623,36 +688,42 @@ def train_svm_fold(features_dir, output_dir, fold_num, feature_mode='framewise',
                    random_state=20171021, parameter_search=False, parameter_search_valid_fold=True,
                    parameter_search_valid_ratio=0.15, parameter_search_train_with_valid=False, gsheet_id=None,
                    google_dev_app_name=None, verbose=False, non_overlap=False, non_overlap_chunk_size=10, use_min_max=False,
-                   preprocess_device=None, platt='device', **model_args):
+                   preprocess_device=None, platt='device', parameter_search_split_seed=None, **model_args):
     """classifier/train.py:495-709 for model_type='svm': one cross-validation fold as train() runs it for the MLP, written to
     <output_dir>/classifier/<features desc>/<mode>/<overlap>/<min-max>/svm/fold<N>/<timestamp>/: config.json, min_max_scaler.pkl,
     stdizer.pkl, model.pkl, results.pkl.  preprocess_device: a GPU index preprocesses the folds on that GPU and the SVM is
     fitted and scored from the splits there (nothing is downloaded but the results); config.json names it only when it is set.
     parameter_search: train_svm_search over C = 0.1 ... 1000 (platt: its sigmoid fit, 'device' or 'host'); else one train_svm with
     model_args (C, kernel, tol, max_iterations).  train_batch_size and patience are recorded as the reference records them; the
-    SVM does not use them.  -> that directory."""
+    SVM does not use them.  parameter_search_split_seed: as in train(); the cut and the search on it are train_svm_search's.
+    -> that directory."""
     return _svm_fold(None, features_dir, output_dir, fold_num, feature_mode, train_batch_size, patience, random_state, parameter_search,
                      parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id,
-                     google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, platt, model_args)
+                     google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, platt, model_args,
+                     parameter_search_split_seed=parameter_search_split_seed)
 
 
 def _svm_fold(splits, features_dir, output_dir, fold_num, feature_mode, train_batch_size, patience, random_state, parameter_search,
               parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id,
-              google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, platt, model_args):
+              google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, platt, model_args,
+              parameter_search_split_seed=None):
     """train_svm_fold()'s fold; `splits` as _start_fold takes them -> the fold's directory"""
-    if parameter_search and not parameter_search_valid_fold:
+    without_valid_fold = parameter_search and not parameter_search_valid_fold
+    if without_valid_fold and parameter_search_split_seed is None:
         raise ValueError(NO_SSS)
     if gsheet_id:
         LOGGER.warning('Google Sheets logging is not built; gsheet_id ignored')
     model_dir, dataset, splits = _start_fold(
         features_dir, output_dir, fold_num, 'svm', feature_mode, train_batch_size, patience, random_state, parameter_search,
         parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id, google_dev_app_name,
-        verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args, splits=splits)
+        verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args, splits=splits,
+        parameter_search_split_seed=parameter_search_split_seed)
     common = dict(random_state=random_state, num_classes=DATASET_NUM_CLASSES[dataset], verbose=verbose)
     try:
         if parameter_search:
+            seed = dict(valid_ratio=parameter_search_valid_ratio, split_random_state=parameter_search_split_seed) if without_valid_fold else {}
             outcome = train_svm_search(*splits, model_dir, train_with_valid=parameter_search_train_with_valid, platt=platt,
-                                       **dict(common, **model_args))
+                                       **dict(common, **model_args), **seed)
         else:
             outcome = train_svm(*splits, model_dir, evaluate_on_device=True, **dict(common, **model_args))
     finally:
@@ -694,7 +765,7 @@ def cross_validate(features_dir, output_dir, model_type='svm', folds=None, fold_
                    feature_mode='framewise', train_batch_size=64, patience=20, random_state=20171021, parameter_search=False,
                    parameter_search_valid_fold=True, parameter_search_valid_ratio=0.15, parameter_search_train_with_valid=False,
                    gsheet_id=None, google_dev_app_name=None, verbose=False, non_overlap=False, non_overlap_chunk_size=10,
-                   use_min_max=False, platt='device', **model_args):
+                   use_min_max=False, platt='device', parameter_search_split_seed=None, **model_args):
     """Every fold of a dataset in one run: what one train(model_type='mlp') or train_svm_fold (model_type='svm'; 'rf' raises as in
     train) call per fold does -- the same per-fold directories and files, from the same arguments -- with the feature files read
     and uploaded once (usc.FoldBank on preprocess_device; None keeps the folds and their preprocessing on the host) and every
@@ -703,6 +774,7 @@ def cross_validate(features_dir, output_dir, model_type='svm', folds=None, fold_
     folds: the test folds to run, 1-based; None runs all of the dataset's.  fold_seed: an int seeds NumPy's global state
     (np.random.seed) before each fold, so that fold k equals a separate per-fold call made after np.random.seed(fold_seed); None
     leaves the global state alone, and the folds draw their shuffles one after the other from it.  platt: train_svm_fold's.
+    parameter_search_split_seed: train()'s and train_svm_fold's, the same seed for every fold.
     A fold's splits are closed before the next fold's are assembled.
 
     Afterwards <output_dir>/classifier/<model_id>/cross_validation/<timestamp>/results.pkl and results.json hold
@@ -717,7 +789,7 @@ def cross_validate(features_dir, output_dir, model_type='svm', folds=None, fold_
     if dataset not in DATASET_NUM_CLASSES:
         raise ValueError('the features directory must name a dataset right after "features/" (one of {})'.format(
             ', '.join(sorted(DATASET_NUM_CLASSES))))
-    if parameter_search and not parameter_search_valid_fold:
+    if parameter_search and not parameter_search_valid_fold and parameter_search_split_seed is None:
         raise ValueError(NO_SSS)
     fold_args = (feature_mode, train_batch_size, patience, random_state, parameter_search, parameter_search_valid_fold,
                  parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id, google_dev_app_name, verbose, non_overlap,
@@ -738,9 +810,11 @@ def cross_validate(features_dir, output_dir, model_type='svm', folds=None, fold_
                 np.random.seed(fold_seed)
             try:
                 if model_type == 'mlp':
-                    fold_dirs.append(_mlp_fold(splits, features_dir, output_dir, fold_num, *fold_args, model_args))
+                    fold_dirs.append(_mlp_fold(splits, features_dir, output_dir, fold_num, *fold_args, model_args,
+                                               parameter_search_split_seed=parameter_search_split_seed))
                 else:
-                    fold_dirs.append(_svm_fold(splits, features_dir, output_dir, fold_num, *fold_args, platt, model_args))
+                    fold_dirs.append(_svm_fold(splits, features_dir, output_dir, fold_num, *fold_args, platt, model_args,
+                                               parameter_search_split_seed=parameter_search_split_seed))
             finally:
                 _close_splits(made)          # also after a failure between the assembly and the fold's own clean-up
 

@@ -1,6 +1,8 @@
 """Command line of the reference's 06_train_classifier.py (same flags, same defaults: 06_train_classifier.py:5-203) driving
 l3embedding_amd.classifier.train().  The fold driver runs the MLP alone: `-mt svm` (the default, as in the reference; the SVM
-itself is classifier.train_svm) and `-mt rf` fail at once, and so does `-psnv` (it needs sklearn's StratifiedShuffleSplit).
+itself is classifier.train_svm) and `-mt rf` fail at once, and so does `-psnv` without `--parameter-search-split-seed N`: the
+stratified cut of the training rows it searches on is drawn from that seed (usc.stratified_shuffle_split; the reference draws an
+unseeded one with sklearn's StratifiedShuffleSplit).
 
     python -m l3embedding_amd.cli_classifier -mt mlp -e 150 -lr 1e-4 -wd 1e-5 <features_dir> <output_dir> <fold_num>
 """
@@ -20,9 +22,9 @@ _OPTIONS = [
     ('-ps', '--parameter-search', 'parameter_search', dict(action='store_true'),
      'grid-search learning rate and weight decay on the validation fold'),
     ('-psnv', '--parameter-search-no-valid-fold', 'parameter_search_valid_fold', dict(action='store_false'),
-     'search on a stratified split of the training folds instead of the validation fold (not built)'),
+     'search on a stratified split of the training folds instead of the validation fold (needs --parameter-search-split-seed)'),
     ('-psvr', '--parameter-search-valid-ratio', 'parameter_search_valid_ratio', dict(type=float, default=0.15),
-     'share of the training rows such a split would hold out'),
+     'share of the training rows such a split holds out'),
     ('-pstwv', '--parameter-search-train-without-valid', 'parameter_search_train_with_valid', dict(action='store_false'),
      'after the search keep the chosen run instead of retraining on train + validation'),
     ('-lr', '--learning-rate', 'learning_rate', dict(type=float, default=1e-4), 'MLP: Adam learning rate'),
@@ -50,6 +52,9 @@ _OPTIONS = [
     # not a flag of 06_train_classifier.py: the folds are preprocessed on this GPU and handed to the MLP there
     ('-ppd', '--preprocess-device', 'preprocess_device', dict(type=int, default=None),
      'preprocess the folds on this GPU instead of in NumPy on the host'),
+    # not a flag of 06_train_classifier.py either: the reference's stratified split is unseeded, here every draw has a seed
+    ('-psss', '--parameter-search-split-seed', 'parameter_search_split_seed', dict(type=int, default=None),
+     'seed of the stratified split -psnv searches on; -psnv is refused without it'),
 ]
 _POSITIONALS = [
     ('features_dir', str, 'directory holding fold1 .. foldN of .npz feature files; its path names the dataset after features/'),
@@ -69,12 +74,12 @@ def build_parser():
 
 
 def parse_arguments(argv=None):
-    """-> dict of the parsed flags; exits with status 2 and a message for what is not built (svm, rf, -psnv)"""
+    """-> dict of the parsed flags; exits with status 2 and a message for what is not built (svm, rf, -psnv without a split seed)"""
     p = build_parser()
     args = vars(p.parse_args(argv))
     if args['model_type'] != 'mlp':
         p.error(ONLY_MLP.format(args['model_type']))
-    if not args['parameter_search_valid_fold']:
+    if not args['parameter_search_valid_fold'] and args['parameter_search_split_seed'] is None:
         p.error('-psnv: ' + NO_SSS)
     return args
 

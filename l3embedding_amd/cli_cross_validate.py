@@ -1,6 +1,7 @@
 """Command line of classifier.cross_validate: every fold of a dataset in one run, from folds read once and kept on the GPU.  The flags
 are those of cli_classifier (the reference's 06_train_classifier.py) without the positional fold number, plus --folds and
---fold-seed; `-mt svm` (the default) and `-mt mlp` run, `-mt rf` and `-psnv` fail at once as they do there.
+--fold-seed; `-mt svm` (the default) and `-mt mlp` run, `-mt rf` fails at once as it does there, and so does `-psnv` without
+`--parameter-search-split-seed N` (with it, both classifiers search on a stratified cut of the training rows drawn from that seed).
 
     python -m l3embedding_amd.cli_cross_validate -mt svm -ppd 0 <features_dir> <output_dir>
 """
@@ -31,12 +32,12 @@ def build_parser():
 
 
 def parse_arguments(argv=None):
-    """-> dict of cross_validate's arguments; exits with status 2 and a message for what is not built (rf, -psnv)"""
+    """-> dict of cross_validate's arguments; exits with status 2 and a message for what is not built (rf, -psnv without a split seed)"""
     p = build_parser()
     args = vars(p.parse_args(argv))
     if args['model_type'] not in ('svm', 'mlp'):
         p.error(ONLY_MLP.format(args['model_type']))
-    if not args['parameter_search_valid_fold']:
+    if not args['parameter_search_valid_fold'] and args['parameter_search_split_seed'] is None:
         p.error('-psnv: ' + NO_SSS)
     if args['preprocess_device'] is not None and args['preprocess_device'] < 0:
         args['preprocess_device'] = None

@@ -9,6 +9,7 @@
 //   feat_standardize   (x - mean) / scale through float64, two float32 roundings (StandardScaler.transform)
 //   feat_file_stats    compute_stats_features of every file (:243-253)
 //   feat_assemble      row ranges of other matrices -> a new matrix  (the np.vstack of data/usc/folds.py:24-112)
+//   feat_split         X[rows_a], X[rows_b] -> two new matrices, X kept  (train_param_search's cut, classifier/train.py:416-423)
 //
 // The arithmetic whose roundings are part of the contract is written with the __f*_rn / __d*_rn intrinsics, which the compiler
 // never contracts into a fused multiply-add; the file is also built with -ffp-contract=off (_build.py).
@@ -20,6 +21,7 @@
 
 #include "../../include/l3hip.h"
 #include "feat_assemble.h"
+#include "feat_split.h"
 #include "featprep.h"
 
 namespace l3 {
@@ -287,6 +289,52 @@ __global__ __launch_bounds__(ASM_BLOCK) void feat_assemble_kernel(const Assemble
     }
 }
 
+// ---- split: the output rows of both new matrices, A's then B's, in spans of `rows_per_wave`, one wave per span -------------------------
+// table = rows_a followed by rows_b (n_out entries): output row o copies source row table[o], into ya at row o when o < n_a and into yb
+// at row o - n_a otherwise.  Dv pieces of V floats per row (V = 4: 16-byte accesses, x, ya and yb hipMalloc'ed and D % 4 == 0, so every
+// row starts 16-byte aligned; V = 1: 4-byte accesses).  A row of 64 pieces or more is swept by the whole wave, its index wave-uniform;
+// shorter rows are taken together as one flat run of pieces, each lane finding the row of its piece.  The source may be read more
+// than once (repeated indices); every output float is written once: non-temporal.  No atomics, no order between waves.
+static_assert(SPLIT_BLOCK == ASM_BLOCK && SPLIT_WAVE_FLOATS == ASM_WAVE_FLOATS, "feat_split.h plans for the assembly kernel's shape");
+template <int V>
+struct Piece;
+template <>
+struct Piece<1> { typedef float type; };
+template <>
+struct Piece<4> { typedef f32x4 type; };
+
+template <int V>
+__global__ __launch_bounds__(SPLIT_BLOCK) void feat_split_kernel(const float* __restrict__ x, const int64_t* __restrict__ table,
+                                                                float* __restrict__ ya, float* __restrict__ yb, int64_t n_a, int64_t n_out,
+                                                                int Dv, int rows_per_wave) {
+    typedef typename Piece<V>::type P;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * (SPLIT_BLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t r0 = wave * rows_per_wave;
+    if (r0 >= n_out) return;
+    const int nr = (int)min((int64_t)rows_per_wave, n_out - r0);
+    const int64_t D = (int64_t)Dv * V;
+    if (Dv >= 64) {
+        for (int r = 0; r < nr; ++r) {
+            const int64_t o = r0 + r;
+            const P* src = reinterpret_cast<const P*>(x + table[o] * D);
+            P* dst = reinterpret_cast<P*>(o < n_a ? ya + o * D : yb + (o - n_a) * D);
+#pragma unroll 4
+            for (int i = lane; i < Dv; i += 64) __builtin_nontemporal_store(__builtin_nontemporal_load(src + i), dst + i);
+        }
+    } else {
+        const int span = nr * Dv;          // < 64 * rows_per_wave <= SPLIT_WAVE_FLOATS
+#pragma unroll 4
+        for (int e = lane; e < span; e += 64) {
+            const int r = e / Dv, i = e - r * Dv;
+            const int64_t o = r0 + r;
+            const P* src = reinterpret_cast<const P*>(x + table[o] * D);
+            P* dst = reinterpret_cast<P*>(o < n_a ? ya + o * D : yb + (o - n_a) * D);
+            __builtin_nontemporal_store(__builtin_nontemporal_load(src + i), dst + i);
+        }
+    }
+}
+
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
 bool vec4(const l3_feat* f) { return f->D % 4 == 0; }          // hipMalloc'ed base, rows of a multiple of 16 bytes
 
@@ -429,6 +477,56 @@ int l3_feat_assemble(int device, const l3_feat_segment* segs, int64_t n_segs, l3
         return fail(L3_EHIP, "l3_feat_assemble: HIP error");
     }
     *out = f;
+    return L3_OK;
+}
+
+int l3_feat_split(const l3_feat* src, const int64_t* rows_a, int64_t n_a, const int64_t* rows_b, int64_t n_b, l3_feat** out_a,
+                  l3_feat** out_b) {
+    SplitPlan plan;
+    std::string err;
+    if (!plan_split(src != nullptr, src ? src->n : 0, src ? src->D : 0, rows_a, n_a, rows_b, n_b, out_a != nullptr, out_b != nullptr, &plan,
+                    &err))
+        return fail(L3_EINVAL, err);
+    if (hipSetDevice(src->device) != hipSuccess) return fail(L3_EHIP, no_gpu_message("l3_feat_split", src->device));
+    // as in l3_feat_assemble: the source holds its final values at entry, and its stream is synchronised all the same
+    if (hipStreamSynchronize(src->s) != hipSuccess) return fail(L3_EHIP, "l3_feat_split: the source's stream failed");
+    l3_feat* parts[2] = {new l3_feat(), n_b ? new l3_feat() : nullptr};
+    const int64_t counts[2] = {n_a, n_b};
+    bool ok = true;
+    for (int k = 0; k < 2 && ok; ++k) {
+        l3_feat* f = parts[k];
+        if (!f) continue;
+        f->device = src->device, f->n = counts[k], f->D = src->D;
+        f->x = f->bufs.alloc<float>((size_t)(counts[k] * src->D));
+        ok = f->x && hipStreamCreateWithFlags(&f->s, hipStreamNonBlocking) == hipSuccess;
+    }
+    // both tables in one buffer, A's entries then B's; the launch runs on A's stream and writes both matrices
+    l3_feat* a = parts[0];
+    int64_t* table = ok ? a->bufs.alloc<int64_t>((size_t)(n_a + n_b)) : nullptr;
+    if (!table) {
+        l3_feat_destroy(parts[0]), l3_feat_destroy(parts[1]);
+        return fail(L3_ENOMEM, "l3_feat_split: device allocation of " + std::to_string((n_a + n_b) * (src->D * 4 + 8)) + " bytes failed");
+    }
+    ok = hipMemcpyAsync(table, rows_a, (size_t)n_a * sizeof(int64_t), hipMemcpyHostToDevice, a->s) == hipSuccess &&
+         (!n_b || hipMemcpyAsync(table + n_a, rows_b, (size_t)n_b * sizeof(int64_t), hipMemcpyHostToDevice, a->s) == hipSuccess);
+    if (ok) {
+        float* yb = parts[1] ? parts[1]->x : nullptr;
+        const int Dv = (int)(src->D / plan.vec);
+        if (plan.vec == 4)
+            hipLaunchKernelGGL(feat_split_kernel<4>, dim3(plan.blocks), dim3(SPLIT_BLOCK), 0, a->s, src->x, table, a->x, yb, n_a, n_a + n_b, Dv,
+                               plan.rows_per_wave);
+        else
+            hipLaunchKernelGGL(feat_split_kernel<1>, dim3(plan.blocks), dim3(SPLIT_BLOCK), 0, a->s, src->x, table, a->x, yb, n_a, n_a + n_b, Dv,
+                               plan.rows_per_wave);
+    }
+    ok = finished(a) && ok;          // also after a failed copy: the stream has let go of the host tables
+    a->bufs.release(table);
+    if (!ok) {
+        l3_feat_destroy(parts[0]), l3_feat_destroy(parts[1]);
+        return fail(L3_EHIP, "l3_feat_split: HIP error");
+    }
+    *out_a = parts[0];
+    if (n_b) *out_b = parts[1];
     return L3_OK;
 }
 

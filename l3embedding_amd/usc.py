@@ -12,6 +12,9 @@ Quirks kept on purpose:
 preprocess_split_data(..., device=<index>) runs the passes over the (n, D) matrices on the GPU (csrc/featprep.hip):
 the splits' 'features' become DeviceFeatures, which classifier.MLPModel takes without a trip through the host.
 
+stratified_shuffle_split restates sklearn's StratifiedShuffleSplit(n_splits=1) in NumPy, index for index: the cut of the training
+rows that the parameter search without a validation fold makes (classifier/train.py:408-423).
+
 FoldBank reads every fold of a dataset once and puts the splits of any cross-validation fold together from them, on the GPU by one
 copy kernel per split (l3_feat_assemble): what classifier.cross_validate runs on.
 """
@@ -359,6 +362,12 @@ class DeviceFeatures(object):
         (_lib.Features.assemble); the sources stay as they are"""
         return cls.from_handle(_lib.Features.assemble([(f.handle, lo, hi) for f, lo, hi in segments], device=device))
 
+    def split(self, rows_a, rows_b=None):
+        """X[rows_a] and X[rows_b] as two new DeviceFeatures on this GPU, which the caller owns and closes, written by one kernel
+        (_lib.Features.split); this matrix stays as it is.  rows_b None: -> (DeviceFeatures, None)"""
+        a, b = self.handle.split(rows_a, rows_b)
+        return type(self).from_handle(a), (None if b is None else type(self).from_handle(b))
+
     @property
     def shape(self):
         return self.handle.shape
@@ -479,3 +488,68 @@ def preprocess_split_data(train_data, valid_data, test_data, feature_mode='frame
     train_data['labels'] = train_data['labels'][order]
     train_data['file_idxs'] = [new_position[s:e] for s, e in train_data['file_idxs']]
     return unit_range, stdizer
+
+
+def _approximate_mode(class_counts, n_draws, rng):
+    """sklearn.utils.extmath._approximate_mode: how many of n_draws rows each class gets -- the floor of its proportional share,
+    then one more for the classes with the largest remainders, equal remainders drawn with rng.choice(replace=False)"""
+    continuous = class_counts / class_counts.sum() * n_draws
+    floored = np.floor(continuous)
+    need_to_add = int(n_draws - floored.sum())
+    if need_to_add > 0:
+        remainder = continuous - floored
+        for value in np.sort(np.unique(remainder))[::-1]:
+            inds, = np.where(remainder == value)
+            add_now = min(len(inds), need_to_add)
+            floored[rng.choice(inds, size=add_now, replace=False)] += 1
+            need_to_add -= add_now
+            if need_to_add == 0:
+                break
+    return floored.astype(int)
+
+
+def stratified_shuffle_split(labels, valid_ratio=0.15, random_state=None):
+    """sklearn 1.7's StratifiedShuffleSplit(n_splits=1, test_size=valid_ratio, random_state=random_state) over `labels`
+    -> (train_idx, valid_idx), int64, the indices sklearn gives for the same integer seed: n_valid = ceil(valid_ratio * n) rows
+    validate, each class is shared out between the two parts in proportion (_approximate_mode), and every draw comes from one
+    np.random.RandomState(random_state) in sklearn's order -- the remainder ties of the train counts, then of the validation counts,
+    one permutation per class in class order, one of the train list, one of the validation list.
+
+    random_state must be given (the reference passes none, so its split differs from run to run; here every draw has a seed).
+    ValueError where sklearn raises one: a ratio outside (0, 1), a class of fewer than two members, fewer train or validation rows
+    than classes."""
+    if random_state is None:
+        raise ValueError('stratified_shuffle_split needs a random_state: every draw of this project comes from an explicit seed')
+    labels = np.asarray(labels)
+    if labels.ndim != 1:
+        raise ValueError('labels must be one class per row, not an array of {} dimensions'.format(labels.ndim))
+    if not 0.0 < valid_ratio < 1.0:
+        raise ValueError('valid_ratio={} should be a float in the (0, 1) range'.format(valid_ratio))
+    n = labels.shape[0]
+    n_valid = int(np.ceil(valid_ratio * n))
+    n_train = n - n_valid
+    if n_train == 0:
+        raise ValueError('With n_samples={} and valid_ratio={}, the resulting train set will be empty.'.format(n, valid_ratio))
+    classes, y_indices = np.unique(labels, return_inverse=True)
+    n_classes = classes.shape[0]
+    class_counts = np.bincount(y_indices)
+    if np.min(class_counts) < 2:
+        raise ValueError('The least populated class in y has only 1 member, which is too few. The minimum number of groups for any '
+                         'class cannot be less than 2.')
+    if n_train < n_classes:
+        raise ValueError('The train_size = %d should be greater or equal to the number of classes = %d' % (n_train, n_classes))
+    if n_valid < n_classes:
+        raise ValueError('The test_size = %d should be greater or equal to the number of classes = %d' % (n_valid, n_classes))
+    class_indices = np.split(np.argsort(y_indices, kind='mergesort'), np.cumsum(class_counts)[:-1])
+
+    rng = np.random.RandomState(random_state)
+    n_i = _approximate_mode(class_counts, n_train, rng)
+    t_i = _approximate_mode(class_counts - n_i, n_valid, rng)
+    train, valid = [], []
+    for i in range(n_classes):
+        shuffled = class_indices[i].take(rng.permutation(class_counts[i]), mode='clip')
+        train.append(shuffled[:n_i[i]])
+        valid.append(shuffled[n_i[i]:n_i[i] + t_i[i]])
+    train = rng.permutation(np.concatenate(train).astype(np.int64))
+    valid = rng.permutation(np.concatenate(valid).astype(np.int64))
+    return train, valid
