@@ -19,8 +19,15 @@ it.  Deviations from the reference, all deliberate:
     and the model is pickled with `pickle` (the reference uses joblib).  train() still runs only the MLP; train_svm_fold is
     the reference's train(model_type='svm'), and train_svm_search its parameter search over C with the whole grid fitted in
     one pass on the GPU (svm.fit_grid).
+
+How the file is put together: train, train_svm_fold and cross_validate pass their arguments, by name in one dict, to one fold driver
+(_run_fold), and the model types differ in one function each (_mlp_part, _svm_part).  train_param_search and train_svm_search are
+one search body (_search) with two ways to fit the grid.  A usc.DeviceFeatures is closed by whoever made it, through _closing: the
+driver closes the fold's splits, a search the parts of its cut and its merged matrix, and nobody what a caller passed in.
 """
+import contextlib
 import datetime
+import functools
 import getpass
 import json
 import logging
@@ -166,46 +173,29 @@ class MLPModel(object):
 
         x (and the validation features) may be usc.DeviceFeatures: their rows are then copied on the device into the model's
         own matrices, validation_split slicing by row range."""
-        if isinstance(x, DeviceFeatures):
-            return self._fit(*self._set_data_dev(x, y, int(batch_size), validation_split, validation_data), batch_size=batch_size,
-                             epochs=epochs, verbose=verbose, callbacks=callbacks, shuffle=shuffle, random_state=random_state)
-        x = np.asarray(x, np.float32)
+        on_device = isinstance(x, DeviceFeatures)
+        if not on_device:
+            x = np.asarray(x, np.float32)
         labels = np.argmax(np.asarray(y), axis=1).astype(np.int32)
-        if validation_data is not None:
-            vx = np.asarray(validation_data[0], np.float32)
-            vy = np.argmax(np.asarray(validation_data[1]), axis=1).astype(np.int32)
-        elif validation_split and 0.0 < validation_split < 1.0:
-            split_at = int(len(x) * (1.0 - validation_split))
-            x, vx = x[:split_at], x[split_at:]
-            labels, vy = labels[:split_at], labels[split_at:]
-        else:
-            vx = vy = None
-        h = self._handle(int(batch_size))
-        h.set_data(x, labels, vx, vy)
-        return self._fit(h, len(x), vx is not None, batch_size=batch_size, epochs=epochs, verbose=verbose, callbacks=callbacks,
-                         shuffle=shuffle, random_state=random_state)
-
-    def _set_data_dev(self, x, y, batch_size, validation_split, validation_data):
-        """fit's data set-up for DeviceFeatures -> (handle, training rows, whether there is validation data)"""
-        labels = np.argmax(np.asarray(y), axis=1).astype(np.int32)
-        n = len(x)
-        valid, vlo, vhi, vy = None, 0, 0, None
+        n_train = len(x)
+        # the split: the training rows are x[:n_train]; the validation rows are vx[vlo:vhi], of the held-out matrix or of x itself
+        vx, vlo, vhi, vy = None, 0, 0, None
         if validation_data is not None:
             vx = validation_data[0]
             if not isinstance(vx, DeviceFeatures):
-                vx = DeviceFeatures(np.asarray(vx, np.float32), x.device)
-            valid, vhi = vx.handle, len(vx)
+                vx = DeviceFeatures(np.asarray(vx, np.float32), x.device) if on_device else np.asarray(vx, np.float32)
+            vhi = len(vx)
             vy = np.argmax(np.asarray(validation_data[1]), axis=1).astype(np.int32)
         elif validation_split and 0.0 < validation_split < 1.0:
-            split_at = int(n * (1.0 - validation_split))
-            valid, vlo, vhi, vy = x.handle, split_at, n, labels[split_at:]
-            n, labels = split_at, labels[:split_at]
-        h = self._handle(batch_size)
-        h.set_data_dev(x.handle, 0, n, labels, valid, vlo, vhi, vy)
-        return h, n, vy is not None
+            n_train = int(len(x) * (1.0 - validation_split))
+            vx, vlo, vhi, vy = x, n_train, len(x), labels[n_train:]
+            labels = labels[:n_train]
+        h = self._handle(int(batch_size))
+        if on_device:
+            h.set_data_dev(x.handle, 0, n_train, labels, None if vx is None else vx.handle, vlo, vhi, vy)
+        else:
+            h.set_data(x[:n_train], labels, None if vx is None else vx[vlo:vhi], vy)
 
-    def _fit(self, h, n_train, with_valid, batch_size, epochs, verbose, callbacks, shuffle, random_state):
-        """the epochs of fit over the data the handle holds"""
         rs = np.random.RandomState(random_state)
         cbs = list(callbacks or [])
         for cb in cbs:
@@ -222,7 +212,7 @@ class MLPModel(object):
             perm = rs.permutation(n_train) if shuffle else np.arange(n_train)
             logs = h.epoch(perm, self.lr, self.iterations)
             self.iterations += steps
-            if not with_valid:
+            if vy is None:
                 logs = {k: logs[k] for k in ('loss', 'acc')}
             for k, v in logs.items():
                 history.setdefault(k, []).append(v)
@@ -341,19 +331,19 @@ def train_svm(train_data, valid_data, test_data, model_dir, C=1.0, kernel='rbf',
     probability=True, random_state) fitted on the GPU and pickled to model_dir/model.pkl; 'loss' is sklearn's hinge loss of the
     (ovr) decision values; the test set is classified per file as the argmax of the mean of its frames' predict_proba.
     evaluate_on_device: the splits stay as they are (usc.DeviceFeatures are not downloaded) and each is scored by one
-    SVC.evaluate on the GPU; the same four values come back.  That path reads the classes off the fitted model (clf.classes_)
-    where the default one passes labels=np.arange(num_classes) to hinge_loss: the two agree when every class of
+    SVC.evaluate on the GPU (_svm_metrics_on_device); the same four values come back.  That path reads the classes off the fitted
+    model (clf.classes_) where the default one passes labels=np.arange(num_classes) to hinge_loss: the two agree when every class of
     range(num_classes) occurs in the training split, and a validation label the training split lacks is a ValueError there."""
-    if evaluate_on_device:
-        return _train_svm_on_device(train_data, valid_data, test_data, model_dir, C, kernel, num_classes, tol, max_iterations,
-                                    verbose, random_state)
-    train_data, valid_data, test_data = (_on_host(d) for d in (train_data, valid_data, test_data))
+    if not evaluate_on_device:
+        train_data, valid_data, test_data = (_on_host(d) for d in (train_data, valid_data, test_data))
     features, labels = train_data['features'], train_data['labels']
     clf = SVC(C=C, probability=True, kernel=kernel, max_iter=max_iterations, tol=tol, random_state=random_state, verbose=verbose)
     LOGGER.debug('Fitting model to data...')
     clf.fit(features, labels)
     LOGGER.info('Saving model...')
     _dump(os.path.join(model_dir, 'model.pkl'), clf)
+    if evaluate_on_device:
+        return (clf,) + _svm_metrics_on_device(clf, train_data, valid_data, test_data, num_classes)
 
     classes = np.arange(num_classes)
     train_metrics = compute_metrics(labels, clf.predict(features), num_classes=num_classes)
@@ -372,20 +362,9 @@ def train_svm(train_data, valid_data, test_data, model_dir, C=1.0, kernel='rbf',
     return clf, train_metrics, valid_metrics, test_metrics
 
 
-def _train_svm_on_device(train_data, valid_data, test_data, model_dir, C, kernel, num_classes, tol, max_iterations, verbose,
-                         random_state):
-    """train_svm with the fit from the split as it is and one SVC.evaluate per split: predictions and the hinge loss of the train
-    and validation rows (no (n, C) array returns), the per-file classes of the test set"""
-    clf = SVC(C=C, probability=True, kernel=kernel, max_iter=max_iterations, tol=tol, random_state=random_state, verbose=verbose)
-    LOGGER.debug('Fitting model to data...')
-    clf.fit(train_data['features'], train_data['labels'])
-    LOGGER.info('Saving model...')
-    _dump(os.path.join(model_dir, 'model.pkl'), clf)
-    return (clf,) + _svm_metrics_on_device(clf, train_data, valid_data, test_data, num_classes)
-
-
 def _svm_metrics_on_device(clf, train_data, valid_data, test_data, num_classes):
-    """-> (train_metrics, valid_metrics, test_metrics) of a fitted SVC, one SVC.evaluate per split"""
+    """-> (train_metrics, valid_metrics, test_metrics) of a fitted SVC, one SVC.evaluate per split: predictions and the hinge loss
+    of the train and validation rows (no (n, C) array returns), the per-file classes of the test set"""
     metrics = []
     for name, data in (('Train', train_data), ('Valid', valid_data)):
         if not data:
@@ -403,6 +382,22 @@ def _svm_metrics_on_device(clf, train_data, valid_data, test_data, num_classes):
     return metrics[0], metrics[1], test_metrics
 
 
+# ---- who owns a feature matrix ----------------------------------------------------------------------------------------------------
+# A split is {'features', 'labels', ...}; its features are a NumPy array or a usc.DeviceFeatures, which holds device memory until it
+# is closed.  Whoever makes a DeviceFeatures closes it, once, through _closing: the fold driver the splits it obtained (whatever
+# their features are by then: the preprocessing uploads arrays), a search the two parts of its cut and its merged matrix.  What a
+# caller passes in is the caller's.
+@contextlib.contextmanager
+def _closing(splits):
+    """the splits, for the length of a with block; on the way out the DeviceFeatures that they hold by then are closed"""
+    try:
+        yield splits
+    finally:
+        for d in splits:
+            if d and isinstance(d.get('features'), DeviceFeatures):
+                d['features'].close()
+
+
 def _on_host(data):
     """the split with its features as a NumPy array (downloaded if preprocess_split_data left them on the device)"""
     if data and isinstance(data['features'], DeviceFeatures):
@@ -410,10 +405,16 @@ def _on_host(data):
     return data
 
 
+def _require_split_seed(search_on_cut, seed):
+    """the one refusal of the search without a validation fold: it needs the seed of its cut"""
+    if search_on_cut and seed is None:
+        raise ValueError(NO_SSS)
+
+
 def _cut_for_search(train_data, valid_ratio, split_random_state):
     """classifier/train.py:412-423 -> (search part, validation part), {'features', 'labels'} each: the training rows cut by
     usc.stratified_shuffle_split(labels, valid_ratio, split_random_state).  A DeviceFeatures is cut on its GPU by one
-    DeviceFeatures.split into two new ones (the caller closes them: _close_splits), a NumPy array by indexing: the same bits."""
+    DeviceFeatures.split into two new ones (the caller owns them), a NumPy array by indexing: the same bits."""
     labels = np.asarray(train_data['labels'])
     train_idx, valid_idx = stratified_shuffle_split(labels, valid_ratio, split_random_state)
     features = train_data['features']
@@ -424,55 +425,82 @@ def _cut_for_search(train_data, valid_ratio, split_random_state):
     return {'features': kept, 'labels': labels[train_idx]}, {'features': held, 'labels': labels[valid_idx]}
 
 
-def train_param_search(train_data, valid_data, test_data, model_dir, train_func, search_space, valid_ratio=0.15,
-                       train_with_valid=True, split_random_state=None, **kwargs):
-    """classifier/train.py:394-492: train_func once per point of the grid (the product of the search_space values, in key
-    order), keep the point with the best validation accuracy (the first one on ties), then either retrain with no validation
-    data (train_with_valid) or keep that run.  With a validation fold the search runs on (train, valid) and the retrain on the two
-    shuffled together.  Without one (valid_data None) the reference cuts valid_ratio of the training rows off with sklearn's
-    StratifiedShuffleSplit: split_random_state, an int, is the seed of that cut (_cut_for_search), the search runs on its two
-    parts, the retrain on the whole of train_data as it is, and the parts are closed at the end; None refuses (NO_SSS)."""
-    cut = ()
-    if not valid_data:
-        if split_random_state is None:
-            raise ValueError(NO_SSS)
-        cut = _cut_for_search(train_data, valid_ratio, split_random_state)
-    try:
-        return _param_search(train_data, valid_data, test_data, model_dir, train_func, search_space, train_with_valid, cut, kwargs)
-    finally:
-        _close_splits(cut)
-
-
-def _param_search(train_data, valid_data, test_data, model_dir, train_func, search_space, train_with_valid, cut, kwargs):
-    """train_param_search on (train_data, valid_data), or on the two parts of `cut` when it is not empty"""
-    search_train, search_valid = cut or (train_data, valid_data)
-    names = list(search_space)
-    runs = []                       # (point, model, train metrics, valid metrics, test metrics)
-    for point in product(*(search_space[n] for n in names)):
-        LOGGER.info('Search point %s', dict(zip(names, point)))
-        kwargs.update(zip(names, point))
-        runs.append((point,) + tuple(train_func(search_train, search_valid, test_data, model_dir, **kwargs)))
-    accuracies = [run[3]['accuracy'] for run in runs]
-    chosen = runs[int(np.argmax(accuracies))]
-    point = chosen[0]
-    LOGGER.info('Chosen %s (validation accuracy %s)', dict(zip(names, point)), chosen[3]['accuracy'])
-    kwargs.update(zip(names, point))
-
-    if train_with_valid and cut:          # :471-474: the entire training set, neither merged nor shuffled
-        model, train_metrics, _, test_metrics = train_func(train_data, None, test_data, model_dir, **kwargs)
-    elif train_with_valid:
-        merged_labels = np.concatenate((train_data['labels'], valid_data['labels']))
-        mix = np.random.permutation(merged_labels.size)
-        merged = {'features': np.vstack((train_data['features'], valid_data['features']))[mix], 'labels': merged_labels[mix]}
-        model, train_metrics, _, test_metrics = train_func(merged, None, test_data, model_dir, **kwargs)
+@contextlib.contextmanager
+def _merged_and_shuffled(train_data, valid_data):
+    """classifier/train.py:476-479: train + valid as one split, shuffled by one np.random.permutation (the global state), for the
+    length of a with block.  Two DeviceFeatures on one GPU are stacked and shuffled there into a new one (one copy kernel, one
+    gather; closed on the way out), anything else on the host: the same bits."""
+    labels = np.concatenate((train_data['labels'], valid_data['labels']))
+    mix = np.random.permutation(labels.size)
+    tx, vx = train_data['features'], valid_data['features']
+    resident = isinstance(tx, DeviceFeatures) and isinstance(vx, DeviceFeatures) and tx.device == vx.device
+    if resident:
+        stacked = DeviceFeatures.assemble([(tx, 0, len(tx)), (vx, 0, len(vx))], device=tx.device)
     else:
-        model, train_metrics, test_metrics = chosen[1], dict(chosen[2]), chosen[4]
+        stacked = np.vstack((_on_host(train_data)['features'], _on_host(valid_data)['features']))[mix]
+    with _closing(({'features': stacked, 'labels': labels[mix]},)) as (merged,):
+        if resident:
+            stacked.handle.gather(mix)
+        yield merged
+
+
+def _search(train_data, valid_data, names, valid_ratio, split_random_state, train_with_valid, run_grid, refit):
+    """The body of both parameter searches (classifier/train.py:394-492) -> (model, train_metrics, valid_metrics, test_metrics).
+    With a validation fold the grid runs on (train_data, valid_data); without one (valid_data None) on the two parts of
+    _cut_for_search, which needs split_random_state (None refuses, NO_SSS).  The point with the best validation accuracy is kept,
+    the first one on ties.  train_with_valid then refits it without validation data: after a cut on the whole of train_data as it
+    is (:471-474), else on train + valid shuffled together; without train_with_valid the chosen run stands.
+    run_grid(search_train, search_valid) -> [(point, model, train metrics, valid metrics, test metrics)] in grid order;
+    refit(point, data) -> (model, train metrics, test metrics); names: the searched parameters, in the order of a point's values."""
+    _require_split_seed(not valid_data, split_random_state)
+    with contextlib.ExitStack() as made:          # what the search makes: closed when it ends, however it ends
+        searched = (train_data, valid_data) if valid_data else made.enter_context(
+            _closing(_cut_for_search(train_data, valid_ratio, split_random_state)))
+        runs = run_grid(*searched)
+        chosen = runs[int(np.argmax([run[3]['accuracy'] for run in runs]))]
+        point = chosen[0]
+        LOGGER.info('Chosen %s (validation accuracy %s)', dict(zip(names, point)), chosen[3]['accuracy'])
+        if not train_with_valid:
+            model, train_metrics, test_metrics = chosen[1], dict(chosen[2]), chosen[4]
+        elif valid_data:
+            model, train_metrics, test_metrics = refit(point, made.enter_context(_merged_and_shuffled(train_data, valid_data)))
+        else:
+            model, train_metrics, test_metrics = refit(point, train_data)
 
     search_record = {'search_params': names, 'search_params_best_values': point}
     train_metrics.update(search_record, search={run[0]: run[2] for run in runs})
     valid_metrics = dict(chosen[3])
     valid_metrics.update(search_record, search={run[0]: run[3] for run in runs})
     return model, train_metrics, valid_metrics, test_metrics
+
+
+def train_param_search(train_data, valid_data, test_data, model_dir, train_func, search_space, valid_ratio=0.15,
+                       train_with_valid=True, split_random_state=None, **kwargs):
+    """classifier/train.py:394-492: train_func once per point of the grid (the product of the search_space values, in key
+    order), keep the point with the best validation accuracy (the first one on ties), then either retrain with no validation
+    data (train_with_valid) or keep that run.  With a validation fold the search runs on (train, valid) and the retrain on the two
+    shuffled together (on the GPU when both are usc.DeviceFeatures there).  Without one (valid_data None) the reference cuts
+    valid_ratio of the training rows off with sklearn's StratifiedShuffleSplit: split_random_state, an int, is the seed of that cut
+    (_cut_for_search), the search runs on its two parts, the retrain on the whole of train_data as it is, and the parts are closed
+    at the end; None refuses (NO_SSS)."""
+    names = list(search_space)
+
+    def fit(point, train, valid):
+        kwargs.update(zip(names, point))
+        return tuple(train_func(train, valid, test_data, model_dir, **kwargs))
+
+    def run_grid(search_train, search_valid):
+        runs = []
+        for point in product(*(search_space[n] for n in names)):
+            LOGGER.info('Search point %s', dict(zip(names, point)))
+            runs.append((point,) + fit(point, search_train, search_valid))
+        return runs
+
+    def refit(point, data):
+        model, train_metrics, _, test_metrics = fit(point, data, None)
+        return model, train_metrics, test_metrics
+
+    return _search(train_data, valid_data, names, valid_ratio, split_random_state, train_with_valid, run_grid, refit)
 
 
 SVM_SEARCH_CS = (0.1, 1, 10, 100, 1000)        # classifier/train.py:609
@@ -492,73 +520,41 @@ def train_svm_search(train_data, valid_data, test_data, model_dir, Cs=SVM_SEARCH
     Without a validation fold (valid_data None): train_param_search's cut of valid_ratio of the training rows, seeded by
     split_random_state (None refuses, NO_SSS); the grid is fitted and scored on its two parts, and train_with_valid refits the
     chosen cost on the whole of train_data as it is."""
-    cut = ()
-    if not valid_data:
-        if split_random_state is None:
-            raise ValueError(NO_SSS)
-        cut = _cut_for_search(train_data, valid_ratio, split_random_state)
-    try:
-        return _svm_search(train_data, valid_data, test_data, model_dir, list(Cs), train_with_valid, platt, num_classes, max_entries, cut,
-                           dict(probability=True, kernel=kernel, max_iter=max_iterations, tol=tol, random_state=random_state,
-                                verbose=verbose))
-    finally:
-        _close_splits(cut)
+    Cs = list(Cs)
 
+    def fit(data, costs):
+        return _svm.fit_grid(data['features'], data['labels'], costs, platt=platt, max_entries=max_entries, probability=True,
+                             kernel=kernel, max_iter=max_iterations, tol=tol, random_state=random_state, verbose=verbose)
 
-def _svm_search(train_data, valid_data, test_data, model_dir, Cs, train_with_valid, platt, num_classes, max_entries, cut, params):
-    """train_svm_search on (train_data, valid_data), or on the two parts of `cut` when it is not empty"""
-    search_train, search_valid = cut or (train_data, valid_data)
-    LOGGER.info('Fitting the grid C = %s', Cs)
-    models = _svm.fit_grid(search_train['features'], search_train['labels'], Cs, platt=platt, max_entries=max_entries, **params)
-    runs = []                       # (point, model, train metrics, valid metrics, test metrics)
-    for c, clf in zip(Cs, models):
-        LOGGER.info('Search point %s', {'C': c})
-        runs.append(((c,), clf) + _svm_metrics_on_device(clf, search_train, search_valid, test_data, num_classes))
-    chosen = runs[int(np.argmax([run[3]['accuracy'] for run in runs]))]
-    point = chosen[0]
-    LOGGER.info('Chosen %s (validation accuracy %s)', {'C': point[0]}, chosen[3]['accuracy'])
+    def run_grid(search_train, search_valid):
+        LOGGER.info('Fitting the grid C = %s', Cs)
+        runs = []
+        for c, clf in zip(Cs, fit(search_train, Cs)):
+            LOGGER.info('Search point %s', {'C': c})
+            runs.append(((c,), clf) + _svm_metrics_on_device(clf, search_train, search_valid, test_data, num_classes))
+        return runs
 
-    if train_with_valid and cut:          # classifier/train.py:471-474: the entire training set, neither merged nor shuffled
-        model = _svm.fit_grid(train_data['features'], train_data['labels'], [point[0]], platt=platt, max_entries=max_entries, **params)[0]
-        train_metrics, _, test_metrics = _svm_metrics_on_device(model, train_data, None, test_data, num_classes)
-    elif train_with_valid:
-        merged_labels = np.concatenate((train_data['labels'], valid_data['labels']))
-        mix = np.random.permutation(merged_labels.size)
-        tx, vx = train_data['features'], valid_data['features']
-        resident = isinstance(tx, DeviceFeatures) and isinstance(vx, DeviceFeatures) and tx.device == vx.device
-        if resident:          # vstack((train, valid))[mix] where the two splits are: one copy kernel, one gather
-            stacked = DeviceFeatures.assemble([(tx, 0, len(tx)), (vx, 0, len(vx))], device=tx.device)
-            try:
-                stacked.handle.gather(mix)
-            except Exception:
-                stacked.close()
-                raise
-        else:
-            stacked = np.vstack((_on_host(train_data)['features'], _on_host(valid_data)['features']))[mix]
-        merged = {'features': stacked, 'labels': merged_labels[mix]}
-        try:
-            model = _svm.fit_grid(merged['features'], merged['labels'], [point[0]], platt=platt, max_entries=max_entries, **params)[0]
-            train_metrics, _, test_metrics = _svm_metrics_on_device(model, merged, None, test_data, num_classes)
-        finally:
-            if resident:
-                stacked.close()
-    else:
-        model, train_metrics, test_metrics = chosen[1], dict(chosen[2]), chosen[4]
+    def refit(point, data):
+        model = fit(data, [point[0]])[0]
+        train_metrics, _, test_metrics = _svm_metrics_on_device(model, data, None, test_data, num_classes)
+        return model, train_metrics, test_metrics
+
+    outcome = _search(train_data, valid_data, ['C'], valid_ratio, split_random_state, train_with_valid, run_grid, refit)
     LOGGER.info('Saving model...')
-    _dump(os.path.join(model_dir, 'model.pkl'), model)
-
-    search_record = {'search_params': ['C'], 'search_params_best_values': point}
-    train_metrics.update(search_record, search={run[0]: run[2] for run in runs})
-    valid_metrics = dict(chosen[3])
-    valid_metrics.update(search_record, search={run[0]: run[3] for run in runs})
-    return model, train_metrics, valid_metrics, test_metrics
+    _dump(os.path.join(model_dir, 'model.pkl'), outcome[0])
+    return outcome
 
 
+# ---- one cross-validation fold ------------------------------------------------------------------------------------------------------
 def _dataset_of(features_dir):
-    """'.../features/us8k/l3/...' -> ('us8k', 'us8k/l3/...'): the path after the last 'features/' and its first part"""
+    """'.../features/us8k/l3/...' -> ('us8k', 'us8k/l3/...'): the path after the last 'features/' and its first part, a dataset"""
     at = features_dir.rindex('features')
     desc = features_dir[at + len('features/'):]
-    return desc.split('/')[0], desc
+    dataset = desc.split('/')[0]
+    if dataset not in DATASET_NUM_CLASSES:
+        raise ValueError('the features directory must name a dataset right after "features/" (one of {})'.format(
+            ', '.join(sorted(DATASET_NUM_CLASSES))))
+    return dataset, desc
 
 
 def _model_id(desc, feature_mode, non_overlap, use_min_max, model_type):
@@ -571,50 +567,85 @@ def _dump(path, obj):
         pk.dump(obj, fh, protocol=pk.HIGHEST_PROTOCOL)
 
 
-def _start_fold(features_dir, output_dir, fold_num, model_type, feature_mode, train_batch_size, patience, random_state,
-                parameter_search, parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid,
-                gsheet_id, google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device,
-                model_args, splits=None, parameter_search_split_seed=None):
-    """what a fold of any model type begins with (classifier/train.py:495-603): the run's directory, config.json, the fold's
-    splits preprocessed, the two scalers pickled -> (model_dir, dataset, splits).  splits: a function of (with_valid_fold) that
-    gives the fold's (train, valid or None, test) in place of usc.get_split (cross_validate's come from its FoldBank)."""
-    dataset, desc = _dataset_of(features_dir)
-    if dataset not in DATASET_NUM_CLASSES:
-        raise ValueError('the features directory must name a dataset right after "features/" (one of {})'.format(
-            ', '.join(sorted(DATASET_NUM_CLASSES))))
+def _searches_on_a_cut(fold):
+    """whether the fold's parameter search has no validation fold and cuts the training rows instead; refuses without the seed"""
+    on_cut = bool(fold['parameter_search'] and not fold['parameter_search_valid_fold'])
+    _require_split_seed(on_cut, fold['parameter_search_split_seed'])
+    return on_cut
 
-    model_id = _model_id(desc, feature_mode, non_overlap, use_min_max, model_type)
-    stamp = datetime.datetime.now().strftime('%Y%m%d%H%M%S')
-    model_dir = os.path.join(output_dir, 'classifier', model_id, 'fold%d' % fold_num, stamp)
+
+# config.json: the reference's keys in its order (no git metadata: git_commit is None), then the two that are named only when set
+_CONFIG_KEYS = ('fold_num', 'parameter_search', 'parameter_search_valid_fold', 'parameter_search_valid_ratio',
+                'parameter_search_train_with_valid', 'model_type', 'feature_mode', 'train_batch_size', 'patience', 'non_overlap',
+                'non_overlap_chunk_size', 'random_state', 'verbose')
+_CONFIG_KEYS_WHEN_SET = ('preprocess_device', 'parameter_search_split_seed')
+
+
+def _run_fold(fold, get_splits=None):
+    """One cross-validation fold of any model type (classifier/train.py:495-709) -> its directory.  fold: the settings, the
+    arguments of train / train_svm_fold by name (model_type, fold_num and model_args among them).  get_splits: a function of
+    (with_valid_fold) that gives the fold's (train, valid or None, test) in place of usc.get_split (cross_validate's come from its
+    FoldBank).  The splits are the driver's from the moment it has them: closed once, whatever fails after that."""
+    on_cut = _searches_on_a_cut(fold)
+    if fold['gsheet_id']:
+        LOGGER.warning('Google Sheets logging is not built; gsheet_id ignored')
+    features_dir, fold_num = fold['features_dir'], fold['fold_num']
+    dataset, desc = _dataset_of(features_dir)
+    model_id = _model_id(desc, fold['feature_mode'], fold['non_overlap'], fold['use_min_max'], fold['model_type'])
+    model_dir = os.path.join(fold['output_dir'], 'classifier', model_id, 'fold%d' % fold_num,
+                             datetime.datetime.now().strftime('%Y%m%d%H%M%S'))
     os.makedirs(model_dir, exist_ok=True)
 
-    # the run's settings under the reference's config.json keys (no git metadata: git_commit is None)
-    settings = dict(username=getpass.getuser(), features_dir=features_dir, output_dir=output_dir, model_dir=model_dir,
-                    model_id=model_id, fold_num=fold_num, parameter_search=parameter_search,
-                    parameter_search_valid_fold=parameter_search_valid_fold,
-                    parameter_search_valid_ratio=parameter_search_valid_ratio,
-                    parameter_search_train_with_valid=parameter_search_train_with_valid, model_type=model_type,
-                    feature_mode=feature_mode, train_batch_size=train_batch_size, patience=patience, non_overlap=non_overlap,
-                    non_overlap_chunk_size=non_overlap_chunk_size, random_state=random_state, verbose=verbose,
-                    git_commit=None, gsheet_id=gsheet_id, google_dev_app_name=google_dev_app_name)
-    if preprocess_device is not None:
-        settings['preprocess_device'] = preprocess_device
-    if parameter_search_split_seed is not None:
-        settings['parameter_search_split_seed'] = parameter_search_split_seed
-    settings.update(model_args)
+    config = dict(username=getpass.getuser(), features_dir=features_dir, output_dir=fold['output_dir'], model_dir=model_dir,
+                  model_id=model_id)
+    config.update((k, fold[k]) for k in _CONFIG_KEYS)
+    config.update(git_commit=None, gsheet_id=fold['gsheet_id'], google_dev_app_name=fold['google_dev_app_name'])
+    config.update((k, fold[k]) for k in _CONFIG_KEYS_WHEN_SET if fold[k] is not None)
+    config.update(fold['model_args'])
     with open(os.path.join(model_dir, 'config.json'), 'w') as fh:
-        json.dump(settings, fh)
+        json.dump(config, fh)
 
-    with_valid_fold = parameter_search_valid_fold or not parameter_search
     LOGGER.info('Fold %d of %s: loading and preprocessing', fold_num, dataset)
-    splits = splits(with_valid_fold) if splits else get_split(features_dir, fold_num - 1, dataset, valid=with_valid_fold)
-    scalers = preprocess_split_data(*splits, feature_mode=feature_mode, non_overlap=non_overlap,
-                                    non_overlap_chunk_size=int(non_overlap_chunk_size), use_min_max=use_min_max,
-                                    device=preprocess_device)
-    for name, scaler in zip(('min_max_scaler.pkl', 'stdizer.pkl'), scalers):
-        _dump(os.path.join(model_dir, name), scaler)
+    get_splits = get_splits or functools.partial(get_split, features_dir, fold_num - 1, dataset)
+    with _closing(get_splits(not on_cut)) as splits:
+        scalers = preprocess_split_data(*splits, feature_mode=fold['feature_mode'], non_overlap=fold['non_overlap'],
+                                        non_overlap_chunk_size=int(fold['non_overlap_chunk_size']), use_min_max=fold['use_min_max'],
+                                        device=fold['preprocess_device'])
+        for name, scaler in zip(('min_max_scaler.pkl', 'stdizer.pkl'), scalers):
+            _dump(os.path.join(model_dir, name), scaler)
+        model_part = {'mlp': _mlp_part, 'svm': _svm_part}[fold['model_type']]
+        _, train_metrics, valid_metrics, test_metrics = model_part(
+            splits, model_dir, dict(fold, num_classes=DATASET_NUM_CLASSES[dataset], search_on_cut=on_cut))
+    _dump(os.path.join(model_dir, 'results.pkl'), {'train': train_metrics, 'valid': valid_metrics, 'test': test_metrics})
+    LOGGER.info('Fold %d done: results in %s', fold_num, model_dir)
+    return model_dir
 
-    return model_dir, dataset, splits
+
+def _mlp_part(splits, model_dir, fold):
+    """the MLP's part of a fold -> (model, train_metrics, valid_metrics, test_metrics): one train_mlp, or the search over learning
+    rate and weight decay"""
+    args = dict(dict(batch_size=fold['train_batch_size'], patience=fold['patience'], random_state=fold['random_state'],
+                     num_classes=fold['num_classes'], verbose=fold['verbose']), **fold['model_args'])
+    if not fold['parameter_search']:
+        return train_mlp(*splits, model_dir, **args)
+    grid = {'learning_rate': [1e-5, 1e-4, 1e-3], 'weight_decay': [1e-5, 1e-4, 1e-3]}
+    if not fold['search_on_cut']:          # with a validation fold: one download; the search then runs as on the host
+        splits = tuple(_on_host(d) for d in splits)
+    # on a cut the splits stay where they are: train_mlp takes DeviceFeatures as it does without a search
+    return train_param_search(*splits, model_dir, train_func=train_mlp, search_space=grid, valid_ratio=fold['parameter_search_valid_ratio'],
+                              train_with_valid=fold['parameter_search_train_with_valid'],
+                              split_random_state=fold['parameter_search_split_seed'], **args)
+
+
+def _svm_part(splits, model_dir, fold):
+    """the SVM's part of a fold -> (model, train_metrics, valid_metrics, test_metrics): one train_svm scored on the device, or the
+    search over C"""
+    args = dict(dict(random_state=fold['random_state'], num_classes=fold['num_classes'], verbose=fold['verbose']), **fold['model_args'])
+    if not fold['parameter_search']:
+        return train_svm(*splits, model_dir, evaluate_on_device=True, **args)
+    if fold['search_on_cut']:
+        args.update(valid_ratio=fold['parameter_search_valid_ratio'], split_random_state=fold['parameter_search_split_seed'])
+    return train_svm_search(*splits, model_dir, train_with_valid=fold['parameter_search_train_with_valid'], platt=fold['platt'], **args)
 
 
 def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='framewise', train_batch_size=64, patience=20,
@@ -632,56 +663,10 @@ def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='fr
     split_random_state), and with preprocess_device the rows stay on the GPU through the cut and every run of the grid; None
     refuses that mode (NO_SSS).  config.json names it only when it is set.
     -> that directory."""
+    fold = dict(locals())          # the fold's settings by name, before any other local exists
     if model_type != 'mlp':
         raise ValueError(ONLY_MLP.format(model_type))
-    return _mlp_fold(None, features_dir, output_dir, fold_num, feature_mode, train_batch_size, patience, random_state, parameter_search,
-                     parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id,
-                     google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args,
-                     parameter_search_split_seed=parameter_search_split_seed)
-
-
-def _close_splits(splits):
-    for d in splits:
-        if d and isinstance(d.get('features'), DeviceFeatures):
-            d['features'].close()
-
-
-def _mlp_fold(splits, features_dir, output_dir, fold_num, feature_mode, train_batch_size, patience, random_state, parameter_search,
-              parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id,
-              google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args,
-              parameter_search_split_seed=None):
-    """train()'s fold; `splits` as _start_fold takes them -> the fold's directory"""
-    without_valid_fold = parameter_search and not parameter_search_valid_fold
-    if without_valid_fold and parameter_search_split_seed is None:
-        raise ValueError(NO_SSS)
-    if gsheet_id:
-        LOGGER.warning('Google Sheets logging is not built; gsheet_id ignored')
-    model_dir, dataset, splits = _start_fold(
-        features_dir, output_dir, fold_num, 'mlp', feature_mode, train_batch_size, patience, random_state, parameter_search,
-        parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id, google_dev_app_name,
-        verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args, splits=splits,
-        parameter_search_split_seed=parameter_search_split_seed)
-
-    common = dict(batch_size=train_batch_size, patience=patience, random_state=random_state,
-                  num_classes=DATASET_NUM_CLASSES[dataset], verbose=verbose)
-    try:
-        if parameter_search:
-            grid = {'learning_rate': [1e-5, 1e-4, 1e-3], 'weight_decay': [1e-5, 1e-4, 1e-3]}
-            if without_valid_fold:          # the splits stay where they are: train_mlp takes DeviceFeatures as it does without a search
-                searched, seed = splits, dict(split_random_state=parameter_search_split_seed)
-            else:                           # one download; the search then runs as on the host
-                searched, seed = tuple(_on_host(d) for d in splits), {}
-            outcome = train_param_search(*searched, model_dir, train_func=train_mlp, search_space=grid,
-                                         valid_ratio=parameter_search_valid_ratio,
-                                         train_with_valid=parameter_search_train_with_valid, **dict(common, **model_args), **seed)
-        else:
-            outcome = train_mlp(*splits, model_dir, **dict(common, **model_args))
-    finally:
-        _close_splits(splits)
-    _, train_metrics, valid_metrics, test_metrics = outcome
-    _dump(os.path.join(model_dir, 'results.pkl'), {'train': train_metrics, 'valid': valid_metrics, 'test': test_metrics})
-    LOGGER.info('Fold %d done: results in %s', fold_num, model_dir)
-    return model_dir
+    return _run_fold(fold)
 
 
 def train_svm_fold(features_dir, output_dir, fold_num, feature_mode='framewise', train_batch_size=64, patience=20,
@@ -697,41 +682,7 @@ def train_svm_fold(features_dir, output_dir, fold_num, feature_mode='framewise',
     model_args (C, kernel, tol, max_iterations).  train_batch_size and patience are recorded as the reference records them; the
     SVM does not use them.  parameter_search_split_seed: as in train(); the cut and the search on it are train_svm_search's.
     -> that directory."""
-    return _svm_fold(None, features_dir, output_dir, fold_num, feature_mode, train_batch_size, patience, random_state, parameter_search,
-                     parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id,
-                     google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, platt, model_args,
-                     parameter_search_split_seed=parameter_search_split_seed)
-
-
-def _svm_fold(splits, features_dir, output_dir, fold_num, feature_mode, train_batch_size, patience, random_state, parameter_search,
-              parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id,
-              google_dev_app_name, verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, platt, model_args,
-              parameter_search_split_seed=None):
-    """train_svm_fold()'s fold; `splits` as _start_fold takes them -> the fold's directory"""
-    without_valid_fold = parameter_search and not parameter_search_valid_fold
-    if without_valid_fold and parameter_search_split_seed is None:
-        raise ValueError(NO_SSS)
-    if gsheet_id:
-        LOGGER.warning('Google Sheets logging is not built; gsheet_id ignored')
-    model_dir, dataset, splits = _start_fold(
-        features_dir, output_dir, fold_num, 'svm', feature_mode, train_batch_size, patience, random_state, parameter_search,
-        parameter_search_valid_fold, parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id, google_dev_app_name,
-        verbose, non_overlap, non_overlap_chunk_size, use_min_max, preprocess_device, model_args, splits=splits,
-        parameter_search_split_seed=parameter_search_split_seed)
-    common = dict(random_state=random_state, num_classes=DATASET_NUM_CLASSES[dataset], verbose=verbose)
-    try:
-        if parameter_search:
-            seed = dict(valid_ratio=parameter_search_valid_ratio, split_random_state=parameter_search_split_seed) if without_valid_fold else {}
-            outcome = train_svm_search(*splits, model_dir, train_with_valid=parameter_search_train_with_valid, platt=platt,
-                                       **dict(common, **model_args), **seed)
-        else:
-            outcome = train_svm(*splits, model_dir, evaluate_on_device=True, **dict(common, **model_args))
-    finally:
-        _close_splits(splits)
-    _, train_metrics, valid_metrics, test_metrics = outcome
-    _dump(os.path.join(model_dir, 'results.pkl'), {'train': train_metrics, 'valid': valid_metrics, 'test': test_metrics})
-    LOGGER.info('Fold %d done: results in %s', fold_num, model_dir)
-    return model_dir
+    return _run_fold(dict(locals(), model_type='svm'))          # the fold's settings by name
 
 
 # what a fold's metrics hold besides numbers and lists of numbers with one entry per class: the per-epoch histories (their length
@@ -783,17 +734,11 @@ def cross_validate(features_dir, output_dir, model_type='svm', folds=None, fold_
     value is a number or a list of numbers}.  Not aggregated (NOT_AGGREGATED): loss_history and accuracy_history, whose lengths
     differ between folds, and the search records search, search_params and search_params_best_values.  In results.json NumPy
     values are plain numbers and the search's tuple keys are strings.  -> that directory."""
+    settings = dict(locals())          # every fold's settings by name, before any other local exists
     if model_type not in ('mlp', 'svm'):
         raise ValueError(ONLY_MLP.format(model_type))
     dataset, desc = _dataset_of(features_dir)
-    if dataset not in DATASET_NUM_CLASSES:
-        raise ValueError('the features directory must name a dataset right after "features/" (one of {})'.format(
-            ', '.join(sorted(DATASET_NUM_CLASSES))))
-    if parameter_search and not parameter_search_valid_fold and parameter_search_split_seed is None:
-        raise ValueError(NO_SSS)
-    fold_args = (feature_mode, train_batch_size, patience, random_state, parameter_search, parameter_search_valid_fold,
-                 parameter_search_valid_ratio, parameter_search_train_with_valid, gsheet_id, google_dev_app_name, verbose, non_overlap,
-                 non_overlap_chunk_size, use_min_max, preprocess_device)
+    _searches_on_a_cut(settings)          # refused before anything is read
     fold_dirs = []
     with FoldBank(features_dir, dataset, device=preprocess_device) as bank:
         folds = list(range(1, bank.num_folds + 1)) if folds is None else [int(f) for f in folds]
@@ -801,22 +746,9 @@ def cross_validate(features_dir, output_dir, model_type='svm', folds=None, fold_
             if not 1 <= fold_num <= bank.num_folds:
                 raise ValueError('fold {} of {} ({} folds, counted from 1)'.format(fold_num, dataset, bank.num_folds))
         for fold_num in folds:
-            made = []
-
-            def splits(with_valid_fold, fold_num=fold_num, made=made):
-                made.extend(bank.split(fold_num - 1, valid=with_valid_fold))
-                return tuple(made)
             if fold_seed is not None:
                 np.random.seed(fold_seed)
-            try:
-                if model_type == 'mlp':
-                    fold_dirs.append(_mlp_fold(splits, features_dir, output_dir, fold_num, *fold_args, model_args,
-                                               parameter_search_split_seed=parameter_search_split_seed))
-                else:
-                    fold_dirs.append(_svm_fold(splits, features_dir, output_dir, fold_num, *fold_args, platt, model_args,
-                                               parameter_search_split_seed=parameter_search_split_seed))
-            finally:
-                _close_splits(made)          # also after a failure between the assembly and the fold's own clean-up
+            fold_dirs.append(_run_fold(dict(settings, fold_num=fold_num), get_splits=functools.partial(bank.split, fold_num - 1)))
 
     results = {'folds': folds, 'fold_dirs': fold_dirs}
     per_fold = []

@@ -1,7 +1,7 @@
 """Folds resident on the GPU: l3_feat_assemble (csrc/featprep.hip) against np.concatenate, usc.FoldBank.split against usc.get_split,
 usc.preprocess_split_data(device=0) on resident splits against uploaded ones, classifier.cross_validate against separate per-fold
-calls, and train_svm_search's merge of two resident splits.  Every comparison is for equal bits: the assembly is a copy, and
-everything after it is the existing code on an identical matrix."""
+calls, the searches' merge of two resident splits, and who closes a fold's splits after a failure.  Every comparison is for equal
+bits: the assembly is a copy, and everything after it is the existing code on an identical matrix."""
 import os
 import pickle
 
@@ -321,3 +321,76 @@ def test_search_merges_resident_splits_on_the_device(gpu_required, tmp_path, mon
         np.testing.assert_array_equal(getattr(got[0], name), getattr(want[0], name), err_msg=name)
     for d, x in zip(resident, (train, valid, test)):          # the splits themselves are as they were
         np.testing.assert_array_equal(_bits(to_host(d['features'])), _bits(x['features']))
+
+
+def _closed(f):
+    return f.handle.h is None
+
+
+@pytest.mark.parametrize('D', [20, 7])          # rows of 80 bytes move as 16-byte accesses, rows of 28 bytes as 4-byte ones
+def test_param_search_merges_resident_splits_on_the_device(gpu_required, tmp_path, monkeypatch, D):
+    """train_param_search with a validation fold and train_with_valid on two resident splits: the retrain's train + valid is put
+    together and shuffled on the GPU, as train_svm_search's is, and everything equals the same search on the same rows as arrays"""
+    r = np.random.RandomState(D)
+    nc = 4
+    centres = r.randn(nc, D) * 0.9
+
+    def split(n):
+        y = np.arange(n) % nc
+        return {'features': (centres[y] + r.randn(n, D)).astype(np.float32), 'labels': y}
+    train, valid = split(96), split(32)
+    yf = np.arange(8) % nc
+    test = {'features': (centres[np.repeat(yf, 6)] + r.randn(48, D)).astype(np.float32), 'labels': yf,
+            'file_idxs': [(6 * f, 6 * f + 6) for f in range(8)]}
+    d1, d2 = str(tmp_path / 'a'), str(tmp_path / 'b')
+    os.makedirs(d1), os.makedirs(d2)
+    args = dict(train_func=classifier.train_svm, search_space={'C': [0.5, 2.0]}, train_with_valid=True, evaluate_on_device=True,
+                num_classes=nc, random_state=3)
+    np.random.seed(7)
+    want = classifier.train_param_search(train, valid, test, d1, **args)
+
+    resident = [usc.DeviceFeatures(d['features'], 0) for d in (train, valid)]
+    made = []
+    assemble = usc.DeviceFeatures.assemble.__func__
+
+    def watched(cls, segments, device=0):
+        made.append(assemble(cls, segments, device))
+        return made[-1]
+    monkeypatch.setattr(usc.DeviceFeatures, 'assemble', classmethod(watched))
+    np.random.seed(7)
+    got = classifier.train_param_search(dict(train, features=resident[0]), dict(valid, features=resident[1]), test, d2, **args)
+    for name in ('dual_coef_', 'support_', 'intercept_', 'probA_', 'probB_'):
+        np.testing.assert_array_equal(getattr(got[0], name), getattr(want[0], name), err_msg=name)
+    for k in range(1, 4):
+        np.testing.assert_equal(got[k], want[k])
+    assert got[1]['search_params_best_values'] == want[1]['search_params_best_values'] and len(got[2]['search']) == 2
+    # the merged matrix was made on the GPU and is closed; the caller's two are open and as they were
+    assert len(made) == 1 and all(_closed(f) for f in made)
+    for f, d in zip(resident, (train, valid)):
+        assert not _closed(f)
+        np.testing.assert_array_equal(_bits(f.to_host()), _bits(d['features']))
+        f.close()
+
+
+def test_cross_validate_closes_the_fold_after_an_early_failure(gpu_required, tmp_path, monkeypatch):
+    """a failure between the assembly of a fold's splits and its fit (here: the preprocessing) closes the splits, and the bank"""
+    feats = str(tmp_path / 'features' / 'esc50' / 'l3' / 'x')
+    _write_feature_tree(feats)
+    banks, made = [], []
+    split = usc.FoldBank.split
+
+    def watched(self, test_fold_idx, valid=True):
+        splits = split(self, test_fold_idx, valid=valid)
+        banks.append(self)
+        made.extend(d['features'] for d in splits if d)
+        return splits
+    monkeypatch.setattr(usc.FoldBank, 'split', watched)
+
+    def failing(*splits, **kwargs):
+        assert len(made) == 3 and not any(_closed(f) for f in made)          # the splits exist
+        raise RuntimeError('the preprocessing fails')
+    monkeypatch.setattr(classifier, 'preprocess_split_data', failing)
+    with pytest.raises(RuntimeError, match='the preprocessing fails'):
+        classifier.cross_validate(feats, str(tmp_path / 'out'), preprocess_device=0, folds=[2])
+    assert len(made) == 3 and all(isinstance(f, usc.DeviceFeatures) and _closed(f) for f in made)
+    assert len(banks) == 1 and banks[0].folds is None
