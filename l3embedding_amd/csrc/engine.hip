@@ -23,6 +23,7 @@
 
 #include "../../include/l3hip.h"
 #include "comm.h"
+#include "conv_path.h"
 #include "kernels.h"
 
 namespace {
@@ -67,19 +68,19 @@ struct Param {
 };
 
 // The kernel path of one tower op, resolved by plan_tower() at the head of a pass and only executed by tower_forward() /
-// tower_backward_block().  Flops are the issued ones (-1: the algorithmic count), bytes the algorithmic HBM traffic of the launch.
-enum ConvFwd { CF_BF16_STORED, CF_BF16_CAST, CF_FIRST, CF_FP32 };      // bf16 MFMA (operands stored bf16 / cast at fetch), FMA first layer, conv_fwd
-enum ConvWgrad { WG_AUG, WG_AUG_DEFERRED, WG_BF16_STORED, WG_BF16_CAST, WG_FP32 };      // augmented first layer (dY formed from the deferred BatchNorm), ...
-enum ConvDgrad { DG_NONE, DG_SMALL, DG_BF16_STORED, DG_BF16_CAST, DG_WINO, DG_FLIPPED };
+// tower_backward_block().  The convolution's own paths (with their issued flops) are conv_path.h's; bytes are the algorithmic
+// HBM traffic of the launch.
+enum FirstWgrad { FW_NONE, FW_AUG, FW_AUG_DEFERRED };      // augmented first layer (dY formed from the deferred BatchNorm): replaces wgrad + dgrad
 struct ConvPlan {
-    ConvFwd fwd = CF_FP32;
-    bool wino_filter = false;    // the forward filter is transformed into the Winograd domain first and conv_fwd is given it
+    ConvStorage st;              // the storage of the op's tensors, fixed at creation
+    ConvFwdPath fwd;
     int stat_mode = 0;           // > 0: the epilogue leaves the BatchNorm statistic partials of op.bn_follow (1 output, 2 relu(output))
-    ConvWgrad wgrad = WG_FP32;
+    FirstWgrad aug = FW_NONE;
+    ConvWgradPath wgrad;
     bool colsum = false;         // the bias gradient is a launch of its own
-    ConvDgrad dgrad = DG_NONE;
+    ConvDgradPath dgrad;
     int bwd_bn = -1;             // >= 0: the data gradient's epilogue leaves this BatchNorm's backward reduction partials (BnBwdFuse)
-    double fwd_executed = -1.0, fwd_bytes = 0.0, wg_executed = -1.0, wg_bytes = 0.0, dg_executed = -1.0, dg_bytes = 0.0;
+    double fwd_bytes = 0.0, wg_bytes = 0.0, dg_bytes = 0.0;
 };
 enum BnStats { BS_PARTIALS, BS_FAST, BS_PLAIN, BS_MOVING };
 enum BnBwd { BB_BY_FIRST_CONV, BB_FAST_POOLED, BB_FAST, BB_FAST_DEFERRED, BB_PLAIN };      // (training) the first conv produces it, ...
@@ -410,20 +411,13 @@ int push_conv(l3_engine* e, Tower& tw, const std::string& name, int cout, int kh
     Tensor y;
     y.N = x.N;
     y.C = cout;
-    int pt = 0, pl = 0;
-    if (same) {
-        tf_same(x.H, kh, 1, &y.H, &pt);
-        tf_same(x.W, kw, 1, &y.W, &pl);
-    } else {
-        y.H = x.H - kh + 1;
-        y.W = x.W - kw + 1;
-    }
-    y.batch_stride = (int64_t)y.H * y.W * y.C;
     op.kh = kh; op.kw = kw; op.cout = cout; op.same = same;
-    op.geom = ConvGeom{x.N, x.H, x.W, x.C, y.H, y.W, cout, kh, kw, pt, pl};
-    // data gradient = stride-1 conv of dY with flipped/transposed filter, pad' = k-1-pad
-    op.dgeom = ConvGeom{x.N, y.H, y.W, cout, x.H, x.W, x.C, kh, kw, kh - 1 - pt, kw - 1 - pl};
-    op.geom.f2x2 = op.dgeom.f2x2 = e->cfg.fp32_conv == L3_FP32_CONV_F2X2 ? 1 : e->cfg.fp32_conv == L3_FP32_CONV_F2X2_BF16X6 ? 2 : 0;
+    op.geom = conv_geom(x.N, x.H, x.W, x.C, cout, kh, kw, same,
+                        e->cfg.fp32_conv == L3_FP32_CONV_F2X2 ? 1 : e->cfg.fp32_conv == L3_FP32_CONV_F2X2_BF16X6 ? 2 : 0);
+    op.dgeom = conv_dgrad_geom(op.geom);
+    y.H = op.geom.Ho;
+    y.W = op.geom.Wo;
+    y.batch_stride = (int64_t)y.H * y.W * y.C;
     add_param(e, tw.prefix + "/" + name + "/kernel", {kh, kw, x.C, cout}, true, PK_KERNEL, &op.p_kernel);
     add_param(e, tw.prefix + "/" + name + "/bias", {cout}, true, PK_BIAS, &op.p_bias);
     tw.t.push_back(y);
@@ -1241,11 +1235,15 @@ int run_frontend(l3_engine* e) {
 static inline double act_bytes(const Tensor& t) { return (double)t.numel() * (t.d_bf16 ? 2.0 : 4.0); }
 static inline double grad_bytes(const Tensor& t) { return (double)t.numel() * (t.g_bf16 ? 2.0 : 4.0); }
 
-// Resolves, for one pass over a tower, which kernel path every convolution and BatchNorm takes (Op::cp, Op::bp): the only place that
-// asks the kernels' predicates, the engine's dtype and the per-call debug knobs (L3_WINO4, L3_CONV_FIRST, L3_BF16_HALO: the kernels
-// read them per launch, so a plan holds for the pass it was resolved for -- a forward and the backward behind it).  Also the
-// per-pass launch settings of every convolution: ConvGeom::solo is 1 while the tower runs on its own (l3_tower_step, l3_embed_*),
-// 0 in the two-tower step (kernels.h).
+// Resolves, for one pass over a tower, which kernel path every convolution and BatchNorm takes (Op::cp, Op::bp).  The path of a
+// convolution on its own -- forward, weight gradient, data gradient, from its geometry and its tensors' storage -- is resolved by
+// conv_path.h, the one place in the library that asks the convolution kernels' predicates and, through them, the per-call debug
+// knobs (L3_WINO4, L3_CONV_FIRST, L3_BF16_HALO: the kernels read them per launch, so a plan holds for the pass it was resolved
+// for -- a forward and the backward behind it); the operator entry points and VGGish resolve there too.  What only an engine
+// knows is decided here: which BatchNorm takes a convolution's epilogue partials (forward statistics, backward reduction) and
+// whether they fit the scratch, the deferred BatchNorm and the augmented first layer, the separate bias column sum, the BatchNorm
+// paths and the byte accounting.  Also the per-pass launch settings of every convolution: ConvGeom::solo is 1 while the tower
+// runs on its own (l3_tower_step, l3_embed_*), 0 in the two-tower step (kernels.h).
 int plan_tower(l3_engine* e, Tower& tw, bool training, int solo) {
     static const int epi_stats = knob_int("L3_EPILOGUE_STATS", 1);
     const bool bf16 = e->cfg.dtype == L3_DTYPE_BF16;
@@ -1278,15 +1276,13 @@ int plan_tower(l3_engine* e, Tower& tw, bool training, int solo) {
         const Tensor &x = tw.t[op.in], &y = tw.t[op.out];
         const double wbytes = (double)e->params[op.p_kernel].numel * 4.0;
         ConvPlan& p = op.cp = ConvPlan{};
+        p.st = ConvStorage{bf16, x.d_bf16, y.d_bf16, y.g_bf16, x.g_bf16};
         // forward.  Training: the epilogue also leaves the batch-norm statistic partials of its output
-        const bool mp = bf16 && conv_bf16_ok(op.geom);      // mixed precision: bf16 operands, fp32 accumulate (conv_bf16.hip)
-        p.fwd = mp ? (x.d_bf16 ? CF_BF16_STORED : CF_BF16_CAST) : conv_first_ok(op.geom) ? CF_FIRST : CF_FP32;
-        p.wino_filter = op.wino_uf && !mp;
-        p.fwd_executed = p.wino_filter ? conv_wino_executed_flops(op.geom) : -1.0;
+        p.fwd = conv_resolve_fwd(op.geom, p.st, op.wino_uf != nullptr);
         p.fwd_bytes = act_bytes(x) + act_bytes(y) + wbytes;
-        const int nblk = p.fwd == CF_BF16_STORED ? conv_bf16_stat_blocks(op.geom)
-                         : p.fwd == CF_FIRST     ? conv_first_stat_blocks(op.geom)
-                         : p.fwd == CF_FP32 && p.wino_filter ? conv_wino_stat_blocks(op.geom) : 0;
+        const int nblk = p.fwd.path == CF_BF16_STORED ? conv_bf16_stat_blocks(op.geom)
+                         : p.fwd.path == CF_FIRST     ? conv_first_stat_blocks(op.geom)
+                         : p.fwd.path == CF_FP32 && p.fwd.wino_filter ? conv_wino_stat_blocks(op.geom) : 0;
         if (epi_stats && training && op.bn_follow >= 0 && e->stat_max > 0 && nblk > 0) {
             if (!fits(op, nblk, op.geom.Cout)) return L3_ESTATE;
             p.stat_mode = tw.ops[op.bn_follow].prerelu ? 2 : 1;
@@ -1296,21 +1292,15 @@ int plan_tower(l3_engine* e, Tower& tw, bool training, int solo) {
         if (training && op.in_bn >= 0) {
             // [x^, 1]; + dY, or the conv output and the gradient behind its BatchNorm
             const Op* fb = op.bn_defer >= 0 && defers(tw.ops[op.bn_defer]) ? &tw.ops[op.bn_defer] : nullptr;
-            p.wgrad = fb ? WG_AUG_DEFERRED : WG_AUG;
+            p.aug = fb ? FW_AUG_DEFERRED : FW_AUG;
             p.wg_bytes = (double)x.rows() * op.ageom.Cin * 4.0 + (fb ? act_bytes(tw.t[fb->in]) + grad_bytes(tw.t[fb->out]) : grad_bytes(y));
             continue;       // gamma / beta / bias gradients come with it, and nothing trainable lies in front
         }
-        const bool wbf = bf16 && conv_wgrad_bf16_ok(op.geom);
-        p.wgrad = !wbf ? WG_FP32 : x.d_bf16 && y.g_bf16 ? WG_BF16_STORED : WG_BF16_CAST;
-        p.wg_executed = conv_wgrad_executed_flops(op.geom, wbf);
+        p.wgrad = conv_resolve_wgrad(op.geom, p.st);
         p.wg_bytes = act_bytes(x) + grad_bytes(y) + wbytes;
         p.colsum = !op.bias_by_bn;
         if (!op.need_dx) continue;
-        const bool dbf = bf16 && conv_bf16_ok(op.dgeom);
-        p.dgrad = conv_dgrad_small_ok(op.geom) ? DG_SMALL
-                  : dbf                        ? (y.g_bf16 ? DG_BF16_STORED : DG_BF16_CAST)
-                  : op.wino_ud                 ? DG_WINO : DG_FLIPPED;
-        p.dg_executed = op.wino_ud && !dbf ? conv_wino_executed_flops(op.dgeom) : -1.0;
+        p.dgrad = conv_resolve_dgrad(op.geom, op.dgeom, p.st, op.wino_ud != nullptr);
         p.dg_bytes = grad_bytes(y) + grad_bytes(x) + wbytes;
         // the gradient this launch writes is dL/dy of the BatchNorm(+ReLU) in front of the conv (through the 2x2 pool folded into
         // it: over the window winners): the epilogue leaves that BatchNorm's backward reduction partials -- the halo kernel on
@@ -1320,8 +1310,8 @@ int plan_tower(l3_engine* e, Tower& tw, bool training, int solo) {
         if (bn == nullptr) continue;
         const bool bx = tw.t[bn->in].d_bf16;
         int blocks = -1;
-        if (p.dgrad == DG_BF16_STORED && x.g_bf16 && bx && conv_bf16_halo_ok(op.dgeom)) blocks = conv_bf16_stat_blocks(op.dgeom);
-        if (p.dgrad == DG_WINO && !x.g_bf16 && !bx && conv_wino_ok(op.dgeom)) blocks = conv_wino_stat_blocks(op.dgeom);
+        if (p.dgrad.path == DG_BF16_STORED && x.g_bf16 && bx && conv_bf16_halo_ok(op.dgeom)) blocks = conv_bf16_stat_blocks(op.dgeom);
+        if (p.dgrad.path == DG_WINO && !x.g_bf16 && !bx && conv_wino_ok(op.dgeom)) blocks = conv_wino_stat_blocks(op.dgeom);
         if (blocks < 0) continue;
         if (!fits(op, blocks, op.dgeom.Cout)) return L3_ESTATE;
         p.bwd_bn = op.dy_to_bn;
@@ -1355,27 +1345,13 @@ void tower_forward(l3_engine* e, Tower& tw) {
         switch (op.kind) {
             case OP_CONV: {
                 const ConvPlan& p = op.cp;
-                const float *w = e->params[op.p_kernel].d, *bias = e->params[op.p_bias].d;
-                float* part = p.stat_mode ? e->stat_scratch : nullptr;
-                ProfScope ps(e, F_CONV_FWD, conv_flops(op.geom), op.name.c_str(), p.fwd_executed);
+                ConvBufs b;
+                b.x = x.d, b.w = e->params[op.p_kernel].d, b.bias = e->params[op.p_bias].d, b.y = y.d;
+                b.wprep = op.wflip, b.wino_u = op.wino_uf;
+                b.stat_part = p.stat_mode ? e->stat_scratch : nullptr, b.stat_mode = p.stat_mode;
+                ProfScope ps(e, F_CONV_FWD, conv_flops(op.geom), op.name.c_str(), p.fwd.executed);
                 ps.bytes(p.fwd_bytes);
-                if (p.wino_filter) conv_wino_transform_weights(w, op.wino_uf, op.geom, false, e->stream);
-                switch (p.fwd) {
-                    case CF_BF16_STORED:
-                        conv_weights_bf16(w, op.wflip, op.kh, op.kw, x.C, op.cout, true, e->stream);
-                        conv_bf16_fwd(x.d, op.wflip, bias, y.d, op.geom, e->stream, true, part, p.stat_mode, y.d_bf16);
-                        break;
-                    case CF_BF16_CAST:
-                        conv_flip_weights(w, op.wflip, op.kh, op.kw, x.C, op.cout, e->stream);
-                        conv_bf16_fwd(x.d, op.wflip, bias, y.d, op.geom, e->stream);
-                        break;
-                    case CF_FIRST:      // FMA kernel with the statistics (and, bf16 engines, the bf16 store) fused
-                        conv_first_fwd(x.d, w, bias, y.d, op.geom, e->stream, part, p.stat_mode, y.d_bf16);
-                        break;
-                    case CF_FP32:
-                        conv_fwd(x.d, w, bias, y.d, op.geom, e->stream, p.wino_filter ? op.wino_uf : nullptr, part, p.stat_mode);
-                        break;
-                }
+                conv_run_fwd(p.fwd, op.geom, p.st, b, e->stream);
                 break;
             }
             case OP_BN: {
@@ -1490,11 +1466,11 @@ void tower_backward_block(l3_engine* e, Tower& tw, int block) {
             case OP_CONV: {
                 const ConvPlan& p = op.cp;
                 const float* w = e->params[op.p_kernel].d;
-                if (p.wgrad == WG_AUG || p.wgrad == WG_AUG_DEFERRED) {
+                if (p.aug != FW_NONE) {
                     ProfScope ps(e, F_CONV_WGRAD, conv_flops(op.geom), op.name.c_str());
                     ps.bytes(p.wg_bytes);
                     const Op& bn = tw.ops[op.in_bn];
-                    if (p.wgrad == WG_AUG_DEFERRED) {
+                    if (p.aug == FW_AUG_DEFERRED) {
                         // the BatchNorm behind this conv left coefficients (in the scratch of its bn_bwd_fast), not dY: formed inside the
                         // weight-gradient kernel from the conv's stored output and the gradient behind the BatchNorm; the bias gradient
                         // is the ones-channel row
@@ -1509,49 +1485,32 @@ void tower_backward_block(l3_engine* e, Tower& tw, int block) {
                     }
                     first_conv_grads(op.gaug, w, e->params[bn.p_gamma].d, e->params[bn.p_beta].d, e->params[op.p_kernel].g,
                                      e->params[bn.p_gamma].g, e->params[bn.p_beta].g,
-                                     op.bias_by_bn && p.wgrad == WG_AUG ? nullptr : e->params[op.p_bias].g, op.kh * op.kw, x.C, op.cout,
+                                     op.bias_by_bn && p.aug == FW_AUG ? nullptr : e->params[op.p_bias].g, op.kh * op.kw, x.C, op.cout,
                                      e->stream);
                     break;
                 }
+                ConvBufs b;
+                b.x = x.d, b.w = w, b.y = y.g, b.dx = x.g, b.dw = e->params[op.p_kernel].g;
+                b.wprep = op.wflip, b.wino_u = op.wino_ud, b.wg_part = e->wg_scratch;
                 {
-                    ProfScope ps(e, F_CONV_WGRAD, conv_flops(op.geom), op.name.c_str(), p.wg_executed);
+                    ProfScope ps(e, F_CONV_WGRAD, conv_flops(op.geom), op.name.c_str(), p.wgrad.executed);
                     ps.bytes(p.wg_bytes);
-                    conv_wgrad(x.d, y.g, e->params[op.p_kernel].g, e->wg_scratch, op.geom, e->stream, p.wgrad != WG_FP32,
-                               p.wgrad == WG_BF16_STORED);
+                    conv_run_wgrad(p.wgrad, op.geom, b, e->stream);
                 }
                 if (p.colsum) {
                     ProfScope ps(e, F_ELEMWISE, 0.0);
                     ps.bytes(grad_bytes(y));
                     colsum(y.g, e->params[op.p_bias].g, e->red_scratch, y.rows(), y.C, e->stream);
                 }
-                if (p.dgrad == DG_NONE) break;
-                ProfScope ps(e, F_CONV_DGRAD, conv_flops(op.geom), op.name.c_str(), p.dg_executed);
+                if (p.dgrad.path == DG_NONE) break;
+                ProfScope ps(e, F_CONV_DGRAD, conv_flops(op.geom), op.name.c_str(), p.dgrad.executed);
                 ps.bytes(p.dg_bytes);
                 BnBwdFuse bb{};
-                if (p.bwd_bn >= 0) bb = bn_bwd_fuse(tw, tw.ops[p.bwd_bn]);
-                const BnBwdFuse* fuse = p.bwd_bn >= 0 ? &bb : nullptr;
-                float* part = p.bwd_bn >= 0 ? e->stat_scratch : nullptr;
-                switch (p.dgrad) {
-                    case DG_SMALL:
-                        (void)conv_dgrad_small(y.g, w, x.g, op.geom, e->stream);
-                        break;
-                    case DG_BF16_STORED:       // filter cast once into the (now free) forward-operand buffer
-                        conv_weights_bf16(w, op.wflip, op.kh, op.kw, x.C, op.cout, false, e->stream);
-                        conv_bf16_fwd(y.g, op.wflip, nullptr, x.g, op.dgeom, e->stream, true, part, 0, x.g_bf16, fuse);
-                        break;
-                    case DG_BF16_CAST:
-                        conv_bf16_fwd(y.g, w, nullptr, x.g, op.dgeom, e->stream);
-                        break;
-                    case DG_WINO:
-                        conv_wino_transform_weights(w, op.wino_ud, op.dgeom, true, e->stream);
-                        conv_fwd(y.g, nullptr, nullptr, x.g, op.dgeom, e->stream, op.wino_ud, part, 0, fuse);
-                        break;
-                    case DG_FLIPPED:
-                        conv_flip_weights(w, op.wflip, op.kh, op.kw, x.C, op.cout, e->stream);
-                        conv_fwd(y.g, op.wflip, nullptr, x.g, op.dgeom, e->stream);
-                        break;
-                    case DG_NONE: break;
+                if (p.bwd_bn >= 0) {
+                    bb = bn_bwd_fuse(tw, tw.ops[p.bwd_bn]);
+                    b.bn_bwd = &bb, b.stat_part = e->stat_scratch;
                 }
+                conv_run_dgrad(p.dgrad, op.geom, op.dgeom, p.st, b, e->stream);
                 break;
             }
             default: break;

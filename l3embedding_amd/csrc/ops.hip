@@ -1,6 +1,6 @@
 // ops.hip -- stand-alone operator entry points of the C ABI (host buffers in/out).
-// They run exactly the kernels the engine uses and exist for the op-level parity
-// tests in tests/ (each op replaces a TF op instantiated by a Keras/kapre layer,
+// They run the kernels the engine uses -- the convolutions through the engine's own path resolution and launches (conv_path.h) --
+// and exist for the op-level parity tests in tests/ (each op replaces a TF op instantiated by a Keras/kapre layer,
 // SURVEY.md section 2.3).
 #include <hip/hip_runtime.h>
 
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/l3hip.h"
+#include "conv_path.h"
 #include "kernels.h"
 #include "knobs.h"
 #include "mlp.h"
@@ -41,6 +42,13 @@ struct Scope {
         if (hipDeviceSynchronize() != hipSuccess) ok = false;
         if (hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) ok = false;
     }
+    // `dev` holds count floats, or (bf16) count bfloat16 values: returned widened, every value a bfloat16
+    void get_stored(float* host, const float* dev, size_t count, bool bf16) {
+        if (!bf16) return get(host, dev, count);
+        std::vector<uint16_t> h16(count);
+        get(h16.data(), reinterpret_cast<const uint16_t*>(dev), count);
+        if (host) widen_bf16(host, h16.data(), count);
+    }
     int status() {
         if (hipDeviceSynchronize() != hipSuccess) ok = false;
         if (hipGetLastError() != hipSuccess) ok = false;
@@ -49,17 +57,10 @@ struct Scope {
 };
 
 ConvGeom make_geom(int n, int h, int w, int cin, int cout, int kh, int kw, int same) {
-    ConvGeom g{n, h, w, cin, 0, 0, cout, kh, kw, 0, 0};
-    if (same) {
-        tf_same(h, kh, 1, &g.Ho, &g.padT);
-        tf_same(w, kw, 1, &g.Wo, &g.padL);
-    } else {
-        g.Ho = h - kh + 1;
-        g.Wo = w - kw + 1;
-    }
-    g.solo = 1;          // an operator on its own: nothing queued beside it
     const char* algo = l3_knob("L3_FP32_CONV");          // the tests run every l3_config.fp32_conv value through the operators
-    if (algo != nullptr) g.f2x2 = strcmp(algo, "f2x2_bf16x6") == 0 ? 2 : strcmp(algo, "f2x2") == 0 ? 1 : 0;
+    ConvGeom g = conv_geom(n, h, w, cin, cout, kh, kw, same != 0,
+                           algo == nullptr ? 0 : strcmp(algo, "f2x2_bf16x6") == 0 ? 2 : strcmp(algo, "f2x2") == 0 ? 1 : 0);
+    g.solo = 1;          // an operator on its own: nothing queued beside it
     return g;
 }
 
@@ -79,63 +80,37 @@ PoolGeom make_pool(int n, int h, int w, int c, int ph, int pw, int sh, int sw, i
 
 extern "C" {
 
+// Upload, map `dtype` to the tensors' storage, resolve as the engine does (conv_path.h), run, download.  L3_OP_BF16_STORED(_OUT):
+// bfloat16 in HBM as alloc_everything lays a mixed-precision layer out -- x where the bf16 kernel reads it, y (_OUT; returned
+// widened) where that kernel or the first-layer kernel writes it.
 int l3_op_conv2d_fwd_dt(int device, int dtype, const float* x, const float* w, const float* b, float* y, int n, int h,
                         int wd, int cin, int cout, int kh, int kw, int same) {
     Scope sc(device);
     if (!sc.ok) return L3_EHIP;
     const ConvGeom g = make_geom(n, h, wd, cin, cout, kh, kw, same);
-    float* dx = sc.put(x, (size_t)n * h * wd * cin);
-    float* dw = sc.put(w, (size_t)kh * kw * cin * cout);
-    float* db = b ? sc.put(b, (size_t)cout) : nullptr;
-    float* dy = sc.alloc<float>((size_t)n * g.Ho * g.Wo * cout);
+    const size_t nx = (size_t)n * h * wd * cin, nw = (size_t)kh * kw * cin * cout, ny = (size_t)n * g.Ho * g.Wo * cout;
+    const bool stored = dtype == L3_OP_BF16_STORED || dtype == L3_OP_BF16_STORED_OUT;
+    ConvStorage st;
+    st.mixed = dtype != L3_DTYPE_F32;
+    st.x_bf16 = stored && conv_bf16_ok(g);
+    const ConvFwdPath p = conv_resolve_fwd(g, st, conv_wino_floats(g) != 0);
+    st.y_bf16 = dtype == L3_OP_BF16_STORED_OUT && (p.path == CF_BF16_STORED || p.path == CF_FIRST);
+    ConvBufs cb;
+    float* d_x = sc.put(x, nx);
+    cb.x = d_x;
+    cb.w = sc.put(w, nw);
+    cb.bias = b ? sc.put(b, (size_t)cout) : nullptr;
+    cb.y = sc.alloc<float>(ny);
+    cb.wprep = sc.alloc<float>(nw);
+    cb.wino_u = p.wino_filter ? sc.alloc<float>(conv_wino_floats(g)) : nullptr;
+    uint16_t* xb = st.x_bf16 ? sc.alloc<uint16_t>(nx) : nullptr;
     if (!sc.ok) return L3_ENOMEM;
-    if ((dtype == L3_OP_BF16_STORED || dtype == L3_OP_BF16_STORED_OUT) && conv_bf16_ok(g)) {
-        // the engine's mixed-precision layers: activation and filter live in HBM as bfloat16
-        const size_t nx = (size_t)n * h * wd * cin, nw = (size_t)kh * kw * cin * cout, ny = (size_t)n * g.Ho * g.Wo * cout;
-        uint16_t* xb = sc.alloc<uint16_t>(nx);
-        uint16_t* wb = sc.alloc<uint16_t>(2 * nw);      // both layouts of conv_weights_bf16
-        if (!sc.ok) return L3_ENOMEM;
-        cast_bf16(dx, xb, (int64_t)nx, sc.s);
-        conv_weights_bf16(dw, wb, kh, kw, cin, cout, true, sc.s);
-        if (dtype == L3_OP_BF16_STORED_OUT) {
-            // ... and so does the output (read back widened: every value returned is a bfloat16)
-            uint16_t* yb = sc.alloc<uint16_t>(ny);
-            if (!sc.ok) return L3_ENOMEM;
-            conv_bf16_fwd(reinterpret_cast<const float*>(xb), reinterpret_cast<const float*>(wb), db,
-                          reinterpret_cast<float*>(yb), g, sc.s, true, nullptr, 0, true);
-            std::vector<uint16_t> hy(ny);
-            sc.get(hy.data(), yb, ny);
-            widen_bf16(y, hy.data(), ny);
-            return sc.status();
-        }
-        conv_bf16_fwd(reinterpret_cast<const float*>(xb), reinterpret_cast<const float*>(wb), db, dy, g, sc.s, true);
-    } else if (dtype != L3_DTYPE_F32 && conv_bf16_ok(g)) {
-        float* dwn = sc.alloc<float>((size_t)kh * kw * cin * cout);
-        if (!sc.ok) return L3_ENOMEM;
-        conv_flip_weights(dw, dwn, kh, kw, cin, cout, sc.s);
-        conv_bf16_fwd(dx, dwn, db, dy, g, sc.s);
-    } else if (conv_first_ok(g)) {
-        if (dtype == L3_OP_BF16_STORED_OUT) {                 // first conv of a tower in a bf16 engine: fp32 math, bf16 store
-            const size_t ny = (size_t)n * g.Ho * g.Wo * cout;
-            uint16_t* yb = sc.alloc<uint16_t>(ny);
-            if (!sc.ok) return L3_ENOMEM;
-            conv_first_fwd(dx, dw, db, yb, g, sc.s, nullptr, 0, true);
-            std::vector<uint16_t> hy(ny);
-            sc.get(hy.data(), yb, ny);
-            widen_bf16(y, hy.data(), ny);
-            return sc.status();
-        }
-        conv_first_fwd(dx, dw, db, dy, g, sc.s);
-    } else {
-        float* du = nullptr;
-        if (conv_wino_floats(g)) {
-            du = sc.alloc<float>(conv_wino_floats(g));
-            if (!sc.ok) return L3_ENOMEM;
-            conv_wino_transform_weights(dw, du, g, false, sc.s);
-        }
-        conv_fwd(dx, dw, db, dy, g, sc.s, du);
+    if (st.x_bf16) {
+        cast_bf16(d_x, xb, (int64_t)nx, sc.s);
+        cb.x = reinterpret_cast<const float*>(xb);
     }
-    sc.get(y, dy, (size_t)n * g.Ho * g.Wo * cout);
+    conv_run_fwd(p, g, st, cb, sc.s);
+    sc.get_stored(y, cb.y, ny, st.y_bf16);
     return sc.status();
 }
 
@@ -144,72 +119,48 @@ int l3_op_conv2d_fwd(int device, const float* x, const float* w, const float* b,
     return l3_op_conv2d_fwd_dt(device, L3_DTYPE_F32, x, w, b, y, n, h, wd, cin, cout, kh, kw, same);
 }
 
+// As the forward: bfloat16-stored operands (x, dy; _OUT: dx too, returned widened) where the engine keeps them so, i.e. where
+// both gradients of the layer take a bf16 kernel; the bias gradient stays a plain fp32 column sum of the unrounded dy.
 int l3_op_conv2d_bwd_dt(int device, int dtype, const float* x, const float* w, const float* dy, float* dx, float* dw,
                         float* db, int n, int h, int wd, int cin, int cout, int kh, int kw, int same) {
     Scope sc(device);
     if (!sc.ok) return L3_EHIP;
-    const ConvGeom g = make_geom(n, h, wd, cin, cout, kh, kw, same);
+    const ConvGeom g = make_geom(n, h, wd, cin, cout, kh, kw, same), dg = conv_dgrad_geom(g);
     const size_t nx = (size_t)n * h * wd * cin, ny = (size_t)n * g.Ho * g.Wo * cout, nw = (size_t)kh * kw * cin * cout;
+    const bool stored = (dtype == L3_OP_BF16_STORED || dtype == L3_OP_BF16_STORED_OUT) && conv_wgrad_bf16_ok(g) && conv_bf16_ok(dg);
+    ConvStorage st;
+    st.mixed = dtype != L3_DTYPE_F32;
+    st.x_bf16 = st.dy_bf16 = stored;
+    st.dx_bf16 = stored && dtype == L3_OP_BF16_STORED_OUT;
+    const ConvWgradPath pw = conv_resolve_wgrad(g, st);
+    const ConvDgradPath pd = conv_resolve_dgrad(g, dg, st, conv_wino_floats(dg) != 0);
+    ConvBufs cb;
     float* d_x = sc.put(x, nx);
-    float* d_w = sc.put(w, nw);
     float* d_dy = sc.put(dy, ny);
-    float* d_dx = sc.alloc<float>(nx);
-    float* d_dw = sc.alloc<float>(nw);
+    cb.x = d_x;
+    cb.y = d_dy;
+    cb.w = sc.put(w, nw);
+    cb.dx = sc.alloc<float>(nx);
+    cb.dw = sc.alloc<float>(nw);
+    cb.wprep = sc.alloc<float>(nw);
+    cb.wino_u = pd.path == DG_WINO ? sc.alloc<float>(conv_wino_floats(dg)) : nullptr;
+    cb.wg_part = sc.alloc<float>(conv_wgrad_scratch_floats(g));
     float* d_db = sc.alloc<float>((size_t)cout);
-    float* d_wf = sc.alloc<float>(nw);
-    float* d_part = sc.alloc<float>(conv_wgrad_scratch_floats(g));
     float* d_red = sc.alloc<float>(colreduce_scratch_floats((int64_t)n * g.Ho * g.Wo, cout));
+    uint16_t* xb = stored ? sc.alloc<uint16_t>(nx) : nullptr;
+    uint16_t* gb = stored ? sc.alloc<uint16_t>(ny) : nullptr;
     if (!sc.ok) return L3_ENOMEM;
-    const bool mp = dtype != L3_DTYPE_F32;
-    ConvGeom dg{n, g.Ho, g.Wo, cout, h, wd, cin, kh, kw, kh - 1 - g.padT, kw - 1 - g.padL};
-    dg.solo = 1;
-    dg.f2x2 = g.f2x2;
-    if ((dtype == L3_OP_BF16_STORED || dtype == L3_OP_BF16_STORED_OUT) && conv_wgrad_bf16_ok(g) && conv_bf16_ok(dg)) {
-        // bfloat16-stored operands, as the engine keeps them for its mixed-precision layers; the bias
-        // gradient stays a plain fp32 column sum of the unrounded dy
-        uint16_t* xb = sc.alloc<uint16_t>(nx);
-        uint16_t* gb = sc.alloc<uint16_t>(ny);
-        uint16_t* wb = sc.alloc<uint16_t>(2 * nw);      // both layouts of conv_weights_bf16
-        if (!sc.ok) return L3_ENOMEM;
+    if (stored) {
         cast_bf16(d_x, xb, (int64_t)nx, sc.s);
         cast_bf16(d_dy, gb, (int64_t)ny, sc.s);
-        conv_wgrad(reinterpret_cast<const float*>(xb), reinterpret_cast<const float*>(gb), d_dw, d_part, g, sc.s, true, true);
-        colsum(d_dy, d_db, d_red, (int64_t)n * g.Ho * g.Wo, cout, sc.s);
-        conv_weights_bf16(d_w, wb, kh, kw, cin, cout, false, sc.s);
-        if (dtype == L3_OP_BF16_STORED_OUT) {      // the data gradient is stored as bfloat16 too (returned widened)
-            uint16_t* dxb = sc.alloc<uint16_t>(nx);
-            if (!sc.ok) return L3_ENOMEM;
-            conv_bf16_fwd(reinterpret_cast<const float*>(gb), reinterpret_cast<const float*>(wb), nullptr,
-                          reinterpret_cast<float*>(dxb), dg, sc.s, true, nullptr, 0, true);
-            std::vector<uint16_t> hx(nx);
-            sc.get(hx.data(), dxb, nx);
-            widen_bf16(dx, hx.data(), nx);
-        } else {
-            conv_bf16_fwd(reinterpret_cast<const float*>(gb), reinterpret_cast<const float*>(wb), nullptr, d_dx, dg, sc.s, true);
-            sc.get(dx, d_dx, nx);
-        }
-        sc.get(dw, d_dw, nw);
-        sc.get(db, d_db, (size_t)cout);
-        return sc.status();
+        cb.x = reinterpret_cast<const float*>(xb);
+        cb.y = reinterpret_cast<float*>(gb);
     }
-    conv_wgrad(d_x, d_dy, d_dw, d_part, g, sc.s, mp && conv_wgrad_bf16_ok(g));
+    conv_run_wgrad(pw, g, cb, sc.s);
     colsum(d_dy, d_db, d_red, (int64_t)n * g.Ho * g.Wo, cout, sc.s);
-    if (!conv_dgrad_small(d_dy, d_w, d_dx, g, sc.s)) {
-        if (mp && conv_bf16_ok(dg)) {
-            conv_bf16_fwd(d_dy, d_w, nullptr, d_dx, dg, sc.s);      // the forward filter is the dgrad's [flip][n][k]
-        } else {
-            float* d_u = nullptr;
-            if (conv_wino_floats(dg)) {
-                d_u = sc.alloc<float>(conv_wino_floats(dg));
-                if (!sc.ok) return L3_ENOMEM;
-                conv_wino_transform_weights(d_w, d_u, dg, true, sc.s);
-            }
-            conv_flip_weights(d_w, d_wf, kh, kw, cin, cout, sc.s);
-            conv_fwd(d_dy, d_wf, nullptr, d_dx, dg, sc.s, d_u);
-        }
-    }
-    sc.get(dx, d_dx, nx);
-    sc.get(dw, d_dw, nw);
+    conv_run_dgrad(pd, g, dg, st, cb, sc.s);
+    sc.get_stored(dx, cb.dx, nx, st.dx_bf16);
+    sc.get(dw, cb.dw, nw);
     sc.get(db, d_db, (size_t)cout);
     return sc.status();
 }
@@ -1035,20 +986,19 @@ extern "C" int l3_op_vggish_conv(int device, int fp32_conv, const float* x, cons
     }
     Scope sc(device);
     if (int rc = vggish_op_device("l3_op_vggish_conv", sc, device)) return rc;
-    ConvGeom g{n, h, wd, cin, h, wd, cout, 3, 3, 1, 1};
+    ConvGeom g = conv_geom(n, h, wd, cin, cout, 3, 3, true, fp32_conv == L3_FP32_CONV_F2X2 ? 1 : 0);
     g.solo = 1;
-    g.f2x2 = fp32_conv == L3_FP32_CONV_F2X2 ? 1 : 0;
-    const bool wino = fp32_conv != L3_VGGISH_CONV_DIRECT && conv_wino_ok(g);
+    const ConvFwdPath p = conv_resolve_fwd(g, ConvStorage{}, fp32_conv != L3_VGGISH_CONV_DIRECT);
     const size_t nx = (size_t)n * h * wd * cin, nc = (size_t)n * h * wd * cout, ny = pool ? nc / 4 : nc;
-    const float* d_x = sc.put(x, nx);
-    const float* d_w = sc.put(w, (size_t)9 * cin * cout);
+    ConvBufs cb;
+    cb.x = sc.put(x, nx);
+    cb.w = sc.put(w, (size_t)9 * cin * cout);
     const float* d_b = sc.put(b, (size_t)cout);
-    float* d_u = wino ? sc.alloc<float>(conv_wino_floats(g)) : nullptr;
-    float* d_c = sc.alloc<float>(nc);
+    cb.wino_u = p.wino_filter ? sc.alloc<float>(conv_wino_floats(g)) : nullptr;
+    float* d_c = cb.y = sc.alloc<float>(nc);
     float* d_y = sc.alloc<float>(ny);
     if (!sc.ok) return L3_ENOMEM;
-    if (wino) conv_wino_transform_weights(d_w, d_u, g, false, sc.s);
-    conv_fwd(d_x, d_w, nullptr, d_c, g, sc.s, d_u);
+    conv_run_fwd(p, g, ConvStorage{}, cb, sc.s);
     vggish_bias_relu(d_c, d_b, d_y, n, h, wd, cout, pool ? 1 : 0, sc.s);
     sc.get(y, d_y, ny);
     return sc.status();

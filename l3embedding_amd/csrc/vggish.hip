@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/l3hip.h"
+#include "conv_path.h"
 #include "device_common.h"
 #include "kernels.h"
 #include "mlp.h"
@@ -297,9 +298,8 @@ struct l3_vggish {
 
 namespace {
 ConvGeom layer_geom(const l3_vggish* v, const VgLayer& L, int n) {
-    ConvGeom g{n, L.H, L.W, L.Cin, L.H, L.W, L.Cout, 3, 3, 1, 1};
+    ConvGeom g = conv_geom(n, L.H, L.W, L.Cin, L.Cout, 3, 3, true, v->conv == L3_FP32_CONV_F2X2 ? 1 : 0);
     g.solo = 1;
-    g.f2x2 = v->conv == L3_FP32_CONV_F2X2 ? 1 : 0;
     return g;
 }
 
@@ -309,12 +309,11 @@ int run_convs(l3_vggish* v, int n) {
     for (int l = 1; l <= 5; ++l) {
         const VgLayer& L = VG_LAYERS[l];
         const ConvGeom g = layer_geom(v, L, n);
-        const bool wino = v->conv != L3_VGGISH_CONV_DIRECT && conv_wino_ok(g);
-        if (wino && !v->u_fresh[l]) {
-            conv_wino_transform_weights(v->w[l], v->u[l], g, false, v->s);
-            v->u_fresh[l] = true;
-        }
-        conv_fwd(v->act[cur], v->w[l], nullptr, v->act[cur ^ 1], g, v->s, wino ? v->u[l] : nullptr);
+        const ConvFwdPath p = conv_resolve_fwd(g, ConvStorage{}, v->conv != L3_VGGISH_CONV_DIRECT);
+        ConvBufs b;          // no bias: it goes with the ReLU below.  The transformed filter is kept until the weights change
+        b.x = v->act[cur], b.w = v->w[l], b.y = v->act[cur ^ 1], b.wino_u = v->u[l], b.u_ready = v->u_fresh[l];
+        conv_run_fwd(p, g, ConvStorage{}, b, v->s);
+        if (p.wino_filter) v->u_fresh[l] = true;
         cur ^= 1;
         if (L.pool) {
             vggish_bias_relu(v->act[cur], v->b[l], v->act[cur ^ 1], n, L.H, L.W, L.Cout, 1, v->s);

@@ -116,3 +116,57 @@ def test_knob_changed_between_two_steps_of_one_engine(gpu_required, data, monkey
     _assert_same(got, want, 'L3_WINO4 unset -> 0 between steps, fresh engine')
     _assert_same(got, want_late, 'L3_WINO4 unset -> 0 between steps, engine created under 0')
     assert any(not np.array_equal(base[k], got[k]) for k in got), 'the knob changed nothing in step 2'
+
+
+def _first_convs(eng):
+    """Per tower: (tower, full name) of its first convolution (the first-layer kernel) and of its first wide one.  param_table()
+    lists a tower's parameters in the order of its ops, as in _first_bns."""
+    out = []
+    for tower in ('vision', 'audio'):
+        convs = [n[:-len('/kernel')] for n, _, _ in eng.param_table() if n.startswith(tower + '_model/') and n.endswith('/kernel')]
+        out += [(tower, c) for c in convs[:2]]
+    return out
+
+
+def _is_bf16(a):
+    """every value is a bfloat16: what Engine.activation() returns of a bfloat16-stored tensor"""
+    return not (a.view(np.uint32) & 0xffff).any()
+
+
+@pytest.mark.parametrize('dtype', ['f32', 'bf16'])
+def test_operator_is_the_engines_convolution(gpu_required, data, dtype):
+    """op_conv2d_fwd resolves and runs a convolution through the same code as the engine (csrc/conv_path.h), so on an engine's own
+    operands it returns the engine's own activation, bit for bit.  The first two convolutions of each tower -- the first-layer
+    kernel, the first wide layer -- in a solo training forward (l3_tower_step: ConvGeom::solo = 1, the operators' setting).
+
+    What a convolution reads is the output tensor of the BatchNorm in front of it: the input BatchNorm for the first one, and
+    for the second the BatchNorm behind the first, whose ReLU is folded into it (find_tower_tensor returns an op's output
+    tensor, and push_relu gives a ReLU fused into a BatchNorm no tensor of its own), so that name holds the post-ReLU tensor.
+    In the bf16 engine both convolutions store bfloat16 (alloc_everything): the first-layer kernel from fp32 input, the wide
+    layer from the bfloat16-stored BatchNorm output -- the operator's stored-out form of either."""
+    P, batches = data
+    eng = _engine(P, dtype)
+    eng.upload_batch(*batches[0])
+    bns, convs = _first_bns(eng), _first_convs(eng)
+    acts = {}
+    for tower in ('vision', 'audio'):
+        eng.tower_step(tower, backward=False)
+        eng.sync()
+        for n in bns + [c for _, c in convs]:
+            if n.startswith(tower):
+                acts[n] = eng.activation(n)
+    params = eng.get_params()
+    eng.close()
+    for i, (tower, name) in enumerate(convs):
+        k, b = params[name + '/kernel'], params[name + '/bias']
+        want = acts[name]
+        x = acts[bns[i]].reshape((B,) + {'vision': (224, 224), 'audio': (256, 199)}[tower] + (k.shape[2],))
+        first = i % 2 == 0
+        assert (k.shape[2] in (1, 3)) == first and k.shape[3] == 64, (name, k.shape)
+        if dtype == 'bf16':
+            assert _is_bf16(want) and _is_bf16(x) == (not first), name       # the storage the operator's dtype has to state
+        got = _lib.op_conv2d_fwd(x, k, b, True, dtype='f32' if dtype == 'f32' else 'bf16_stored_out')
+        same = np.array_equal(got.reshape(-1), want)
+        print('%s %s: %d values, max |.| %.3e, bit-identical %s' % (dtype, name, want.size, np.abs(want).max(), same))
+        assert np.isfinite(want).all() and np.abs(want).max() > 0
+        assert same, (dtype, name, float(np.abs(got.reshape(-1) - want).max()))
