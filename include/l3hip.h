@@ -716,6 +716,72 @@ int l3_mlp_set_data_dev(l3_mlp *m, const l3_feat *train, int64_t lo, int64_t hi,
 /* l3_mlp_predict of rows [lo, hi) of a device matrix, in l3_mlp_predict's row blocks without its staging copy: the same bits */
 int l3_mlp_predict_dev(l3_mlp *m, const l3_feat *x, int64_t lo, int64_t hi, float *probs_out);
 
+/* ---- Downstream random forest (classifier/train.py:169-227) ----------------------------------------------------------------------
+ * train_rf's sklearn.ensemble.RandomForestClassifier(n_estimators, random_state) with sklearn 0.19's defaults (Gini, bootstrap,
+ * max_features sqrt(D), trees grown out), as a level-wise histogram forest on the GPU (csrc/forest.hip): per feature at
+ * most 255 float32 cuts from a row sample, uint8 bin codes stored feature-major, every tree grown one level per launch group with
+ * integer class counts and one float64 formula for a split's worth, so the trees do not depend on the order of any sum and equal a
+ * NumPy restatement of the algorithm exactly (tests/forest_ref.py).  The caller draws the bootstrap multiplicities and the tree
+ * seeds (NumPy's RandomState); a node's features are drawn on the device by a counter-based mixer of (tree seed, node, draw).
+ * One handle owns one resident float32 matrix, one stream and at most one fitted or uploaded forest; calls on one handle are not
+ * re-entrant and have finished when they return.  NaN inputs are out of contract.  Errors: l3_last_error(NULL). */
+#define L3_FOREST_MAX_CLASSES 60       /* the (bin x class) histogram of a node and feature, 256 (C + 1) words, stays within 64 KiB of LDS */
+#define L3_FOREST_MAX_CUTS 255         /* cuts per feature: a bin code is a uint8 */
+#define L3_FOREST_MAX_DRAWS 256        /* max_features: the features drawn per node */
+#define L3_FOREST_MAX_BIN_SAMPLE 8192  /* rows of the cut sample: one column of it is sorted in LDS */
+#define L3_FOREST_NARROW_ROWS 64       /* a node of at most this many distinct rows can be searched by one wave, a lane per row */
+typedef struct l3_forest_config {
+    int32_t n_classes;          /* 1 .. L3_FOREST_MAX_CLASSES; labels are indices below it */
+    int32_t max_features;       /* K distinct features per node, 1 .. min(D, L3_FOREST_MAX_DRAWS) */
+    int32_t max_depth;          /* <= 0: unbounded (the level loop is bounded by n) */
+    int32_t min_samples_split;  /* >= 2, counted in distinct rows as sklearn counts them under bootstrap weights */
+    int32_t min_samples_leaf;   /* >= 1, distinct rows on each side of a split */
+    int32_t wide_min_rows;      /* a node of at least this many distinct rows, or of more than L3_FOREST_NARROW_ROWS, is searched by a
+                                   workgroup per (node, drawn feature) with the histogram in LDS; smaller ones by a wave per node.
+                                   0: L3_FOREST_NARROW_ROWS + 1.  Both searches give the same trees. */
+    int64_t n_bin_rows;         /* rows of the cut sample (<= L3_FOREST_MAX_BIN_SAMPLE); 0: every row (then n <= the same bound) */
+    const int32_t *bin_rows;    /* the sample's rows, ascending and distinct; NULL with n_bin_rows 0 */
+} l3_forest_config;
+typedef struct l3_forest l3_forest;
+int l3_forest_create(int device, l3_forest **m);
+void l3_forest_destroy(l3_forest *m);
+/* classifier/train.py:169-227 (clf.fit's X): X (n, D) float32 row major, copied once.  1 <= n < 2^31, 1 <= D <= 2^21 */
+int l3_forest_set_data(l3_forest *m, const float *X, int64_t n, int D);
+/* classifier/train.py:169-227 (clf.fit's X when preprocess_split_data left it on the device): l3_forest_set_data from rows [lo, hi)
+ * of a device matrix, copied device to device; the l3_feat may be destroyed afterwards */
+int l3_forest_set_data_dev(l3_forest *m, const struct l3_feat *f, int64_t lo, int64_t hi);
+/* classifier/train.py:169-227 (clf.fit): n_trees trees on the resident matrix.  labels (n) class indices; boot (n_trees, n) the
+ * bootstrap multiplicities of each tree's rows (a tree needs one non-zero row at least); seeds (n_trees) in [0, 2^31).  Every label,
+ * sample row and config field is checked here, on the host, before anything is launched: L3_EINVAL names the first one out of
+ * range.  The fitted forest replaces the handle's forest and is resident for l3_forest_predict_proba. */
+int l3_forest_fit(l3_forest *m, const l3_forest_config *cfg, const int32_t *labels, int n_trees, const uint16_t *boot,
+                  const int64_t *seeds);
+/* the handle's forest: trees, nodes over all trees, classes, features (L3_ESTATE without one) */
+int l3_forest_sizes(const l3_forest *m, int *n_trees, int64_t *n_nodes, int *n_classes, int *D);
+/* classifier/train.py:169-227 (what joblib.dump keeps of clf.estimators_): the trees as flat arrays.  Tree t owns the nodes
+ * [tree_off[t], tree_off[t + 1]) (tree_off has n_trees + 1 entries), numbered level by level in parent order, left before right,
+ * the root first; left / right are node numbers inside the tree (-1 at a leaf); feature and bin are -1 and threshold 0 at a leaf;
+ * a row goes left iff x[feature] <= threshold (threshold = the feature's cut number bin); counts (n_nodes, n_classes) are the
+ * bootstrap-weighted class counts of the node's rows and n_distinct the number of distinct rows. */
+int l3_forest_get_trees(l3_forest *m, int64_t *tree_off, int32_t *left, int32_t *right, int32_t *feature, float *threshold,
+                        int32_t *bin, int32_t *counts, int32_t *n_distinct);
+/* classifier/train.py:169-227 (joblib.load's side): a forest in l3_forest_get_trees' arrays becomes the handle's forest.  Checked on
+ * the host: each child number lies above its parent's and inside the tree, both children or neither, features in [0, D), counts
+ * non-negative with a positive sum at every leaf; L3_EINVAL otherwise. */
+int l3_forest_set_trees(l3_forest *m, int n_trees, int n_classes, int D, const int64_t *tree_off, const int32_t *left,
+                        const int32_t *right, const int32_t *feature, const float *threshold, const int32_t *counts);
+/* classifier/train.py:169-227 (clf.predict_proba): out (n, n_classes) float64.  One thread per row walks the trees in order on the
+ * raw features, adds each leaf's counts / their sum in float64 and divides by n_trees at the end: deterministic. */
+int l3_forest_predict_proba(l3_forest *m, const float *X, int64_t n, int D, double *out);
+/* classifier/train.py:169-227 (clf.predict_proba of a split on the device): l3_forest_predict_proba of rows [lo, hi) of a device
+ * matrix: the same bits */
+int l3_forest_predict_proba_dev(l3_forest *m, const struct l3_feat *f, int64_t lo, int64_t hi, double *out);
+/* classifier/train.py:169-227 (the fit's binning, for tests): cuts (D, L3_FOREST_MAX_CUTS) and ncuts (D) of the last fit */
+int l3_forest_get_cuts(l3_forest *m, float *cuts, int32_t *ncuts);
+/* classifier/train.py:169-227 (the fit's course, for profiles): the last fit's levels -> their number; up to max_levels entries each of
+ * the nodes searched at the level over all trees, those of them searched by the wide kernel, and the level's wall time in ms */
+int l3_forest_level_stats(const l3_forest *m, int max_levels, int64_t *nodes, int64_t *wide, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

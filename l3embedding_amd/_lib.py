@@ -220,6 +220,19 @@ SIGNATURES = {
     'l3_mlp_set_data_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                       C.c_void_p]),
     'l3_mlp_predict_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    # downstream random forest (csrc/forest.hip): classifier/train.py:169-227
+    'l3_forest_create': (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    'l3_forest_destroy': (None, [C.c_void_p]),
+    'l3_forest_set_data': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
+    'l3_forest_set_data_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    'l3_forest_fit': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'l3_forest_sizes': (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'l3_forest_get_trees': (C.c_int, [C.c_void_p] * 9),
+    'l3_forest_set_trees': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    'l3_forest_predict_proba': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    'l3_forest_predict_proba_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'l3_forest_get_cuts': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_forest_level_stats': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -1570,3 +1583,119 @@ def op_vggish_postprocess(emb, pca_matrix, pca_means, quantize=True, device=0):
     out = np.empty_like(e)
     check(load().l3_op_vggish_postprocess(device, _ptr(e), e.shape[0], _ptr(m), _ptr(mu), 1 if quantize else 0, _ptr(out)))
     return out
+
+
+# ---- downstream random forest (csrc/forest.hip) ------------------------------------------------------------------------------------
+FOREST_MAX_CLASSES = 60          # L3_FOREST_MAX_CLASSES
+FOREST_MAX_CUTS = 255            # L3_FOREST_MAX_CUTS
+FOREST_MAX_DRAWS = 256           # L3_FOREST_MAX_DRAWS
+FOREST_MAX_BIN_SAMPLE = 8192     # L3_FOREST_MAX_BIN_SAMPLE
+FOREST_NARROW_ROWS = 64          # L3_FOREST_NARROW_ROWS
+FOREST_TREE_ARRAYS = ('tree_off', 'left', 'right', 'feature', 'threshold', 'bin', 'counts', 'n_distinct')
+
+
+class ForestConfig(C.Structure):
+    """struct l3_forest_config (include/l3hip.h)"""
+    _fields_ = [('n_classes', C.c_int32), ('max_features', C.c_int32), ('max_depth', C.c_int32), ('min_samples_split', C.c_int32),
+                ('min_samples_leaf', C.c_int32), ('wide_min_rows', C.c_int32), ('n_bin_rows', C.c_int64), ('bin_rows', C.c_void_p)]
+
+
+class Forest(object):
+    """RAII wrapper over an l3_forest handle: the resident training matrix, the level-wise fit and the resident forest of
+    classifier/train.py:169-227's random forest on one device."""
+
+    def __init__(self, device=0):
+        self.lib = load()
+        h = C.c_void_p()
+        check(self.lib.l3_forest_create(int(device), C.byref(h)), None)
+        self.h = h
+        self.n = self.D = 0
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_forest_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_data(self, X):
+        x = _f32(X)
+        check(self.lib.l3_forest_set_data(self.h, _ptr(x), x.shape[0], x.shape[1]))
+        self.n, self.D = x.shape
+
+    def set_data_dev(self, feat, lo=0, hi=None):
+        """set_data from rows [lo, hi) of the Features `feat`, copied device to device; it may be closed afterwards"""
+        n, d = feat.shape
+        hi = n if hi is None else hi
+        check(self.lib.l3_forest_set_data_dev(self.h, feat.h, int(lo), int(hi)))
+        self.n, self.D = int(hi - lo), int(d)
+
+    def fit(self, labels, boot, seeds, n_classes, max_features, max_depth=0, min_samples_split=2, min_samples_leaf=1,
+            bin_rows=None, wide_min_rows=0):
+        """labels (n) class indices; boot (n_trees, n) bootstrap multiplicities (uint16); seeds (n_trees); bin_rows: the ascending
+        rows of the cut sample, None for all rows.  The forest stays resident; trees() downloads it."""
+        y = _i32(labels).reshape(-1)
+        b = np.ascontiguousarray(boot, np.uint16)
+        sd = _i64(seeds).reshape(-1)
+        if y.size != self.n or b.ndim != 2 or b.shape[1] != self.n or b.shape[0] != sd.size:
+            raise ValueError('labels (n), boot (n_trees, n) and seeds (n_trees) must match the resident matrix of %d rows' % self.n)
+        rows = None if bin_rows is None else _i32(bin_rows).reshape(-1)
+        cfg = ForestConfig(int(n_classes), int(max_features), int(max_depth or 0), int(min_samples_split), int(min_samples_leaf),
+                           int(wide_min_rows), 0 if rows is None else rows.size, None if rows is None else rows.ctypes.data)
+        check(self.lib.l3_forest_fit(self.h, C.byref(cfg), _ptr(y), sd.size, _ptr(b), _ptr(sd)))
+
+    def sizes(self):
+        """-> (n_trees, n_nodes, n_classes, D) of the resident forest"""
+        t, nn, c, d = C.c_int(), C.c_int64(), C.c_int(), C.c_int()
+        check(self.lib.l3_forest_sizes(self.h, C.byref(t), C.byref(nn), C.byref(c), C.byref(d)))
+        return t.value, nn.value, c.value, d.value
+
+    def trees(self):
+        """the resident forest as l3_forest_get_trees' flat arrays -> dict of FOREST_TREE_ARRAYS"""
+        t, nn, c, _ = self.sizes()
+        out = dict(tree_off=np.empty(t + 1, np.int64), left=np.empty(nn, np.int32), right=np.empty(nn, np.int32),
+                   feature=np.empty(nn, np.int32), threshold=np.empty(nn, np.float32), bin=np.empty(nn, np.int32),
+                   counts=np.empty((nn, c), np.int32), n_distinct=np.empty(nn, np.int32))
+        check(self.lib.l3_forest_get_trees(self.h, *(_ptr(out[k]) for k in FOREST_TREE_ARRAYS)))
+        return out
+
+    def set_trees(self, trees, D):
+        """a forest in trees()' arrays becomes the resident one"""
+        off = _i64(trees['tree_off']).reshape(-1)
+        counts = np.ascontiguousarray(trees['counts'], np.int32)
+        nn = counts.shape[0]
+        arrays = [_i32(trees[k]).reshape(-1) for k in ('left', 'right', 'feature')] + [_f32(trees['threshold']).reshape(-1)]
+        if counts.ndim != 2 or off.size < 2 or off[-1] != nn or any(a.size != nn for a in arrays):
+            raise ValueError('the tree arrays do not hold one entry per node')
+        check(self.lib.l3_forest_set_trees(self.h, off.size - 1, counts.shape[1], int(D), _ptr(off), *(_ptr(a) for a in arrays),
+                                           _ptr(counts)))
+
+    def predict_proba(self, X):
+        x = _f32(X)
+        out = np.empty((x.shape[0], self.sizes()[2]), np.float64)
+        check(self.lib.l3_forest_predict_proba(self.h, _ptr(x), x.shape[0], x.shape[1], _ptr(out)))
+        return out
+
+    def predict_proba_dev(self, feat, lo=0, hi=None):
+        n, _ = feat.shape
+        hi = n if hi is None else hi
+        out = np.empty((max(int(hi - lo), 0), self.sizes()[2]), np.float64)
+        check(self.lib.l3_forest_predict_proba_dev(self.h, feat.h, int(lo), int(hi), _ptr(out)))
+        return out
+
+    def cuts(self):
+        """the last fit's (cuts (D, 255) float32, ncuts (D))"""
+        cuts, ncuts = np.empty((self.D, FOREST_MAX_CUTS), np.float32), np.empty(self.D, np.int32)
+        check(self.lib.l3_forest_get_cuts(self.h, _ptr(cuts), _ptr(ncuts)))
+        return cuts, ncuts
+
+    def level_stats(self):
+        """the last fit's levels -> (nodes searched, of them by the wide kernel, wall ms), one entry per level"""
+        L = self.lib.l3_forest_level_stats(self.h, 0, None, None, None)
+        nodes, wide, ms = np.empty(L, np.int64), np.empty(L, np.int64), np.empty(L, np.float64)
+        self.lib.l3_forest_level_stats(self.h, L, _ptr(nodes), _ptr(wide), _ptr(ms))
+        return nodes, wide, ms

@@ -7,7 +7,11 @@ it.  Deviations from the reference, all deliberate:
     are not reproducible); the Glorot initialisation is seeded with random_state too;
   * the random start delay and the Google Sheets logging of train() are skipped; config.json has git_commit None;
   * the scalers are pickled with `pickle` (the reference uses sklearn's joblib; these are NumPy restatements, usc.py);
-  * the random forest (sklearn on the host) is not built: it raises;
+  * the random forest (train_rf, classifier/train.py:169-227) trains and predicts on the GPU as a level-wise histogram forest
+    (forest.py, csrc/forest.hip), not as sklearn's exact-split trees: forest.py's header lists how it differs.  train_rf does not
+    seed NumPy's and Python's global generators (the reference does; every draw here has its own RandomState), pickles the model
+    with `pickle`, and takes usc.DeviceFeatures as they are.  train() and cross_validate still refuse 'rf'; train_rf_fold is the
+    reference's train(model_type='rf'), and its parameter search (over n_estimators, :623-630) is not built: it raises;
   * the parameter search without a validation fold (train_param_search :408-423, :470-479) cuts the training rows with
     usc.stratified_shuffle_split, a NumPy restatement of sklearn's StratifiedShuffleSplit, and only when the caller gives the
     split's seed (split_random_state / parameter_search_split_seed; the reference passes none, so its split differs from run to
@@ -20,8 +24,9 @@ it.  Deviations from the reference, all deliberate:
     the reference's train(model_type='svm'), and train_svm_search its parameter search over C with the whole grid fitted in
     one pass on the GPU (svm.fit_grid).
 
-How the file is put together: train, train_svm_fold and cross_validate pass their arguments, by name in one dict, to one fold driver
-(_run_fold), and the model types differ in one function each (_mlp_part, _svm_part).  train_param_search and train_svm_search are
+How the file is put together: train, train_svm_fold, train_rf_fold and cross_validate pass their arguments, by name in one dict, to
+one fold driver (_run_fold), and the model types differ in one function each (_mlp_part, _svm_part, _rf_part).  train_param_search and
+train_svm_search are
 one search body (_search) with two ways to fit the grid.  A usc.DeviceFeatures is closed by whoever made it, through _closing: the
 driver closes the fold's splits, a search the parts of its cut and its merged matrix, and nobody what a caller passed in.
 """
@@ -39,6 +44,7 @@ import numpy as np
 
 from . import _lib, callbacks, kerasfile
 from . import svm as _svm
+from .forest import RandomForestClassifier
 from .svm import SVC, hinge_loss  # noqa: F401  (re-exported: the reference imports them into classifier/train.py)
 from .usc import DeviceFeatures, FoldBank, get_split, preprocess_split_data, stratified_shuffle_split
 
@@ -54,6 +60,8 @@ ONLY_MLP = ('only the mlp classifier is built (model_type {!r}: the fold driver 
             'the SVM on the GPU, and the random forest is not built)')
 NO_SSS = ('the parameter search without a validation fold needs sklearn\'s StratifiedShuffleSplit, which is not built: '
           'search on the validation fold instead')
+NO_RF_SEARCH = ('the parameter search of the random forest (over n_estimators, classifier/train.py:623-630) is not built: run '
+                'train_rf_fold once per n_estimators instead')
 
 
 class EarlyStopping(callbacks.Callback):
@@ -362,6 +370,41 @@ def train_svm(train_data, valid_data, test_data, model_dir, C=1.0, kernel='rbf',
     return clf, train_metrics, valid_metrics, test_metrics
 
 
+def train_rf(train_data, valid_data, test_data, model_dir, n_estimators=100, num_classes=10, random_state=12345678, **kwargs):
+    """classifier/train.py:169-227 -> (model, train_metrics, valid_metrics, test_metrics): forest.RandomForestClassifier(
+    n_estimators, random_state) fitted on the GPU and pickled to model_dir/model.pkl; 'loss' is 0 as in the reference; the test set
+    is classified per file as the argmax of the mean of its frames' predict_proba, taken on the host over the downloaded (n, C)
+    matrix.  The splits' features may be NumPy rows or usc.DeviceFeatures (fitted and scored where they are).  Of kwargs the
+    forest's own arguments are passed on (RF_ARGS); the rest is ignored, as the reference ignores it."""
+    features, labels = train_data['features'], train_data['labels']
+    forest_args = {k: kwargs[k] for k in RF_ARGS if k in kwargs}
+    if isinstance(features, DeviceFeatures):
+        forest_args.setdefault('device', features.device)
+    clf = RandomForestClassifier(n_estimators=n_estimators, random_state=random_state, **forest_args)
+    LOGGER.debug('Fitting model to data...')
+    clf.fit(features, labels)
+    LOGGER.info('Saving model...')
+    _dump(os.path.join(model_dir, 'model.pkl'), clf)
+
+    train_metrics = compute_metrics(labels, clf.predict(features), num_classes=num_classes)
+    train_metrics['loss'] = 0
+    LOGGER.info('Train - acc: %s', train_metrics['accuracy'])
+    valid_metrics = {}
+    if valid_data:
+        valid_metrics = compute_metrics(valid_data['labels'], clf.predict(valid_data['features']), num_classes=num_classes)
+        valid_metrics['loss'] = 0
+        LOGGER.info('Valid - acc: %s', valid_metrics['accuracy'])
+    test_metrics = {}
+    if test_data:
+        per_file = _file_predictions(clf.predict_proba(test_data['features']), test_data['file_idxs'])
+        test_metrics = compute_metrics(test_data['labels'], per_file, num_classes=num_classes)
+    return clf, train_metrics, valid_metrics, test_metrics
+
+
+# the arguments of forest.RandomForestClassifier that train_rf passes on from its keyword arguments
+RF_ARGS = ('max_depth', 'min_samples_split', 'min_samples_leaf', 'max_features', 'bin_sample', 'device', 'wide_min_rows')
+
+
 def _svm_metrics_on_device(clf, train_data, valid_data, test_data, num_classes):
     """-> (train_metrics, valid_metrics, test_metrics) of a fitted SVC, one SVC.evaluate per split: predictions and the hinge loss
     of the train and validation rows (no (n, C) array returns), the per-file classes of the test set"""
@@ -613,7 +656,7 @@ def _run_fold(fold, get_splits=None):
                                         device=fold['preprocess_device'])
         for name, scaler in zip(('min_max_scaler.pkl', 'stdizer.pkl'), scalers):
             _dump(os.path.join(model_dir, name), scaler)
-        model_part = {'mlp': _mlp_part, 'svm': _svm_part}[fold['model_type']]
+        model_part = {'mlp': _mlp_part, 'svm': _svm_part, 'rf': _rf_part}[fold['model_type']]
         _, train_metrics, valid_metrics, test_metrics = model_part(
             splits, model_dir, dict(fold, num_classes=DATASET_NUM_CLASSES[dataset], search_on_cut=on_cut))
     _dump(os.path.join(model_dir, 'results.pkl'), {'train': train_metrics, 'valid': valid_metrics, 'test': test_metrics})
@@ -646,6 +689,14 @@ def _svm_part(splits, model_dir, fold):
     if fold['search_on_cut']:
         args.update(valid_ratio=fold['parameter_search_valid_ratio'], split_random_state=fold['parameter_search_split_seed'])
     return train_svm_search(*splits, model_dir, train_with_valid=fold['parameter_search_train_with_valid'], platt=fold['platt'], **args)
+
+
+def _rf_part(splits, model_dir, fold):
+    """the random forest's part of a fold -> (model, train_metrics, valid_metrics, test_metrics): one train_rf; no search"""
+    if fold['parameter_search']:
+        raise ValueError(NO_RF_SEARCH)
+    args = dict(dict(random_state=fold['random_state'], num_classes=fold['num_classes'], verbose=fold['verbose']), **fold['model_args'])
+    return train_rf(*splits, model_dir, **args)
 
 
 def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='framewise', train_batch_size=64, patience=20,
@@ -683,6 +734,22 @@ def train_svm_fold(features_dir, output_dir, fold_num, feature_mode='framewise',
     SVM does not use them.  parameter_search_split_seed: as in train(); the cut and the search on it are train_svm_search's.
     -> that directory."""
     return _run_fold(dict(locals(), model_type='svm'))          # the fold's settings by name
+
+
+def train_rf_fold(features_dir, output_dir, fold_num, feature_mode='framewise', train_batch_size=64, patience=20,
+                  random_state=20171021, parameter_search=False, parameter_search_valid_fold=True,
+                  parameter_search_valid_ratio=0.15, parameter_search_train_with_valid=False, gsheet_id=None,
+                  google_dev_app_name=None, verbose=False, non_overlap=False, non_overlap_chunk_size=10, use_min_max=False,
+                  preprocess_device=None, parameter_search_split_seed=None, **model_args):
+    """classifier/train.py:495-709 for model_type='rf': one cross-validation fold as train() runs it for the MLP, written to
+    <output_dir>/classifier/<features desc>/<mode>/<overlap>/<min-max>/rf/fold<N>/<timestamp>/: config.json, min_max_scaler.pkl,
+    stdizer.pkl, model.pkl, results.pkl.  preprocess_device: a GPU index preprocesses the folds on that GPU and the forest is fitted
+    and scored from the splits there; config.json names it only when it is set.  One train_rf with model_args (n_estimators and
+    RF_ARGS); parameter_search=True raises (NO_RF_SEARCH) before anything is read.  train_batch_size and patience are recorded as
+    the reference records them; the forest does not use them.  -> that directory."""
+    if parameter_search:
+        raise ValueError(NO_RF_SEARCH)
+    return _run_fold(dict(locals(), model_type='rf'))          # the fold's settings by name
 
 
 # what a fold's metrics hold besides numbers and lists of numbers with one entry per class: the per-epoch histories (their length

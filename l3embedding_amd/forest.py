@@ -1,0 +1,170 @@
+"""The reference's random-forest sound classifier (classifier/train.py:169-227): sklearn.ensemble.RandomForestClassifier of
+scikit-learn 0.19 with the arguments train_rf gives it (n_estimators, random_state; everything else at its default: Gini, bootstrap,
+max_features sqrt(D), trees grown until the leaves are pure), trained and evaluated on the GPU through the l3_forest handle of
+libl3hip (csrc/forest.hip).
+
+The forest is grown level by level from histograms: per feature at most 255 float32 cuts from a sample of
+bin_sample rows, a uint8 bin code per value, all trees advancing one level per group of launches, integer class counts and one float64
+formula for a split's worth.  Here are the draws a fit needs from NumPy (the tree seeds, each tree's bootstrap multiplicities, the
+rows of the cut sample) and sklearn's shell: fit / predict / predict_proba, classes_, estimators_ and pickling.
+
+Deviations from sklearn 0.19, all deliberate:
+  * a split is searched among at most 255 cuts per feature (sklearn tries every midpoint of the node's own values), so the trees are
+    not sklearn's; they are judged against sklearn's seed-to-seed spread (tests/golden/make_forest_golden.py) and are equal, node for
+    node, to the NumPy restatement of this algorithm in tests/forest_ref.py;
+  * the bootstrap of tree t is np.bincount(RandomState(seed_t).randint(0, n, n)) with seed_t from RandomState(random_state) as
+    sklearn draws them, but a node's max_features features come from Floyd's subset sampling driven by a counter-based mixer of
+    (seed_t, node, draw) on the device (sklearn walks its private rand_r stream through a Fisher-Yates shuffle);
+  * sklearn keeps drawing past max_features until it has found one feature that is not constant in the node; here a node draws exactly
+    max_features features, and one that finds no valid split among them becomes a leaf;
+  * among equally good splits the earlier draw wins, then the lower cut (sklearn: the first it meets in its own order);
+  * estimators_ holds the trees as flat arrays (_lib.FOREST_TREE_ARRAYS), not DecisionTreeClassifier objects;
+  * class_weight, sample weights, oob_score, min_weight_fraction_leaf, max_leaf_nodes, min_impurity_decrease, warm_start and criteria
+    other than Gini are not built; at most _lib.FOREST_MAX_CLASSES classes.
+"""
+import numpy as np
+
+from . import _lib
+from .usc import DeviceFeatures
+
+
+def tree_seeds(random_state, n_estimators):
+    """sklearn's per-tree seeds (ensemble/base.py _set_random_states: randint(MAX_INT) per estimator)"""
+    return np.random.RandomState(random_state).randint(np.iinfo(np.int32).max, size=n_estimators).astype(np.int64)
+
+
+def bootstrap_counts(seeds, n):
+    """(n_trees, n) uint16: how often each row occurs in each tree's bootstrap sample (sklearn's _generate_sample_indices)"""
+    boot = np.empty((len(seeds), n), np.uint16)
+    for t, seed in enumerate(seeds):
+        counts = np.bincount(np.random.RandomState(int(seed)).randint(0, n, n), minlength=n)
+        if counts.max() > np.iinfo(np.uint16).max:
+            raise ValueError('a row occurs %d times in a bootstrap sample; at most 65535 are built' % counts.max())
+        boot[t] = counts
+    return boot
+
+
+def bin_sample_rows(random_state, n, bin_sample):
+    """the rows the cuts are taken from: None for all of them, else bin_sample of them drawn without replacement, ascending"""
+    if n <= bin_sample:
+        return None
+    return np.sort(np.random.RandomState(random_state).choice(n, bin_sample, replace=False)).astype(np.int32)
+
+
+def resolve_max_features(max_features, D):
+    """sklearn 0.19's reading of max_features for a classifier -> the number of features drawn per node"""
+    if max_features is None:
+        return D
+    if isinstance(max_features, str):
+        if max_features in ('sqrt', 'auto'):
+            return max(1, int(np.sqrt(D)))
+        if max_features == 'log2':
+            return max(1, int(np.log2(D)))
+        raise ValueError("max_features must be 'sqrt', 'auto', 'log2', None, an int or a float, not %r" % (max_features,))
+    if isinstance(max_features, (int, np.integer)):
+        k = int(max_features)
+    else:
+        k = max(1, int(float(max_features) * D)) if max_features > 0 else 0
+    if not 1 <= k <= D:
+        raise ValueError('max_features must be in (0, n_features]')
+    return k
+
+
+class RandomForestClassifier(object):
+    """sklearn 0.19's RandomForestClassifier(n_estimators, random_state) on the GPU: fit / predict / predict_proba, classes_,
+    estimators_ (the trees as the flat arrays of _lib.FOREST_TREE_ARRAYS).  The fitted model pickles without its device handle and
+    uploads its trees again on first use.  wide_min_rows: the node size from which the search takes a workgroup per (node, feature)
+    instead of a wave per node (0: the library's default); the trees do not depend on it."""
+
+    def __init__(self, n_estimators=100, random_state=None, max_depth=None, min_samples_split=2, min_samples_leaf=1,
+                 max_features='sqrt', bin_sample=4096, device=0, wide_min_rows=0):
+        self.n_estimators, self.random_state, self.max_depth = n_estimators, random_state, max_depth
+        self.min_samples_split, self.min_samples_leaf, self.max_features = min_samples_split, min_samples_leaf, max_features
+        self.bin_sample, self.device, self.wide_min_rows = bin_sample, device, wide_min_rows
+        self._h = None
+        self._resident = False
+
+    # pickling: everything but the device handle
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state['_h'] = None
+        state['_resident'] = False
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+
+    def _handle(self):
+        if self._h is None:
+            self._h = _lib.Forest(self.device)
+            self._resident = False
+        return self._h
+
+    def fit(self, X, y):
+        """X: NumPy rows, or a usc.DeviceFeatures, which is copied on the device (no download; the fit sees the same bits)"""
+        on_device = isinstance(X, DeviceFeatures)
+        if not on_device:
+            X = np.ascontiguousarray(X, np.float32)
+        y = np.asarray(y).reshape(-1)
+        if len(X.shape) != 2 or X.shape[0] != y.size or y.size == 0:
+            raise ValueError('X must be (n_samples, n_features) with one label per row')
+        n, D = int(X.shape[0]), int(X.shape[1])
+        if int(self.n_estimators) < 1:
+            raise ValueError('n_estimators must be at least 1')
+        if self.max_depth is not None and int(self.max_depth) < 1:
+            raise ValueError('max_depth must be at least 1, or None')
+        if int(self.min_samples_split) < 2 or int(self.min_samples_leaf) < 1:
+            raise ValueError('min_samples_split must be at least 2 and min_samples_leaf at least 1 (row counts)')
+        if not 1 <= int(self.bin_sample) <= _lib.FOREST_MAX_BIN_SAMPLE:
+            raise ValueError('bin_sample must be in [1, %d]' % _lib.FOREST_MAX_BIN_SAMPLE)
+        classes, yenc = np.unique(y, return_inverse=True)
+        if classes.size > _lib.FOREST_MAX_CLASSES:
+            raise ValueError('at most %d classes are built' % _lib.FOREST_MAX_CLASSES)
+        k = resolve_max_features(self.max_features, D)
+        if k > _lib.FOREST_MAX_DRAWS:
+            raise ValueError('max_features gives %d features per node; at most %d are built' % (k, _lib.FOREST_MAX_DRAWS))
+        seeds = tree_seeds(self.random_state, int(self.n_estimators))
+        boot = bootstrap_counts(seeds, n)
+        rows = bin_sample_rows(self.random_state, n, int(self.bin_sample))
+        h = self._handle()
+        self._resident = False
+        if on_device:
+            h.set_data_dev(X.handle)
+        else:
+            h.set_data(X)
+        h.fit(yenc, boot, seeds, classes.size, k, max_depth=self.max_depth or 0, min_samples_split=self.min_samples_split,
+              min_samples_leaf=self.min_samples_leaf, bin_rows=rows, wide_min_rows=self.wide_min_rows)
+        self.classes_, self.n_classes_, self.n_features_, self.max_features_ = classes, classes.size, D, k
+        self.estimators_ = h.trees()
+        self.level_stats_ = h.level_stats()
+        self._resident = True
+        return self
+
+    def _check_fitted(self):
+        if not hasattr(self, 'estimators_'):
+            raise ValueError('This RandomForestClassifier instance is not fitted yet')
+
+    def _ensure_model(self):
+        """the handle with this model's trees resident: as the fit left them, or uploaded again after unpickling"""
+        h = self._handle()
+        if not self._resident:
+            h.set_trees(self.estimators_, self.n_features_)
+            self._resident = True
+        return h
+
+    def predict_proba(self, X):
+        """(n, n_classes) float64: the mean over the trees of the class fractions of the leaf each row falls into"""
+        self._check_fitted()
+        on_device = isinstance(X, DeviceFeatures)
+        if not on_device:
+            X = np.ascontiguousarray(X, np.float32)
+        if len(X.shape) != 2 or X.shape[1] != self.n_features_:
+            raise ValueError('X has %s features per sample; expecting %d' % (tuple(X.shape[1:]), self.n_features_))
+        if X.shape[0] == 0:
+            raise ValueError('no rows to predict')
+        h = self._ensure_model()
+        return h.predict_proba_dev(X.handle) if on_device else h.predict_proba(X)
+
+    def predict(self, X):
+        proba = self.predict_proba(X)
+        return self.classes_[np.argmax(proba, axis=1)]
