@@ -776,6 +776,25 @@ int l3_forest_predict_proba(l3_forest *m, const float *X, int64_t n, int D, doub
 /* classifier/train.py:169-227 (clf.predict_proba of a split on the device): l3_forest_predict_proba of rows [lo, hi) of a device
  * matrix: the same bits */
 int l3_forest_predict_proba_dev(l3_forest *m, const struct l3_feat *f, int64_t lo, int64_t hi, double *out);
+/* classifier/train.py:193-227, 623-630 (clf.predict / predict_proba of every forest of the n_estimators grid, and the per-file means
+ * of :211-222; the entries around it cite classifier/train.py:169-227 for the forest as a whole): the rows scored by the first
+ * prefix[g] trees of the resident forest for every g at once, each tree walked once per row.  Rows: exactly one of
+ * host rows X (hi of them, lo 0, D features), rows [lo, hi) of the device matrix f, and rows [lo, hi) of the handle's resident matrix
+ * (resident != 0).  prefix: n_prefix forest sizes, strictly increasing, in [1, n_trees].  labels: int32 class indices of the rows,
+ * or NULL.  files: n_files pairs [start, end) over the rows, or NULL.  Outputs, each NULL when not wanted (a NULL proba is never
+ * allocated or copied): pred (n_prefix, n) int32, the first of the largest probabilities; correct (n_prefix) int64, the rows whose
+ * pred is their label (needs labels); file_mean (n_prefix, n_files, n_classes) float64 and file_pred (n_prefix, n_files) int32, a
+ * file's rows added in row order, / their number, and the first of the largest (files and a file output come together); proba
+ * (n_prefix, n, n_classes) float64.  For every row and class count / total of the leaf is added in float64 strictly in tree order
+ * and divided by prefix[g] after tree prefix[g] - 1: the bits of l3_forest_predict_proba on the forest of the first prefix[g]
+ * trees.  chunk_rows: the rows per launch, which bounds every scratch buffer (0: 2^28 bytes of float32 rows); stage_bytes: the LDS
+ * budget of a workgroup's 4 rows, above which the walk reads them from global memory (0: 96 KiB, so D <= 6144); neither changes a
+ * bit of the result.  Everything is checked on the host before anything is launched: L3_ESTATE without a forest or without the
+ * resident matrix asked for, L3_EINVAL otherwise. */
+int l3_forest_score(l3_forest *m, const float *X, const struct l3_feat *f, int64_t lo, int64_t hi, int D, int resident,
+                    const int32_t *prefix, int n_prefix, const int32_t *labels, const int64_t *files, int64_t n_files,
+                    int64_t chunk_rows, int64_t stage_bytes, int32_t *pred, int64_t *correct, double *file_mean, int32_t *file_pred,
+                    double *proba);
 /* classifier/train.py:169-227 (the fit's binning, for tests): cuts (D, L3_FOREST_MAX_CUTS) and ncuts (D) of the last fit */
 int l3_forest_get_cuts(l3_forest *m, float *cuts, int32_t *ncuts);
 /* classifier/train.py:169-227 (the fit's course, for profiles): the last fit's levels -> their number; up to max_levels entries each of

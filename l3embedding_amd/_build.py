@@ -36,7 +36,8 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC'] + (['-DL3_EXPERI
 # featprep.hip: its contract counts float32 / float64 roundings (NumPy's in-place scaler arithmetic), so no multiply and add may
 # be contracted into a fused multiply-add
 # svm_eval.hip: likewise, its contract counts float64 roundings (NumPy's and libsvm's scalar arithmetic)
-# forest.hip: likewise, a split's worth is two float64 divisions and one addition, equal to the NumPy oracle's bit for bit
+# forest.hip: likewise, a split's worth is two float64 divisions and one addition, equal to the NumPy oracle's bit for bit, and the
+# scoring at nested forest sizes (l3_forest_score) is pinned to forest_predict_kernel's divisions and additions
 FILE_FLAGS = {'conv_wino4.hip': ['-fno-slp-vectorize'], 'conv_wino_bx6.hip': ['-fno-slp-vectorize'], 'conv_wgrad_bx6.hip': ['-fno-slp-vectorize'],
               'conv_first.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'featprep.hip': ['-ffp-contract=off'], 'svm_eval.hip': ['-ffp-contract=off'],
               'forest.hip': ['-ffp-contract=off']}

@@ -231,6 +231,8 @@ SIGNATURES = {
     'l3_forest_set_trees': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
     'l3_forest_predict_proba': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     'l3_forest_predict_proba_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'l3_forest_score': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 5),
     'l3_forest_get_cuts': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'l3_forest_level_stats': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
@@ -1591,6 +1593,7 @@ FOREST_MAX_CUTS = 255            # L3_FOREST_MAX_CUTS
 FOREST_MAX_DRAWS = 256           # L3_FOREST_MAX_DRAWS
 FOREST_MAX_BIN_SAMPLE = 8192     # L3_FOREST_MAX_BIN_SAMPLE
 FOREST_NARROW_ROWS = 64          # L3_FOREST_NARROW_ROWS
+FOREST_SCORE_OUTPUTS = ('pred', 'correct', 'file_mean', 'file_pred', 'proba')          # l3_forest_score's, in its order
 FOREST_TREE_ARRAYS = ('tree_off', 'left', 'right', 'feature', 'threshold', 'bin', 'counts', 'n_distinct')
 
 
@@ -1685,6 +1688,37 @@ class Forest(object):
         hi = n if hi is None else hi
         out = np.empty((max(int(hi - lo), 0), self.sizes()[2]), np.float64)
         check(self.lib.l3_forest_predict_proba_dev(self.h, feat.h, int(lo), int(hi), _ptr(out)))
+        return out
+
+    def score(self, X=None, feat=None, lo=0, hi=None, resident=False, prefixes=None, labels=None, files=None, outputs=('pred',),
+              chunk_rows=0, stage_bytes=0):
+        """l3_forest_score: the rows of exactly one of X (NumPy rows), rows [lo, hi) of the Features `feat` and rows [lo, hi) of the
+        resident matrix, scored by the first prefixes[g] trees for every g in one pass (None: the whole forest) -> dict of the
+        FOREST_SCORE_OUTPUTS that `outputs` names, each with the leading axis G.  labels: class indices; files: (F, 2) [start, end).
+        chunk_rows, stage_bytes: the rows per launch and the LDS budget of the staged rows (0: the library's), for tests."""
+        unknown = set(outputs) - set(FOREST_SCORE_OUTPUTS)
+        if unknown:
+            raise ValueError('unknown outputs %s; choose from %s' % (sorted(unknown), list(FOREST_SCORE_OUTPUTS)))
+        T, _, nc, D = self.sizes()
+        x = None
+        if X is not None:
+            x = _f32(X)
+            lo, hi, D = 0, x.shape[0], x.shape[1] if x.ndim == 2 else -1
+        elif hi is None:
+            hi = feat.shape[0] if feat is not None else self.n
+        n = max(int(hi) - int(lo), 0)
+        p = _i32([T] if prefixes is None else prefixes).reshape(-1)
+        y = None if labels is None else _i32(labels).reshape(-1)
+        if y is not None and y.size != n:
+            raise ValueError('one label per row')
+        fl = None if files is None else _i64(files).reshape(-1, 2)
+        F = 0 if fl is None else fl.shape[0]
+        shapes = dict(pred=((p.size, n), np.int32), correct=((p.size,), np.int64), file_mean=((p.size, F, nc), np.float64),
+                      file_pred=((p.size, F), np.int32), proba=((p.size, n, nc), np.float64))
+        out = {k: np.empty(*shapes[k]) for k in FOREST_SCORE_OUTPUTS if k in outputs}
+        check(self.lib.l3_forest_score(self.h, _ptr(x), None if feat is None else feat.h, int(lo), int(hi), int(D), 1 if resident else 0,
+                                       _ptr(p), p.size, _ptr(y), _ptr(fl), F, int(chunk_rows), int(stage_bytes),
+                                       *(_ptr(out.get(k)) for k in FOREST_SCORE_OUTPUTS)))
         return out
 
     def cuts(self):

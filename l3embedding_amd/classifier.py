@@ -11,7 +11,11 @@ it.  Deviations from the reference, all deliberate:
     (forest.py, csrc/forest.hip), not as sklearn's exact-split trees: forest.py's header lists how it differs.  train_rf does not
     seed NumPy's and Python's global generators (the reference does; every draw here has its own RandomState), pickles the model
     with `pickle`, and takes usc.DeviceFeatures as they are.  train() and cross_validate still refuse 'rf'; train_rf_fold is the
-    reference's train(model_type='rf'), and its parameter search (over n_estimators, :623-630) is not built: it raises;
+    reference's train(model_type='rf') without a parameter search (with one it raises), and train_rf_search / train_rf_search_fold
+    are its parameter search over n_estimators (:623-630) fitted in one pass: one forest of the largest size, whose first n trees
+    are the forest of n trees (forest.py), scored at every size of the grid in one pass over each split
+    (RandomForestClassifier.evaluate); every metric and the chosen size equal the loop's.  model_dir/model.pkl holds the returned
+    model there (the loop over train_rf leaves the one it fitted last);
   * the parameter search without a validation fold (train_param_search :408-423, :470-479) cuts the training rows with
     usc.stratified_shuffle_split, a NumPy restatement of sklearn's StratifiedShuffleSplit, and only when the caller gives the
     split's seed (split_random_state / parameter_search_split_seed; the reference passes none, so its split differs from run to
@@ -25,9 +29,9 @@ it.  Deviations from the reference, all deliberate:
     one pass on the GPU (svm.fit_grid).
 
 How the file is put together: train, train_svm_fold, train_rf_fold and cross_validate pass their arguments, by name in one dict, to
-one fold driver (_run_fold), and the model types differ in one function each (_mlp_part, _svm_part, _rf_part).  train_param_search and
-train_svm_search are
-one search body (_search) with two ways to fit the grid.  A usc.DeviceFeatures is closed by whoever made it, through _closing: the
+one fold driver (_run_fold), and the model types differ in one function each (_mlp_part, _svm_part, _rf_part; train_rf_search_fold
+hands the driver its own, _rf_search_part).  train_param_search, train_svm_search and train_rf_search are one search body (_search)
+with three ways to fit the grid.  A usc.DeviceFeatures is closed by whoever made it, through _closing: the
 driver closes the fold's splits, a search the parts of its cut and its merged matrix, and nobody what a caller passed in.
 """
 import contextlib
@@ -44,7 +48,7 @@ import numpy as np
 
 from . import _lib, callbacks, kerasfile
 from . import svm as _svm
-from .forest import RandomForestClassifier
+from .forest import FITTED_ROWS, RandomForestClassifier
 from .svm import SVC, hinge_loss  # noqa: F401  (re-exported: the reference imports them into classifier/train.py)
 from .usc import DeviceFeatures, FoldBank, get_split, preprocess_split_data, stratified_shuffle_split
 
@@ -588,6 +592,76 @@ def train_svm_search(train_data, valid_data, test_data, model_dir, Cs=SVM_SEARCH
     return outcome
 
 
+RF_SEARCH_GRID = (100, 500, 1000)        # classifier/train.py:626
+
+
+def _rf_grid(n_estimators_grid):
+    """the grid as a list of distinct positive ints, in the caller's order"""
+    grid = list(n_estimators_grid)
+    if not grid or any(isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1 for n in grid) or len(set(grid)) != len(grid):
+        raise ValueError('n_estimators_grid must hold distinct positive ints, one at least, not %r' % (n_estimators_grid,))
+    return [int(n) for n in grid]
+
+
+def train_rf_search(train_data, valid_data, test_data, model_dir, n_estimators_grid=RF_SEARCH_GRID, train_with_valid=False,
+                    num_classes=10, random_state=12345678, valid_ratio=0.15, split_random_state=None, n_estimators=None, **kwargs):
+    """train_param_search(..., train_func=train_rf, search_space={'n_estimators': n_estimators_grid}) with the grid fitted in one
+    pass: one forest of max(grid) trees on the search's training part, whose first n trees are the forest train_rf fits with
+    n_estimators=n (RandomForestClassifier.prefix), and one RandomForestClassifier.evaluate per split at all sizes at once: the
+    training rows where the fit left them on the GPU, the validation rows, the test rows with their files.  The size with the best
+    validation accuracy is kept (the earlier grid entry on ties), and with train_with_valid it is refitted as train_param_search
+    refits it.  -> the same tuple (model, train_metrics, valid_metrics, test_metrics) with the same search records and the same
+    numbers; 'loss' is 0.  model_dir/model.pkl holds the returned model (the loop over train_rf leaves the one it fitted last
+    there).  n_estimators is ignored (the search sets it); of kwargs RF_ARGS are passed on, as in train_rf.  Without a validation
+    fold (valid_data None): train_param_search's cut of valid_ratio of the training rows, seeded by split_random_state (None
+    refuses, NO_SSS)."""
+    grid = _rf_grid(n_estimators_grid)
+    sizes = sorted(grid)
+    forest_args = {k: kwargs[k] for k in RF_ARGS if k in kwargs}
+
+    def fit(data, n):
+        args = dict(forest_args)
+        if isinstance(data['features'], DeviceFeatures):
+            args.setdefault('device', data['features'].device)
+        return RandomForestClassifier(n_estimators=n, random_state=random_state, **args).fit(data['features'], data['labels'])
+
+    def score(clf, prefixes, train, valid):
+        """-> [(train metrics, valid metrics, test metrics)] per prefix of the forest just fitted on `train`"""
+        on_train = clf.evaluate(FITTED_ROWS, prefixes=prefixes)['predict']
+        on_valid = clf.evaluate(valid['features'], prefixes=prefixes)['predict'] if valid else None
+        per_file = None
+        if test_data:          # train_rf scores the files by class index
+            per_file = np.searchsorted(clf.classes_, clf.evaluate(test_data['features'], file_idxs=test_data['file_idxs'],
+                                                                  prefixes=prefixes, outputs=('file_predict',))['file_predict'])
+        scored = []
+        for g in range(len(on_train)):
+            train_metrics = compute_metrics(train['labels'], on_train[g], num_classes=num_classes)
+            train_metrics['loss'] = 0
+            valid_metrics = {}
+            if valid:
+                valid_metrics = compute_metrics(valid['labels'], on_valid[g], num_classes=num_classes)
+                valid_metrics['loss'] = 0
+            test_metrics = compute_metrics(test_data['labels'], per_file[g], num_classes=num_classes) if test_data else {}
+            scored.append((train_metrics, valid_metrics, test_metrics))
+        return scored
+
+    def run_grid(search_train, search_valid):
+        LOGGER.info('Fitting the grid n_estimators = %s as one forest of %d trees', grid, sizes[-1])
+        whole = fit(search_train, sizes[-1])
+        scored = score(whole, sizes, search_train, search_valid)
+        return [((n,), whole.prefix(n)) + scored[sizes.index(n)] for n in grid]
+
+    def refit(point, data):
+        model = fit(data, point[0])
+        train_metrics, _, test_metrics = score(model, None, data, None)[0]
+        return model, train_metrics, test_metrics
+
+    outcome = _search(train_data, valid_data, ['n_estimators'], valid_ratio, split_random_state, train_with_valid, run_grid, refit)
+    LOGGER.info('Saving model...')
+    _dump(os.path.join(model_dir, 'model.pkl'), outcome[0])
+    return outcome
+
+
 # ---- one cross-validation fold ------------------------------------------------------------------------------------------------------
 def _dataset_of(features_dir):
     """'.../features/us8k/l3/...' -> ('us8k', 'us8k/l3/...'): the path after the last 'features/' and its first part, a dataset"""
@@ -626,7 +700,8 @@ _CONFIG_KEYS_WHEN_SET = ('preprocess_device', 'parameter_search_split_seed')
 
 def _run_fold(fold, get_splits=None):
     """One cross-validation fold of any model type (classifier/train.py:495-709) -> its directory.  fold: the settings, the
-    arguments of train / train_svm_fold by name (model_type, fold_num and model_args among them).  get_splits: a function of
+    arguments of train / train_svm_fold by name (model_type, fold_num and model_args among them; model_part, where given, is the
+    function that runs the fold's model in place of the model type's own).  get_splits: a function of
     (with_valid_fold) that gives the fold's (train, valid or None, test) in place of usc.get_split (cross_validate's come from its
     FoldBank).  The splits are the driver's from the moment it has them: closed once, whatever fails after that."""
     on_cut = _searches_on_a_cut(fold)
@@ -656,7 +731,7 @@ def _run_fold(fold, get_splits=None):
                                         device=fold['preprocess_device'])
         for name, scaler in zip(('min_max_scaler.pkl', 'stdizer.pkl'), scalers):
             _dump(os.path.join(model_dir, name), scaler)
-        model_part = {'mlp': _mlp_part, 'svm': _svm_part, 'rf': _rf_part}[fold['model_type']]
+        model_part = fold.get('model_part') or {'mlp': _mlp_part, 'svm': _svm_part, 'rf': _rf_part}[fold['model_type']]
         _, train_metrics, valid_metrics, test_metrics = model_part(
             splits, model_dir, dict(fold, num_classes=DATASET_NUM_CLASSES[dataset], search_on_cut=on_cut))
     _dump(os.path.join(model_dir, 'results.pkl'), {'train': train_metrics, 'valid': valid_metrics, 'test': test_metrics})
@@ -697,6 +772,15 @@ def _rf_part(splits, model_dir, fold):
         raise ValueError(NO_RF_SEARCH)
     args = dict(dict(random_state=fold['random_state'], num_classes=fold['num_classes'], verbose=fold['verbose']), **fold['model_args'])
     return train_rf(*splits, model_dir, **args)
+
+
+def _rf_search_part(splits, model_dir, fold):
+    """the part of a fold that searches the random forest's n_estimators -> (model, train_metrics, valid_metrics, test_metrics):
+    train_rf_search with the fold's grid (in model_args), on the validation fold or on a cut"""
+    args = dict(dict(random_state=fold['random_state'], num_classes=fold['num_classes'], verbose=fold['verbose']), **fold['model_args'])
+    if fold['search_on_cut']:
+        args.update(valid_ratio=fold['parameter_search_valid_ratio'], split_random_state=fold['parameter_search_split_seed'])
+    return train_rf_search(*splits, model_dir, train_with_valid=fold['parameter_search_train_with_valid'], **args)
 
 
 def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='framewise', train_batch_size=64, patience=20,
@@ -750,6 +834,20 @@ def train_rf_fold(features_dir, output_dir, fold_num, feature_mode='framewise', 
     if parameter_search:
         raise ValueError(NO_RF_SEARCH)
     return _run_fold(dict(locals(), model_type='rf'))          # the fold's settings by name
+
+
+def train_rf_search_fold(features_dir, output_dir, fold_num, feature_mode='framewise', train_batch_size=64, patience=20,
+                         random_state=20171021, n_estimators_grid=RF_SEARCH_GRID, parameter_search_valid_fold=True,
+                         parameter_search_valid_ratio=0.15, parameter_search_train_with_valid=False, gsheet_id=None,
+                         google_dev_app_name=None, verbose=False, non_overlap=False, non_overlap_chunk_size=10, use_min_max=False,
+                         preprocess_device=None, parameter_search_split_seed=None, **model_args):
+    """classifier/train.py:495-709 for model_type='rf' with parameter_search (:623-630): train_rf_fold's fold, directory
+    (.../rf/fold<N>/<timestamp>/) and five files, the model chosen by train_rf_search over n_estimators_grid: on the validation
+    fold, or with parameter_search_valid_fold=False on a stratified cut seeded by parameter_search_split_seed (None refuses,
+    NO_SSS).  config.json records parameter_search true and n_estimators_grid; model_args are RF_ARGS.  -> that directory."""
+    fold = dict(locals(), model_type='rf', parameter_search=True, model_part=_rf_search_part)          # the fold's settings by name
+    fold['model_args'] = dict(model_args, n_estimators_grid=_rf_grid(fold.pop('n_estimators_grid')))
+    return _run_fold(fold)
 
 
 # what a fold's metrics hold besides numbers and lists of numbers with one entry per class: the per-epoch histories (their length

@@ -18,6 +18,13 @@
 // over integer counts, the sums of squares in int64: it does not depend on the order of any accumulation, both searches give the
 // same trees, and tests/forest_ref.py restates the whole in NumPy with equal results.  Compiled with -ffp-contract=off.
 // A node's K features come from Floyd's subset sampling driven by a counter-based mixer of (tree seed, node, draw).
+//
+// Scoring at nested forest sizes (l3_forest_score; the parameter search over n_estimators, classifier/train.py:623-630):
+//   forest_score     a workgroup per 4 rows, a wave per row, a lane per tree of a 64-tree pass: the rows staged in LDS when they fit,
+//                    the walk over packed 16-byte node records, the pass's count / total fractions computed across the wave into
+//                    LDS, then a lane per class adds them in tree order and emits arg-max, hit and probabilities at every prefix
+//   forest_file_*    a thread per (size, file, class) adds a file's rows in row order; a thread per (size, file) takes the arg-max
+// The sums are those of forest_predict_kernel, operation for operation: the outputs are its bits.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -458,10 +465,16 @@ __global__ __launch_bounds__(256) void forest_number_kernel(Grow p, int32_t* __r
 }
 
 // ---- prediction --------------------------------------------------------------------------------------------------------------------
+struct alignas(16) Node {          // a node as the scoring walk reads it, in one 16-byte load: left < 0 at a leaf
+    int32_t left, right, feat;
+    float thr;
+};
 struct Model {
     const int64_t* off;
     const int32_t *left, *right, *feat, *counts;
     const float* thr;
+    const Node* nodes;             // the same trees, packed
+    const int32_t* total;          // per node: the sum of its counts
     int T, C;
 };
 __global__ __launch_bounds__(256) void forest_predict_kernel(Model m, const float* __restrict__ X, int64_t n, int D, double* __restrict__ out) {
@@ -480,6 +493,124 @@ __global__ __launch_bounds__(256) void forest_predict_kernel(Model m, const floa
         for (int k = 0; k < m.C; ++k) o[k] += (double)c[k] / (double)total;
     }
     for (int k = 0; k < m.C; ++k) o[k] /= (double)m.T;
+}
+
+// ---- scoring at nested forest sizes ------------------------------------------------------------------------------------------------
+constexpr int SCORE_ROWS = 4;                               // rows per workgroup, a wave each
+constexpr int SCORE_CHUNK = 64;                             // trees per pass, a lane each
+constexpr int SCORE_MAX_PREFIXES = 4096;                    // the hit counters of a workgroup live in LDS
+constexpr int64_t SCORE_LDS_MAX = 160 * 1024;               // a CU's LDS
+constexpr int64_t SCORE_STAGE_BYTES = 96 * 1024;            // the default budget of the staged rows: 4 rows of 6144 floats
+constexpr int64_t SCORE_CHUNK_BYTES = (int64_t)1 << 28;     // the default bound of a host chunk's rows, as float32
+
+struct Score {
+    const float* X;                  // the chunk's rows
+    const int32_t* prefix;           // (G) forest sizes, ascending
+    const int32_t* labels;           // the chunk's, or null
+    int32_t* pred;                   // (G, n) of the chunk, or null
+    unsigned long long* correct;     // (G), or null
+    double* proba;                   // (G, n, C) of the chunk, or null
+    double* fproba;                  // (G, span, C): the chunk's rows [f_lo, f_hi) are its rows f_at ..., or null
+    int64_t n, f_lo, f_hi, f_at, span;
+    int D, G, T;                     // T: the largest size
+};
+
+// LDS: the waves' fractions (SCORE_ROWS, SCORE_CHUNK, C) float64, the workgroup's hits (G, padded to 16 bytes), the staged rows
+template <bool STAGED>
+__global__ __launch_bounds__(256) void forest_score_kernel(Model m, Score a) {
+    extern __shared__ double score_lds[];
+    const int C = m.C, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* frac = score_lds + (size_t)wave * SCORE_CHUNK * C;
+    int* hits = (int*)(score_lds + (size_t)SCORE_ROWS * SCORE_CHUNK * C);
+    float* xs = (float*)(hits + ((a.G + 3) & ~3));
+    for (int g = threadIdx.x; g < a.G; g += 256) hits[g] = 0;
+    const int64_t tiles = (a.n + SCORE_ROWS - 1) / SCORE_ROWS;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t r0 = tile * SCORE_ROWS, row = r0 + wave;
+        const bool live = row < a.n;
+        if (STAGED) {
+            __syncthreads();          // the last tile's walks are over
+            const int64_t cnt = (a.n - r0 < SCORE_ROWS ? a.n - r0 : SCORE_ROWS) * a.D;
+            const float* src = a.X + r0 * a.D;
+            for (int64_t i = threadIdx.x; i < cnt; i += 256) xs[i] = src[i];
+        }
+        __syncthreads();
+        const float* x = STAGED ? xs + (size_t)wave * a.D : a.X + (live ? row : 0) * a.D;
+        const int kk = lane < C ? lane : C - 1;
+        double acc = 0.0;
+        int gi = 0, nextp = a.prefix[0];
+        for (int t0 = 0; t0 < a.T; t0 += SCORE_CHUNK) {
+            const int cnt = a.T - t0 < SCORE_CHUNK ? a.T - t0 : SCORE_CHUNK;
+            if (live) {
+                int leaf = 0;
+                if (lane < cnt) {
+                    const int64_t base = m.off[t0 + lane];
+                    const Node* nd = m.nodes + base;
+                    int node = 0;
+                    for (Node r; (r = nd[node]).left >= 0;) node = x[r.feat] <= r.thr ? r.left : r.right;
+                    leaf = (int)base + node;
+                }
+                const int pairs = cnt * C;          // the pass's (tree, class) pairs, spread over the lanes
+                for (int p0 = 0; p0 < pairs; p0 += 64) {
+                    const int p = p0 + lane;
+                    const int tr = (p < pairs ? p : pairs - 1) / C;
+                    const int lf = __shfl(leaf, tr);
+                    if (p < pairs) frac[p] = (double)m.counts[(int64_t)lf * C + (p - tr * C)] / (double)m.total[lf];
+                }
+            }
+            __syncthreads();
+            if (live)
+                for (int j = 0; j < cnt; ++j) {          // a lane per class, in tree order
+                    acc += frac[j * C + kk];
+                    if (t0 + j + 1 != nextp) continue;
+                    const double p = acc / (double)nextp;
+                    if (lane < C) {
+                        if (a.proba) a.proba[((int64_t)gi * a.n + row) * C + lane] = p;
+                        if (a.fproba && row >= a.f_lo && row < a.f_hi) a.fproba[((int64_t)gi * a.span + a.f_at + (row - a.f_lo)) * C + lane] = p;
+                    }
+                    if (a.pred || a.correct) {
+                        double v = lane < C ? p : -1.0;
+                        int pos = lane;
+                        wave_argmax(v, pos);
+                        if (lane == 0) {
+                            if (a.pred) a.pred[(int64_t)gi * a.n + row] = pos;
+                            if (a.correct && pos == a.labels[row]) atomicAdd(&hits[gi], 1);
+                        }
+                    }
+                    ++gi;
+                    nextp = gi < a.G ? a.prefix[gi] : -1;
+                }
+            __syncthreads();
+        }
+    }
+    if (!a.correct) return;
+    __syncthreads();
+    for (int g = threadIdx.x; g < a.G; g += 256)
+        if (hits[g]) atomicAdd(&a.correct[g], (unsigned long long)hits[g]);
+}
+
+// a thread per (size, file, class): the file's rows added in row order, / their number
+__global__ void forest_file_mean_kernel(const double* __restrict__ fproba, const int64_t* __restrict__ files, int64_t fmin, int64_t span,
+                                        int64_t F, int C, int G, double* __restrict__ mean) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)G * F * C) return;
+    const int k = (int)(i % C);
+    const int64_t f = (i / C) % F, g = i / ((int64_t)C * F);
+    const int64_t s = files[2 * f], e = files[2 * f + 1];
+    const double* p = fproba + (g * span + (s - fmin)) * C + k;
+    double sum = 0.0;
+    for (int64_t r = s; r < e; ++r, p += C) sum += *p;
+    mean[i] = sum / (double)(e - s);
+}
+// a thread per (size, file): the first of the largest means
+__global__ void forest_file_pred_kernel(const double* __restrict__ mean, int64_t GF, int C, int32_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= GF) return;
+    const double* v = mean + i * C;
+    int best = 0;
+    for (int k = 1; k < C; ++k)
+        if (v[k] > v[best]) best = k;
+    out[i] = best;
 }
 
 }  // namespace
@@ -538,8 +669,19 @@ int upload_model(l3_forest* m, const char* fn) {
     dm.feat = b.put(m->feat.data(), m->feat.size(), m->s);
     dm.counts = b.put(m->counts.data(), m->counts.size(), m->s);
     dm.thr = b.put(m->thr.data(), m->thr.size(), m->s);
+    const size_t total = m->left.size();
+    std::vector<Node> nodes(total);          // what the scoring walk reads
+    std::vector<int32_t> sums(total);
+    for (size_t i = 0; i < total; ++i) {
+        nodes[i] = Node{m->left[i], m->right[i], m->feat[i], m->thr[i]};
+        int32_t sum = 0;
+        for (int k = 0; k < m->C; ++k) sum += m->counts[i * m->C + k];
+        sums[i] = sum;
+    }
+    dm.nodes = b.put(nodes.data(), total, m->s);
+    dm.total = b.put(sums.data(), total, m->s);
     dm.T = m->T, dm.C = m->C;
-    if (!dm.off || !dm.left || !dm.right || !dm.feat || !dm.counts || !dm.thr) {
+    if (!dm.off || !dm.left || !dm.right || !dm.feat || !dm.counts || !dm.thr || !dm.nodes || !dm.total) {
         b.clear();
         return fail(L3_ENOMEM, std::string(fn) + ": device allocation of the forest failed");
     }
@@ -852,6 +994,117 @@ int l3_forest_predict_proba_dev(l3_forest* m, const l3_feat* f, int64_t lo, int6
         return fail(L3_EINVAL, "l3_forest_predict_proba_dev: rows [lo, hi) lie outside the matrix, are none, or have another width than the forest");
     (void)hipSetDevice(m->device);
     return predict_device(m, f->x + lo * f->D, hi - lo, (int)f->D, out, "l3_forest_predict_proba_dev");
+}
+
+int l3_forest_score(l3_forest* m, const float* X, const l3_feat* f, int64_t lo, int64_t hi, int D, int resident, const int32_t* prefix,
+                    int n_prefix, const int32_t* labels, const int64_t* files, int64_t n_files, int64_t chunk_rows, int64_t stage_bytes,
+                    int32_t* pred, int64_t* correct, double* file_mean, int32_t* file_pred, double* proba) {
+    const std::string fn = "l3_forest_score: ";
+    if (!m) return fail(L3_EINVAL, fn + "NULL handle");
+    if (!m->has_model) return fail(L3_ESTATE, fn + "no forest (l3_forest_fit or l3_forest_set_trees)");
+    if ((X != nullptr) + (f != nullptr) + (resident != 0) != 1) return fail(L3_EINVAL, fn + "the rows come from exactly one of X, a device matrix and the resident matrix");
+    const float* dx = nullptr;          // the rows where they already are on the device
+    if (resident) {
+        if (m->n <= 0) return fail(L3_ESTATE, fn + "no resident matrix (l3_forest_set_data)");
+        if (lo < 0 || hi <= lo || hi > m->n) return fail(L3_EINVAL, fn + "rows [lo, hi) lie outside the resident matrix or are none");
+        D = m->D, dx = m->x + lo * m->D;
+    } else if (f) {
+        if (f->device != m->device) return fail(L3_EINVAL, fn + "the feature matrix is on another device");
+        if (lo < 0 || hi <= lo || hi > f->n) return fail(L3_EINVAL, fn + "rows [lo, hi) lie outside the matrix or are none");
+        D = (int)f->D, dx = f->x + lo * f->D;
+    } else if (lo != 0 || hi <= 0) {
+        return fail(L3_EINVAL, fn + "host rows are [0, hi) with hi >= 1");
+    }
+    const int64_t n = hi - lo;
+    const int C = m->C, G = n_prefix;
+    if (D != m->mD) return fail(L3_EINVAL, fn + "the rows have " + std::to_string(D) + " features, the forest " + std::to_string(m->mD));
+    if (!prefix || G < 1 || G > SCORE_MAX_PREFIXES) return fail(L3_EINVAL, fn + "need 1 to " + std::to_string(SCORE_MAX_PREFIXES) + " forest sizes");
+    for (int g = 0; g < G; ++g)
+        if (prefix[g] < 1 || prefix[g] > m->T || (g > 0 && prefix[g] <= prefix[g - 1]))
+            return fail(L3_EINVAL, fn + "prefix[" + std::to_string(g) + "] is outside [1, " + std::to_string(m->T) + "] or not above its predecessor");
+    if (correct && !labels) return fail(L3_EINVAL, fn + "correct needs labels");
+    if (labels)
+        for (int64_t i = 0; i < n; ++i)
+            if (labels[i] < 0 || labels[i] >= C) return fail(L3_EINVAL, fn + "labels[" + std::to_string(i) + "] outside [0, n_classes)");
+    const bool file_out = file_mean || file_pred;
+    if (n_files < 0 || (n_files > 0) != (files != nullptr)) return fail(L3_EINVAL, fn + "files and n_files come together");
+    if ((n_files > 0) != file_out) return fail(L3_EINVAL, fn + "files and the file outputs (file_mean, file_pred) come together");
+    int64_t fmin = n, fmax = 0;
+    for (int64_t i = 0; i < n_files; ++i) {
+        const int64_t s = files[2 * i], e = files[2 * i + 1];
+        if (s < 0 || e <= s || e > n) return fail(L3_EINVAL, fn + "file " + std::to_string(i) + " is empty or lies outside the rows");
+        fmin = std::min(fmin, s), fmax = std::max(fmax, e);
+    }
+    if (chunk_rows < 0 || stage_bytes < 0) return fail(L3_EINVAL, fn + "chunk_rows and stage_bytes are 0 (the defaults) or positive");
+    if (!pred && !correct && !file_out && !proba) return fail(L3_EINVAL, fn + "no output is asked for");
+
+    // LDS: fractions + hits (+ the staged rows when they fit the budget and the CU)
+    const int64_t lds_plain = (int64_t)SCORE_ROWS * SCORE_CHUNK * C * 8 + (int64_t)((G + 3) & ~3) * 4;
+    const int64_t row_bytes = (int64_t)SCORE_ROWS * D * 4;
+    const bool staged = row_bytes <= (stage_bytes > 0 ? stage_bytes : SCORE_STAGE_BYTES) && lds_plain + row_bytes <= SCORE_LDS_MAX;
+    const int64_t lds = lds_plain + (staged ? row_bytes : 0);
+    int64_t chunk = chunk_rows > 0 ? chunk_rows : std::max<int64_t>(SCORE_ROWS, SCORE_CHUNK_BYTES / (4 * (int64_t)D));
+    chunk = std::min(chunk, n);
+    const int64_t span = n_files > 0 ? fmax - fmin : 0;
+
+    (void)hipSetDevice(m->device);
+    hipStream_t s = m->s;
+    (void)hipStreamSynchronize(s);
+    const void* kernel = staged ? (const void*)forest_score_kernel<true> : (const void*)forest_score_kernel<false>;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCORE_LDS_MAX) != hipSuccess)
+        return fail(L3_EHIP, fn + "the kernel's LDS size could not be set");
+    DeviceBufs b;
+    Score a{};
+    a.prefix = b.put(prefix, (size_t)G, s);
+    const int32_t* d_labels = labels ? b.put(labels, (size_t)n, s) : nullptr;
+    float* d_x = dx ? nullptr : b.alloc<float>((size_t)chunk * D);
+    int32_t* d_pred = pred ? b.alloc<int32_t>((size_t)G * chunk) : nullptr;
+    double* d_proba = proba ? b.alloc<double>((size_t)G * chunk * C) : nullptr;
+    unsigned long long* d_correct = correct ? b.alloc<unsigned long long>((size_t)G) : nullptr;
+    double* d_fproba = n_files ? b.alloc<double>((size_t)G * span * C) : nullptr;
+    double* d_fmean = n_files ? b.alloc<double>((size_t)G * n_files * C) : nullptr;
+    int32_t* d_fpred = file_pred ? b.alloc<int32_t>((size_t)G * n_files) : nullptr;
+    const int64_t* d_files = n_files ? b.put(files, (size_t)2 * n_files, s) : nullptr;
+    if (!b.ok()) return fail(L3_ENOMEM, fn + "device allocation failed");
+    if (d_correct && hipMemsetAsync(d_correct, 0, (size_t)G * sizeof(unsigned long long), s) != hipSuccess) return fail(L3_EHIP, fn + "HIP error");
+    a.pred = d_pred, a.correct = d_correct, a.proba = d_proba, a.span = span, a.D = D, a.G = G, a.T = prefix[G - 1];
+    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+        const int64_t cn = std::min(chunk, n - c0);
+        if (d_x && hipMemcpyAsync(d_x, X + c0 * D, (size_t)cn * D * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)
+            return fail(L3_EHIP, fn + "copy of the rows failed");
+        a.X = d_x ? d_x : dx + c0 * D;
+        a.labels = d_labels ? d_labels + c0 : nullptr;
+        a.n = cn;
+        const int64_t flo = std::max(fmin, c0), fhi = std::min(fmax, c0 + cn);          // the chunk's rows inside the files' span
+        a.fproba = n_files && flo < fhi ? d_fproba : nullptr;
+        a.f_lo = flo - c0, a.f_hi = fhi - c0, a.f_at = flo - fmin;
+        const unsigned grid = (unsigned)std::min<int64_t>((cn + SCORE_ROWS - 1) / SCORE_ROWS, 2048);
+        if (staged) hipLaunchKernelGGL(forest_score_kernel<true>, dim3(grid), dim3(256), (size_t)lds, s, m->dm, a);
+        else hipLaunchKernelGGL(forest_score_kernel<false>, dim3(grid), dim3(256), (size_t)lds, s, m->dm, a);
+        if (hipGetLastError() != hipSuccess) return fail(L3_EHIP, fn + "launch failed");
+        for (int g = 0; g < G; ++g) {
+            if (pred && hipMemcpyAsync(pred + (int64_t)g * n + c0, d_pred + (int64_t)g * cn, (size_t)cn * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
+                return fail(L3_EHIP, fn + "copy of the predictions failed");
+            if (proba && hipMemcpyAsync(proba + ((int64_t)g * n + c0) * C, d_proba + (int64_t)g * cn * C, (size_t)cn * C * 8, hipMemcpyDeviceToHost,
+                                        s) != hipSuccess)
+                return fail(L3_EHIP, fn + "copy of the probabilities failed");
+        }
+        if (hipStreamSynchronize(s) != hipSuccess) return fail(L3_EHIP, fn + "HIP error in the scoring kernel");
+    }
+    if (n_files) {
+        const int64_t items = (int64_t)G * n_files * C, gf = (int64_t)G * n_files;
+        hipLaunchKernelGGL(forest_file_mean_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, d_fproba, d_files, fmin, span, n_files, C,
+                           G, d_fmean);
+        if (file_pred) hipLaunchKernelGGL(forest_file_pred_kernel, dim3((unsigned)((gf + 255) / 256)), dim3(256), 0, s, d_fmean, gf, C, d_fpred);
+        if (hipGetLastError() != hipSuccess ||
+            (file_mean && hipMemcpyAsync(file_mean, d_fmean, (size_t)items * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+            (file_pred && hipMemcpyAsync(file_pred, d_fpred, (size_t)gf * 4, hipMemcpyDeviceToHost, s) != hipSuccess))
+            return fail(L3_EHIP, fn + "HIP error in the file means");
+    }
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the hit counters are read back as int64");
+    if (correct && hipMemcpyAsync(correct, d_correct, (size_t)G * 8, hipMemcpyDeviceToHost, s) != hipSuccess) return fail(L3_EHIP, fn + "HIP error");
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(L3_EHIP, fn + "HIP error");
+    return L3_OK;
 }
 
 int l3_forest_get_cuts(l3_forest* m, float* cuts, int32_t* ncuts) {

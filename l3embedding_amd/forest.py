@@ -8,6 +8,13 @@ bin_sample rows, a uint8 bin code per value, all trees advancing one level per g
 formula for a split's worth.  Here are the draws a fit needs from NumPy (the tree seeds, each tree's bootstrap multiplicities, the
 rows of the cut sample) and sklearn's shell: fit / predict / predict_proba, classes_, estimators_ and pickling.
 
+Beyond sklearn's interface, for the parameter search over n_estimators (classifier.train_rf_search): a forest
+of n trees is the first n trees of a larger one fitted with the same random_state (the cuts depend on the data and random_state
+alone, a tree on the cuts, its seed and its bootstrap, and RandomState(random_state).randint(2^31 - 1, size=n) is a prefix of the
+same call with a larger size).  evaluate() scores rows by several such prefixes in one pass on the GPU (l3_forest_score: predictions,
+hits, probabilities, per-file means, each tree walked once per row, bit for bit what predict_proba gives for each prefix), and
+prefix(n) is the fitted classifier of the first n trees.
+
 Deviations from sklearn 0.19, all deliberate:
   * a split is searched among at most 255 cuts per feature (sklearn tries every midpoint of the node's own values), so the trees are
     not sklearn's; they are judged against sklearn's seed-to-seed spread (tests/golden/make_forest_golden.py) and are equal, node for
@@ -26,6 +33,12 @@ import numpy as np
 
 from . import _lib
 from .usc import DeviceFeatures
+
+
+# evaluate()'s X for "the rows this forest was fitted on": they are still on the GPU, in the handle the fit left them in
+FITTED_ROWS = object()
+EVALUATE_OUTPUTS = ('predict', 'correct', 'proba', 'file_mean', 'file_predict')
+_SCORE_NAMES = {'predict': 'pred', 'correct': 'correct', 'proba': 'proba', 'file_mean': 'file_mean', 'file_predict': 'file_pred'}
 
 
 def tree_seeds(random_state, n_estimators):
@@ -83,21 +96,25 @@ class RandomForestClassifier(object):
         self.bin_sample, self.device, self.wide_min_rows = bin_sample, device, wide_min_rows
         self._h = None
         self._resident = False
+        self._fitted_rows = 0          # rows of the fit's matrix while this model's handle still holds it (evaluate(FITTED_ROWS))
 
     # pickling: everything but the device handle
     def __getstate__(self):
         state = dict(self.__dict__)
         state['_h'] = None
         state['_resident'] = False
+        state['_fitted_rows'] = 0
         return state
 
     def __setstate__(self, state):
         self.__dict__.update(state)
+        self.__dict__.setdefault('_fitted_rows', 0)          # a model pickled before evaluate() existed
 
     def _handle(self):
         if self._h is None:
             self._h = _lib.Forest(self.device)
             self._resident = False
+            self._fitted_rows = 0
         return self._h
 
     def fit(self, X, y):
@@ -128,6 +145,7 @@ class RandomForestClassifier(object):
         rows = bin_sample_rows(self.random_state, n, int(self.bin_sample))
         h = self._handle()
         self._resident = False
+        self._fitted_rows = 0
         if on_device:
             h.set_data_dev(X.handle)
         else:
@@ -138,6 +156,7 @@ class RandomForestClassifier(object):
         self.estimators_ = h.trees()
         self.level_stats_ = h.level_stats()
         self._resident = True
+        self._fitted_rows = n
         return self
 
     def _check_fitted(self):
@@ -168,3 +187,66 @@ class RandomForestClassifier(object):
     def predict(self, X):
         proba = self.predict_proba(X)
         return self.classes_[np.argmax(proba, axis=1)]
+
+    def evaluate(self, X, y=None, file_idxs=None, prefixes=None, outputs=('predict',), chunk_rows=0, stage_bytes=0):
+        """One scoring pass on the GPU over X by the forests of the first prefixes[g] trees, every tree walked once per row -> dict
+        of what `outputs` names (EVALUATE_OUTPUTS), each with the leading axis G = len(prefixes); without prefixes the whole forest,
+        G = 1.  X: NumPy rows, a usc.DeviceFeatures, or FITTED_ROWS (the rows of the last fit, as long as this model's handle still
+        holds them: not after pickling).  prefixes: distinct forest sizes in [1, n_estimators], ascending.
+        'predict' (G, n): classes_ values; 'correct' (G): the rows predicted as y (classes_ values, every one of them known to the
+        forest); 'proba' (G, n, C): predict_proba of each prefix, bit for bit; 'file_mean' (G, F, C): the mean of the probabilities of
+        the rows [s, e) of each file_idxs entry, added in row order as NumPy's mean(axis=0) adds them, and 'file_predict' (G, F) its
+        arg-max as classes_ values.  chunk_rows, stage_bytes: _lib.Forest.score's, for tests; they change no bit."""
+        self._check_fitted()
+        outputs = tuple(outputs)
+        unknown = set(outputs) - set(EVALUATE_OUTPUTS)
+        if unknown:
+            raise ValueError('unknown outputs %s; choose from %s' % (sorted(unknown), list(EVALUATE_OUTPUTS)))
+        by_file = 'file_mean' in outputs or 'file_predict' in outputs
+        if by_file and file_idxs is None:
+            raise ValueError("'file_mean' and 'file_predict' need file_idxs")
+        if 'correct' in outputs and y is None:
+            raise ValueError("'correct' needs y")
+        if X is FITTED_ROWS:
+            if not self._fitted_rows or self._h is None:
+                raise ValueError('the rows of the fit are no longer on the GPU: pass them to evaluate')
+            rows, n = dict(resident=True), self._fitted_rows
+        else:
+            on_device = isinstance(X, DeviceFeatures)
+            if not on_device:
+                X = np.ascontiguousarray(X, np.float32)
+            if len(X.shape) != 2 or X.shape[1] != self.n_features_:
+                raise ValueError('X has %s features per sample; expecting %d' % (tuple(X.shape[1:]), self.n_features_))
+            if X.shape[0] == 0:
+                raise ValueError('no rows to score')
+            rows, n = (dict(feat=X.handle) if on_device else dict(X=X)), int(X.shape[0])
+        labels = None
+        if 'correct' in outputs:
+            y = np.asarray(y).reshape(-1)
+            if y.size != n:
+                raise ValueError('one label per row')
+            labels = np.searchsorted(self.classes_, y).clip(max=self.classes_.size - 1)
+            if not np.array_equal(self.classes_[labels], y):
+                raise ValueError('y holds a label the forest was not fitted on')
+        h = self._ensure_model()
+        got = h.score(prefixes=prefixes, labels=labels, files=file_idxs if by_file else None,
+                      outputs=tuple(_SCORE_NAMES[k] for k in outputs), chunk_rows=chunk_rows, stage_bytes=stage_bytes, **rows)
+        out = {k: got[_SCORE_NAMES[k]] for k in outputs}
+        for k in ('predict', 'file_predict'):
+            if k in out:
+                out[k] = self.classes_[out[k]]
+        return out
+
+    def prefix(self, n):
+        """the fitted classifier of this forest's first n trees, n_estimators = n: what fit gives with n_estimators=n and everything
+        else equal.  Its estimators_ are views of this forest's arrays; it has no handle and uploads its trees on first use."""
+        self._check_fitted()
+        n = int(n)
+        if not 1 <= n <= int(self.n_estimators):
+            raise ValueError('a prefix holds between 1 and n_estimators = %d trees' % self.n_estimators)
+        part = type(self).__new__(type(self))
+        part.__dict__.update(self.__getstate__(), n_estimators=n)
+        part.__dict__.pop('level_stats_', None)          # the course of the larger fit
+        nodes = int(self.estimators_['tree_off'][n])
+        part.estimators_ = {k: v[:n + 1] if k == 'tree_off' else v[:nodes] for k, v in self.estimators_.items()}
+        return part
