@@ -716,6 +716,50 @@ int l3_mlp_set_data_dev(l3_mlp *m, const l3_feat *train, int64_t lo, int64_t hi,
 /* l3_mlp_predict of rows [lo, hi) of a device matrix, in l3_mlp_predict's row blocks without its staging copy: the same bits */
 int l3_mlp_predict_dev(l3_mlp *m, const l3_feat *x, int64_t lo, int64_t hi, float *probs_out);
 
+/* ---- A group of MLP classifiers (the learning_rate x weight_decay search of classifier/train.py:638-651) ---------------------------
+ * n_members models of one shape (D, C, batch) trained on ONE resident data set in the same launches: an epoch's step is seven
+ * launches whatever the number of members, and the validation pass and prediction run every member per launch too.
+ * Per member: weights, Adam moments, activations, split-K partials and counters, learning rate, weight decay.  Shared: the features,
+ * labels and permutation.  Member i computes, bit for bit, what an l3_mlp created with (weight_decay[i], seed[i]) computes from the
+ * same calls: l3_mlp is a group of one, on the same kernels, and no member's arithmetic depends on the others.  One stream per
+ * handle; calls on one handle are not re-entrant.  Errors as l3_mlp: l3_last_error(NULL) gives the message. */
+typedef struct l3_mlp_group l3_mlp_group;
+/* l3_mlp_create for 1 <= n_members <= 16 models: member i gets weight_decay[i] and the Glorot draw l3_mlp_create makes from seed[i].
+ * L3_EINVAL: D, C or batch outside l3_mlp_create's ranges, n_members outside [1, 16], a NULL array, a negative weight decay;
+ * L3_ENOMEM: a failed allocation (a member needs what an l3_mlp needs but the staging block of predict, which is shared). */
+int l3_mlp_group_create(int device, int D, int C, int batch, int n_members, const float *weight_decay, const uint64_t *seed,
+                        l3_mlp_group **g);
+void l3_mlp_group_destroy(l3_mlp_group *g);
+/* a member's element count: l3_mlp_param_count */
+int64_t l3_mlp_group_param_count(const l3_mlp_group *g);
+/* l3_mlp_set_data / l3_mlp_set_data_dev: the same contract, checks and error codes; one resident copy serves all members. */
+int l3_mlp_group_set_data(l3_mlp_group *g, const float *X_train, const int32_t *y_train, int64_t n_train, const float *X_valid,
+                          const int32_t *y_valid, int64_t n_valid);
+int l3_mlp_group_set_data_dev(l3_mlp_group *g, const l3_feat *train, int64_t lo, int64_t hi, const int32_t *y, const l3_feat *valid,
+                              int64_t vlo, int64_t vhi, const int32_t *yv);
+/* l3_mlp_epoch of every live member (live[i] != 0) at its own rate lr[i]: the steps over `perm` (Adam steps t0 + 1, ... for all of
+ * them), then the validation rows.  lr, live: n_members entries.  stats_out (n_members x 4): loss, acc, val_loss, val_acc per member
+ * as l3_mlp_epoch gives them.  A member that is not live is left as it is (weights, moments) and its four statistics are NaN; with
+ * no live member nothing is launched.  L3_EINVAL: a NULL argument, t0 < 0, a perm entry outside [0, n_train); L3_ESTATE: no data. */
+int l3_mlp_group_epoch(l3_mlp_group *g, const int32_t *perm, const float *lr, const int32_t *live, int64_t t0, double *stats_out);
+/* keep_best: member i's weights (bit i of mask) are copied, device to device, into the member's own slot, replacing what it held;
+ * restore_best copies them back.  The search's stand-in for ModelCheckpoint(save_best_only, save_weights_only) and the load_weights
+ * that follows the fit: float32 copies, so the bits are those of the trip through model.h5.  The Adam moments are not part of it.
+ * L3_EINVAL: a mask bit at or past n_members; L3_ESTATE: restore_best of a member that never was kept; L3_ENOMEM: the slots (one
+ * more copy of the weights, allocated by the first keep_best) could not be allocated. */
+int l3_mlp_group_keep_best(l3_mlp_group *g, uint32_t mask);
+int l3_mlp_group_restore_best(l3_mlp_group *g, uint32_t mask);
+/* l3_mlp_predict / l3_mlp_predict_dev through every member in one pass: probs_out (n_members, n, C), member i's rows as l3_mlp_predict
+ * gives them (the same row blocks).  predict_resident: of the rows l3_mlp_group_set_data left on the device, the training rows
+ * (valid 0) or the validation rows (valid 1), without another upload; L3_ESTATE when there are none. */
+int l3_mlp_group_predict(l3_mlp_group *g, const float *X, int64_t n, float *probs_out);
+int l3_mlp_group_predict_dev(l3_mlp_group *g, const l3_feat *x, int64_t lo, int64_t hi, float *probs_out);
+int l3_mlp_group_predict_resident(l3_mlp_group *g, int valid, float *probs_out);
+/* l3_mlp_get_weights / l3_mlp_set_weights of one member (keras order; n must be l3_mlp_group_param_count).  L3_EINVAL: no such
+ * member, NULL, wrong n. */
+int l3_mlp_group_get_weights(l3_mlp_group *g, int member, float *dst, int64_t n);
+int l3_mlp_group_set_weights(l3_mlp_group *g, int member, const float *src, int64_t n);
+
 /* ---- Downstream random forest (classifier/train.py:169-227) ----------------------------------------------------------------------
  * train_rf's sklearn.ensemble.RandomForestClassifier(n_estimators, random_state) with sklearn 0.19's defaults (Gini, bootstrap,
  * max_features sqrt(D), trees grown out), as a level-wise histogram forest on the GPU (csrc/forest.hip): per feature at

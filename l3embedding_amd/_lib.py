@@ -220,6 +220,21 @@ SIGNATURES = {
     'l3_mlp_set_data_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                       C.c_void_p]),
     'l3_mlp_predict_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    # a group of MLPs trained in the same launches (csrc/mlp.hip)
+    'l3_mlp_group_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    'l3_mlp_group_destroy': (None, [C.c_void_p]),
+    'l3_mlp_group_param_count': (C.c_int64, [C.c_void_p]),
+    'l3_mlp_group_set_data': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_mlp_group_set_data_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.c_int64, C.c_void_p]),
+    'l3_mlp_group_epoch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_mlp_group_keep_best': (C.c_int, [C.c_void_p, C.c_uint32]),
+    'l3_mlp_group_restore_best': (C.c_int, [C.c_void_p, C.c_uint32]),
+    'l3_mlp_group_predict': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_mlp_group_predict_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'l3_mlp_group_predict_resident': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    'l3_mlp_group_get_weights': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
+    'l3_mlp_group_set_weights': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     # downstream random forest (csrc/forest.hip): classifier/train.py:169-227
     'l3_forest_create': (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     'l3_forest_destroy': (None, [C.c_void_p]),
@@ -982,6 +997,131 @@ class MLP(object):
         out = np.empty((max(0, hi - lo), self.C), np.float32)
         if hi > lo:
             check(self.lib.l3_mlp_predict_dev(self.h, feat.h, int(lo), int(hi), _ptr(out)))
+        return out
+
+
+MLP_MAX_MEMBERS = 16
+
+
+class MLPGroup(object):
+    """RAII wrapper over an l3_mlp_group handle: len(weight_decays) models of one shape trained on one resident data set in the
+    same launches; member i equals MLP(D, num_classes, batch, weight_decays[i], seeds[i]) bit for bit."""
+
+    def __init__(self, D, num_classes, batch, weight_decays, seeds, device=0):
+        self.lib = load()
+        self.D, self.C, self.batch = int(D), int(num_classes), int(batch)
+        self.weight_decays = [float(w) for w in weight_decays]
+        self.n_members = len(self.weight_decays)
+        if len(seeds) != self.n_members:
+            raise ValueError('one seed per member is needed')
+        wd = np.asarray(self.weight_decays, np.float32)
+        sd = np.asarray([int(s) & (2 ** 64 - 1) for s in seeds], np.uint64)
+        h = C.c_void_p()
+        check(self.lib.l3_mlp_group_create(int(device), self.D, self.C, self.batch, self.n_members, _ptr(wd), _ptr(sd), C.byref(h)),
+              None)
+        self.h = h
+        self.n_train = self.n_valid = 0
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_mlp_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def param_count(self):
+        return int(self.lib.l3_mlp_group_param_count(self.h))
+
+    def get_weights(self, member):
+        flat = np.empty(self.param_count(), np.float32)
+        check(self.lib.l3_mlp_group_get_weights(self.h, int(member), _ptr(flat), flat.size))
+        out, o = [], 0
+        for shp in mlp_shapes(self.D, self.C):
+            n = int(np.prod(shp))
+            out.append(flat[o:o + n].reshape(shp).copy())
+            o += n
+        return out
+
+    def set_weights(self, member, weights):
+        shapes = mlp_shapes(self.D, self.C)
+        if [tuple(np.shape(w)) for w in weights] != shapes:
+            raise ValueError('weight shapes %s, expected %s' % ([np.shape(w) for w in weights], shapes))
+        flat = np.concatenate([np.asarray(w, np.float32).ravel() for w in weights])
+        check(self.lib.l3_mlp_group_set_weights(self.h, int(member), _ptr(flat), flat.size))
+
+    def set_data(self, X_train, y_train, X_valid=None, y_valid=None):
+        xt, yt = _f32(X_train), _i32(y_train)
+        xv = _f32(X_valid) if X_valid is not None else None
+        yv = _i32(y_valid) if y_valid is not None else None
+        nv = 0 if xv is None else xv.shape[0]
+        check(self.lib.l3_mlp_group_set_data(self.h, _ptr(xt), _ptr(yt), xt.shape[0], _ptr(xv), _ptr(yv), nv))
+        self.n_train, self.n_valid = xt.shape[0], nv
+
+    def set_data_dev(self, train, lo, hi, y_train, valid=None, vlo=0, vhi=0, y_valid=None):
+        """MLP.set_data_dev for the group: one resident copy serves every member"""
+        yt = _i32(y_train)
+        yv = _i32(y_valid) if valid is not None and vhi > vlo else None
+        if yt.shape != (hi - lo,) or (yv is not None and yv.shape != (vhi - vlo,)):
+            raise ValueError('one label per copied row is needed')
+        check(self.lib.l3_mlp_group_set_data_dev(self.h, train.h, int(lo), int(hi), _ptr(yt), None if yv is None else valid.h,
+                                                 int(vlo), int(vhi), _ptr(yv)))
+        self.n_train, self.n_valid = int(hi - lo), 0 if yv is None else int(vhi - vlo)
+
+    def epoch(self, perm, lrs, t0, live=None):
+        """One epoch of the live members (live: one flag per member; None: all) -> one dict(loss, acc, val_loss, val_acc) per
+        member, as MLP.epoch gives it; every value of a member that is not live is NaN."""
+        p = _i32(perm)
+        if p.shape != (self.n_train,):
+            raise ValueError('perm must have n_train = %d entries' % self.n_train)
+        lr = np.ascontiguousarray(lrs, dtype=np.float32)
+        lv = np.ones(self.n_members, np.int32) if live is None else np.ascontiguousarray(np.asarray(live, bool), dtype=np.int32)
+        if lr.shape != (self.n_members,) or lv.shape != (self.n_members,):
+            raise ValueError('one learning rate and one live flag per member are needed')
+        st = np.empty((self.n_members, 4), np.float64)
+        check(self.lib.l3_mlp_group_epoch(self.h, _ptr(p), _ptr(lr), _ptr(lv), int(t0), _ptr(st)))
+        return [dict(loss=float(s[0]), acc=float(s[1]), val_loss=float(s[2]), val_acc=float(s[3])) for s in st]
+
+    @staticmethod
+    def _mask(members):
+        mask = 0
+        for i in members:
+            if not 0 <= int(i) < 32:
+                raise ValueError('no member %r' % (i,))
+            mask |= 1 << int(i)
+        return mask
+
+    def keep_best(self, members):
+        """snapshot the weights of `members` (indices) on the device, each into its own slot"""
+        check(self.lib.l3_mlp_group_keep_best(self.h, self._mask(members)))
+
+    def restore_best(self, members):
+        """the weights of `members` back from their slots"""
+        check(self.lib.l3_mlp_group_restore_best(self.h, self._mask(members)))
+
+    def predict(self, X):
+        """-> (n_members, n, C): MLP.predict of every member in one pass"""
+        x = _f32(X)
+        out = np.empty((self.n_members, x.shape[0], self.C), np.float32)
+        if x.shape[0]:
+            check(self.lib.l3_mlp_group_predict(self.h, _ptr(x), x.shape[0], _ptr(out)))
+        return out
+
+    def predict_dev(self, feat, lo=0, hi=None):
+        """-> (n_members, hi - lo, C): MLP.predict_dev of every member in one pass"""
+        hi = feat.shape[0] if hi is None else hi
+        out = np.empty((self.n_members, max(0, hi - lo), self.C), np.float32)
+        if hi > lo:
+            check(self.lib.l3_mlp_group_predict_dev(self.h, feat.h, int(lo), int(hi), _ptr(out)))
+        return out
+
+    def predict_resident(self, valid=False):
+        """-> (n_members, n, C) of the rows set_data left on the device: the training rows, or with `valid` the validation rows"""
+        out = np.empty((self.n_members, self.n_valid if valid else self.n_train, self.C), np.float32)
+        check(self.lib.l3_mlp_group_predict_resident(self.h, int(bool(valid)), _ptr(out)))
         return out
 
 

@@ -26,12 +26,18 @@ it.  Deviations from the reference, all deliberate:
     cross-validation fold permutation from np.random.RandomState(random_state) as the MLP's shuffle does (libsvm uses rand()),
     and the model is pickled with `pickle` (the reference uses joblib).  train() still runs only the MLP; train_svm_fold is
     the reference's train(model_type='svm'), and train_svm_search its parameter search over C with the whole grid fitted in
-    one pass on the GPU (svm.fit_grid).
+    one pass on the GPU (svm.fit_grid);
+  * train_mlp_search / train_mlp_search_fold are the MLP's parameter search over learning rate and weight decay
+    (classifier/train.py:638-651; MLP_SEARCH_SPACE) with the grid fitted as one group of models on the GPU (fit_mlp_grid over an
+    _lib.MLPGroup: the rows resident once, every live point in the same seven launches per step, train_mlp's checkpoint and
+    early-stopping rules per point): every metric, history, search record, the chosen point, the returned weights and
+    history_csvlog.csv equal the loop of train_mlp over the grid bit for bit.  model_dir/model.h5 holds the returned model there
+    (the loop leaves the checkpoint of the run it made last).  train(parameter_search=True) and cross_validate still run the loop.
 
 How the file is put together: train, train_svm_fold, train_rf_fold and cross_validate pass their arguments, by name in one dict, to
 one fold driver (_run_fold), and the model types differ in one function each (_mlp_part, _svm_part, _rf_part; train_rf_search_fold
-hands the driver its own, _rf_search_part).  train_param_search, train_svm_search and train_rf_search are one search body (_search)
-with three ways to fit the grid.  A usc.DeviceFeatures is closed by whoever made it, through _closing: the
+and train_mlp_search_fold hand the driver their own, _rf_search_part and _mlp_search_part).  train_param_search, train_svm_search,
+train_rf_search and train_mlp_search are one search body (_search) with four ways to fit the grid.  A usc.DeviceFeatures is closed by whoever made it, through _closing: the
 driver closes the fold's splits, a search the parts of its cut and its merged matrix, and nobody what a caller passed in.
 """
 import contextlib
@@ -662,6 +668,173 @@ def train_rf_search(train_data, valid_data, test_data, model_dir, n_estimators_g
     return outcome
 
 
+MLP_SEARCH_SPACE = {'learning_rate': [1e-5, 1e-4, 1e-3], 'weight_decay': [1e-5, 1e-4, 1e-3]}        # classifier/train.py:638-651
+
+
+class _GroupMember(object):
+    """What train_mlp's callbacks see of a model, for one member of an _lib.MLPGroup: stop_training, and save_weights, which
+    snapshots the member's weights on the device (ModelCheckpoint's file is written once, at the end, for the returned model)."""
+
+    def __init__(self, group, index, patience, verbose):
+        self.group, self.index = group, index
+        self.stop_training = False
+        self.logs = []          # one dict per epoch the member ran
+        self.series = MetricCallback(verbose=verbose)
+        # train_mlp's callbacks that decide something, in its order; the two that only write files are replayed afterwards
+        self.hooks = [callbacks.ModelCheckpoint('', monitor='val_loss', save_best_only=True, save_weights_only=True),
+                      EarlyStopping(monitor='val_loss', patience=patience), self.series]
+        for cb in self.hooks:
+            cb.set_model(self)
+            cb.on_train_begin()
+
+    def save_weights(self, filepath, overwrite=True):
+        self.group.keep_best([self.index])
+
+    def epoch_end(self, epoch, logs):
+        self.logs.append(logs)
+        for cb in self.hooks:
+            cb.on_epoch_end(epoch, dict(logs))
+
+
+def fit_mlp_grid(train_data, valid_data, test_data, model_dir, points, batch_size=64, num_epochs=100, valid_split=0.15, patience=20,
+                 num_classes=10, random_state=12345678, verbose=False):
+    """train_mlp at every (learning_rate, weight_decay) of `points`, fitted together as one _lib.MLPGroup (at most
+    _lib.MLP_MAX_MEMBERS points at a time) -> [(model, train_metrics, valid_metrics, test_metrics)], one per point, each what
+    train_mlp returns for that point, bit for bit.
+
+    train_mlp seeds the Glorot draw and the epoch shuffle from random_state at every point, so the members start from the same
+    weights and take the same rows at every step; they differ in the rate, the weight decay and the epoch at which early stopping
+    ends them.  The rows are resident once (NumPy rows are uploaded once, a usc.DeviceFeatures is copied on its device); an epoch's
+    step is seven launches for all live members.  Per member and in train_mlp's order: ModelCheckpoint's rule (a device snapshot
+    when val_loss improves: strict <, so the first minimum), EarlyStopping, the metric series; a member that stops leaves the live
+    set from the next epoch.  The validation rows are valid_data, or without it the last valid_split of the training rows, as
+    MLPModel.fit slices them.  Every member is scored on the resident rows and, in one pass, on the test rows.
+    In model_dir: history_csvlog.csv gets the rows train_mlp's CSVLogger appends, point by point in the order of `points`, and
+    history_checkpoint.pkl is the last point's; model.h5 is left to the caller.  Each model is an MLPModel holding the point's
+    best weights (no optimizer state)."""
+    points = [(float(lr), float(wd)) for lr, wd in points]
+    features, labels = train_data['features'], np.asarray(train_data['labels']).reshape(-1).astype(np.int32)
+    on_device = isinstance(features, DeviceFeatures)
+    if not on_device:
+        features = np.asarray(features, np.float32)
+    n_train, held_out = len(features), None
+    if valid_data:
+        held_out = valid_data['features']
+        if not isinstance(held_out, DeviceFeatures):
+            held_out = np.asarray(held_out, np.float32)
+            if on_device:
+                raise ValueError('the validation rows must be where the training rows are: a usc.DeviceFeatures')
+        elif not on_device:
+            raise ValueError('the validation rows must be where the training rows are: NumPy rows')
+        valid_labels = np.asarray(valid_data['labels']).reshape(-1).astype(np.int32)
+    elif valid_split and 0.0 < valid_split < 1.0:
+        n_train = int(len(features) * (1.0 - valid_split))
+        valid_labels = labels[n_train:]
+    else:
+        raise ValueError('the grid needs validation rows (early stopping and the checkpoint follow val_loss): valid_data, or a '
+                         'valid_split in (0, 1)')
+    targets = one_hot(labels, num_classes)
+    steps = -(-n_train // int(batch_size))
+    results = []
+    for first in range(0, len(points), _lib.MLP_MAX_MEMBERS):
+        chunk = points[first:first + _lib.MLP_MAX_MEMBERS]
+        lrs = [lr for lr, _ in chunk]
+        group = _lib.MLPGroup(features.shape[1], num_classes, int(batch_size), [wd for _, wd in chunk], [random_state] * len(chunk),
+                              device=features.device if on_device else 0)
+        try:
+            if on_device:
+                vx, vlo, vhi = (held_out, 0, len(held_out)) if held_out is not None else (features, n_train, len(features))
+                group.set_data_dev(features.handle, 0, n_train, labels[:n_train], vx.handle, vlo, vhi, valid_labels)
+            else:
+                group.set_data(features[:n_train], labels[:n_train], held_out if held_out is not None else features[n_train:],
+                               valid_labels)
+            members = [_GroupMember(group, i, patience, verbose) for i in range(len(chunk))]
+            rs = np.random.RandomState(random_state)
+            for epoch in range(int(num_epochs)):
+                live = [not m.stop_training for m in members]
+                if not any(live):
+                    break
+                stats = group.epoch(rs.permutation(n_train), lrs, epoch * steps, live)
+                for m, alive, logs in zip(members, live, stats):
+                    if alive:
+                        m.epoch_end(epoch, logs)
+            # back to every member's lowest-val_loss snapshot, then all of them through each split in one pass
+            group.restore_best(range(len(chunk)))
+            if held_out is not None:
+                on_train, on_valid = group.predict_resident(), group.predict_resident(valid=True)
+            else:          # train_mlp predicts the whole of `features`, the validation tail included, in predict's row blocks
+                on_train, on_valid = group.predict_dev(features.handle) if on_device else group.predict(features), None
+            on_test = None
+            if test_data:
+                tx = test_data['features']
+                on_test = group.predict_dev(tx.handle) if isinstance(tx, DeviceFeatures) else group.predict(tx)
+            for i, ((lr, wd), m) in enumerate(zip(chunk, members)):
+                for cb in (callbacks.LossHistory(os.path.join(model_dir, 'history_checkpoint.pkl')),
+                           callbacks.CSVLogger(os.path.join(model_dir, 'history_csvlog.csv'), separator=',', append=True)):
+                    cb.on_train_begin()
+                    for epoch, logs in enumerate(m.logs):
+                        cb.on_epoch_end(epoch, dict(logs))
+                    cb.on_train_end()
+                best = int(np.argmin(m.series.valid_loss))
+                train_metrics = _series_metrics((m.series.train_loss, m.series.train_acc), best)
+                scored = compute_metrics(targets, on_train[i], num_classes=num_classes)
+                train_metrics['class_accuracy'] = scored['class_accuracy']
+                train_metrics['average_class_accuracy'] = scored['average_class_accuracy']
+                valid_metrics = _series_metrics((m.series.valid_loss, m.series.valid_acc), best)
+                if on_valid is not None:
+                    valid_metrics.update(compute_metrics(one_hot(valid_labels, num_classes), on_valid[i], num_classes=num_classes))
+                test_metrics = {}
+                if test_data:
+                    per_file = _file_predictions(on_test[i], test_data['file_idxs'])
+                    test_metrics = compute_metrics(test_data['labels'], per_file, num_classes=num_classes)
+                model, _, _ = construct_mlp_model(features.shape[1:], weight_decay=wd, num_classes=num_classes, seed=random_state)
+                model.compile(lr=lr)
+                model.set_weights(group.get_weights(i))
+                results.append((model, train_metrics, valid_metrics, test_metrics))
+        finally:
+            group.close()
+    return results
+
+
+def train_mlp_search(train_data, valid_data, test_data, model_dir, search_space=MLP_SEARCH_SPACE, train_with_valid=True,
+                     valid_ratio=0.15, split_random_state=None, batch_size=64, num_epochs=100, valid_split=0.15, patience=20,
+                     num_classes=10, random_state=12345678, verbose=False, **kwargs):
+    """train_param_search(..., train_func=train_mlp, search_space=search_space) with the grid fitted as one group of models on the
+    GPU (fit_mlp_grid: one resident copy of the rows, seven launches per step for all live points, every point scored on the
+    resident rows): every metric, history and search record, the chosen point and the returned weights equal the loop's bit for
+    bit.  search_space: values for 'learning_rate' and 'weight_decay', the grid being their product in key order.  The splits'
+    features are NumPy rows or usc.DeviceFeatures (kept on their device).  With train_with_valid the chosen point is refitted by a
+    plain train_mlp, as train_param_search refits it; without a validation fold (valid_data None) the search runs on
+    train_param_search's cut (valid_ratio, split_random_state; None refuses, NO_SSS).  -> (model, train_metrics, valid_metrics,
+    test_metrics); model is an MLPModel with the chosen point's best weights.  In model_dir history_csvlog.csv and
+    history_checkpoint.pkl are what the loop leaves; model.h5 holds the returned model (the loop over train_mlp leaves the
+    checkpoint of the run it made last).  learning_rate and weight_decay among kwargs are ignored (the search sets them), and so
+    is the rest, as train_mlp ignores it."""
+    names = list(search_space)
+    if sorted(names) != ['learning_rate', 'weight_decay']:
+        raise ValueError('the MLP\'s grid is over learning_rate and weight_decay, not %r' % (names,))
+    grid = list(product(*(search_space[n] for n in names)))
+    at = {n: names.index(n) for n in names}
+    args = dict(batch_size=batch_size, num_epochs=num_epochs, valid_split=valid_split, patience=patience, num_classes=num_classes,
+                random_state=random_state, verbose=verbose)
+
+    def run_grid(search_train, search_valid):
+        LOGGER.info('Fitting the grid %s as one group of %d models', dict(search_space), len(grid))
+        fitted = fit_mlp_grid(search_train, search_valid, test_data, model_dir,
+                              [(p[at['learning_rate']], p[at['weight_decay']]) for p in grid], **args)
+        return [(point,) + run for point, run in zip(grid, fitted)]
+
+    def refit(point, data):
+        model, train_metrics, _, test_metrics = train_mlp(data, None, test_data, model_dir, learning_rate=point[at['learning_rate']],
+                                                          weight_decay=point[at['weight_decay']], **args)
+        return model, train_metrics, test_metrics
+
+    outcome = _search(train_data, valid_data, names, valid_ratio, split_random_state, train_with_valid, run_grid, refit)
+    LOGGER.info('Saving model...')
+    outcome[0].save_weights(os.path.join(model_dir, 'model.h5'))
+    return outcome
+
+
 # ---- one cross-validation fold ------------------------------------------------------------------------------------------------------
 def _dataset_of(features_dir):
     """'.../features/us8k/l3/...' -> ('us8k', 'us8k/l3/...'): the path after the last 'features/' and its first part, a dataset"""
@@ -746,13 +919,22 @@ def _mlp_part(splits, model_dir, fold):
                      num_classes=fold['num_classes'], verbose=fold['verbose']), **fold['model_args'])
     if not fold['parameter_search']:
         return train_mlp(*splits, model_dir, **args)
-    grid = {'learning_rate': [1e-5, 1e-4, 1e-3], 'weight_decay': [1e-5, 1e-4, 1e-3]}
     if not fold['search_on_cut']:          # with a validation fold: one download; the search then runs as on the host
         splits = tuple(_on_host(d) for d in splits)
     # on a cut the splits stay where they are: train_mlp takes DeviceFeatures as it does without a search
-    return train_param_search(*splits, model_dir, train_func=train_mlp, search_space=grid, valid_ratio=fold['parameter_search_valid_ratio'],
+    return train_param_search(*splits, model_dir, train_func=train_mlp, search_space=MLP_SEARCH_SPACE, valid_ratio=fold['parameter_search_valid_ratio'],
                               train_with_valid=fold['parameter_search_train_with_valid'],
                               split_random_state=fold['parameter_search_split_seed'], **args)
+
+
+def _mlp_search_part(splits, model_dir, fold):
+    """the part of a fold that searches the MLP's learning rate and weight decay as one group of models -> (model, train_metrics,
+    valid_metrics, test_metrics): train_mlp_search on the validation fold or on a cut, the splits staying where they are"""
+    args = dict(dict(batch_size=fold['train_batch_size'], patience=fold['patience'], random_state=fold['random_state'],
+                     num_classes=fold['num_classes'], verbose=fold['verbose']), **fold['model_args'])
+    return train_mlp_search(*splits, model_dir, valid_ratio=fold['parameter_search_valid_ratio'],
+                            train_with_valid=fold['parameter_search_train_with_valid'],
+                            split_random_state=fold['parameter_search_split_seed'], **args)
 
 
 def _svm_part(splits, model_dir, fold):
@@ -848,6 +1030,20 @@ def train_rf_search_fold(features_dir, output_dir, fold_num, feature_mode='frame
     fold = dict(locals(), model_type='rf', parameter_search=True, model_part=_rf_search_part)          # the fold's settings by name
     fold['model_args'] = dict(model_args, n_estimators_grid=_rf_grid(fold.pop('n_estimators_grid')))
     return _run_fold(fold)
+
+
+def train_mlp_search_fold(features_dir, output_dir, fold_num, feature_mode='framewise', train_batch_size=64, patience=20,
+                          random_state=20171021, parameter_search_valid_fold=True, parameter_search_valid_ratio=0.15,
+                          parameter_search_train_with_valid=False, gsheet_id=None, google_dev_app_name=None, verbose=False,
+                          non_overlap=False, non_overlap_chunk_size=10, use_min_max=False, preprocess_device=None,
+                          parameter_search_split_seed=None, **model_args):
+    """classifier/train.py:495-709 for model_type='mlp' with parameter_search (:638-651): train(parameter_search=True)'s fold,
+    directory (.../mlp/fold<N>/<timestamp>/), seven files and config.json keys, the model chosen by train_mlp_search: the grid over
+    learning rate and weight decay (MLP_SEARCH_SPACE) fitted as one group of models on the GPU, on the validation fold, or with
+    parameter_search_valid_fold=False on a stratified cut seeded by parameter_search_split_seed (None refuses, NO_SSS).  With
+    preprocess_device the splits stay on that GPU through the search.  model_args: train_mlp's (num_epochs, ...; learning_rate and
+    weight_decay are recorded and then set by the search).  model.h5 holds the returned model.  -> that directory."""
+    return _run_fold(dict(locals(), model_type='mlp', parameter_search=True, model_part=_mlp_search_part))      # the settings by name
 
 
 # what a fold's metrics hold besides numbers and lists of numbers with one entry per class: the per-epoch histories (their length

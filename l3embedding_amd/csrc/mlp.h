@@ -13,6 +13,29 @@ constexpr int MLP_MAX_BATCH = 4096;
 constexpr int64_t MLP_PART_FLOATS = 4 << 20;   // split-K partial buffer (16 MiB)
 constexpr int MLP_FWD_COUNTERS = 4096;         // one per output tile of a split-K forward launch
 
+// ---- the member dimension ---------------------------------------------------------------------------------------------------------
+// Every kernel of the step runs a group of models of one shape per launch: block row y (blockIdx.y) works on member
+// (ids >> 4y) & 15, so `ids` is a table of up to MLP_MAX_MEMBERS member numbers, four bits each, in any order and with holes (the
+// live members of a parameter search).  A member's pointer is the launch's pointer + member * its stride, in elements; a stride of
+// 0 shares the buffer (the features, the labels, the permutation).  A member's tiles, split count, sums and counters are those of
+// the launch's shape alone: what the other block rows do does not enter its result.  The launchers without a member argument run
+// one member with every stride 0 (MLP_ONE_MEMBER): the same kernels.
+constexpr int MLP_MAX_MEMBERS = 16;
+struct MlpMembers { uint64_t ids; int n; };
+constexpr MlpMembers MLP_ONE_MEMBER{0, 1};
+__host__ __device__ inline int mlp_member(const MlpMembers& m, int y) { return (int)((m.ids >> (4 * y)) & 15); }
+struct MlpFwdStride { int64_t x, w, b, y, part, ctr; };
+struct MlpBwdStride { int64_t dy, w, h, dx; };
+struct MlpCeStride { int64_t z, probs, dz, ce; };          // ce: of ce and of correct
+// x, dy: per layer; p: of w, b and the four moments (one arena per member); ce: of ce and correct (acc: 2 doubles per member).
+// par: MLP_MEMBER_PARS floats per member, {lr, wd, 2 wd} (null: the launch's lr_t, wd, l2x2); lr_t = lr * lr_scale.
+constexpr int MLP_MEMBER_PARS = 4;
+struct MlpWgStride {
+    int64_t x[3], dy[3], p, w2part, ctr, ce;
+    const float* par;
+    float lr_scale;
+};
+
 // Y = act(X[idx] . W + b): X (rows of ldx floats; row r of the product is X row idx[r], or r when idx is null), W (K, N) row major.
 // Split-K over `part` (MLP_PART_FLOATS) when the output has too few 32x32 tiles to fill the GPU; the last wave to finish a tile sums
 // its partials in split order and applies the epilogue.  ctr: MLP_FWD_COUNTERS ints, zero between launches (the last wave resets).
@@ -51,5 +74,14 @@ struct MlpWgrad {
 };
 int mlp_wgrad_tiles(const MlpWgrad& a);        // waves of the launch = floats of w2part
 void mlp_wgrad(const MlpWgrad& a, float* w2part, int* ctr, hipStream_t s);
+
+// The four launches over the members `mem` of a group (above): the arguments are member 0's, the strides lead to the others'.
+void mlp_dense_fwd_members(const float* x, const int* idx, int64_t ldx, const float* w, const float* b, float* y, int rows, int K,
+                           int N, int relu, float* part, int* ctr, const MlpMembers& mem, const MlpFwdStride& stride, hipStream_t s);
+void mlp_dense_bwd_x_members(const float* dy, const float* w, const float* h, float* dx, int rows, int K, int N,
+                             const MlpMembers& mem, const MlpBwdStride& stride, hipStream_t s);
+void mlp_softmax_ce_members(const float* z, const int* labels, const int* idx, int rows, int C, float gscale, float* probs, float* dz,
+                            float* ce, float* correct, const MlpMembers& mem, const MlpCeStride& stride, hipStream_t s);
+void mlp_wgrad_members(const MlpWgrad& a, float* w2part, int* ctr, const MlpMembers& mem, const MlpWgStride& stride, hipStream_t s);
 
 }  // namespace l3

@@ -3,7 +3,16 @@
 the validation pass) against the same training step in torch on the CPU (16 threads), timed over --cpu-steps steps and scaled to
 an epoch.  One JSON line per width.  Per-kernel times: run a short configuration under `rocprofv3 --kernel-trace --stats`.
 
+--group N (record profiles/r24_mlp_group.txt) times instead, per width and alternating --reps times after a warm-up
+of each: one epoch of an N-member group (l3_mlp_group_epoch, members with the rates and weight decays of the reference's grid)
+and N epochs of the single model one after the other, which is what the loop over the grid runs.  --search-epochs E adds the whole
+search on the same set as one fold (the validation rows as the validation fold and, in files of 28 frames, as the test fold):
+classifier.train_mlp_search against train_param_search(train_func=train_mlp), E epochs per point with patience E, the results
+compared for equality.  On a checkout without the group handle only the single model and the loop are timed, so the same file
+measures an earlier commit.
+
     python scripts/classifier_throughput.py [--widths 512 6144] [--epochs 2] [--cpu-steps 200]
+    python scripts/classifier_throughput.py --group 9 --reps 3 --search-epochs 10 --cpu-steps 0
 """
 import argparse
 import json
@@ -50,6 +59,78 @@ def cpu_epoch_seconds(X, y, Xv, C, batch, steps, threads, lr=1e-4, wd=1e-5):
     return per_step, val
 
 
+GRID = [(lr, wd) for lr in (1e-5, 1e-4, 1e-3) for wd in (1e-5, 1e-4, 1e-3)]          # classifier/train.py:638-651
+
+
+def group_against_singles(a, D, X, y, Xv, yv, rs):
+    """--group: one group epoch against a.group single-model epochs -> the fields of the width's JSON line"""
+    steps = -(-a.n_train // a.batch)
+    points = [GRID[i % len(GRID)] for i in range(a.group)]
+    single = _lib.MLP(D, a.classes, a.batch, weight_decay=points[0][1], seed=0)
+    single.set_data(X, y, Xv, yv)
+    group = None
+    if hasattr(_lib, 'MLPGroup'):
+        group = _lib.MLPGroup(D, a.classes, a.batch, [wd for _, wd in points], [0] * a.group)
+        group.set_data(X, y, Xv, yv)
+    group_s, singles_s, epoch = [], [], 0
+    for rep in range(a.reps + 1):          # rep 0 warms up both
+        perm = rs.permutation(a.n_train)
+        if group is not None:
+            t = time.perf_counter()
+            group.epoch(perm, [lr for lr, _ in points], epoch * steps)
+            group_s.append(time.perf_counter() - t)
+        t = time.perf_counter()
+        for k in range(1 if rep == 0 else a.group):
+            single.epoch(perm, points[k][0], (epoch + k) * steps)
+        singles_s.append(time.perf_counter() - t)
+        epoch += a.group
+    single.close()
+    rec = dict(members=a.group, singles_epochs_s=[round(x, 4) for x in singles_s[1:]],
+               single_step_us=round(1e6 * min(singles_s[1:]) / (a.group * steps), 2))
+    if group is not None:
+        group.close()
+        rec.update(group_epoch_s=[round(x, 4) for x in group_s[1:]], group_step_us=round(1e6 * min(group_s[1:]) / steps, 2),
+                   singles_over_group=round(min(singles_s[1:]) / min(group_s[1:]), 2))
+    return rec
+
+
+def search_against_loop(a, X, y, Xv, yv):
+    """--search-epochs: the whole nine-point search as one group and as the loop -> the fields of a JSON line"""
+    import shutil
+    import tempfile
+    from l3embedding_amd import classifier
+    frames = 28
+    files = len(Xv) // frames
+    train, valid = {'features': X, 'labels': y}, {'features': Xv, 'labels': yv}
+    test = {'features': Xv[:files * frames], 'labels': yv[:files * frames:frames],
+            'file_idxs': [(i * frames, (i + 1) * frames) for i in range(files)]}
+    args = dict(batch_size=a.batch, num_epochs=a.search_epochs, patience=a.search_epochs, num_classes=a.classes, random_state=1,
+                train_with_valid=False)
+    grid = {'learning_rate': [1e-5, 1e-4, 1e-3], 'weight_decay': [1e-5, 1e-4, 1e-3]}
+    routes = {'loop': lambda d: classifier.train_param_search(train, valid, test, d, train_func=classifier.train_mlp,
+                                                              search_space=grid, **args)}
+    if hasattr(classifier, 'train_mlp_search'):
+        routes['group'] = lambda d: classifier.train_mlp_search(train, valid, test, d, search_space=grid, **args)
+    wall, outcome = {}, {}
+    for rep in range(a.reps):
+        for name, run in routes.items():
+            d = tempfile.mkdtemp(prefix='mlp_search_')
+            try:
+                t = time.perf_counter()
+                outcome[name] = run(d)
+                wall.setdefault(name, []).append(round(time.perf_counter() - t, 3))
+            finally:
+                shutil.rmtree(d, ignore_errors=True)
+    rec = dict(part='search', epochs_per_point=a.search_epochs, points=9, wall_s=wall,
+               chosen=list(outcome['loop'][1]['search_params_best_values']))
+    if 'group' in outcome:
+        same = all(np.array_equal(g, w) for g, w in zip(outcome['group'][0].get_weights(), outcome['loop'][0].get_weights()))
+        same = same and all(outcome['group'][k]['search'][p]['loss_history'] == outcome['loop'][k]['search'][p]['loss_history']
+                            for k in (1, 2) for p in outcome['loop'][k]['search'])
+        rec.update(equal_weights_and_histories=bool(same), loop_over_group=round(min(wall['loop']) / min(wall['group']), 2))
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--widths', type=int, nargs='+', default=[512, 6144])
@@ -60,6 +141,9 @@ def main():
     ap.add_argument('--epochs', type=int, default=2)
     ap.add_argument('--cpu-steps', type=int, default=200, help='0: no torch-CPU baseline')
     ap.add_argument('--threads', type=int, default=16)
+    ap.add_argument('--group', type=int, default=0, help='N > 0: an N-member group epoch against N single-model epochs')
+    ap.add_argument('--reps', type=int, default=3, help='--group / --search-epochs: timed repetitions, alternating')
+    ap.add_argument('--search-epochs', type=int, default=0, help='E > 0: the whole search, E epochs per point, group against loop')
     a = ap.parse_args()
     for D in a.widths:
         gen, rs = np.random.default_rng(D), np.random.RandomState(D)
@@ -67,6 +151,14 @@ def main():
         y = rs.randint(0, a.classes, a.n_train).astype(np.int32)
         Xv = gen.standard_normal((a.n_valid, D), dtype=np.float32)
         yv = rs.randint(0, a.classes, a.n_valid).astype(np.int32)
+        if a.group or a.search_epochs:
+            rec = dict(D=D, C=a.classes, batch=a.batch, n_train=a.n_train, n_valid=a.n_valid, steps_per_epoch=-(-a.n_train // a.batch))
+            if a.group:
+                print(json.dumps(dict(rec, **group_against_singles(a, D, X, y, Xv, yv, rs))), flush=True)
+            if a.search_epochs:
+                print(json.dumps(dict(rec, **search_against_loop(a, X, y, Xv, yv))), flush=True)
+            del X, Xv
+            continue
         m = _lib.MLP(D, a.classes, a.batch, weight_decay=1e-5, seed=0)
         t = time.perf_counter()
         m.set_data(X, y, Xv, yv)
