@@ -201,6 +201,42 @@ int l3_step_results_enqueue(l3_engine *e, int slot, int reduce);   /* reduce = 1
                                                                        training_utils.py:165-170; every rank must call it */
 int l3_step_results_wait(l3_engine *e, int slot, float *loss, float *acc);
 
+/* Serial replicas -- multi_gpu_model on ONE GPU, training_utils.py:121-170.  The reference cuts the fed batch into `gpus` slices
+ * (:121-133), calls the one template model on each (:141-157: each replica normalises with its own batch statistics and adds its
+ * own moving-average update to the shared BatchNormalization variables) and adds the replicas' gradients (:165-170).  Nothing makes
+ * the replicas run at the same time: an engine created like a data-parallel rank's -- batch = B, the slice; global_batch = R * B --
+ * works through the R slices of a resident global batch one after another, so the activations are those of one slice and a step
+ * of R * B pairs fits where a step of B pairs fits.  The result is l3_step_dp's over R ranks, bit for bit: the gradient arena holds
+ * ((g0 + g1) + g2) + ... in replica order (fp32 addition does not associate: the order is part of the contract), the moving
+ * statistics receive the R updates in replica order, Adam runs once.
+ *   l3_replicas_upload          float global batch: video (R*B,224,224,3), audio (R*B,1,48000), labels (R*B,2); kept on the device
+ *   l3_replicas_upload_raw      the stored dtypes (uint8 frames, int16 PCM, int32 labels); slice r is scaled by the kernels of
+ *                               l3_upload_batch_raw from rows [rB, (r+1)B) of the resident raw batch when its turn comes
+ *   l3_replicas_upload_raw_aug  ... augmented by the kernels of l3_upload_batch_raw_aug: R*B records and R*B gain draws
+ *   l3_replicas_stage_raw(_aug) the NEXT global batch over the copy stream while a step runs; the next l3_step_replicas /
+ *                               l3_eval_replicas adopts it (as l3_stage_batch_raw); an explicit upload supersedes it
+ *   l3_step_replicas            for r = 0 .. R-1: slice r -> training forward, loss, every backward bucket (the towers overlap as in
+ *                               l3_step_resident) -> the slice's BatchNorm batch statistics into slot r of the replica buffer, its
+ *                               loss / accuracy sums and its gradient arena folded into accumulators; then ONE l3_step_update:
+ *                               one Adam step, R moving-average updates (l3_optimizer_steps moves by (1, R)).  One global step
+ *                               counts once against the two-steps-in-flight bound of l3_step_forward.
+ *   l3_eval_replicas            test_on_batch of the resident global batch (inference-mode BatchNorm), slice by slice
+ * After either, l3_step_results / l3_step_results_enqueue(slot, 0) + _wait give the loss (L2 term included) and accuracy of the
+ * concatenated batch -- the sums over the slices divided by global_batch; probs / logits are refused (L3_ESTATE: the engine holds
+ * one slice's).  Refused, with the numbers in l3_last_error: replicas < 1 (L3_EINVAL); global_batch != replicas * batch
+ * (L3_EINVAL); no resident global batch (L3_ESTATE); l3_config.dp_moving == L3_DP_MOVING_RANK_LOCAL (L3_ESTATE: one update per
+ * step is not what R replicas apply); an engine that holds a communicator (L3_ESTATE: l3_step_dp is its step).  The resident
+ * buffers grow on demand and are freed with the engine. */
+int l3_replicas_upload(l3_engine *e, const float *video, const float *audio, const float *labels, int replicas);
+int l3_replicas_upload_raw(l3_engine *e, const uint8_t *video_u8, const int16_t *audio_i16, const int32_t *labels_i32, int replicas);
+int l3_replicas_upload_raw_aug(l3_engine *e, const uint8_t *video_u8, const int16_t *audio_i16, const int32_t *labels_i32,
+                               const l3_augment_params *params, const double *u, int replicas);
+int l3_replicas_stage_raw(l3_engine *e, const uint8_t *video_u8, const int16_t *audio_i16, const int32_t *labels_i32, int replicas);
+int l3_replicas_stage_raw_aug(l3_engine *e, const uint8_t *video_u8, const int16_t *audio_i16, const int32_t *labels_i32,
+                              const l3_augment_params *params, const double *u, int replicas);
+int l3_step_replicas(l3_engine *e, float lr);
+int l3_eval_replicas(l3_engine *e, float *loss, float *acc);
+
 /* Data parallelism -- multi_gpu_model, training_utils.py:21-170, reached through gpu_wrapper
  * (model.py:184-195).  One process per GPU; every rank owns an engine created with batch = its shard
  * (training_utils.py:121-133) and global_batch = the batch over all ranks.  The reference's implicit
@@ -448,6 +484,11 @@ int l3_op_adam(int device, float *p, const float *g, float *m, float *v, int64_t
  * term; l3_step_update's grad_scale). */
 int l3_op_adam_scaled(int device, float *p, const float *g, float *m, float *v, int64_t n, int64_t n_l2, float l2x2, float lr_t,
                       float b1, float b2, float eps, float gscale);
+/* The arena fold of l3_step_replicas (the replicas' gradient sum, training_utils.py:165-170) on its own: acc and g are two host
+ * arenas of `total` floats (in/out); the fold runs on the elements [off, off + n) of both and leaves every other element as it
+ * was.  mode 0: acc = g; 1: acc = acc + g; 2: g = acc + g.  Each sum is one IEEE fp32 addition (NumPy float32 a + b, subnormals
+ * kept).  L3_EINVAL for a NULL pointer, a range outside the arenas or another mode. */
+int l3_op_arena_fold(int device, float *acc, float *g, int64_t total, int64_t off, int64_t n, int mode);
 
 /* Operators of the engine's head, loss and update on their own (host buffers; parity tests).  Each runs the launcher the engine
  * calls.  y (B, N) = x (B, K) . w (K, N) + b, ReLU when relu != 0.  L3_EINVAL when the launch's dynamic LDS, (K + 8 N) * 4 bytes,

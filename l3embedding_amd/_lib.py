@@ -88,6 +88,14 @@ SIGNATURES = {
     'l3_step_backward_bucket': (C.c_int, [C.c_void_p, C.c_int]),
     'l3_step_update': (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
     'l3_step_resident': (C.c_int, [C.c_void_p, C.c_float]),
+    # serial replicas: multi_gpu_model's replicas one after another on one engine (csrc/engine.hip)
+    'l3_replicas_upload': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    'l3_replicas_upload_raw': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    'l3_replicas_stage_raw': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    'l3_replicas_upload_raw_aug': (C.c_int, [C.c_void_p] * 6 + [C.c_int]),
+    'l3_replicas_stage_raw_aug': (C.c_int, [C.c_void_p] * 6 + [C.c_int]),
+    'l3_step_replicas': (C.c_int, [C.c_void_p, C.c_float]),
+    'l3_eval_replicas': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     'l3_step_results': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
     'l3_step_results_enqueue': (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     'l3_step_results_wait': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -158,6 +166,7 @@ SIGNATURES = {
     'l3_op_mlp_softmax_ce': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 4),
     'l3_op_adam': (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_float, C.c_float]),
     'l3_op_adam_scaled': (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int64] + [C.c_float] * 6),
+    'l3_op_arena_fold': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int]),
     # head / loss / L2 sums / BatchNorm moving averages on their own (csrc/elementwise.hip)
     'l3_op_head_dense_fwd': (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 4),
     'l3_op_head_dense_bwd': (C.c_int, [C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 3),
@@ -514,6 +523,64 @@ class Engine(object):
 
     def step_resident(self, lr):
         check(self.lib.l3_step_resident(self.h, lr), self.h)
+
+    # -- serial replicas: multi_gpu_model's replicas one after another on this engine (batch = the slice, global_batch = R * batch) --
+    def _replica_rows(self, replicas, *arrays):
+        rows = int(replicas) * self.batch
+        for a in arrays:
+            if len(a) != rows:
+                raise ValueError('%d rows for %d replicas of batch %d (%d rows)' % (len(a), replicas, self.batch, rows))
+
+    def replicas_upload(self, video, audio, labels, replicas):
+        """Float global batch of replicas * batch rows, kept on the device for step_replicas / eval_replicas."""
+        v, a, l = _f32(video), _f32(audio), _f32(labels)
+        self._replica_rows(replicas, v, a, l)
+        check(self.lib.l3_replicas_upload(self.h, _ptr(v), _ptr(a), _ptr(l), int(replicas)), self.h)
+
+    @staticmethod
+    def _raw_args(video_u8, audio_i16, labels_i32):
+        return (np.ascontiguousarray(video_u8, dtype=np.uint8), np.ascontiguousarray(audio_i16, dtype=np.int16),
+                np.ascontiguousarray(labels_i32, dtype=np.int32))
+
+    def _replica_aug_args(self, params, u, replicas):
+        p, g = augment_records(params), np.ascontiguousarray(u, dtype=np.float64)
+        self._replica_rows(replicas, p, g)
+        return p, g
+
+    def replicas_upload_raw(self, video_u8, audio_i16, labels_i32, replicas):
+        """The stored dtypes of a global batch; each slice is scaled by upload_batch_raw's kernels when its turn comes."""
+        v, a, l = self._raw_args(video_u8, audio_i16, labels_i32)
+        self._replica_rows(replicas, v, a, l)
+        check(self.lib.l3_replicas_upload_raw(self.h, _ptr(v), _ptr(a), _ptr(l), int(replicas)), self.h)
+
+    def replicas_stage_raw(self, video_u8, audio_i16, labels_i32, replicas):
+        """Next global batch to the device while the current step runs; adopted by the next step_replicas / eval_replicas."""
+        v, a, l = self._raw_args(video_u8, audio_i16, labels_i32)
+        self._replica_rows(replicas, v, a, l)
+        check(self.lib.l3_replicas_stage_raw(self.h, _ptr(v), _ptr(a), _ptr(l), int(replicas)), self.h)
+
+    def replicas_upload_raw_aug(self, video_u8, audio_i16, labels_i32, params, u, replicas):
+        v, a, l = self._raw_args(video_u8, audio_i16, labels_i32)
+        self._replica_rows(replicas, v, a, l)
+        p, g = self._replica_aug_args(params, u, replicas)
+        check(self.lib.l3_replicas_upload_raw_aug(self.h, _ptr(v), _ptr(a), _ptr(l), _ptr(p), _ptr(g), int(replicas)), self.h)
+
+    def replicas_stage_raw_aug(self, video_u8, audio_i16, labels_i32, params, u, replicas):
+        v, a, l = self._raw_args(video_u8, audio_i16, labels_i32)
+        self._replica_rows(replicas, v, a, l)
+        p, g = self._replica_aug_args(params, u, replicas)
+        check(self.lib.l3_replicas_stage_raw_aug(self.h, _ptr(v), _ptr(a), _ptr(l), _ptr(p), _ptr(g), int(replicas)), self.h)
+
+    def step_replicas(self, lr):
+        """One training step of the resident global batch, slice by slice: the replicas' gradients added in replica order, one
+        moving-average update per replica, one Adam step.  step_results() / results_enqueue() then give the global batch's."""
+        check(self.lib.l3_step_replicas(self.h, lr), self.h)
+
+    def eval_replicas(self):
+        """test_on_batch (inference-mode BatchNorm) of the resident global batch: (loss, acc)."""
+        loss, acc = C.c_float(), C.c_float()
+        check(self.lib.l3_eval_replicas(self.h, C.byref(loss), C.byref(acc)), self.h)
+        return loss.value, acc.value
 
     def step_results(self, want_probs=False):
         loss, acc = C.c_float(), C.c_float()
@@ -1301,6 +1368,15 @@ def op_adam(p, g, m, v, n_l2, l2x2, lr_t, device=0):
     g = _f32(g).ravel()
     check(load().l3_op_adam(device, _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.size, int(n_l2), float(l2x2), float(lr_t)))
     return p, m, v
+
+
+def op_arena_fold(acc, g, off, n, mode, device=0):
+    """The gradient fold of step_replicas on elements [off, off + n) of two arenas: mode 'set' acc = g, 'add' acc += g, 'out'
+    g = acc + g.  Returns the two arenas as the device left them."""
+    a, b = _f32(acc).copy(), _f32(g).copy()
+    assert a.shape == b.shape and a.ndim == 1
+    check(load().l3_op_arena_fold(device, _ptr(a), _ptr(b), a.size, int(off), int(n), {'set': 0, 'add': 1, 'out': 2}[mode]))
+    return a, b
 
 
 def op_adam_scaled(p, g, m, v, n_l2, l2x2, lr_t, b1=0.9, b2=0.999, eps=1e-8, gscale=1.0, device=0):

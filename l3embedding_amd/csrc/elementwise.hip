@@ -12,6 +12,8 @@
 //
 // Channel-wise reductions are two-stage and deterministic: stage 1 writes fp32
 // per-block partials, stage 2 combines them in fp64.
+#include <algorithm>
+
 #include "kernels.h"
 
 namespace l3 {
@@ -982,6 +984,49 @@ __global__ __launch_bounds__(256) void fill_kernel(float* p, float v, int64_t n)
 }
 void fill(float* p, float v, int64_t n, hipStream_t s) {
     hipLaunchKernelGGL(fill_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, p, v, n);
+}
+
+// ---- arena fold: the gradient sum over the replicas of l3_step_replicas (training_utils.py:141-170's AddN, one replica at a time) --
+// One fp32 add per element (never fused with anything: the result is IEEE a + b, subnormals kept), 16 bytes per lane in the body;
+// the up-to-3 elements in front of g's first 16-byte boundary and the up-to-3 behind the last whole float4 go one by one.  acc and g
+// sit at the same element offset of two arenas that are allocated alike, so one head serves both; when they do not share their
+// alignment every element takes the scalar path.  Plain loads and stores: both arenas (19 MB each for the VGG-style models) were
+// just written, are read again by the next fold or by Adam, and fit the last-level cache many times over.
+template <int MODE>
+__global__ __launch_bounds__(256) void arena_fold_kernel(float* __restrict__ acc, float* __restrict__ g, int64_t n, int64_t head) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    const int64_t n4 = (n - head) / 4;
+    float4* a4 = reinterpret_cast<float4*>(acc + head);
+    float4* g4 = reinterpret_cast<float4*>(g + head);
+    for (int64_t i = tid; i < n4; i += stride) {
+        const float4 b = g4[i];
+        if (MODE == ARENA_FOLD_SET) {
+            a4[i] = b;
+        } else {
+            float4 a = a4[i];
+            a.x = a.x + b.x, a.y = a.y + b.y, a.z = a.z + b.z, a.w = a.w + b.w;
+            if (MODE == ARENA_FOLD_ADD) a4[i] = a;
+            else g4[i] = a;
+        }
+    }
+    const int64_t tail0 = head + 4 * n4, edge = head + (n - tail0);
+    for (int64_t i = tid; i < edge; i += stride) {
+        const int64_t j = i < head ? i : tail0 + (i - head);
+        const float b = g[j];
+        if (MODE == ARENA_FOLD_SET) acc[j] = b;
+        else if (MODE == ARENA_FOLD_ADD) acc[j] = acc[j] + b;
+        else g[j] = acc[j] + b;
+    }
+}
+void arena_fold(float* acc, float* g, int64_t n, int mode, hipStream_t s) {
+    if (n <= 0) return;
+    int64_t head = (int64_t)((16 - (reinterpret_cast<uintptr_t>(g) & 15)) & 15) / 4;
+    if (head > n) head = n;
+    if ((reinterpret_cast<uintptr_t>(acc + head) & 15) != 0 || (reinterpret_cast<uintptr_t>(g) & 3) != 0) head = n;
+    const int blocks = std::min(ew_blocks(std::max((n - head) / 4, head + 3)), 2048);
+    if (mode == ARENA_FOLD_SET) hipLaunchKernelGGL(arena_fold_kernel<ARENA_FOLD_SET>, dim3(blocks), dim3(256), 0, s, acc, g, n, head);
+    else if (mode == ARENA_FOLD_ADD) hipLaunchKernelGGL(arena_fold_kernel<ARENA_FOLD_ADD>, dim3(blocks), dim3(256), 0, s, acc, g, n, head);
+    else hipLaunchKernelGGL(arena_fold_kernel<ARENA_FOLD_OUT>, dim3(blocks), dim3(256), 0, s, acc, g, n, head);
 }
 
 // fp32 -> bfloat16 storage (round to nearest even, as v_cvt_pk_bf16_f32 and the BatchNorm/pool writers do)

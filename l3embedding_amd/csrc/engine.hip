@@ -233,6 +233,24 @@ struct l3_engine {
     l3::AugmentParams *aug_params = nullptr, *nxt_aug_params = nullptr;
     double *aug_u = nullptr, *nxt_aug_u = nullptr, *aug_gains = nullptr;
     bool staged_aug = false, gains_valid = false;
+    // serial replicas (l3_replicas_*, l3_step_replicas): the resident global batch of rep_n slices of B rows -- as floats (kind 1) or
+    // in the stored dtypes (kind 2; 3: with augmentation records) --, the set [1] the copy stream fills for the next step beside the
+    // current set [0], and the accumulators of the gradient arena and of the loss / accuracy sums
+    int rep_n = 0, rep_kind = 0, rep_staged_n = 0;
+    bool rep_staged_aug = false, rep_adopted_once = false;
+    float *rep_video = nullptr, *rep_audio = nullptr, *rep_labels = nullptr;
+    size_t rep_video_cap = 0, rep_audio_cap = 0, rep_labels_cap = 0;
+    uint8_t* rep_raw_video[2] = {nullptr, nullptr};
+    int16_t* rep_raw_audio[2] = {nullptr, nullptr};
+    int32_t* rep_raw_labels[2] = {nullptr, nullptr};
+    l3::AugmentParams* rep_aug_params[2] = {nullptr, nullptr};
+    double* rep_aug_u[2] = {nullptr, nullptr};
+    size_t rep_raw_video_cap[2] = {0, 0}, rep_raw_audio_cap[2] = {0, 0}, rep_raw_labels_cap[2] = {0, 0}, rep_aug_params_cap[2] = {0, 0},
+           rep_aug_u_cap[2] = {0, 0};
+    hipEvent_t ev_rep_staged = nullptr, ev_rep_adopted = nullptr;
+    float *rep_acc = nullptr, *rep_stats = nullptr;
+    bool results_global = false;    // e->stats holds the sums over every slice of the global batch (l3_step_replicas, l3_eval_replicas)
+    bool res_global[2] = {false, false};
     // head
     int nv = 0, na = 0, head = 0;
     int p_w1 = -1, p_b1 = -1, p_w2 = -1, p_b2 = -1;
@@ -1542,6 +1560,7 @@ void l2_sums(l3_engine* e) {
 int forward_all(l3_engine* e, bool training) {
     int rc;
     e->fwd_done = false;      // the plans below belong to this pass: no backward of an earlier one may run under them
+    e->results_global = false;
     if ((rc = plan_tower(e, e->vis, training, 0)) || (rc = plan_tower(e, e->aud, training, 0))) return rc;
     if (e->side && e->overlap) {
         HIPCHK(e, hipEventRecord(e->ev_fork, e->stream));
@@ -1641,16 +1660,18 @@ int ensure_bn_table(l3_engine* e) {
 }
 
 // this rank's batch statistics of the training forward just run, packed on the engine's stream; `world` slots for everybody's
-int bn_stats_pack(l3_engine* e, int world) {
+// (slot >= 0: straight into that slot of the buffer of everybody's -- the replica that runs on this engine, l3_step_replicas)
+int bn_stats_pack(l3_engine* e, int world, int slot = -1) {
     int rc = ensure_bn_table(e);
     if (rc) return rc;
     if (e->bn_pack_floats == 0) return L3_OK;
-    if (e->bn_send == nullptr && (rc = dev_alloc_t(e, &e->bn_send, (size_t)e->bn_pack_floats))) return rc;
+    if (slot < 0 && e->bn_send == nullptr && (rc = dev_alloc_t(e, &e->bn_send, (size_t)e->bn_pack_floats))) return rc;
     if (e->bn_gathered_world < world) {
         if ((rc = dev_alloc_t(e, &e->bn_gathered, (size_t)e->bn_pack_floats * world))) return rc;      // (the smaller one stays with e->bufs)
         e->bn_gathered_world = world;
     }
-    bn_moving_pack(e->bn_table, e->bn_table_n, e->bn_table_max_c, e->bn_send, e->stream);
+    bn_moving_pack(e->bn_table, e->bn_table_n, e->bn_table_max_c,
+                   slot < 0 ? e->bn_send : e->bn_gathered + (size_t)slot * e->bn_pack_floats, e->stream);
     return L3_OK;
 }
 
@@ -1694,6 +1715,17 @@ int read_results(l3_engine* e, float* loss, float* acc, float* probs, float* log
     int si = 0;
     for (auto& s : e->segments)
         if (s.l2) reg += (double)L2_WEIGHT * (double)l2[si++];
+    if (e->results_global) {     // sums over the slices of a global batch (l3_step_replicas, l3_eval_replicas)
+        if (probs || logits) {
+            e->err = "probs / logits after a replicas step: the engine holds those of the last slice of " + std::to_string(e->B) +
+                     " rows, not of the global batch of " + std::to_string(e->cfg.global_batch > 0 ? e->cfg.global_batch : e->B);
+            return L3_ESTATE;
+        }
+        const double gb = (double)(e->cfg.global_batch > 0 ? e->cfg.global_batch : e->B);
+        if (loss) *loss = (float)((double)st[0] / gb + reg);
+        if (acc) *acc = (float)((double)st[1] / gb);
+        return L3_OK;
+    }
     if (loss) *loss = (float)((double)st[0] / (double)e->B + reg);
     if (acc) *acc = st[1] / (float)e->B;
     if (probs) HIPCHK(e, hipMemcpy(probs, e->probs, (size_t)e->B * 2 * 4, hipMemcpyDeviceToHost));
@@ -1882,6 +1914,8 @@ void l3_destroy(l3_engine* e) {
     if (e->ev_res_b) (void)hipEventDestroy(e->ev_res_b);
     for (auto ev : e->ev_step)
         if (ev) (void)hipEventDestroy(ev);
+    if (e->ev_rep_staged) (void)hipEventDestroy(e->ev_rep_staged);
+    if (e->ev_rep_adopted) (void)hipEventDestroy(e->ev_rep_adopted);
     if (e->res_host) (void)hipHostFree(e->res_host);
     e->bufs.clear();
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
@@ -2055,12 +2089,12 @@ int l3_upload_batch_raw(l3_engine* e, const uint8_t* video_u8, const int16_t* au
 }
 
 // the device buffers of the augmentation records; the engine's frames are already 224 x 224, so a record must not move the crop
-static int aug_prepare(l3_engine* e, const l3_augment_params* params, const double* u) {
+static int aug_prepare(l3_engine* e, const l3_augment_params* params, const double* u, int rows = 0) {
     if (!params || !u) {
         e->err = "augmented batch without its parameter records or gain draws";
         return L3_EINVAL;
     }
-    for (int i = 0; i < e->B; ++i)
+    for (int i = 0; i < (rows > 0 ? rows : e->B); ++i)
         if (params[i].start_x != 0 || params[i].start_y != 0) {
             e->err = "augmentation record " + std::to_string(i) + ": the engine's frames are 224 x 224, the crop must start at (0, 0)";
             return L3_EINVAL;
@@ -2101,14 +2135,21 @@ int l3_upload_batch_raw_aug(l3_engine* e, const uint8_t* video_u8, const int16_t
     return L3_OK;
 }
 
+// the copy stream of the staged batches (l3_stage_batch_raw*, l3_replicas_stage_raw*) and the events of the former
+static int ensure_copy_stream(l3_engine* e) {
+    if (e->copy_stream) return L3_OK;
+    HIPCHK(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+    HIPCHK(e, hipEventCreateWithFlags(&e->ev_staged, hipEventDisableTiming));
+    HIPCHK(e, hipEventCreateWithFlags(&e->ev_adopted, hipEventDisableTiming));
+    return L3_OK;
+}
+
 static int stage_batch(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
                        const l3_augment_params* params, const double* u) {
     const int B = e->B;
-    if (!e->copy_stream) {
-        HIPCHK(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-        HIPCHK(e, hipEventCreateWithFlags(&e->ev_staged, hipEventDisableTiming));
-        HIPCHK(e, hipEventCreateWithFlags(&e->ev_adopted, hipEventDisableTiming));
-        int rc;
+    int rc = ensure_copy_stream(e);
+    if (rc) return rc;
+    if (!e->nxt_video) {
         if ((rc = dev_alloc_t(e, &e->nxt_video, (size_t)B * 224 * 224 * 3))) return rc;
         if ((rc = dev_alloc_t(e, &e->nxt_audio, (size_t)B * AUDIO_T))) return rc;
         if ((rc = dev_alloc_t(e, &e->nxt_labels, (size_t)B * 2))) return rc;
@@ -2273,6 +2314,234 @@ int l3_step_resident(l3_engine* e, float lr) {
     for (int b = 1; b < nb; ++b)
         if ((rc = l3_step_backward_bucket(e, b))) return rc;
     return l3_step_update(e, lr, 1.0f);
+}
+
+// ---- serial replicas: multi_gpu_model's replicas one after another on this engine (training_utils.py:121-170) -------------------
+// what every l3_replicas_* / l3_*_replicas entry point refuses, with the numbers
+static int rep_refuse(l3_engine* e, const char* name, int replicas) {
+    const int gb = e->cfg.global_batch > 0 ? e->cfg.global_batch : e->B;
+    if (replicas < 1) {
+        e->err = std::string(name) + ": replicas = " + std::to_string(replicas) + ", must be >= 1";
+        return L3_EINVAL;
+    }
+    if ((int64_t)replicas * e->B != gb) {
+        e->err = std::string(name) + ": " + std::to_string(replicas) + " replicas of batch " + std::to_string(e->B) + " are " +
+                 std::to_string((int64_t)replicas * e->B) + " rows, the engine's global_batch is " + std::to_string(gb);
+        return L3_EINVAL;
+    }
+    if (e->cfg.dp_moving == L3_DP_MOVING_RANK_LOCAL) {
+        e->err = std::string(name) + ": dp_moving = L3_DP_MOVING_RANK_LOCAL (1) applies one moving-average update per step, " +
+                 std::to_string(replicas) + " replicas apply " + std::to_string(replicas) + ": create the engine with L3_DP_MOVING_REPLICAS (0)";
+        return L3_ESTATE;
+    }
+    if (e->comm) {
+        e->err = std::string(name) + ": the engine holds a communicator of " + std::to_string(l3::comm_world(e->comm)) +
+                 " ranks; its step is l3_step_dp (l3_comm_destroy first)";
+        return L3_ESTATE;
+    }
+    return L3_OK;
+}
+
+static int rep_grow_raw(l3_engine* e, int set, size_t rows, bool aug) {
+    int rc;
+    if ((rc = dev_grow_t(e, &e->rep_raw_video[set], &e->rep_raw_video_cap[set], rows * 224 * 224 * 3))) return rc;
+    if ((rc = dev_grow_t(e, &e->rep_raw_audio[set], &e->rep_raw_audio_cap[set], rows * AUDIO_T))) return rc;
+    if ((rc = dev_grow_t(e, &e->rep_raw_labels[set], &e->rep_raw_labels_cap[set], rows * 2))) return rc;
+    if (!aug) return L3_OK;
+    if ((rc = dev_grow_t(e, &e->rep_aug_params[set], &e->rep_aug_params_cap[set], rows))) return rc;
+    return dev_grow_t(e, &e->rep_aug_u[set], &e->rep_aug_u_cap[set], rows);
+}
+
+int l3_replicas_upload(l3_engine* e, const float* video, const float* audio, const float* labels, int replicas) {
+    if (!e) return L3_EINVAL;
+    int rc = rep_refuse(e, "l3_replicas_upload", replicas);
+    if (rc) return rc;
+    if (!video || !audio || !labels) {
+        e->err = "l3_replicas_upload: NULL batch pointer";
+        return L3_EINVAL;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    const size_t rows = (size_t)replicas * e->B;
+    if ((rc = dev_grow_t(e, &e->rep_video, &e->rep_video_cap, rows * 224 * 224 * 3))) return rc;
+    if ((rc = dev_grow_t(e, &e->rep_audio, &e->rep_audio_cap, rows * AUDIO_T))) return rc;
+    if ((rc = dev_grow_t(e, &e->rep_labels, &e->rep_labels_cap, rows * 2))) return rc;
+    e->rep_staged_n = 0;        // an explicit upload supersedes a staged global batch
+    e->rep_n = 0;
+    HIPCHK(e, hipMemcpyAsync(e->rep_video, video, rows * 224 * 224 * 3 * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->rep_audio, audio, rows * AUDIO_T * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->rep_labels, labels, rows * 2 * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, l3::stream_wait(e->stream));
+    e->rep_n = replicas;
+    e->rep_kind = 1;
+    return L3_OK;
+}
+
+// the stored dtypes of a global batch into set 0 on the engine's stream (upload) or into set 1 on the copy stream (stage)
+static int rep_send_raw(l3_engine* e, const char* name, bool stage, const uint8_t* video_u8, const int16_t* audio_i16,
+                        const int32_t* labels_i32, const l3_augment_params* params, const double* u, bool aug, int replicas) {
+    if (!e) return L3_EINVAL;
+    int rc = rep_refuse(e, name, replicas);
+    if (rc) return rc;
+    if (!video_u8 || !audio_i16 || !labels_i32) {
+        e->err = std::string(name) + ": NULL batch pointer";
+        return L3_EINVAL;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    const size_t rows = (size_t)replicas * e->B;
+    if (aug && (rc = aug_prepare(e, params, u, (int)rows))) return rc;
+    const int set = stage ? 1 : 0;
+    if ((rc = rep_grow_raw(e, set, rows, aug))) return rc;
+    hipStream_t s = e->stream;
+    if (stage) {
+        if ((rc = ensure_copy_stream(e))) return rc;
+        if (!e->ev_rep_staged) {
+            HIPCHK(e, hipEventCreateWithFlags(&e->ev_rep_staged, hipEventDisableTiming));
+            HIPCHK(e, hipEventCreateWithFlags(&e->ev_rep_adopted, hipEventDisableTiming));
+        }
+        s = e->copy_stream;
+        // set 1 was the current set until the last adoption: its readers are the steps enqueued before that adoption's event
+        if (e->rep_adopted_once) HIPCHK(e, hipStreamWaitEvent(s, e->ev_rep_adopted, 0));
+    } else {
+        e->rep_staged_n = 0;        // an explicit upload supersedes a staged global batch
+        e->rep_n = 0;
+    }
+    HIPCHK(e, hipMemcpyAsync(e->rep_raw_video[set], video_u8, rows * 224 * 224 * 3, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->rep_raw_audio[set], audio_i16, rows * AUDIO_T * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->rep_raw_labels[set], labels_i32, rows * 2 * 4, hipMemcpyHostToDevice, s));
+    if (aug) {
+        HIPCHK(e, hipMemcpyAsync(e->rep_aug_params[set], params, rows * sizeof(l3::AugmentParams), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(e->rep_aug_u[set], u, rows * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    if (stage) {
+        HIPCHK(e, hipEventRecord(e->ev_rep_staged, s));
+        e->rep_staged_n = replicas;
+        e->rep_staged_aug = aug;
+        return L3_OK;
+    }
+    HIPCHK(e, l3::stream_wait(s));
+    e->rep_n = replicas;
+    e->rep_kind = aug ? 3 : 2;
+    return L3_OK;
+}
+
+int l3_replicas_upload_raw(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32, int replicas) {
+    return rep_send_raw(e, "l3_replicas_upload_raw", false, video_u8, audio_i16, labels_i32, nullptr, nullptr, false, replicas);
+}
+int l3_replicas_upload_raw_aug(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
+                               const l3_augment_params* params, const double* u, int replicas) {
+    return rep_send_raw(e, "l3_replicas_upload_raw_aug", false, video_u8, audio_i16, labels_i32, params, u, true, replicas);
+}
+int l3_replicas_stage_raw(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32, int replicas) {
+    return rep_send_raw(e, "l3_replicas_stage_raw", true, video_u8, audio_i16, labels_i32, nullptr, nullptr, false, replicas);
+}
+int l3_replicas_stage_raw_aug(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
+                              const l3_augment_params* params, const double* u, int replicas) {
+    return rep_send_raw(e, "l3_replicas_stage_raw_aug", true, video_u8, audio_i16, labels_i32, params, u, true, replicas);
+}
+
+// A staged global batch becomes the resident one: the two sets change places in stream order behind the previous step.  Then the
+// refusals, against the replica count of the batch that is resident now.
+static int rep_begin(l3_engine* e, const char* name) {
+    if (e->rep_staged_n > 0) {
+        HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_rep_staged, 0));
+        std::swap(e->rep_raw_video[0], e->rep_raw_video[1]), std::swap(e->rep_raw_video_cap[0], e->rep_raw_video_cap[1]);
+        std::swap(e->rep_raw_audio[0], e->rep_raw_audio[1]), std::swap(e->rep_raw_audio_cap[0], e->rep_raw_audio_cap[1]);
+        std::swap(e->rep_raw_labels[0], e->rep_raw_labels[1]), std::swap(e->rep_raw_labels_cap[0], e->rep_raw_labels_cap[1]);
+        std::swap(e->rep_aug_params[0], e->rep_aug_params[1]), std::swap(e->rep_aug_params_cap[0], e->rep_aug_params_cap[1]);
+        std::swap(e->rep_aug_u[0], e->rep_aug_u[1]), std::swap(e->rep_aug_u_cap[0], e->rep_aug_u_cap[1]);
+        // everything that read what is set 1 from here on is in front of this event
+        HIPCHK(e, hipEventRecord(e->ev_rep_adopted, e->stream));
+        e->rep_adopted_once = true;
+        e->rep_n = e->rep_staged_n;
+        e->rep_kind = e->rep_staged_aug ? 3 : 2;
+        e->rep_staged_n = 0;
+    }
+    if (e->rep_n < 1) {
+        e->err = std::string(name) + ": no resident global batch (l3_replicas_upload* or l3_replicas_stage_raw* first); batch " +
+                 std::to_string(e->B) + ", global_batch " + std::to_string(e->cfg.global_batch > 0 ? e->cfg.global_batch : e->B);
+        return L3_ESTATE;
+    }
+    e->staged = false;      // the resident global batch supersedes a staged single batch
+    return rep_refuse(e, name, e->rep_n);
+}
+
+// slice r of the resident global batch into the engine's inputs, by the kernels of l3_upload_batch_raw(_aug) from its rows
+static int rep_adopt_slice(l3_engine* e, int r) {
+    const size_t B = (size_t)e->B, pv = B * 224 * 224 * 3, pa = B * AUDIO_T;
+    if (e->rep_kind == 1) {
+        HIPCHK(e, hipMemcpyAsync(e->video, e->rep_video + r * pv, pv * 4, hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(e, hipMemcpyAsync(e->audio, e->rep_audio + r * pa, pa * 4, hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(e, hipMemcpyAsync(e->labels, e->rep_labels + r * B * 2, B * 2 * 4, hipMemcpyDeviceToDevice, e->stream));
+    } else {
+        if (e->rep_kind == 3) {
+            augment_video(e->rep_raw_video[0] + r * pv, (int)B, 224, 224, e->rep_aug_params[0] + r * B, nullptr, e->video, e->stream);
+            augment_audio(e->rep_raw_audio[0] + r * pa, (int)B, AUDIO_T, e->rep_aug_u[0] + r * B, nullptr, e->audio, e->aug_gains, e->stream);
+        } else {
+            preprocess_video(e->rep_raw_video[0] + r * pv, e->video, (int64_t)pv, e->stream);
+            preprocess_audio(e->rep_raw_audio[0] + r * pa, e->audio, (int64_t)pa, e->stream);
+        }
+        labels_onehot(e->rep_raw_labels[0] + r * B * 2, e->labels, (int64_t)B * 2, e->stream);
+    }
+    e->gains_valid = e->rep_kind == 3;
+    return L3_OK;
+}
+
+static int rep_accumulators(l3_engine* e) {
+    if (e->rep_acc) return L3_OK;
+    int rc = dev_alloc_t(e, &e->rep_stats, 16);
+    if (rc) return rc;
+    return dev_alloc_t(e, &e->rep_acc, (size_t)e->n_train);
+}
+
+int l3_step_replicas(l3_engine* e, float lr) {
+    if (!e) return L3_EINVAL;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    int rc = rep_begin(e, "l3_step_replicas");
+    if (rc) return rc;
+    const int R = e->rep_n, nb = (int)e->buckets.size();
+    if (R > 1 && (rc = rep_accumulators(e))) return rc;
+    for (int r = 0; r < R; ++r) {
+        if ((rc = rep_adopt_slice(e, r))) return rc;
+        // (the two-steps-in-flight wait inside is on the event of the global step two back: steps_enqueued moves with the update)
+        if ((rc = l3_step_forward(e, 1))) return rc;
+        // the slice's batch statistics are final with its forward pass: slot r of the replicas' buffer
+        if (R > 1 && (rc = bn_stats_pack(e, R, r))) return rc;
+        for (int b = 1; b < nb; ++b)
+            if ((rc = l3_step_backward_bucket(e, b))) return rc;
+        if (R > 1) {
+            // behind the join of the towers that the optimizer step waits at; ((g0 + g1) + g2) + ... : the last fold leaves the sum
+            // in the gradient arena, where Adam (and l3_get_grad) reads it
+            ProfScope ps(e, F_ELEMWISE, 0.0);
+            const int mode = r == 0 ? ARENA_FOLD_SET : r == R - 1 ? ARENA_FOLD_OUT : ARENA_FOLD_ADD;
+            arena_fold(e->rep_stats, e->stats, 2, mode, e->stream);
+            arena_fold(e->rep_acc, e->arena_g, e->n_train, mode, e->stream);
+        }
+    }
+    if (R > 1 && e->bn_pack_floats > 0) e->bn_replicas_armed = R;
+    if ((rc = l3_step_update(e, lr, 1.0f))) return rc;
+    e->results_global = true;
+    return L3_OK;
+}
+
+int l3_eval_replicas(l3_engine* e, float* loss, float* acc) {
+    if (!e) return L3_EINVAL;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    int rc = rep_begin(e, "l3_eval_replicas");
+    if (rc) return rc;
+    const int R = e->rep_n;
+    if (R > 1 && (rc = rep_accumulators(e))) return rc;
+    e->bn_replicas_armed = 0;
+    e->bn_packed = false;
+    for (int r = 0; r < R; ++r) {
+        if ((rc = rep_adopt_slice(e, r))) return rc;
+        if ((rc = forward_all(e, false))) return rc;
+        loss_and_head_backward(e, false);
+        if (R > 1) arena_fold(e->rep_stats, e->stats, 2, r == 0 ? ARENA_FOLD_SET : r == R - 1 ? ARENA_FOLD_OUT : ARENA_FOLD_ADD, e->stream);
+    }
+    e->fwd_done = false;
+    e->results_global = true;
+    HIPCHK(e, hipGetLastError());
+    return read_results(e, loss, acc, nullptr, nullptr);
 }
 
 // ---- data parallelism behind the C ABI -----------------------------------------------------------------
@@ -2607,6 +2876,7 @@ int l3_step_results_enqueue(l3_engine* e, int slot, int reduce) {
         src = e->res_sum;
     }
     e->res_reduced[slot] = reduce != 0;
+    e->res_global[slot] = e->results_global;
     HIPCHK(e, hipMemcpyAsync(h, src, 16 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipMemcpyAsync(h + 16, e->l2part, 64 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipEventRecord(e->ev_res[slot], e->stream));
@@ -2628,7 +2898,7 @@ int l3_step_results_wait(l3_engine* e, int slot, float* loss, float* acc) {
     int si = 0;
     for (auto& s : e->segments)
         if (s.l2) reg += (double)L2_WEIGHT * (double)h[16 + si++];
-    const double n = e->res_reduced[slot] && e->cfg.global_batch > 0 ? (double)e->cfg.global_batch : (double)e->B;
+    const double n = (e->res_reduced[slot] || e->res_global[slot]) && e->cfg.global_batch > 0 ? (double)e->cfg.global_batch : (double)e->B;
     if (loss) *loss = (float)((double)h[0] / n + reg);
     if (acc) *acc = (float)((double)h[1] / n);
     return L3_OK;

@@ -376,6 +376,10 @@ void sumsq_multi(const float* base, const SumsqSegs& segs, float* out, float* sc
 void adam_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_l2, float l2x2,
                float lr_t, float b1, float b2, float eps, float gscale, hipStream_t s);
 void fill(float* p, float v, int64_t n, hipStream_t s);
+// the gradient sum over the replicas of l3_step_replicas (training_utils.py:141-170), element by element as IEEE fp32 a + b over
+// n floats at any element offset of two arenas: SET acc = g, ADD acc += g, OUT g = acc + g
+enum { ARENA_FOLD_SET = 0, ARENA_FOLD_ADD = 1, ARENA_FOLD_OUT = 2 };
+void arena_fold(float* acc, float* g, int64_t n, int mode, hipStream_t s);
 // fp32 -> bfloat16 storage, round to nearest even (op-level entry points: emulates a mixed-precision writer)
 void cast_bf16(const float* x, void* y, int64_t n, hipStream_t s);
 

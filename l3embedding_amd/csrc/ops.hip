@@ -718,6 +718,22 @@ extern "C" int l3_op_adam_scaled(int device, float* p, const float* g, float* m,
     return sc.status();
 }
 
+extern "C" int l3_op_arena_fold(int device, float* acc, float* g, int64_t total, int64_t off, int64_t n, int mode) {
+    if (!acc || !g || total <= 0 || off < 0 || n < 0 || off > total || n > total - off || mode < ARENA_FOLD_SET || mode > ARENA_FOLD_OUT) {
+        set_op_error("l3_op_arena_fold: NULL arena, a range [" + std::to_string(off) + ", " + std::to_string(off) + " + " +
+                     std::to_string(n) + ") outside the " + std::to_string(total) + " floats, or mode " + std::to_string(mode) +
+                     " (0 set, 1 add, 2 out)");
+        return L3_EINVAL;
+    }
+    Scope sc(device);
+    float* da = sc.put(acc, (size_t)total);
+    float* dg = sc.put(g, (size_t)total);
+    if (!sc.ok) return L3_ENOMEM;
+    arena_fold(da + off, dg + off, n, mode, sc.s);
+    sc.get(acc, da, (size_t)total), sc.get(g, dg, (size_t)total);
+    return sc.status();
+}
+
 // ---- head, loss, L2 sums and BatchNorm moving averages on their own (elementwise.hip; model.py:25-31, train.py:270-284) ----------
 namespace {
 constexpr size_t HEAD_MAX_DYN_LDS = 64 * 1024;      // dynamic LDS of a launch that sets no function attribute

@@ -205,6 +205,7 @@ class L3Model(object):
             self._table = _host_param_table(self.model_type)
         return self._table
 
+    serial = False       # replicas > 1: the replicas run one after another on this model's GPU (as_data_parallel(serial=True))
     MAX_ENGINES = 3      # engines kept alive at once (one per fed batch size; ~0.4 GB of HBM per pair of batch)
 
     def _ensure_engine(self, batch, global_batch=0):
@@ -219,7 +220,7 @@ class L3Model(object):
         e = self._engines.get(key)
         if e is None:
             stream = None
-            if self.replicas > 1:
+            if self.replicas > 1 and not self.serial:
                 import torch
                 if getattr(self, '_tstream', None) is None:
                     self._tstream = torch.cuda.Stream(device=self.device)
@@ -382,10 +383,15 @@ class L3Model(object):
         self.loss = loss
         self.metrics_names = ['loss'] + (['acc'] if metrics and ('accuracy' in metrics or 'acc' in metrics) else [])
 
-    def as_data_parallel(self, gpus):
+    def as_data_parallel(self, gpus, serial=False):
+        """serial=True: the `gpus` replicas of multi_gpu_model (training_utils.py:121-170) run one after another on this model's
+        GPU, in this process (Engine.step_replicas): no torch.distributed, any number of devices.  A fed batch is cut into `gpus`
+        equal slices; a batch that does not divide is refused (the reference would give the last replica the remainder)."""
         import os
         self.replicas = int(gpus)
-        self.device = int(os.environ.get('LOCAL_RANK', self.device))     # one process per GPU
+        self.serial = bool(serial)
+        if not self.serial:
+            self.device = int(os.environ.get('LOCAL_RANK', self.device))     # one process per GPU
         if self._engine is not None:
             self._host_weights = self._engine.get_params()
             self._drop_engines()
@@ -403,7 +409,7 @@ class L3Model(object):
     def _split(self, x, y=None):
         """[video, audio] (+ labels) -> this rank's shard (training_utils.py:121-133)."""
         v, a = x
-        if self.replicas <= 1:
+        if self.replicas <= 1 or self.serial:       # serial replicas: the whole batch goes to the one engine, which cuts it
             return v, a, y, len(v)
         dist = self._dist()
         if getattr(x, 'global_batch', None):       # blobfeed.ShardedInputs: the feed already read only this rank's rows
@@ -419,10 +425,18 @@ class L3Model(object):
         """This rank's rows of the augmentation parameters a training batch carries (augment.AugmentedInputs; None for a plain
         batch).  The rows are those of the global batch, cut with the bounds `_split` cuts the arrays with."""
         params = getattr(x, 'augment', None)
-        if params is None or self.replicas <= 1:
+        if params is None or self.replicas <= 1 or self.serial:
             return params
         lo, hi = get_slice_bounds(len(params), self.replicas, self._dist().get_rank())
         return params[lo:hi]
+
+    def _serial_slice(self, n):
+        """Rows per replica of an n-row batch fed to a serial-replica model."""
+        if n % self.replicas:
+            raise ValueError('a batch of %d rows does not divide over %d serial replicas: the reference would give the last '
+                             'replica the remainder (training_utils.py:121-133), serial replicas take equal slices only'
+                             % (n, self.replicas))
+        return n // self.replicas
 
     @staticmethod
     def _is_raw(v, a):
@@ -449,6 +463,19 @@ class L3Model(object):
         if aug is not None and not raw:
             raise ValueError('only raw batches (uint8 video, int16 audio) can be augmented: the arithmetic of '
                              'data/avc/sample.py is defined on the stored dtypes')
+        if self.replicas > 1 and self.serial:
+            R = self.replicas
+            e = self._ensure_engine(self._serial_slice(len(v)), global_batch=gb)
+            if not staged:
+                if aug is not None:
+                    e.replicas_upload_raw_aug(v, a, np.asarray(l).astype(np.int32), aug, aug['u_gain'], R)
+                elif raw:
+                    e.replicas_upload_raw(v, a, np.asarray(l).astype(np.int32), R)
+                else:
+                    e.replicas_upload(v, a, l, R)
+            e.step_replicas(self.optimizer.lr)
+            self._inflight = (e, len(v), gb)
+            return
         dp = self.replicas > 1
         e = self._ensure_engine(len(v), global_batch=gb if dp else 0)
         if dp and e._trainer is None:
@@ -480,7 +507,7 @@ class L3Model(object):
         e, n_local, gb = self._inflight
         if not hasattr(e, 'results_enqueue'):
             return None
-        reduce = self.replicas > 1
+        reduce = self.replicas > 1 and not self.serial      # (serial replicas: the engine has summed its slices itself)
         if reduce and not getattr(e._trainer, 'reduces_results', False):
             return None          # the torch.distributed double: the ranks' values are reduced by _finish_train
         slot = self._res_slot = 1 - getattr(self, '_res_slot', 1)
@@ -501,7 +528,12 @@ class L3Model(object):
         if len(v) != n_local or not self._is_raw(v, a):
             return False
         aug = self._split_augment(x)
-        if aug is not None:
+        if self.replicas > 1 and self.serial:
+            if aug is not None:
+                e.replicas_stage_raw_aug(v, a, np.asarray(l).astype(np.int32), aug, aug['u_gain'], self.replicas)
+            else:
+                e.replicas_stage_raw(v, a, np.asarray(l).astype(np.int32), self.replicas)
+        elif aug is not None:
             e.stage_batch_raw_aug(v, a, np.asarray(l).astype(np.int32), aug, aug['u_gain'])
         else:
             e.stage_batch_raw(v, a, np.asarray(l).astype(np.int32))
@@ -511,7 +543,7 @@ class L3Model(object):
         e, n_local, gb = self._inflight
         self._inflight = None
         loss, acc = e.step_results()
-        if self.replicas <= 1:
+        if self.replicas <= 1 or self.serial:
             return [loss, acc]
         import torch
         # logged loss/acc are over the concatenated batch (training_utils.py:165-170)
@@ -521,6 +553,13 @@ class L3Model(object):
 
     def test_on_batch(self, x, y):
         v, a, l, gb = self._split(x, y)
+        if self.replicas > 1 and self.serial:
+            e = self._ensure_engine(self._serial_slice(len(v)), global_batch=gb)
+            if self._is_raw(v, a):
+                e.replicas_upload_raw(v, a, np.asarray(l).astype(np.int32), self.replicas)
+            else:
+                e.replicas_upload(v, a, l, self.replicas)
+            return list(e.eval_replicas())
         e = self._ensure_engine(len(v), global_batch=gb if self.replicas > 1 else 0)
         if self._is_raw(v, a):
             e.upload_batch_raw(v, a, np.asarray(l).astype(np.int32))
@@ -887,9 +926,9 @@ def _resample_rows(clips, rates, offs, lengths, base, top):
 # ---------------------------------------------------------------------------------------------------
 # reference entry points
 # ---------------------------------------------------------------------------------------------------
-def multi_gpu_model(model, gpus, validate=True):
+def multi_gpu_model(model, gpus, validate=True, serial=False):
     from .training_utils import multi_gpu_model as _m
-    return _m(model, gpus, validate)
+    return _m(model, gpus, validate, serial)
 
 
 def gpu_wrapper(model_f):

@@ -145,13 +145,39 @@ def train_augmented(train_data_dir, validation_data_dir, output_dir, augment_ran
                   extra_config=dict(augment=True, augment_random_state=augment_random_state))
 
 
+def train_serial_replicas(train_data_dir, validation_data_dir, output_dir, augment=False, augment_random_state=20180123,
+                          **train_args):
+    """`train()` of a `gpus`-replica model on ONE GPU, in this process: the replicas of multi_gpu_model (training_utils.py:121-170)
+    run one after another on each fed batch (Engine.step_replicas) -- per-replica batch statistics, `gpus` moving-average updates
+    per step in replica order, the replicas' gradients added in replica order, one Adam step -- so a run continues, or reproduces,
+    what a `gpus`-GPU job computes.  No torch.distributed, no GPU-count check.  `train_batch_size` and `validation_batch_size` are
+    the GLOBAL batches (64 per GPU in the reference's jobs) and must divide by `gpus`; the feed is not sharded.  Checkpoints are an
+    N-replica model's: `load_model(path, model_type, src_num_gpus=gpus)` reads them, `continue_model_dir` resumes.  augment: as
+    `train_augmented`.  `train_args`: the keyword arguments of `train()`.  config.json also records `serial_replicas`."""
+    import inspect
+    args = {k: v.default for k, v in inspect.signature(train).parameters.items() if v.default is not inspect.Parameter.empty}
+    unknown = sorted(set(train_args) - set(args))
+    if unknown:
+        raise TypeError('train_serial_replicas() got unexpected keyword arguments: %s' % ', '.join(unknown))
+    args.update(train_args)
+    extra, wrap = dict(serial_replicas=True), None
+    if augment:
+        from .augment import AugmentingFeed
+        wrap = lambda batches: AugmentingFeed(batches, augment_random_state)
+        extra.update(augment=True, augment_random_state=augment_random_state)
+    return _train(train_data_dir, validation_data_dir, output_dir, **args, wrap_train_feed=wrap, extra_config=extra,
+                  serial_replicas=True)
+
+
 def _train(train_data_dir, validation_data_dir, output_dir, num_epochs, train_epoch_size, validation_epoch_size,
            train_batch_size, validation_batch_size, model_type, random_state, learning_rate, verbose, checkpoint_interval,
            log_path, disable_logging, gpus, continue_model_dir, gsheet_id, google_dev_app_name,
-           wrap_train_feed=None, extra_config=None):
+           wrap_train_feed=None, extra_config=None, serial_replicas=False):
     """The body of `train()`.  wrap_train_feed: a wrapper around the generator of training batches (train_augmented);
-    extra_config: entries added to config.json."""
-    call_args = {k: v for k, v in locals().items() if k not in ('wrap_train_feed', 'extra_config')}
+    extra_config: entries added to config.json; serial_replicas: the `gpus` replicas run one after another in this process
+    (train_serial_replicas)."""
+    call_args = {k: v for k, v in locals().items() if k not in ('wrap_train_feed', 'extra_config', 'serial_replicas')}
+    serial = bool(serial_replicas) and gpus > 1
     if not disable_logging and log_path:
         handler = logging.FileHandler(log_path)
         handler.setFormatter(logging.Formatter('%(asctime)s - %(name)s - %(levelname)s - %(message)s'))
@@ -165,11 +191,16 @@ def _train(train_data_dir, validation_data_dir, output_dir, num_epochs, train_ep
         model_dir = continue_model_dir
         resume = get_restart_info(os.path.join(model_dir, ARTEFACTS['csv']))
         m, _, _ = load_model(os.path.join(model_dir, ARTEFACTS['latest']), model_type, return_io=True, src_num_gpus=gpus)
+        if serial:
+            m.as_data_parallel(gpus, serial=True)
     else:
         model_dir = os.path.join(output_dir, 'embedding', model_id, datetime.datetime.now().strftime('%Y%m%d%H%M%S'))
-        m, _, _ = MODELS[model_type](num_gpus=gpus)
+        m, _, _ = MODELS[model_type](num_gpus=0 if serial else gpus)
+        if serial:
+            from .training_utils import multi_gpu_model
+            m = multi_gpu_model(m, gpus, serial=True)
 
-    rank, world, distributed = _world()
+    rank, world, distributed = (0, 1, False) if serial else _world()
     if distributed:
         model_dir = _agree_on(model_dir)
     writes = rank == 0

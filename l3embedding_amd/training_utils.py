@@ -299,15 +299,20 @@ def check_gpus_available(gpus):
                          % (gpus, target_devices, have))
 
 
-def multi_gpu_model(model, gpus, validate=True):
+def multi_gpu_model(model, gpus, validate=True, serial=False):
     """Reference-compatible entry point (training_utils.py:21): wrap `model` for data-parallel training on
     `gpus` devices, with the reference's argument checks and messages (training_utils.py:99-119).  Here a
     replica is a process, so the wrapper records the replica count and the model shards each fed batch by
     torch.distributed rank.  validate=False (used when only a wrapper-layout weight FILE is being read,
-    model.load_model) skips the device check, so a file trained on 8 GPUs converts on a smaller box."""
+    model.load_model) skips the device check, so a file trained on 8 GPUs converts on a smaller box.
+    serial=True: the `gpus` replicas run one after another on the model's one GPU, in this process (Engine.step_replicas; the
+    arithmetic of training_utils.py:121-170 replica by replica) -- no device check, no torch.distributed.  A fed batch must divide
+    by `gpus`: the reference gives the last replica the remainder, which serial replicas do not take (ValueError)."""
     if gpus <= 1:
         raise ValueError('For multi-gpu usage to be effective, call `multi_gpu_model` with `gpus >= 2`. '
                          'Received: `gpus=%d`' % gpus)
+    if serial:
+        return model.as_data_parallel(gpus, serial=True)
     if validate:
         check_gpus_available(gpus)
     return model.as_data_parallel(gpus)
