@@ -144,15 +144,24 @@ int l3_eval_step(l3_engine *e, const float *video, const float *audio,
 /* Device-resident input path (the measured one: inputs already in HBM).
  * l3_upload_batch copies caller host buffers into the engine's input tensors;
  * l3_upload_batch_raw takes the HDF5 blob dtypes (uint8 frames, int16 PCM, int
- * labels; data/avc/sample.py:371-377) and applies train.py:186,189 on the GPU. */
+ * labels; data/avc/sample.py:371-377) and applies train.py:186,189 on the GPU; a NULL input stays as it was.
+ *
+ * Every batch in the stored dtypes goes through ONE feed, which keeps two sets of device buffers: the resident batch and the
+ * staged one.  A batch is either single (B rows: l3_upload_batch_raw*, l3_stage_batch_raw*; converted into the float inputs once,
+ * by the upload or by the step that adopts it) or the global batch of serial replicas (R * B rows: l3_replicas_*; it stays
+ * resident and slice r is converted when its turn comes in every l3_step_replicas / l3_eval_replicas).  The engine holds one
+ * resident batch: a single raw batch, uploaded or adopted, replaces a resident raw global batch (l3_upload_batch and the float
+ * entry points leave it alone).  An explicit upload supersedes a staged batch of its kind (single / global), a resident global
+ * batch supersedes a staged single batch when a replicas step begins, and of two batches staged without an adoption in between,
+ * single or global, the later one wins. */
 int l3_upload_batch(l3_engine *e, const float *video, const float *audio, const float *labels);
 int l3_upload_batch_raw(l3_engine *e, const uint8_t *video_u8, const int16_t *audio_i16,
                         const int32_t *labels_i32);
-/* Pipelined variant for a training loop: copies the NEXT batch (stored dtypes) to the device over the
+/* Pipelined variant for a training loop: copies the NEXT batch (stored dtypes) into the feed's staged set over the
  * engine's own copy stream and returns; the copy overlaps the step that is still running, and the
- * following l3_step_forward() adopts the staged batch (scaling kernels in stream order) before it
- * starts.  Keras' fit_generator keeps batches queued ahead of the device the same way
- * (train.py:408-414, max_queue_size=10). */
+ * following l3_step_forward() / l3_tower_step() adopts the staged batch (the sets change places and the scaling
+ * kernels run in stream order) before it starts.  Keras' fit_generator keeps batches queued ahead of the device the
+ * same way (train.py:408-414, max_queue_size=10). */
 int l3_stage_batch_raw(l3_engine *e, const uint8_t *video_u8, const int16_t *audio_i16, const int32_t *labels_i32);
 /* Training-set augmentation (02_generate_samples.py --augment; data/avc/sample.py:24-69,117-166,169-283), one record per sample.
  * The draws are the caller's (l3embedding_amd/augment.py draw_params keeps the reference's order of random calls); the library
@@ -213,8 +222,8 @@ int l3_step_results_wait(l3_engine *e, int slot, float *loss, float *acc);
  *   l3_replicas_upload_raw      the stored dtypes (uint8 frames, int16 PCM, int32 labels); slice r is scaled by the kernels of
  *                               l3_upload_batch_raw from rows [rB, (r+1)B) of the resident raw batch when its turn comes
  *   l3_replicas_upload_raw_aug  ... augmented by the kernels of l3_upload_batch_raw_aug: R*B records and R*B gain draws
- *   l3_replicas_stage_raw(_aug) the NEXT global batch over the copy stream while a step runs; the next l3_step_replicas /
- *                               l3_eval_replicas adopts it (as l3_stage_batch_raw); an explicit upload supersedes it
+ *   l3_replicas_stage_raw(_aug) the NEXT global batch into the same staged set, over the same copy stream, as l3_stage_batch_raw;
+ *                               the next l3_step_replicas / l3_eval_replicas adopts it; an explicit l3_replicas_upload* supersedes it
  *   l3_step_replicas            for r = 0 .. R-1: slice r -> training forward, loss, every backward bucket (the towers overlap as in
  *                               l3_step_resident) -> the slice's BatchNorm batch statistics into slot r of the replica buffer, its
  *                               loss / accuracy sums and its gradient arena folded into accumulators; then ONE l3_step_update:
@@ -225,8 +234,8 @@ int l3_step_results_wait(l3_engine *e, int slot, float *loss, float *acc);
  * concatenated batch -- the sums over the slices divided by global_batch; probs / logits are refused (L3_ESTATE: the engine holds
  * one slice's).  Refused, with the numbers in l3_last_error: replicas < 1 (L3_EINVAL); global_batch != replicas * batch
  * (L3_EINVAL); no resident global batch (L3_ESTATE); l3_config.dp_moving == L3_DP_MOVING_RANK_LOCAL (L3_ESTATE: one update per
- * step is not what R replicas apply); an engine that holds a communicator (L3_ESTATE: l3_step_dp is its step).  The resident
- * buffers grow on demand and are freed with the engine. */
+ * step is not what R replicas apply); an engine that holds a communicator (L3_ESTATE: l3_step_dp is its step).  The feed's
+ * buffers are allocated by the first batch that needs them, grow on demand and are freed with the engine. */
 int l3_replicas_upload(l3_engine *e, const float *video, const float *audio, const float *labels, int replicas);
 int l3_replicas_upload_raw(l3_engine *e, const uint8_t *video_u8, const int16_t *audio_i16, const int32_t *labels_i32, int replicas);
 int l3_replicas_upload_raw_aug(l3_engine *e, const uint8_t *video_u8, const int16_t *audio_i16, const int32_t *labels_i32,

@@ -14,11 +14,11 @@ LIBPATH = os.path.join(LIBDIR, 'libl3hip.so')
 # The product library.  One file per kernel family of DESIGN.md section 4: fp32 convolutions (F(4x4,3x3) forward / data gradient,
 # F(2x2,3x3) = l3_config.fp32_conv F2X2 + the dispatch, F(3x3,2x2) weight gradient, direct implicit GEMM for the DFT and every
 # geometry Winograd does not take), mixed precision (halo forward / data gradient, transpose-read weight gradient, the dispatch +
-# fp32-tensor entry points), first layers, BatchNorm / pool, head / loss / Adam, front-end, clip framing, resampling, engine, operator
+# fp32-tensor entry points), first layers, BatchNorm / pool, head / loss / Adam, front-end, clip framing, resampling, the training-batch feed, engine, operator
 # entry points, RCCL, the downstream MLP and SVM classifiers, the VGGish baseline features, training-set augmentation, the
 # classifier's fold preprocessing, the SVM's scoring and sigmoid fits, the downstream random forest.
 SOURCES = ['conv.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_bf16.hip', 'conv_bf16_halo.hip', 'conv_wgrad_bf16.hip', 'conv_wgrad_wino.hip',
-           'conv_first.hip', 'conv_path.hip', 'elementwise.hip', 'bn_fused.hip', 'frontend.hip', 'clips.hip', 'resample.hip', 'engine.hip', 'ops.hip',
+           'conv_first.hip', 'conv_path.hip', 'elementwise.hip', 'bn_fused.hip', 'frontend.hip', 'clips.hip', 'resample.hip', 'batch_feed.hip', 'engine.hip', 'ops.hip',
            'comm.hip', 'mlp.hip', 'svm.hip', 'vggish.hip', 'augment.hip', 'featprep.hip', 'svm_eval.hip', 'forest.hip']
 # Measured-and-rejected kernel variants (split-bf16 fp32 convolutions, flat-tile MODE 5, tap-split bf16 weight gradient; round 6: the
 # filter-in-registers 64-channel halo kernel, the split-bf16 first convolution): records of negative results (profiles/r05_bx6_ablations.txt,

@@ -463,40 +463,40 @@ class Engine(object):
         v, a, l = _f32(video), _f32(audio), _f32(labels)
         check(self.lib.l3_upload_batch(self.h, _ptr(v), _ptr(a), _ptr(l)), self.h)
 
-    def upload_batch_raw(self, video_u8=None, audio_i16=None, labels_i32=None):
-        v = None if video_u8 is None else np.ascontiguousarray(video_u8, dtype=np.uint8)
-        a = None if audio_i16 is None else np.ascontiguousarray(audio_i16, dtype=np.int16)
-        l = None if labels_i32 is None else np.ascontiguousarray(labels_i32, dtype=np.int32)
-        check(self.lib.l3_upload_batch_raw(self.h, _ptr(v), _ptr(a), _ptr(l)), self.h)
-
-    def stage_batch_raw(self, video_u8, audio_i16, labels_i32):
-        """Next batch to the device while the current step runs; adopted by the next step_forward()."""
-        v = np.ascontiguousarray(video_u8, dtype=np.uint8)
-        a = np.ascontiguousarray(audio_i16, dtype=np.int16)
-        l = np.ascontiguousarray(labels_i32, dtype=np.int32)
-        check(self.lib.l3_stage_batch_raw(self.h, _ptr(v), _ptr(a), _ptr(l)), self.h)
-
-    def _aug_args(self, params, u):
+    def _aug_args(self, params, u, replicas=None):
         p, g = augment_records(params), np.ascontiguousarray(u, dtype=np.float64)
-        if len(p) != self.batch or len(g) != self.batch:
+        if replicas is not None:
+            self._replica_rows(replicas, p, g)
+        elif len(p) != self.batch or len(g) != self.batch:
             raise ValueError('%d augmentation records and %d gain draws for a batch of %d' % (len(p), len(g), self.batch))
         return p, g
 
+    def _send_raw(self, fn, video_u8, audio_i16, labels_i32, records=None, replicas=None):
+        """One batch in the stored dtypes to the entry point `fn`: the arrays cast (None: that input stays as it was), their rows
+        checked against `replicas` slices, the (params, u) records packed."""
+        args = [None if x is None else np.ascontiguousarray(x, dtype=t)
+                for x, t in ((video_u8, np.uint8), (audio_i16, np.int16), (labels_i32, np.int32))]
+        if replicas is not None:
+            self._replica_rows(replicas, *args)
+        if records is not None:
+            args += self._aug_args(records[0], records[1], replicas)
+        tail = [] if replicas is None else [int(replicas)]
+        check(fn(self.h, *([_ptr(x) for x in args] + tail)), self.h)
+
+    def upload_batch_raw(self, video_u8=None, audio_i16=None, labels_i32=None):
+        self._send_raw(self.lib.l3_upload_batch_raw, video_u8, audio_i16, labels_i32)
+
+    def stage_batch_raw(self, video_u8, audio_i16, labels_i32):
+        """Next batch to the device while the current step runs; adopted by the next step_forward()."""
+        self._send_raw(self.lib.l3_stage_batch_raw, video_u8, audio_i16, labels_i32)
+
     def upload_batch_raw_aug(self, video_u8, audio_i16, labels_i32, params, u):
         """upload_batch_raw with the batch augmented on the way (data/avc/sample.py:146-162,241-281)."""
-        v = np.ascontiguousarray(video_u8, dtype=np.uint8)
-        a = np.ascontiguousarray(audio_i16, dtype=np.int16)
-        l = np.ascontiguousarray(labels_i32, dtype=np.int32)
-        p, g = self._aug_args(params, u)
-        check(self.lib.l3_upload_batch_raw_aug(self.h, _ptr(v), _ptr(a), _ptr(l), _ptr(p), _ptr(g)), self.h)
+        self._send_raw(self.lib.l3_upload_batch_raw_aug, video_u8, audio_i16, labels_i32, (params, u))
 
     def stage_batch_raw_aug(self, video_u8, audio_i16, labels_i32, params, u):
         """stage_batch_raw with the records; the adopting step augments the batch in place of scaling it."""
-        v = np.ascontiguousarray(video_u8, dtype=np.uint8)
-        a = np.ascontiguousarray(audio_i16, dtype=np.int16)
-        l = np.ascontiguousarray(labels_i32, dtype=np.int32)
-        p, g = self._aug_args(params, u)
-        check(self.lib.l3_stage_batch_raw_aug(self.h, _ptr(v), _ptr(a), _ptr(l), _ptr(p), _ptr(g)), self.h)
+        self._send_raw(self.lib.l3_stage_batch_raw_aug, video_u8, audio_i16, labels_i32, (params, u))
 
     def batch_gains(self):
         """Audio gains of the augmented batch the engine holds (waits for the device)."""
@@ -537,39 +537,19 @@ class Engine(object):
         self._replica_rows(replicas, v, a, l)
         check(self.lib.l3_replicas_upload(self.h, _ptr(v), _ptr(a), _ptr(l), int(replicas)), self.h)
 
-    @staticmethod
-    def _raw_args(video_u8, audio_i16, labels_i32):
-        return (np.ascontiguousarray(video_u8, dtype=np.uint8), np.ascontiguousarray(audio_i16, dtype=np.int16),
-                np.ascontiguousarray(labels_i32, dtype=np.int32))
-
-    def _replica_aug_args(self, params, u, replicas):
-        p, g = augment_records(params), np.ascontiguousarray(u, dtype=np.float64)
-        self._replica_rows(replicas, p, g)
-        return p, g
-
     def replicas_upload_raw(self, video_u8, audio_i16, labels_i32, replicas):
         """The stored dtypes of a global batch; each slice is scaled by upload_batch_raw's kernels when its turn comes."""
-        v, a, l = self._raw_args(video_u8, audio_i16, labels_i32)
-        self._replica_rows(replicas, v, a, l)
-        check(self.lib.l3_replicas_upload_raw(self.h, _ptr(v), _ptr(a), _ptr(l), int(replicas)), self.h)
+        self._send_raw(self.lib.l3_replicas_upload_raw, video_u8, audio_i16, labels_i32, replicas=replicas)
 
     def replicas_stage_raw(self, video_u8, audio_i16, labels_i32, replicas):
         """Next global batch to the device while the current step runs; adopted by the next step_replicas / eval_replicas."""
-        v, a, l = self._raw_args(video_u8, audio_i16, labels_i32)
-        self._replica_rows(replicas, v, a, l)
-        check(self.lib.l3_replicas_stage_raw(self.h, _ptr(v), _ptr(a), _ptr(l), int(replicas)), self.h)
+        self._send_raw(self.lib.l3_replicas_stage_raw, video_u8, audio_i16, labels_i32, replicas=replicas)
 
     def replicas_upload_raw_aug(self, video_u8, audio_i16, labels_i32, params, u, replicas):
-        v, a, l = self._raw_args(video_u8, audio_i16, labels_i32)
-        self._replica_rows(replicas, v, a, l)
-        p, g = self._replica_aug_args(params, u, replicas)
-        check(self.lib.l3_replicas_upload_raw_aug(self.h, _ptr(v), _ptr(a), _ptr(l), _ptr(p), _ptr(g), int(replicas)), self.h)
+        self._send_raw(self.lib.l3_replicas_upload_raw_aug, video_u8, audio_i16, labels_i32, (params, u), replicas)
 
     def replicas_stage_raw_aug(self, video_u8, audio_i16, labels_i32, params, u, replicas):
-        v, a, l = self._raw_args(video_u8, audio_i16, labels_i32)
-        self._replica_rows(replicas, v, a, l)
-        p, g = self._replica_aug_args(params, u, replicas)
-        check(self.lib.l3_replicas_stage_raw_aug(self.h, _ptr(v), _ptr(a), _ptr(l), _ptr(p), _ptr(g), int(replicas)), self.h)
+        self._send_raw(self.lib.l3_replicas_stage_raw_aug, video_u8, audio_i16, labels_i32, (params, u), replicas)
 
     def step_replicas(self, lr):
         """One training step of the resident global batch, slice by slice: the replicas' gradients added in replica order, one

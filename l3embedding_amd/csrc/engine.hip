@@ -205,17 +205,10 @@ struct l3_engine {
     int *mel_start = nullptr, *mel_len = nullptr, *mel_off = nullptr;
     int64_t melw_cap = 0;
 
-    // inputs
+    // inputs: the floats the towers read, and the feed that fills them from batches in the stored dtypes (single or global, uploaded
+    // or staged, plain or augmented) and holds the resident global batch of serial replicas
     float *video = nullptr, *audio = nullptr, *labels = nullptr;
-    uint8_t* raw_video = nullptr;
-    int16_t* raw_audio = nullptr;
-    int32_t* raw_labels = nullptr;
-    // l3_stage_batch_raw: the NEXT batch lands here over an own copy stream while the current step runs
-    uint8_t* nxt_video = nullptr;
-    int16_t* nxt_audio = nullptr;
-    int32_t* nxt_labels = nullptr;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_staged = nullptr, ev_adopted = nullptr;
+    l3::BatchFeed feed;
     // deferred step results (l3_step_results_enqueue / _wait): two pinned slots of {stats[16], l2part[64]} and their events
     float* res_host = nullptr;
     float* res_sum = nullptr;             // device: the stats vector summed over the ranks (reduce = 1)
@@ -227,27 +220,7 @@ struct l3_engine {
     hipEvent_t ev_step[2] = {nullptr, nullptr};
     bool ev_step_set[2] = {false, false};
     int64_t steps_enqueued = 0;
-    bool staged = false, adopted_once = false;
-    // l3_upload_batch_raw_aug / l3_stage_batch_raw_aug: the records and draws of the current and of the staged batch, the gains of
-    // the current one (allocated by the first augmented batch)
-    l3::AugmentParams *aug_params = nullptr, *nxt_aug_params = nullptr;
-    double *aug_u = nullptr, *nxt_aug_u = nullptr, *aug_gains = nullptr;
-    bool staged_aug = false, gains_valid = false;
-    // serial replicas (l3_replicas_*, l3_step_replicas): the resident global batch of rep_n slices of B rows -- as floats (kind 1) or
-    // in the stored dtypes (kind 2; 3: with augmentation records) --, the set [1] the copy stream fills for the next step beside the
-    // current set [0], and the accumulators of the gradient arena and of the loss / accuracy sums
-    int rep_n = 0, rep_kind = 0, rep_staged_n = 0;
-    bool rep_staged_aug = false, rep_adopted_once = false;
-    float *rep_video = nullptr, *rep_audio = nullptr, *rep_labels = nullptr;
-    size_t rep_video_cap = 0, rep_audio_cap = 0, rep_labels_cap = 0;
-    uint8_t* rep_raw_video[2] = {nullptr, nullptr};
-    int16_t* rep_raw_audio[2] = {nullptr, nullptr};
-    int32_t* rep_raw_labels[2] = {nullptr, nullptr};
-    l3::AugmentParams* rep_aug_params[2] = {nullptr, nullptr};
-    double* rep_aug_u[2] = {nullptr, nullptr};
-    size_t rep_raw_video_cap[2] = {0, 0}, rep_raw_audio_cap[2] = {0, 0}, rep_raw_labels_cap[2] = {0, 0}, rep_aug_params_cap[2] = {0, 0},
-           rep_aug_u_cap[2] = {0, 0};
-    hipEvent_t ev_rep_staged = nullptr, ev_rep_adopted = nullptr;
+    // serial replicas (l3_step_replicas, l3_eval_replicas): the accumulators of the gradient arena and of the loss / accuracy sums
     float *rep_acc = nullptr, *rep_stats = nullptr;
     bool results_global = false;    // e->stats holds the sums over every slice of the global batch (l3_step_replicas, l3_eval_replicas)
     bool res_global[2] = {false, false};
@@ -1031,9 +1004,7 @@ int alloc_everything(l3_engine* e, uint64_t seed) {
     if ((rc = dev_alloc_t(e, &e->video, (size_t)B * 224 * 224 * 3))) return rc;
     if ((rc = dev_alloc_t(e, &e->audio, (size_t)B * AUDIO_T))) return rc;
     if ((rc = dev_alloc_t(e, &e->labels, (size_t)B * 2))) return rc;
-    if ((rc = dev_alloc_t(e, &e->raw_video, (size_t)B * 224 * 224 * 3))) return rc;
-    if ((rc = dev_alloc_t(e, &e->raw_audio, (size_t)B * AUDIO_T))) return rc;
-    if ((rc = dev_alloc_t(e, &e->raw_labels, (size_t)B * 2))) return rc;
+    e->feed.bind(B, AUDIO_T, e->video, e->audio, e->labels);
     HIPCHK(e, hipMemset(e->labels, 0, (size_t)B * 2 * 4));
     // head
     const int D = e->nv + e->na;
@@ -1735,8 +1706,7 @@ int read_results(l3_engine* e, float* loss, float* acc, float* probs, float* log
 
 int upload_inputs(l3_engine* e, const float* video, const float* audio, const float* labels) {
     const int B = e->B;
-    e->staged = false;      // an explicit upload supersedes a staged batch
-    e->gains_valid = false;
+    e->feed.inputs_replaced(BATCH_SINGLE);
     if (video) HIPCHK(e, hipMemcpyAsync(e->video, video, (size_t)B * 224 * 224 * 3 * 4, hipMemcpyHostToDevice, e->stream));
     if (audio) HIPCHK(e, hipMemcpyAsync(e->audio, audio, (size_t)B * AUDIO_T * 4, hipMemcpyHostToDevice, e->stream));
     if (labels) HIPCHK(e, hipMemcpyAsync(e->labels, labels, (size_t)B * 2 * 4, hipMemcpyHostToDevice, e->stream));
@@ -1891,12 +1861,7 @@ void l3_destroy(l3_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->cfg.device);
     if (e->stream) (void)l3::stream_wait(e->stream);
-    if (e->copy_stream) {
-        (void)l3::stream_wait(e->copy_stream);
-        (void)hipStreamDestroy(e->copy_stream);
-        (void)hipEventDestroy(e->ev_staged);
-        (void)hipEventDestroy(e->ev_adopted);
-    }
+    e->feed.destroy();
     if (e->side) {
         (void)l3::stream_wait(e->side);
         (void)hipStreamDestroy(e->side);
@@ -1914,8 +1879,6 @@ void l3_destroy(l3_engine* e) {
     if (e->ev_res_b) (void)hipEventDestroy(e->ev_res_b);
     for (auto ev : e->ev_step)
         if (ev) (void)hipEventDestroy(ev);
-    if (e->ev_rep_staged) (void)hipEventDestroy(e->ev_rep_staged);
-    if (e->ev_rep_adopted) (void)hipEventDestroy(e->ev_rep_adopted);
     if (e->res_host) (void)hipHostFree(e->res_host);
     e->bufs.clear();
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
@@ -2066,160 +2029,68 @@ int l3_upload_batch(l3_engine* e, const float* video, const float* audio, const 
     return upload_inputs(e, video, audio, labels);
 }
 
+// The raw entry points below: an argument check, then the feed (kernels.h BatchFeed) sends the batch and, for a single batch,
+// converts it into the float inputs.
 int l3_upload_batch_raw(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32) {
     if (!e) return L3_EINVAL;
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    const int B = e->B;
-    e->staged = false;      // an explicit upload supersedes a staged batch
-    e->gains_valid = false;
-    if (video_u8) {
-        HIPCHK(e, hipMemcpyAsync(e->raw_video, video_u8, (size_t)B * 224 * 224 * 3, hipMemcpyHostToDevice, e->stream));
-        preprocess_video(e->raw_video, e->video, (int64_t)B * 224 * 224 * 3, e->stream);
-    }
-    if (audio_i16) {
-        HIPCHK(e, hipMemcpyAsync(e->raw_audio, audio_i16, (size_t)B * AUDIO_T * 2, hipMemcpyHostToDevice, e->stream));
-        preprocess_audio(e->raw_audio, e->audio, (int64_t)B * AUDIO_T, e->stream);
-    }
-    if (labels_i32) {
-        HIPCHK(e, hipMemcpyAsync(e->raw_labels, labels_i32, (size_t)B * 2 * 4, hipMemcpyHostToDevice, e->stream));
-        labels_onehot(e->raw_labels, e->labels, (int64_t)B * 2, e->stream);
-    }
-    HIPCHK(e, l3::stream_wait(e->stream));
-    return L3_OK;
+    return e->feed.upload(BATCH_SINGLE, 1, video_u8, audio_i16, labels_i32, nullptr, nullptr, e->stream, &e->err);
 }
 
-// the device buffers of the augmentation records; the engine's frames are already 224 x 224, so a record must not move the crop
-static int aug_prepare(l3_engine* e, const l3_augment_params* params, const double* u, int rows = 0) {
+// what every augmented entry point checks: the engine's frames are already 224 x 224, so a record must not move the crop
+static int aug_prepare(l3_engine* e, const l3_augment_params* params, const double* u, int rows) {
     if (!params || !u) {
         e->err = "augmented batch without its parameter records or gain draws";
         return L3_EINVAL;
     }
-    for (int i = 0; i < (rows > 0 ? rows : e->B); ++i)
+    for (int i = 0; i < rows; ++i)
         if (params[i].start_x != 0 || params[i].start_y != 0) {
             e->err = "augmentation record " + std::to_string(i) + ": the engine's frames are 224 x 224, the crop must start at (0, 0)";
             return L3_EINVAL;
         }
-    if (e->aug_gains) return L3_OK;
-    int rc;
-    const size_t B = (size_t)e->B;
-    if ((rc = dev_alloc_t(e, &e->aug_params, B))) return rc;
-    if ((rc = dev_alloc_t(e, &e->nxt_aug_params, B))) return rc;
-    if ((rc = dev_alloc_t(e, &e->aug_u, B))) return rc;
-    if ((rc = dev_alloc_t(e, &e->nxt_aug_u, B))) return rc;
-    return dev_alloc_t(e, &e->aug_gains, B);
+    return L3_OK;
+}
+
+static int single_raw_aug(l3_engine* e, const char* name, bool stage, const uint8_t* video_u8, const int16_t* audio_i16,
+                          const int32_t* labels_i32, const l3_augment_params* params, const double* u) {
+    if (!e) return L3_EINVAL;
+    if (!video_u8 || !audio_i16 || !labels_i32) {
+        e->err = std::string(name) + ": NULL batch pointer";
+        return L3_EINVAL;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    if (int rc = aug_prepare(e, params, u, e->B)) return rc;
+    const AugmentParams* p = reinterpret_cast<const AugmentParams*>(params);
+    return stage ? e->feed.stage(BATCH_SINGLE, 1, video_u8, audio_i16, labels_i32, p, u, &e->err)
+                 : e->feed.upload(BATCH_SINGLE, 1, video_u8, audio_i16, labels_i32, p, u, e->stream, &e->err);
 }
 
 // data/avc/sample.py:146-162,241-281 on the batch, in the pass that l3_upload_batch_raw spends on train.py:186,189
 int l3_upload_batch_raw_aug(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
                             const l3_augment_params* params, const double* u) {
-    if (!e) return L3_EINVAL;
-    if (!video_u8 || !audio_i16 || !labels_i32) {
-        e->err = "l3_upload_batch_raw_aug: NULL batch pointer";
-        return L3_EINVAL;
-    }
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    int rc = aug_prepare(e, params, u);
-    if (rc) return rc;
-    const int B = e->B;
-    e->staged = false;      // an explicit upload supersedes a staged batch
-    HIPCHK(e, hipMemcpyAsync(e->aug_params, params, (size_t)B * sizeof(l3::AugmentParams), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->aug_u, u, (size_t)B * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->raw_video, video_u8, (size_t)B * 224 * 224 * 3, hipMemcpyHostToDevice, e->stream));
-    augment_video(e->raw_video, B, 224, 224, e->aug_params, nullptr, e->video, e->stream);
-    HIPCHK(e, hipMemcpyAsync(e->raw_audio, audio_i16, (size_t)B * AUDIO_T * 2, hipMemcpyHostToDevice, e->stream));
-    augment_audio(e->raw_audio, B, AUDIO_T, e->aug_u, nullptr, e->audio, e->aug_gains, e->stream);
-    HIPCHK(e, hipMemcpyAsync(e->raw_labels, labels_i32, (size_t)B * 2 * 4, hipMemcpyHostToDevice, e->stream));
-    labels_onehot(e->raw_labels, e->labels, (int64_t)B * 2, e->stream);
-    HIPCHK(e, l3::stream_wait(e->stream));
-    e->gains_valid = true;
-    return L3_OK;
-}
-
-// the copy stream of the staged batches (l3_stage_batch_raw*, l3_replicas_stage_raw*) and the events of the former
-static int ensure_copy_stream(l3_engine* e) {
-    if (e->copy_stream) return L3_OK;
-    HIPCHK(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-    HIPCHK(e, hipEventCreateWithFlags(&e->ev_staged, hipEventDisableTiming));
-    HIPCHK(e, hipEventCreateWithFlags(&e->ev_adopted, hipEventDisableTiming));
-    return L3_OK;
-}
-
-static int stage_batch(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
-                       const l3_augment_params* params, const double* u) {
-    const int B = e->B;
-    int rc = ensure_copy_stream(e);
-    if (rc) return rc;
-    if (!e->nxt_video) {
-        if ((rc = dev_alloc_t(e, &e->nxt_video, (size_t)B * 224 * 224 * 3))) return rc;
-        if ((rc = dev_alloc_t(e, &e->nxt_audio, (size_t)B * AUDIO_T))) return rc;
-        if ((rc = dev_alloc_t(e, &e->nxt_labels, (size_t)B * 2))) return rc;
-    }
-    // the staging buffers are free once the scaling kernels of the batch adopted from them have run
-    if (e->adopted_once) HIPCHK(e, hipStreamWaitEvent(e->copy_stream, e->ev_adopted, 0));
-    // host memory is the caller's (pageable) array: these calls return once it has been read, while the
-    // device side of the copy overlaps whatever the engine's streams are running
-    HIPCHK(e, hipMemcpyAsync(e->nxt_video, video_u8, (size_t)B * 224 * 224 * 3, hipMemcpyHostToDevice, e->copy_stream));
-    HIPCHK(e, hipMemcpyAsync(e->nxt_audio, audio_i16, (size_t)B * AUDIO_T * 2, hipMemcpyHostToDevice, e->copy_stream));
-    HIPCHK(e, hipMemcpyAsync(e->nxt_labels, labels_i32, (size_t)B * 2 * 4, hipMemcpyHostToDevice, e->copy_stream));
-    if (params) {
-        HIPCHK(e, hipMemcpyAsync(e->nxt_aug_params, params, (size_t)B * sizeof(l3::AugmentParams), hipMemcpyHostToDevice, e->copy_stream));
-        HIPCHK(e, hipMemcpyAsync(e->nxt_aug_u, u, (size_t)B * sizeof(double), hipMemcpyHostToDevice, e->copy_stream));
-    }
-    HIPCHK(e, hipEventRecord(e->ev_staged, e->copy_stream));
-    e->staged = true;
-    e->staged_aug = params != nullptr;
-    return L3_OK;
+    return single_raw_aug(e, "l3_upload_batch_raw_aug", false, video_u8, audio_i16, labels_i32, params, u);
 }
 
 int l3_stage_batch_raw(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32) {
     if (!e || !video_u8 || !audio_i16 || !labels_i32) return L3_EINVAL;
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    return stage_batch(e, video_u8, audio_i16, labels_i32, nullptr, nullptr);
+    return e->feed.stage(BATCH_SINGLE, 1, video_u8, audio_i16, labels_i32, nullptr, nullptr, &e->err);
 }
 
 int l3_stage_batch_raw_aug(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
                            const l3_augment_params* params, const double* u) {
-    if (!e) return L3_EINVAL;
-    if (!video_u8 || !audio_i16 || !labels_i32) {
-        e->err = "l3_stage_batch_raw_aug: NULL batch pointer";
-        return L3_EINVAL;
-    }
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    int rc = aug_prepare(e, params, u);
-    if (rc) return rc;
-    return stage_batch(e, video_u8, audio_i16, labels_i32, params, u);
-}
-
-// a staged batch becomes the current one: in stream order behind the previous step, which still read
-// the float inputs
-static int adopt_staged(l3_engine* e) {
-    if (!e->staged) return L3_OK;
-    const int B = e->B;
-    HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_staged, 0));
-    if (e->staged_aug) {
-        augment_video(e->nxt_video, B, 224, 224, e->nxt_aug_params, nullptr, e->video, e->stream);
-        augment_audio(e->nxt_audio, B, AUDIO_T, e->nxt_aug_u, nullptr, e->audio, e->aug_gains, e->stream);
-    } else {
-        preprocess_video(e->nxt_video, e->video, (int64_t)B * 224 * 224 * 3, e->stream);
-        preprocess_audio(e->nxt_audio, e->audio, (int64_t)B * AUDIO_T, e->stream);
-    }
-    e->gains_valid = e->staged_aug;
-    labels_onehot(e->nxt_labels, e->labels, (int64_t)B * 2, e->stream);
-    HIPCHK(e, hipEventRecord(e->ev_adopted, e->stream));
-    e->adopted_once = true;
-    e->staged = false;
-    return L3_OK;
+    return single_raw_aug(e, "l3_stage_batch_raw_aug", true, video_u8, audio_i16, labels_i32, params, u);
 }
 
 int l3_batch_gains(l3_engine* e, double* gains) {
     if (!e || !gains) return L3_EINVAL;
-    if (!e->gains_valid) {
+    if (!e->feed.gains_valid) {
         e->err = "l3_batch_gains: the current batch was not augmented";
         return L3_ESTATE;
     }
     HIPCHK(e, hipSetDevice(e->cfg.device));
     HIPCHK(e, l3::stream_wait(e->stream));
-    HIPCHK(e, hipMemcpy(gains, e->aug_gains, (size_t)e->B * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(gains, e->feed.gains, (size_t)e->B * sizeof(double), hipMemcpyDeviceToHost));
     return L3_OK;
 }
 
@@ -2237,7 +2108,7 @@ int l3_step_forward(l3_engine* e, int training) {
         const int slot = (int)(e->steps_enqueued & 1);
         if (e->ev_step_set[slot]) HIPCHK(e, l3::event_wait(e->ev_step[slot]));
     }
-    int rc = adopt_staged(e);
+    int rc = e->feed.adopt(BATCH_SINGLE, e->stream, &e->err);      // a staged single batch: in stream order behind the previous step
     if (rc) return rc;
     rc = forward_all(e, training != 0);
     if (rc) return rc;
@@ -2250,7 +2121,7 @@ int l3_step_forward(l3_engine* e, int training) {
 int l3_tower_step(l3_engine* e, int tower, int backward) {
     if (!e || (tower != 0 && tower != 1)) return L3_EINVAL;
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    int rc = adopt_staged(e);
+    int rc = e->feed.adopt(BATCH_SINGLE, e->stream, &e->err);      // a staged single batch: in stream order behind the previous step
     if (rc) return rc;
     Tower& tw = tower == 0 ? e->vis : e->aud;
     if (tower == 1 && (rc = run_frontend(e))) return rc;
@@ -2342,16 +2213,6 @@ static int rep_refuse(l3_engine* e, const char* name, int replicas) {
     return L3_OK;
 }
 
-static int rep_grow_raw(l3_engine* e, int set, size_t rows, bool aug) {
-    int rc;
-    if ((rc = dev_grow_t(e, &e->rep_raw_video[set], &e->rep_raw_video_cap[set], rows * 224 * 224 * 3))) return rc;
-    if ((rc = dev_grow_t(e, &e->rep_raw_audio[set], &e->rep_raw_audio_cap[set], rows * AUDIO_T))) return rc;
-    if ((rc = dev_grow_t(e, &e->rep_raw_labels[set], &e->rep_raw_labels_cap[set], rows * 2))) return rc;
-    if (!aug) return L3_OK;
-    if ((rc = dev_grow_t(e, &e->rep_aug_params[set], &e->rep_aug_params_cap[set], rows))) return rc;
-    return dev_grow_t(e, &e->rep_aug_u[set], &e->rep_aug_u_cap[set], rows);
-}
-
 int l3_replicas_upload(l3_engine* e, const float* video, const float* audio, const float* labels, int replicas) {
     if (!e) return L3_EINVAL;
     int rc = rep_refuse(e, "l3_replicas_upload", replicas);
@@ -2361,22 +2222,10 @@ int l3_replicas_upload(l3_engine* e, const float* video, const float* audio, con
         return L3_EINVAL;
     }
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    const size_t rows = (size_t)replicas * e->B;
-    if ((rc = dev_grow_t(e, &e->rep_video, &e->rep_video_cap, rows * 224 * 224 * 3))) return rc;
-    if ((rc = dev_grow_t(e, &e->rep_audio, &e->rep_audio_cap, rows * AUDIO_T))) return rc;
-    if ((rc = dev_grow_t(e, &e->rep_labels, &e->rep_labels_cap, rows * 2))) return rc;
-    e->rep_staged_n = 0;        // an explicit upload supersedes a staged global batch
-    e->rep_n = 0;
-    HIPCHK(e, hipMemcpyAsync(e->rep_video, video, rows * 224 * 224 * 3 * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->rep_audio, audio, rows * AUDIO_T * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->rep_labels, labels, rows * 2 * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, l3::stream_wait(e->stream));
-    e->rep_n = replicas;
-    e->rep_kind = 1;
-    return L3_OK;
+    return e->feed.upload_float(replicas, video, audio, labels, e->stream, &e->err);
 }
 
-// the stored dtypes of a global batch into set 0 on the engine's stream (upload) or into set 1 on the copy stream (stage)
+// the stored dtypes of a global batch: resident at once (upload) or behind the running step (stage)
 static int rep_send_raw(l3_engine* e, const char* name, bool stage, const uint8_t* video_u8, const int16_t* audio_i16,
                         const int32_t* labels_i32, const l3_augment_params* params, const double* u, bool aug, int replicas) {
     if (!e) return L3_EINVAL;
@@ -2387,41 +2236,10 @@ static int rep_send_raw(l3_engine* e, const char* name, bool stage, const uint8_
         return L3_EINVAL;
     }
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    const size_t rows = (size_t)replicas * e->B;
-    if (aug && (rc = aug_prepare(e, params, u, (int)rows))) return rc;
-    const int set = stage ? 1 : 0;
-    if ((rc = rep_grow_raw(e, set, rows, aug))) return rc;
-    hipStream_t s = e->stream;
-    if (stage) {
-        if ((rc = ensure_copy_stream(e))) return rc;
-        if (!e->ev_rep_staged) {
-            HIPCHK(e, hipEventCreateWithFlags(&e->ev_rep_staged, hipEventDisableTiming));
-            HIPCHK(e, hipEventCreateWithFlags(&e->ev_rep_adopted, hipEventDisableTiming));
-        }
-        s = e->copy_stream;
-        // set 1 was the current set until the last adoption: its readers are the steps enqueued before that adoption's event
-        if (e->rep_adopted_once) HIPCHK(e, hipStreamWaitEvent(s, e->ev_rep_adopted, 0));
-    } else {
-        e->rep_staged_n = 0;        // an explicit upload supersedes a staged global batch
-        e->rep_n = 0;
-    }
-    HIPCHK(e, hipMemcpyAsync(e->rep_raw_video[set], video_u8, rows * 224 * 224 * 3, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(e->rep_raw_audio[set], audio_i16, rows * AUDIO_T * 2, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(e->rep_raw_labels[set], labels_i32, rows * 2 * 4, hipMemcpyHostToDevice, s));
-    if (aug) {
-        HIPCHK(e, hipMemcpyAsync(e->rep_aug_params[set], params, rows * sizeof(l3::AugmentParams), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(e->rep_aug_u[set], u, rows * sizeof(double), hipMemcpyHostToDevice, s));
-    }
-    if (stage) {
-        HIPCHK(e, hipEventRecord(e->ev_rep_staged, s));
-        e->rep_staged_n = replicas;
-        e->rep_staged_aug = aug;
-        return L3_OK;
-    }
-    HIPCHK(e, l3::stream_wait(s));
-    e->rep_n = replicas;
-    e->rep_kind = aug ? 3 : 2;
-    return L3_OK;
+    if (aug && (rc = aug_prepare(e, params, u, replicas * e->B))) return rc;
+    const AugmentParams* p = reinterpret_cast<const AugmentParams*>(params);
+    return stage ? e->feed.stage(BATCH_GLOBAL, replicas, video_u8, audio_i16, labels_i32, p, u, &e->err)
+                 : e->feed.upload(BATCH_GLOBAL, replicas, video_u8, audio_i16, labels_i32, p, u, e->stream, &e->err);
 }
 
 int l3_replicas_upload_raw(l3_engine* e, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32, int replicas) {
@@ -2439,52 +2257,21 @@ int l3_replicas_stage_raw_aug(l3_engine* e, const uint8_t* video_u8, const int16
     return rep_send_raw(e, "l3_replicas_stage_raw_aug", true, video_u8, audio_i16, labels_i32, params, u, true, replicas);
 }
 
-// A staged global batch becomes the resident one: the two sets change places in stream order behind the previous step.  Then the
-// refusals, against the replica count of the batch that is resident now.
+// A staged global batch becomes the resident one in stream order behind the previous step.  Then the refusals, against the replica
+// count of the batch that is resident now; that batch supersedes a staged single batch.
 static int rep_begin(l3_engine* e, const char* name) {
-    if (e->rep_staged_n > 0) {
-        HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_rep_staged, 0));
-        std::swap(e->rep_raw_video[0], e->rep_raw_video[1]), std::swap(e->rep_raw_video_cap[0], e->rep_raw_video_cap[1]);
-        std::swap(e->rep_raw_audio[0], e->rep_raw_audio[1]), std::swap(e->rep_raw_audio_cap[0], e->rep_raw_audio_cap[1]);
-        std::swap(e->rep_raw_labels[0], e->rep_raw_labels[1]), std::swap(e->rep_raw_labels_cap[0], e->rep_raw_labels_cap[1]);
-        std::swap(e->rep_aug_params[0], e->rep_aug_params[1]), std::swap(e->rep_aug_params_cap[0], e->rep_aug_params_cap[1]);
-        std::swap(e->rep_aug_u[0], e->rep_aug_u[1]), std::swap(e->rep_aug_u_cap[0], e->rep_aug_u_cap[1]);
-        // everything that read what is set 1 from here on is in front of this event
-        HIPCHK(e, hipEventRecord(e->ev_rep_adopted, e->stream));
-        e->rep_adopted_once = true;
-        e->rep_n = e->rep_staged_n;
-        e->rep_kind = e->rep_staged_aug ? 3 : 2;
-        e->rep_staged_n = 0;
-    }
-    if (e->rep_n < 1) {
+    BatchFeed& f = e->feed;
+    int rc = f.adopt(BATCH_GLOBAL, e->stream, &e->err);
+    if (rc) return rc;
+    if (f.cur.form != BATCH_GLOBAL && f.cur.form != BATCH_GLOBAL_FLOAT) {
         e->err = std::string(name) + ": no resident global batch (l3_replicas_upload* or l3_replicas_stage_raw* first); batch " +
                  std::to_string(e->B) + ", global_batch " + std::to_string(e->cfg.global_batch > 0 ? e->cfg.global_batch : e->B);
         return L3_ESTATE;
     }
-    e->staged = false;      // the resident global batch supersedes a staged single batch
-    return rep_refuse(e, name, e->rep_n);
+    f.inputs_replaced(BATCH_SINGLE);
+    return rep_refuse(e, name, f.cur.slices);
 }
 
-// slice r of the resident global batch into the engine's inputs, by the kernels of l3_upload_batch_raw(_aug) from its rows
-static int rep_adopt_slice(l3_engine* e, int r) {
-    const size_t B = (size_t)e->B, pv = B * 224 * 224 * 3, pa = B * AUDIO_T;
-    if (e->rep_kind == 1) {
-        HIPCHK(e, hipMemcpyAsync(e->video, e->rep_video + r * pv, pv * 4, hipMemcpyDeviceToDevice, e->stream));
-        HIPCHK(e, hipMemcpyAsync(e->audio, e->rep_audio + r * pa, pa * 4, hipMemcpyDeviceToDevice, e->stream));
-        HIPCHK(e, hipMemcpyAsync(e->labels, e->rep_labels + r * B * 2, B * 2 * 4, hipMemcpyDeviceToDevice, e->stream));
-    } else {
-        if (e->rep_kind == 3) {
-            augment_video(e->rep_raw_video[0] + r * pv, (int)B, 224, 224, e->rep_aug_params[0] + r * B, nullptr, e->video, e->stream);
-            augment_audio(e->rep_raw_audio[0] + r * pa, (int)B, AUDIO_T, e->rep_aug_u[0] + r * B, nullptr, e->audio, e->aug_gains, e->stream);
-        } else {
-            preprocess_video(e->rep_raw_video[0] + r * pv, e->video, (int64_t)pv, e->stream);
-            preprocess_audio(e->rep_raw_audio[0] + r * pa, e->audio, (int64_t)pa, e->stream);
-        }
-        labels_onehot(e->rep_raw_labels[0] + r * B * 2, e->labels, (int64_t)B * 2, e->stream);
-    }
-    e->gains_valid = e->rep_kind == 3;
-    return L3_OK;
-}
 
 static int rep_accumulators(l3_engine* e) {
     if (e->rep_acc) return L3_OK;
@@ -2498,10 +2285,10 @@ int l3_step_replicas(l3_engine* e, float lr) {
     HIPCHK(e, hipSetDevice(e->cfg.device));
     int rc = rep_begin(e, "l3_step_replicas");
     if (rc) return rc;
-    const int R = e->rep_n, nb = (int)e->buckets.size();
+    const int R = e->feed.cur.slices, nb = (int)e->buckets.size();
     if (R > 1 && (rc = rep_accumulators(e))) return rc;
     for (int r = 0; r < R; ++r) {
-        if ((rc = rep_adopt_slice(e, r))) return rc;
+        if ((rc = e->feed.convert(r, e->stream, &e->err))) return rc;
         // (the two-steps-in-flight wait inside is on the event of the global step two back: steps_enqueued moves with the update)
         if ((rc = l3_step_forward(e, 1))) return rc;
         // the slice's batch statistics are final with its forward pass: slot r of the replicas' buffer
@@ -2528,12 +2315,12 @@ int l3_eval_replicas(l3_engine* e, float* loss, float* acc) {
     HIPCHK(e, hipSetDevice(e->cfg.device));
     int rc = rep_begin(e, "l3_eval_replicas");
     if (rc) return rc;
-    const int R = e->rep_n;
+    const int R = e->feed.cur.slices;
     if (R > 1 && (rc = rep_accumulators(e))) return rc;
     e->bn_replicas_armed = 0;
     e->bn_packed = false;
     for (int r = 0; r < R; ++r) {
-        if ((rc = rep_adopt_slice(e, r))) return rc;
+        if ((rc = e->feed.convert(r, e->stream, &e->err))) return rc;
         if ((rc = forward_all(e, false))) return rc;
         loss_and_head_backward(e, false);
         if (R > 1) arena_fold(e->rep_stats, e->stats, 2, r == 0 ? ARENA_FOLD_SET : r == R - 1 ? ARENA_FOLD_OUT : ARENA_FOLD_ADD, e->stream);

@@ -357,6 +357,61 @@ private:
     uint64_t tabs_on_device = ~(uint64_t)0;          // generation of `tabs` that d_tabs holds
 };
 
+// A training batch in the stored dtypes (uint8 frames, int16 PCM, int32 labels, optional augmentation records and gain draws) on
+// its way into an engine's float inputs (batch_feed.hip).  A batch is `slices` x B rows: one slice for a single batch, one per
+// replica for the global batch of serial replicas.
+enum BatchForm { BATCH_NONE, BATCH_SINGLE, BATCH_GLOBAL, BATCH_GLOBAL_FLOAT };
+struct RawBatch {
+    uint8_t* video = nullptr;
+    int16_t* audio = nullptr;
+    int32_t* labels = nullptr;
+    AugmentParams* params = nullptr;
+    double* u = nullptr;
+    size_t cap_video = 0, cap_audio = 0, cap_labels = 0, cap_params = 0, cap_u = 0;
+    BatchForm form = BATCH_NONE;        // what the set holds (BATCH_GLOBAL_FLOAT: the feed's float buffers hold it, not the set)
+    int slices = 0;
+    bool aug = false;                   // it carries records: its conversion augments instead of scaling
+};
+// The owner of such batches for an engine: the resident one and the one being staged, the float form of a resident global batch,
+// the copy stream with its event pair, and the gains of the last augmented conversion.  Every method returns L3_OK, L3_ENOMEM or
+// L3_EHIP with the reason in *err; the device must be current.  The ordering rule of the two sets stands at stage() / adopt().
+struct BatchFeed {
+    RawBatch cur, nxt;
+    double* gains = nullptr;            // of the B rows last converted with records (allocated by the first augmented batch)
+    bool gains_valid = false;
+
+    // B rows of T samples per slice; conversions write the owner's float inputs
+    void bind(int rows, int samples, float* video, float* audio, float* labels);
+    // The owner has written (SINGLE) or is about to replace (a global form) the batch by an explicit upload: that supersedes a
+    // staged batch of the same kind.
+    void inputs_replaced(BatchForm form);
+    // Into the resident set on s, and waits for s.  BATCH_SINGLE: converted at once; a null input stays as it was.
+    int upload(BatchForm form, int slices, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
+               const AugmentParams* params, const double* u, hipStream_t s, std::string* err);
+    int upload_float(int slices, const float* video, const float* audio, const float* labels, hipStream_t s, std::string* err);
+    // Into the staged set over the copy stream, without waiting.
+    int stage(BatchForm form, int slices, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
+              const AugmentParams* params, const double* u, std::string* err);
+    // A staged batch of this form becomes the resident one in s's order (a single batch is converted there); else nothing.
+    int adopt(BatchForm form, hipStream_t s, std::string* err);
+    // Slice r of the resident batch -> float inputs (and gains): augment_video / augment_audio or preprocess_video /
+    // preprocess_audio, then labels_onehot; device-to-device copies of the float form.
+    int convert(int r, hipStream_t s, std::string* err, bool video = true, bool audio = true, bool labels = true);
+    void destroy();                     // waits for the copy stream; frees it, the events and every buffer
+
+private:
+    int send(RawBatch& dst, BatchForm form, int slices, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
+             const AugmentParams* params, const double* u, hipStream_t s, std::string* err);
+    int B = 0, T = 0;
+    float *out_video = nullptr, *out_audio = nullptr, *out_labels = nullptr;
+    float *f_video = nullptr, *f_audio = nullptr, *f_labels = nullptr;
+    size_t cap_f_video = 0, cap_f_audio = 0, cap_f_labels = 0;
+    DeviceBufs bufs;
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t ev_staged = nullptr, ev_adopted = nullptr;
+    bool adopted_once = false;
+};
+
 // head: dense + softmax + categorical cross-entropy
 void dense_fwd(const float* x, const float* w, const float* b, float* y, int B, int K, int N, int relu,
                hipStream_t s);

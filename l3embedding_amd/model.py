@@ -448,6 +448,24 @@ class L3Model(object):
             raise ValueError('raw batches need uint8 video AND int16 audio')
         return False
 
+    def _feed(self, e, v, a, l, aug=None, stage=False):
+        """How a split batch reaches the engine: raw (stored dtypes straight to the GPU; the scaling of train.py:186,189 happens
+        there, bit-exact) or float, with the augmentation records of data/avc/sample.py:146-162,241-281 or without, as the global
+        batch of serial replicas or as this rank's own, uploaded now or staged behind the running step."""
+        raw = self._is_raw(v, a)
+        if aug is not None and not raw:
+            raise ValueError('only raw batches (uint8 video, int16 audio) can be augmented: the arithmetic of '
+                             'data/avc/sample.py is defined on the stored dtypes')
+        serial = self.replicas > 1 and self.serial
+        if not raw:
+            return e.replicas_upload(v, a, l, self.replicas) if serial else e.upload_batch(v, a, l)
+        if serial:
+            name, tail = 'replicas_stage_raw' if stage else 'replicas_upload_raw', (self.replicas,)
+        else:
+            name, tail = 'stage_batch_raw' if stage else 'upload_batch_raw', ()
+        records = () if aug is None else (aug, aug['u_gain'])
+        return getattr(e, name + ('_aug' if records else ''))(v, a, np.asarray(l).astype(np.int32), *(records + tail))
+
     def train_on_batch(self, x, y):
         self._launch_train(x, y, staged=False)
         return self._finish_train()
@@ -458,21 +476,11 @@ class L3Model(object):
         if self.optimizer is None:
             raise RuntimeError('You must compile a model before training/testing. Use `model.compile(optimizer, loss)`.')
         v, a, l, gb = self._split(x, y)
-        raw = self._is_raw(v, a)
         aug = self._split_augment(x)
-        if aug is not None and not raw:
-            raise ValueError('only raw batches (uint8 video, int16 audio) can be augmented: the arithmetic of '
-                             'data/avc/sample.py is defined on the stored dtypes')
         if self.replicas > 1 and self.serial:
-            R = self.replicas
             e = self._ensure_engine(self._serial_slice(len(v)), global_batch=gb)
             if not staged:
-                if aug is not None:
-                    e.replicas_upload_raw_aug(v, a, np.asarray(l).astype(np.int32), aug, aug['u_gain'], R)
-                elif raw:
-                    e.replicas_upload_raw(v, a, np.asarray(l).astype(np.int32), R)
-                else:
-                    e.replicas_upload(v, a, l, R)
+                self._feed(e, v, a, l, aug)
             e.step_replicas(self.optimizer.lr)
             self._inflight = (e, len(v), gb)
             return
@@ -487,12 +495,7 @@ class L3Model(object):
             else:
                 e._trainer = DataParallelTrainer(e, self.device, self.replicas, self._dist().get_rank(), stream=self._tstream)
         if not staged:
-            if aug is not None:      # ... and augmented in that same pass (data/avc/sample.py:146-162,241-281)
-                e.upload_batch_raw_aug(v, a, np.asarray(l).astype(np.int32), aug, aug['u_gain'])
-            elif raw:      # stored dtypes straight to the GPU; train.py:186,189 scaling happens there, bit-exact
-                e.upload_batch_raw(v, a, np.asarray(l).astype(np.int32))
-            else:
-                e.upload_batch(v, a, l)
+            self._feed(e, v, a, l, aug)
         if dp:
             e._trainer.step(self.optimizer.lr)
         else:
@@ -527,16 +530,7 @@ class L3Model(object):
         v, a, l, _ = self._split(x, y)
         if len(v) != n_local or not self._is_raw(v, a):
             return False
-        aug = self._split_augment(x)
-        if self.replicas > 1 and self.serial:
-            if aug is not None:
-                e.replicas_stage_raw_aug(v, a, np.asarray(l).astype(np.int32), aug, aug['u_gain'], self.replicas)
-            else:
-                e.replicas_stage_raw(v, a, np.asarray(l).astype(np.int32), self.replicas)
-        elif aug is not None:
-            e.stage_batch_raw_aug(v, a, np.asarray(l).astype(np.int32), aug, aug['u_gain'])
-        else:
-            e.stage_batch_raw(v, a, np.asarray(l).astype(np.int32))
+        self._feed(e, v, a, l, self._split_augment(x), stage=True)
         return True
 
     def _finish_train(self):
@@ -555,18 +549,12 @@ class L3Model(object):
         v, a, l, gb = self._split(x, y)
         if self.replicas > 1 and self.serial:
             e = self._ensure_engine(self._serial_slice(len(v)), global_batch=gb)
-            if self._is_raw(v, a):
-                e.replicas_upload_raw(v, a, np.asarray(l).astype(np.int32), self.replicas)
-            else:
-                e.replicas_upload(v, a, l, self.replicas)
+            self._feed(e, v, a, l)
             return list(e.eval_replicas())
         e = self._ensure_engine(len(v), global_batch=gb if self.replicas > 1 else 0)
-        if self._is_raw(v, a):
-            e.upload_batch_raw(v, a, np.asarray(l).astype(np.int32))
-            e.step_forward(training=False)
-            loss, acc = e.step_results()
-        else:
-            loss, acc = e.eval_step(v, a, l)
+        self._feed(e, v, a, l)
+        e.step_forward(training=False)
+        loss, acc = e.step_results()
         if self.replicas > 1:
             import torch
             dist = self._dist()
