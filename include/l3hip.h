@@ -889,6 +889,22 @@ int l3_forest_score(l3_forest *m, const float *X, const struct l3_feat *f, int64
                     const int32_t *prefix, int n_prefix, const int32_t *labels, const int64_t *files, int64_t n_files,
                     int64_t chunk_rows, int64_t stage_bytes, int32_t *pred, int64_t *correct, double *file_mean, int32_t *file_pred,
                     double *proba);
+/* classifier/train.py:169-227 (what oob_score=True adds to clf.fit, sklearn's _set_oob_score, at every forest size of the
+ * n_estimators grid of :623-630): all rows of the handle's resident matrix -- the one the fit left there, or one set again with
+ * l3_forest_set_data[_dev] after l3_forest_set_trees -- scored by the trees whose bootstrap missed them, for the first prefix[g]
+ * trees of the resident forest for every g at once.  boot (n_trees, n): the bootstrap multiplicities the trees were
+ * fitted with; n_trees must be the forest's tree count.  It is uploaded in slabs of 64 trees and kept as one 64-bit word per (row,
+ * pass of 64 trees): bit j is set iff tree 64 pass + j has multiplicity 0 at the row.  prefix, labels, chunk_rows and stage_bytes
+ * are l3_forest_score's.  Outputs, each NULL when not wanted (a NULL sums is never allocated or copied): pred (n_prefix, n) int32,
+ * the first of the largest sums, 0 for a row that no tree of the prefix left out; correct (n_prefix) int64, the rows whose pred is
+ * their label (needs labels); n_oob (n_prefix, n) int32, the trees of the prefix that left the row out; sums (n_prefix, n,
+ * n_classes) float64, count / total of the leaf added in float64 strictly in tree order over those trees alone.  Nothing is divided
+ * by a tree count here: sklearn's normalisation is the caller's.  Everything is checked on the host before anything is launched:
+ * L3_ESTATE without a forest or without a resident matrix; L3_EINVAL for another tree count than the forest's, a matrix of another
+ * width than the forest's, prefixes that are not strictly increasing or lie outside [1, n_trees], labels outside the classes, correct
+ * without labels, or no output. */
+int l3_forest_oob(l3_forest *m, const uint16_t *boot, int n_trees, const int32_t *prefix, int n_prefix, const int32_t *labels,
+                  int64_t chunk_rows, int64_t stage_bytes, int32_t *pred, int64_t *correct, int32_t *n_oob, double *sums);
 /* classifier/train.py:169-227 (the fit's binning, for tests): cuts (D, L3_FOREST_MAX_CUTS) and ncuts (D) of the last fit */
 int l3_forest_get_cuts(l3_forest *m, float *cuts, int32_t *ncuts);
 /* classifier/train.py:169-227 (the fit's course, for profiles): the last fit's levels -> their number; up to max_levels entries each of

@@ -257,6 +257,7 @@ SIGNATURES = {
     'l3_forest_predict_proba_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     'l3_forest_score': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 5),
+    'l3_forest_oob': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4),
     'l3_forest_get_cuts': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'l3_forest_level_stats': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
@@ -1790,6 +1791,7 @@ FOREST_MAX_DRAWS = 256           # L3_FOREST_MAX_DRAWS
 FOREST_MAX_BIN_SAMPLE = 8192     # L3_FOREST_MAX_BIN_SAMPLE
 FOREST_NARROW_ROWS = 64          # L3_FOREST_NARROW_ROWS
 FOREST_SCORE_OUTPUTS = ('pred', 'correct', 'file_mean', 'file_pred', 'proba')          # l3_forest_score's, in its order
+FOREST_OOB_OUTPUTS = ('pred', 'correct', 'n_oob', 'sums')          # l3_forest_oob's, in its order
 FOREST_TREE_ARRAYS = ('tree_off', 'left', 'right', 'feature', 'threshold', 'bin', 'counts', 'n_distinct')
 
 
@@ -1915,6 +1917,30 @@ class Forest(object):
         check(self.lib.l3_forest_score(self.h, _ptr(x), None if feat is None else feat.h, int(lo), int(hi), int(D), 1 if resident else 0,
                                        _ptr(p), p.size, _ptr(y), _ptr(fl), F, int(chunk_rows), int(stage_bytes),
                                        *(_ptr(out.get(k)) for k in FOREST_SCORE_OUTPUTS)))
+        return out
+
+    def oob(self, boot, prefixes=None, labels=None, outputs=('correct',), chunk_rows=0, stage_bytes=0):
+        """l3_forest_oob: every row of the resident matrix scored by the trees whose bootstrap missed it (boot (n_trees, n): the
+        multiplicities the resident forest was fitted with), among the first prefixes[g] trees for every g in one pass (None: the
+        whole forest) -> dict of the FOREST_OOB_OUTPUTS that `outputs` names, each with the leading axis G.  labels: class indices.
+        chunk_rows, stage_bytes: score()'s."""
+        unknown = set(outputs) - set(FOREST_OOB_OUTPUTS)
+        if unknown:
+            raise ValueError('unknown outputs %s; choose from %s' % (sorted(unknown), list(FOREST_OOB_OUTPUTS)))
+        T, _, nc, _ = self.sizes()
+        b = np.ascontiguousarray(boot, np.uint16)
+        if b.ndim != 2 or (self.n and b.shape[1] != self.n):          # without a matrix the library refuses (L3_ESTATE)
+            raise ValueError('boot must be (n_trees, n) for the resident matrix of %d rows' % self.n)
+        n = self.n
+        p = _i32([T] if prefixes is None else prefixes).reshape(-1)
+        y = None if labels is None else _i32(labels).reshape(-1)
+        if y is not None and y.size != n:
+            raise ValueError('one label per row')
+        shapes = dict(pred=((p.size, n), np.int32), correct=((p.size,), np.int64), n_oob=((p.size, n), np.int32),
+                      sums=((p.size, n, nc), np.float64))
+        out = {k: np.empty(*shapes[k]) for k in FOREST_OOB_OUTPUTS if k in outputs}
+        check(self.lib.l3_forest_oob(self.h, _ptr(b), b.shape[0], _ptr(p), p.size, _ptr(y), int(chunk_rows), int(stage_bytes),
+                                     *(_ptr(out.get(k)) for k in FOREST_OOB_OUTPUTS)))
         return out
 
     def cuts(self):

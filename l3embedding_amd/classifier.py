@@ -668,6 +668,62 @@ def train_rf_search(train_data, valid_data, test_data, model_dir, n_estimators_g
     return outcome
 
 
+def train_rf_oob_search(train_data, valid_data, test_data, model_dir, n_estimators_grid=RF_SEARCH_GRID, train_with_valid=False,
+                        num_classes=10, random_state=12345678, n_estimators=None, **kwargs):
+    """The search over n_estimators (classifier/train.py:623-630) decided by out-of-bag accuracy instead of validation rows
+    (DESIGN.md 8l): one forest of max(grid) trees fitted on the search rows -- train_data, or with train_with_valid and a
+    valid_data train + valid shuffled together as train_param_search's refit merges them -- and one
+    RandomForestClassifier.oob_evaluate of those rows at all sizes at once.  No row is cut off and nothing is fitted twice: the
+    size with the best out-of-bag accuracy is kept (the earlier grid entry on ties) and the returned model is that prefix of the one
+    forest, bit for bit the forest a separate fit of that size gives.  -> train_rf_search's tuple (model, train_metrics,
+    valid_metrics, test_metrics): the metrics of the chosen size on the search rows, the validation rows (when given; with
+    train_with_valid they were trained on) and the test files, scored as train_rf_search scores them, 'loss' 0, with its search
+    records ('search' holds every size's metrics of that split); train_metrics also carries 'oob', compute_metrics of the chosen
+    size's out-of-bag predictions, and 'oob_search', {(n,): those metrics} in grid order.  model_dir/model.pkl holds the returned
+    model.  n_estimators is ignored (the search sets it); of kwargs RF_ARGS are passed on, as in train_rf."""
+    grid = _rf_grid(n_estimators_grid)
+    sizes = sorted(grid)
+    forest_args = {k: kwargs[k] for k in RF_ARGS if k in kwargs}
+    with contextlib.ExitStack() as made:
+        rows = made.enter_context(_merged_and_shuffled(train_data, valid_data)) if train_with_valid and valid_data else train_data
+        if isinstance(rows['features'], DeviceFeatures):
+            forest_args.setdefault('device', rows['features'].device)
+        LOGGER.info('Fitting the grid n_estimators = %s as one forest of %d trees', grid, sizes[-1])
+        whole = RandomForestClassifier(n_estimators=sizes[-1], random_state=random_state, **forest_args)
+        whole.fit(rows['features'], rows['labels'])
+        out_of_bag = whole.oob_evaluate(prefixes=sizes, outputs=('predict',))['predict']
+        on_train = whole.evaluate(FITTED_ROWS, prefixes=sizes)['predict']
+        labels = np.asarray(rows['labels'])
+    on_valid = whole.evaluate(valid_data['features'], prefixes=sizes)['predict'] if valid_data else None
+    per_file = None
+    if test_data:          # train_rf scores the files by class index
+        per_file = np.searchsorted(whole.classes_, whole.evaluate(test_data['features'], file_idxs=test_data['file_idxs'], prefixes=sizes,
+                                                                  outputs=('file_predict',))['file_predict'])
+
+    def metrics(y, pred, loss=True):
+        m = compute_metrics(y, pred, num_classes=num_classes)
+        if loss:
+            m['loss'] = 0
+        return m
+
+    at = [sizes.index(n) for n in grid]
+    oob = [metrics(labels, out_of_bag[g], loss=False) for g in at]
+    best = int(np.argmax([m['accuracy'] for m in oob]))          # the first of the largest: the earlier grid entry
+    point = (grid[best],)
+    LOGGER.info('Chosen %s (out-of-bag accuracy %s)', {'n_estimators': point[0]}, oob[best]['accuracy'])
+    points = [(n,) for n in grid]
+    record = {'search_params': ['n_estimators'], 'search_params_best_values': point}
+    train_runs = [metrics(labels, on_train[g]) for g in at]
+    train_metrics = dict(train_runs[best], search=dict(zip(points, train_runs)), oob=oob[best], oob_search=dict(zip(points, oob)), **record)
+    valid_runs = [metrics(valid_data['labels'], on_valid[g]) if valid_data else {} for g in at]
+    valid_metrics = dict(valid_runs[best], search=dict(zip(points, valid_runs)), **record)
+    test_metrics = compute_metrics(test_data['labels'], per_file[at[best]], num_classes=num_classes) if test_data else {}
+    model = whole.prefix(point[0])
+    LOGGER.info('Saving model...')
+    _dump(os.path.join(model_dir, 'model.pkl'), model)
+    return model, train_metrics, valid_metrics, test_metrics
+
+
 MLP_SEARCH_SPACE = {'learning_rate': [1e-5, 1e-4, 1e-3], 'weight_decay': [1e-5, 1e-4, 1e-3]}        # classifier/train.py:638-651
 
 
@@ -857,9 +913,15 @@ def _dump(path, obj):
         pk.dump(obj, fh, protocol=pk.HIGHEST_PROTOCOL)
 
 
+def _searches_without_valid_fold(fold):
+    """whether the fold's parameter search has no validation fold: every fold but the test fold then trains"""
+    return bool(fold['parameter_search'] and not fold['parameter_search_valid_fold'])
+
+
 def _searches_on_a_cut(fold):
-    """whether the fold's parameter search has no validation fold and cuts the training rows instead; refuses without the seed"""
-    on_cut = bool(fold['parameter_search'] and not fold['parameter_search_valid_fold'])
+    """whether the fold's parameter search has no validation fold and cuts the training rows instead; refuses without the seed.  A
+    search that says it needs no validation rows (search_without_cut: the forest's out-of-bag search) makes no cut."""
+    on_cut = _searches_without_valid_fold(fold) and not fold.get('search_without_cut')
     _require_split_seed(on_cut, fold['parameter_search_split_seed'])
     return on_cut
 
@@ -898,7 +960,7 @@ def _run_fold(fold, get_splits=None):
 
     LOGGER.info('Fold %d of %s: loading and preprocessing', fold_num, dataset)
     get_splits = get_splits or functools.partial(get_split, features_dir, fold_num - 1, dataset)
-    with _closing(get_splits(not on_cut)) as splits:
+    with _closing(get_splits(not _searches_without_valid_fold(fold))) as splits:
         scalers = preprocess_split_data(*splits, feature_mode=fold['feature_mode'], non_overlap=fold['non_overlap'],
                                         non_overlap_chunk_size=int(fold['non_overlap_chunk_size']), use_min_max=fold['use_min_max'],
                                         device=fold['preprocess_device'])
@@ -965,6 +1027,14 @@ def _rf_search_part(splits, model_dir, fold):
     return train_rf_search(*splits, model_dir, train_with_valid=fold['parameter_search_train_with_valid'], **args)
 
 
+def _rf_oob_part(splits, model_dir, fold):
+    """the part of a fold that searches the random forest's n_estimators by out-of-bag accuracy -> (model, train_metrics,
+    valid_metrics, test_metrics): train_rf_oob_search with the fold's grid (in model_args); without a validation fold every
+    training row is fitted and none is cut off"""
+    args = dict(dict(random_state=fold['random_state'], num_classes=fold['num_classes'], verbose=fold['verbose']), **fold['model_args'])
+    return train_rf_oob_search(*splits, model_dir, train_with_valid=fold['parameter_search_train_with_valid'], **args)
+
+
 def train(features_dir, output_dir, fold_num, model_type='svm', feature_mode='framewise', train_batch_size=64, patience=20,
           random_state=20171021, parameter_search=False, parameter_search_valid_fold=True, parameter_search_valid_ratio=0.15,
           parameter_search_train_with_valid=False, gsheet_id=None, google_dev_app_name=None, verbose=False, non_overlap=False,
@@ -1029,6 +1099,31 @@ def train_rf_search_fold(features_dir, output_dir, fold_num, feature_mode='frame
     NO_SSS).  config.json records parameter_search true and n_estimators_grid; model_args are RF_ARGS.  -> that directory."""
     fold = dict(locals(), model_type='rf', parameter_search=True, model_part=_rf_search_part)          # the fold's settings by name
     fold['model_args'] = dict(model_args, n_estimators_grid=_rf_grid(fold.pop('n_estimators_grid')))
+    return _run_fold(fold)
+
+
+def _refuse_cut_settings(model_args):
+    """the out-of-bag search's one refusal of its own: the settings of a cut that it does not make"""
+    named = sorted({'parameter_search_valid_ratio', 'parameter_search_split_seed'} & set(model_args))
+    if named:
+        raise ValueError('the out-of-bag search cuts no validation rows off: %s do not apply' % ', '.join(named))
+
+
+def train_rf_oob_fold(features_dir, output_dir, fold_num, feature_mode='framewise', train_batch_size=64, patience=20,
+                      random_state=20171021, n_estimators_grid=RF_SEARCH_GRID, parameter_search_valid_fold=True,
+                      parameter_search_train_with_valid=False, gsheet_id=None, google_dev_app_name=None, verbose=False,
+                      non_overlap=False, non_overlap_chunk_size=10, use_min_max=False, preprocess_device=None, **model_args):
+    """classifier/train.py:495-709 for model_type='rf' with parameter_search (:623-630), the size chosen by out-of-bag accuracy
+    (DESIGN.md 8l): train_rf_search_fold's fold, directory (.../rf/fold<N>/<timestamp>/) and five files, the model chosen by
+    train_rf_oob_search over n_estimators_grid.  With parameter_search_valid_fold=False no seed is needed: no rows are cut off, every
+    fold but the test fold trains, and the search decides on the rows it trains on.  With a validation fold that fold is scored
+    (and with parameter_search_train_with_valid trained on) but does not decide.  config.json records parameter_search true,
+    n_estimators_grid and selection 'oob'; it has no ratio and no seed of a cut to record (parameter_search_valid_ratio is null).
+    model_args are RF_ARGS.  -> that directory."""
+    _refuse_cut_settings(model_args)
+    fold = dict(locals(), model_type='rf', parameter_search=True, model_part=_rf_oob_part, search_without_cut=True,
+                parameter_search_valid_ratio=None, parameter_search_split_seed=None)          # the fold's settings by name
+    fold['model_args'] = dict(model_args, n_estimators_grid=_rf_grid(fold.pop('n_estimators_grid')), selection='oob')
     return _run_fold(fold)
 
 

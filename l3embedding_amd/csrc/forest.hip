@@ -25,6 +25,14 @@
 //                    LDS, then a lane per class adds them in tree order and emits arg-max, hit and probabilities at every prefix
 //   forest_file_*    a thread per (size, file, class) adds a file's rows in row order; a thread per (size, file) takes the arg-max
 // The sums are those of forest_predict_kernel, operation for operation: the outputs are its bits.
+//
+// Out-of-bag scoring at nested forest sizes (l3_forest_oob; what oob_score=True adds to the fit, at every size of the
+// grid):
+//   forest_oob_mask  a lane per row over a slab of 64 trees' bootstrap multiplicities: one 64-bit word per (row, pass), bit j set iff
+//                    tree j of the pass left the row out of its bag
+//   forest_oob       forest_score's walk under the row's word: a lane whose bit is clear neither walks nor adds; the set lanes'
+//                    fractions are added in tree order, and at every prefix the sums as they stand, the number of trees that left
+//                    the row out, the arg-max and the hit are written.  Nothing is divided on the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -515,6 +523,27 @@ struct Score {
     int D, G, T;                     // T: the largest size
 };
 
+// the leaf (a node number over all trees) that row x reaches in tree t
+__device__ __forceinline__ int score_walk(const Model& m, const float* x, int t) {
+    const int64_t base = m.off[t];
+    const Node* nd = m.nodes + base;
+    int node = 0;
+    for (Node r; (r = nd[node]).left >= 0;) node = x[r.feat] <= r.thr ? r.left : r.right;
+    return (int)base + node;
+}
+// the count / total fractions of a pass's (tree, class) pairs, spread over the wave's lanes, into frac (cnt, C); lane j holds
+// the leaf of the pass's tree j.  MASKED: only the trees whose bit of `use` is set; the others' entries are left as they are.
+template <bool MASKED>
+__device__ __forceinline__ void score_fractions(const Model& m, int leaf, int cnt, int lane, unsigned long long use, double* frac) {
+    const int C = m.C, pairs = cnt * C;
+    for (int p0 = 0; p0 < pairs; p0 += 64) {
+        const int p = p0 + lane;
+        const int tr = (p < pairs ? p : pairs - 1) / C;
+        const int lf = __shfl(leaf, tr);
+        if (p < pairs && (!MASKED || ((use >> tr) & 1ull))) frac[p] = (double)m.counts[(int64_t)lf * C + (p - tr * C)] / (double)m.total[lf];
+    }
+}
+
 // LDS: the waves' fractions (SCORE_ROWS, SCORE_CHUNK, C) float64, the workgroup's hits (G, padded to 16 bytes), the staged rows
 template <bool STAGED>
 __global__ __launch_bounds__(256) void forest_score_kernel(Model m, Score a) {
@@ -542,21 +571,8 @@ __global__ __launch_bounds__(256) void forest_score_kernel(Model m, Score a) {
         for (int t0 = 0; t0 < a.T; t0 += SCORE_CHUNK) {
             const int cnt = a.T - t0 < SCORE_CHUNK ? a.T - t0 : SCORE_CHUNK;
             if (live) {
-                int leaf = 0;
-                if (lane < cnt) {
-                    const int64_t base = m.off[t0 + lane];
-                    const Node* nd = m.nodes + base;
-                    int node = 0;
-                    for (Node r; (r = nd[node]).left >= 0;) node = x[r.feat] <= r.thr ? r.left : r.right;
-                    leaf = (int)base + node;
-                }
-                const int pairs = cnt * C;          // the pass's (tree, class) pairs, spread over the lanes
-                for (int p0 = 0; p0 < pairs; p0 += 64) {
-                    const int p = p0 + lane;
-                    const int tr = (p < pairs ? p : pairs - 1) / C;
-                    const int lf = __shfl(leaf, tr);
-                    if (p < pairs) frac[p] = (double)m.counts[(int64_t)lf * C + (p - tr * C)] / (double)m.total[lf];
-                }
+                const int leaf = lane < cnt ? score_walk(m, x, t0 + lane) : 0;
+                score_fractions<false>(m, leaf, cnt, lane, 0ull, frac);
             }
             __syncthreads();
             if (live)
@@ -611,6 +627,92 @@ __global__ void forest_file_pred_kernel(const double* __restrict__ mean, int64_t
     for (int k = 1; k < C; ++k)
         if (v[k] > v[best]) best = k;
     out[i] = best;
+}
+
+// ---- out-of-bag scoring at nested forest sizes (l3_forest_oob) ------------------------------------------------------
+// a lane per row over a slab of at most 64 trees' bootstrap multiplicities (cnt, n): bit j of the row's word is set iff tree j of
+// the slab left the row out of its bag.  Every read runs along a tree's row; the bits of trees past cnt stay 0.
+__global__ __launch_bounds__(256) void forest_oob_mask_kernel(const uint16_t* __restrict__ slab, int cnt, int64_t n,
+                                                               unsigned long long* __restrict__ out) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    unsigned long long w = 0;
+    for (int j = 0; j < cnt; ++j)
+        if (slab[(int64_t)j * n + row] == 0) w |= 1ull << j;
+    out[row] = w;
+}
+
+struct Oob {
+    const float* X;                        // the chunk's rows
+    const unsigned long long* mask;        // (passes, n_all): the words of all rows of the matrix, pass-major
+    const int32_t* prefix;                 // (G) forest sizes, ascending
+    const int32_t* labels;                 // the chunk's, or null
+    int32_t* pred;                         // (G, n) of the chunk, or null
+    unsigned long long* correct;           // (G), or null
+    int32_t* n_oob;                        // (G, n) of the chunk, or null
+    double* sums;                          // (G, n, C) of the chunk, or null
+    int64_t n, row0, n_all;                // the chunk's rows are the matrix's rows row0 ...
+    int D, G, T;                           // T: the largest size
+};
+
+// forest_score_kernel's walk under the row's mask: a lane whose bit is clear neither walks nor adds, the set ones' fractions are
+// added in tree order, and after tree prefix[g] - 1 the wave writes the sums as they stand.  LDS as in forest_score_kernel.
+template <bool STAGED>
+__global__ __launch_bounds__(256) void forest_oob_kernel(Model m, Oob a) {
+    extern __shared__ double score_lds[];
+    const int C = m.C, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* frac = score_lds + (size_t)wave * SCORE_CHUNK * C;
+    int* hits = (int*)(score_lds + (size_t)SCORE_ROWS * SCORE_CHUNK * C);
+    float* xs = (float*)(hits + ((a.G + 3) & ~3));
+    for (int g = threadIdx.x; g < a.G; g += 256) hits[g] = 0;
+    const int64_t tiles = (a.n + SCORE_ROWS - 1) / SCORE_ROWS;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t r0 = tile * SCORE_ROWS, row = r0 + wave;
+        const bool live = row < a.n;
+        if (STAGED) {
+            __syncthreads();          // the last tile's walks are over
+            const int64_t cnt = (a.n - r0 < SCORE_ROWS ? a.n - r0 : SCORE_ROWS) * a.D;
+            const float* src = a.X + r0 * a.D;
+            for (int64_t i = threadIdx.x; i < cnt; i += 256) xs[i] = src[i];
+        }
+        __syncthreads();
+        const float* x = STAGED ? xs + (size_t)wave * a.D : a.X + (live ? row : 0) * a.D;
+        const int kk = lane < C ? lane : C - 1;
+        double acc = 0.0;
+        int seen = 0, gi = 0, nextp = a.prefix[0];
+        for (int t0 = 0; t0 < a.T; t0 += SCORE_CHUNK) {
+            const int cnt = a.T - t0 < SCORE_CHUNK ? a.T - t0 : SCORE_CHUNK;
+            const unsigned long long out = live ? a.mask[(int64_t)(t0 / SCORE_CHUNK) * a.n_all + a.row0 + row] : 0ull;      // one word per wave
+            if (live) {
+                const int leaf = lane < cnt && ((out >> lane) & 1ull) ? score_walk(m, x, t0 + lane) : 0;
+                score_fractions<true>(m, leaf, cnt, lane, out, frac);
+            }
+            __syncthreads();
+            if (live)
+                for (int j = 0; j < cnt; ++j) {          // a lane per class, in tree order
+                    if ((out >> j) & 1ull) acc += frac[j * C + kk], ++seen;
+                    if (t0 + j + 1 != nextp) continue;
+                    if (a.sums && lane < C) a.sums[((int64_t)gi * a.n + row) * C + lane] = acc;
+                    if (a.n_oob && lane == 0) a.n_oob[(int64_t)gi * a.n + row] = seen;
+                    if (a.pred || a.correct) {
+                        double v = lane < C ? acc : -1.0;          // no tree yet: every sum is 0 and class 0 is the first of them
+                        int pos = lane;
+                        wave_argmax(v, pos);
+                        if (lane == 0) {
+                            if (a.pred) a.pred[(int64_t)gi * a.n + row] = pos;
+                            if (a.correct && pos == a.labels[row]) atomicAdd(&hits[gi], 1);
+                        }
+                    }
+                    ++gi;
+                    nextp = gi < a.G ? a.prefix[gi] : -1;
+                }
+            __syncthreads();
+        }
+    }
+    if (!a.correct) return;
+    __syncthreads();
+    for (int g = threadIdx.x; g < a.G; g += 256)
+        if (hits[g]) atomicAdd(&a.correct[g], (unsigned long long)hits[g]);
 }
 
 }  // namespace
@@ -701,6 +803,36 @@ int predict_device(l3_forest* m, const float* dx, int64_t n, int D, double* out,
         hipStreamSynchronize(m->s) != hipSuccess)
         return fail(L3_EHIP, std::string(fn) + ": HIP error");
     return L3_OK;
+}
+
+// what l3_forest_score and l3_forest_oob check alike before a launch: the forest sizes, the labels, the two test knobs
+int check_scoring(const std::string& fn, const l3_forest* m, const int32_t* prefix, int G, const int32_t* labels, int64_t n, bool correct,
+                  int64_t chunk_rows, int64_t stage_bytes) {
+    if (!prefix || G < 1 || G > SCORE_MAX_PREFIXES) return fail(L3_EINVAL, fn + "need 1 to " + std::to_string(SCORE_MAX_PREFIXES) + " forest sizes");
+    for (int g = 0; g < G; ++g)
+        if (prefix[g] < 1 || prefix[g] > m->T || (g > 0 && prefix[g] <= prefix[g - 1]))
+            return fail(L3_EINVAL, fn + "prefix[" + std::to_string(g) + "] is outside [1, " + std::to_string(m->T) + "] or not above its predecessor");
+    if (correct && !labels) return fail(L3_EINVAL, fn + "correct needs labels");
+    if (labels)
+        for (int64_t i = 0; i < n; ++i)
+            if (labels[i] < 0 || labels[i] >= m->C) return fail(L3_EINVAL, fn + "labels[" + std::to_string(i) + "] outside [0, n_classes)");
+    if (chunk_rows < 0 || stage_bytes < 0) return fail(L3_EINVAL, fn + "chunk_rows and stage_bytes are 0 (the defaults) or positive");
+    return L3_OK;
+}
+
+// a scoring launch's LDS, fractions + hits (+ the staged rows when they fit the budget and the CU), and the rows per launch
+struct ScorePlan {
+    bool staged;
+    int64_t lds, chunk;
+};
+ScorePlan plan_scoring(int C, int G, int D, int64_t n, int64_t chunk_rows, int64_t stage_bytes) {
+    const int64_t lds_plain = (int64_t)SCORE_ROWS * SCORE_CHUNK * C * 8 + (int64_t)((G + 3) & ~3) * 4;
+    const int64_t row_bytes = (int64_t)SCORE_ROWS * D * 4;
+    ScorePlan p;
+    p.staged = row_bytes <= (stage_bytes > 0 ? stage_bytes : SCORE_STAGE_BYTES) && lds_plain + row_bytes <= SCORE_LDS_MAX;
+    p.lds = lds_plain + (p.staged ? row_bytes : 0);
+    p.chunk = std::min(chunk_rows > 0 ? chunk_rows : std::max<int64_t>(SCORE_ROWS, SCORE_CHUNK_BYTES / (4 * (int64_t)D)), n);
+    return p;
 }
 
 }  // namespace
@@ -1018,14 +1150,7 @@ int l3_forest_score(l3_forest* m, const float* X, const l3_feat* f, int64_t lo, 
     const int64_t n = hi - lo;
     const int C = m->C, G = n_prefix;
     if (D != m->mD) return fail(L3_EINVAL, fn + "the rows have " + std::to_string(D) + " features, the forest " + std::to_string(m->mD));
-    if (!prefix || G < 1 || G > SCORE_MAX_PREFIXES) return fail(L3_EINVAL, fn + "need 1 to " + std::to_string(SCORE_MAX_PREFIXES) + " forest sizes");
-    for (int g = 0; g < G; ++g)
-        if (prefix[g] < 1 || prefix[g] > m->T || (g > 0 && prefix[g] <= prefix[g - 1]))
-            return fail(L3_EINVAL, fn + "prefix[" + std::to_string(g) + "] is outside [1, " + std::to_string(m->T) + "] or not above its predecessor");
-    if (correct && !labels) return fail(L3_EINVAL, fn + "correct needs labels");
-    if (labels)
-        for (int64_t i = 0; i < n; ++i)
-            if (labels[i] < 0 || labels[i] >= C) return fail(L3_EINVAL, fn + "labels[" + std::to_string(i) + "] outside [0, n_classes)");
+    if (const int rc = check_scoring(fn, m, prefix, G, labels, n, correct != nullptr, chunk_rows, stage_bytes)) return rc;
     const bool file_out = file_mean || file_pred;
     if (n_files < 0 || (n_files > 0) != (files != nullptr)) return fail(L3_EINVAL, fn + "files and n_files come together");
     if ((n_files > 0) != file_out) return fail(L3_EINVAL, fn + "files and the file outputs (file_mean, file_pred) come together");
@@ -1035,16 +1160,11 @@ int l3_forest_score(l3_forest* m, const float* X, const l3_feat* f, int64_t lo, 
         if (s < 0 || e <= s || e > n) return fail(L3_EINVAL, fn + "file " + std::to_string(i) + " is empty or lies outside the rows");
         fmin = std::min(fmin, s), fmax = std::max(fmax, e);
     }
-    if (chunk_rows < 0 || stage_bytes < 0) return fail(L3_EINVAL, fn + "chunk_rows and stage_bytes are 0 (the defaults) or positive");
     if (!pred && !correct && !file_out && !proba) return fail(L3_EINVAL, fn + "no output is asked for");
 
-    // LDS: fractions + hits (+ the staged rows when they fit the budget and the CU)
-    const int64_t lds_plain = (int64_t)SCORE_ROWS * SCORE_CHUNK * C * 8 + (int64_t)((G + 3) & ~3) * 4;
-    const int64_t row_bytes = (int64_t)SCORE_ROWS * D * 4;
-    const bool staged = row_bytes <= (stage_bytes > 0 ? stage_bytes : SCORE_STAGE_BYTES) && lds_plain + row_bytes <= SCORE_LDS_MAX;
-    const int64_t lds = lds_plain + (staged ? row_bytes : 0);
-    int64_t chunk = chunk_rows > 0 ? chunk_rows : std::max<int64_t>(SCORE_ROWS, SCORE_CHUNK_BYTES / (4 * (int64_t)D));
-    chunk = std::min(chunk, n);
+    const ScorePlan plan = plan_scoring(C, G, D, n, chunk_rows, stage_bytes);
+    const bool staged = plan.staged;
+    const int64_t lds = plan.lds, chunk = plan.chunk;
     const int64_t span = n_files > 0 ? fmax - fmin : 0;
 
     (void)hipSetDevice(m->device);
@@ -1102,6 +1222,76 @@ int l3_forest_score(l3_forest* m, const float* X, const l3_feat* f, int64_t lo, 
             return fail(L3_EHIP, fn + "HIP error in the file means");
     }
     static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the hit counters are read back as int64");
+    if (correct && hipMemcpyAsync(correct, d_correct, (size_t)G * 8, hipMemcpyDeviceToHost, s) != hipSuccess) return fail(L3_EHIP, fn + "HIP error");
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(L3_EHIP, fn + "HIP error");
+    return L3_OK;
+}
+
+int l3_forest_oob(l3_forest* m, const uint16_t* boot, int n_trees, const int32_t* prefix, int n_prefix, const int32_t* labels,
+                  int64_t chunk_rows, int64_t stage_bytes, int32_t* pred, int64_t* correct, int32_t* n_oob, double* sums) {
+    const std::string fn = "l3_forest_oob: ";
+    if (!m || !boot) return fail(L3_EINVAL, fn + "NULL argument");
+    if (!m->has_model) return fail(L3_ESTATE, fn + "no forest (l3_forest_fit or l3_forest_set_trees)");
+    if (m->n <= 0) return fail(L3_ESTATE, fn + "no resident matrix (l3_forest_set_data)");
+    const int64_t n = m->n;
+    const int C = m->C, D = m->D, G = n_prefix;
+    if (n_trees != m->T) return fail(L3_EINVAL, fn + "boot holds " + std::to_string(n_trees) + " trees, the forest " + std::to_string(m->T));
+    if (D != m->mD) return fail(L3_EINVAL, fn + "the rows have " + std::to_string(D) + " features, the forest " + std::to_string(m->mD));
+    if (const int rc = check_scoring(fn, m, prefix, G, labels, n, correct != nullptr, chunk_rows, stage_bytes)) return rc;
+    if (!pred && !correct && !n_oob && !sums) return fail(L3_EINVAL, fn + "no output is asked for");
+
+    const ScorePlan plan = plan_scoring(C, G, D, n, chunk_rows, stage_bytes);
+    const int64_t chunk = plan.chunk;
+    const int T = prefix[G - 1], passes = (T + SCORE_CHUNK - 1) / SCORE_CHUNK;          // the trees past the largest size are not read
+
+    (void)hipSetDevice(m->device);
+    hipStream_t s = m->s;
+    (void)hipStreamSynchronize(s);
+    const void* kernel = plan.staged ? (const void*)forest_oob_kernel<true> : (const void*)forest_oob_kernel<false>;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCORE_LDS_MAX) != hipSuccess)
+        return fail(L3_EHIP, fn + "the kernel's LDS size could not be set");
+    DeviceBufs b;
+    Oob a{};
+    a.prefix = b.put(prefix, (size_t)G, s);
+    const int32_t* d_labels = labels ? b.put(labels, (size_t)n, s) : nullptr;
+    uint16_t* d_slab = b.alloc<uint16_t>((size_t)std::min(T, SCORE_CHUNK) * n);
+    unsigned long long* d_mask = b.alloc<unsigned long long>((size_t)passes * n);
+    int32_t* d_pred = pred ? b.alloc<int32_t>((size_t)G * chunk) : nullptr;
+    int32_t* d_noob = n_oob ? b.alloc<int32_t>((size_t)G * chunk) : nullptr;
+    double* d_sums = sums ? b.alloc<double>((size_t)G * chunk * C) : nullptr;
+    unsigned long long* d_correct = correct ? b.alloc<unsigned long long>((size_t)G) : nullptr;
+    if (!b.ok()) return fail(L3_ENOMEM, fn + "device allocation failed");
+    if (d_correct && hipMemsetAsync(d_correct, 0, (size_t)G * sizeof(unsigned long long), s) != hipSuccess) return fail(L3_EHIP, fn + "HIP error");
+    // the masks: a slab of 64 trees' multiplicities at a time, in stream order through one buffer
+    for (int p = 0; p < passes; ++p) {
+        const int t0 = p * SCORE_CHUNK, cnt = std::min(T - t0, SCORE_CHUNK);
+        if (hipMemcpyAsync(d_slab, boot + (size_t)t0 * n, (size_t)cnt * n * sizeof(uint16_t), hipMemcpyHostToDevice, s) != hipSuccess)
+            return fail(L3_EHIP, fn + "copy of the multiplicities failed");
+        hipLaunchKernelGGL(forest_oob_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_slab, cnt, n, d_mask + (size_t)p * n);
+        if (hipGetLastError() != hipSuccess) return fail(L3_EHIP, fn + "launch failed");
+    }
+    a.mask = d_mask, a.pred = d_pred, a.correct = d_correct, a.n_oob = d_noob, a.sums = d_sums;
+    a.n_all = n, a.D = D, a.G = G, a.T = T;
+    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+        const int64_t cn = std::min(chunk, n - c0);
+        a.X = m->x + c0 * D;
+        a.labels = d_labels ? d_labels + c0 : nullptr;
+        a.n = cn, a.row0 = c0;
+        const unsigned grid = (unsigned)std::min<int64_t>((cn + SCORE_ROWS - 1) / SCORE_ROWS, 2048);
+        if (plan.staged) hipLaunchKernelGGL(forest_oob_kernel<true>, dim3(grid), dim3(256), (size_t)plan.lds, s, m->dm, a);
+        else hipLaunchKernelGGL(forest_oob_kernel<false>, dim3(grid), dim3(256), (size_t)plan.lds, s, m->dm, a);
+        if (hipGetLastError() != hipSuccess) return fail(L3_EHIP, fn + "launch failed");
+        for (int g = 0; g < G; ++g) {
+            if (pred && hipMemcpyAsync(pred + (int64_t)g * n + c0, d_pred + (int64_t)g * cn, (size_t)cn * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
+                return fail(L3_EHIP, fn + "copy of the predictions failed");
+            if (n_oob && hipMemcpyAsync(n_oob + (int64_t)g * n + c0, d_noob + (int64_t)g * cn, (size_t)cn * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
+                return fail(L3_EHIP, fn + "copy of the tree counts failed");
+            if (sums && hipMemcpyAsync(sums + ((int64_t)g * n + c0) * C, d_sums + (int64_t)g * cn * C, (size_t)cn * C * 8, hipMemcpyDeviceToHost,
+                                       s) != hipSuccess)
+                return fail(L3_EHIP, fn + "copy of the sums failed");
+        }
+        if (hipStreamSynchronize(s) != hipSuccess) return fail(L3_EHIP, fn + "HIP error in the scoring kernel");
+    }
     if (correct && hipMemcpyAsync(correct, d_correct, (size_t)G * 8, hipMemcpyDeviceToHost, s) != hipSuccess) return fail(L3_EHIP, fn + "HIP error");
     if (hipStreamSynchronize(s) != hipSuccess) return fail(L3_EHIP, fn + "HIP error");
     return L3_OK;

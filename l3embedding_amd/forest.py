@@ -15,6 +15,11 @@ same call with a larger size).  evaluate() scores rows by several such prefixes 
 hits, probabilities, per-file means, each tree walked once per row, bit for bit what predict_proba gives for each prefix), and
 prefix(n) is the fitted classifier of the first n trees.
 
+Out-of-bag scores: with oob_score=True fit also sets oob_score_ and oob_decision_function_ by sklearn 0.19's
+_set_oob_score rule, and oob_evaluate() gives the out-of-bag predictions, hits, sums and decisions of the training rows at several
+forest sizes in one pass on the GPU (l3_forest_oob: each row scored by the trees whose bootstrap missed it, the masks built on the
+device from the multiplicities the fit drew).  A prefix's out-of-bag values are those of a separate fit of its size, bit for bit.
+
 Deviations from sklearn 0.19, all deliberate:
   * a split is searched among at most 255 cuts per feature (sklearn tries every midpoint of the node's own values), so the trees are
     not sklearn's; they are judged against sklearn's seed-to-seed spread (tests/golden/make_forest_golden.py) and are equal, node for
@@ -26,9 +31,13 @@ Deviations from sklearn 0.19, all deliberate:
     max_features features, and one that finds no valid split among them becomes a leaf;
   * among equally good splits the earlier draw wins, then the lower cut (sklearn: the first it meets in its own order);
   * estimators_ holds the trees as flat arrays (_lib.FOREST_TREE_ARRAYS), not DecisionTreeClassifier objects;
-  * class_weight, sample weights, oob_score, min_weight_fraction_leaf, max_leaf_nodes, min_impurity_decrease, warm_start and criteria
+  * oob_score_ and oob_decision_function_ are not pickled and a prefix does not carry the larger forest's: they belong to the rows
+    of the fit, and oob_evaluate(X=those rows) gives them again (sklearn pickles both);
+  * class_weight, sample weights, min_weight_fraction_leaf, max_leaf_nodes, min_impurity_decrease, warm_start and criteria
     other than Gini are not built; at most _lib.FOREST_MAX_CLASSES classes.
 """
+import warnings
+
 import numpy as np
 
 from . import _lib
@@ -39,6 +48,9 @@ from .usc import DeviceFeatures
 FITTED_ROWS = object()
 EVALUATE_OUTPUTS = ('predict', 'correct', 'proba', 'file_mean', 'file_predict')
 _SCORE_NAMES = {'predict': 'pred', 'correct': 'correct', 'proba': 'proba', 'file_mean': 'file_mean', 'file_predict': 'file_pred'}
+OOB_OUTPUTS = ('predict', 'correct', 'sums', 'n_oob', 'decision')
+_OOB_NAMES = {'predict': 'pred', 'correct': 'correct', 'sums': 'sums', 'n_oob': 'n_oob', 'decision': 'sums'}
+_OOB_ATTRIBUTES = ('oob_score_', 'oob_decision_function_')          # of one fit's rows: neither pickled nor handed to a prefix
 
 
 def tree_seeds(random_state, n_estimators):
@@ -83,17 +95,28 @@ def resolve_max_features(max_features, D):
     return k
 
 
+def oob_decision(sums):
+    """sklearn 0.19's _set_oob_score normalisation of one forest's out-of-bag sums (n, C): each row over its own total, NaN where no
+    tree left the row out (then the warning sklearn gives)"""
+    if (sums.sum(axis=1) == 0).any():
+        warnings.warn('Some inputs do not have OOB scores. This probably means too few trees were used to compute any reliable oob '
+                      'estimates.')
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return sums / sums.sum(axis=1)[:, None]
+
+
 class RandomForestClassifier(object):
-    """sklearn 0.19's RandomForestClassifier(n_estimators, random_state) on the GPU: fit / predict / predict_proba, classes_,
-    estimators_ (the trees as the flat arrays of _lib.FOREST_TREE_ARRAYS).  The fitted model pickles without its device handle and
-    uploads its trees again on first use.  wide_min_rows: the node size from which the search takes a workgroup per (node, feature)
-    instead of a wave per node (0: the library's default); the trees do not depend on it."""
+    """sklearn 0.19's RandomForestClassifier(n_estimators, random_state, oob_score) on the GPU: fit / predict / predict_proba,
+    classes_, estimators_ (the trees as the flat arrays of _lib.FOREST_TREE_ARRAYS), and with oob_score=True oob_score_ and
+    oob_decision_function_.  The fitted model pickles without its device handle and uploads its trees again on first use.
+    wide_min_rows: the node size from which the search takes a workgroup per (node, feature) instead of a wave per node (0: the
+    library's default); the trees do not depend on it."""
 
     def __init__(self, n_estimators=100, random_state=None, max_depth=None, min_samples_split=2, min_samples_leaf=1,
-                 max_features='sqrt', bin_sample=4096, device=0, wide_min_rows=0):
+                 max_features='sqrt', bin_sample=4096, device=0, wide_min_rows=0, oob_score=False):
         self.n_estimators, self.random_state, self.max_depth = n_estimators, random_state, max_depth
         self.min_samples_split, self.min_samples_leaf, self.max_features = min_samples_split, min_samples_leaf, max_features
-        self.bin_sample, self.device, self.wide_min_rows = bin_sample, device, wide_min_rows
+        self.bin_sample, self.device, self.wide_min_rows, self.oob_score = bin_sample, device, wide_min_rows, oob_score
         self._h = None
         self._resident = False
         self._fitted_rows = 0          # rows of the fit's matrix while this model's handle still holds it (evaluate(FITTED_ROWS))
@@ -104,11 +127,14 @@ class RandomForestClassifier(object):
         state['_h'] = None
         state['_resident'] = False
         state['_fitted_rows'] = 0
+        for k in _OOB_ATTRIBUTES:
+            state.pop(k, None)
         return state
 
     def __setstate__(self, state):
         self.__dict__.update(state)
         self.__dict__.setdefault('_fitted_rows', 0)          # a model pickled before evaluate() existed
+        self.__dict__.setdefault('oob_score', False)         # or before oob_score did
 
     def _handle(self):
         if self._h is None:
@@ -157,6 +183,12 @@ class RandomForestClassifier(object):
         self.level_stats_ = h.level_stats()
         self._resident = True
         self._fitted_rows = n
+        for k in _OOB_ATTRIBUTES:
+            self.__dict__.pop(k, None)
+        if self.oob_score:          # sklearn 0.19's _set_oob_score, on the rows and the multiplicities of this fit
+            got = h.oob(boot, outputs=('pred', 'sums'))
+            self.oob_decision_function_ = oob_decision(got['sums'][0])
+            self.oob_score_ = np.mean(yenc == got['pred'][0])
         return self
 
     def _check_fitted(self):
@@ -170,6 +202,16 @@ class RandomForestClassifier(object):
             h.set_trees(self.estimators_, self.n_features_)
             self._resident = True
         return h
+
+    def _class_indices(self, y, n):
+        """the n labels y (classes_ values, every one of them known to the forest) as indices into classes_"""
+        y = np.asarray(y).reshape(-1)
+        if y.size != n:
+            raise ValueError('one label per row')
+        labels = np.searchsorted(self.classes_, y).clip(max=self.classes_.size - 1)
+        if not np.array_equal(self.classes_[labels], y):
+            raise ValueError('y holds a label the forest was not fitted on')
+        return labels
 
     def predict_proba(self, X):
         """(n, n_classes) float64: the mean over the trees of the class fractions of the leaf each row falls into"""
@@ -220,14 +262,7 @@ class RandomForestClassifier(object):
             if X.shape[0] == 0:
                 raise ValueError('no rows to score')
             rows, n = (dict(feat=X.handle) if on_device else dict(X=X)), int(X.shape[0])
-        labels = None
-        if 'correct' in outputs:
-            y = np.asarray(y).reshape(-1)
-            if y.size != n:
-                raise ValueError('one label per row')
-            labels = np.searchsorted(self.classes_, y).clip(max=self.classes_.size - 1)
-            if not np.array_equal(self.classes_[labels], y):
-                raise ValueError('y holds a label the forest was not fitted on')
+        labels = self._class_indices(y, n) if 'correct' in outputs else None
         h = self._ensure_model()
         got = h.score(prefixes=prefixes, labels=labels, files=file_idxs if by_file else None,
                       outputs=tuple(_SCORE_NAMES[k] for k in outputs), chunk_rows=chunk_rows, stage_bytes=stage_bytes, **rows)
@@ -237,9 +272,60 @@ class RandomForestClassifier(object):
                 out[k] = self.classes_[out[k]]
         return out
 
+    def oob_evaluate(self, y=None, prefixes=None, outputs=('correct',), X=FITTED_ROWS, chunk_rows=0, stage_bytes=0):
+        """One out-of-bag pass on the GPU over the rows of the fit by the forests of the first prefixes[g] trees: every row is scored
+        by the trees whose bootstrap sample missed it, each of them walked once -> dict of what `outputs` names (OOB_OUTPUTS), each
+        with the leading axis G = len(prefixes); without prefixes the whole forest, G = 1.  X: FITTED_ROWS (the rows where the fit
+        left them, as in evaluate), or the same rows again as NumPy rows or a usc.DeviceFeatures (after unpickling; they replace the
+        handle's matrix, so FITTED_ROWS is no longer served afterwards).  The multiplicities are drawn again from random_state, an int.
+        'sums' (G, n, C): the leaves' class fractions added in tree order over the row's out-of-bag trees; 'n_oob' (G, n): their
+        number; 'predict' (G, n): classes_[argmax(sums)], classes_[0] for a row without such a tree; 'correct' (G): the rows
+        predicted as y; 'decision' (G, n, C): oob_decision of the sums, what a fit of prefixes[g] trees with oob_score=True leaves in
+        oob_decision_function_ (NaN rows and the warning included), bit for bit.  chunk_rows, stage_bytes: evaluate's."""
+        self._check_fitted()
+        outputs = tuple(outputs)
+        unknown = set(outputs) - set(OOB_OUTPUTS)
+        if unknown:
+            raise ValueError('unknown outputs %s; choose from %s' % (sorted(unknown), list(OOB_OUTPUTS)))
+        if 'correct' in outputs and y is None:
+            raise ValueError("'correct' needs y")
+        if isinstance(self.random_state, bool) or not isinstance(self.random_state, (int, np.integer)):
+            raise ValueError('the bootstrap samples can be drawn again only from an int random_state, not %r' % (self.random_state,))
+        if X is FITTED_ROWS:
+            if not self._fitted_rows or self._h is None:
+                raise ValueError('the rows of the fit are no longer on the GPU: pass them to oob_evaluate')
+            h, n = self._ensure_model(), self._fitted_rows
+        else:
+            on_device = isinstance(X, DeviceFeatures)
+            if not on_device:
+                X = np.ascontiguousarray(X, np.float32)
+            if len(X.shape) != 2 or X.shape[1] != self.n_features_:
+                raise ValueError('X has %s features per sample; expecting %d' % (tuple(X.shape[1:]), self.n_features_))
+            if X.shape[0] == 0:
+                raise ValueError('no rows to score')
+            h, n = self._ensure_model(), int(X.shape[0])
+            self._fitted_rows = 0
+            if on_device:
+                h.set_data_dev(X.handle)
+            else:
+                h.set_data(X)
+        labels = None
+        if 'correct' in outputs:
+            labels = self._class_indices(y, n)
+        boot = bootstrap_counts(tree_seeds(self.random_state, int(self.n_estimators)), n)
+        got = h.oob(boot, prefixes=prefixes, labels=labels, outputs=tuple(sorted({_OOB_NAMES[k] for k in outputs})),
+                    chunk_rows=chunk_rows, stage_bytes=stage_bytes)
+        out = {k: got[_OOB_NAMES[k]] for k in outputs}
+        if 'predict' in out:
+            out['predict'] = self.classes_[out['predict']]
+        if 'decision' in out:
+            out['decision'] = np.stack([oob_decision(s) for s in got['sums']])
+        return out
+
     def prefix(self, n):
         """the fitted classifier of this forest's first n trees, n_estimators = n: what fit gives with n_estimators=n and everything
-        else equal.  Its estimators_ are views of this forest's arrays; it has no handle and uploads its trees on first use."""
+        else equal (but for oob_score_ and oob_decision_function_: this forest's are not the prefix's, oob_evaluate gives those).
+        Its estimators_ are views of this forest's arrays; it has no handle and uploads its trees on first use."""
         self._check_fitted()
         n = int(n)
         if not 1 <= n <= int(self.n_estimators):
