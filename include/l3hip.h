@@ -420,6 +420,32 @@ int l3_op_resample_clips(int device, const float *x, int64_t n_in, const int64_t
  * Runs the engine's second reduction stage on a buffer of exactly nblk rows; L3_EINVAL if it wrote past them. */
 int l3_op_bn_stats_from_partials(int device, const float *part, int nblk, int c, const float *pivot, int64_t rows,
                                  float eps, float *mean, float *var);
+/* What a convolution's epilogue leaves for the BatchNormalization behind it (vision_model.py:124-187, audio_model.py:370-433), on
+ * its own: the convolution of l3_op_conv2d_fwd_dt (same dtype values, same kernel choice) with the statistics on.  stat_mode 1:
+ * moments of y, 2: of relu(y) (the Activation-before-BatchNormalization order).  part (nblk, 2, cout): per-block [sum, sum of
+ * squares] about the pivot b[c] (relu(b[c]) in mode 2), bf16-stored output: of the ROUNDED values; mean, var: the engine's second
+ * stage over them.  y comes back widened when stored as bfloat16.  *nblk is the engine's block count for the layer; with part
+ * NULL the call only reports it (no device work).  The kernel writes into a buffer of exactly *nblk blocks preset to NaN with a
+ * guard behind it: L3_EINVAL (message in l3_last_error(NULL)) if a block stayed unwritten or the guard changed, and for a layer
+ * whose kernel leaves no statistics (direct implicit GEMM, bf16 operands cast at fetch). */
+int l3_op_conv2d_fwd_stats(int device, int dtype, const float *x, const float *w, const float *b, float *y, float *part, int *nblk,
+                           float *mean, float *var, int n, int h, int wd, int cin, int cout, int kh, int kw, int same,
+                           int stat_mode);
+/* The data gradient of a convolution with the backward reduction of the BatchNormalization(+ReLU) in FRONT of it in the epilogue:
+ * n, h, wd, cin, cout describe the forward convolution; dy (n, ho, wo, cout); bn_x (n, h, wd, cin) is that BatchNorm's input (or,
+ * for a pooled BatchNorm, the window winners of l3_op_bn_relu_pool2_fwd_xwin) with parameters and batch moments of cin channels
+ * over bn_rows rows.  part (nblk, 2, cin): per-block [sum of m dx, sum of m dx x_hat], m the ReLU mask bn_x * scale + shift > 0
+ * (relu != 0) or 1; dgamma, dbeta: the second stage over them.  dtype L3_DTYPE_F32 (Winograd kernels) or L3_OP_BF16_STORED_OUT
+ * (dy, bn_x, dx bfloat16 in HBM; dx returned widened).  nblk, part NULL, the guarded buffer and L3_EINVAL as above; L3_EINVAL
+ * also wherever an engine would not fuse the two. */
+int l3_op_conv2d_dgrad_bn_bwd(int device, int dtype, const float *dy, const float *w, const float *bn_x, const float *gamma,
+                              const float *beta, const float *mean, const float *var, float *dx, float *part, int *nblk,
+                              float *dgamma, float *dbeta, int n, int h, int wd, int cin, int cout, int kh, int kw, int same,
+                              int relu, int64_t bn_rows);
+/* l3_op_bn_relu_pool2_fwd as a TRAINING forward runs it: also xwin (n, ho, wo, c), the input element (relu_mode 2: the rectified
+ * one) that won each window -- what the backward reduction above reads for a pooled BatchNorm.  Widened when x_bf16. */
+int l3_op_bn_relu_pool2_fwd_xwin(int device, const float *x, const float *gamma, const float *beta, float *p, float *mean,
+                                 float *var, float *xwin, int n, int h, int wd, int c, int same, int relu_mode, int x_bf16);
 int l3_op_preprocess(int device, const uint8_t *video_u8, int64_t nv, float *video,
                      const int16_t *audio_i16, int64_t na, float *audio);
 /* sample_one_frame(augment=True) after the frame has been chosen (data/avc/sample.py:235-281): crop to 224 x 224 at

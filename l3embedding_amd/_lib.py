@@ -144,6 +144,11 @@ SIGNATURES = {
                                        C.c_int, C.c_int64, C.c_int, C.c_void_p]),
     'l3_op_bn_stats_from_partials': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_float,
                                                C.c_void_p, C.c_void_p]),
+    'l3_op_conv2d_fwd_stats': (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(C.c_int), C.c_void_p, C.c_void_p] +
+                               [C.c_int] * 9),
+    'l3_op_conv2d_dgrad_bn_bwd': (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(C.c_int), C.c_void_p, C.c_void_p] +
+                                  [C.c_int] * 9 + [C.c_int64]),
+    'l3_op_bn_relu_pool2_fwd_xwin': (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 7),
     'l3_op_preprocess': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'l3_op_augment_video': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'l3_op_augment_audio': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -755,6 +760,50 @@ def op_conv2d_bwd(x, w, dy, same, device=0, dtype='f32'):
     return dx, dw, db
 
 
+def op_conv2d_fwd_stats(x, w, b, same, stat_mode, dtype='f32', device=0):
+    """The convolution of op_conv2d_fwd with its epilogue's BatchNorm statistics: y, partials (nblk, 2, Cout) about the pivot b
+    (relu(b) when stat_mode == 2: moments of relu(y)), and the batch mean / biased variance the engine's second stage makes of them."""
+    lib = load()
+    x, w, b = _f32(x), _f32(w), _f32(b)
+    n, h, wd, cin = x.shape
+    kh, kw, _, cout = w.shape
+    ho, wo = (h, wd) if same else (h - kh + 1, wd - kw + 1)
+    dims = (n, h, wd, cin, cout, kh, kw, int(same), int(stat_mode))
+    nblk = C.c_int(0)
+    check(lib.l3_op_conv2d_fwd_stats(device, OP_DTYPES[dtype], None, None, None, None, None, C.byref(nblk), None, None, *dims))
+    y = np.empty((n, ho, wo, cout), np.float32)
+    part = np.empty((nblk.value, 2, cout), np.float32)
+    mean, var = np.empty(cout, np.float32), np.empty(cout, np.float32)
+    check(lib.l3_op_conv2d_fwd_stats(device, OP_DTYPES[dtype], _ptr(x), _ptr(w), _ptr(b), _ptr(y), _ptr(part), C.byref(nblk),
+                                     _ptr(mean), _ptr(var), *dims))
+    assert nblk.value == part.shape[0]
+    return y, part, mean, var
+
+
+def op_conv2d_dgrad_bn_bwd(dy, w, same, bn_x, gamma, beta, mean, var, relu, bn_rows=None, dtype='f32', device=0):
+    """The data gradient of the convolution with filter w (KH, KW, Cin, Cout) from dy (N, Ho, Wo, Cout), with the backward reduction
+    of the BatchNorm(+ReLU) in front of the convolution -- input bn_x (N, H, W, Cin), moments over bn_rows rows (default: bn_x's) --
+    in its epilogue: dx, partials (nblk, 2, Cin) of [mask * dx, mask * dx * x_hat], dgamma, dbeta."""
+    lib = load()
+    dy, w, bn_x = _f32(dy), _f32(w), _f32(bn_x)
+    n, h, wd, cin = bn_x.shape
+    kh, kw, wci, cout = w.shape
+    ho, wo = (h, wd) if same else (h - kh + 1, wd - kw + 1)
+    assert wci == cin and dy.shape == (n, ho, wo, cout)
+    rows = int(bn_rows) if bn_rows is not None else n * h * wd
+    dims = (n, h, wd, cin, cout, kh, kw, int(same), int(relu), rows)
+    nblk = C.c_int(0)
+    check(lib.l3_op_conv2d_dgrad_bn_bwd(device, OP_DTYPES[dtype], *([None] * 9), C.byref(nblk), None, None, *dims))
+    dx = np.empty_like(bn_x)
+    part = np.empty((nblk.value, 2, cin), np.float32)
+    dg, db = np.empty(cin, np.float32), np.empty(cin, np.float32)
+    vecs = [_f32(v) for v in (gamma, beta, mean, var)]
+    assert all(v.shape == (cin,) for v in vecs)
+    check(lib.l3_op_conv2d_dgrad_bn_bwd(device, OP_DTYPES[dtype], _ptr(dy), _ptr(w), _ptr(bn_x), *[_ptr(v) for v in vecs], _ptr(dx),
+                                        _ptr(part), C.byref(nblk), _ptr(dg), _ptr(db), *dims))
+    return dx, part, dg, db
+
+
 def op_bn_relu_fwd(x, gamma, beta, relu, device=0, x_bf16=False):
     lib = load()
     x = _f32(x)
@@ -779,12 +828,18 @@ def op_bn_relu_bwd(x, y, dy, gamma, mean, var, relu, device=0, beta=None, x_bf16
     return dx, dg, db
 
 
-def op_bn_relu_pool2_fwd(x, gamma, beta, same, device=0, relu_mode=1, x_bf16=False):
+def op_bn_relu_pool2_fwd(x, gamma, beta, same, device=0, relu_mode=1, x_bf16=False, want_xwin=False):
+    """want_xwin: as a training forward runs it -- also returns the window winners (p's shape; widened when x_bf16)."""
     lib = load()
     x = _f32(x)
     n, h, wd, c = x.shape
     p = np.empty((n, _pool_out(h, 2, 2, same), _pool_out(wd, 2, 2, same), c), np.float32)
     mean, var = np.empty((c,), np.float32), np.empty((c,), np.float32)
+    if want_xwin:
+        xwin = np.empty_like(p)
+        check(lib.l3_op_bn_relu_pool2_fwd_xwin(device, _ptr(x), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(p), _ptr(mean), _ptr(var),
+                                               _ptr(xwin), n, h, wd, c, int(same), int(relu_mode), int(x_bf16)))
+        return p, mean, var, xwin
     check(lib.l3_op_bn_relu_pool2_fwd(device, _ptr(x), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(p), _ptr(mean),
                                       _ptr(var), n, h, wd, c, int(same), int(relu_mode), int(x_bf16)))
     return p, mean, var

@@ -374,16 +374,14 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_bf16in_kernel(BfArgs a) {
                     }
                     *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(a.y) + (size_t)m * a.Cout + n) = h;
                 } else {
+                    v += bz;                                           // the statistics are those of the STORED values
                     if constexpr (STATS) {
-                        f32x4 d = v;                                   // y - bias
-                        if (srelu) {
+                        f32x4 d;
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) d[e] = fmaxf(v[e] + bz[e], 0.f) - fmaxf(bz[e], 0.f);
-                        }
+                        for (int e = 0; e < 4; ++e) d[e] = srelu ? fmaxf(v[e], 0.f) - fmaxf(bz[e], 0.f) : v[e] - bz[e];
                         st0 += d;
                         st1 += d * d;
                     }
-                    v += bz;
                     *reinterpret_cast<f32x4*>(a.y + (size_t)m * a.Cout + n) = v;
                 }
             }

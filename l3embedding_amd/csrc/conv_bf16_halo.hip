@@ -459,16 +459,17 @@ __global__ __launch_bounds__(256 * WN, (HaloGeom<PW, WN, MODE>::BLOCKS_PER_CU * 
                     }
                     *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(a.y) + o) = h;
                 } else {
+                    // the statistics are those of the STORED values (accumulator + bias, rounded once), as in every other epilogue:
+                    // the accumulator itself differs from y - bias by up to half an ulp of y, which on a short channel with
+                    // |y - bias| << |bias| is more than the BatchNorm's sums are held to
+                    v += bz;
                     if constexpr (STATS) {
-                        f32x4 d = v;
-                        if (srelu) {
+                        f32x4 d;
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) d[e] = fmaxf(v[e] + bz[e], 0.f) - pvt[e];
-                        }
+                        for (int e = 0; e < 4; ++e) d[e] = (srelu ? fmaxf(v[e], 0.f) : v[e]) - pvt[e];
                         st0 += d;
                         st1 += d * d;
                     }
-                    v += bz;
                     *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.y) + o) = v;
                 }
             }
@@ -755,16 +756,16 @@ __global__ __launch_bounds__(256, 4) void conv_bf16_halo64_kernel(HaloArgs a) {
                     }
                     __builtin_amdgcn_raw_buffer_store_b64(hw, ysrd, (int)off[j], 0, 0);
                 } else {
+                    const f32x4 vb = v[j] + bz;          // the statistics are those of the stored values (see conv_bf16_halo_kernel)
                     if constexpr (STATS) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const float d0 = srelu ? fmaxf(v[j][e] + bz[e], 0.f) - pvt[e] : v[j][e];
+                            const float d0 = (srelu ? fmaxf(vb[e], 0.f) : vb[e]) - pvt[e];
                             const float d = in ? d0 : 0.f;
                             st0[e] += d;
                             st1[e] = fmaf(d, d, st1[e]);
                         }
                     }
-                    const f32x4 vb = v[j] + bz;
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, vb), ysrd, in ? (int)(off[j] * 2) : (int)0x80000000u, 0, 0);
                 }
             }

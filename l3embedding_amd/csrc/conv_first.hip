@@ -88,6 +88,11 @@ __global__ __launch_bounds__(256) void conv_first_fwd_kernel(FirstArgs a) {
                 for (int ci = 0; ci < CIN; ++ci) win[r][c + 1][ci] = S[r * ROWF + c * CIN + ci];
         const size_t out_row = ((size_t)row * a.W + x0) * 64 + lane;
         const int npx = min(RUN, a.W - x0);
+        // bf16 output: the statistics of this run on their own, added to the wave's once per run.  One chain over all of a wave's
+        // pixels (16 runs = 512 terms) of bfloat16-valued relu(y) - relu(b) lost up to 3.8e-6 of the sum of magnitudes on a single
+        // block, past the 3e-6 the BatchNorm's sums are held to; per run it is 0.5e-6.  With fp32 output the chain stays (2.5e-6 at
+        // worst, profiles/r27_epilogue_stats_bounds.txt): the fp32 step keeps its moments bit for bit
+        float r0 = 0.f, r1 = 0.f;
         // fully unrolled: the window rotation becomes register renaming instead of 6 x CIN moves per pixel
 #pragma unroll
         for (int px = 0; px < RUN; ++px) {
@@ -117,10 +122,19 @@ __global__ __launch_bounds__(256) void conv_first_fwd_kernel(FirstArgs a) {
                 }
                 if constexpr (STATS) {
                     const float d = (srelu ? fmaxf(yv, 0.f) : yv) - pivot;
-                    s0 += d;
-                    s1 = fmaf(d, d, s1);
+                    if constexpr (OBF) {
+                        r0 += d;
+                        r1 = fmaf(d, d, r1);
+                    } else {
+                        s0 += d;
+                        s1 = fmaf(d, d, s1);
+                    }
                 }
             }
+        }
+        if constexpr (STATS && OBF) {
+            s0 += r0;
+            s1 += r1;
         }
         __builtin_amdgcn_wave_barrier();       // the next run overwrites the slab
     }

@@ -45,6 +45,13 @@ struct ConvDgradPath {
 ConvFwdPath conv_resolve_fwd(const ConvGeom& g, const ConvStorage& st, bool have_u);
 ConvWgradPath conv_resolve_wgrad(const ConvGeom& g, const ConvStorage& st);
 ConvDgradPath conv_resolve_dgrad(const ConvGeom& g, const ConvGeom& dg, const ConvStorage& st, bool have_u);
+// Partial blocks of [2][Cout] the forward epilogue of a resolved path leaves in ConvBufs::stat_part for the BatchNorm behind it
+// (0: that path writes no statistics -- the direct implicit GEMM, the cast-at-fetch bf16 kernel).
+int conv_fwd_stat_blocks(const ConvFwdPath& p, const ConvGeom& g);
+// Partial blocks of [2][dg.Cout] the data gradient's epilogue leaves for the backward reduction of the BatchNorm in front of the
+// convolution (ConvBufs::bn_bwd), -1 where it does not fuse: the halo kernel on bf16-stored tensors (dx and the BatchNorm's
+// input both bfloat16), the Winograd kernels on fp32 ones (both fp32).
+int conv_dgrad_bn_blocks(const ConvDgradPath& p, const ConvGeom& dg, bool dx_bf16, bool bn_x_bf16);
 
 // The device buffers of one launch.  A path reads only those it needs; the rest may be null.
 struct ConvBufs {

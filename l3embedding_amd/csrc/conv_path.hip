@@ -48,6 +48,19 @@ ConvDgradPath conv_resolve_dgrad(const ConvGeom& g, const ConvGeom& dg, const Co
     return p;
 }
 
+int conv_fwd_stat_blocks(const ConvFwdPath& p, const ConvGeom& g) {
+    return p.path == CF_BF16_STORED ? conv_bf16_stat_blocks(g)
+           : p.path == CF_FIRST     ? conv_first_stat_blocks(g)
+           : p.path == CF_FP32 && p.wino_filter ? conv_wino_stat_blocks(g) : 0;
+}
+
+int conv_dgrad_bn_blocks(const ConvDgradPath& p, const ConvGeom& dg, bool dx_bf16, bool bn_x_bf16) {
+    int blocks = -1;
+    if (p.path == DG_BF16_STORED && dx_bf16 && bn_x_bf16 && conv_bf16_halo_ok(dg)) blocks = conv_bf16_stat_blocks(dg);
+    if (p.path == DG_WINO && !dx_bf16 && !bn_x_bf16 && conv_wino_ok(dg)) blocks = conv_wino_stat_blocks(dg);
+    return blocks;
+}
+
 void conv_run_fwd(const ConvFwdPath& p, const ConvGeom& g, const ConvStorage& st, const ConvBufs& b, hipStream_t s) {
     if (p.wino_filter && !b.u_ready) conv_wino_transform_weights(b.w, b.wino_u, g, false, s);
     switch (p.path) {

@@ -1269,9 +1269,7 @@ int plan_tower(l3_engine* e, Tower& tw, bool training, int solo) {
         // forward.  Training: the epilogue also leaves the batch-norm statistic partials of its output
         p.fwd = conv_resolve_fwd(op.geom, p.st, op.wino_uf != nullptr);
         p.fwd_bytes = act_bytes(x) + act_bytes(y) + wbytes;
-        const int nblk = p.fwd.path == CF_BF16_STORED ? conv_bf16_stat_blocks(op.geom)
-                         : p.fwd.path == CF_FIRST     ? conv_first_stat_blocks(op.geom)
-                         : p.fwd.path == CF_FP32 && p.fwd.wino_filter ? conv_wino_stat_blocks(op.geom) : 0;
+        const int nblk = conv_fwd_stat_blocks(p.fwd, op.geom);
         if (epi_stats && training && op.bn_follow >= 0 && e->stat_max > 0 && nblk > 0) {
             if (!fits(op, nblk, op.geom.Cout)) return L3_ESTATE;
             p.stat_mode = tw.ops[op.bn_follow].prerelu ? 2 : 1;
@@ -1297,10 +1295,7 @@ int plan_tower(l3_engine* e, Tower& tw, bool training, int solo) {
         Op* bn = training && op.dy_to_bn >= 0 && e->stat_max > 0 ? &tw.ops[op.dy_to_bn] : nullptr;
         if (bn != nullptr && bn->fuse_pool >= 0 && (bn->xwin == nullptr || x.batch_stride != (int64_t)x.H * x.W * x.C)) bn = nullptr;
         if (bn == nullptr) continue;
-        const bool bx = tw.t[bn->in].d_bf16;
-        int blocks = -1;
-        if (p.dgrad.path == DG_BF16_STORED && x.g_bf16 && bx && conv_bf16_halo_ok(op.dgeom)) blocks = conv_bf16_stat_blocks(op.dgeom);
-        if (p.dgrad.path == DG_WINO && !x.g_bf16 && !bx && conv_wino_ok(op.dgeom)) blocks = conv_wino_stat_blocks(op.dgeom);
+        const int blocks = conv_dgrad_bn_blocks(p.dgrad, op.dgeom, x.g_bf16, tw.t[bn->in].d_bf16);
         if (blocks < 0) continue;
         if (!fits(op, blocks, op.dgeom.Cout)) return L3_ESTATE;
         p.bwd_bn = op.dy_to_bn;

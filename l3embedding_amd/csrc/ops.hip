@@ -254,7 +254,7 @@ int l3_op_bn_relu_bwd(int device, const float* x, const float* y, const float* d
 
 static int pool2_common(int device, const float* x, const float* gamma, const float* beta, const float* dp, float* p,
                         float* mean, float* var, float* dx, float* dgamma, float* dbeta, float* dbias, int n, int h,
-                        int wd, int c, int same, int mode, int x_bf16) {
+                        int wd, int c, int same, int mode, int x_bf16, float* xwin = nullptr) {
     if (!bn_fast_ok(c) || (mode != 1 && mode != 2)) return L3_EINVAL;
     Scope sc(device);
     if (!sc.ok) return L3_EHIP;
@@ -277,8 +277,11 @@ static int pool2_common(int device, const float* x, const float* gamma, const fl
         bn_stats_fast(d_x, d_g, d_b, d_m, d_v, d_sc, d_sh, d_red, (int64_t)n * h * wd, c, 1e-3f, mode == 2 ? 1 : 0, sc.s, x_bf16 & 1);
     else
         bn_stats(d_x, d_g, d_b, d_m, d_v, d_sc, d_sh, d_red, (int64_t)n * h * wd, c, 1e-3f, sc.s);
-    bn_relu_pool2_fwd(d_x, d_sc, d_sh, d_p, n, h, wd, c, g.Ho, g.Wo, g.out_batch_stride, mode, sc.s, 0, x_bf16 & 1);
+    float* d_win = xwin ? sc.alloc<float>(np_) : nullptr;      // the window winners, in x's storage type (the training forward)
+    if (!sc.ok) return L3_ENOMEM;
+    bn_relu_pool2_fwd(d_x, d_sc, d_sh, d_p, n, h, wd, c, g.Ho, g.Wo, g.out_batch_stride, mode, sc.s, 0, x_bf16 & 1, d_win);
     sc.get(p, d_p, np_);
+    if (xwin) sc.get_stored(xwin, d_win, np_, (x_bf16 & 1) != 0);
     sc.get(mean, d_m, (size_t)c);
     sc.get(var, d_v, (size_t)c);
     if (dp) {
@@ -306,6 +309,13 @@ int l3_op_bn_relu_pool2_fwd(int device, const float* x, const float* gamma, cons
                             float* var, int n, int h, int wd, int c, int same, int relu_mode, int x_bf16) {
     return pool2_common(device, x, gamma, beta, nullptr, p, mean, var, nullptr, nullptr, nullptr, nullptr, n, h, wd, c,
                         same, relu_mode, x_bf16);
+}
+
+int l3_op_bn_relu_pool2_fwd_xwin(int device, const float* x, const float* gamma, const float* beta, float* p, float* mean,
+                                 float* var, float* xwin, int n, int h, int wd, int c, int same, int relu_mode, int x_bf16) {
+    if (!xwin) return L3_EINVAL;
+    return pool2_common(device, x, gamma, beta, nullptr, p, mean, var, nullptr, nullptr, nullptr, nullptr, n, h, wd, c,
+                        same, relu_mode, x_bf16, xwin);
 }
 
 int l3_op_bn_relu_pool2_bwd(int device, const float* x, const float* gamma, const float* beta, const float* dp,
@@ -371,6 +381,194 @@ int l3_op_bn_stats_from_partials(int device, const float* part, int nblk, int c,
     sc.get(host.data() + n, d_part + n, guard);
     for (size_t i = 0; i < guard; ++i)
         if (host[n + i] != -12345.f) return L3_EINVAL;
+    return sc.status();
+}
+
+}  // extern "C"
+
+// ---- what the convolution epilogues leave for the BatchNorm beside them, on its own ------------------------------------------------
+namespace {
+// The partial buffer of an epilogue under test: EXACTLY nblk blocks of [2][c], NaN before the launch (a block the kernel does not
+// write stays NaN), and a guard of max(nblk, 8) further blocks of a sentinel behind them (a kernel that writes more blocks than
+// conv_path.h counts changes it).
+struct GuardedPartials {
+    static constexpr float SENTINEL = -12345.f;
+    size_t n = 0, guard = 0, row = 0;
+    float* dev = nullptr;
+    std::vector<float> host;
+    GuardedPartials(Scope& sc, int nblk, int c) {
+        row = (size_t)2 * c;
+        n = (size_t)nblk * 2 * c;
+        guard = (size_t)(nblk > 8 ? nblk : 8) * 2 * c;
+        host.assign(n + guard, SENTINEL);
+        uint32_t nan_bits = 0x7fc00000u;
+        float nan;
+        memcpy(&nan, &nan_bits, sizeof nan);
+        for (size_t i = 0; i < n; ++i) host[i] = nan;
+        dev = sc.put(host.data(), n + guard);
+    }
+    // after the launch that fills them (and BEFORE stage 2, which may reduce in place): download, check, hand out
+    int fetch(Scope& sc, const char* name, float* part) {
+        sc.get(host.data(), dev, n + guard);
+        if (!sc.ok) return L3_EHIP;
+        if (const int rc = guard_check(name)) return rc;
+        for (size_t i = 0; i < n; ++i)
+            if (host[i] != host[i]) {
+                set_op_error(std::string(name) + ": the epilogue left partial block " + std::to_string(i / row) + " unwritten");
+                return L3_EINVAL;
+            }
+        if (part) memcpy(part, host.data(), n * sizeof(float));
+        return L3_OK;
+    }
+    // after stage 2: the guard once more
+    int recheck(Scope& sc, const char* name) {
+        sc.get(host.data() + n, dev + n, guard);
+        if (!sc.ok) return L3_EHIP;
+        return guard_check(name);
+    }
+    int guard_check(const char* name) {
+        for (size_t i = 0; i < guard; ++i)
+            if (host[n + i] != SENTINEL) {
+                set_op_error(std::string(name) + ": float " + std::to_string(i) + " of the guard behind the partial blocks changed");
+                return L3_EINVAL;
+            }
+        return L3_OK;
+    }
+};
+}  // namespace
+
+extern "C" {
+
+// The forward of l3_op_conv2d_fwd_dt with the BatchNorm statistics of its epilogue: same storage, same resolution, same launch,
+// ConvBufs::stat_part / stat_mode set as tower_forward sets them; then the engine's stage 2 with pivot = bias.
+int l3_op_conv2d_fwd_stats(int device, int dtype, const float* x, const float* w, const float* b, float* y, float* part, int* nblk,
+                           float* mean, float* var, int n, int h, int wd, int cin, int cout, int kh, int kw, int same,
+                           int stat_mode) {
+    const char* name = "l3_op_conv2d_fwd_stats";
+    if (!nblk || (stat_mode != 1 && stat_mode != 2)) {
+        set_op_error(std::string(name) + ": NULL nblk or a stat_mode other than 1 (output) and 2 (relu(output))");
+        return L3_EINVAL;
+    }
+    const ConvGeom g = make_geom(n, h, wd, cin, cout, kh, kw, same);
+    const size_t nx = (size_t)n * h * wd * cin, nw = (size_t)kh * kw * cin * cout, ny = (size_t)n * g.Ho * g.Wo * cout;
+    const bool stored = dtype == L3_OP_BF16_STORED || dtype == L3_OP_BF16_STORED_OUT;
+    ConvStorage st;
+    st.mixed = dtype != L3_DTYPE_F32;
+    st.x_bf16 = stored && conv_bf16_ok(g);
+    const ConvFwdPath p = conv_resolve_fwd(g, st, conv_wino_floats(g) != 0);
+    st.y_bf16 = dtype == L3_OP_BF16_STORED_OUT && (p.path == CF_BF16_STORED || p.path == CF_FIRST);
+    const int blocks = conv_fwd_stat_blocks(p, g);
+    if (blocks <= 0) {
+        set_op_error(std::string(name) + ": the resolved forward path leaves no statistics");
+        return L3_EINVAL;
+    }
+    *nblk = blocks;
+    if (!part) return L3_OK;           // the query form: how many blocks to bring
+    if (!x || !w || !b || !y || !mean || !var) {
+        set_op_error(std::string(name) + ": NULL pointer (the bias is the pivot of the sums)");
+        return L3_EINVAL;
+    }
+    Scope sc(device);
+    if (!sc.ok) return L3_EHIP;
+    ConvBufs cb;
+    float* d_x = sc.put(x, nx);
+    cb.x = d_x;
+    cb.w = sc.put(w, nw);
+    cb.bias = sc.put(b, (size_t)cout);
+    cb.y = sc.alloc<float>(ny);
+    cb.wprep = sc.alloc<float>(nw);
+    cb.wino_u = p.wino_filter ? sc.alloc<float>(conv_wino_floats(g)) : nullptr;
+    uint16_t* xb = st.x_bf16 ? sc.alloc<uint16_t>(nx) : nullptr;
+    GuardedPartials gp(sc, blocks, cout);
+    std::vector<float> ones((size_t)cout, 1.f), zeros((size_t)cout, 0.f);
+    float* d_gamma = sc.put(ones.data(), (size_t)cout);
+    float* d_beta = sc.put(zeros.data(), (size_t)cout);
+    float *d_mean = sc.alloc<float>((size_t)cout), *d_var = sc.alloc<float>((size_t)cout);
+    float *d_scale = sc.alloc<float>((size_t)cout), *d_shift = sc.alloc<float>((size_t)cout);
+    if (!sc.ok) return L3_ENOMEM;
+    if (st.x_bf16) {
+        cast_bf16(d_x, xb, (int64_t)nx, sc.s);
+        cb.x = reinterpret_cast<const float*>(xb);
+    }
+    cb.stat_part = gp.dev, cb.stat_mode = stat_mode;
+    conv_run_fwd(p, g, st, cb, sc.s);
+    sc.get_stored(y, cb.y, ny, st.y_bf16);
+    if (const int rc = gp.fetch(sc, name, part)) return rc;
+    bn_stats_from_partials(gp.dev, blocks, cb.bias, d_gamma, d_beta, d_mean, d_var, d_scale, d_shift, (int64_t)n * g.Ho * g.Wo, cout,
+                           1e-3f, stat_mode == 2 ? 1 : 0, sc.s);
+    sc.get(mean, d_mean, (size_t)cout);
+    sc.get(var, d_var, (size_t)cout);
+    if (const int rc = gp.recheck(sc, name)) return rc;
+    return sc.status();
+}
+
+// The data gradient of l3_op_conv2d_bwd_dt with the backward reduction of the BatchNorm(+ReLU) in FRONT of the convolution in its
+// epilogue (BnBwdFuse): n, h, wd, cin, cout are the FORWARD convolution's, so dy is (n, Ho, Wo, cout) and dx, bn_x are
+// (n, h, wd, cin); gamma, beta, mean, var have cin channels.  L3_DTYPE_F32: the Winograd kernels on fp32 tensors;
+// L3_OP_BF16_STORED_OUT: the halo kernel with dy, bn_x and dx bfloat16-stored.  Then bn_bwd_fast's stage 2 alone (dx = NULL).
+int l3_op_conv2d_dgrad_bn_bwd(int device, int dtype, const float* dy, const float* w, const float* bn_x, const float* gamma,
+                              const float* beta, const float* mean, const float* var, float* dx, float* part, int* nblk,
+                              float* dgamma, float* dbeta, int n, int h, int wd, int cin, int cout, int kh, int kw, int same,
+                              int relu, int64_t bn_rows) {
+    const char* name = "l3_op_conv2d_dgrad_bn_bwd";
+    if (!nblk || (dtype != L3_DTYPE_F32 && dtype != L3_OP_BF16_STORED_OUT) || bn_rows < 1 || bn_rows >= (int64_t)1 << 30) {
+        set_op_error(std::string(name) + ": NULL nblk, a dtype other than f32 / bf16_stored_out, or bn_rows outside [1, 2^30)");
+        return L3_EINVAL;
+    }
+    const ConvGeom g = make_geom(n, h, wd, cin, cout, kh, kw, same), dg = conv_dgrad_geom(g);
+    const size_t nx = (size_t)n * h * wd * cin, ny = (size_t)n * g.Ho * g.Wo * cout, nw = (size_t)kh * kw * cin * cout;
+    const bool stored = dtype == L3_OP_BF16_STORED_OUT && conv_bf16_ok(dg);
+    ConvStorage st;
+    st.mixed = dtype != L3_DTYPE_F32;
+    st.dy_bf16 = st.dx_bf16 = stored;
+    const ConvDgradPath pd = conv_resolve_dgrad(g, dg, st, conv_wino_floats(dg) != 0);
+    const int blocks = bn_fast_ok(cin) ? conv_dgrad_bn_blocks(pd, dg, st.dx_bf16, stored) : -1;
+    if (blocks <= 0) {
+        set_op_error(std::string(name) + ": the engine would not leave this BatchNorm's reduction to this data gradient");
+        return L3_EINVAL;
+    }
+    *nblk = blocks;
+    if (!part) return L3_OK;           // the query form
+    if (!dy || !w || !bn_x || !gamma || !beta || !mean || !var || !dx || !dgamma || !dbeta) {
+        set_op_error(std::string(name) + ": NULL pointer");
+        return L3_EINVAL;
+    }
+    Scope sc(device);
+    if (!sc.ok) return L3_EHIP;
+    ConvBufs cb;
+    float* d_dy = sc.put(dy, ny);
+    float* d_bx = sc.put(bn_x, nx);
+    cb.y = d_dy;
+    cb.w = sc.put(w, nw);
+    cb.dx = sc.alloc<float>(nx);
+    cb.wprep = sc.alloc<float>(nw);
+    cb.wino_u = pd.path == DG_WINO ? sc.alloc<float>(conv_wino_floats(dg)) : nullptr;
+    float *d_g = sc.put(gamma, (size_t)cin), *d_b = sc.put(beta, (size_t)cin), *d_m = sc.put(mean, (size_t)cin), *d_v = sc.put(var, (size_t)cin);
+    float *d_sc = sc.alloc<float>((size_t)cin), *d_sh = sc.alloc<float>((size_t)cin);
+    float *d_dg = sc.alloc<float>((size_t)cin), *d_db = sc.alloc<float>((size_t)cin);
+    float* d_red = sc.alloc<float>(bn_fast_scratch_floats(cin));
+    uint16_t* gb = stored ? sc.alloc<uint16_t>(ny) : nullptr;
+    uint16_t* xb = stored ? sc.alloc<uint16_t>(nx) : nullptr;
+    GuardedPartials gp(sc, blocks, cin);
+    if (!sc.ok) return L3_ENOMEM;
+    const float* bx = d_bx;
+    if (stored) {
+        cast_bf16(d_dy, gb, (int64_t)ny, sc.s);
+        cast_bf16(d_bx, xb, (int64_t)nx, sc.s);
+        cb.y = reinterpret_cast<float*>(gb);
+        bx = reinterpret_cast<const float*>(xb);
+    }
+    bn_scale_shift(d_g, d_b, d_m, d_v, d_sc, d_sh, cin, 1e-3f, sc.s);
+    const BnBwdFuse bb{bx, d_sc, d_sh, d_m, d_v, 1e-3f, relu ? 1 : 0};
+    cb.bn_bwd = &bb, cb.stat_part = gp.dev;
+    conv_run_dgrad(pd, g, dg, st, cb, sc.s);
+    sc.get_stored(dx, cb.dx, nx, st.dx_bf16);
+    if (const int rc = gp.fetch(sc, name, part)) return rc;
+    bn_bwd_fast(bx, d_sc, d_sh, d_m, d_v, d_g, cb.dx, 0, 1, 1, (int)bn_rows, cin, 1, (int)bn_rows, bn_rows * cin, nullptr, d_dg, d_db,
+                nullptr, d_red, 1e-3f, relu ? 1 : 0, 1, sc.s, 0, stored ? 1 : 0, stored ? 1 : 0, gp.dev, blocks);
+    sc.get(dgamma, d_dg, (size_t)cin);
+    sc.get(dbeta, d_db, (size_t)cin);
+    if (const int rc = gp.recheck(sc, name)) return rc;
     return sc.status();
 }
 
