@@ -380,7 +380,10 @@ int l3_op_conv2d_bwd(int device, const float *x, const float *w, const float *dy
 /* x_bf16 (these four BatchNorm operators; c a power of two >= 4), a bit mask: bit 0 -- x is first written to HBM as
  * bfloat16 and the kernels that widen it on load run (how an L3_DTYPE_BF16 engine reads the output of a
  * mixed-precision conv); bit 1 (the two backward operators) -- the incoming gradient dy / dp likewise (how it
- * reads the data gradient a mixed-precision conv stored). */
+ * reads the data gradient a mixed-precision conv stored); bit 2 -- the tensor output (y; the pooled p; dx of the two backward
+ * operators) is stored in HBM as bfloat16, rounded to nearest even, as such an engine keeps the operands of its mixed-precision
+ * convs, and comes back widened; l3_op_bn_relu_fwd then runs the fast kernels for either form of x.  The per-channel outputs
+ * (mean, var, dgamma, dbeta, and dbias, the column sum of the UNROUNDED dx) do not depend on bit 2. */
 int l3_op_bn_relu_fwd(int device, const float *x, const float *gamma, const float *beta,
                       float *y, float *mean, float *var, int64_t rows, int c, int relu, int x_bf16);
 /* beta non-NULL and c a power of two >= 4: the engine's fast kernels (ReLU mask recomputed from

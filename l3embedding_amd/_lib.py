@@ -804,7 +804,9 @@ def op_conv2d_dgrad_bn_bwd(dy, w, same, bn_x, gamma, beta, mean, var, relu, bn_r
     return dx, part, dg, db
 
 
-def op_bn_relu_fwd(x, gamma, beta, relu, device=0, x_bf16=False):
+def op_bn_relu_fwd(x, gamma, beta, relu, device=0, x_bf16=False, out_bf16=False):
+    """out_bf16 (the BatchNorm operators): the tensor output -- y, the pooled p, dx -- is stored as bfloat16 on the device (bit 2 of
+    the x_bf16 flag word) and returned widened."""
     lib = load()
     x = _f32(x)
     c = x.shape[-1]
@@ -812,11 +814,11 @@ def op_bn_relu_fwd(x, gamma, beta, relu, device=0, x_bf16=False):
     y = np.empty_like(x)
     mean, var = np.empty((c,), np.float32), np.empty((c,), np.float32)
     check(lib.l3_op_bn_relu_fwd(device, _ptr(x), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(y), _ptr(mean),
-                                _ptr(var), rows, c, int(relu), int(x_bf16)))
+                                _ptr(var), rows, c, int(relu), int(x_bf16) | (4 if out_bf16 else 0)))
     return y, mean, var
 
 
-def op_bn_relu_bwd(x, y, dy, gamma, mean, var, relu, device=0, beta=None, x_bf16=False):
+def op_bn_relu_bwd(x, y, dy, gamma, mean, var, relu, device=0, beta=None, x_bf16=False, out_bf16=False):
     lib = load()
     x, y, dy = _f32(x), _f32(y), _f32(dy)
     c = x.shape[-1]
@@ -824,13 +826,14 @@ def op_bn_relu_bwd(x, y, dy, gamma, mean, var, relu, device=0, beta=None, x_bf16
     dx = np.empty_like(x)
     dg, db = np.empty((c,), np.float32), np.empty((c,), np.float32)
     check(lib.l3_op_bn_relu_bwd(device, _ptr(x), _ptr(y), _ptr(dy), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(_f32(mean)),
-                                _ptr(_f32(var)), _ptr(dx), _ptr(dg), _ptr(db), rows, c, int(relu), int(x_bf16)))
+                                _ptr(_f32(var)), _ptr(dx), _ptr(dg), _ptr(db), rows, c, int(relu), int(x_bf16) | (4 if out_bf16 else 0)))
     return dx, dg, db
 
 
-def op_bn_relu_pool2_fwd(x, gamma, beta, same, device=0, relu_mode=1, x_bf16=False, want_xwin=False):
+def op_bn_relu_pool2_fwd(x, gamma, beta, same, device=0, relu_mode=1, x_bf16=False, want_xwin=False, out_bf16=False):
     """want_xwin: as a training forward runs it -- also returns the window winners (p's shape; widened when x_bf16)."""
     lib = load()
+    flags = int(x_bf16) | (4 if out_bf16 else 0)
     x = _f32(x)
     n, h, wd, c = x.shape
     p = np.empty((n, _pool_out(h, 2, 2, same), _pool_out(wd, 2, 2, same), c), np.float32)
@@ -838,21 +841,21 @@ def op_bn_relu_pool2_fwd(x, gamma, beta, same, device=0, relu_mode=1, x_bf16=Fal
     if want_xwin:
         xwin = np.empty_like(p)
         check(lib.l3_op_bn_relu_pool2_fwd_xwin(device, _ptr(x), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(p), _ptr(mean), _ptr(var),
-                                               _ptr(xwin), n, h, wd, c, int(same), int(relu_mode), int(x_bf16)))
+                                               _ptr(xwin), n, h, wd, c, int(same), int(relu_mode), flags))
         return p, mean, var, xwin
     check(lib.l3_op_bn_relu_pool2_fwd(device, _ptr(x), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(p), _ptr(mean),
-                                      _ptr(var), n, h, wd, c, int(same), int(relu_mode), int(x_bf16)))
+                                      _ptr(var), n, h, wd, c, int(same), int(relu_mode), flags))
     return p, mean, var
 
 
-def op_bn_relu_pool2_bwd(x, gamma, beta, dp, same, device=0, relu_mode=1, x_bf16=False):
+def op_bn_relu_pool2_bwd(x, gamma, beta, dp, same, device=0, relu_mode=1, x_bf16=False, out_bf16=False):
     lib = load()
     x, dp = _f32(x), _f32(dp)
     n, h, wd, c = x.shape
     dx = np.empty_like(x)
     dg, db, dbias = (np.empty((c,), np.float32) for _ in range(3))
     check(lib.l3_op_bn_relu_pool2_bwd(device, _ptr(x), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(dp), _ptr(dx),
-                                      _ptr(dg), _ptr(db), _ptr(dbias), n, h, wd, c, int(same), int(relu_mode), int(x_bf16)))
+                                      _ptr(dg), _ptr(db), _ptr(dbias), n, h, wd, c, int(same), int(relu_mode), int(x_bf16) | (4 if out_bf16 else 0)))
     return dx, dg, db, dbias
 
 

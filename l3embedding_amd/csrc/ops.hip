@@ -174,7 +174,8 @@ int l3_op_bn_relu_fwd(int device, const float* x, const float* gamma, const floa
                       float* var, int64_t rows, int c, int relu, int x_bf16) {
     Scope sc(device);
     if (!sc.ok) return L3_EHIP;
-    if ((x_bf16 & 1) && !bn_fast_ok(c)) return L3_EINVAL;
+    const bool obf = (x_bf16 & 4) != 0;          // y stored as bfloat16 (returned widened): the fast kernels for either input form
+    if ((x_bf16 & 5) && !bn_fast_ok(c)) return L3_EINVAL;
     const size_t n = (size_t)rows * c, cp = (size_t)(c + 3) / 4 * 4;
     float* d_x = sc.put(x, n);
     float* d_g = sc.alloc<float>(cp);
@@ -190,12 +191,15 @@ int l3_op_bn_relu_fwd(int device, const float* x, const float* gamma, const floa
         if (!sc.ok) return L3_ENOMEM;
         cast_bf16(d_x, xb, (int64_t)n, sc.s);
         bn_stats_fast(reinterpret_cast<const float*>(xb), d_g, d_b, d_m, d_v, d_sc, d_sh, d_red, rows, c, 1e-3f, 0, sc.s, 1);
-        bn_apply_fast(reinterpret_cast<const float*>(xb), d_sc, d_sh, d_y, rows, c, relu, sc.s, 0, 1);
+        bn_apply_fast(reinterpret_cast<const float*>(xb), d_sc, d_sh, d_y, rows, c, relu, sc.s, obf ? 1 : 0, 1);
+    } else if (obf) {
+        bn_stats_fast(d_x, d_g, d_b, d_m, d_v, d_sc, d_sh, d_red, rows, c, 1e-3f, 0, sc.s, 0);
+        bn_apply_fast(d_x, d_sc, d_sh, d_y, rows, c, relu, sc.s, 1, 0);
     } else {
         bn_stats(d_x, d_g, d_b, d_m, d_v, d_sc, d_sh, d_red, rows, c, 1e-3f, sc.s);
         bn_apply(d_x, d_sc, d_sh, d_y, rows, c, relu, sc.s);
     }
-    sc.get(y, d_y, n);
+    sc.get_stored(y, d_y, n, obf);
     sc.get(mean, d_m, (size_t)c);
     sc.get(var, d_v, (size_t)c);
     return sc.status();
@@ -215,6 +219,7 @@ int l3_op_bn_relu_bwd(int device, const float* x, const float* y, const float* d
     float* d_dx = sc.alloc<float>(n);
     const bool fast = beta != nullptr && bn_fast_ok(c) && rows < (int64_t)1 << 30;
     if (x_bf16 && !fast) return L3_EINVAL;
+    const bool obf = (x_bf16 & 4) != 0;          // dx stored as bfloat16 (returned widened)
     size_t red = colreduce_scratch_floats(rows, c);
     if (fast && bn_fast_scratch_floats(c) > red) red = bn_fast_scratch_floats(c);
     float* d_red = sc.alloc<float>(red);
@@ -242,11 +247,11 @@ int l3_op_bn_relu_bwd(int device, const float* x, const float* y, const float* d
             dyin = reinterpret_cast<const float*>(gb);
         }
         bn_bwd_fast(xin, d_sc, d_sh, d_m, d_v, d_g, dyin, 0, 1, 1, (int)rows, c, 1, (int)rows, (int64_t)rows * c, d_dx, d_dg,
-                    d_db, nullptr, d_red, 1e-3f, relu, 1, sc.s, 0, (x_bf16 & 1) ? 1 : 0, (x_bf16 & 2) ? 1 : 0);
+                    d_db, nullptr, d_red, 1e-3f, relu, 1, sc.s, obf ? 1 : 0, (x_bf16 & 1) ? 1 : 0, (x_bf16 & 2) ? 1 : 0);
     } else {
         bn_bwd(d_x, d_y, d_dy, d_g, d_m, d_v, d_dx, d_dg, d_db, d_red, rows, c, 1e-3f, relu, 1, sc.s);
     }
-    sc.get(dx, d_dx, n);
+    sc.get_stored(dx, d_dx, n, obf);
     sc.get(dgamma, d_dg, (size_t)c);
     sc.get(dbeta, d_db, (size_t)c);
     return sc.status();
@@ -260,6 +265,7 @@ static int pool2_common(int device, const float* x, const float* gamma, const fl
     if (!sc.ok) return L3_EHIP;
     const PoolGeom g = make_pool(n, h, wd, c, 2, 2, 2, 2, same);
     const size_t nx = (size_t)n * h * wd * c, np_ = (size_t)n * g.Ho * g.Wo * c;
+    const bool obf = (x_bf16 & 4) != 0;          // p (forward) / dx (backward) stored as bfloat16, returned widened
     float* d_x = sc.put(x, nx);
     float* d_g = sc.put(gamma, (size_t)c);
     float* d_b = sc.put(beta, (size_t)c);
@@ -279,8 +285,8 @@ static int pool2_common(int device, const float* x, const float* gamma, const fl
         bn_stats(d_x, d_g, d_b, d_m, d_v, d_sc, d_sh, d_red, (int64_t)n * h * wd, c, 1e-3f, sc.s);
     float* d_win = xwin ? sc.alloc<float>(np_) : nullptr;      // the window winners, in x's storage type (the training forward)
     if (!sc.ok) return L3_ENOMEM;
-    bn_relu_pool2_fwd(d_x, d_sc, d_sh, d_p, n, h, wd, c, g.Ho, g.Wo, g.out_batch_stride, mode, sc.s, 0, x_bf16 & 1, d_win);
-    sc.get(p, d_p, np_);
+    bn_relu_pool2_fwd(d_x, d_sc, d_sh, d_p, n, h, wd, c, g.Ho, g.Wo, g.out_batch_stride, mode, sc.s, obf ? 1 : 0, x_bf16 & 1, d_win);
+    sc.get_stored(p, d_p, np_, obf);
     if (xwin) sc.get_stored(xwin, d_win, np_, (x_bf16 & 1) != 0);
     sc.get(mean, d_m, (size_t)c);
     sc.get(var, d_v, (size_t)c);
@@ -296,8 +302,8 @@ static int pool2_common(int device, const float* x, const float* gamma, const fl
         float *d_dg = sc.alloc<float>(c), *d_db = sc.alloc<float>(c), *d_dbias = sc.alloc<float>(c);
         if (!sc.ok) return L3_ENOMEM;
         bn_bwd_fast(d_x, d_sc, d_sh, d_m, d_v, d_g, d_dp, 1, n, h, wd, c, g.Ho, g.Wo, g.out_batch_stride, d_dx, d_dg,
-                    d_db, d_dbias, d_red, 1e-3f, mode, 1, sc.s, 0, x_bf16 & 1, (x_bf16 & 2) ? 1 : 0);
-        sc.get(dx, d_dx, nx);
+                    d_db, d_dbias, d_red, 1e-3f, mode, 1, sc.s, obf ? 1 : 0, x_bf16 & 1, (x_bf16 & 2) ? 1 : 0);
+        sc.get_stored(dx, d_dx, nx, obf);
         sc.get(dgamma, d_dg, (size_t)c);
         sc.get(dbeta, d_db, (size_t)c);
         sc.get(dbias, d_dbias, (size_t)c);

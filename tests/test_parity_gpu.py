@@ -184,7 +184,8 @@ def test_maxpool_exact(gpu_required, cfg):
     assert np.array_equal(_lib.op_maxpool_bwd(x, dy, ph, pw, ph, pw, same), o.maxpool_bwd(dy, cache))
 
 
-@pytest.mark.parametrize('cfg', [(2, 8, 8, 64, 0), (2, 9, 7, 16, 0), (2, 9, 7, 16, 1), (1, 199, 6, 64, 0), (3, 10, 11, 128, 1), (1, 4, 4, 512, 1)])
+@pytest.mark.parametrize('cfg', [(2, 8, 8, 64, 0), (2, 9, 7, 16, 0), (2, 9, 7, 16, 1), (1, 199, 6, 64, 0), (3, 10, 11, 128, 1), (1, 4, 4, 512, 1),
+                                 (2, 9, 7, 4, 1), (2, 6, 5, 8, 0), (1, 4, 4, 1024, 1)])       # C4 = 1, C = 8, C4 = the block size
 def test_fused_bn_relu_pool2(gpu_required, cfg):
     """Conv-BN-ReLU-MaxPool tail as one kernel (full-resolution activation never stored):
     forward and backward against the unfused oracle ops, odd sizes, 'valid' and 'same'."""
