@@ -732,6 +732,8 @@ int l3_op_vggish_postprocess(int device, const float *emb, int64_t n, const floa
 typedef struct l3_feat l3_feat;
 /* X (n, D) float32 row major, copied to the device once.  1 <= n <= 2^31 - 1, 1 <= D <= 2^21 (any D, not only multiples of 4). */
 int l3_feat_create(int device, const float *X, int64_t n, int64_t D, l3_feat **f);
+/* A zero-filled (n, D) matrix for rows the device produces (l3_embed_audio_frames_dev); limits and errors as l3_feat_create */
+int l3_feat_alloc(int device, int64_t n, int64_t D, l3_feat **f);
 void l3_feat_destroy(l3_feat *f);
 int l3_feat_shape(const l3_feat *f, int64_t *n, int64_t *D);
 /* rows [lo, hi) -> dst ((hi - lo), D) */
@@ -794,6 +796,29 @@ int l3_mlp_set_data_dev(l3_mlp *m, const l3_feat *train, int64_t lo, int64_t hi,
                         int64_t vhi, const int32_t *yv);
 /* l3_mlp_predict of rows [lo, hi) of a device matrix, in l3_mlp_predict's row blocks without its staging copy: the same bits */
 int l3_mlp_predict_dev(l3_mlp *m, const l3_feat *x, int64_t lo, int64_t hi, float *probs_out);
+/* The per-file step of the classifiers' test metrics and of notebooks/pimodel.ipynb on l3_mlp_predict_dev's probabilities, which
+ * stay on the device: file_mean (n_files, C) float32 and file_pred (n_files) int32 (either may be NULL) of the rows [s_i, e_i) of x
+ * that file_idxs[i] = {s_i, e_i} names (host int64 pairs, 0 <= s_i < e_i <= n, in any order, overlaps allowed).  The arithmetic is
+ * NumPy's probs[s:e].mean(axis=0).argmax() on float32 rows: a float32 sum in row order, one float32 division by fl32(e - s), the
+ * first maximum.  One wave per file, a lane per class (C <= 64), no atomics: deterministic.  L3_EINVAL for a NULL pointer, a matrix
+ * on another device or of another width, C > 64, n_files < 1 or a bad range (the message names the file). */
+int l3_mlp_predict_files_dev(l3_mlp *m, const l3_feat *x, const int64_t *file_idxs, int64_t n_files, float *file_mean,
+                             int32_t *file_pred);
+/* That reduction on its own, on host probabilities probs (n, C) float32 (kernel tests) */
+int l3_op_file_mean(int device, const float *probs, int64_t n, int C, const int64_t *file_idxs, int64_t n_files, float *file_mean,
+                    int32_t *file_pred);
+
+/* l3_embed_audio_frames and l3_embed_audio_clips_resampled with the pooled rows kept on the device: the same validation, gather or
+ * resampling, front-end, tower and pooling, whose kernel writes rows [row0, row0 + n_frames) of dst directly (of the last, partial
+ * engine batch only its real rows) -- the same bits as `out` receives, and no other row of dst is touched.  The work runs on the
+ * engine's stream and has finished when the call returns, as every call on an l3_feat has; no other call may run on dst meanwhile.
+ * L3_EINVAL (message in l3_last_error(e)) with nothing written also for a NULL dst, a dst on another device than the engine, of
+ * another width than l3_embed_dim, row0 < 0 or row0 + n_frames > n. */
+int l3_embed_audio_frames_dev(l3_engine *e, const float *samples, int64_t n_samples, const int64_t *table, int64_t n_frames,
+                              int pool_h, int pool_w, l3_feat *dst, int64_t row0);
+int l3_embed_audio_clips_resampled_dev(l3_engine *e, const float *native, int64_t n_native, const int64_t *clips, int64_t n_clips,
+                                       const double *half_window, int64_t n_window, int num_table, int64_t n_samples,
+                                       const int64_t *table, int64_t n_frames, int pool_h, int pool_w, l3_feat *dst, int64_t row0);
 
 /* ---- A group of MLP classifiers (the learning_rate x weight_decay search of classifier/train.py:638-651) ---------------------------
  * n_members models of one shape (D, C, batch) trained on ONE resident data set in the same launches: an epoch's step is seven

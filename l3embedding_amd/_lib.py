@@ -117,6 +117,12 @@ SIGNATURES = {
     'l3_embed_audio_clips_resampled': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                  C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                                  C.c_void_p]),
+    # ... with the pooled rows kept on the device, in rows [row0, row0 + n_frames) of an l3_feat
+    'l3_embed_audio_frames_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_int64]),
+    'l3_embed_audio_clips_resampled_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                                     C.c_void_p, C.c_int64]),
     'l3_get_activation': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     'l3_activation_numel': (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
     'l3_sync': (C.c_int, [C.c_void_p]),
@@ -220,6 +226,7 @@ SIGNATURES = {
     'l3_op_vggish_conv': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6),
     # fold preprocessing of the classifier (csrc/featprep.hip) and its hand-off to the MLP (csrc/mlp.hip)
     'l3_feat_create': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    'l3_feat_alloc': (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     'l3_feat_destroy': (None, [C.c_void_p]),
     'l3_feat_shape': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'l3_feat_download': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
@@ -234,6 +241,8 @@ SIGNATURES = {
     'l3_mlp_set_data_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                       C.c_void_p]),
     'l3_mlp_predict_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'l3_mlp_predict_files_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'l3_op_file_mean': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     # a group of MLPs trained in the same launches (csrc/mlp.hip)
     'l3_mlp_group_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     'l3_mlp_group_destroy': (None, [C.c_void_p]),
@@ -654,11 +663,21 @@ class Engine(object):
         check(self.lib.l3_embed_audio(self.h, _ptr(a), a.shape[0], pool[0], pool[1], _ptr(out)), self.h)
         return out
 
-    def embed_audio_frames(self, samples, table, pool, out=None):
+    def embed_audio_frames(self, samples, table, pool, out=None, dst=None, row0=0):
         """l3_embed_audio_frames: samples (n,) float32 (clips back to back), table (n_frames, 3) int64 {start, lo, hi}
-        (features.frame_table) -> (n_frames, D) embeddings, written into `out` when given (C-contiguous float32)."""
+        (features.frame_table) -> (n_frames, D) embeddings, written into `out` when given (C-contiguous float32).
+        dst: a Features on the engine's device; the rows then stay there, in rows [row0, row0 + n_frames) of dst
+        (l3_embed_audio_frames_dev), and dst is returned."""
         s = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
         t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 3)
+        if dst is not None:
+            if out is not None:
+                raise ValueError('give out or dst, not both')
+            if s.size == 0:
+                s = np.zeros(1, np.float32)[:0]
+            check(self.lib.l3_embed_audio_frames_dev(self.h, _ptr(s), s.size, _ptr(t), t.shape[0], pool[0], pool[1], dst.h,
+                                                     int(row0)), self.h)
+            return dst
         d = self.lib.l3_embed_dim(self.h, 0, pool[0], pool[1])
         if out is None:
             out = np.empty((t.shape[0], max(d, 0)), np.float32)
@@ -670,15 +689,26 @@ class Engine(object):
               self.h)
         return out
 
-    def embed_audio_clips_resampled(self, native, clips, half_window, num_table, n_samples, table, pool, out=None):
+    def embed_audio_clips_resampled(self, native, clips, half_window, num_table, n_samples, table, pool, out=None, dst=None,
+                                    row0=0):
         """l3_embed_audio_clips_resampled: native (n,) float32 (clips at their own rates back to back), clips (n_clips, 6) int64
         {x_off, L, sr_orig, t0, n_out, y_off}, half_window (n_window,) float64 with num_table entries per zero crossing,
         n_samples the 48 kHz buffer the rows fill, table (n_frames, 3) int64 {start, lo, hi} over it -> (n_frames, D)
-        embeddings, written into `out` when given (C-contiguous float32)."""
+        embeddings, written into `out` when given (C-contiguous float32).  dst, row0: as embed_audio_frames'
+        (l3_embed_audio_clips_resampled_dev)."""
         x = np.ascontiguousarray(native, dtype=np.float32).reshape(-1)
         c = np.ascontiguousarray(clips, dtype=np.int64).reshape(-1, 6)
         w = np.ascontiguousarray(half_window, dtype=np.float64).reshape(-1)
         t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 3)
+        if dst is not None:
+            if out is not None:
+                raise ValueError('give out or dst, not both')
+            if x.size == 0:
+                x = np.zeros(1, np.float32)[:0]
+            check(self.lib.l3_embed_audio_clips_resampled_dev(self.h, _ptr(x), x.size, _ptr(c), c.shape[0], _ptr(w), w.size,
+                                                              int(num_table), int(n_samples), _ptr(t), t.shape[0], pool[0],
+                                                              pool[1], dst.h, int(row0)), self.h)
+            return dst
         d = self.lib.l3_embed_dim(self.h, 0, pool[0], pool[1])
         if out is None:
             out = np.empty((t.shape[0], max(d, 0)), np.float32)
@@ -1105,6 +1135,16 @@ class MLP(object):
             check(self.lib.l3_mlp_predict_dev(self.h, feat.h, int(lo), int(hi), _ptr(out)))
         return out
 
+    def predict_files_dev(self, feat, files):
+        """-> (file_mean (F, C) float32, file_pred (F,) int32): predict_dev's probabilities of the Features `feat`, kept on the
+        device, reduced there over the rows [s, e) of each files entry (l3_mlp_predict_files_dev)"""
+        f = _i64(files)
+        if f.ndim != 2 or f.shape[1] != 2:
+            raise ValueError('files must be (n_files, 2) row ranges')
+        mean, pred = np.empty((f.shape[0], self.C), np.float32), np.empty(f.shape[0], np.int32)
+        check(self.lib.l3_mlp_predict_files_dev(self.h, feat.h, _ptr(f), f.shape[0], _ptr(mean), _ptr(pred)))
+        return mean, pred
+
 
 MLP_MAX_MEMBERS = 16
 
@@ -1254,6 +1294,17 @@ class Features(object):
         self.h = h
         self.device = int(device)
 
+    @classmethod
+    def alloc(cls, n, D, device=0):
+        """A zero-filled (n, D) Features for rows the device writes (Engine.embed_audio_frames(dst=...)): l3_feat_alloc"""
+        self = cls.__new__(cls)
+        self.lib = load()
+        h = C.c_void_p()
+        check(self.lib.l3_feat_alloc(int(device), int(n), int(D), C.byref(h)), None)
+        self.h = h
+        self.device = int(device)
+        return self
+
     SEGMENT = np.dtype([('src', np.uintp), ('lo', np.int64), ('hi', np.int64)])          # l3_feat_segment
 
     @classmethod
@@ -1347,6 +1398,15 @@ class Features(object):
         if f.ndim != 2 or f.shape[1] != 2:
             raise ValueError('file_idxs must be (n_files, 2) row ranges')
         check(self.lib.l3_feat_file_stats(self.h, _ptr(f), f.shape[0]))
+
+
+def op_file_mean(probs, files, device=0):
+    """l3_op_file_mean: probs (n, C) float32, files (F, 2) row ranges -> (file_mean (F, C) float32, file_pred (F,) int32)"""
+    p = _f32(probs)
+    f = _i64(files).reshape(-1, 2)
+    mean, pred = np.empty((f.shape[0], p.shape[1]), np.float32), np.empty(f.shape[0], np.int32)
+    check(load().l3_op_file_mean(int(device), _ptr(p), p.shape[0], p.shape[1], _ptr(f), f.shape[0], _ptr(mean), _ptr(pred)))
+    return mean, pred
 
 
 def op_mlp_dense_fwd(x, w, b, idx=None, relu=True, device=0):

@@ -184,6 +184,15 @@ class MLPModel(object):
         h = self._handle(self._h.batch if self._h is not None else 64)
         return h.predict_dev(x.handle) if isinstance(x, DeviceFeatures) else h.predict(x)
 
+    def predict_files(self, x, file_idxs):
+        """-> (file_proba (F, C) float32, file_predict (F,)): the mean of predict(x)[s:e] of each file_idxs entry and its arg-max,
+        _file_predictions' bits.  x: a usc.DeviceFeatures; the (n, C) probabilities never leave the GPU (l3_mlp_predict_files_dev)."""
+        if not isinstance(x, DeviceFeatures):
+            raise TypeError('predict_files takes a usc.DeviceFeatures; on host rows use predict and _file_predictions')
+        h = self._handle(self._h.batch if self._h is not None else 64)
+        mean, pred = h.predict_files_dev(x.handle, np.asarray(file_idxs, np.int64).reshape(-1, 2))
+        return mean, pred.astype(np.int64)
+
     def fit(self, x, y, batch_size=64, epochs=1, verbose=0, callbacks=None, validation_split=0.0, validation_data=None,
             shuffle=True, random_state=None):
         """keras Model.fit with shuffle=True: y one-hot (n, C); validation_split takes the LAST fraction of x before any

@@ -24,6 +24,7 @@
 #include "../../include/l3hip.h"
 #include "comm.h"
 #include "conv_path.h"
+#include "featprep.h"
 #include "kernels.h"
 
 namespace {
@@ -2771,17 +2772,31 @@ static int embed_check(l3_engine* e, bool vision, int ph, int pw, int64_t* D) {
     return L3_OK;
 }
 
+// Where the pooled rows go: the caller's host rows `host` (n x D), or rows [row0, row0 + n) of the device matrix `feat`
+// (l3_embed_audio_frames_dev), which the pool kernel writes directly.
+struct EmbedDest {
+    bool dev = false;          // which of the two the entry point takes (its pointer may be NULL: an argument error)
+    float* host = nullptr;
+    l3_feat* feat = nullptr;
+    int64_t row0 = 0;
+};
+
 // load_embedding(...).predict on n rows: per engine batch, the input rows -> (audio) front-end -> solo tower forward ->
-// MaxPooling2D into the device output buffer; the pooled rows go to the host when the buffer is full and at the end.
-static int embed_rows(l3_engine* e, bool vision, const EmbedSource& src, int64_t n, int ph, int pw, int64_t D, float* out) {
+// MaxPooling2D.  To the host: into the device output buffer, whose pooled rows go to the host when the buffer is full and at the
+// end.  To a device matrix: straight into its rows, only the `cnt` real rows of the last engine batch (the matrix is not rounded up
+// to whole batches as emb_out is); the call returns when the engine's stream has finished, as every call on an l3_feat does.
+static int embed_rows(l3_engine* e, bool vision, const EmbedSource& src, int64_t n, int ph, int pw, int64_t D, const EmbedDest& dst) {
     Tower& tw = vision ? e->vis : e->aud;
     const int B = e->B;
-    int64_t cap_rows = (int64_t)(EMBED_OUT_BYTES / ((size_t)D * 4)) / B * B;
-    if (cap_rows < B) cap_rows = B;
-    const int64_t need_rows = (n + B - 1) / B * B;
-    if (cap_rows > need_rows) cap_rows = need_rows;
-    int rc = dev_grow_t(e, &e->emb_out, &e->emb_out_cap, (size_t)cap_rows * D);
-    if (rc) return rc;
+    int rc = L3_OK;
+    int64_t cap_rows = 0;
+    if (!dst.dev) {
+        cap_rows = (int64_t)(EMBED_OUT_BYTES / ((size_t)D * 4)) / B * B;
+        if (cap_rows < B) cap_rows = B;
+        const int64_t need_rows = (n + B - 1) / B * B;
+        if (cap_rows > need_rows) cap_rows = need_rows;
+        if ((rc = dev_grow_t(e, &e->emb_out, &e->emb_out_cap, (size_t)cap_rows * D))) return rc;
+    }
     const Tensor& t = tw.t[tw.ops[tw.emb_conv_op].out];
     PoolGeom pg{};
     pg.N = B; pg.H = t.H; pg.W = t.W; pg.C = t.C; pg.ph = ph; pg.pw = pw; pg.sh = ph; pg.sw = pw;
@@ -2805,13 +2820,19 @@ static int embed_rows(l3_engine* e, bool vision, const EmbedSource& src, int64_t
         }
         if ((rc = plan_tower(e, tw, false, 1))) return rc;
         tower_forward(e, tw);
+        if (dst.dev) {
+            pg.N = (int)cnt;          // rows [row0 + s0, row0 + s0 + cnt) and not one more
+            maxpool_fwd(t.d, dst.feat->x + (size_t)(dst.row0 + s0) * D, pg, e->stream);
+            continue;
+        }
         maxpool_fwd(t.d, e->emb_out + (size_t)(s0 - f0) * D, pg, e->stream);
         if (s0 + cnt == n || s0 + 2 * B - f0 > cap_rows) {
-            HIPCHK(e, hipMemcpyAsync(out + (size_t)f0 * D, e->emb_out, (size_t)(s0 + cnt - f0) * D * 4, hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(e, hipMemcpyAsync(dst.host + (size_t)f0 * D, e->emb_out, (size_t)(s0 + cnt - f0) * D * 4, hipMemcpyDeviceToHost, e->stream));
             HIPCHK(e, l3::stream_wait(e->stream));
             f0 = s0 + B;
         }
     }
+    if (dst.dev) HIPCHK(e, l3::stream_wait(e->stream));
     prof_collect(e);
     return L3_OK;
 }
@@ -2824,7 +2845,9 @@ static int embed_common(l3_engine* e, bool vision, const float* in, int64_t n, i
     if (rc) return rc;
     EmbedSource src;
     src.host = in;
-    return embed_rows(e, vision, src, n, ph, pw, D, out);
+    EmbedDest dst;
+    dst.host = out;
+    return embed_rows(e, vision, src, n, ph, pw, D, dst);
 }
 
 int l3_embed_audio(l3_engine* e, const float* audio, int64_t n, int pool_h, int pool_w, float* out) {
@@ -2834,23 +2857,42 @@ int l3_embed_vision(l3_engine* e, const float* video, int64_t n, int pool_h, int
     return embed_common(e, true, video, n, pool_h, pool_w, out);
 }
 
-int l3_embed_audio_frames(l3_engine* e, const float* samples, int64_t n_samples, const int64_t* table, int64_t n_frames,
-                          int pool_h, int pool_w, float* out) {
-    if (!e) return L3_EINVAL;
-    if (!samples || !table || !out) {
-        e->err = "l3_embed_audio_frames: samples, table and out must not be NULL";
+// The destination of a call is its host rows or a device matrix; for the matrix: on the engine's device, D wide, rows
+// [row0, row0 + n_frames) inside it.  Checked before anything is uploaded or written.
+static int embed_dest_check(l3_engine* e, const char* fn, const EmbedDest& dst, int64_t n_frames, int64_t D) {
+    if (!dst.dev) return L3_OK;
+    const l3_feat* f = dst.feat;
+    std::string why;
+    if (f->device != e->cfg.device)
+        why = "dst is on device " + std::to_string(f->device) + ", the engine on device " + std::to_string(e->cfg.device);
+    else if (f->D != D)
+        why = "dst has " + std::to_string(f->D) + " columns, the embedding " + std::to_string(D);
+    else if (dst.row0 < 0 || n_frames > f->n || dst.row0 > f->n - n_frames)
+        why = "rows [" + std::to_string(dst.row0) + ", " + std::to_string(dst.row0) + " + " + std::to_string(n_frames) +
+              ") outside the " + std::to_string(f->n) + " rows of dst";
+    if (why.empty()) return L3_OK;
+    e->err = std::string(fn) + ": " + why;
+    return L3_EINVAL;
+}
+
+static int embed_frames_to(l3_engine* e, const char* fn, const float* samples, int64_t n_samples, const int64_t* table, int64_t n_frames,
+                           int pool_h, int pool_w, const EmbedDest& dst) {
+    const std::string name(fn);
+    if (!samples || !table || !(dst.host || dst.feat)) {
+        e->err = name + ": samples, table and " + (dst.dev ? "dst" : "out") + " must not be NULL";
         return L3_EINVAL;
     }
     if (n_samples < 0 || n_frames < 0) {
-        e->err = "l3_embed_audio_frames: n_samples and n_frames must be >= 0";
+        e->err = name + ": n_samples and n_frames must be >= 0";
         return L3_EINVAL;
     }
     int64_t D = 0;
     int rc = embed_check(e, false, pool_h, pool_w, &D);
     if (rc) return rc;
+    if ((rc = embed_dest_check(e, fn, dst, n_frames, D))) return rc;
     int64_t bad = 0;
     if (const char* why = frame_table_error(table, n_frames, n_samples, &bad)) {
-        e->err = std::string("l3_embed_audio_frames: frame ") + std::to_string(bad) + ": " + why;
+        e->err = name + ": frame " + std::to_string(bad) + ": " + why;
         return L3_EINVAL;
     }
     if (n_frames == 0) return L3_OK;
@@ -2863,31 +2905,48 @@ int l3_embed_audio_frames(l3_engine* e, const float* samples, int64_t n_samples,
     EmbedSource src;
     src.samples = e->clip_samples;
     src.table = e->clip_table;
-    return embed_rows(e, false, src, n_frames, pool_h, pool_w, D, out);
+    return embed_rows(e, false, src, n_frames, pool_h, pool_w, D, dst);
 }
 
-int l3_embed_audio_clips_resampled(l3_engine* e, const float* native, int64_t n_native, const int64_t* clips, int64_t n_clips,
-                                   const double* half_window, int64_t n_window, int num_table, int64_t n_samples,
-                                   const int64_t* table, int64_t n_frames, int pool_h, int pool_w, float* out) {
+int l3_embed_audio_frames(l3_engine* e, const float* samples, int64_t n_samples, const int64_t* table, int64_t n_frames,
+                          int pool_h, int pool_w, float* out) {
     if (!e) return L3_EINVAL;
-    if (!native || !clips || !half_window || !table || !out) {
-        e->err = "l3_embed_audio_clips_resampled: native, clips, half_window, table and out must not be NULL";
+    EmbedDest dst;
+    dst.host = out;
+    return embed_frames_to(e, "l3_embed_audio_frames", samples, n_samples, table, n_frames, pool_h, pool_w, dst);
+}
+
+int l3_embed_audio_frames_dev(l3_engine* e, const float* samples, int64_t n_samples, const int64_t* table, int64_t n_frames,
+                              int pool_h, int pool_w, l3_feat* dst_feat, int64_t row0) {
+    if (!e) return L3_EINVAL;
+    EmbedDest dst;
+    dst.dev = true, dst.feat = dst_feat, dst.row0 = row0;
+    return embed_frames_to(e, "l3_embed_audio_frames_dev", samples, n_samples, table, n_frames, pool_h, pool_w, dst);
+}
+
+static int embed_clips_resampled_to(l3_engine* e, const char* fn, const float* native, int64_t n_native, const int64_t* clips,
+                                    int64_t n_clips, const double* half_window, int64_t n_window, int num_table, int64_t n_samples,
+                                    const int64_t* table, int64_t n_frames, int pool_h, int pool_w, const EmbedDest& dst) {
+    const std::string name(fn);
+    if (!native || !clips || !half_window || !table || !(dst.host || dst.feat)) {
+        e->err = name + ": native, clips, half_window, table and " + (dst.dev ? "dst" : "out") + " must not be NULL";
         return L3_EINVAL;
     }
     if (n_native < 0 || n_clips < 0 || n_samples < 0 || n_frames < 0) {
-        e->err = "l3_embed_audio_clips_resampled: n_native, n_clips, n_samples and n_frames must be >= 0";
+        e->err = name + ": n_native, n_clips, n_samples and n_frames must be >= 0";
         return L3_EINVAL;
     }
     int64_t D = 0;
     int rc = embed_check(e, false, pool_h, pool_w, &D);
     if (rc) return rc;
+    if ((rc = embed_dest_check(e, fn, dst, n_frames, D))) return rc;
     int64_t bad = 0;
     if (const char* why = resample_clips_error(clips, n_clips, n_native, AUDIO_T, n_window, num_table, n_samples, true, &bad)) {
-        e->err = std::string("l3_embed_audio_clips_resampled: ") + (bad >= 0 ? "clip " + std::to_string(bad) + ": " : std::string()) + why;
+        e->err = name + ": " + (bad >= 0 ? "clip " + std::to_string(bad) + ": " : std::string()) + why;
         return L3_EINVAL;
     }
     if (const char* why = frame_table_error(table, n_frames, n_samples, &bad)) {
-        e->err = std::string("l3_embed_audio_clips_resampled: frame ") + std::to_string(bad) + ": " + why;
+        e->err = name + ": frame " + std::to_string(bad) + ": " + why;
         return L3_EINVAL;
     }
     if (n_frames == 0) return L3_OK;
@@ -2901,7 +2960,28 @@ int l3_embed_audio_clips_resampled(l3_engine* e, const float* native, int64_t n_
     EmbedSource src;
     src.samples = e->clip_samples;
     src.table = e->clip_table;
-    return embed_rows(e, false, src, n_frames, pool_h, pool_w, D, out);
+    return embed_rows(e, false, src, n_frames, pool_h, pool_w, D, dst);
+}
+
+int l3_embed_audio_clips_resampled(l3_engine* e, const float* native, int64_t n_native, const int64_t* clips, int64_t n_clips,
+                                   const double* half_window, int64_t n_window, int num_table, int64_t n_samples,
+                                   const int64_t* table, int64_t n_frames, int pool_h, int pool_w, float* out) {
+    if (!e) return L3_EINVAL;
+    EmbedDest dst;
+    dst.host = out;
+    return embed_clips_resampled_to(e, "l3_embed_audio_clips_resampled", native, n_native, clips, n_clips, half_window, n_window,
+                                    num_table, n_samples, table, n_frames, pool_h, pool_w, dst);
+}
+
+int l3_embed_audio_clips_resampled_dev(l3_engine* e, const float* native, int64_t n_native, const int64_t* clips, int64_t n_clips,
+                                       const double* half_window, int64_t n_window, int num_table, int64_t n_samples,
+                                       const int64_t* table, int64_t n_frames, int pool_h, int pool_w, l3_feat* dst_feat,
+                                       int64_t row0) {
+    if (!e) return L3_EINVAL;
+    EmbedDest dst;
+    dst.dev = true, dst.feat = dst_feat, dst.row0 = row0;
+    return embed_clips_resampled_to(e, "l3_embed_audio_clips_resampled_dev", native, n_native, clips, n_clips, half_window, n_window,
+                                    num_table, n_samples, table, n_frames, pool_h, pool_w, dst);
 }
 
 int l3_activation_numel(l3_engine* e, const char* name, int64_t* numel) {

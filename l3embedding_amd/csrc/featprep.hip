@@ -412,6 +412,27 @@ int l3_feat_create(int device, const float* X, int64_t n, int64_t D, l3_feat** o
     return L3_OK;
 }
 
+int l3_feat_alloc(int device, int64_t n, int64_t D, l3_feat** out) {
+    if (!out) return fail(L3_EINVAL, "l3_feat_alloc: out is NULL");
+    *out = nullptr;
+    if (n < 1 || n > INT32_MAX || D < 1 || D > (1 << 21))
+        return fail(L3_EINVAL, "l3_feat_alloc: need 1 <= n <= 2^31 - 1 rows and 1 <= D <= 2^21 columns");
+    if (!device_ok(device)) return fail(L3_EHIP, no_gpu_message("l3_feat_alloc", device));
+    l3_feat* f = new l3_feat();
+    f->device = device, f->n = n, f->D = D;
+    f->x = f->bufs.alloc<float>((size_t)(n * D));
+    if (!f->x || hipStreamCreateWithFlags(&f->s, hipStreamNonBlocking) != hipSuccess) {
+        l3_feat_destroy(f);
+        return fail(L3_ENOMEM, "l3_feat_alloc: device allocation of " + std::to_string(n * D * 4) + " bytes failed");
+    }
+    if (hipMemsetAsync(f->x, 0, (size_t)(n * D) * sizeof(float), f->s) != hipSuccess || !finished(f)) {
+        l3_feat_destroy(f);
+        return fail(L3_EHIP, "l3_feat_alloc: zero fill on the device failed");
+    }
+    *out = f;
+    return L3_OK;
+}
+
 void l3_feat_destroy(l3_feat* f) {
     if (!f) return;
     (void)hipSetDevice(f->device);

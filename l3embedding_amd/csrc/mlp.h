@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 namespace l3 {
 
 constexpr int MLP_H1 = 512, MLP_H2 = 128;      // hidden widths of construct_mlp_model
@@ -50,6 +52,12 @@ void mlp_dense_bwd_x(const float* dy, const float* w, const float* h, float* dx,
 // probs / dz / ce / correct may each be null.  dz = d(sum of the rows' losses * gscale) / dz.
 void mlp_softmax_ce(const float* z, const int* labels, const int* idx, int rows, int C, float gscale, float* probs, float* dz,
                     float* ce, float* correct, hipStream_t s);
+
+// Per file i = rows [files[2i], files[2i + 1]) of probs (n, C), C <= 64: file_mean (n_files, C) = the float32 mean of its rows
+// (sum in row order, one division) and file_pred (n_files) its first maximum.  One wave per file; either output may be null.
+void mlp_file_mean(const float* probs, int C, const int64_t* files, int64_t n_files, float* file_mean, int* file_pred, hipStream_t s);
+// "" when the n_files host ranges are non-empty and inside [0, n), else what is wrong with them
+std::string mlp_file_ranges_error(const int64_t* files, int64_t n_files, int64_t n);
 
 // Weight gradient of up to three Dense layers in one launch: dW = X[idx]^T . dY (K = rows), db = column sums of dY.  With
 // adam != 0 the gradient never leaves registers: dW + l2x2 * W feeds the keras Adam update of adam_kernel (elementwise.hip), and

@@ -268,6 +268,55 @@ void mlp_softmax_ce(const float* z, const int* labels, const int* idx, int rows,
     mlp_softmax_ce_members(z, labels, idx, rows, C, gscale, probs, dz, ce, correct, MLP_ONE_MEMBER, MlpCeStride{}, s);
 }
 
+// ---- per-file mean of the rows' probabilities and its arg-max (classifier._file_predictions) ---------------------------------------
+// NumPy's probs[s:e].mean(axis=0).argmax() on float32 rows: one wave per file, lane c owns class c and adds its column in row order
+// (eight loads in flight, the additions in order), divides once by fl32(e - s), and the wave takes the first maximum.  A long file
+// stays on its one wave: the order of the sum is the contract.  Consecutive lanes read consecutive floats of a row.
+__global__ __launch_bounds__(256) void mlp_file_mean_kernel(const float* __restrict__ probs, int C, const int64_t* __restrict__ files,
+                                                            int64_t n_files, float* __restrict__ file_mean, int* __restrict__ file_pred) {
+    const int c = threadIdx.x & 63;
+    const int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (f >= n_files) return;          // the whole wave
+    const int64_t s = files[2 * f], F = files[2 * f + 1] - s;
+    const bool cv = c < C;
+    const float* p = probs + s * C + (cv ? c : 0);          // a lane without a class reads class 0's column and drops it
+    float sum = 0.f;
+    int64_t r = 0;
+    for (; r + 8 <= F; r += 8) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = p[(r + j) * C];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sum = __fadd_rn(sum, v[j]);
+    }
+    for (; r < F; ++r) sum = __fadd_rn(sum, p[r * C]);
+    const float mean = __fdiv_rn(sum, (float)F);
+    if (file_mean && cv) file_mean[f * C + c] = mean;
+    float bv = cv ? mean : -INFINITY;
+    int bi = c;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off);
+        if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
+    }
+    if (file_pred && c == 0) file_pred[f] = bi;
+}
+void mlp_file_mean(const float* probs, int C, const int64_t* files, int64_t n_files, float* file_mean, int* file_pred, hipStream_t s) {
+    hipLaunchKernelGGL(mlp_file_mean_kernel, dim3((unsigned)((n_files + 3) / 4)), dim3(256), 0, s, probs, C, files, n_files, file_mean,
+                       file_pred);
+}
+std::string mlp_file_ranges_error(const int64_t* files, int64_t n_files, int64_t n) {
+    if (n_files < 1 || n_files > INT32_MAX) return "need 1 <= n_files <= 2^31 - 1";
+    for (int64_t i = 0; i < n_files; ++i) {
+        const int64_t s = files[2 * i], e = files[2 * i + 1];
+        if (s < 0 || e <= s || e > n)
+            return "file " + std::to_string(i) + " = [" + std::to_string(s) + ", " + std::to_string(e) + ") is empty or outside [0, " +
+                   std::to_string(n) + ")";
+    }
+    return std::string();
+}
+
 // ---- weight gradient + L2 + Adam ------------------------------------------------------------------------------------------------
 // Layer l's waves: ceil(K/32) * ceil(N/32) weight tiles, then ceil(N/64) bias tiles.  Weight tile (kt, nt): the sum runs over the
 // batch, lane (r, h) holding A = X[idx[b0 + 4h + j]][kt*32 + r] and B = dY[b0 + 4h + j][nt*32 + r].  Bias tile: lane n sums its
@@ -471,9 +520,9 @@ void forward(l3_mlp_group* g, const MlpMembers& mem, const float* x, const int* 
 
 // Rows [0, n) of x (on the device, labels y or none) through the members `mem`, `block` rows per forward.  sums (may be null):
 // 2 doubles per member of the group, the sums of ce and of correct in row order.  probs_host (may be null): member i's (n, C)
-// probabilities go to probs_host + i * probs_stride.
+// probabilities go to probs_host + i * probs_stride -- host memory, or with probs_kind = hipMemcpyDeviceToDevice a device buffer.
 int evaluate(l3_mlp_group* g, const char* fn, const MlpMembers& mem, const float* x, const int* y, int64_t n, int64_t block,
-             double* sums, float* probs_host, int64_t probs_stride) {
+             double* sums, float* probs_host, int64_t probs_stride, hipMemcpyKind probs_kind = hipMemcpyDeviceToHost) {
     std::vector<float> ce(sums ? block : 0), cor(sums ? block : 0);
     const MlpCeStride stride{(int64_t)g->rows * g->C, (int64_t)g->rows * g->C, 0, g->rows};
     for (int k = 0; sums && k < mem.n; ++k) sums[2 * mlp_member(mem, k)] = sums[2 * mlp_member(mem, k) + 1] = 0.0;
@@ -490,7 +539,7 @@ int evaluate(l3_mlp_group* g, const char* fn, const MlpMembers& mem, const float
                                         g->s) != hipSuccess))
                 return fail(L3_EHIP, std::string(fn) + ": HIP error during evaluation");
             if (probs_host && hipMemcpyAsync(probs_host + i * probs_stride + r0 * g->C, g->dz + (int64_t)i * g->rows * g->C,
-                                             (size_t)rows * g->C * sizeof(float), hipMemcpyDeviceToHost, g->s) != hipSuccess)
+                                             (size_t)rows * g->C * sizeof(float), probs_kind, g->s) != hipSuccess)
                 return fail(L3_EHIP, std::string(fn) + ": HIP error during evaluation");
             if (hipStreamSynchronize(g->s) != hipSuccess) return fail(L3_EHIP, std::string(fn) + ": HIP error during evaluation");
             for (int r = 0; sums && r < rows; ++r) sums[2 * i] += ce[r], sums[2 * i + 1] += cor[r];
@@ -728,15 +777,17 @@ int group_epoch(l3_mlp_group* m, const char* fn, const int32_t* perm, const floa
 
 // softmax probabilities of n rows through every member, member i's (n, C) at probs_out + i * n * C.  The rows are host rows X,
 // staged block by block, or device rows xd; either way in blocks of xin_rows, so that every forward launch has the same shape
-// (and split-K order) whichever way the rows come.
-int group_predict(l3_mlp_group* m, const char* fn, const float* X, const float* xd, int64_t n, float* probs_out) {
+// (and split-K order) whichever way the rows come.  probs_kind: where probs_out is (evaluate).
+int group_predict(l3_mlp_group* m, const char* fn, const float* X, const float* xd, int64_t n, float* probs_out,
+                  hipMemcpyKind probs_kind = hipMemcpyDeviceToHost) {
     (void)hipSetDevice(m->device);
     const MlpMembers mem = all_members(m);
     for (int64_t r0 = 0; r0 < n; r0 += m->xin_rows) {
         const int64_t rows = std::min(m->xin_rows, n - r0);
         if (X && hipMemcpyAsync(m->xin, X + r0 * m->D, rows * m->D * sizeof(float), hipMemcpyHostToDevice, m->s) != hipSuccess)
             return fail(L3_EHIP, std::string(fn) + ": copy to the device failed");
-        const int rc = evaluate(m, fn, mem, X ? m->xin : xd + r0 * m->D, nullptr, rows, rows, nullptr, probs_out + r0 * m->C, n * m->C);
+        const int rc = evaluate(m, fn, mem, X ? m->xin : xd + r0 * m->D, nullptr, rows, rows, nullptr, probs_out + r0 * m->C, n * m->C,
+                                probs_kind);
         if (rc != L3_OK) return rc;
     }
     return L3_OK;
@@ -904,6 +955,35 @@ int l3_mlp_predict(l3_mlp* m, const float* X, int64_t n, float* probs_out) {
 
 int l3_mlp_predict_dev(l3_mlp* m, const l3_feat* x, int64_t lo, int64_t hi, float* probs_out) {
     return group_predict_dev(m ? m->g : nullptr, "l3_mlp_predict_dev", x, lo, hi, probs_out);
+}
+
+int l3_mlp_predict_files_dev(l3_mlp* m, const l3_feat* x, const int64_t* file_idxs, int64_t n_files, float* file_mean,
+                             int32_t* file_pred) {
+    const std::string name("l3_mlp_predict_files_dev");
+    if (!m || !x || !file_idxs) return fail(L3_EINVAL, name + ": NULL argument");
+    l3_mlp_group* g = m->g;
+    if (x->device != g->device || x->D != g->D)
+        return fail(L3_EINVAL, name + ": the feature matrix is on another device or not " + std::to_string(g->D) + " columns wide");
+    const std::string bad = mlp_file_ranges_error(file_idxs, n_files, x->n);
+    if (!bad.empty()) return fail(L3_EINVAL, name + ": " + bad);
+    (void)hipSetDevice(g->device);
+    const int C = g->C;
+    float* probs = g->bufs.alloc<float>((size_t)(x->n * C));
+    int64_t* files = g->bufs.put(file_idxs, (size_t)(2 * n_files), g->s);
+    float* mean = g->bufs.alloc<float>((size_t)(n_files * C));
+    int* pred = g->bufs.alloc<int>((size_t)n_files);
+    int rc = probs && files && mean && pred ? L3_OK : fail(L3_ENOMEM, name + ": device allocation failed");
+    if (rc == L3_OK) rc = group_predict(g, "l3_mlp_predict_files_dev", nullptr, x->x, x->n, probs, hipMemcpyDeviceToDevice);
+    if (rc == L3_OK) {
+        mlp_file_mean(probs, C, files, n_files, mean, pred, g->s);
+        if ((file_mean && hipMemcpyAsync(file_mean, mean, (size_t)(n_files * C) * sizeof(float), hipMemcpyDeviceToHost, g->s) != hipSuccess) ||
+            (file_pred && hipMemcpyAsync(file_pred, pred, (size_t)n_files * sizeof(int), hipMemcpyDeviceToHost, g->s) != hipSuccess))
+            rc = fail(L3_EHIP, name + ": copy from the device failed");
+    }
+    // also after a failure: the stream has let go of the host table and of the buffers
+    if ((hipStreamSynchronize(g->s) != hipSuccess || hipGetLastError() != hipSuccess) && rc == L3_OK) rc = fail(L3_EHIP, name + ": HIP error");
+    g->bufs.release(probs), g->bufs.release(files), g->bufs.release(mean), g->bufs.release(pred);
+    return rc;
 }
 
 int l3_mlp_get_weights(l3_mlp* m, float* dst, int64_t n) { return copy_weights(m ? m->g : nullptr, "l3_mlp_get_weights", 0, dst, n, true); }

@@ -887,6 +887,33 @@ extern "C" int l3_op_mlp_softmax_ce(int device, const float* z, const int32_t* l
     return sc.status();
 }
 
+extern "C" int l3_op_file_mean(int device, const float* probs, int64_t n, int C, const int64_t* file_idxs, int64_t n_files,
+                               float* file_mean, int32_t* file_pred) {
+    if (!probs || !file_idxs || n < 1 || C < 1 || C > MLP_MAX_CLASSES) {
+        set_op_error("l3_op_file_mean: NULL pointer, n < 1 or a class count outside [1, 64]");
+        return L3_EINVAL;
+    }
+    const std::string bad = mlp_file_ranges_error(file_idxs, n_files, n);
+    if (!bad.empty()) {
+        set_op_error("l3_op_file_mean: " + bad);
+        return L3_EINVAL;
+    }
+    if (!device_ok(device)) {
+        set_op_error(no_gpu_message("l3_op_file_mean", device));
+        return L3_EHIP;
+    }
+    Scope sc(device);
+    const float* dp = sc.put(probs, (size_t)(n * C));
+    const int64_t* df = sc.put(file_idxs, (size_t)(2 * n_files));
+    float* dm = sc.alloc<float>((size_t)(n_files * C));
+    int* dq = sc.alloc<int>((size_t)n_files);
+    if (!sc.ok) return L3_ENOMEM;
+    mlp_file_mean(dp, C, df, n_files, dm, dq, sc.s);
+    if (file_mean) sc.get(file_mean, dm, (size_t)(n_files * C));
+    if (file_pred) sc.get(file_pred, dq, (size_t)n_files);
+    return sc.status();
+}
+
 extern "C" int l3_op_adam(int device, float* p, const float* g, float* m, float* v, int64_t n, int64_t n_l2, float l2x2, float lr_t) {
     const int rc = mlp_op_check("l3_op_adam", device, p && g && m && v && n_l2 >= 0 && n_l2 <= n, 1, 1, 1, nullptr, n > 0 ? 1 : 0);
     if (rc != L3_OK || n <= 0) {

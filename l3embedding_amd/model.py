@@ -35,6 +35,9 @@ AUDIO_POOLING = {
     'cnn_L3_melspec2': {'original': (8, 8), 'short': (32, 24)},
 }
 VISION_POOLING = (7, 7)   # vision_model.py:212
+# (H, W, C) of the audio embedding layer's convolution output, which MaxPooling2D(pool, padding='same') pools: the 'short' pooling
+# is the pool over all of it
+AUDIO_EMBEDDING_MAP = {mt: pools['short'] + (512,) for mt, pools in AUDIO_POOLING.items()}
 
 
 class Input(object):
@@ -793,7 +796,7 @@ class EmbeddingModel(object):
     CLIP_CALL_FRAMES = 4096
     CLIP_CALL_SAMPLES = 1 << 26
 
-    def predict_clips(self, clips, hop_length, batch_size=32, rates=None):
+    def predict_clips(self, clips, hop_length, batch_size=32, rates=None, to_device=False):
         """get_l3_frames_uniform's framing + predict for many clips at once (data/usc/features.py:276-306): clips is a
         sequence of 1-D float32 arrays at 48 kHz, hop_length the hop in samples.  Returns one (n_i, D) array per clip, n_i
         from features.frame_table.  The engine is chosen as predict chooses it (the model's current one, else batch
@@ -805,7 +808,12 @@ class EmbeddingModel(object):
         rates: clip i's sample rate (whole Hz) when the clips are not all at 48 kHz.  Each clip is then resampled to 48 kHz on
         the device as load_audio resamples it (resampy 'kaiser_best', features.py:25-26; a clip at 48 kHz is taken as it is),
         and the 48 kHz lengths are framed and packed exactly as above: the result equals predict_clips on the clips resampled
-        by resample.resample.  A clip is uploaded at its own rate, once per call its frames reach."""
+        by resample.resample.  A clip is uploaded at its own rate, once per call its frames reach.
+
+        to_device: the rows stay on the engine's GPU.  Returns (usc.DeviceFeatures of all clips' rows in clip order, file_idxs),
+        file_idxs (n_clips, 2) the row range [s, e) of each clip: the same rows in the same order from the same calls, written by
+        the pooling kernel into the matrix (l3_embed_audio_frames_dev), the bits of the host form's np.concatenate.  The caller
+        owns the DeviceFeatures and closes it."""
         from .features import frame_table
         if self.embedding_type != 'audio':
             raise TypeError('predict_clips needs an audio embedding model')
@@ -825,6 +833,8 @@ class EmbeddingModel(object):
                                np.int64)
         table, counts = frame_table(lengths, hop_length)
         if not clips:
+            if to_device:
+                raise ValueError('no clips: a device matrix has at least one row')
             return []
         total = int(counts.sum())
         e = self.base._ensure_engine(self.base._engine.batch if self.base._engine is not None else max(1, min(batch_size, total)))
@@ -846,7 +856,13 @@ class EmbeddingModel(object):
         b = np.maximum(np.minimum(rows[:, 0] + 48000, rows[:, 2]), a)
         b = np.maximum.accumulate(b)
         D = int(e.lib.l3_embed_dim(e.h, 0, self.pool[0], self.pool[1]))
-        out = np.empty((len(rows), D), np.float32)
+        if to_device:
+            from . import usc
+            out = _lib.Features.alloc(len(rows), D, device=self.base.device)
+            where = lambda lo, hi: dict(dst=out, row0=lo)
+        else:
+            out = np.empty((len(rows), D), np.float32)
+            where = lambda lo, hi: dict(out=out[lo:hi])
         max_frames = max(B, self.CLIP_CALL_FRAMES // B * B)
         offs = ends - lengths
         r0, n = 0, len(rows)
@@ -863,12 +879,23 @@ class EmbeddingModel(object):
             t[:, 1] = a[r0:r1] - base
             t[:, 2] = np.maximum(np.minimum(rows[r0:r1, 0] + 48000, rows[r0:r1, 2]), a[r0:r1]) - base
             if rates is None:
-                e.embed_audio_frames(_clip_span(clips, offs, base, top), t, self.pool, out=out[r0:r1])
+                e.embed_audio_frames(_clip_span(clips, offs, base, top), t, self.pool, **where(r0, r1))
             else:
                 x, descs = _resample_rows(clips, rates, offs, lengths, base, top)
-                e.embed_audio_clips_resampled(x, descs, win, num_table, top - base, t, self.pool, out=out[r0:r1])
+                e.embed_audio_clips_resampled(x, descs, win, num_table, top - base, t, self.pool, **where(r0, r1))
             r0 = r1
+        if to_device:
+            if len(rows) != total:          # 'batch' scope: the pad rows of every clip's last engine batch go
+                out.gather(np.concatenate([np.arange(row0[i], row0[i] + counts[i]) for i in range(len(clips))]))
+            return usc.DeviceFeatures.from_handle(out), usc._row_ranges(counts)
         return [out[row0[i]:row0[i] + counts[i]] for i in range(len(clips))]
+
+    def embedding_dim(self):
+        """D of an audio embedding model from the model type and the pooling alone: no engine is made (l3_embed_dim's value)"""
+        if self.embedding_type != 'audio' or self.base.model_type not in AUDIO_EMBEDDING_MAP:
+            raise TypeError('embedding_dim needs an audio embedding model')
+        h, w, c = AUDIO_EMBEDDING_MAP[self.base.model_type]
+        return -(-h // self.pool[0]) * -(-w // self.pool[1]) * c
 
     @property
     def output_shape(self):
