@@ -329,6 +329,22 @@ int l3_embed_audio_clips_resampled(l3_engine *e, const float *native, int64_t n_
                                    int64_t n_clips, const double *half_window, int64_t n_window, int num_table,
                                    int64_t n_samples, const int64_t *table, int64_t n_frames, int pool_h, int pool_w,
                                    float *out);
+/* Vision embeddings from raw frames of any size -- read_video's resize (data/avc/sample.py:286-316), the 224 x 224 crop
+ * (:169-193) and 2 * img_as_float(u8) - 1 (train.py:186) on the device, then the path of l3_embed_vision.
+ * pixels: n_bytes of uint8, frames of H x W x 3 (HWC) back to back at any byte offsets.  table: n_frames rows of 7 int64
+ * {offset, H, W, Ho, Wo, y0, x0}: rows [y0, y0 + 224) x [x0, x0 + 224) of the frame at pixels[offset ..) resized from H x W to
+ * Ho x Wo become one input row; only that window is computed.  The sizes and the crop are the caller's rule:
+ * l3embedding_amd/features.py image_table.  The resize is bilinear with half-pixel centres, the tent widened by the scale when
+ * shrinking (PIL's and torch's antialiased bilinear), defined as an order of float64 operations (csrc/frames.hip, DESIGN.md
+ * section 8n; tests/image_ref.py is its NumPy form), rounded half up to uint8 and scaled as preprocess_video scales: with
+ * H == Ho and W == Wo the window is the source bytes.  The pixels and the table's device form (a descriptor per frame, one tap
+ * table per distinct axis) go to the device once, in buffers the engine keeps and grows; per engine batch the frame kernel fills
+ * the real rows of the video batch and zeroes the rest.  out (n_frames, D); n_frames == 0 is L3_OK.
+ * L3_EINVAL (message in l3_last_error, naming the frame) for a NULL pointer, H or W outside [1, 8192], Ho or Wo outside
+ * [224, 8192], a crop outside Ho x Wo, offset < 0 or offset + 3 * H * W > n_bytes, a bad pooling size, or a model without a
+ * vision embedding layer; nothing is uploaded then. */
+int l3_embed_vision_frames(l3_engine *e, const uint8_t *pixels, int64_t n_bytes, const int64_t *table, int64_t n_frames,
+                           int pool_h, int pool_w, float *out);
 
 /* Diagnostics / parity taps. */
 int l3_get_activation(l3_engine *e, const char *name, float *dst, int64_t numel); /* e.g. "audio_model/frontend", "vision_model/conv2d_1" */
@@ -408,6 +424,10 @@ int l3_op_frontend(int device, int model_type, const float *audio, int n, int db
 /* The frame gather of l3_embed_audio_frames on its own: frames (n_frames, 48000) from samples + table as above (parity tests). */
 int l3_op_gather_frames(int device, const float *samples, int64_t n_samples, const int64_t *table,
                         int64_t n_frames, float *frames);
+/* The frame kernel of l3_embed_vision_frames on its own: from pixels + table as there, out_u8 (n_frames, 224, 224, 3) the resized
+ * and cropped uint8 frames and out_f32 the same scaled to [-1, 1], the network's input rows.  Either output may be NULL. */
+int l3_op_image_frames(int device, const uint8_t *pixels, int64_t n_bytes, const int64_t *table, int64_t n_frames,
+                       uint8_t *out_u8, float *out_f32);
 /* resampy.resample(x, sr_orig, sr_new, filter=...)[t0 : t0 + n_out] -- data/usc/features.py:25-26 -- for one clip of n_in
  * samples, on the device (csrc/resample.hip, exact output times as above).  Always filters, equal rates included, as resampy
  * does.  L3_EINVAL for rates <= 0, int(n_in * sr_new / sr_orig) < 1, or a range past that length. */
@@ -819,6 +839,9 @@ int l3_embed_audio_frames_dev(l3_engine *e, const float *samples, int64_t n_samp
 int l3_embed_audio_clips_resampled_dev(l3_engine *e, const float *native, int64_t n_native, const int64_t *clips, int64_t n_clips,
                                        const double *half_window, int64_t n_window, int num_table, int64_t n_samples,
                                        const int64_t *table, int64_t n_frames, int pool_h, int pool_w, l3_feat *dst, int64_t row0);
+/* l3_embed_vision_frames likewise: rows [row0, row0 + n_frames) of dst, the bits `out` receives; dst is checked before the table */
+int l3_embed_vision_frames_dev(l3_engine *e, const uint8_t *pixels, int64_t n_bytes, const int64_t *table, int64_t n_frames,
+                               int pool_h, int pool_w, l3_feat *dst, int64_t row0);
 
 /* ---- A group of MLP classifiers (the learning_rate x weight_decay search of classifier/train.py:638-651) ---------------------------
  * n_members models of one shape (D, C, batch) trained on ONE resident data set in the same launches: an epoch's step is seven

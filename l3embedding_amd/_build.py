@@ -14,11 +14,11 @@ LIBPATH = os.path.join(LIBDIR, 'libl3hip.so')
 # The product library.  One file per kernel family of DESIGN.md section 4: fp32 convolutions (F(4x4,3x3) forward / data gradient,
 # F(2x2,3x3) = l3_config.fp32_conv F2X2 + the dispatch, F(3x3,2x2) weight gradient, direct implicit GEMM for the DFT and every
 # geometry Winograd does not take), mixed precision (halo forward / data gradient, transpose-read weight gradient, the dispatch +
-# fp32-tensor entry points), first layers, BatchNorm / pool, head / loss / Adam, front-end, clip framing, resampling, the training-batch feed, engine, operator
+# fp32-tensor entry points), first layers, BatchNorm / pool, head / loss / Adam, front-end, clip framing, image frames, resampling, the training-batch feed, engine, operator
 # entry points, RCCL, the downstream MLP and SVM classifiers, the VGGish baseline features, training-set augmentation, the
 # classifier's fold preprocessing, the SVM's scoring and sigmoid fits, the downstream random forest.
 SOURCES = ['conv.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_bf16.hip', 'conv_bf16_halo.hip', 'conv_wgrad_bf16.hip', 'conv_wgrad_wino.hip',
-           'conv_first.hip', 'conv_path.hip', 'elementwise.hip', 'bn_fused.hip', 'frontend.hip', 'clips.hip', 'resample.hip', 'batch_feed.hip', 'engine.hip', 'ops.hip',
+           'conv_first.hip', 'conv_path.hip', 'elementwise.hip', 'bn_fused.hip', 'frontend.hip', 'clips.hip', 'frames.hip', 'resample.hip', 'batch_feed.hip', 'engine.hip', 'ops.hip',
            'comm.hip', 'mlp.hip', 'svm.hip', 'vggish.hip', 'augment.hip', 'featprep.hip', 'svm_eval.hip', 'forest.hip']
 # Measured-and-rejected kernel variants (split-bf16 fp32 convolutions, flat-tile MODE 5, tap-split bf16 weight gradient; round 6: the
 # filter-in-registers 64-channel halo kernel, the split-bf16 first convolution): records of negative results (profiles/r05_bx6_ablations.txt,
@@ -35,12 +35,14 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC'] + (['-DL3_EXPERI
 # instructions per 4-pixel unit, round 6)
 # featprep.hip: its contract counts float32 / float64 roundings (NumPy's in-place scaler arithmetic), so no multiply and add may
 # be contracted into a fused multiply-add
+# frames.hip: likewise, the resize is an order of float64 multiplications and additions (tests/image_ref.py), on the device and in
+# the host code that works out the tap weights
 # svm_eval.hip: likewise, its contract counts float64 roundings (NumPy's and libsvm's scalar arithmetic)
 # forest.hip: likewise, a split's worth is two float64 divisions and one addition, equal to the NumPy oracle's bit for bit, and the
 # scoring at nested forest sizes (l3_forest_score) is pinned to forest_predict_kernel's divisions and additions
 FILE_FLAGS = {'conv_wino4.hip': ['-fno-slp-vectorize'], 'conv_wino_bx6.hip': ['-fno-slp-vectorize'], 'conv_wgrad_bx6.hip': ['-fno-slp-vectorize'],
               'conv_first.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'featprep.hip': ['-ffp-contract=off'], 'svm_eval.hip': ['-ffp-contract=off'],
-              'forest.hip': ['-ffp-contract=off']}
+              'forest.hip': ['-ffp-contract=off'], 'frames.hip': ['-ffp-contract=off']}
 
 
 def _headers():

@@ -123,6 +123,11 @@ SIGNATURES = {
     'l3_embed_audio_clips_resampled_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                      C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                                      C.c_void_p, C.c_int64]),
+    # vision embeddings from raw uint8 frames of any size, resized and cropped on the device (csrc/frames.hip)
+    'l3_embed_vision_frames': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                         C.c_void_p]),
+    'l3_embed_vision_frames_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_int64]),
     'l3_get_activation': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     'l3_activation_numel': (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
     'l3_sync': (C.c_int, [C.c_void_p]),
@@ -144,6 +149,7 @@ SIGNATURES = {
     'l3_op_maxpool_bwd': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9),
     'l3_op_frontend': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'l3_op_gather_frames': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_op_image_frames': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'l3_op_resample': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
                                  C.c_int64, C.c_int64, C.c_void_p]),
     'l3_op_resample_clips': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
@@ -728,6 +734,29 @@ class Engine(object):
         check(self.lib.l3_embed_vision(self.h, _ptr(v), v.shape[0], pool[0], pool[1], _ptr(out)), self.h)
         return out
 
+    def embed_vision_frames(self, pixels, table, pool=(7, 7), out=None, dst=None, row0=0):
+        """l3_embed_vision_frames: pixels (n_bytes,) uint8 (HWC frames back to back), table (n_frames, 7) int64
+        {offset, H, W, Ho, Wo, y0, x0} (features.image_table) -> (n_frames, D) embeddings, written into `out` when given
+        (C-contiguous float32).  dst, row0: as embed_audio_frames' (l3_embed_vision_frames_dev)."""
+        p = np.ascontiguousarray(pixels, dtype=np.uint8).reshape(-1)
+        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 7)
+        if p.size == 0:
+            p = np.zeros(1, np.uint8)[:0]
+        if dst is not None:
+            if out is not None:
+                raise ValueError('give out or dst, not both')
+            check(self.lib.l3_embed_vision_frames_dev(self.h, _ptr(p), p.size, _ptr(t), t.shape[0], pool[0], pool[1], dst.h,
+                                                      int(row0)), self.h)
+            return dst
+        d = self.lib.l3_embed_dim(self.h, 1, pool[0], pool[1])
+        if out is None:
+            out = np.empty((t.shape[0], max(d, 0)), np.float32)
+        elif out.dtype != np.float32 or not out.flags['C_CONTIGUOUS'] or out.shape != (t.shape[0], d):
+            raise ValueError('out must be a C-contiguous float32 array of shape %s' % ((t.shape[0], d),))
+        check(self.lib.l3_embed_vision_frames(self.h, _ptr(p), p.size, _ptr(t), t.shape[0], pool[0], pool[1], _ptr(out)),
+              self.h)
+        return out
+
     def activation(self, name):
         n = C.c_int64()
         check(self.lib.l3_activation_numel(self.h, name.encode(), C.byref(n)), self.h)
@@ -943,6 +972,20 @@ def op_gather_frames(samples, table, device=0):
     out = np.empty((t.shape[0], 48000), np.float32)
     check(lib.l3_op_gather_frames(device, _ptr(s), s.size, _ptr(t), t.shape[0], _ptr(out)))
     return out
+
+
+def op_image_frames(pixels, table, device=0, want_u8=True, want_f32=True):
+    """l3_op_image_frames: (u8, f32), each (n_frames, 224, 224, 3) -- the resized and cropped uint8 frames and the input rows
+    l3_embed_vision_frames feeds the vision tower (None for an output not asked for)."""
+    lib = load()
+    p = np.ascontiguousarray(pixels, dtype=np.uint8).reshape(-1)
+    t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 7)
+    if p.size == 0:
+        p = np.zeros(1, np.uint8)[:0]
+    u8 = np.empty((t.shape[0], 224, 224, 3), np.uint8) if want_u8 else None
+    f32 = np.empty((t.shape[0], 224, 224, 3), np.float32) if want_f32 else None
+    check(lib.l3_op_image_frames(device, _ptr(p), p.size, _ptr(t), t.shape[0], _ptr(u8), _ptr(f32)))
+    return u8, f32
 
 
 def op_resample(x, sr_orig, sr_new, half_window, num_table, t0=0, n_out=None, device=0):

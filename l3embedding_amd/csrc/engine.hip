@@ -238,6 +238,11 @@ struct l3_engine {
     int64_t* clip_table = nullptr;
     size_t clip_samples_cap = 0, clip_table_cap = 0;
     l3::ResampleStage resample;         // l3_embed_audio_clips_resampled: native-rate clips -> clip_samples
+    // l3_embed_vision_frames: the call's pixels, frame descriptors and tap tables (grown on demand), and their host form
+    uint8_t* image_pixels = nullptr;
+    int64_t *image_descs = nullptr, *image_taps = nullptr;
+    size_t image_pixels_cap = 0, image_descs_cap = 0, image_taps_cap = 0;
+    l3::ImagePlan image_plan;
     bool last_training = false;
     bool fwd_done = false;
 
@@ -2747,12 +2752,16 @@ int64_t l3_embed_dim(const l3_engine* e, int vision, int pool_h, int pool_w) {
     return (int64_t)ho * wo * t.C;
 }
 
-// Where the input rows of one engine batch come from: the caller's host rows (l3_embed_audio / l3_embed_vision) or the clip
-// frames gathered on the device from the samples and frame table l3_embed_audio_frames uploaded.
+// Where the input rows of one engine batch come from: the caller's host rows (l3_embed_audio / l3_embed_vision), the clip
+// frames gathered on the device from the samples and frame table l3_embed_audio_frames uploaded, or the windows of raw frames
+// resized on the device from the pixels and plan l3_embed_vision_frames uploaded.
 struct EmbedSource {
     const float* host = nullptr;          // n rows, host memory
     const float* samples = nullptr;       // device (audio only)
     const int64_t* table = nullptr;       // device, n x {start, lo, hi}
+    const uint8_t* pixels = nullptr;      // device (vision only)
+    const int64_t* descs = nullptr;       // device, n x IMAGE_DESC
+    const int64_t* taps = nullptr;        // device
 };
 
 // Pooled rows stay on the device between two copies to the host; one copy (and one host wait) per call up to this many bytes.
@@ -2811,6 +2820,9 @@ static int embed_rows(l3_engine* e, bool vision, const EmbedSource& src, int64_t
         if (src.host) {
             HIPCHK(e, hipMemcpyAsync(dst_in, src.host + (size_t)s0 * per, (size_t)cnt * per * 4, hipMemcpyHostToDevice, e->stream));
             if (cnt < B) HIPCHK(e, hipMemsetAsync(dst_in + (size_t)cnt * per, 0, (size_t)(B - cnt) * per * 4, e->stream));
+        } else if (src.pixels) {
+            ProfScope ps(e, F_FRONTEND, 0.0);          // profiled with the input-side kernels: the vision tower has no other
+            image_frames(src.pixels, src.descs + IMAGE_DESC * s0, src.taps, nullptr, dst_in, B, (int)cnt, e->stream);
         } else {
             gather_frames(src.samples, src.table + 3 * s0, dst_in, B, (int)cnt, AUDIO_T, e->stream);
         }
@@ -2922,6 +2934,59 @@ int l3_embed_audio_frames_dev(l3_engine* e, const float* samples, int64_t n_samp
     EmbedDest dst;
     dst.dev = true, dst.feat = dst_feat, dst.row0 = row0;
     return embed_frames_to(e, "l3_embed_audio_frames_dev", samples, n_samples, table, n_frames, pool_h, pool_w, dst);
+}
+
+static int embed_vision_frames_to(l3_engine* e, const char* fn, const uint8_t* pixels, int64_t n_bytes, const int64_t* table,
+                                  int64_t n_frames, int pool_h, int pool_w, const EmbedDest& dst) {
+    const std::string name(fn);
+    if (!pixels || !table || !(dst.host || dst.feat)) {
+        e->err = name + ": pixels, table and " + (dst.dev ? "dst" : "out") + " must not be NULL";
+        return L3_EINVAL;
+    }
+    if (n_bytes < 0 || n_frames < 0) {
+        e->err = name + ": n_bytes and n_frames must be >= 0";
+        return L3_EINVAL;
+    }
+    int64_t D = 0;
+    int rc = embed_check(e, true, pool_h, pool_w, &D);
+    if (rc) return rc;
+    if ((rc = embed_dest_check(e, fn, dst, n_frames, D))) return rc;
+    int64_t bad = 0;
+    if (const char* why = image_table_error(table, n_frames, n_bytes, &bad)) {
+        e->err = name + ": frame " + std::to_string(bad) + ": " + why;
+        return L3_EINVAL;
+    }
+    if (n_frames == 0) return L3_OK;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    image_plan(table, n_frames, &e->image_plan);          // the engine's: the copies below read it until the stream has run
+    const ImagePlan& plan = e->image_plan;
+    if ((rc = dev_grow_t(e, &e->image_pixels, &e->image_pixels_cap, (size_t)n_bytes))) return rc;
+    if ((rc = dev_grow_t(e, &e->image_descs, &e->image_descs_cap, plan.frames.size()))) return rc;
+    if ((rc = dev_grow_t(e, &e->image_taps, &e->image_taps_cap, plan.taps.size()))) return rc;
+    HIPCHK(e, hipMemcpyAsync(e->image_pixels, pixels, (size_t)n_bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->image_descs, plan.frames.data(), plan.frames.size() * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->image_taps, plan.taps.data(), plan.taps.size() * 8, hipMemcpyHostToDevice, e->stream));
+    EmbedSource src;
+    src.pixels = e->image_pixels;
+    src.descs = e->image_descs;
+    src.taps = e->image_taps;
+    return embed_rows(e, true, src, n_frames, pool_h, pool_w, D, dst);
+}
+
+int l3_embed_vision_frames(l3_engine* e, const uint8_t* pixels, int64_t n_bytes, const int64_t* table, int64_t n_frames,
+                           int pool_h, int pool_w, float* out) {
+    if (!e) return L3_EINVAL;
+    EmbedDest dst;
+    dst.host = out;
+    return embed_vision_frames_to(e, "l3_embed_vision_frames", pixels, n_bytes, table, n_frames, pool_h, pool_w, dst);
+}
+
+int l3_embed_vision_frames_dev(l3_engine* e, const uint8_t* pixels, int64_t n_bytes, const int64_t* table, int64_t n_frames,
+                               int pool_h, int pool_w, l3_feat* dst_feat, int64_t row0) {
+    if (!e) return L3_EINVAL;
+    EmbedDest dst;
+    dst.dev = true, dst.feat = dst_feat, dst.row0 = row0;
+    return embed_vision_frames_to(e, "l3_embed_vision_frames_dev", pixels, n_bytes, table, n_frames, pool_h, pool_w, dst);
 }
 
 static int embed_clips_resampled_to(l3_engine* e, const char* fn, const float* native, int64_t n_native, const int64_t* clips,

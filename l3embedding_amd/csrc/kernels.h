@@ -310,6 +310,24 @@ inline const char* frame_table_error(const int64_t* table, int64_t n_frames, int
     return nullptr;
 }
 
+// network inputs from raw uint8 frames of any size (frames.hip; data/avc/sample.py:286-316, :169-193, train.py:186).  A caller's
+// row is IMAGE_ROW int64 {offset, H, W, Ho, Wo, y0, x0}: the 224 x 224 window at (y0, x0) of the H x W x 3 frame at
+// pixels[offset ..) resized to Ho x Wo (antialiased bilinear, an order of float64 operations), rounded to uint8, scaled to [-1, 1].
+constexpr int IMG = 224;
+constexpr int IMAGE_ROW = 7;
+constexpr int IMAGE_DESC = 4;          // the device's row: {offset, W, first word of the x taps, of the y taps}
+constexpr int64_t IMAGE_MAX_SIDE = 8192;
+// host-side check of such a table against n_bytes of pixels: nullptr if every row is valid, else what is wrong
+const char* image_table_error(const int64_t* table, int64_t n_frames, int64_t n_bytes, int64_t* bad_row);
+// what the kernel reads beside the pixels: a descriptor per frame and the tap tables of every distinct (n_in, n_out, first output)
+struct ImagePlan {
+    std::vector<int64_t> frames, taps;
+};
+void image_plan(const int64_t* table, int64_t n_frames, ImagePlan* plan);          // the table has passed image_table_error
+// out_u8 and / or out_f32 (rows, 224, 224, 3) from the device copies of the pixels and the plan; rows >= n_real are zeroed
+void image_frames(const uint8_t* pixels, const int64_t* frames, const int64_t* taps, uint8_t* out_u8, float* out_f32, int rows,
+                  int n_real, hipStream_t s);
+
 // resampling of whole clips (resample.hip; resampy.resample, data/usc/features.py:25-26).  A caller's clip row is RESAMPLE_ROW int64
 // {x_off, L, sr_orig, t0, n_out, y_off}: outputs [t0, t0 + n_out) of the L native samples at x[x_off ..) go to y[y_off ..).
 constexpr int RESAMPLE_ROW = 6;

@@ -679,6 +679,42 @@ int l3_op_gather_frames(int device, const float* samples, int64_t n_samples, con
     return sc.status();
 }
 
+int l3_op_image_frames(int device, const uint8_t* pixels, int64_t n_bytes, const int64_t* table, int64_t n_frames, uint8_t* out_u8,
+                       float* out_f32) {
+    if (!pixels || !table || n_bytes < 0 || n_frames < 0) {
+        set_op_error("l3_op_image_frames: NULL pointer or negative count");
+        return L3_EINVAL;
+    }
+    int64_t bad = 0;
+    if (const char* why = image_table_error(table, n_frames, n_bytes, &bad)) {
+        set_op_error(std::string("l3_op_image_frames: frame ") + std::to_string(bad) + ": " + why);
+        return L3_EINVAL;
+    }
+    if (n_frames == 0) return L3_OK;
+    Scope sc(device);
+    if (!sc.ok) {
+        set_op_error(no_gpu_message("l3_op_image_frames", device));
+        return L3_EHIP;
+    }
+    ImagePlan plan;
+    image_plan(table, n_frames, &plan);
+    const size_t n_out = (size_t)n_frames * IMG * IMG * 3;
+    const uint8_t* d_p = sc.put(pixels, (size_t)n_bytes);
+    const int64_t* d_d = sc.put(plan.frames.data(), plan.frames.size());
+    const int64_t* d_t = sc.put(plan.taps.data(), plan.taps.size());
+    uint8_t* d_u8 = out_u8 ? sc.alloc<uint8_t>(n_out) : nullptr;
+    float* d_f32 = out_f32 ? sc.alloc<float>(n_out) : nullptr;
+    if (!sc.ok) return L3_ENOMEM;
+    for (int64_t r0 = 0; r0 < n_frames; r0 += 65535) {
+        const int rows = (int)(n_frames - r0 < 65535 ? n_frames - r0 : 65535);
+        const size_t o = (size_t)r0 * IMG * IMG * 3;
+        image_frames(d_p, d_d + IMAGE_DESC * r0, d_t, d_u8 ? d_u8 + o : nullptr, d_f32 ? d_f32 + o : nullptr, rows, rows, sc.s);
+    }
+    if (out_u8) sc.get(out_u8, d_u8, n_out);
+    if (out_f32) sc.get(out_f32, d_f32, n_out);
+    return sc.status();
+}
+
 static int op_resample(const char* name, int device, const float* x, int64_t n_in, const int64_t* clips, int64_t n_clips,
                        int64_t sr_new, const double* half_window, int64_t n_window, int num_table, int64_t n_samples, bool copy_equal,
                        float* y) {

@@ -51,6 +51,58 @@ def frame_table(lengths, hop_length):
     return table, counts
 
 
+IMAGE_SIDE = 224            # the vision tower's input (data/avc/sample.py:182-183)
+
+
+def image_table(shapes, resize=256, crop='center'):
+    """Where raw frames stored back to back are resized to and cropped: one row {offset, H, W, Ho, Wo, y0, x0} per frame for
+    l3_embed_vision_frames (csrc/frames.hip), which only follows the table on the GPU.
+
+    shapes: (n, 2) frame sizes (H, W); frame i holds 3 * H * W bytes (HWC uint8) at the returned offset.
+    resize: the shorter side after the resize, read_video's rule (data/avc/sample.py:303-305): scaling = resize / min(W, H),
+    Wo = ceil(scaling * W), Ho = ceil(scaling * H).  None takes every frame as it is (Ho = H, Wo = W, the source bytes), and each
+    side must then be at least 224.
+    crop: 'center' (y0 = (Ho - 224) // 2, x0 = (Wo - 224) // 2) or an (n, 2) array of (y0, x0) in the resized frame.
+
+    Returns (table, offsets): table (n, 7) int64 and offsets (n,) int64, the byte offset of each frame."""
+    import math
+    hw = np.asarray(shapes, dtype=np.int64).reshape(-1, 2)
+    if (hw < 1).any():
+        raise ValueError('frame sides must be >= 1')
+    if resize is not None and int(resize) < IMAGE_SIDE:
+        raise ValueError('resize must be >= %d or None (got %r)' % (IMAGE_SIDE, resize))
+    n = hw.shape[0]
+    table = np.empty((n, 7), np.int64)
+    sizes = 3 * hw[:, 0] * hw[:, 1]
+    table[:, 0] = np.cumsum(sizes) - sizes
+    table[:, 1:3] = hw
+    if resize is None:
+        if (hw < IMAGE_SIDE).any():
+            i = int(np.nonzero((hw < IMAGE_SIDE).any(axis=1))[0][0])
+            raise ValueError('frame %d is %d x %d: without a resize every side must be >= %d'
+                             % (i, hw[i, 0], hw[i, 1], IMAGE_SIDE))
+        table[:, 3:5] = hw
+    else:
+        for i, (h, w) in enumerate(hw.tolist()):
+            scaling = float(resize) / min(w, h)
+            table[i, 3] = math.ceil(scaling * h)
+            table[i, 4] = math.ceil(scaling * w)
+    if isinstance(crop, str):
+        if crop != 'center':
+            raise ValueError("crop must be 'center' or an (n, 2) array of (y0, x0) (got %r)" % (crop,))
+        table[:, 5:7] = (table[:, 3:5] - IMAGE_SIDE) // 2
+    else:
+        yx = np.asarray(crop, dtype=np.int64)
+        if yx.shape != (n, 2):
+            raise ValueError('crop must give one (y0, x0) per frame: shape %s, not %s' % ((n, 2), yx.shape))
+        if (yx < 0).any() or (yx > table[:, 3:5] - IMAGE_SIDE).any():
+            i = int(np.nonzero(((yx < 0) | (yx > table[:, 3:5] - IMAGE_SIDE)).any(axis=1))[0][0])
+            raise ValueError('frame %d: the crop at (%d, %d) is outside the %d x %d resized frame'
+                             % (i, yx[i, 0], yx[i, 1], table[i, 3], table[i, 4]))
+        table[:, 5:7] = yx
+    return table, table[:, 0].copy()
+
+
 def load_audio(path, sr):
     """features.py:18-28 for PCM16 WAV files: int16 / 32768 (soundfile's float32 read), then the float32 mean over the
     channels.  The reference resamples other rates with resampy and reads any format soundfile knows; neither is a

@@ -890,6 +890,76 @@ class EmbeddingModel(object):
             return usc.DeviceFeatures.from_handle(out), usc._row_ranges(counts)
         return [out[row0[i]:row0[i] + counts[i]] for i in range(len(clips))]
 
+    # Caps of one l3_embed_vision_frames call of predict_images (device memory held by a call: the pixels, the tables and the
+    # pooled rows): at most IMAGE_CALL_FRAMES frames and IMAGE_CALL_BYTES of pixels -- or one engine batch, whatever its size, if
+    # that is more.  Larger inputs are split into several calls at engine-batch boundaries.
+    IMAGE_CALL_FRAMES = 4096
+    IMAGE_CALL_BYTES = 1 << 28
+
+    def predict_images(self, images, batch_size=32, resize=256, crop='center', to_device=False):
+        """read_video's resize, the 224 x 224 crop, 2 * img_as_float(u8) - 1 and predict for raw frames of any sizes
+        (data/avc/sample.py:286-316, :169-193, train.py:186): images is a sequence of (H, W, 3) uint8 arrays or one
+        (T, H, W, 3) uint8 array.  resize, crop: features.image_table's (shorter side 256 and the centre crop by default;
+        resize=None takes frames as they are).  Each frame goes to the device once, as bytes, and is resized there
+        (csrc/frames.hip: antialiased bilinear).  The engine is chosen as predict chooses it.  Returns
+        (n, D) float32, or with to_device=True a usc.DeviceFeatures of the same rows, which the caller owns and closes."""
+        from .features import image_table
+        if self.embedding_type != 'vision':
+            raise TypeError('predict_images needs a vision embedding model')
+        whole = None          # a C-contiguous (T, H, W, 3) array is the packed buffer already
+        if isinstance(images, np.ndarray) and images.ndim == 4:
+            frames = [images[i] for i in range(images.shape[0])]
+            if images.dtype == np.uint8 and images.flags['C_CONTIGUOUS']:
+                whole = images.reshape(-1)
+        elif isinstance(images, np.ndarray):
+            raise ValueError('images must be a sequence of (H, W, 3) arrays or one (T, H, W, 3) array (got shape %s)' % (images.shape,))
+        else:
+            frames = [np.asarray(f) for f in images]
+        for f in frames:
+            if f.dtype != np.uint8:
+                raise ValueError('every image must be uint8 (got %s)' % (f.dtype,))
+            if f.ndim != 3 or f.shape[2] != 3 or f.shape[0] < 1 or f.shape[1] < 1:
+                raise ValueError('every image must have shape (H, W, 3) (got %s)' % (f.shape,))
+        table, offs = image_table([f.shape[:2] for f in frames], resize=resize, crop=crop)
+        n = len(frames)
+        if n == 0:
+            if to_device:
+                raise ValueError('no images: a device matrix has at least one row')
+        e = self.base._ensure_engine(self.base._engine.batch if self.base._engine is not None else max(1, min(batch_size, n)))
+        B = e.batch
+        D = int(e.lib.l3_embed_dim(e.h, 1, self.pool[0], self.pool[1]))
+        if to_device:
+            from . import usc
+            out = _lib.Features.alloc(n, D, device=self.base.device)
+            where = lambda lo, hi: dict(dst=out, row0=lo)
+        else:
+            out = np.empty((n, D), np.float32)
+            where = lambda lo, hi: dict(out=out[lo:hi])
+        max_frames = max(B, self.IMAGE_CALL_FRAMES // B * B)
+        ends = offs + 3 * table[:, 1] * table[:, 2]
+        r0 = 0
+        while r0 < n:
+            r1 = min(n, r0 + B)
+            while r1 < n:
+                r2 = min(n, r1 + B)
+                if r2 - r0 > max_frames or ends[r2 - 1] - offs[r0] > self.IMAGE_CALL_BYTES:
+                    break
+                r1 = r2
+            base = int(offs[r0])
+            if whole is not None:
+                pixels = whole[base:int(ends[r1 - 1])]
+            else:
+                pixels = np.empty(int(ends[r1 - 1]) - base, np.uint8)
+                for i in range(r0, r1):
+                    pixels[offs[i] - base:ends[i] - base] = frames[i].reshape(-1)
+            t = table[r0:r1].copy()
+            t[:, 0] -= base
+            e.embed_vision_frames(pixels, t, self.pool, **where(r0, r1))
+            r0 = r1
+        if to_device:
+            return usc.DeviceFeatures.from_handle(out)
+        return out
+
     def embedding_dim(self):
         """D of an audio embedding model from the model type and the pooling alone: no engine is made (l3_embed_dim's value)"""
         if self.embedding_type != 'audio' or self.base.model_type not in AUDIO_EMBEDDING_MAP:
