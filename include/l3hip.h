@@ -465,6 +465,28 @@ int l3_op_conv2d_dgrad_bn_bwd(int device, int dtype, const float *dy, const floa
                               const float *beta, const float *mean, const float *var, float *dx, float *part, int *nblk,
                               float *dgamma, float *dbeta, int n, int h, int wd, int cin, int cout, int kh, int kw, int same,
                               int relu, int64_t bn_rows);
+/* The backward of a tower's first block -- input BatchNorm (c = 1 or 3 channels) -> 3x3 'same' convolution to 64 filters ->
+ * BatchNorm(+ReLU) -- as an engine runs it: bn_stats and bn_xhat_ones (engine.hip:1363, :1371, tower_forward, OP_BN: `p.bwd ==
+ * BB_BY_FIRST_CONV`), bn_bwd_fast of the BatchNorm behind the convolution (engine.hip:1447-1453, tower_backward_block, OP_BN), then
+ * conv_wgrad over [x^, 1] and first_conv_grads (engine.hip:1459-1480, OP_CONV: `p.aug != FW_NONE`).  form 0: FW_AUG -- bn_bwd_fast writes dY
+ * (n, h, wd, 64) and dbias; form 1 / 2: FW_AUG_DEFERRED on fp32 / bfloat16-stored y and dA -- bn_bwd_fast(dx = NULL) leaves
+ * coeffs (3, 64) = cA, cB, cC (bn_bwd_fast_coeffs of the one scratch), the weight-gradient kernel forms dY = cA mask(dA) + cB y + cC
+ * itself (FirstWgFuse) and first_conv_grads writes dbias.  y (n, h, wd, 64), the convolution's stored output, is an input: the
+ * second BatchNorm's statistics are bn_stats_fast's over it.  Every stage's result comes back: mean_in, var_in (c); xaug
+ * (n, h, wd, c + 1); mean2 .. dbeta2 (64); coeffs or dY (the other may be NULL); gaug (9, c + 1, 64); dw (3, 3, c, 64); dbias (64);
+ * dgamma_in, dbeta_in (c).  Every output and scratch buffer is NaN before the launches; the weight-gradient partials have exactly
+ * conv_wgrad_scratch_floats floats and a guard behind them.  L3_EINVAL where conv_first_wgrad would not run (another shape,
+ * L3_FIRST_WGRAD=0) or the guard changed. */
+int l3_op_first_block_bwd(int device, int form, int relu, const float *x, const float *gamma_in, const float *beta_in, const float *w,
+                          const float *y, const float *gamma2, const float *beta2, const float *dA, float *mean_in, float *var_in,
+                          float *xaug, float *mean2, float *var2, float *scale2, float *shift2, float *dgamma2, float *dbeta2,
+                          float *coeffs, float *dY, float *gaug, float *dw, float *dbias, float *dgamma_in, float *dbeta_in, int n,
+                          int h, int wd, int c, int cout);
+/* first_conv_grads (engine.hip:1476-1479, the call behind conv_wgrad in tower_backward_block) alone: gaug (taps, c + 1, co), channel c
+ * the ones channel, and the filter w (taps, c, co) to dw = gamma G + beta S (taps, c, co), dgamma = sum W G, dbeta = sum W S (c)
+ * and, unless NULL, dbias (co) = the ones-channel row of tap taps / 2.  Any taps, c, co. */
+int l3_op_first_conv_grads(int device, const float *gaug, const float *w, const float *gamma, const float *beta, float *dw,
+                           float *dgamma, float *dbeta, float *dbias, int taps, int c, int co);
 /* l3_op_bn_relu_pool2_fwd as a TRAINING forward runs it: also xwin (n, ho, wo, c), the input element (relu_mode 2: the rectified
  * one) that won each window -- what the backward reduction above reads for a pooled BatchNorm.  Widened when x_bf16. */
 int l3_op_bn_relu_pool2_fwd_xwin(int device, const float *x, const float *gamma, const float *beta, float *p, float *mean,

@@ -160,6 +160,8 @@ SIGNATURES = {
                                [C.c_int] * 9),
     'l3_op_conv2d_dgrad_bn_bwd': (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(C.c_int), C.c_void_p, C.c_void_p] +
                                   [C.c_int] * 9 + [C.c_int64]),
+    'l3_op_first_block_bwd': (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 24 + [C.c_int] * 5),
+    'l3_op_first_conv_grads': (C.c_int, [C.c_int] + [C.c_void_p] * 8 + [C.c_int] * 3),
     'l3_op_bn_relu_pool2_fwd_xwin': (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 7),
     'l3_op_preprocess': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'l3_op_augment_video': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -861,6 +863,56 @@ def op_conv2d_dgrad_bn_bwd(dy, w, same, bn_x, gamma, beta, mean, var, relu, bn_r
     check(lib.l3_op_conv2d_dgrad_bn_bwd(device, OP_DTYPES[dtype], _ptr(dy), _ptr(w), _ptr(bn_x), *[_ptr(v) for v in vecs], _ptr(dx),
                                         _ptr(part), C.byref(nblk), _ptr(dg), _ptr(db), *dims))
     return dx, part, dg, db
+
+
+FIRST_BLOCK_FORMS = dict(explicit=0, deferred=1, deferred_bf16=2)
+
+
+def op_first_block_bwd(x, gamma_in, beta_in, w, y, gamma2, beta2, dA, relu, form, device=0):
+    """The backward of a tower's first block as the engine runs it (include/l3hip.h l3_op_first_block_bwd), every stage's result in
+    a dict: mean_in, var_in, xaug, mean2, var2, scale2, shift2, dgamma2, dbeta2, cA / cB / cC (deferred forms) or dY ('explicit'),
+    gaug, dw, dbias, dgamma_in, dbeta_in.  form 'deferred_bf16': y and dA are stored as bfloat16 on the device."""
+    lib = load()
+    x, w, y, dA = _f32(x), _f32(w), _f32(y), _f32(dA)
+    n, h, wd, c = x.shape
+    co = w.shape[3]
+    assert w.shape == (3, 3, c, co) and y.shape == (n, h, wd, co) and dA.shape == y.shape
+    vin = [_f32(v) for v in (gamma_in, beta_in)]
+    v2 = [_f32(v) for v in (gamma2, beta2)]
+    assert all(v.shape == (c,) for v in vin) and all(v.shape == (co,) for v in v2)
+    f32 = np.float32
+    out = dict(mean_in=np.empty(c, f32), var_in=np.empty(c, f32), xaug=np.empty((n, h, wd, c + 1), f32))
+    for k in ('mean2', 'var2', 'scale2', 'shift2', 'dgamma2', 'dbeta2'):
+        out[k] = np.empty(co, f32)
+    coeffs = np.empty((3, co), f32) if form != 'explicit' else None
+    dY = np.empty_like(y) if form == 'explicit' else None
+    out.update(gaug=np.empty((9, c + 1, co), f32), dw=np.empty((3, 3, c, co), f32), dbias=np.empty(co, f32),
+               dgamma_in=np.empty(c, f32), dbeta_in=np.empty(c, f32))
+    names = ('mean_in', 'var_in', 'xaug', 'mean2', 'var2', 'scale2', 'shift2', 'dgamma2', 'dbeta2')
+    tail = ('gaug', 'dw', 'dbias', 'dgamma_in', 'dbeta_in')
+    check(lib.l3_op_first_block_bwd(device, FIRST_BLOCK_FORMS[form], int(relu), _ptr(x), _ptr(vin[0]), _ptr(vin[1]), _ptr(w), _ptr(y),
+                                    _ptr(v2[0]), _ptr(v2[1]), _ptr(dA), *([_ptr(out[k]) for k in names] + [_ptr(coeffs), _ptr(dY)] +
+                                                                          [_ptr(out[k]) for k in tail] + [n, h, wd, c, co])))
+    if dY is not None:
+        out['dY'] = dY
+    else:
+        out['cA'], out['cB'], out['cC'] = coeffs
+    return out
+
+
+def op_first_conv_grads(gaug, w, gamma, beta, want_dbias=True, device=0):
+    """first_conv_grads alone: gaug (taps, C + 1, Co), w (taps, C, Co), gamma, beta (C) -> dw, dgamma, dbeta, dbias (None unless
+    want_dbias)."""
+    lib = load()
+    gaug, w, gamma, beta = _f32(gaug), _f32(w), _f32(gamma), _f32(beta)
+    taps, c, co = w.shape
+    assert gaug.shape == (taps, c + 1, co) and gamma.shape == (c,) and beta.shape == (c,)
+    dw = np.empty_like(w)
+    dg, db = np.empty(c, np.float32), np.empty(c, np.float32)
+    dbias = np.empty(co, np.float32) if want_dbias else None
+    check(lib.l3_op_first_conv_grads(device, _ptr(gaug), _ptr(w), _ptr(gamma), _ptr(beta), _ptr(dw), _ptr(dg), _ptr(db), _ptr(dbias),
+                                     taps, c, co))
+    return dw, dg, db, dbias
 
 
 def op_bn_relu_fwd(x, gamma, beta, relu, device=0, x_bf16=False, out_bf16=False):

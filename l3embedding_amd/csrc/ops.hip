@@ -578,6 +578,151 @@ int l3_op_conv2d_dgrad_bn_bwd(int device, int dtype, const float* dy, const floa
     return sc.status();
 }
 
+// The backward of a tower's first block as tower_forward / tower_backward_block run it (engine.hip, OP_BN's bn_xhat_ones and
+// OP_CONV's `p.aug != FW_NONE` branch): the same library calls in the same order on ONE reduction scratch -- the coefficients
+// conv_first_wgrad reads are bn_bwd_fast_coeffs of it -- and one weight-gradient scratch of exactly
+// conv_wgrad_scratch_floats(ageom) floats, NaN before the launch, with a guard behind it.  The convolution's stored output y is an
+// input, so the BatchNorm behind it takes its statistics from y itself (bn_stats_fast, the engine's pass where no epilogue left
+// partials).  form 0: FW_AUG (bn_bwd_fast writes dY and the bias gradient); 1 / 2: FW_AUG_DEFERRED on fp32 / bfloat16-stored y, dA.
+int l3_op_first_block_bwd(int device, int form, int relu, const float* x, const float* gamma_in, const float* beta_in, const float* w,
+                          const float* y, const float* gamma2, const float* beta2, const float* dA, float* mean_in, float* var_in,
+                          float* xaug, float* mean2, float* var2, float* scale2, float* shift2, float* dgamma2, float* dbeta2,
+                          float* coeffs, float* dY, float* gaug, float* dw, float* dbias, float* dgamma_in, float* dbeta_in, int n,
+                          int h, int wd, int c, int cout) {
+    const char* name = "l3_op_first_block_bwd";
+    if (form < 0 || form > 2 || (relu != 0 && relu != 1) || n < 1 || h < 1 || wd < 1 || c < 1 || cout < 1) {
+        set_op_error(std::string(name) + ": form outside 0..2, relu outside 0..1 or an empty shape");
+        return L3_EINVAL;
+    }
+    if (!x || !gamma_in || !beta_in || !w || !y || !gamma2 || !beta2 || !dA || !mean_in || !var_in || !xaug || !mean2 || !var2 ||
+        !scale2 || !shift2 || !dgamma2 || !dbeta2 || !(form == 0 ? dY : coeffs) || !gaug || !dw || !dbias || !dgamma_in || !dbeta_in) {
+        set_op_error(std::string(name) + ": NULL pointer");
+        return L3_EINVAL;
+    }
+    ConvGeom ageom = make_geom(n, h, wd, c, cout, 3, 3, 1);
+    ageom.Cin = c + 1;
+    if (!conv_first_wgrad_ok(ageom) || !bn_fast_ok(cout)) {
+        set_op_error(std::string(name) + ": not a first block (3x3 'same', 1 or 3 channels, 64 filters, L3_FIRST_WGRAD on): the "
+                     "generic weight gradient would run");
+        return L3_EINVAL;
+    }
+    const bool defer = form != 0, bf16 = form == 2;
+    const int64_t rows = (int64_t)n * h * wd;
+    const int ca = c + 1;
+    const size_t nx = (size_t)rows * c, nxa = (size_t)rows * ca, ny = (size_t)rows * cout, nw = (size_t)9 * c * cout,
+                 ng = (size_t)9 * ca * cout, cp = (size_t)(c + 3) / 4 * 4, co = (size_t)cout;
+    const size_t wg = conv_wgrad_scratch_floats(ageom), guard = 4096;
+    size_t red = colreduce_scratch_floats(rows, c);
+    if (bn_fast_scratch_floats(cout) > red) red = bn_fast_scratch_floats(cout);
+    Scope sc(device);
+    if (!sc.ok) return L3_EHIP;
+    const uint32_t nan_bits = 0x7fc00000u;
+    float sentinel = -12345.f;
+    uint32_t sentinel_bits;
+    memcpy(&sentinel_bits, &sentinel, sizeof sentinel_bits);
+    auto fresh = [&](size_t count) {          // an output or scratch buffer: NaN until a kernel writes it
+        float* p = sc.alloc<float>(count);
+        if (p && hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p), (int)nan_bits, count) != hipSuccess) sc.ok = false;
+        return p;
+    };
+    float* d_x = sc.put(x, nx);
+    float* d_w = sc.put(w, nw);
+    float* d_y = sc.put(y, ny);
+    float* d_dA = sc.put(dA, ny);
+    float *d_gi = sc.alloc<float>(cp), *d_bi = sc.alloc<float>(cp);
+    float *d_g2 = sc.put(gamma2, co), *d_b2 = sc.put(beta2, co);
+    float *d_mi = fresh(cp), *d_vi = fresh(cp), *d_sci = fresh(cp), *d_shi = fresh(cp);
+    float *d_m2 = fresh(co), *d_v2 = fresh(co), *d_sc2 = fresh(co), *d_sh2 = fresh(co), *d_dg2 = fresh(co), *d_db2 = fresh(co);
+    float* d_xa = fresh(nxa);
+    float* d_dY = defer ? nullptr : fresh(ny);
+    float* d_gaug = fresh(ng);
+    float *d_dw = fresh(nw), *d_dbias = fresh(co), *d_dgi = fresh(cp), *d_dbi = fresh(cp);
+    float* d_red = fresh(red);
+    float* d_part = fresh(wg + guard);
+    uint16_t* yb = bf16 ? sc.alloc<uint16_t>(ny) : nullptr;
+    uint16_t* ab = bf16 ? sc.alloc<uint16_t>(ny) : nullptr;
+    if (!sc.ok) return L3_ENOMEM;
+    if (hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d_part + wg), (int)sentinel_bits, guard) != hipSuccess) return L3_EHIP;
+    (void)hipMemcpy(d_gi, gamma_in, c * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(d_bi, beta_in, c * 4, hipMemcpyHostToDevice);
+    const float *ys = d_y, *as = d_dA;
+    if (bf16) {          // both tensors as the mixed-precision kernels leave them (the engine's defers())
+        cast_bf16(d_y, yb, (int64_t)ny, sc.s);
+        cast_bf16(d_dA, ab, (int64_t)ny, sc.s);
+        ys = reinterpret_cast<const float*>(yb);
+        as = reinterpret_cast<const float*>(ab);
+    }
+    // forward: the input BatchNorm's statistics and [x^, 1] (engine.hip OP_BN, BS_PLAIN); the following BatchNorm's from y
+    bn_stats(d_x, d_gi, d_bi, d_mi, d_vi, d_sci, d_shi, d_red, rows, c, 1e-3f, sc.s);
+    bn_xhat_ones(d_x, d_mi, d_vi, 1e-3f, d_xa, rows, c, sc.s);
+    bn_stats_fast(ys, d_g2, d_b2, d_m2, d_v2, d_sc2, d_sh2, d_red, rows, cout, 1e-3f, 0, sc.s, bf16 ? 1 : 0);
+    // backward, in the engine's order: BatchNorm behind the conv (BB_FAST / BB_FAST_DEFERRED), then the conv's FW_AUG(_DEFERRED)
+    bn_bwd_fast(ys, d_sc2, d_sh2, d_m2, d_v2, d_g2, as, 0, n, h, wd, cout, h, wd, (int64_t)h * wd * cout, defer ? nullptr : d_dY, d_dg2,
+                d_db2, defer ? nullptr : d_dbias, d_red, 1e-3f, relu, 1, sc.s, 0, bf16 ? 1 : 0, bf16 ? 1 : 0);
+    const float* cf = bn_bwd_fast_coeffs(d_red, cout);
+    if (defer) {
+        const FirstWgFuse f{ys, as, d_sc2, d_sh2, cf, cf + cout, cf + 2 * cout, relu, bf16 ? 1 : 0};
+        conv_wgrad(d_xa, nullptr, d_gaug, d_part, ageom, sc.s, false, false, &f);
+    } else {
+        conv_wgrad(d_xa, d_dY, d_gaug, d_part, ageom, sc.s);
+    }
+    first_conv_grads(d_gaug, d_w, d_gi, d_bi, d_dw, d_dgi, d_dbi, defer ? d_dbias : nullptr, 9, c, cout, sc.s);
+    std::vector<float> g(guard);
+    sc.get(g.data(), d_part + wg, guard);
+    if (!sc.ok) return L3_EHIP;
+    for (size_t i = 0; i < guard; ++i)
+        if (g[i] != sentinel) {
+            set_op_error(std::string(name) + ": float " + std::to_string(i) + " of the guard behind the weight-gradient partials changed");
+            return L3_EINVAL;
+        }
+    sc.get(mean_in, d_mi, (size_t)c);
+    sc.get(var_in, d_vi, (size_t)c);
+    sc.get(xaug, d_xa, nxa);
+    sc.get(mean2, d_m2, co);
+    sc.get(var2, d_v2, co);
+    sc.get(scale2, d_sc2, co);
+    sc.get(shift2, d_sh2, co);
+    sc.get(dgamma2, d_dg2, co);
+    sc.get(dbeta2, d_db2, co);
+    if (defer) sc.get(coeffs, cf, 3 * co);
+    else sc.get(dY, d_dY, ny);
+    sc.get(gaug, d_gaug, ng);
+    sc.get(dw, d_dw, nw);
+    sc.get(dbias, d_dbias, co);
+    sc.get(dgamma_in, d_dgi, (size_t)c);
+    sc.get(dbeta_in, d_dbi, (size_t)c);
+    return sc.status();
+}
+
+// first_conv_grads (elementwise.hip) alone on a caller's gaug (taps, c + 1, co) and filter w (taps, c, co): dw, dgamma (c),
+// dbeta (c) and, unless NULL, dbias (co) -- the ones-channel row of tap taps / 2.
+int l3_op_first_conv_grads(int device, const float* gaug, const float* w, const float* gamma, const float* beta, float* dw,
+                           float* dgamma, float* dbeta, float* dbias, int taps, int c, int co) {
+    if (!gaug || !w || !gamma || !beta || !dw || !dgamma || !dbeta || taps < 1 || c < 1 || co < 1 ||
+        (int64_t)taps * (c + 1) * co >= (int64_t)1 << 31) {
+        set_op_error("l3_op_first_conv_grads: NULL pointer, an empty shape or more than 2^31 entries");
+        return L3_EINVAL;
+    }
+    Scope sc(device);
+    if (!sc.ok) return L3_EHIP;
+    const size_t ng = (size_t)taps * (c + 1) * co, nw = (size_t)taps * c * co;
+    const uint32_t nan_bits = 0x7fc00000u;
+    auto fresh = [&](size_t count) {
+        float* p = sc.alloc<float>(count);
+        if (p && hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p), (int)nan_bits, count) != hipSuccess) sc.ok = false;
+        return p;
+    };
+    float *d_g = sc.put(gaug, ng), *d_w = sc.put(w, nw), *d_ga = sc.put(gamma, (size_t)c), *d_be = sc.put(beta, (size_t)c);
+    float *d_dw = fresh(nw), *d_dg = fresh((size_t)c), *d_db = fresh((size_t)c), *d_dbias = dbias ? fresh((size_t)co) : nullptr;
+    if (!sc.ok) return L3_ENOMEM;
+    first_conv_grads(d_g, d_w, d_ga, d_be, d_dw, d_dg, d_db, d_dbias, taps, c, co, sc.s);
+    sc.get(dw, d_dw, nw);
+    sc.get(dgamma, d_dg, (size_t)c);
+    sc.get(dbeta, d_db, (size_t)c);
+    if (dbias) sc.get(dbias, d_dbias, (size_t)co);
+    return sc.status();
+}
+
 int l3_op_preprocess(int device, const uint8_t* video_u8, int64_t nv, float* video, const int16_t* audio_i16,
                      int64_t na, float* audio) {
     Scope sc(device);
