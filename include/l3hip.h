@@ -185,6 +185,59 @@ int l3_stage_batch_raw_aug(l3_engine *e, const uint8_t *video_u8, const int16_t 
 /* The audio gains (sample.py:156,162 'gain') of the batch the engine holds -- the last one uploaded, or staged and adopted by a
  * step -- B doubles.  Waits for the device: for tests and metadata.  L3_ESTATE if that batch was not augmented. */
 int l3_batch_gains(l3_engine *e, double *gains);
+/* ---- AVC training samples cut on the GPU from decoded clips held there (csrc/avsample.hip) --------------------------------------
+ * 02_generate_samples.py's sampler after decoding (data/avc/sample.py:117-166 sample_one_second, :169-193 sample_cropped_frame,
+ * :196-283 sample_one_frame, :319-387 generate_sample, :445-448 the mono mix).  The draws are the caller's
+ * (l3embedding_amd/avsample.py draw_samples keeps the reference's order of random calls); the library follows the records.
+ *
+ * A bank is two arenas allocated once by l3_clipbank_create -- pixel_bytes of uint8 frames, audio_samples of int16 mono samples --
+ * and filled by bump allocation: nothing ever moves or is freed before l3_clipbank_destroy, so a batch staged from the bank can
+ * never read a freed buffer.  Pixels are kept as uploaded (original size); only a sample's 224 x 224 window is ever resized.  What
+ * that costs: a 10 s clip of 360 x 640 at 30 fps is 300 * 360 * 640 * 3 = 207 MB of pixels and 0.96 MB of audio.
+ * resize: the shorter side frames are resized to before the crop, read_video's rule (sample.py:303-305: scaling = resize /
+ * min(W, H), Wo = ceil(scaling * W), Ho = ceil(scaling * H); >= 225), or 0 for frames the caller's decoder has already resized
+ * (Ho = H, Wo = W, both >= 225: sample.py:182's randrange(n - 224) raises at 224).  Errors: l3_last_error(NULL). */
+typedef struct l3_clipbank l3_clipbank;
+int l3_clipbank_create(int device, int64_t pixel_bytes, int64_t audio_samples, int resize, l3_clipbank **bank);
+/* One decoded clip: frames (n_frames, h, w, 3) uint8 and audio (n, channels) int16 PCM at 48 kHz, interleaved, 1 <= channels <= 8,
+ * n >= 1.  The audio is stored as sample.py:445-448 leaves it, audio.mean(axis=-1).astype('int16'): the channels summed in float64
+ * (exact), one IEEE division by `channels`, truncation toward zero; a mono clip is copied as it is.  Waits for the uploads.
+ * *clip_id: the clip's number, counted from 0.  L3_ENOMEM, with the sizes in the message, when an arena is full; L3_EINVAL for a
+ * NULL pointer, an empty clip, sides outside [1, 8192] or (resize 0) below 225, or a channel count outside [1, 8]. */
+int l3_clipbank_add(l3_clipbank *bank, const uint8_t *frames, int n_frames, int h, int w, const int16_t *audio, int64_t n,
+                    int channels, int *clip_id);
+/* info[0..5] = {n_frames, H, W, Ho, Wo, samples} of a clip; clip == -1: {clips, pixel bytes used, pixel_bytes, samples used,
+ * audio_samples, resize} of the bank. */
+int l3_clipbank_info(const l3_clipbank *bank, int clip, int64_t *info);
+/* A clip's mono samples back on the host (for tests and metadata): `samples` int16. */
+int l3_clipbank_audio(l3_clipbank *bank, int clip, int16_t *out);
+void l3_clipbank_destroy(l3_clipbank *bank);
+/* One sample of generate_sample (sample.py:319-387) after its draws. */
+typedef struct l3_sample {
+    int32_t video_clip, frame;      /* sample_one_frame's frame of that clip (sample.py:212-234) */
+    int32_t audio_clip, audio_start; /* sample_one_second's start, in samples (sample.py:130-136): 0 <= start <= max(len - 48000, 0);
+                                     * the row is zero past the clip's end (sample.py:138-144) */
+    int32_t label;                  /* int(video_choice != audio_choice), sample.py:363; the labels row is {label, 1 - label} (:376) */
+    int32_t reserved;
+    double u_gain;                  /* the gain's draw of random() (sample.py:156); read only when augmenting */
+    l3_augment_params aug;          /* start_x / start_y: the crop in the Ho x Wo frame (sample.py:181-191), always applied; the
+                                     * rest only when augmenting */
+} l3_sample;
+/* l3_upload_batch_raw[_aug] / l3_stage_batch_raw[_aug] of a batch that the engine builds itself from n = batch records: the
+ * records' tables go up on the stream, csrc/frames.hip's resize writes each record's window -- rows [start_x, start_x + 224) x
+ * columns [start_y, start_y + 224) of the frame resized to Ho x Wo -- into the feed's uint8 video rows, the seconds kernel writes
+ * the int16 audio rows, then the labels follow; with augment != 0 also the l3_augment_params rows, crop offsets zeroed because the
+ * crop is done, and the gain draws.  From there on the batch is a raw batch: the same scaling or augmenting conversion, the same
+ * staging protocol, l3_batch_gains.  augment is per batch.  Every record is checked before anything is launched: L3_EINVAL, with
+ * the sample's number in l3_last_error(e), for a clip id out of range, a frame outside the clip, an audio_start outside
+ * [0, max(len - 48000, 0)], a crop outside Ho x Wo or a label other than 0 / 1; also for n != batch or a bank on another device. */
+int l3_upload_batch_sampled(l3_engine *e, l3_clipbank *bank, const l3_sample *records, int n, int augment);
+int l3_stage_batch_sampled(l3_engine *e, l3_clipbank *bank, const l3_sample *records, int n, int augment);
+/* The same kernels alone, in the stored dtypes, for any n >= 1: out_u8 (n, 224, 224, 3), out_i16 (n, 48000) -- what
+ * generate_sample leaves as 'video' and 'audio' -- and, when augmenting, gains (n doubles; else it may be NULL).  Augmented rows
+ * are l3_op_augment_video / l3_op_augment_audio of the un-augmented ones.  Errors as above, in l3_last_error(NULL). */
+int l3_op_sample_batch(l3_clipbank *bank, const l3_sample *records, int n, int augment, uint8_t *out_u8, int16_t *out_i16,
+                       double *gains);
 /* Staged step on the resident batch, so the host can overlap the gradient
  * all-reduce with backward (buckets complete head -> block4 -> ... -> block1):
  *   l3_step_forward          forward + loss + head backward          (bucket 0 ready)

@@ -83,6 +83,16 @@ SIGNATURES = {
     'l3_upload_batch_raw_aug': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'l3_stage_batch_raw_aug': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'l3_batch_gains': (C.c_int, [C.c_void_p, C.c_void_p]),
+    # AVC samples cut on the device from decoded clips held there (csrc/avsample.hip)
+    'l3_clipbank_create': (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    'l3_clipbank_add': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
+                                  C.POINTER(C.c_int)]),
+    'l3_clipbank_info': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    'l3_clipbank_audio': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    'l3_clipbank_destroy': (None, [C.c_void_p]),
+    'l3_upload_batch_sampled': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    'l3_stage_batch_sampled': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    'l3_op_sample_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'l3_step_forward': (C.c_int, [C.c_void_p, C.c_int]),
     'l3_step_bucket_count': (C.c_int, [C.c_void_p]),
     'l3_step_backward_bucket': (C.c_int, [C.c_void_p, C.c_int]),
@@ -526,6 +536,16 @@ class Engine(object):
         out = np.empty(self.batch, np.float64)
         check(self.lib.l3_batch_gains(self.h, _ptr(out)), self.h)
         return out
+
+    def upload_batch_sampled(self, bank, records, augment=False):
+        """upload_batch_raw[_aug] of a batch the engine cuts itself from a ClipBank's clips by `records` (SAMPLE_RECORD rows)."""
+        r = sample_records(records)
+        check(self.lib.l3_upload_batch_sampled(self.h, bank.h, _ptr(r), len(r), int(bool(augment))), self.h)
+
+    def stage_batch_sampled(self, bank, records, augment=False):
+        """stage_batch_raw[_aug] of such a batch: the tables go up and the kernels run on the copy stream, behind the running step."""
+        r = sample_records(records)
+        check(self.lib.l3_stage_batch_sampled(self.h, bank.h, _ptr(r), len(r), int(bool(augment))), self.h)
 
     def tower_step(self, tower, backward=True):
         """One tower alone ('vision' | 'audio') on the resident batch: training-mode forward (+ backward
@@ -1124,6 +1144,78 @@ def op_augment_audio(audio_i16, u, out='i16', device=0):
     gains = np.empty(a.shape[0], np.float64)
     check(lib.l3_op_augment_audio(device, _ptr(a), a.shape[0], a.shape[1], _ptr(g), _ptr(oi), _ptr(of), _ptr(gains)))
     return ((oi, of) if out == 'both' else (oi if of is None else of)), gains
+
+
+# l3_sample of include/l3hip.h: one sample of generate_sample (data/avc/sample.py:319-387) after its draws
+SAMPLE_RECORD = np.dtype({'names': ['video_clip', 'frame', 'audio_clip', 'audio_start', 'label', 'u_gain', 'start_x', 'start_y',
+                                    'flip', 'sat_first', 'saturation', 'brightness'],
+                          'formats': [np.int32] * 5 + [np.float64] + [np.int32] * 4 + [np.float32] * 2,
+                          'offsets': [0, 4, 8, 12, 16, 24, 32, 36, 40, 44, 48, 52], 'itemsize': 56})
+
+
+def sample_records(records):
+    """Any structured array with the fields of l3_sample, packed as the library reads them."""
+    records = np.asarray(records)
+    if records.dtype == SAMPLE_RECORD and records.flags['C_CONTIGUOUS']:
+        return records
+    rec = np.zeros(records.shape, SAMPLE_RECORD)
+    for name in SAMPLE_RECORD.names:
+        rec[name] = records[name]
+    return rec
+
+
+class ClipBank(object):
+    """Thin RAII wrapper over an l3_clipbank handle: decoded clips resident on the device (csrc/avsample.hip)."""
+
+    def __init__(self, device, pixel_bytes, audio_samples, resize):
+        self.lib = load()
+        h = C.c_void_p()
+        check(self.lib.l3_clipbank_create(int(device), int(pixel_bytes), int(audio_samples), int(resize or 0), C.byref(h)))
+        self.h = h
+        self.device = int(device)
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_clipbank_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, frames_u8, audio_i16):
+        """(T, H, W, 3) uint8 and (n, C) int16 -> the clip's id."""
+        f, a = np.ascontiguousarray(frames_u8, dtype=np.uint8), np.ascontiguousarray(audio_i16, dtype=np.int16)
+        if f.ndim != 4 or f.shape[3] != 3 or a.ndim != 2:
+            raise ValueError('a clip is (T, H, W, 3) frames and (n, C) samples, got %r and %r' % (f.shape, a.shape))
+        cid = C.c_int()
+        check(self.lib.l3_clipbank_add(self.h, _ptr(f), f.shape[0], f.shape[1], f.shape[2], _ptr(a), a.shape[0], a.shape[1],
+                                       C.byref(cid)))
+        return cid.value
+
+    def info(self, clip=-1):
+        """{n_frames, H, W, Ho, Wo, samples} of a clip; clip = -1: {clips, pixel bytes used, capacity, samples used, capacity,
+        resize} of the bank."""
+        out = np.zeros(6, np.int64)
+        check(self.lib.l3_clipbank_info(self.h, int(clip), _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    def audio(self, clip):
+        out = np.empty(self.info(clip)[5], np.int16)
+        check(self.lib.l3_clipbank_audio(self.h, int(clip), _ptr(out)))
+        return out
+
+
+def op_sample_batch(bank, records, augment=False):
+    """l3_op_sample_batch: (video (n, 224, 224, 3) uint8, audio (n, 48000) int16, gains (n,) float64 or None)."""
+    r = sample_records(records)
+    n = len(r)
+    v, a = np.empty((n, 224, 224, 3), np.uint8), np.empty((n, 48000), np.int16)
+    g = np.empty(n, np.float64) if augment else None
+    check(load().l3_op_sample_batch(bank.h, _ptr(r), n, int(bool(augment)), _ptr(v), _ptr(a), _ptr(g)))
+    return v, a, g
 
 
 # ---- downstream MLP classifier (classifier/train.py:230-391; csrc/mlp.hip) ---------------------------------------------------------

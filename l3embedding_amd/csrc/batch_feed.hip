@@ -109,16 +109,103 @@ int BatchFeed::upload_float(int slices, const float* video, const float* audio, 
 // records ev_adopted on the engine's stream at the swap and every later stage() makes the copy stream wait for it; in the other
 // direction adopt() makes the engine's stream wait for ev_staged, recorded behind the copies.  A second stage() before an
 // adoption overwrites the first, whatever their forms: the later stage wins.
-int BatchFeed::stage(BatchForm form, int slices, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
-                     const AugmentParams* params, const double* u, std::string* err) {
+int BatchFeed::stage_begin(std::string* err) {
     if (!copy_stream) {
         FEEDCHK(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
         FEEDCHK(hipEventCreateWithFlags(&ev_staged, hipEventDisableTiming));
         FEEDCHK(hipEventCreateWithFlags(&ev_adopted, hipEventDisableTiming));
     }
     if (adopted_once) FEEDCHK(hipStreamWaitEvent(copy_stream, ev_adopted, 0));
-    int rc = send(nxt, form, slices, video_u8, audio_i16, labels_i32, params, u, copy_stream, err);
+    return L3_OK;
+}
+
+int BatchFeed::stage(BatchForm form, int slices, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
+                     const AugmentParams* params, const double* u, std::string* err) {
+    int rc = stage_begin(err);
     if (rc) return rc;
+    if ((rc = send(nxt, form, slices, video_u8, audio_i16, labels_i32, params, u, copy_stream, err))) return rc;
+    FEEDCHK(hipEventRecord(ev_staged, copy_stream));
+    return L3_OK;
+}
+
+// A batch built on the device from sample records.  The set's raw buffers are written by two kernels instead of two copies, on the
+// same stream the copies of send() would take, so the staging rule above covers them as it stands: the copy stream has waited for
+// ev_adopted before either kernel writes into `nxt`.  What is new is host memory that asynchronous copies read: the tables live in
+// the set (RawBatch::host), and a set's tables are rewritten only after the event behind its last fill's copies has passed.
+int BatchFeed::plan_sampled(RawBatch& dst, const ::l3_clipbank* bank, const ::l3_sample* records, int n, bool aug, std::string* err) {
+    if (n != B) {
+        *err = std::to_string(n) + " sample records for a batch of " + std::to_string(B);
+        return L3_EINVAL;
+    }
+    if (T != SAMPLE_T) {
+        *err = "sampled batches are rows of " + std::to_string(SAMPLE_T) + " samples, the engine's are " + std::to_string(T);
+        return L3_EINVAL;
+    }
+    int rc = sampled_plan(bank, records, n, aug, &planned, err);
+    if (rc) return rc;
+    if (dst.tables_pending) {
+        FEEDCHK(event_wait(dst.tables_read));
+        dst.tables_pending = false;
+    }
+    std::swap(dst.host, planned);
+    return L3_OK;
+}
+
+int BatchFeed::fill_sampled(RawBatch& dst, hipStream_t s, std::string* err) {
+    const SampledHost& h = dst.host;
+    const size_t rows = (size_t)B, n_desc = h.plan.frames.size(), n_sec = h.seconds.size(), n_taps = h.plan.taps.size();
+    int rc;
+    if ((rc = grow(bufs, &dst.video, &dst.cap_video, rows * FRAME, err))) return rc;
+    if ((rc = grow(bufs, &dst.audio, &dst.cap_audio, rows * T, err))) return rc;
+    if ((rc = grow(bufs, &dst.labels, &dst.cap_labels, rows * 2, err))) return rc;
+    if ((rc = grow(bufs, &dst.tables, &dst.cap_tables, n_desc + n_sec + n_taps, err))) return rc;
+    if (h.aug) {
+        if ((rc = grow(bufs, &dst.params, &dst.cap_params, rows, err))) return rc;
+        if ((rc = grow(bufs, &dst.u, &dst.cap_u, rows, err))) return rc;
+        if (!gains && !(gains = bufs.alloc<double>((size_t)B))) {
+            *err = "hipMalloc of the batch gains failed";
+            return L3_ENOMEM;
+        }
+    }
+    if (!dst.tables_read) FEEDCHK(hipEventCreateWithFlags(&dst.tables_read, hipEventDisableTiming));
+    dst.form = BATCH_NONE;      // until everything is enqueued
+    int64_t *d_desc = dst.tables, *d_sec = dst.tables + n_desc, *d_taps = d_sec + n_sec;
+    dst.tables_pending = true;          // from the first copy on, whatever happens to the later ones
+    FEEDCHK(hipMemcpyAsync(d_desc, h.plan.frames.data(), n_desc * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    FEEDCHK(hipMemcpyAsync(d_sec, h.seconds.data(), n_sec * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    FEEDCHK(hipMemcpyAsync(d_taps, h.plan.taps.data(), n_taps * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    if (mark) mark(mark_ctx, "sampled: image_frames", s, 1);
+    image_frames(h.pixels, d_desc, d_taps, dst.video, nullptr, B, B, s);
+    if (mark) mark(mark_ctx, "sampled: image_frames", s, 0);
+    if (mark) mark(mark_ctx, "sampled: audio_seconds", s, 1);
+    audio_seconds(h.audio, d_sec, dst.audio, B, T, s);
+    if (mark) mark(mark_ctx, "sampled: audio_seconds", s, 0);
+    FEEDCHK(hipMemcpyAsync(dst.labels, h.labels.data(), rows * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (h.aug) {
+        FEEDCHK(hipMemcpyAsync(dst.params, h.params.data(), rows * sizeof(AugmentParams), hipMemcpyHostToDevice, s));
+        FEEDCHK(hipMemcpyAsync(dst.u, h.u.data(), rows * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    FEEDCHK(hipEventRecord(dst.tables_read, s));
+    FEEDCHK(hipGetLastError());
+    dst.form = BATCH_SINGLE, dst.slices = 1, dst.aug = h.aug;
+    return L3_OK;
+}
+
+int BatchFeed::upload_sampled(const ::l3_clipbank* bank, const ::l3_sample* records, int n, bool aug, hipStream_t s, std::string* err) {
+    int rc = plan_sampled(cur, bank, records, n, aug, err);          // a refusal leaves both sets as they were
+    if (rc) return rc;
+    inputs_replaced(BATCH_SINGLE);
+    if ((rc = fill_sampled(cur, s, err))) return rc;
+    if ((rc = convert(0, s, err))) return rc;
+    FEEDCHK(stream_wait(s));
+    return L3_OK;
+}
+
+int BatchFeed::stage_sampled(const ::l3_clipbank* bank, const ::l3_sample* records, int n, bool aug, std::string* err) {
+    int rc = plan_sampled(nxt, bank, records, n, aug, err);
+    if (rc) return rc;
+    if ((rc = stage_begin(err))) return rc;
+    if ((rc = fill_sampled(nxt, copy_stream, err))) return rc;
     FEEDCHK(hipEventRecord(ev_staged, copy_stream));
     return L3_OK;
 }
@@ -163,6 +250,11 @@ void BatchFeed::destroy() {
         (void)hipEventDestroy(ev_adopted);
         copy_stream = nullptr;
     }
+    for (RawBatch* b : {&cur, &nxt})
+        if (b->tables_read) {
+            (void)hipEventDestroy(b->tables_read);
+            b->tables_read = nullptr;
+        }
     bufs.clear();
 }
 

@@ -2083,6 +2083,57 @@ int l3_stage_batch_raw_aug(l3_engine* e, const uint8_t* video_u8, const int16_t*
     return single_raw_aug(e, "l3_stage_batch_raw_aug", true, video_u8, audio_i16, labels_i32, params, u);
 }
 
+// BatchFeed::mark: the two launches of a sampled fill as profiler records of the input-side family, on whichever stream they took
+static void sampled_fill_mark(void* ctx, const char* tag, hipStream_t s, int begin) {
+    l3_engine* e = static_cast<l3_engine*>(ctx);
+    static thread_local ProfRec open;
+    if (!e->prof_on) return;
+    if (begin) {
+        open = ProfRec{};
+        open.family = F_FRONTEND, open.tag = tag;
+        for (hipEvent_t* ev : {&open.a, &open.b}) {
+            if (!e->ev_pool.empty()) {
+                *ev = e->ev_pool.back();
+                e->ev_pool.pop_back();
+            } else {
+                (void)hipEventCreate(ev);
+            }
+        }
+        (void)hipEventRecord(open.a, s);
+    } else {
+        (void)hipEventRecord(open.b, s);
+        e->prof_recs.push_back(open);
+    }
+}
+
+// data/avc/sample.py:136-144,181-191,234 on the device from records (csrc/avsample.hip), then the raw batch's own path
+static int single_sampled(l3_engine* e, const char* name, bool stage, l3_clipbank* bank, const l3_sample* records, int n, int augment) {
+    if (!e) return L3_EINVAL;
+    if (!bank || !records) {
+        e->err = std::string(name) + ": NULL bank or records";
+        return L3_EINVAL;
+    }
+    if (l3::clipbank_device(bank) != e->cfg.device) {
+        e->err = std::string(name) + ": the bank lives on device " + std::to_string(l3::clipbank_device(bank)) + ", the engine on device " +
+                 std::to_string(e->cfg.device);
+        return L3_EINVAL;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    e->feed.mark = sampled_fill_mark, e->feed.mark_ctx = e;
+    const int rc = stage ? e->feed.stage_sampled(bank, records, n, augment != 0, &e->err)
+                         : e->feed.upload_sampled(bank, records, n, augment != 0, e->stream, &e->err);
+    if (rc == L3_EINVAL) e->err = std::string(name) + ": " + e->err;
+    return rc;
+}
+
+int l3_upload_batch_sampled(l3_engine* e, l3_clipbank* bank, const l3_sample* records, int n, int augment) {
+    return single_sampled(e, "l3_upload_batch_sampled", false, bank, records, n, augment);
+}
+
+int l3_stage_batch_sampled(l3_engine* e, l3_clipbank* bank, const l3_sample* records, int n, int augment) {
+    return single_sampled(e, "l3_stage_batch_sampled", true, bank, records, n, augment);
+}
+
 int l3_batch_gains(l3_engine* e, double* gains) {
     if (!e || !gains) return L3_EINVAL;
     if (!e->feed.gains_valid) {

@@ -9,6 +9,9 @@
 
 #include "host_common.h"
 
+struct l3_clipbank;          // include/l3hip.h
+struct l3_sample;
+
 namespace l3 {
 
 struct ConvGeom {
@@ -328,6 +331,33 @@ void image_plan(const int64_t* table, int64_t n_frames, ImagePlan* plan);       
 void image_frames(const uint8_t* pixels, const int64_t* frames, const int64_t* taps, uint8_t* out_u8, float* out_f32, int rows,
                   int n_real, hipStream_t s);
 
+// AVC samples from decoded clips resident on the device (avsample.hip; data/avc/sample.py:117-166, 196-283, 319-387, 445-448)
+constexpr int SAMPLE_T = 48000;            // one second (sample.py:129-136 at the sampler's 48 kHz)
+constexpr int DOWNMIX_MAX_CHANNELS = 8;
+// out[i] = (int16) trunc(sum_c in[i * C + c] / C) in float64 (numpy's mean(axis=-1).astype('int16')): in is 16-byte aligned,
+// out 16-byte aligned, any n >= 1, 1 <= C <= 8
+void audio_downmix(const int16_t* in, int16_t* out, int64_t n, int C, hipStream_t s);
+// out row r (T int16, 16-byte aligned rows) = samples[table[2 r] + j] for j < table[2 r + 1], else 0.  `samples` is 16-byte
+// aligned and readable up to the next multiple of 8 samples behind every row's last valid sample (the bank rounds its arena up).
+void audio_seconds(const int16_t* samples, const int64_t* table, int16_t* out, int rows, int T, hipStream_t s);
+// What a batch of l3_sample records becomes on the host once it has passed the checks: image_table rows, the plan made of them,
+// the {source offset, valid length} rows of audio_seconds, the labels rows and, for an augmented batch, the records with the
+// crop taken out and the gain draws.  Owned by whoever enqueues the copies, until the stream has consumed them.
+struct SampledHost {
+    std::vector<int64_t> table, seconds;
+    ImagePlan plan;
+    std::vector<int32_t> labels;
+    std::vector<AugmentParams> params;
+    std::vector<double> u;
+    const uint8_t* pixels = nullptr;        // the bank's arenas
+    const int16_t* audio = nullptr;
+    bool aug = false;
+    int n = 0;
+};
+// Checks every record against the bank and fills *out; L3_EINVAL with the sample's number in *err, nothing touched on the device.
+int sampled_plan(const ::l3_clipbank* bank, const ::l3_sample* records, int n, bool aug, SampledHost* out, std::string* err);
+int clipbank_device(const ::l3_clipbank* bank);
+
 // resampling of whole clips (resample.hip; resampy.resample, data/usc/features.py:25-26).  A caller's clip row is RESAMPLE_ROW int64
 // {x_off, L, sr_orig, t0, n_out, y_off}: outputs [t0, t0 + n_out) of the L native samples at x[x_off ..) go to y[y_off ..).
 constexpr int RESAMPLE_ROW = 6;
@@ -389,6 +419,13 @@ struct RawBatch {
     BatchForm form = BATCH_NONE;        // what the set holds (BATCH_GLOBAL_FLOAT: the feed's float buffers hold it, not the set)
     int slices = 0;
     bool aug = false;                   // it carries records: its conversion augments instead of scaling
+    // A batch the feed built on the device from sample records (fill_sampled): the device copy of the plan and the seconds table
+    // ({descriptors | seconds rows | taps}), and their host form, which the copies read until `tables_read` has passed.
+    int64_t* tables = nullptr;
+    size_t cap_tables = 0;
+    SampledHost host;
+    hipEvent_t tables_read = nullptr;
+    bool tables_pending = false;
 };
 // The owner of such batches for an engine: the resident one and the one being staged, the float form of a resident global batch,
 // the copy stream with its event pair, and the gains of the last augmented conversion.  Every method returns L3_OK, L3_ENOMEM or
@@ -410,6 +447,16 @@ struct BatchFeed {
     // Into the staged set over the copy stream, without waiting.
     int stage(BatchForm form, int slices, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
               const AugmentParams* params, const double* u, std::string* err);
+    // A single batch built on the device from n = B sample records of a clip bank (avsample.hip): checked on the host first
+    // (L3_EINVAL, nothing enqueued, the sets as they were), then the tables and records go up on the stream, image_frames and
+    // audio_seconds write the set's raw video and audio rows from the bank's arenas, the labels (and an augmented batch's records,
+    // crop offsets zero, and gain draws) follow.  From there the set is a raw single batch like any other.  upload_sampled: into
+    // the resident set on s, converted, and waits for s; stage_sampled: into the staged set over the copy stream, without waiting.
+    int upload_sampled(const ::l3_clipbank* bank, const ::l3_sample* records, int n, bool aug, hipStream_t s, std::string* err);
+    int stage_sampled(const ::l3_clipbank* bank, const ::l3_sample* records, int n, bool aug, std::string* err);
+    // (profiling) called around each of the two launches of a sampled fill with the stream they go to; null: not called
+    void (*mark)(void* ctx, const char* tag, hipStream_t s, int begin) = nullptr;
+    void* mark_ctx = nullptr;
     // A staged batch of this form becomes the resident one in s's order (a single batch is converted there); else nothing.
     int adopt(BatchForm form, hipStream_t s, std::string* err);
     // Slice r of the resident batch -> float inputs (and gains): augment_video / augment_audio or preprocess_video /
@@ -420,6 +467,10 @@ struct BatchFeed {
 private:
     int send(RawBatch& dst, BatchForm form, int slices, const uint8_t* video_u8, const int16_t* audio_i16, const int32_t* labels_i32,
              const AugmentParams* params, const double* u, hipStream_t s, std::string* err);
+    int stage_begin(std::string* err);          // the copy stream exists and waits for the last adoption
+    int plan_sampled(RawBatch& dst, const ::l3_clipbank* bank, const ::l3_sample* records, int n, bool aug, std::string* err);
+    int fill_sampled(RawBatch& dst, hipStream_t s, std::string* err);
+    SampledHost planned;                // a sampled batch's host form until it has passed the checks
     int B = 0, T = 0;
     float *out_video = nullptr, *out_audio = nullptr, *out_labels = nullptr;
     float *f_video = nullptr, *f_audio = nullptr, *f_labels = nullptr;

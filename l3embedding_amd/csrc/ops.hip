@@ -860,6 +860,50 @@ int l3_op_image_frames(int device, const uint8_t* pixels, int64_t n_bytes, const
     return sc.status();
 }
 
+int l3_op_sample_batch(l3_clipbank* bank, const l3_sample* records, int n, int augment, uint8_t* out_u8, int16_t* out_i16,
+                       double* gains) {
+    if (!bank || !records || !out_u8 || !out_i16 || n < 1 || (augment && !gains)) {
+        set_op_error("l3_op_sample_batch: NULL pointer, n < 1 or an augmented batch without a place for its gains");
+        return L3_EINVAL;
+    }
+    SampledHost h;
+    std::string why;
+    if (int rc = sampled_plan(bank, records, n, augment != 0, &h, &why)) {
+        set_op_error("l3_op_sample_batch: " + why);
+        return rc;
+    }
+    const int device = clipbank_device(bank);
+    Scope sc(device);
+    if (!sc.ok) {
+        set_op_error(no_gpu_message("l3_op_sample_batch", device));
+        return L3_EHIP;
+    }
+    const size_t n_out = (size_t)n * IMG * IMG * 3, n_aud = (size_t)n * SAMPLE_T;
+    const int64_t* d_d = sc.put(h.plan.frames.data(), h.plan.frames.size());
+    const int64_t* d_t = sc.put(h.plan.taps.data(), h.plan.taps.size());
+    const int64_t* d_s = sc.put(h.seconds.data(), h.seconds.size());
+    uint8_t* d_u8 = sc.alloc<uint8_t>(n_out);
+    int16_t* d_i16 = sc.alloc<int16_t>(n_aud);
+    if (!sc.ok) return L3_ENOMEM;
+    image_frames(h.pixels, d_d, d_t, d_u8, nullptr, n, n, sc.s);
+    audio_seconds(h.audio, d_s, d_i16, n, SAMPLE_T, sc.s);
+    if (augment) {          // as BatchFeed::convert augments the rows of a sampled batch, in the stored dtypes
+        const AugmentParams* d_par = sc.put(h.params.data(), (size_t)n);
+        const double* d_u = sc.put(h.u.data(), (size_t)n);
+        uint8_t* d_u8a = sc.alloc<uint8_t>(n_out);
+        int16_t* d_i16a = sc.alloc<int16_t>(n_aud);
+        double* d_g = sc.alloc<double>((size_t)n);
+        if (!sc.ok) return L3_ENOMEM;
+        augment_video(d_u8, n, AUG_CROP, AUG_CROP, d_par, d_u8a, nullptr, sc.s);
+        augment_audio(d_i16, n, SAMPLE_T, d_u, d_i16a, nullptr, d_g, sc.s);
+        d_u8 = d_u8a, d_i16 = d_i16a;
+        sc.get(gains, d_g, (size_t)n);
+    }
+    sc.get(out_u8, d_u8, n_out);
+    sc.get(out_i16, d_i16, n_aud);
+    return sc.status();
+}
+
 static int op_resample(const char* name, int device, const float* x, int64_t n_in, const int64_t* clips, int64_t n_clips,
                        int64_t sr_new, const double* half_window, int64_t n_window, int num_table, int64_t n_samples, bool copy_equal,
                        float* y) {

@@ -469,6 +469,16 @@ class L3Model(object):
         records = () if aug is None else (aug, aug['u_gain'])
         return getattr(e, name + ('_aug' if records else ''))(v, a, np.asarray(l).astype(np.int32), *(records + tail))
 
+    def _sampled_engine(self, x):
+        """The engine for a batch that carries sample records in place of arrays (avsample.SampledInputs; None for any other
+        batch): the engine cuts such a batch itself from the bank's clips.  Data-parallel and serial replicas are out of scope."""
+        if getattr(x, 'sample_records', None) is None:
+            return None
+        if self.replicas > 1:
+            raise ValueError('a sampled batch (avsample.SampledInputs) cannot be fed to a %d-replica model: the engine builds it '
+                             'whole on one GPU' % self.replicas)
+        return self._ensure_engine(len(x.sample_records))
+
     def train_on_batch(self, x, y):
         self._launch_train(x, y, staged=False)
         return self._finish_train()
@@ -478,6 +488,13 @@ class L3Model(object):
         already sent with Engine.stage_batch_raw() and is adopted by the step."""
         if self.optimizer is None:
             raise RuntimeError('You must compile a model before training/testing. Use `model.compile(optimizer, loss)`.')
+        e = self._sampled_engine(x)
+        if e is not None:
+            if not staged:
+                e.upload_batch_sampled(x.bank, x.sample_records, x.augmented)
+            e.step_resident(self.optimizer.lr)
+            self._inflight = (e, len(x), len(x))
+            return
         v, a, l, gb = self._split(x, y)
         aug = self._split_augment(x)
         if self.replicas > 1 and self.serial:
@@ -530,6 +547,11 @@ class L3Model(object):
         if self._inflight is None:
             return False
         e, n_local, _ = self._inflight
+        if getattr(x, 'sample_records', None) is not None:
+            if len(x) != n_local or self.replicas > 1:
+                return False
+            e.stage_batch_sampled(x.bank, x.sample_records, x.augmented)
+            return True
         v, a, l, _ = self._split(x, y)
         if len(v) != n_local or not self._is_raw(v, a):
             return False

@@ -169,14 +169,43 @@ def train_serial_replicas(train_data_dir, validation_data_dir, output_dir, augme
                   serial_replicas=True)
 
 
+def train_sampled(bank, validation_data_dir, output_dir, subset_name, sampler_args=None, **train_args):
+    """`train()` with the training batches sampled on the GPU from the decoded clips of `bank` (avsample.ClipBank) instead of read
+    from blobs: every batch is cut by the engine from an avsample.ClipSampler's records -- new seconds, frames and crops (and, with
+    sampler_args['augment'], new colour and gain draws) every epoch.  Validation still comes from the blobs of
+    `validation_data_dir` and is never sampled or augmented.  subset_name takes the place of the training directory's name in the
+    run directory (`music_train` -> embedding/music/<model_type>/...).  sampler_args: ClipSampler's keyword arguments; batch_size
+    defaults to train_batch_size and random_state to train()'s.  One GPU only.  `train_args`: the keyword arguments of `train()`.
+    config.json also records `sampled` and the sampler's arguments."""
+    import inspect
+    from .avsample import ClipSampler
+    args = {k: v.default for k, v in inspect.signature(train).parameters.items() if v.default is not inspect.Parameter.empty}
+    unknown = sorted(set(train_args) - set(args))
+    if unknown:
+        raise TypeError('train_sampled() got unexpected keyword arguments: %s' % ', '.join(unknown))
+    args.update(train_args)
+    if args['gpus'] > 1:
+        raise ValueError('train_sampled runs on one GPU: a sampled batch is built whole by one engine (gpus=%d)' % args['gpus'])
+    if args['continue_model_dir']:
+        raise ValueError('train_sampled cannot resume a run: the sampler has no position to return to')
+    sargs = dict(batch_size=args['train_batch_size'], random_state=args['random_state'])
+    sargs.update(sampler_args or {})
+    if sargs['batch_size'] != args['train_batch_size']:
+        raise ValueError('the sampler\'s batch_size (%d) is not train_batch_size (%d)' % (sargs['batch_size'], args['train_batch_size']))
+    return _train(subset_name, validation_data_dir, output_dir, **args, make_train_batches=lambda: ClipSampler(bank, **sargs),
+                  extra_config=dict(sampled=True, sampler_args=sargs))
+
+
 def _train(train_data_dir, validation_data_dir, output_dir, num_epochs, train_epoch_size, validation_epoch_size,
            train_batch_size, validation_batch_size, model_type, random_state, learning_rate, verbose, checkpoint_interval,
            log_path, disable_logging, gpus, continue_model_dir, gsheet_id, google_dev_app_name,
-           wrap_train_feed=None, extra_config=None, serial_replicas=False):
+           wrap_train_feed=None, extra_config=None, serial_replicas=False, make_train_batches=None):
     """The body of `train()`.  wrap_train_feed: a wrapper around the generator of training batches (train_augmented);
     extra_config: entries added to config.json; serial_replicas: the `gpus` replicas run one after another in this process
-    (train_serial_replicas)."""
-    call_args = {k: v for k, v in locals().items() if k not in ('wrap_train_feed', 'extra_config', 'serial_replicas')}
+    (train_serial_replicas); make_train_batches: called for the generator of training batches in place of the blob feed over
+    train_data_dir, which then only names the run (train_sampled)."""
+    call_args = {k: v for k, v in locals().items()
+                 if k not in ('wrap_train_feed', 'extra_config', 'serial_replicas', 'make_train_batches')}
     serial = bool(serial_replicas) and gpus > 1
     if not disable_logging and log_path:
         handler = logging.FileHandler(log_path)
@@ -232,13 +261,18 @@ def _train(train_data_dir, validation_data_dir, output_dir, num_epochs, train_ep
     first_epoch = resume[0] + 1 if resume is not None else 0
     shard = dict(rank=rank, world=world) if gpus > 1 and distributed else {}
     LOGGER.info('Setting up train data generator...')
-    train_feed = blobfeed.BlobFeed(train_data_dir, train_batch_size, random_state,
-                                   start_batch_idx=train_epoch_size * first_epoch if resume is not None else None, **shard)
+    train_feed = None
+    if make_train_batches is None:
+        train_feed = blobfeed.BlobFeed(train_data_dir, train_batch_size, random_state,
+                                       start_batch_idx=train_epoch_size * first_epoch if resume is not None else None, **shard)
     LOGGER.info('Setting up validation data generator...')
     val_feed = blobfeed.RestartingFeed(
         lambda: blobfeed.BlobFeed(validation_data_dir, validation_batch_size, random_state, **shard), validation_epoch_size)
 
-    train_batches = blobfeed.as_model_inputs(train_feed, train_batch_size, sharded=bool(shard))
+    if train_feed is None:
+        train_batches = make_train_batches()
+    else:
+        train_batches = blobfeed.as_model_inputs(train_feed, train_batch_size, sharded=bool(shard))
     if wrap_train_feed is not None:
         train_batches = wrap_train_feed(train_batches)
     LOGGER.info('Fitting model...')
@@ -248,7 +282,8 @@ def _train(train_data_dir, validation_data_dir, output_dir, num_epochs, train_ep
                                   validation_steps=validation_epoch_size, callbacks=callbacks,
                                   verbose=1 if verbose else 2, initial_epoch=first_epoch)
     finally:
-        train_feed.close()          # the feeds keep their last few blobs open (memory-mapped): released with the run
+        if train_feed is not None:
+            train_feed.close()      # the feeds keep their last few blobs open (memory-mapped): released with the run
         val_feed.close()
 
     LOGGER.info('Done training. Saving results to disk...')
