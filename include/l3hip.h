@@ -474,6 +474,39 @@ int l3_op_maxpool_fwd(int device, const float *x, float *y, int n, int h, int wd
 int l3_op_maxpool_bwd(int device, const float *x, const float *dy, float *dx, int n, int h,
                       int wd, int c, int ph, int pw, int sh, int sw, int same);
 int l3_op_frontend(int device, int model_type, const float *audio, int n, int db_max_scope, float *out);
+/* The front-end's kernels one by one (csrc/frontend.hip; tests/frontend_ref.py).  Every output buffer is NaN before the launch and
+ * has a guard behind it that must come back untouched (L3_EINVAL otherwise); shapes the kernels cannot index are L3_EINVAL.
+ *
+ * l3_frontend_cfg (host only): the geometry the engine derives for t samples, 'same' (TensorFlow) or 'valid' framing:
+ * cfg[L3_FRONTEND_CFG_FIELDS] = n_frames, pad_left, n_freq, ncols_pad, ke, ko, nc, N1, N2.
+ * l3_frontend_tables (host only), n_dft = 2048 = 32 x 64: the periodic Hann window win (2048), the factored DFT's b1 (32, 64),
+ * b2 (128, 64) and twiddles tw (64, 32, 2), and -- n_mels > 0 -- the filterbank freq2mel (1025, n_mels; NULL: the stock HTK bank at
+ * 48 kHz) packed as bands: filter q = melw[mel_off[q] .. + mel_len[q]) on the bins from mel_start[q], first to last nonzero weight.
+ * *n_melw = the number of packed weights; more than melw_cap is L3_EINVAL.  All exactly as an engine uploads them. */
+#define L3_FRONTEND_CFG_FIELDS 9
+int l3_frontend_cfg(int t, int n_dft, int n_hop, int same, int n_mels, int32_t *cfg);
+int l3_frontend_tables(const float *freq2mel, int n_mels, float *win, float *b1, float *b2, float *tw, int32_t *mel_start,
+                       int32_t *mel_len, int32_t *mel_off, float *melw, int64_t melw_cap, int64_t *n_melw);
+/* frame_audio, frame_audio_folded and (a1 != NULL, n_dft = 2048) dft_pack_frames on audio (b, t), frame f of a sample = its samples
+ * f n_hop - pad_left ..., zeros outside: frames (b n_frames, n_dft), fe (b n_frames, ke), fo (b n_frames, ko), a1 (b n_frames, 64, 32). */
+int l3_op_frontend_frames(int device, const float *audio, int b, int t, int n_dft, int n_hop, int pad_left, int n_frames,
+                          float *frames, float *fe, float *fo, float *a1);
+/* dft_twiddle on y (frames, 64, [re k1 (32) | im k1 (32)]): a2 (frames, 32, [re n2 (64) | im n2 (64)]) and nyq (frames). */
+int l3_op_dft_twiddle(int device, const float *y, int frames, float *a2, float *nyq);
+/* spec_to_features on a caller's transform of b n_frames rows.  L3_SPEC_UNFOLDED: spec (rows, ncols_pad) = [re | im | pad];
+ * L3_SPEC_FOLDED: (2 rows, nc), the re rows then the im rows; L3_SPEC_FACTORED (n_dft = 2048): (rows, 32, [re k2 (32) | im k2 (32)]),
+ * bin k1 + 32 k2, and nyq (rows).  n_mels = 0: no mel projection.  flags: bit 0 sqrt_out, bit 1 db, bit 2 loglambda.
+ * out (b, n_mels or n_freq, n_frames), before db_normalize. */
+#define L3_SPEC_UNFOLDED 0
+#define L3_SPEC_FOLDED 1
+#define L3_SPEC_FACTORED 2
+int l3_op_spec_to_features(int device, int layout, const float *spec, const float *nyq, int b, int n_frames, int n_dft, int n_mels,
+                           const float *freq2mel, int flags, float *out);
+/* dft_fused (n_dft = 2048) on audio (b, t) with the library's own tables: out (b, n_mels, n_frames), before db_normalize. */
+int l3_op_dft_fused(int device, const float *audio, int b, int t, int n_hop, int pad_left, int n_frames, int n_mels,
+                    const float *freq2mel, int flags, float *out);
+/* db_normalize in place on x (b, per_sample): x - max (of the sample, or batch_scope = 1 of the batch), clamped at -80. */
+int l3_op_db_normalize(int device, float *x, int b, int64_t per_sample, int batch_scope);
 /* The frame gather of l3_embed_audio_frames on its own: frames (n_frames, 48000) from samples + table as above (parity tests). */
 int l3_op_gather_frames(int device, const float *samples, int64_t n_samples, const int64_t *table,
                         int64_t n_frames, float *frames);

@@ -158,6 +158,13 @@ SIGNATURES = {
     'l3_op_maxpool_fwd': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 9),
     'l3_op_maxpool_bwd': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9),
     'l3_op_frontend': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'l3_frontend_cfg': (C.c_int, [C.c_int] * 5 + [C.c_void_p]),
+    'l3_frontend_tables': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int64, C.POINTER(C.c_int64)]),
+    'l3_op_frontend_frames': (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4),
+    'l3_op_dft_twiddle': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'l3_op_spec_to_features': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p]),
+    'l3_op_dft_fused': (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p]),
+    'l3_op_db_normalize': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int]),
     'l3_op_gather_frames': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     'l3_op_image_frames': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'l3_op_resample': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
@@ -1032,6 +1039,99 @@ def op_frontend(model_type, audio, db_max_scope='sample', device=0):
     out = np.empty((n, probe[0], probe[1], 1), np.float32)
     check(lib.l3_op_frontend(device, MODEL_IDS[model_type], _ptr(a), n, 0 if db_max_scope == 'sample' else 1, _ptr(out)))
     return out
+
+
+FRONTEND_CFG_FIELDS = ('n_frames', 'pad_left', 'n_freq', 'ncols_pad', 'ke', 'ko', 'nc', 'N1', 'N2')
+SPEC_LAYOUTS = dict(unfolded=0, folded=1, factored=2)
+
+
+def frontend_cfg(t, n_dft, n_hop, same, n_mels=0):
+    """The front-end geometry the engine derives for t samples (include/l3hip.h l3_frontend_cfg; host only): a dict of
+    FRONTEND_CFG_FIELDS."""
+    v = np.zeros(len(FRONTEND_CFG_FIELDS), np.int32)
+    check(load().l3_frontend_cfg(int(t), int(n_dft), int(n_hop), int(bool(same)), int(n_mels), _ptr(v)))
+    return dict(zip(FRONTEND_CFG_FIELDS, (int(x) for x in v)))
+
+
+def frontend_tables(n_mels=0, freq2mel=None):
+    """The tables of the 2048-point front-end as an engine uploads them (l3_frontend_tables; host only): dict of win (2048),
+    b1 (32, 64), b2 (128, 64), tw (64, 32, 2) and, n_mels > 0, mel_start / mel_len / mel_off (n_mels) and melw, the packed bands of
+    freq2mel (1025, n_mels), None = the stock bank."""
+    f32 = np.float32
+    out = dict(win=np.empty(2048, f32), b1=np.empty((32, 64), f32), b2=np.empty((128, 64), f32), tw=np.empty((64, 32, 2), f32))
+    fb = _f32(freq2mel)
+    assert fb is None or fb.shape == (1025, n_mels)
+    st, ln, of = (np.zeros(n_mels, np.int32) for _ in range(3))
+    cap = 1025 * max(n_mels, 1)
+    melw = np.empty(cap, f32)
+    n = C.c_int64(0)
+    check(load().l3_frontend_tables(_ptr(fb), int(n_mels), _ptr(out['win']), _ptr(out['b1']), _ptr(out['b2']), _ptr(out['tw']), _ptr(st),
+                                    _ptr(ln), _ptr(of), _ptr(melw), cap, C.byref(n)))
+    if n_mels:
+        out.update(mel_start=st, mel_len=ln, mel_off=of, melw=melw[:n.value].copy())
+    return out
+
+
+def op_frontend_frames(audio, n_dft, n_hop, pad_left, n_frames, device=0):
+    """frame_audio, frame_audio_folded and (n_dft = 2048) dft_pack_frames on audio (B, T): frames (B, n_frames, n_dft), fe
+    (B, n_frames, ke), fo (B, n_frames, ko), a1 (B, n_frames, 64, 32) or None."""
+    a = _f32(audio)
+    b, t = a.shape
+    cfg = frontend_cfg(max(t, n_dft), n_dft, n_hop, False)
+    f32 = np.float32
+    frames, fe, fo = (np.empty((b, n_frames, w), f32) for w in (n_dft, cfg['ke'], cfg['ko']))
+    a1 = np.empty((b, n_frames, 64, 32), f32) if n_dft == 2048 else None
+    check(load().l3_op_frontend_frames(device, _ptr(a), b, t, int(n_dft), int(n_hop), int(pad_left), int(n_frames), _ptr(frames), _ptr(fe),
+                                       _ptr(fo), _ptr(a1)))
+    return frames, fe, fo, a1
+
+
+def op_dft_twiddle(y, device=0):
+    """dft_twiddle on y (frames, 64, 64) = [re k1 | im k1] per n2: a2 (frames, 32, 128) = [re n2 | im n2] per k1, nyq (frames)."""
+    y = _f32(y)
+    frames = y.shape[0]
+    assert y.shape == (frames, 64, 64)
+    a2, nyq = np.empty((frames, 32, 128), np.float32), np.empty(frames, np.float32)
+    check(load().l3_op_dft_twiddle(device, _ptr(y), frames, _ptr(a2), _ptr(nyq)))
+    return a2, nyq
+
+
+def _frontend_flags(sqrt_out, db, loglambda):
+    return int(bool(sqrt_out)) | int(bool(db)) << 1 | int(bool(loglambda)) << 2
+
+
+def op_spec_to_features(layout, spec, b, n_frames, n_dft, n_mels=0, freq2mel=None, nyq=None, sqrt_out=False, db=False, loglambda=False,
+                        device=0):
+    """spec_to_features on a caller's transform in layout 'unfolded' (rows, ncols_pad), 'folded' (2 rows, nc) or 'factored'
+    (rows, 32, 64) with nyq (rows); rows = b n_frames: (b, n_mels or n_freq, n_frames)."""
+    spec, nyq, fb = _f32(spec), _f32(nyq), _f32(freq2mel)
+    rows, nb = b * n_frames, n_dft // 2 + 1
+    cfg = frontend_cfg(n_dft, n_dft, 1, False)
+    want = {'unfolded': rows * cfg['ncols_pad'], 'folded': 2 * rows * cfg['nc'], 'factored': rows * n_dft}[layout]
+    assert spec.size == want and (nyq is None or nyq.size == rows) and (fb is None or fb.shape == (nb, n_mels))
+    out = np.empty((b, n_mels or nb, n_frames), np.float32)
+    check(load().l3_op_spec_to_features(device, SPEC_LAYOUTS[layout], _ptr(spec), _ptr(nyq), b, n_frames, n_dft, n_mels, _ptr(fb),
+                                        _frontend_flags(sqrt_out, db, loglambda), _ptr(out)))
+    return out
+
+
+def op_dft_fused(audio, n_hop, pad_left, n_frames, n_mels, freq2mel=None, sqrt_out=False, db=False, loglambda=False, device=0):
+    """dft_fused on audio (B, T): (B, n_mels, n_frames), before db_normalize.  freq2mel (1025, n_mels), None = the stock bank."""
+    a, fb = _f32(audio), _f32(freq2mel)
+    b, t = a.shape
+    assert fb is None or fb.shape == (1025, n_mels)
+    out = np.empty((b, n_mels, n_frames), np.float32)
+    check(load().l3_op_dft_fused(device, _ptr(a), b, t, int(n_hop), int(pad_left), int(n_frames), int(n_mels), _ptr(fb),
+                                 _frontend_flags(sqrt_out, db, loglambda), _ptr(out)))
+    return out
+
+
+def op_db_normalize(x, scope='sample', device=0):
+    """db_normalize on a copy of x (B, per_sample): x - max (per sample, or scope 'batch' of everything), clamped at -80."""
+    x = np.array(x, dtype=np.float32, order='C')
+    b, per = x.shape
+    check(load().l3_op_db_normalize(device, _ptr(x), b, per, 0 if scope == 'sample' else 1))
+    return x
 
 
 def op_gather_frames(samples, table, device=0):

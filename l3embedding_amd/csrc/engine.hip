@@ -564,27 +564,7 @@ int build_ledger(l3_engine* e) {
     }
     // audio front-end
     FrontendCfg& f = e->fcfg;
-    f.n_dft = e->fe.n_dft;
-    f.n_hop = e->fe.n_hop;
-    f.n_freq = f.n_dft / 2 + 1;
-    f.n_mels = e->fe.n_mels;
-    if (e->fe.same) {
-        tf_same(AUDIO_T, f.n_dft, f.n_hop, &f.n_frames, &f.pad_left);
-    } else {
-        f.n_frames = (AUDIO_T - f.n_dft) / f.n_hop + 1;
-        f.pad_left = 0;
-    }
-    f.sqrt_out = e->fe.sqrt_out;
-    f.db = e->fe.db;
-    f.loglambda = e->fe.loglambda;
-    f.ncols_pad = (2 * f.n_freq + 31) / 32 * 32;
-    f.folded = 0;                                       // decided from the kernels' symmetry (rebuild_consts)
-    f.factored = 0;                                     // ... and from their being kapre's stock kernels
-    f.N1 = 32;
-    f.N2 = f.n_dft / 32;
-    f.ke = (f.n_dft / 2 + 1 + 15) / 16 * 16;
-    f.ko = (f.n_dft / 2 - 1 + 15) / 16 * 16;
-    f.nc = f.ncols_pad / 2;
+    f = frontend_cfg(AUDIO_T, e->fe.n_dft, e->fe.n_hop, e->fe.same != 0, e->fe.n_mels, e->fe.sqrt_out, e->fe.db, e->fe.loglambda);
     const std::string fen = std::string("audio_model/") + e->fe.layer_name;
     add_param(e, fen + "/real_kernels", {f.n_dft, 1, 1, f.n_freq}, false, PK_CONST, &e->p_real);
     add_param(e, fen + "/imag_kernels", {f.n_dft, 1, 1, f.n_freq}, false, PK_CONST, &e->p_imag);
@@ -739,33 +719,6 @@ void host_dft_kernels(int n_dft, std::vector<float>& real, std::vector<float>& i
     }
 }
 
-void host_mel_basis(int sr, int n_fft, int n_mels, std::vector<float>& freq2mel /* (nb, n_mels) */) {
-    const int nb = n_fft / 2 + 1;
-    auto hz2mel = [](double f) { return 2595.0 * std::log10(1.0 + f / 700.0); };
-    auto mel2hz = [](double m) { return 700.0 * (std::pow(10.0, m / 2595.0) - 1.0); };
-    const double fmax = (double)sr / 2.0;
-    std::vector<double> mel_f(n_mels + 2);
-    const double m0 = hz2mel(0.0), m1 = hz2mel(fmax);
-    for (int i = 0; i < n_mels + 2; ++i) {
-        // numpy.linspace: start + i*step, last point exactly stop
-        const double m = (i == n_mels + 1) ? m1 : m0 + (double)i * ((m1 - m0) / (double)(n_mels + 1));
-        mel_f[i] = mel2hz(m);
-    }
-    freq2mel.assign((size_t)nb * n_mels, 0.f);
-    for (int i = 0; i < n_mels; ++i) {
-        const double fd0 = mel_f[i + 1] - mel_f[i], fd1 = mel_f[i + 2] - mel_f[i + 1];
-        const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
-        for (int j = 0; j < nb; ++j) {
-            const double fj = (j == nb - 1) ? fmax : (double)j * (fmax / (double)(nb - 1));
-            const double lower = -(mel_f[i] - fj) / fd0;
-            const double upper = (mel_f[i + 2] - fj) / fd1;
-            double w = lower < upper ? lower : upper;
-            if (w < 0.0) w = 0.0;
-            freq2mel[(size_t)j * n_mels + i] = (float)(w * enorm);
-        }
-    }
-}
-
 struct Rng {
     uint64_t s;
     explicit Rng(uint64_t seed) : s(seed ? seed : 0x9E3779B97F4A7C15ull) {}
@@ -825,32 +778,9 @@ int rebuild_consts(l3_engine* e) {
         }
         fw.factored = stock ? 1 : 0;
         if (stock && !e->dft_consts_done) {
-            const int N1 = fw.N1, N2 = fw.N2;
-            const double two_pi = 2.0 * M_PI;
-            std::vector<float> win(N), b1((size_t)N1 * 2 * N1), b2((size_t)2 * N2 * N2), tw((size_t)N2 * N1 * 2);
-            for (int t = 0; t < N; ++t) win[t] = (float)(0.5 - 0.5 * std::cos(two_pi * (double)t / (double)N));     // as host_dft_kernels
-            for (int n1 = 0; n1 < N1; ++n1)
-                for (int k1 = 0; k1 < N1; ++k1) {
-                    const double a = two_pi * (double)((n1 * k1) % N1) / (double)N1;
-                    b1[(size_t)n1 * 2 * N1 + k1] = (float)std::cos(a);
-                    b1[(size_t)n1 * 2 * N1 + N1 + k1] = (float)-std::sin(a);
-                }
-            const int h2 = N2 / 2;
-            for (int n2 = 0; n2 < N2; ++n2)
-                for (int k2 = 0; k2 < h2; ++k2) {
-                    const double a = two_pi * (double)((n2 * k2) % N2) / (double)N2;
-                    const float c = (float)std::cos(a), s = (float)std::sin(a);
-                    b2[(size_t)n2 * N2 + k2] = c;                   // Zre -> re
-                    b2[(size_t)n2 * N2 + h2 + k2] = -s;             // Zre -> im
-                    b2[(size_t)(N2 + n2) * N2 + k2] = s;            // Zim -> re
-                    b2[(size_t)(N2 + n2) * N2 + h2 + k2] = c;       // Zim -> im
-                }
-            for (int n2 = 0; n2 < N2; ++n2)
-                for (int k1 = 0; k1 < N1; ++k1) {
-                    const double a = two_pi * (double)(n2 * k1) / (double)N;
-                    tw[((size_t)n2 * N1 + k1) * 2] = (float)std::cos(a);
-                    tw[((size_t)n2 * N1 + k1) * 2 + 1] = (float)std::sin(a);
-                }
+            DftTables t;
+            dft_factor_tables(N, fw.N1, fw.N2, t);
+            const std::vector<float>&win = t.win, &b1 = t.b1, &b2 = t.b2, &tw = t.tw;
             HIPCHK(e, hipMemcpy(e->dft_win, win.data(), win.size() * 4, hipMemcpyHostToDevice));
             HIPCHK(e, hipMemcpy(e->dft_b1, b1.data(), b1.size() * 4, hipMemcpyHostToDevice));
             HIPCHK(e, hipMemcpy(e->dft_b2, b2.data(), b2.size() * 4, hipMemcpyHostToDevice));
@@ -876,20 +806,10 @@ int rebuild_consts(l3_engine* e) {
     if (f.n_mels) {
         std::vector<float> fb((size_t)nb * f.n_mels);
         HIPCHK(e, hipMemcpy(fb.data(), e->params[e->p_mel].d, fb.size() * 4, hipMemcpyDeviceToHost));
-        std::vector<int> st(f.n_mels), ln(f.n_mels), of(f.n_mels);
-        std::vector<float> packed;
-        for (int m = 0; m < f.n_mels; ++m) {
-            int first = -1, last = -1;
-            for (int j = 0; j < nb; ++j)
-                if (fb[(size_t)j * f.n_mels + m] != 0.f) {
-                    if (first < 0) first = j;
-                    last = j;
-                }
-            st[m] = first < 0 ? 0 : first;
-            ln[m] = first < 0 ? 0 : last - first + 1;
-            of[m] = (int)packed.size();
-            for (int j = 0; j < ln[m]; ++j) packed.push_back(fb[(size_t)(st[m] + j) * f.n_mels + m]);
-        }
+        MelBands bands;
+        mel_pack_bands(fb.data(), nb, f.n_mels, bands);
+        const std::vector<int>&st = bands.start, &ln = bands.len, &of = bands.off;
+        const std::vector<float>& packed = bands.w;
         if ((int64_t)packed.size() > e->melw_cap) {
             e->err = "mel filterbank too dense for the band buffer";
             return L3_EINVAL;

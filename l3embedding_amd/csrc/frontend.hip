@@ -12,6 +12,8 @@
 // frames (B*n_frames, n_dft) and conv_fwd() multiplies them with the (n_dft, re|im)
 // basis as a 1x1 convolution.  The mel projection uses the band structure of the
 // filterbank (<= 28 taps per filter for 256 mels) instead of a dense 1025x256 GEMM.
+#include <cmath>
+
 #include "kernels.h"
 #include "device_common.h"
 
@@ -125,6 +127,13 @@ __global__ __launch_bounds__(256) void dft_twiddle_kernel(const float* __restric
 void dft_twiddle(const float* y, const float* tw, float* a2, float* nyq, int frames, const FrontendCfg& c, hipStream_t s) {
     hipLaunchKernelGGL(dft_twiddle_kernel, dim3(frames), dim3(256), (size_t)c.N2 * (2 * c.N1 + 1) * sizeof(float), s, y, tw, a2, nyq, c);
 }
+
+// amplitude_to_decibel's 10 log10(max(v, 1e-10)) and the L3 Lambda's log(max(v, 1e-12)) / 5 with the floor taken on the RESULT: a value
+// at or under amin then gives exactly -100, or log(1e-12) / 5 rounded to float, as the float64 oracle does.  Through logf (within one
+// ulp, not correctly rounded) and two more roundings the floors came out as -100.000015 and one ulp under the rounded log floor.
+// logf(0) = -inf and a NaN from a negative argument both end at the floor; above amin nothing changes.
+__device__ __forceinline__ float to_db(float v) { return fmaxf(10.f * logf(v) / 2.302585092994046f, -100.f); }
+__device__ __forceinline__ float to_loglambda(float v) { return fmaxf(logf(v) / 5.0f, -5.526204223185709f); }
 
 // ---- the whole factored front-end of one frame in ONE wave (round 6) ---------------------------------------------------------------
 // window -> 64 length-32 DFTs (MFMA) -> twiddles -> 32 length-64 complex DFTs (MFMA) -> power -> mel -> sqrt / dB, nothing but the
@@ -295,8 +304,8 @@ __global__ __launch_bounds__(64 * DF_WAVES) void dft_fused_kernel(const float* _
                 v = fmaf(k == c.n_dft / 2 ? P[DF_N1 * 33] : P[(k & 31) * 33 + (k >> 5)], melw[of + i], v);
             }
             if (c.sqrt_out) v = sqrtf(v);
-            if (c.db) v = 10.f * logf(fmaxf(v, 1e-10f)) / 2.302585092994046f;
-            if (c.loglambda) v = logf(fmaxf(v, 1e-12f)) / 5.0f;
+            if (c.db) v = to_db(v);
+            if (c.loglambda) v = to_loglambda(v);
             out[((size_t)b * F + q) * c.n_frames + f] = v;
         }
     }
@@ -356,8 +365,8 @@ __global__ __launch_bounds__(256) void spec_to_features_kernel(const float* spec
             v = pw[q];
         }
         if (c.sqrt_out) v = sqrtf(v);
-        if (c.db) v = 10.f * logf(fmaxf(v, 1e-10f)) / 2.302585092994046f;
-        if (c.loglambda) v = logf(fmaxf(v, 1e-12f)) / 5.0f;
+        if (c.db) v = to_db(v);
+        if (c.loglambda) v = to_loglambda(v);
         out[((size_t)b * F + q) * c.n_frames + f] = v;
     }
 }
@@ -408,6 +417,114 @@ void db_normalize(float* x, float* smax, int B, int64_t per_sample, int batch_sc
     int64_t blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(db_sub_clamp_kernel, dim3((int)blocks), dim3(256), 0, s, x, smax, per_sample, total);
+}
+
+// ---- host side: the geometry and the tables the kernels above read -------------------------------------------------------------------
+FrontendCfg frontend_cfg(int T, int n_dft, int n_hop, bool same, int n_mels, int sqrt_out, int db, int loglambda) {
+    FrontendCfg f{};
+    f.n_dft = n_dft;
+    f.n_hop = n_hop;
+    f.n_freq = f.n_dft / 2 + 1;
+    f.n_mels = n_mels;
+    if (same) {
+        tf_same(T, f.n_dft, f.n_hop, &f.n_frames, &f.pad_left);
+    } else {
+        f.n_frames = (T - f.n_dft) / f.n_hop + 1;
+        f.pad_left = 0;
+    }
+    f.sqrt_out = sqrt_out;
+    f.db = db;
+    f.loglambda = loglambda;
+    f.ncols_pad = (2 * f.n_freq + 31) / 32 * 32;
+    f.folded = 0;
+    f.factored = 0;
+    f.N1 = 32;
+    f.N2 = f.n_dft / 32;
+    f.ke = (f.n_dft / 2 + 1 + 15) / 16 * 16;
+    f.ko = (f.n_dft / 2 - 1 + 15) / 16 * 16;
+    f.nc = f.ncols_pad / 2;
+    return f;
+}
+
+void host_mel_basis(int sr, int n_fft, int n_mels, std::vector<float>& freq2mel /* (nb, n_mels) */) {
+    const int nb = n_fft / 2 + 1;
+    auto hz2mel = [](double f) { return 2595.0 * std::log10(1.0 + f / 700.0); };
+    auto mel2hz = [](double m) { return 700.0 * (std::pow(10.0, m / 2595.0) - 1.0); };
+    const double fmax = (double)sr / 2.0;
+    std::vector<double> mel_f(n_mels + 2);
+    const double m0 = hz2mel(0.0), m1 = hz2mel(fmax);
+    for (int i = 0; i < n_mels + 2; ++i) {
+        // numpy.linspace: start + i*step, last point exactly stop
+        const double m = (i == n_mels + 1) ? m1 : m0 + (double)i * ((m1 - m0) / (double)(n_mels + 1));
+        mel_f[i] = mel2hz(m);
+    }
+    freq2mel.assign((size_t)nb * n_mels, 0.f);
+    for (int i = 0; i < n_mels; ++i) {
+        const double fd0 = mel_f[i + 1] - mel_f[i], fd1 = mel_f[i + 2] - mel_f[i + 1];
+        const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
+        for (int j = 0; j < nb; ++j) {
+            const double fj = (j == nb - 1) ? fmax : (double)j * (fmax / (double)(nb - 1));
+            const double lower = -(mel_f[i] - fj) / fd0;
+            const double upper = (mel_f[i + 2] - fj) / fd1;
+            double w = lower < upper ? lower : upper;
+            if (w < 0.0) w = 0.0;
+            freq2mel[(size_t)j * n_mels + i] = (float)(w * enorm);
+        }
+    }
+}
+
+void dft_factor_tables(int n_dft, int N1, int N2, DftTables& t) {
+    const int N = n_dft;
+    const double two_pi = 2.0 * M_PI;
+    std::vector<float>&win = t.win, &b1 = t.b1, &b2 = t.b2, &tw = t.tw;
+    win.assign(N, 0.f);
+    b1.assign((size_t)N1 * 2 * N1, 0.f);
+    b2.assign((size_t)2 * N2 * N2, 0.f);
+    tw.assign((size_t)N2 * N1 * 2, 0.f);
+    for (int n = 0; n < N; ++n) win[n] = (float)(0.5 - 0.5 * std::cos(two_pi * (double)n / (double)N));     // as host_dft_kernels
+    for (int n1 = 0; n1 < N1; ++n1)
+        for (int k1 = 0; k1 < N1; ++k1) {
+            const double a = two_pi * (double)((n1 * k1) % N1) / (double)N1;
+            b1[(size_t)n1 * 2 * N1 + k1] = (float)std::cos(a);
+            b1[(size_t)n1 * 2 * N1 + N1 + k1] = (float)-std::sin(a);
+        }
+    const int h2 = N2 / 2;
+    for (int n2 = 0; n2 < N2; ++n2)
+        for (int k2 = 0; k2 < h2; ++k2) {
+            const double a = two_pi * (double)((n2 * k2) % N2) / (double)N2;
+            const float c = (float)std::cos(a), s = (float)std::sin(a);
+            b2[(size_t)n2 * N2 + k2] = c;                   // Zre -> re
+            b2[(size_t)n2 * N2 + h2 + k2] = -s;             // Zre -> im
+            b2[(size_t)(N2 + n2) * N2 + k2] = s;            // Zim -> re
+            b2[(size_t)(N2 + n2) * N2 + h2 + k2] = c;       // Zim -> im
+        }
+    for (int n2 = 0; n2 < N2; ++n2)
+        for (int k1 = 0; k1 < N1; ++k1) {
+            const double a = two_pi * (double)(n2 * k1) / (double)N;
+            tw[((size_t)n2 * N1 + k1) * 2] = (float)std::cos(a);
+            tw[((size_t)n2 * N1 + k1) * 2 + 1] = (float)std::sin(a);
+        }
+}
+
+void mel_pack_bands(const float* fb, int nb, int n_mels, MelBands& m) {
+    std::vector<int>&st = m.start, &ln = m.len, &of = m.off;
+    std::vector<float>& packed = m.w;
+    st.assign(n_mels, 0);
+    ln.assign(n_mels, 0);
+    of.assign(n_mels, 0);
+    packed.clear();
+    for (int q = 0; q < n_mels; ++q) {
+        int first = -1, last = -1;
+        for (int j = 0; j < nb; ++j)
+            if (fb[(size_t)j * n_mels + q] != 0.f) {
+                if (first < 0) first = j;
+                last = j;
+            }
+        st[q] = first < 0 ? 0 : first;
+        ln[q] = first < 0 ? 0 : last - first + 1;
+        of[q] = (int)packed.size();
+        for (int j = 0; j < ln[q]; ++j) packed.push_back(fb[(size_t)(st[q] + j) * n_mels + q]);
+    }
 }
 
 }  // namespace l3

@@ -295,6 +295,25 @@ void dft_fused(const float* audio, const float* win, const float* b1, const floa
 void spec_to_features(const float* spec, const float* melw, const int* mel_start, const int* mel_len,
                       const int* mel_off, float* out, int B, const FrontendCfg& c, hipStream_t s, const float* nyq = nullptr);
 void db_normalize(float* x, float* smax, int B, int64_t per_sample, int batch_scope, hipStream_t s);
+// Host-side builders of what the front-end kernels read (frontend.hip), shared by the engine and the operator entry points.
+// frontend_cfg: the geometry of T samples framed 'same' (TensorFlow's padding) or 'valid' and every derived field; folded and
+// factored stay 0 (the engine decides them from the kernels it holds, rebuild_consts).
+FrontendCfg frontend_cfg(int T, int n_dft, int n_hop, bool same, int n_mels, int sqrt_out, int db, int loglambda);
+// librosa filters.mel (htk, norm 1) as kapre builds it: freq2mel (n_fft / 2 + 1, n_mels)
+void host_mel_basis(int sr, int n_fft, int n_mels, std::vector<float>& freq2mel);
+// the factored DFT's tables: the periodic Hann window (n_dft), b1 [N1][re k1 (N1) | im k1 (N1)], b2 [re n2 (N2); im n2 (N2)][re k2
+// (N2 / 2) | im k2 (N2 / 2)] and the twiddles tw [N2][N1] pairs (cos, sin) of 2 pi n2 k1 / n_dft
+struct DftTables {
+    std::vector<float> win, b1, b2, tw;
+};
+void dft_factor_tables(int n_dft, int N1, int N2, DftTables& t);
+// a filterbank fb (nb, n_mels) as bands: filter m = w[off[m] .. off[m] + len[m]) on the bins start[m] ..., first to last nonzero
+// weight (an empty filter: start 0, len 0)
+struct MelBands {
+    std::vector<int> start, len, off;
+    std::vector<float> w;
+};
+void mel_pack_bands(const float* fb, int nb, int n_mels, MelBands& m);
 
 // frames of whole clips (clips.hip; data/usc/features.py:276-300): out row r (T floats) = samples[start_r + j] where
 // lo_r <= start_r + j < hi_r, else 0; table = rows x {start, lo, hi}; rows >= n_real are zeroed

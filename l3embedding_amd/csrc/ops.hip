@@ -968,6 +968,259 @@ int l3_op_frontend(int device, int model_type, const float* audio, int n, int db
 
 }  // extern "C"
 
+// ---- the audio front-end's kernels one by one (frontend.hip; tests/frontend_ref.py) -------------------------------------------------
+// Every output buffer is NaN before the launch and has a guard of a sentinel behind it that must come back untouched.
+namespace {
+constexpr size_t FE_GUARD = 4096;
+constexpr float FE_SENTINEL = -12345.f;
+
+struct FeOut {
+    float* d = nullptr;
+    size_t n = 0;
+    const char* what = "";
+};
+
+// the kernels' outputs of one front-end operator
+struct FeBufs {
+    Scope& sc;
+    std::vector<FeOut> outs;
+    explicit FeBufs(Scope& s) : sc(s) {}
+    // `count` floats, NaN (or the `count` floats at init: an in-place operand), and the guard
+    float* fresh(size_t count, const char* what, const float* init = nullptr) {
+        const uint32_t nan_bits = 0x7fc00000u;
+        uint32_t sentinel_bits;
+        memcpy(&sentinel_bits, &FE_SENTINEL, sizeof sentinel_bits);
+        float* p = sc.alloc<float>(count + FE_GUARD);
+        if (!p) return nullptr;
+        if (init) {
+            if (count && hipMemcpy(p, init, count * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) sc.ok = false;
+        } else if (count && hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p), (int)nan_bits, count) != hipSuccess) {
+            sc.ok = false;
+        }
+        if (hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p + count), (int)sentinel_bits, FE_GUARD) != hipSuccess) sc.ok = false;
+        outs.push_back({p, count, what});
+        return p;
+    }
+    // after the launches: waits, then every guard
+    int check(const char* name) {
+        std::vector<float> g(FE_GUARD);
+        for (const FeOut& o : outs) {
+            sc.get(g.data(), o.d + o.n, FE_GUARD);
+            if (!sc.ok) return L3_EHIP;
+            for (size_t i = 0; i < FE_GUARD; ++i)
+                if (g[i] != FE_SENTINEL)
+                    return fail(L3_EINVAL, std::string(name) + ": float " + std::to_string(i) + " of the guard behind " + o.what + " changed");
+        }
+        return L3_OK;
+    }
+};
+
+// the geometry of an operator's call: the frames must stay inside int sample indices and the outputs inside 2^31 floats
+bool fe_geometry_ok(int B, int T, int n_dft, int n_hop, int pad_left, int n_frames) {
+    if (B < 1 || T < 1 || n_dft < 32 || n_dft % 32 != 0 || n_dft > 8192 || n_hop < 1 || pad_left < 0 || n_frames < 1) return false;
+    if ((int64_t)(n_frames - 1) * n_hop + n_dft + pad_left >= (int64_t)1 << 31) return false;
+    if ((int64_t)B * T >= (int64_t)1 << 31) return false;
+    return (int64_t)B * n_frames * (2 * n_dft) < (int64_t)1 << 31;
+}
+
+FrontendCfg fe_cfg(int T, int n_dft, int n_hop, int pad_left, int n_frames, int n_mels, int flags) {
+    FrontendCfg c = frontend_cfg(T, n_dft, n_hop, false, n_mels, flags & 1, (flags >> 1) & 1, (flags >> 2) & 1);
+    c.pad_left = pad_left;
+    c.n_frames = n_frames;
+    return c;
+}
+
+// the filterbank an operator runs with, as the engine would pack it: the caller's (nb, n_mels), or the stock one
+void fe_bands(const float* freq2mel, int n_dft, int n_mels, MelBands& m) {
+    std::vector<float> stock;
+    if (!freq2mel) {
+        host_mel_basis(48000, n_dft, n_mels, stock);
+        freq2mel = stock.data();
+    }
+    mel_pack_bands(freq2mel, n_dft / 2 + 1, n_mels, m);
+}
+
+struct FeDevBands {
+    float* w = nullptr;
+    int *start = nullptr, *len = nullptr, *off = nullptr;
+    void put(Scope& sc, const MelBands& m) {
+        w = sc.put(m.w.data(), m.w.size());
+        start = sc.put(m.start.data(), m.start.size());
+        len = sc.put(m.len.data(), m.len.size());
+        off = sc.put(m.off.data(), m.off.size());
+    }
+};
+}  // namespace
+
+extern "C" {
+
+int l3_frontend_cfg(int t, int n_dft, int n_hop, int same, int n_mels, int32_t* cfg) {
+    if (!cfg || t < 1 || n_dft < 2 || n_hop < 1 || n_mels < 0 || (!same && t < n_dft))
+        return fail(L3_EINVAL, "l3_frontend_cfg: NULL pointer, an empty shape or 'valid' framing of fewer samples than one frame");
+    const FrontendCfg f = frontend_cfg(t, n_dft, n_hop, same != 0, n_mels, 0, 0, 0);
+    const int32_t v[L3_FRONTEND_CFG_FIELDS] = {f.n_frames, f.pad_left, f.n_freq, f.ncols_pad, f.ke, f.ko, f.nc, f.N1, f.N2};
+    memcpy(cfg, v, sizeof v);
+    return L3_OK;
+}
+
+int l3_frontend_tables(const float* freq2mel, int n_mels, float* win, float* b1, float* b2, float* tw, int32_t* mel_start,
+                       int32_t* mel_len, int32_t* mel_off, float* melw, int64_t melw_cap, int64_t* n_melw) {
+    const int N = 2048, N1 = 32, N2 = 64;
+    if (!win || !b1 || !b2 || !tw || n_mels < 0 || (n_mels > 0 && (!mel_start || !mel_len || !mel_off || !melw || !n_melw || melw_cap < 0)))
+        return fail(L3_EINVAL, "l3_frontend_tables: NULL pointer or a negative count");
+    DftTables t;
+    dft_factor_tables(N, N1, N2, t);
+    memcpy(win, t.win.data(), t.win.size() * 4);
+    memcpy(b1, t.b1.data(), t.b1.size() * 4);
+    memcpy(b2, t.b2.data(), t.b2.size() * 4);
+    memcpy(tw, t.tw.data(), t.tw.size() * 4);
+    if (n_mels == 0) return L3_OK;
+    MelBands m;
+    fe_bands(freq2mel, N, n_mels, m);
+    *n_melw = (int64_t)m.w.size();
+    if ((int64_t)m.w.size() > melw_cap) return fail(L3_EINVAL, "l3_frontend_tables: the packed bands hold more weights than melw_cap");
+    memcpy(mel_start, m.start.data(), (size_t)n_mels * 4);
+    memcpy(mel_len, m.len.data(), (size_t)n_mels * 4);
+    memcpy(mel_off, m.off.data(), (size_t)n_mels * 4);
+    if (!m.w.empty()) memcpy(melw, m.w.data(), m.w.size() * 4);
+    return L3_OK;
+}
+
+int l3_op_frontend_frames(int device, const float* audio, int b, int t, int n_dft, int n_hop, int pad_left, int n_frames,
+                          float* frames, float* fe, float* fo, float* a1) {
+    const char* name = "l3_op_frontend_frames";
+    if (!audio || !frames || !fe || !fo || !fe_geometry_ok(b, t, n_dft, n_hop, pad_left, n_frames) || (a1 && n_dft != 2048))
+        return fail(L3_EINVAL, std::string(name) + ": NULL pointer, a shape outside the kernels' index range, or a1 asked for n_dft != 2048");
+    const FrontendCfg c = fe_cfg(t, n_dft, n_hop, pad_left, n_frames, 0, 0);
+    const size_t rows = (size_t)b * n_frames;
+    Scope sc(device);
+    if (!sc.ok) return fail(L3_EHIP, no_gpu_message(name, device));
+    FeBufs out(sc);
+    float* d_audio = sc.put(audio, (size_t)b * t);
+    float* d_frames = out.fresh(rows * n_dft, "frames");
+    float* d_fe = out.fresh(rows * c.ke, "fe");
+    float* d_fo = out.fresh(rows * c.ko, "fo");
+    float *d_a1 = nullptr, *d_win = nullptr;
+    if (a1) {
+        DftTables tb;
+        dft_factor_tables(n_dft, c.N1, c.N2, tb);
+        d_win = sc.put(tb.win.data(), tb.win.size());
+        d_a1 = out.fresh(rows * n_dft, "a1");
+    }
+    if (!sc.ok) return L3_ENOMEM;
+    frame_audio(d_audio, d_frames, b, t, c, sc.s);
+    frame_audio_folded(d_audio, d_fe, d_fo, b, t, c, sc.s);
+    if (a1) dft_pack_frames(d_audio, d_win, d_a1, b, t, c, sc.s);
+    if (const int rc = out.check(name)) return rc;
+    sc.get(frames, d_frames, rows * n_dft);
+    sc.get(fe, d_fe, rows * c.ke);
+    sc.get(fo, d_fo, rows * c.ko);
+    if (a1) sc.get(a1, d_a1, rows * n_dft);
+    return sc.status();
+}
+
+int l3_op_dft_twiddle(int device, const float* y, int frames, float* a2, float* nyq) {
+    const char* name = "l3_op_dft_twiddle";
+    if (!y || !a2 || !nyq || frames < 1 || (int64_t)frames * 4096 >= (int64_t)1 << 31)
+        return fail(L3_EINVAL, std::string(name) + ": NULL pointer or a frame count outside 1 .. 2^19 - 1");
+    const FrontendCfg c = fe_cfg(2048, 2048, 1, 0, 1, 0, 0);
+    const size_t n = (size_t)frames * 2 * c.n_dft;
+    Scope sc(device);
+    if (!sc.ok) return fail(L3_EHIP, no_gpu_message(name, device));
+    FeBufs out(sc);
+    DftTables tb;
+    dft_factor_tables(c.n_dft, c.N1, c.N2, tb);
+    float* d_y = sc.put(y, n);
+    float* d_tw = sc.put(tb.tw.data(), tb.tw.size());
+    float* d_a2 = out.fresh(n, "a2");
+    float* d_nyq = out.fresh((size_t)frames, "nyq");
+    if (!sc.ok) return L3_ENOMEM;
+    dft_twiddle(d_y, d_tw, d_a2, d_nyq, frames, c, sc.s);
+    if (const int rc = out.check(name)) return rc;
+    sc.get(a2, d_a2, n);
+    sc.get(nyq, d_nyq, (size_t)frames);
+    return sc.status();
+}
+
+int l3_op_spec_to_features(int device, int layout, const float* spec, const float* nyq, int b, int n_frames, int n_dft, int n_mels,
+                           const float* freq2mel, int flags, float* out_feat) {
+    const char* name = "l3_op_spec_to_features";
+    if (!spec || !out_feat || layout < L3_SPEC_UNFOLDED || layout > L3_SPEC_FACTORED || b < 1 || n_frames < 1 || n_mels < 0 ||
+        n_mels > 65536 || flags < 0 || flags > 7 || !fe_geometry_ok(b, n_dft, n_dft, 1, 0, n_frames) ||
+        (layout == L3_SPEC_FACTORED && (n_dft != 2048 || !nyq)))
+        return fail(L3_EINVAL, std::string(name) + ": NULL pointer, an unknown layout or flag, an empty shape, or the factored layout without "
+                                                   "n_dft = 2048 and the Nyquist bins");
+    FrontendCfg c = fe_cfg(n_dft, n_dft, 1, 0, n_frames, n_mels, flags);
+    c.folded = layout == L3_SPEC_FOLDED;
+    c.factored = layout == L3_SPEC_FACTORED;
+    const size_t rows = (size_t)b * n_frames, F = n_mels ? (size_t)n_mels : (size_t)c.n_freq;
+    const size_t n_spec = layout == L3_SPEC_UNFOLDED ? rows * c.ncols_pad : layout == L3_SPEC_FOLDED ? 2 * rows * c.nc : rows * n_dft;
+    if ((int64_t)rows * (int64_t)F >= (int64_t)1 << 31) return fail(L3_EINVAL, std::string(name) + ": more than 2^31 outputs");
+    MelBands m;
+    if (n_mels) fe_bands(freq2mel, n_dft, n_mels, m);
+    Scope sc(device);
+    if (!sc.ok) return fail(L3_EHIP, no_gpu_message(name, device));
+    FeBufs out(sc);
+    float* d_spec = sc.put(spec, n_spec);
+    float* d_nyq = layout == L3_SPEC_FACTORED ? sc.put(nyq, rows) : nullptr;
+    FeDevBands db;
+    if (n_mels) db.put(sc, m);
+    float* d_out = out.fresh(rows * F, "the features");
+    if (!sc.ok) return L3_ENOMEM;
+    spec_to_features(d_spec, db.w, db.start, db.len, db.off, d_out, b, c, sc.s, d_nyq);
+    if (const int rc = out.check(name)) return rc;
+    sc.get(out_feat, d_out, rows * F);
+    return sc.status();
+}
+
+int l3_op_dft_fused(int device, const float* audio, int b, int t, int n_hop, int pad_left, int n_frames, int n_mels,
+                    const float* freq2mel, int flags, float* out_feat) {
+    const char* name = "l3_op_dft_fused";
+    if (!audio || !out_feat || n_mels < 1 || n_mels > 65536 || flags < 0 || flags > 7 ||
+        !fe_geometry_ok(b, t, 2048, n_hop, pad_left, n_frames) || (int64_t)b * n_frames * n_mels >= (int64_t)1 << 31)
+        return fail(L3_EINVAL, std::string(name) + ": NULL pointer, no filter, an unknown flag or a shape outside the kernel's index range");
+    FrontendCfg c = fe_cfg(t, 2048, n_hop, pad_left, n_frames, n_mels, flags);
+    c.factored = 1;
+    const size_t rows = (size_t)b * n_frames;
+    MelBands m;
+    fe_bands(freq2mel, c.n_dft, n_mels, m);
+    DftTables tb;
+    dft_factor_tables(c.n_dft, c.N1, c.N2, tb);
+    Scope sc(device);
+    if (!sc.ok) return fail(L3_EHIP, no_gpu_message(name, device));
+    FeBufs out(sc);
+    float* d_audio = sc.put(audio, (size_t)b * t);
+    float *d_win = sc.put(tb.win.data(), tb.win.size()), *d_b1 = sc.put(tb.b1.data(), tb.b1.size());
+    float *d_b2 = sc.put(tb.b2.data(), tb.b2.size()), *d_tw = sc.put(tb.tw.data(), tb.tw.size());
+    FeDevBands db;
+    db.put(sc, m);
+    float* d_out = out.fresh(rows * n_mels, "the features");
+    if (!sc.ok) return L3_ENOMEM;
+    dft_fused(d_audio, d_win, d_b1, d_b2, d_tw, db.w, db.start, db.len, db.off, d_out, b, t, c, sc.s);
+    if (const int rc = out.check(name)) return rc;
+    sc.get(out_feat, d_out, rows * n_mels);
+    return sc.status();
+}
+
+int l3_op_db_normalize(int device, float* x, int b, int64_t per_sample, int batch_scope) {
+    const char* name = "l3_op_db_normalize";
+    if (!x || b < 1 || per_sample < 1 || (batch_scope != 0 && batch_scope != 1) || (int64_t)b * per_sample >= (int64_t)1 << 31)
+        return fail(L3_EINVAL, std::string(name) + ": NULL pointer, an empty shape, a scope outside 0..1 or more than 2^31 values");
+    const size_t n = (size_t)b * per_sample;
+    Scope sc(device);
+    if (!sc.ok) return fail(L3_EHIP, no_gpu_message(name, device));
+    FeBufs out(sc);
+    float* d_x = out.fresh(n, "x", x);
+    float* d_max = out.fresh((size_t)b, "the maxima");
+    if (!sc.ok) return L3_ENOMEM;
+    db_normalize(d_x, d_max, b, per_sample, batch_scope, sc.s);
+    if (const int rc = out.check(name)) return rc;
+    sc.get(x, d_x, n);
+    return sc.status();
+}
+
+}  // extern "C"
+
 // ---- MLP classifier operators (mlp.hip; classifier/train.py:230-257) ---------------------------------------------------------
 namespace {
 int mlp_op_check(const char* name, int device, bool ptrs_ok, int rows, int K, int N, const int32_t* idx, int64_t n_x) {
