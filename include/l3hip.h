@@ -66,6 +66,18 @@ typedef struct l3_engine l3_engine;
 #define L3_DP_MOVING_REPLICAS 0
 #define L3_DP_MOVING_RANK_LOCAL 1
 
+/* The form of the audio front-end, fixed at l3_create.
+ *   L3_FRONTEND_KAPRE (default)  the kapre layer the models were trained with (audio_model.py:39-43,149-151,257-260,367-369)
+ *   L3_FRONTEND_MINISPEC         the spectrogram of the deployed pipeline, notebooks/pimodel.ipynb cell 12: every frame centred
+ *                                (n_dft / 2 zeros on both sides, 199 frames for all three models), the mel filterbank applied to
+ *                                the MAGNITUDE, dB = 10 log10(max(v^2, 1e-10)) with v = mel(|X|) or |X|, minus the sample's
+ *                                maximum, clipped at -80.  Only for cnn_L3_kapredbinputbn, cnn_L3_melspec1 and cnn_L3_melspec2,
+ *                                the models notebooks/extract_*_models_from_avc_models.ipynb convert; refused with
+ *                                db_max_scope = 1.  Such an engine is for inference: every call that computes gradients or
+ *                                updates weights returns L3_EINVAL. */
+#define L3_FRONTEND_KAPRE 0
+#define L3_FRONTEND_MINISPEC 1
+
 typedef struct l3_config {
     int32_t struct_size;     /* sizeof(l3_config) */
     int32_t model_type;      /* L3_MODEL_* */
@@ -89,6 +101,8 @@ typedef struct l3_config {
     void *stream;            /* hipStream_t to launch on, NULL => engine-owned stream */
     int32_t fp32_conv;       /* L3_FP32_CONV_*: see above (ignored by the bf16 engine's 14 layers) */
     int32_t dp_moving;       /* L3_DP_MOVING_*: see above (was reserved0; 0 keeps the struct compatible) */
+    int32_t frontend;        /* L3_FRONTEND_*: see above.  A caller whose struct_size ends before this field gets
+                                L3_FRONTEND_KAPRE */
 } l3_config;
 
 /* MODELS[model_type](num_gpus=...) -- model.py:184-195,307-313; train.py:267.
@@ -474,6 +488,9 @@ int l3_op_maxpool_fwd(int device, const float *x, float *y, int n, int h, int wd
 int l3_op_maxpool_bwd(int device, const float *x, const float *dy, float *dx, int n, int h,
                       int wd, int c, int ph, int pw, int sh, int sw, int same);
 int l3_op_frontend(int device, int model_type, const float *audio, int n, int db_max_scope, float *out);
+/* l3_op_frontend with the front-end form (L3_FRONTEND_*; per-sample maximum): L3_FRONTEND_MINISPEC is the spectrogram of
+ * notebooks/pimodel.ipynb cell 12, out (n, F, 199). */
+int l3_op_frontend_form(int device, int model_type, int frontend, const float *audio, int n, float *out);
 /* The front-end's kernels one by one (csrc/frontend.hip; tests/frontend_ref.py).  Every output buffer is NaN before the launch and
  * has a guard behind it that must come back untouched (L3_EINVAL otherwise); shapes the kernels cannot index are L3_EINVAL.
  *
@@ -950,6 +967,27 @@ int l3_embed_audio_clips_resampled_dev(l3_engine *e, const float *native, int64_
 /* l3_embed_vision_frames likewise: rows [row0, row0 + n_frames) of dst, the bits `out` receives; dst is checked before the table */
 int l3_embed_vision_frames_dev(l3_engine *e, const uint8_t *pixels, int64_t n_bytes, const int64_t *table, int64_t n_frames,
                                int pool_h, int pool_w, l3_feat *dst, int64_t row0);
+
+/* ---- Spectrograms out, spectrograms in --------------------------------------------------------------------------------
+ * The "spec model" of notebooks/extract_spectrogram_models_from_avc_models.ipynb is the audio tower without its front-end layer: it
+ * takes a spectrogram (F, frames, 1).  notebooks/pimodel.ipynb cell 12 computes that spectrogram per second and calls the spec
+ * model's predict.  Here the front-end's output tensor is the interface: the engine exports it and accepts it.
+ * l3_spectrogram_shape: rows = F (n_mels, or n_dft / 2 + 1 for the linear model) and frames = the frame count of the engine's
+ * front-end output -- the spec model's input_shape[1:3] (extract_spectrogram_models cell that builds the Input layer). */
+int l3_spectrogram_shape(const l3_engine *e, int64_t *rows, int64_t *frames);
+/* The spectrogram pimodel.ipynb cell 12 computes for every second (an L3_FRONTEND_MINISPEC engine), or the one the model saw in
+ * training (an L3_FRONTEND_KAPRE engine): samples, table and their validation as l3_embed_audio_frames; every engine batch is
+ * gathered on the device and run through the front-end, and the front-end tensor of its real rows goes to
+ * out (n_frames, F, frames) float32.  n_frames == 0 is L3_OK. */
+int l3_audio_spectrograms(l3_engine *e, const float *samples, int64_t n_samples, const int64_t *table, int64_t n_frames, float *out);
+/* The spec model's predict (pimodel.ipynb cell 12, `model.predict(spectrogram)`): spec (n, F, frames) float32 host rows go straight
+ * into the front-end's output tensor (the rows behind a partial last batch zeroed), the front-end does not run, and the tower and
+ * the pooling run as in l3_embed_audio: out (n, D).  Fed with what l3_audio_spectrograms of the same engine returned, the result
+ * equals l3_embed_audio_frames bit for bit.  Both dtypes: the front-end's output is float32 in the bf16 engine too.
+ * _dev: rows [row0, row0 + n) of dst, with the conventions and checks of l3_embed_audio_frames_dev.  Argument errors are reported
+ * before anything is uploaded. */
+int l3_embed_audio_spec(l3_engine *e, const float *spec, int64_t n, int pool_h, int pool_w, float *out);
+int l3_embed_audio_spec_dev(l3_engine *e, const float *spec, int64_t n, int pool_h, int pool_w, l3_feat *dst, int64_t row0);
 
 /* ---- A group of MLP classifiers (the learning_rate x weight_decay search of classifier/train.py:638-651) ---------------------------
  * n_members models of one shape (D, C, batch) trained on ONE resident data set in the same launches: an epoch's step is seven

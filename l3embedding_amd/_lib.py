@@ -24,6 +24,7 @@ FAMILIES = ('conv_fwd', 'conv_dgrad', 'conv_wgrad', 'elementwise', 'frontend', '
 DTYPES = {'f32': 0, 'fp32': 0, 'float32': 0, 'bf16': 1}
 FP32_CONV = {'f4x4': 0, 'f2x2': 1, 'f2x2_bf16x6': 2}        # L3_FP32_CONV_*: Winograd F(4x4,3x3) (default, fastest) / F(2x2,3x3) (tightest parity)
 DP_MOVING = {'replicas': 0, 'rank_local': 1}       # l3_config.dp_moving (include/l3hip.h L3_DP_MOVING_*)
+FRONTENDS = {'kapre': 0, 'minispec': 1}            # l3_config.frontend (include/l3hip.h L3_FRONTEND_*)
 OP_DTYPES = dict(DTYPES, bf16_stored=2, bf16_stored_out=3)     # L3_OP_BF16_STORED: conv operator entry points only
 
 
@@ -41,6 +42,12 @@ class L3Config(C.Structure):
         ('fp32_conv', C.c_int32),
         ('dp_moving', C.c_int32),
     ]
+
+
+class L3Config2(L3Config):
+    """`struct l3_config` of include/l3hip.h as it is now: L3Config, the struct as it was before the front-end form (a
+    struct_size the library still accepts, and gives the kapre form), and the field added at its end."""
+    _fields_ = [('frontend', C.c_int32)]
 
 
 class L3Error(RuntimeError):
@@ -158,6 +165,11 @@ SIGNATURES = {
     'l3_op_maxpool_fwd': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 9),
     'l3_op_maxpool_bwd': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9),
     'l3_op_frontend': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'l3_op_frontend_form': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    'l3_spectrogram_shape': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_audio_spectrograms': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_embed_audio_spec': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    'l3_embed_audio_spec_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
     'l3_frontend_cfg': (C.c_int, [C.c_int] * 5 + [C.c_void_p]),
     'l3_frontend_tables': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int64, C.POINTER(C.c_int64)]),
     'l3_op_frontend_frames': (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4),
@@ -380,14 +392,15 @@ class Engine(object):
     """Thin RAII wrapper over an l3_engine handle."""
 
     def __init__(self, model_type, batch, device=0, global_batch=0, db_max_scope='sample',
-                 bn_zero_debias=True, seed=20180123, stream=None, dtype='f32', fp32_conv='f4x4', dp_moving='replicas'):
+                 bn_zero_debias=True, seed=20180123, stream=None, dtype='f32', fp32_conv='f4x4', dp_moving='replicas',
+                 frontend='kapre'):
         if model_type not in MODEL_IDS:
             raise ValueError('Invalid model type: "{}"'.format(model_type))
         self.lib = load()
         self.model_type = model_type
         self.batch = int(batch)
-        cfg = L3Config()
-        cfg.struct_size = C.sizeof(L3Config)
+        cfg = L3Config2()
+        cfg.struct_size = C.sizeof(L3Config2)
         cfg.model_type = MODEL_IDS[model_type]
         cfg.batch = int(batch)
         cfg.global_batch = int(global_batch)
@@ -407,6 +420,10 @@ class Engine(object):
             raise ValueError('dp_moving must be one of %s' % sorted(DP_MOVING))
         cfg.dp_moving = DP_MOVING[dp_moving]
         self.dp_moving = dp_moving
+        if frontend not in FRONTENDS:
+            raise ValueError('frontend must be one of %s' % sorted(FRONTENDS))
+        cfg.frontend = FRONTENDS[frontend]
+        self.frontend = frontend
         h = C.c_void_p()
         rc = self.lib.l3_create(C.byref(cfg), int(seed), C.byref(h))
         check(rc, None)
@@ -724,6 +741,46 @@ class Engine(object):
               self.h)
         return out
 
+    def spectrogram_shape(self):
+        """l3_spectrogram_shape: (F, frames) of the front-end's output, the spec model's input."""
+        r, f = C.c_int64(), C.c_int64()
+        check(self.lib.l3_spectrogram_shape(self.h, C.byref(r), C.byref(f)), self.h)
+        return r.value, f.value
+
+    def audio_spectrograms(self, samples, table):
+        """l3_audio_spectrograms: samples and table as embed_audio_frames' -> (n_frames, F, frames) float32, the front-end's
+        output of every frame (of the engine's form: 'minispec' the deployed pipeline's, 'kapre' the training-time one)."""
+        s = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 3)
+        if s.size == 0:
+            s = np.zeros(1, np.float32)[:0]
+        out = np.empty((t.shape[0],) + self.spectrogram_shape(), np.float32)
+        check(self.lib.l3_audio_spectrograms(self.h, _ptr(s), s.size, _ptr(t), t.shape[0], _ptr(out)), self.h)
+        return out
+
+    def embed_audio_spec(self, spec, pool, out=None, dst=None, row0=0):
+        """l3_embed_audio_spec: spec (n, F, frames) float32, the front-end's output -> (n, D) embeddings; the front-end does
+        not run.  out, dst, row0: as embed_audio_frames' (l3_embed_audio_spec_dev)."""
+        x = np.ascontiguousarray(spec, dtype=np.float32)
+        shape = self.spectrogram_shape()
+        if x.ndim == 4 and x.shape[3] == 1:
+            x = x.reshape(x.shape[:3])
+        if x.ndim != 3 or x.shape[1:] != shape:
+            raise ValueError('spec must have shape (n, %d, %d) or (n, %d, %d, 1), not %s' % (shape + shape + (x.shape,)))
+        n = x.shape[0]
+        if dst is not None:
+            if out is not None:
+                raise ValueError('give out or dst, not both')
+            check(self.lib.l3_embed_audio_spec_dev(self.h, _ptr(x), n, pool[0], pool[1], dst.h, int(row0)), self.h)
+            return dst
+        d = self.lib.l3_embed_dim(self.h, 0, pool[0], pool[1])
+        if out is None:
+            out = np.empty((n, max(d, 0)), np.float32)
+        elif out.dtype != np.float32 or not out.flags['C_CONTIGUOUS'] or out.shape != (n, d):
+            raise ValueError('out must be a C-contiguous float32 array of shape %s' % ((n, d),))
+        check(self.lib.l3_embed_audio_spec(self.h, _ptr(x), n, pool[0], pool[1], _ptr(out)), self.h)
+        return out
+
     def embed_audio_clips_resampled(self, native, clips, half_window, num_table, n_samples, table, pool, out=None, dst=None,
                                     row0=0):
         """l3_embed_audio_clips_resampled: native (n,) float32 (clips at their own rates back to back), clips (n_clips, 6) int64
@@ -1038,6 +1095,20 @@ def op_frontend(model_type, audio, db_max_scope='sample', device=0):
              'cnn_L3_melspec1': (128, 199), 'cnn_L3_melspec2': (256, 199)}[model_type]
     out = np.empty((n, probe[0], probe[1], 1), np.float32)
     check(lib.l3_op_frontend(device, MODEL_IDS[model_type], _ptr(a), n, 0 if db_max_scope == 'sample' else 1, _ptr(out)))
+    return out
+
+
+def op_frontend_form(model_type, audio, frontend='minispec', device=0):
+    """l3_op_frontend_form: the front-end of the given form on audio (n, 48000) -> (n, F, frames, 1), per-sample maximum."""
+    lib = load()
+    a = _f32(audio)
+    n = a.shape[0]
+    f, frames = {'cnn_L3_orig': (257, 197), 'tiny_L3': (257, 198), 'cnn_L3_kapredbinputbn': (257, 197),
+                 'cnn_L3_melspec1': (128, 199), 'cnn_L3_melspec2': (256, 199)}[model_type]
+    if frontend == 'minispec':
+        frames = 199
+    out = np.empty((n, f, frames, 1), np.float32)
+    check(lib.l3_op_frontend_form(device, MODEL_IDS[model_type], FRONTENDS[frontend], _ptr(a), n, _ptr(out)))
     return out
 
 

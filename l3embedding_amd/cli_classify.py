@@ -19,6 +19,9 @@ _OPTIONS = [
     ('--model-type', 'model_type', dict(type=str, required=True), 'L3 model type, e.g. cnn_L3_melspec2'),
     ('--pooling-type', 'pooling_type', dict(type=str, default='original'), "pooling of the audio embedding: 'original' or 'short'"),
     ('--hop-size', 'hop_size', dict(type=float, default=0.1), 'seconds between the 1 s frames of a file'),
+    ('--frontend', 'frontend', dict(type=str, default='kapre', choices=('kapre', 'minispec')),
+     "the audio front-end: 'kapre', the layer the model was trained with, or 'minispec', the spectrogram of pimodel.ipynb cell 12 "
+     '(with --hop-size 1.0 the run is then that notebook from the file to the label)'),
 ]
 
 
@@ -35,7 +38,7 @@ def main(argv=None, out=None):
     logging.basicConfig(level=logging.INFO, stream=sys.stderr)
     from .model import load_embedding
     from .sound import SoundClassifier
-    embedding = load_embedding(args.weights, args.model_type, 'audio', args.pooling_type)
+    embedding = load_embedding(args.weights, args.model_type, 'audio', args.pooling_type, frontend=args.frontend)
     got = SoundClassifier.from_run(embedding, args.model_dir, hop_size=args.hop_size).predict_files(args.files)
     out = out or sys.stdout
     for path, cls, proba in zip(args.files, got['file_predict'], got['file_proba']):

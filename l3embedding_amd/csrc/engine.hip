@@ -565,6 +565,13 @@ int build_ledger(l3_engine* e) {
     // audio front-end
     FrontendCfg& f = e->fcfg;
     f = frontend_cfg(AUDIO_T, e->fe.n_dft, e->fe.n_hop, e->fe.same != 0, e->fe.n_mels, e->fe.sqrt_out, e->fe.db, e->fe.loglambda);
+    if (e->cfg.frontend == L3_FRONTEND_MINISPEC) {
+        // every frame centred on a multiple of the hop, zeros outside the second; the dB of the SQUARED value, so no sqrt
+        // (mel models: the kernels' magnitude form, run_frontend; the linear model: |X|^2 straight into to_db)
+        f.pad_left = f.n_dft / 2;
+        f.n_frames = 1 + AUDIO_T / f.n_hop;
+        f.sqrt_out = 0;
+    }
     const std::string fen = std::string("audio_model/") + e->fe.layer_name;
     add_param(e, fen + "/real_kernels", {f.n_dft, 1, 1, f.n_freq}, false, PK_CONST, &e->p_real);
     add_param(e, fen + "/imag_kernels", {f.n_dft, 1, 1, f.n_freq}, false, PK_CONST, &e->p_imag);
@@ -1088,6 +1095,7 @@ int run_frontend(l3_engine* e) {
     const FrontendCfg& f = e->fcfg;
     const int B = e->B;
     const int M = B * f.n_frames;
+    const bool mag = e->cfg.frontend == L3_FRONTEND_MINISPEC && f.n_mels > 0;      // the filterbank on magnitudes
     if (f.factored) {
         // stock kernels: n_dft = N1 N2 = 32 x 64 -- [pack + window] -> GEMM (K = N1: the length-N1 DFTs over n1) -> twiddles + transpose
         // -> GEMM (K = 2 N2: the length-N2 complex DFTs over n2, bins k2 < N2 / 2) ; 5.2x fewer multiplies than the folded GEMMs
@@ -1099,7 +1107,7 @@ int run_frontend(l3_engine* e) {
             ProfScope ps(e, F_FRONTEND, 2.0 * M * (double)f.n_dft * 2.0 * f.n_freq + 2.0 * M * (double)f.n_freq * f.n_mels, nullptr,
                          2.0 * m1 * N1 * 2 * N1 + 2.0 * m2 * 2 * N2 * N2);
             dft_fused(e->audio, e->dft_win, e->dft_b1, e->dft_b2, e->dft_tw, e->melw, e->mel_start, e->mel_len, e->mel_off, e->aud.t[0].d, B,
-                      AUDIO_T, f, e->stream);
+                      AUDIO_T, f, e->stream, mag);
             if (f.db) db_normalize(e->aud.t[0].d, e->smax, B, e->aud.t[0].batch_stride, e->cfg.db_max_scope, e->stream);
             return L3_OK;
         }
@@ -1139,7 +1147,7 @@ int run_frontend(l3_engine* e) {
     }
     {
         ProfScope ps(e, F_FRONTEND, f.n_mels ? 2.0 * B * f.n_frames * (double)f.n_freq * f.n_mels : 0.0);
-        spec_to_features(e->spec, e->melw, e->mel_start, e->mel_len, e->mel_off, e->aud.t[0].d, B, f, e->stream, e->dft_nyq);
+        spec_to_features(e->spec, e->melw, e->mel_start, e->mel_len, e->mel_off, e->aud.t[0].d, B, f, e->stream, e->dft_nyq, mag);
         if (f.db) db_normalize(e->aud.t[0].d, e->smax, B, e->aud.t[0].batch_stride, e->cfg.db_max_scope, e->stream);
     }
     return L3_OK;
@@ -1702,10 +1710,32 @@ int l3_build_experiments(void) {
 #endif
 }
 
-int l3_create(const l3_config* cfg, uint64_t seed, l3_engine** out) {
-    if (!cfg || !out || cfg->struct_size != (int32_t)sizeof(l3_config)) {
+int l3_create(const l3_config* cfg_in, uint64_t seed, l3_engine** out) {
+    // the struct as it was before `frontend` was added ends where that field begins: such a caller gets the kapre form
+    constexpr int32_t OLD_CONFIG_SIZE = (int32_t)offsetof(l3_config, frontend);
+    if (!cfg_in || !out || (cfg_in->struct_size != (int32_t)sizeof(l3_config) && cfg_in->struct_size != OLD_CONFIG_SIZE)) {
         g_create_error = "l3_create: bad config (struct_size mismatch)";
         return L3_EINVAL;
+    }
+    l3_config cfg_full{};
+    memcpy(&cfg_full, cfg_in, (size_t)cfg_in->struct_size);
+    if (cfg_in->struct_size == OLD_CONFIG_SIZE) cfg_full.frontend = L3_FRONTEND_KAPRE;
+    cfg_full.struct_size = (int32_t)sizeof(l3_config);
+    const l3_config* cfg = &cfg_full;
+    if (cfg->frontend != L3_FRONTEND_KAPRE && cfg->frontend != L3_FRONTEND_MINISPEC) {
+        g_create_error = "l3_create: frontend must be L3_FRONTEND_KAPRE or L3_FRONTEND_MINISPEC";
+        return L3_EINVAL;
+    }
+    if (cfg->frontend == L3_FRONTEND_MINISPEC) {
+        if (cfg->model_type != L3_MODEL_CNN_L3_KAPREDBINPUTBN && cfg->model_type != L3_MODEL_CNN_L3_MELSPEC1 &&
+            cfg->model_type != L3_MODEL_CNN_L3_MELSPEC2) {
+            g_create_error = "l3_create: L3_FRONTEND_MINISPEC exists for cnn_L3_kapredbinputbn, cnn_L3_melspec1 and cnn_L3_melspec2 only";
+            return L3_EINVAL;
+        }
+        if (cfg->db_max_scope != 0) {
+            g_create_error = "l3_create: L3_FRONTEND_MINISPEC normalises every frame on its own: db_max_scope must be 0";
+            return L3_EINVAL;
+        }
     }
     if (cfg->batch < 1) {
         g_create_error = "l3_create: batch must be >= 1";
@@ -2066,8 +2096,18 @@ int l3_batch_gains(l3_engine* e, double* gains) {
     return L3_OK;
 }
 
+// A minispec engine is the deployed pipeline's (notebooks/pimodel.ipynb): it infers.  Every entry point that computes gradients or
+// updates weights refuses it before it touches anything.
+static int refuse_minispec_training(l3_engine* e, const char* fn) {
+    if (e->cfg.frontend != L3_FRONTEND_MINISPEC) return L3_OK;
+    e->err = std::string(fn) + ": an L3_FRONTEND_MINISPEC engine is for inference; train with L3_FRONTEND_KAPRE";
+    return L3_EINVAL;
+}
+
 int l3_step_forward(l3_engine* e, int training) {
     if (!e) return L3_EINVAL;
+    if (training)
+        if (int rc = refuse_minispec_training(e, "l3_step_forward(training = 1)")) return rc;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     e->bucket_ready = -1;       // a step that was abandoned between a backward bucket and its reduce must not leave its flag to the next
     e->bn_replicas_armed = 0;   // ... nor the replicas' statistics it had gathered: they are armed behind THIS forward or not at all
@@ -2092,6 +2132,8 @@ int l3_step_forward(l3_engine* e, int training) {
 
 int l3_tower_step(l3_engine* e, int tower, int backward) {
     if (!e || (tower != 0 && tower != 1)) return L3_EINVAL;
+    if (backward)
+        if (int rc = refuse_minispec_training(e, "l3_tower_step(backward = 1)")) return rc;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     int rc = e->feed.adopt(BATCH_SINGLE, e->stream, &e->err);      // a staged single batch: in stream order behind the previous step
     if (rc) return rc;
@@ -2114,6 +2156,7 @@ int l3_step_bucket_count(const l3_engine* e) { return e ? (int)e->buckets.size()
 
 int l3_step_backward_bucket(l3_engine* e, int bucket) {
     if (!e) return L3_EINVAL;
+    if (int rc = refuse_minispec_training(e, "l3_step_backward_bucket")) return rc;
     if (!e->fwd_done) {
         e->err = "l3_step_backward_bucket before l3_step_forward";
         return L3_ESTATE;
@@ -2131,6 +2174,7 @@ int l3_step_backward_bucket(l3_engine* e, int bucket) {
 
 int l3_step_update(l3_engine* e, float lr, float grad_scale) {
     if (!e) return L3_EINVAL;
+    if (int rc = refuse_minispec_training(e, "l3_step_update")) return rc;
     if (!e->fwd_done || !e->last_training) {
         e->err = "l3_step_update without a training-mode forward";
         return L3_ESTATE;
@@ -2151,7 +2195,10 @@ int l3_step_update(l3_engine* e, float lr, float grad_scale) {
 }
 
 int l3_step_resident(l3_engine* e, float lr) {
-    int rc = l3_step_forward(e, 1);
+    if (!e) return L3_EINVAL;
+    int rc = refuse_minispec_training(e, "l3_step_resident");
+    if (rc) return rc;
+    rc = l3_step_forward(e, 1);
     if (rc) return rc;
     const int nb = (int)e->buckets.size();
     for (int b = 1; b < nb; ++b)
@@ -2254,6 +2301,7 @@ static int rep_accumulators(l3_engine* e) {
 
 int l3_step_replicas(l3_engine* e, float lr) {
     if (!e) return L3_EINVAL;
+    if (int rc = refuse_minispec_training(e, "l3_step_replicas")) return rc;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     int rc = rep_begin(e, "l3_step_replicas");
     if (rc) return rc;
@@ -2417,6 +2465,7 @@ static int reduce_bucket(l3_engine* e, int k) {
 
 int l3_step_dp(l3_engine* e, float lr) {
     if (!e) return L3_EINVAL;
+    if (int rc = refuse_minispec_training(e, "l3_step_dp")) return rc;
     if (!e->comm) {
         e->err = "l3_step_dp before l3_comm_init";
         return L3_ESTATE;
@@ -2678,6 +2727,7 @@ int l3_forward(l3_engine* e, const float* video, const float* audio, int trainin
 int l3_train_step(l3_engine* e, const float* video, const float* audio, const float* labels, float lr, float* loss,
                   float* acc) {
     if (!e) return L3_EINVAL;
+    if (int rc = refuse_minispec_training(e, "l3_train_step")) return rc;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     int rc = upload_inputs(e, video, audio, labels);
     if (rc) return rc;
@@ -2723,7 +2773,8 @@ int64_t l3_embed_dim(const l3_engine* e, int vision, int pool_h, int pool_w) {
     return (int64_t)ho * wo * t.C;
 }
 
-// Where the input rows of one engine batch come from: the caller's host rows (l3_embed_audio / l3_embed_vision), the clip
+// Where the input rows of one engine batch come from: the caller's host rows (l3_embed_audio / l3_embed_vision), the caller's
+// spectrograms, which take the place of the front-end's output so that the front-end does not run (l3_embed_audio_spec), the clip
 // frames gathered on the device from the samples and frame table l3_embed_audio_frames uploaded, or the windows of raw frames
 // resized on the device from the pixels and plan l3_embed_vision_frames uploaded.
 struct EmbedSource {
@@ -2733,6 +2784,7 @@ struct EmbedSource {
     const uint8_t* pixels = nullptr;      // device (vision only)
     const int64_t* descs = nullptr;       // device, n x IMAGE_DESC
     const int64_t* taps = nullptr;        // device
+    const float* spec = nullptr;          // n rows (F, frames), host memory: the front-end's OUTPUT (audio only; l3_embed_audio_spec)
 };
 
 // Pooled rows stay on the device between two copies to the host; one copy (and one host wait) per call up to this many bytes.
@@ -2788,7 +2840,11 @@ static int embed_rows(l3_engine* e, bool vision, const EmbedSource& src, int64_t
     int64_t f0 = 0;                 // first row the device output buffer holds
     for (int64_t s0 = 0; s0 < n; s0 += B) {
         const int64_t cnt = n - s0 < B ? n - s0 : B;
-        if (src.host) {
+        if (src.spec) {
+            const size_t sper = (size_t)tw.t[0].batch_stride;
+            HIPCHK(e, hipMemcpyAsync(tw.t[0].d, src.spec + (size_t)s0 * sper, (size_t)cnt * sper * 4, hipMemcpyHostToDevice, e->stream));
+            if (cnt < B) HIPCHK(e, hipMemsetAsync(tw.t[0].d + (size_t)cnt * sper, 0, (size_t)(B - cnt) * sper * 4, e->stream));
+        } else if (src.host) {
             HIPCHK(e, hipMemcpyAsync(dst_in, src.host + (size_t)s0 * per, (size_t)cnt * per * 4, hipMemcpyHostToDevice, e->stream));
             if (cnt < B) HIPCHK(e, hipMemsetAsync(dst_in + (size_t)cnt * per, 0, (size_t)(B - cnt) * per * 4, e->stream));
         } else if (src.pixels) {
@@ -2797,7 +2853,7 @@ static int embed_rows(l3_engine* e, bool vision, const EmbedSource& src, int64_t
         } else {
             gather_frames(src.samples, src.table + 3 * s0, dst_in, B, (int)cnt, AUDIO_T, e->stream);
         }
-        if (!vision) {
+        if (!vision && !src.spec) {
             rc = run_frontend(e);
             if (rc) return rc;
         }
@@ -2905,6 +2961,92 @@ int l3_embed_audio_frames_dev(l3_engine* e, const float* samples, int64_t n_samp
     EmbedDest dst;
     dst.dev = true, dst.feat = dst_feat, dst.row0 = row0;
     return embed_frames_to(e, "l3_embed_audio_frames_dev", samples, n_samples, table, n_frames, pool_h, pool_w, dst);
+}
+
+// ---- spectrograms out, spectrograms in ---------------------------------------------------------------------------------
+int l3_spectrogram_shape(const l3_engine* e, int64_t* rows, int64_t* frames) {
+    if (!e) return L3_EINVAL;
+    const Tensor& t = e->aud.t[0];
+    if (rows) *rows = t.H;
+    if (frames) *frames = t.W;
+    return L3_OK;
+}
+
+int l3_audio_spectrograms(l3_engine* e, const float* samples, int64_t n_samples, const int64_t* table, int64_t n_frames, float* out) {
+    if (!e) return L3_EINVAL;
+    const std::string name("l3_audio_spectrograms");
+    if (!samples || !table || !out) {
+        e->err = name + ": samples, table and out must not be NULL";
+        return L3_EINVAL;
+    }
+    if (n_samples < 0 || n_frames < 0) {
+        e->err = name + ": n_samples and n_frames must be >= 0";
+        return L3_EINVAL;
+    }
+    int64_t bad = 0;
+    if (const char* why = frame_table_error(table, n_frames, n_samples, &bad)) {
+        e->err = name + ": frame " + std::to_string(bad) + ": " + why;
+        return L3_EINVAL;
+    }
+    if (n_frames == 0) return L3_OK;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    int rc;
+    if ((rc = dev_grow_t(e, &e->clip_samples, &e->clip_samples_cap, (size_t)n_samples))) return rc;
+    if ((rc = dev_grow_t(e, &e->clip_table, &e->clip_table_cap, (size_t)n_frames * 3))) return rc;
+    if (n_samples > 0)
+        HIPCHK(e, hipMemcpyAsync(e->clip_samples, samples, (size_t)n_samples * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->clip_table, table, (size_t)n_frames * 3 * 8, hipMemcpyHostToDevice, e->stream));
+    const Tensor& t = e->aud.t[0];
+    const size_t sper = (size_t)t.batch_stride;
+    const int B = e->B;
+    for (int64_t s0 = 0; s0 < n_frames; s0 += B) {
+        const int64_t cnt = n_frames - s0 < B ? n_frames - s0 : B;
+        gather_frames(e->clip_samples, e->clip_table + 3 * s0, e->audio, B, (int)cnt, AUDIO_T, e->stream);
+        if ((rc = run_frontend(e))) return rc;
+        HIPCHK(e, hipMemcpyAsync(out + (size_t)s0 * sper, t.d, (size_t)cnt * sper * 4, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIPCHK(e, l3::stream_wait(e->stream));
+    prof_collect(e);
+    return L3_OK;
+}
+
+static int embed_spec_to(l3_engine* e, const char* fn, const float* spec, int64_t n, int pool_h, int pool_w, const EmbedDest& dst) {
+    const std::string name(fn);
+    if (!spec || !(dst.host || dst.feat)) {
+        e->err = name + ": spec and " + (dst.dev ? "dst" : "out") + " must not be NULL";
+        return L3_EINVAL;
+    }
+    if (n < 0) {
+        e->err = name + ": n must be >= 0";
+        return L3_EINVAL;
+    }
+    if (e->aud.t[0].d_bf16) {       // (no engine stores the front-end's output as bfloat16 today; the copy below assumes floats)
+        e->err = name + ": this engine does not store the front-end's output as float32";
+        return L3_EINVAL;
+    }
+    int64_t D = 0;
+    int rc = embed_check(e, false, pool_h, pool_w, &D);
+    if (rc) return rc;
+    if ((rc = embed_dest_check(e, fn, dst, n, D))) return rc;
+    if (n == 0) return L3_OK;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    EmbedSource src;
+    src.spec = spec;
+    return embed_rows(e, false, src, n, pool_h, pool_w, D, dst);
+}
+
+int l3_embed_audio_spec(l3_engine* e, const float* spec, int64_t n, int pool_h, int pool_w, float* out) {
+    if (!e) return L3_EINVAL;
+    EmbedDest dst;
+    dst.host = out;
+    return embed_spec_to(e, "l3_embed_audio_spec", spec, n, pool_h, pool_w, dst);
+}
+
+int l3_embed_audio_spec_dev(l3_engine* e, const float* spec, int64_t n, int pool_h, int pool_w, l3_feat* dst_feat, int64_t row0) {
+    if (!e) return L3_EINVAL;
+    EmbedDest dst;
+    dst.dev = true, dst.feat = dst_feat, dst.row0 = row0;
+    return embed_spec_to(e, "l3_embed_audio_spec_dev", spec, n, pool_h, pool_w, dst);
 }
 
 static int embed_vision_frames_to(l3_engine* e, const char* fn, const uint8_t* pixels, int64_t n_bytes, const int64_t* table,

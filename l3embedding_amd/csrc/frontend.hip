@@ -158,6 +158,9 @@ constexpr int DF_WAVES = 8;
 constexpr int DF_WAVE = DF_Z;
 constexpr size_t DF_LDS_BYTES = (size_t)(DF_TW + 64 + DF_WAVES * DF_WAVE) * sizeof(float);
 
+// MAG (the minispec form): the filterbank sums magnitudes, sqrt(re^2 + im^2) per bin, and the sum is squared before to_db;
+// MAG = false is the kapre form.
+template <bool MAG>
 __global__ __launch_bounds__(64 * DF_WAVES) void dft_fused_kernel(const float* __restrict__ audio, const float* __restrict__ win,
                                                         const float* __restrict__ b1g, const float* __restrict__ b2g,
                                                         const float* __restrict__ twg, const float* __restrict__ melw,
@@ -291,9 +294,9 @@ __global__ __launch_bounds__(64 * DF_WAVES) void dft_fused_kernel(const float* _
         for (int r = 0; r < 16; ++r) {
             const int k1 = 8 * (r >> 2) + 4 * hf + (r & 3);
             const float re = ac2[0][0][r] + ac2[1][0][r], im = ac2[0][1][r] + ac2[1][1][r];
-            P[k1 * 33 + col] = re * re + im * im;
+            P[k1 * 33 + col] = MAG ? sqrtf(re * re + im * im) : re * re + im * im;
         }
-        if (l == 0) P[DF_N1 * 33] = nyq * nyq;
+        if (l == 0) P[DF_N1 * 33] = MAG ? fabsf(nyq) : nyq * nyq;
         // ---- mel projection + sqrt / dB (spec_to_features_kernel's arithmetic on the same P)
         const int F = c.n_mels;
         for (int q = l; q < F; q += 64) {
@@ -303,6 +306,7 @@ __global__ __launch_bounds__(64 * DF_WAVES) void dft_fused_kernel(const float* _
                 const int k = st + i;
                 v = fmaf(k == c.n_dft / 2 ? P[DF_N1 * 33] : P[(k & 31) * 33 + (k >> 5)], melw[of + i], v);
             }
+            if (MAG) v *= v;
             if (c.sqrt_out) v = sqrtf(v);
             if (c.db) v = to_db(v);
             if (c.loglambda) v = to_loglambda(v);
@@ -312,22 +316,30 @@ __global__ __launch_bounds__(64 * DF_WAVES) void dft_fused_kernel(const float* _
 }
 void dft_fused(const float* audio, const float* win, const float* b1, const float* b2, const float* tw, const float* melw,
                const int* mel_start, const int* mel_len, const int* mel_off, float* out, int B, int T, const FrontendCfg& c,
-               hipStream_t s) {
+               hipStream_t s, bool mag) {
     // per device, once: the LDS attribute and the CU count (hipGetDeviceProperties is not a call to make every step)
     static int cus[L3_MAX_DEVICES] = {0};
     int dev = 0;
     (void)hipGetDevice(&dev);
     int& ncu = cus[dev & (L3_MAX_DEVICES - 1)];
     if (ncu == 0) {
-        (void)hipFuncSetAttribute((const void*)dft_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DF_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)dft_fused_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DF_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)dft_fused_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DF_LDS_BYTES);
         hipDeviceProp_t prop;
         ncu = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     const int M = B * c.n_frames, groups = (M + DF_WAVES - 1) / DF_WAVES;
-    hipLaunchKernelGGL(dft_fused_kernel, dim3(groups < ncu ? groups : ncu), dim3(64 * DF_WAVES), DF_LDS_BYTES, s, audio, win, b1, b2, tw, melw,
-                       mel_start, mel_len, mel_off, out, B, T, c);
+    if (mag)
+        hipLaunchKernelGGL(dft_fused_kernel<true>, dim3(groups < ncu ? groups : ncu), dim3(64 * DF_WAVES), DF_LDS_BYTES, s, audio, win, b1, b2,
+                           tw, melw, mel_start, mel_len, mel_off, out, B, T, c);
+    else
+        hipLaunchKernelGGL(dft_fused_kernel<false>, dim3(groups < ncu ? groups : ncu), dim3(64 * DF_WAVES), DF_LDS_BYTES, s, audio, win, b1, b2,
+                           tw, melw, mel_start, mel_len, mel_off, out, B, T, c);
 }
 
+// MAG as in dft_fused_kernel; it applies to a mel front-end only (the linear minispec form is |X|^2 straight into to_db: MAG = false
+// with sqrt_out = 0).
+template <bool MAG>
 __global__ __launch_bounds__(256) void spec_to_features_kernel(const float* spec, const float* melw,
                                                                const int* mel_start, const int* mel_len,
                                                                const int* mel_off, float* out, FrontendCfg c, const float* nyq) {
@@ -341,16 +353,16 @@ __global__ __launch_bounds__(256) void spec_to_features_kernel(const float* spec
         for (int i = threadIdx.x; i < c.N1 * h2; i += 256) {
             const int k1 = i / h2, k2 = i - k1 * h2;
             const float re = xr[k1 * c.N2 + k2], im = xr[k1 * c.N2 + h2 + k2];
-            pw[k1 + c.N1 * k2] = re * re + im * im;
+            pw[k1 + c.N1 * k2] = MAG ? sqrtf(re * re + im * im) : re * re + im * im;
         }
-        if (threadIdx.x == 0) pw[c.n_dft / 2] = nyq[row] * nyq[row];
+        if (threadIdx.x == 0) pw[c.n_dft / 2] = MAG ? fabsf(nyq[row]) : nyq[row] * nyq[row];
     } else {
     // unfolded: one row = [re | im | pad];  folded: all re rows (nc wide), then all im rows
     const float* spr = c.folded ? spec + (size_t)row * c.nc : spec + (size_t)row * c.ncols_pad;
     const float* spi = c.folded ? spec + ((size_t)gridDim.x + row) * c.nc : spr + c.n_freq;
     for (int j = threadIdx.x; j < c.n_freq; j += 256) {
         const float re = spr[j], im = spi[j];
-        pw[j] = re * re + im * im;
+        pw[j] = MAG ? sqrtf(re * re + im * im) : re * re + im * im;
     }
     }
     __syncthreads();
@@ -361,6 +373,7 @@ __global__ __launch_bounds__(256) void spec_to_features_kernel(const float* spec
             const int st = mel_start[q], ln = mel_len[q], of = mel_off[q];
             v = 0.f;
             for (int i = 0; i < ln; ++i) v = fmaf(pw[st + i], melw[of + i], v);
+            if (MAG) v *= v;
         } else {
             v = pw[q];
         }
@@ -371,9 +384,13 @@ __global__ __launch_bounds__(256) void spec_to_features_kernel(const float* spec
     }
 }
 void spec_to_features(const float* spec, const float* melw, const int* mel_start, const int* mel_len,
-                      const int* mel_off, float* out, int B, const FrontendCfg& c, hipStream_t s, const float* nyq) {
-    hipLaunchKernelGGL(spec_to_features_kernel, dim3(B * c.n_frames), dim3(256), c.n_freq * sizeof(float), s,
-                       spec, melw, mel_start, mel_len, mel_off, out, c, nyq);
+                      const int* mel_off, float* out, int B, const FrontendCfg& c, hipStream_t s, const float* nyq, bool mag) {
+    if (mag && c.n_mels)
+        hipLaunchKernelGGL(spec_to_features_kernel<true>, dim3(B * c.n_frames), dim3(256), c.n_freq * sizeof(float), s,
+                           spec, melw, mel_start, mel_len, mel_off, out, c, nyq);
+    else
+        hipLaunchKernelGGL(spec_to_features_kernel<false>, dim3(B * c.n_frames), dim3(256), c.n_freq * sizeof(float), s,
+                           spec, melw, mel_start, mel_len, mel_off, out, c, nyq);
 }
 
 __global__ __launch_bounds__(256) void sample_max_kernel(const float* x, float* smax, int64_t per_sample) {

@@ -290,10 +290,12 @@ void frame_audio(const float* audio, float* frames, int B, int T, const Frontend
 // ... and all of it, mel projection and sqrt / dB included, in one kernel (n_dft = 2048 = 32 x 64, n_mels > 0): audio -> out (B, mels, frames)
 void dft_fused(const float* audio, const float* win, const float* b1, const float* b2, const float* tw, const float* melw,
                const int* mel_start, const int* mel_len, const int* mel_off, float* out, int B, int T, const FrontendCfg& c,
-               hipStream_t s);
+               hipStream_t s, bool mag = false);
+// mag (both kernels): the minispec form -- the filterbank sums magnitudes and the sum is squared (frontend.hip MAG)
 // (factored: spec = x2[(frame * N1 + k1)][re k2 (N2 / 2) | im k2 (N2 / 2)], bin k = k1 + N1 k2, and nyq[frame])
 void spec_to_features(const float* spec, const float* melw, const int* mel_start, const int* mel_len,
-                      const int* mel_off, float* out, int B, const FrontendCfg& c, hipStream_t s, const float* nyq = nullptr);
+                      const int* mel_off, float* out, int B, const FrontendCfg& c, hipStream_t s, const float* nyq = nullptr,
+                      bool mag = false);
 void db_normalize(float* x, float* smax, int B, int64_t per_sample, int batch_scope, hipStream_t s);
 // Host-side builders of what the front-end kernels read (frontend.hip), shared by the engine and the operator entry points.
 // frontend_cfg: the geometry of T samples framed 'same' (TensorFlow's padding) or 'valid' and every derived field; folded and

@@ -966,6 +966,27 @@ int l3_op_frontend(int device, int model_type, const float* audio, int n, int db
     return rc;
 }
 
+int l3_op_frontend_form(int device, int model_type, int frontend, const float* audio, int n, float* out) {
+    // l3_op_frontend with the form: a throw-away engine of batch n, per-sample maximum
+    l3_config cfg{};
+    cfg.struct_size = (int32_t)sizeof(l3_config);
+    cfg.model_type = model_type;
+    cfg.batch = n;
+    cfg.device = device;
+    cfg.bn_zero_debias = 1;
+    cfg.frontend = frontend;
+    l3_engine* e = nullptr;
+    int rc = l3_create(&cfg, 1, &e);
+    if (rc) return rc;
+    rc = l3_upload_batch(e, nullptr, audio, nullptr);
+    if (!rc) rc = l3_step_forward(e, 0);
+    int64_t numel = 0;
+    if (!rc) rc = l3_activation_numel(e, "audio_model/frontend", &numel);
+    if (!rc) rc = l3_get_activation(e, "audio_model/frontend", out, numel);
+    l3_destroy(e);
+    return rc;
+}
+
 }  // extern "C"
 
 // ---- the audio front-end's kernels one by one (frontend.hip; tests/frontend_ref.py) -------------------------------------------------

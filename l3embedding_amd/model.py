@@ -170,9 +170,13 @@ class L3Model(object):
     """An AVC model bound (lazily) to an l3_engine.  `replicas` > 1 marks the model as
     the data-parallel wrapper of training_utils.multi_gpu_model."""
 
-    def __init__(self, model_type, seed=20180123, device=0, db_max_scope='sample', bn_zero_debias=True):
+    def __init__(self, model_type, seed=20180123, device=0, db_max_scope='sample', bn_zero_debias=True, frontend='kapre'):
         if model_type not in MODEL_TYPES:
             raise ValueError('Invalid model type: "{}"'.format(model_type))
+        if frontend not in _lib.FRONTENDS:
+            raise ValueError('frontend must be one of %s' % sorted(_lib.FRONTENDS))
+        # 'kapre': the layer the model was trained with; 'minispec': the deployed pipeline's spectrogram (inference only; DESIGN.md 8p)
+        self.frontend = frontend
         self.model_type = model_type
         self.name = model_type
         self.seed = seed
@@ -216,7 +220,7 @@ class L3Model(object):
         when the size changes (validation_batch_size != train_batch_size, a ragged last batch) the model
         state -- weights, Adam moments and step, BatchNorm debias accumulators -- moves to the engine of
         the new size device-to-device (`l3_copy_state`) instead of being rebuilt from the weights alone."""
-        key = (int(batch), int(global_batch), self.compute_dtype, self.fp32_conv)
+        key = (int(batch), int(global_batch), self.compute_dtype, self.fp32_conv, self.frontend)
         cur = self._engine
         if cur is not None and cur._key == key:
             return cur
@@ -230,7 +234,8 @@ class L3Model(object):
                 stream = self._tstream.cuda_stream
             e = _lib.Engine(self.model_type, key[0], device=self.device, global_batch=key[1],
                             db_max_scope=self.db_max_scope, bn_zero_debias=self.bn_zero_debias, seed=self.seed,
-                            stream=stream, dtype=self.compute_dtype, fp32_conv=self.fp32_conv, dp_moving=self.dp_moving)
+                            stream=stream, dtype=self.compute_dtype, fp32_conv=self.fp32_conv, dp_moving=self.dp_moving,
+                            frontend=self.frontend)
             e._key = key
             e._trainer = None
             lib_tab = [(n, tuple(s), t) for n, s, t in e.param_table()]
@@ -246,6 +251,17 @@ class L3Model(object):
         self._engine = e
         self._host_weights = None
         return e
+
+    def set_frontend(self, frontend):
+        """Switches the front-end form.  The weights stay; the engines, whose geometry depends on the form, are made anew."""
+        if frontend not in _lib.FRONTENDS:
+            raise ValueError('frontend must be one of %s' % sorted(_lib.FRONTENDS))
+        if frontend == self.frontend:
+            return
+        held = OrderedDict(self._engine.get_params()) if self._engine is not None else self._host_weights
+        self._drop_engines()
+        self._host_weights = held
+        self.frontend = frontend
 
     def _drop_engines(self):
         for e in self._engines.values():
@@ -918,6 +934,44 @@ class EmbeddingModel(object):
     IMAGE_CALL_FRAMES = 4096
     IMAGE_CALL_BYTES = 1 << 28
 
+    def spectrograms(self, clips, hop_length, batch_size=32, rates=None):
+        """The front-end's output for every frame predict_clips would embed: (array (n, F, frames, 1) float32, counts), counts[i]
+        the number of frames of clip i, framed as predict_clips frames them.  On a 'minispec' model this is the spectrogram the
+        deployed pipeline computes per second; on a 'kapre' model the one the tower saw in training."""
+        from .features import frame_table
+        if self.embedding_type != 'audio':
+            raise TypeError('spectrograms needs an audio embedding model')
+        if self.base.db_max_scope != 'sample':
+            raise ValueError("spectrograms needs db_max_scope = 'sample': under 'batch' a frame's values depend on its batch")
+        clips = [np.asarray(c, dtype=np.float32).reshape(-1) for c in clips]
+        if rates is not None:
+            from .resample import resample
+            clips = [c if int(r) == 48000 else np.asarray(resample(c, int(r), 48000), np.float32) for c, r in zip(clips, rates)]
+        lengths = np.array([c.size for c in clips], np.int64)
+        table, counts = frame_table(lengths, hop_length)
+        total = int(counts.sum())
+        e = self.base._ensure_engine(self.base._engine.batch if self.base._engine is not None else max(1, min(batch_size, total)))
+        samples = np.concatenate(clips) if clips else np.zeros(0, np.float32)
+        return e.audio_spectrograms(samples, table)[..., None], counts
+
+    def predict_spectrograms(self, spec, batch_size=32, to_device=False):
+        """The spec model's predict: spec (n, F, frames) or (n, F, frames, 1) float32, the front-end's output, -> (n, D); the
+        front-end does not run.  to_device: a usc.DeviceFeatures of the same rows, which the caller owns and closes."""
+        if self.embedding_type != 'audio':
+            raise TypeError('predict_spectrograms needs an audio embedding model')
+        spec = np.ascontiguousarray(spec, dtype=np.float32)
+        n = spec.shape[0]
+        e = self.base._ensure_engine(self.base._engine.batch if self.base._engine is not None else max(1, min(batch_size, n)))
+        if not to_device:
+            return e.embed_audio_spec(spec, self.pool)
+        from . import usc
+        if n == 0:
+            raise ValueError('no spectrograms: a device matrix has at least one row')
+        D = int(e.lib.l3_embed_dim(e.h, 0, self.pool[0], self.pool[1]))
+        out = _lib.Features.alloc(n, D, device=self.base.device)
+        e.embed_audio_spec(spec, self.pool, dst=out, row0=0)
+        return usc.DeviceFeatures.from_handle(out)
+
     def predict_images(self, images, batch_size=32, resize=256, crop='center', to_device=False):
         """read_video's resize, the 224 x 224 crop, 2 * img_as_float(u8) - 1 and predict for raw frames of any sizes
         (data/avc/sample.py:286-316, :169-193, train.py:186): images is a sequence of (H, W, 3) uint8 arrays or one
@@ -1254,8 +1308,8 @@ def construct_cnn_l3_orig_vision_embedding_model(vision_model, x_i):
 
 
 def load_embedding(weights_path, model_type, embedding_type, pooling_type, src_num_gpus=0, tgt_num_gpus=None,
-                   return_io=False):
-    """model.py:131-181"""
+                   return_io=False, frontend='kapre'):
+    """model.py:131-181.  frontend: 'kapre', or 'minispec' for the deployed pipeline's spectrogram."""
     m, inputs, output = load_model(weights_path, model_type, src_num_gpus=src_num_gpus,
                                    tgt_num_gpus=tgt_num_gpus, return_io=True)
     x_i, x_a = inputs
@@ -1267,6 +1321,7 @@ def load_embedding(weights_path, model_type, embedding_type, pooling_type, src_n
         m_embed, x_embed, y_embed = convert_audio_model_to_embedding(m_embed_model, x_a, model_type, pooling_type)
     else:
         raise ValueError('Invalid embedding type: "{}"'.format(embedding_type))
+    m_embed.base.set_frontend(frontend)
     if return_io:
         return m_embed, x_embed, y_embed
     return m_embed
