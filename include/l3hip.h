@@ -989,6 +989,75 @@ int l3_audio_spectrograms(l3_engine *e, const float *samples, int64_t n_samples,
 int l3_embed_audio_spec(l3_engine *e, const float *spec, int64_t n, int pool_h, int pool_w, float *out);
 int l3_embed_audio_spec_dev(l3_engine *e, const float *spec, int64_t n, int pool_h, int pool_w, l3_feat *dst, int64_t row0);
 
+/* ---- Cross-modal retrieval: every (frame, second) pair through the AVC head (csrc/pairs.hip) ---------------------------
+ * A tower's flattened output -- its half of the concatenate input (model.py:25), nv or na wide: l3_tower_dim -- from ONE tower run in
+ * inference mode, as l3_embed_* run it; the other tower does not run.  tower: 0 = vision_model, rows (n, 224, 224, 3); 1 =
+ * audio_model, rows (n, 1, 48000).  n may exceed the engine batch.
+ *   l3_tower_features              host rows -> out (n, width) on the host
+ *   l3_tower_features_dev          ... -> rows [row0, row0 + n) of dst (width columns, on the engine's device); only the real rows of
+ *                                  the last engine batch are written
+ *   l3_tower_features_sampled_dev  n >= 1 l3_sample records of a bank, not augmented: each engine batch is built by the feed of
+ *                                  l3_upload_batch_sampled (window resize, seconds kernel, conversion to float; the last batch is filled
+ *                                  up with copies of its last record) and REPLACES the engine's resident batch; then both towers run
+ *                                  solo.  vis / aud: the destinations of the frames' and the seconds' rows; either may be NULL (that
+ *                                  tower does not run), not both.  Every record is checked as l3_upload_batch_sampled checks it,
+ *                                  before anything is launched.
+ * L3_EINVAL (message in l3_last_error(e)): a NULL pointer, n < 0 (sampled: n < 1), a tower other than 0 / 1, a destination on another
+ * device, of another width, or too short. */
+int l3_tower_dim(const l3_engine *e, int tower);
+int l3_tower_features(l3_engine *e, int tower, const float *rows, int64_t n, float *out);
+int l3_tower_features_dev(l3_engine *e, int tower, const float *rows, int64_t n, l3_feat *dst, int64_t row0);
+int l3_tower_features_sampled_dev(l3_engine *e, l3_clipbank *bank, const l3_sample *records, int64_t n, l3_feat *vis, l3_feat *aud,
+                                  int64_t row0);
+/* The head over pairs.  dense_1 splits over the concatenation, W1 = [W1v; W1a] (vision rows first), and only the difference of the two
+ * logits matters:
+ *     u_i = v_i W1v   (Nv, head)        t_j = a_j W1a + b1   (Na, head)        wd = fl32(W2[:, 1] - W2[:, 0]),  bd = fl32(b2[1] - b2[0])
+ *     margin_ij = sum_k relu(u_ik + t_jk) wd_k + bd = logit(corresponding) - logit(not);   P(corresponding)_ij = 1 / (1 + exp(-margin_ij))
+ * (index 1 is `corresponding`: the labels row is {label, 1 - label}, sample.py:363,376).  A handle of its own: one device, one stream,
+ * the head and the two projected sets resident; every call has finished when it returns; calls on one handle are not re-entrant.
+ * Arithmetic, which is the contract (tests/pairs_ref.py derives the bounds from it):
+ *   projection   every element is one float32 fma chain over k = 0 .. K-1 in that order, started at 0; t adds b1 last (one rounding).
+ *                A row's bits depend on the row and the weights only: not on the rows projected with it, nor on its position.
+ *   pair         acc = 0; for k = 0 .. head-1: acc = fma(max(fl32(u_k + t_k), 0), wd_k, acc); margin = fl32(acc + bd).  The same bits
+ *                for the same pair in l3_pairs_matrix, any block of it, l3_pairs_list and l3_pairs_ranks.
+ *   probability  fl32(1 / fl32(1 + expf(-margin))).
+ * head: a multiple of 32 in [32, 4096]; a set holds at most 65535 * L3_PAIRS_TILE items.
+ *   l3_pairs_set_head        w1 (nv + na, head), b1 (head), w2 (head, 2), b2 (2), row major; voids the projected sets
+ *   l3_pairs_set_vision/_audio[_dev]   n host rows (n, nv | na), or rows [lo, hi) of an l3_feat on the handle's device -> U / T
+ *   l3_pairs_matrix          the block [v0, v1) x [a0, a1) to the host, row major: margins, or probabilities when prob != 0
+ *   l3_pairs_list            margin_out[q] = margin of the pair (iv[q], ia[q]), n >= 1
+ *   l3_pairs_ranks           rank_v2a[i] = #{j : margin_ij > margin_{i, truth_a[i]} and group_a[j] != group_v[i]}   (Nv int32)
+ *                            rank_a2v[j] = #{i : margin_ij > margin_{truth_v[j], j} and group_a[j] != group_v[i]}   (Na int32)
+ *                            The comparison is strict: a tie with the truth does not count, and the truth pair never counts against
+ *                            itself.  group_v / group_a: int32 clip ids, both NULL to exclude nothing.  A direction whose truth and
+ *                            rank vectors are both NULL is not computed.  The matrix is never stored: a tile's comparisons are counted
+ *                            in registers, summed over lanes, and added with one integer atomic per (row, tile); exact, and the same
+ *                            from run to run.
+ *   l3_pairs_time            device time in ms per launch over `reps` launches (hipEvents, one untimed launch first): what 0 the
+ *                            whole matrix of margins, 1 the rank mode with the diagonal as truth (Nv == Na), 2 / 3 the vision / audio
+ *                            projection of n_rows zero rows.  For the records under profiles/.
+ * L3_EINVAL (message in l3_last_error(NULL)): a NULL pointer, widths that do not match, an empty set or block, a block, a pair or a
+ * truth index out of range, an l3_feat on another device.  L3_ESTATE: a call before the head or the sets it needs. */
+#define L3_PAIRS_TILE 64        /* frames and seconds of one workgroup's tile of pairs */
+typedef struct l3_pairs l3_pairs;
+int l3_pairs_create(int device, int nv, int na, int head, l3_pairs **p);
+void l3_pairs_destroy(l3_pairs *p);
+int l3_pairs_set_head(l3_pairs *p, const float *w1, const float *b1, const float *w2, const float *b2);
+int l3_pairs_set_vision(l3_pairs *p, const float *rows, int64_t n);
+int l3_pairs_set_audio(l3_pairs *p, const float *rows, int64_t n);
+int l3_pairs_set_vision_dev(l3_pairs *p, const l3_feat *f, int64_t lo, int64_t hi);
+int l3_pairs_set_audio_dev(l3_pairs *p, const l3_feat *f, int64_t lo, int64_t hi);
+int l3_pairs_matrix(l3_pairs *p, int64_t v0, int64_t v1, int64_t a0, int64_t a1, int prob, float *out);
+int l3_pairs_list(l3_pairs *p, const int32_t *iv, const int32_t *ia, int64_t n, float *margin_out);
+int l3_pairs_ranks(l3_pairs *p, const int32_t *truth_a, const int32_t *truth_v, const int32_t *group_v, const int32_t *group_a,
+                   int32_t *rank_v2a, int32_t *rank_a2v);
+int l3_pairs_time(l3_pairs *p, int what, int64_t n_rows, int reps, double *ms);
+/* The two kernels alone on host buffers: out (n, H) = x (n, K) w (K, H) [+ b when b != NULL]; out (Nv, Na) = the margins of u (Nv, H)
+ * and t (Na, H). */
+int l3_op_project(int device, const float *x, const float *w, const float *b, int64_t n, int K, int H, float *out);
+int l3_op_pair_margins(int device, const float *u, const float *t, const float *wd, float bd, int64_t Nv, int64_t Na, int H,
+                       float *out);
+
 /* ---- A group of MLP classifiers (the learning_rate x weight_decay search of classifier/train.py:638-651) ---------------------------
  * n_members models of one shape (D, C, batch) trained on ONE resident data set in the same launches: an epoch's step is seven
  * launches whatever the number of members, and the validation pass and prediction run every member per launch too.

@@ -170,6 +170,23 @@ SIGNATURES = {
     'l3_audio_spectrograms': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     'l3_embed_audio_spec': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     'l3_embed_audio_spec_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    'l3_tower_dim': (C.c_int, [C.c_void_p, C.c_int]),
+    'l3_tower_features': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_tower_features_dev': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    'l3_tower_features_sampled_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_pairs_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    'l3_pairs_destroy': (None, [C.c_void_p]),
+    'l3_pairs_set_head': (C.c_int, [C.c_void_p] * 5),
+    'l3_pairs_set_vision': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_pairs_set_audio': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_pairs_set_vision_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    'l3_pairs_set_audio_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    'l3_pairs_matrix': (C.c_int, [C.c_void_p] + [C.c_int64] * 4 + [C.c_int, C.c_void_p]),
+    'l3_pairs_list': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_pairs_ranks': (C.c_int, [C.c_void_p] * 7),
+    'l3_pairs_time': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_double)]),
+    'l3_op_project': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    'l3_op_pair_margins': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     'l3_frontend_cfg': (C.c_int, [C.c_int] * 5 + [C.c_void_p]),
     'l3_frontend_tables': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int64, C.POINTER(C.c_int64)]),
     'l3_op_frontend_frames': (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4),
@@ -843,6 +860,45 @@ class Engine(object):
               self.h)
         return out
 
+    def tower_dim(self, tower):
+        """l3_tower_dim: the width of a tower's flattened output (0 = vision_model, 1 = audio_model)."""
+        d = self.lib.l3_tower_dim(self.h, int(tower))
+        if d < 0:
+            raise ValueError('tower must be 0 (vision_model) or 1 (audio_model), not %r' % (tower,))
+        return d
+
+    def tower_features(self, tower, rows, out=None, dst=None, row0=0):
+        """l3_tower_features: (n, 224, 224, 3) frames (tower 0) or (n, 1, 48000) waveforms (tower 1) -> the tower's flattened output
+        (n, width) from that tower alone, inference-mode BatchNorm.  out, dst, row0: as embed_audio_frames'
+        (l3_tower_features_dev)."""
+        x = _f32(rows)
+        n = x.shape[0]
+        per = 224 * 224 * 3 if tower == 0 else 48000
+        if x.size != n * per:
+            raise ValueError('tower %d takes rows of %d values, not an array of shape %s' % (tower, per, x.shape))
+        if dst is not None:
+            if out is not None:
+                raise ValueError('give out or dst, not both')
+            check(self.lib.l3_tower_features_dev(self.h, int(tower), _ptr(x), n, dst.h, int(row0)), self.h)
+            return dst
+        d = self.tower_dim(tower)
+        if out is None:
+            out = np.empty((n, d), np.float32)
+        elif out.dtype != np.float32 or not out.flags['C_CONTIGUOUS'] or out.shape != (n, d):
+            raise ValueError('out must be a C-contiguous float32 array of shape %s' % ((n, d),))
+        check(self.lib.l3_tower_features(self.h, int(tower), _ptr(x), n, _ptr(out)), self.h)
+        return out
+
+    def tower_features_sampled(self, bank, records, vis=None, aud=None, row0=0):
+        """l3_tower_features_sampled_dev: both towers' outputs of the (frame, second) of every record (SAMPLE_RECORD rows, not
+        augmented) of a ClipBank, into rows [row0, row0 + n) of the Features vis and aud (either may be None).  Replaces the
+        engine's resident batch."""
+        r = sample_records(records)
+        if vis is None and aud is None:
+            raise ValueError('give vis, aud or both')
+        check(self.lib.l3_tower_features_sampled_dev(self.h, bank.h, _ptr(r), len(r), None if vis is None else vis.h,
+                                                     None if aud is None else aud.h, int(row0)), self.h)
+
     def activation(self, name):
         n = C.c_int64()
         check(self.lib.l3_activation_numel(self.h, name.encode(), C.byref(n)), self.h)
@@ -1387,6 +1443,216 @@ def op_sample_batch(bank, records, augment=False):
     g = np.empty(n, np.float64) if augment else None
     check(load().l3_op_sample_batch(bank.h, _ptr(r), n, int(bool(augment)), _ptr(v), _ptr(a), _ptr(g)))
     return v, a, g
+
+
+# ---- cross-modal retrieval: the AVC head over every (frame, second) pair (csrc/pairs.hip) ---------------------------
+PAIRS_TILE = 64                    # L3_PAIRS_TILE
+PAIRS_MAX_ITEMS = 65535 * PAIRS_TILE
+
+
+def _head_width_ok(h):
+    return 32 <= h <= 4096 and h % 32 == 0
+
+
+def _index32(a, name, n, bound, what):
+    """`a` as n int32 indices in [0, bound); ValueError otherwise"""
+    if a is None:
+        raise ValueError('%s must not be None' % name)
+    a = np.asarray(a)
+    if a.ndim != 1 or len(a) != n or a.dtype.kind not in 'iu':
+        raise ValueError('%s must be %d integers, one per %s' % (name, n, what))
+    if n and (a.min() < 0 or a.max() >= bound):
+        bad = int(np.flatnonzero((a < 0) | (a >= bound))[0])
+        raise ValueError('%s[%d] = %d outside [0, %d)' % (name, bad, int(a[bad]), bound))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+class Pairs(object):
+    """RAII wrapper over an l3_pairs handle: the head and the two projected sets resident on one device.  Every argument is checked
+    here first (ValueError) and the handle is created by the first call that needs the device."""
+
+    def __init__(self, nv, na, head, device=0):
+        nv, na, head = int(nv), int(na), int(head)
+        if nv < 1 or na < 1 or not _head_width_ok(head):
+            raise ValueError('tower widths must be >= 1 and the head width a multiple of 32 in [32, 4096]; got %d, %d, %d' % (nv, na, head))
+        self.nv, self.na, self.head, self.device = nv, na, head, int(device)
+        self.lib = None
+        self.h = None
+        self.head_set = False
+        self.n_vision = self.n_audio = 0
+
+    def _handle(self):
+        if self.h is None:
+            self.lib = load()
+            h = C.c_void_p()
+            check(self.lib.l3_pairs_create(self.device, self.nv, self.na, self.head, C.byref(h)))
+            self.h = h
+        return self.h
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_pairs_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_head(self, w1, b1, w2, b2):
+        """dense_1 kernel (nv + na, head) and bias (head), dense_2 kernel (head, 2) and bias (2).  Voids the projected sets."""
+        shapes = ((self.nv + self.na, self.head), (self.head,), (self.head, 2), (2,))
+        arrs = []
+        for name, a, shape in zip(('w1', 'b1', 'w2', 'b2'), (w1, b1, w2, b2), shapes):
+            if a is None:
+                raise ValueError('%s must not be None' % name)
+            a = _f32(a)
+            if a.shape != shape:
+                raise ValueError('%s must have shape %s, not %s' % (name, shape, a.shape))
+            arrs.append(a)
+        h = self._handle()
+        self.head_set = False
+        self.n_vision = self.n_audio = 0
+        check(self.lib.l3_pairs_set_head(h, *[_ptr(a) for a in arrs]))
+        self.head_set = True
+
+    def _set(self, vision, rows, lo, hi):
+        side, width = ('vision', self.nv) if vision else ('audio', self.na)
+        if rows is None:
+            raise ValueError('the %s rows must not be None' % side)
+        if not self.head_set:
+            raise ValueError('set_head comes before set_%s' % side)
+        if isinstance(rows, Features):
+            if not rows.h:
+                raise ValueError('the %s features are closed' % side)
+            if rows.device != self.device:
+                raise ValueError('the %s features are on device %d, the scorer on device %d' % (side, rows.device, self.device))
+            n, d = rows.shape
+            hi = n if hi is None else int(hi)
+            lo = int(lo)
+            if d != width:
+                raise ValueError('the %s features have %d columns, the tower\'s output %d' % (side, d, width))
+            if lo < 0 or hi > n or lo >= hi:
+                raise ValueError('rows [%d, %d) are empty or outside the %d rows of the %s features' % (lo, hi, n, side))
+            count = hi - lo
+        else:
+            x = _f32(rows)
+            if x.ndim != 2 or x.shape[1] != width:
+                raise ValueError('the %s rows must have shape (n, %d), not %s' % (side, width, x.shape))
+            count = x.shape[0]
+            if count < 1:
+                raise ValueError('the %s set is empty' % side)
+        if count > PAIRS_MAX_ITEMS:
+            raise ValueError('a set holds at most %d items, not %d' % (PAIRS_MAX_ITEMS, count))
+        h = self._handle()
+        if vision:
+            self.n_vision = 0
+        else:
+            self.n_audio = 0
+        if isinstance(rows, Features):
+            fn = self.lib.l3_pairs_set_vision_dev if vision else self.lib.l3_pairs_set_audio_dev
+            check(fn(h, rows.h, lo, hi))
+        else:
+            fn = self.lib.l3_pairs_set_vision if vision else self.lib.l3_pairs_set_audio
+            check(fn(h, _ptr(x), count))
+        if vision:
+            self.n_vision = count
+        else:
+            self.n_audio = count
+
+    def set_vision(self, rows, lo=0, hi=None):
+        """(Nv, nv) host rows, or rows [lo, hi) of a Features on this device -> U = V W1v, resident"""
+        self._set(True, rows, lo, hi)
+
+    def set_audio(self, rows, lo=0, hi=None):
+        """(Na, na) host rows, or rows [lo, hi) of a Features on this device -> T = A W1a + b1, resident"""
+        self._set(False, rows, lo, hi)
+
+    def _need_sets(self):
+        if not self.head_set or self.n_vision < 1 or self.n_audio < 1:
+            raise ValueError('set_head, set_vision and set_audio come first')
+
+    def matrix(self, v0=0, v1=None, a0=0, a1=None, prob=False):
+        """the block [v0, v1) x [a0, a1) of margins (logit(corresponding) - logit(not)), or of P(corresponding) with prob"""
+        self._need_sets()
+        v1 = self.n_vision if v1 is None else int(v1)
+        a1 = self.n_audio if a1 is None else int(a1)
+        v0, a0 = int(v0), int(a0)
+        if v0 < 0 or v1 > self.n_vision or v0 >= v1 or a0 < 0 or a1 > self.n_audio or a0 >= a1:
+            raise ValueError('the block [%d, %d) x [%d, %d) is empty or outside the %d x %d pairs' % (v0, v1, a0, a1, self.n_vision,
+                                                                                                      self.n_audio))
+        out = np.empty((v1 - v0, a1 - a0), np.float32)
+        h = self._handle()
+        check(self.lib.l3_pairs_matrix(h, v0, v1, a0, a1, int(bool(prob)), _ptr(out)))
+        return out
+
+    def list(self, iv, ia):
+        """margins of the pairs (iv[q], ia[q])"""
+        self._need_sets()
+        n = len(iv) if iv is not None and np.ndim(iv) == 1 else -1
+        if n < 1:
+            raise ValueError('iv and ia must be two equally long, non-empty 1-d index arrays')
+        iv = _index32(iv, 'iv', n, self.n_vision, 'pair')
+        ia = _index32(ia, 'ia', n, self.n_audio, 'pair')
+        out = np.empty(n, np.float32)
+        h = self._handle()
+        check(self.lib.l3_pairs_list(h, _ptr(iv), _ptr(ia), n, _ptr(out)))
+        return out
+
+    def ranks(self, truth_a=None, truth_v=None, group_v=None, group_a=None):
+        """(rank_v2a, rank_a2v): for every frame i the seconds j that score strictly above its true second truth_a[i] with
+        group_a[j] != group_v[i], and for every second the frames likewise (truth_v).  A direction whose truth is None is not
+        computed and comes back as None; the groups are given together or not at all."""
+        self._need_sets()
+        if truth_a is None and truth_v is None:
+            raise ValueError('truth_a, truth_v or both are needed')
+        if (group_v is None) != (group_a is None):
+            raise ValueError('group_v and group_a are given together or both left None')
+        ta = None if truth_a is None else _index32(truth_a, 'truth_a', self.n_vision, self.n_audio, 'frame')
+        tv = None if truth_v is None else _index32(truth_v, 'truth_v', self.n_audio, self.n_vision, 'second')
+        gv = ga = None
+        if group_v is not None:
+            gv = _index32(group_v, 'group_v', self.n_vision, 2 ** 31, 'frame')
+            ga = _index32(group_a, 'group_a', self.n_audio, 2 ** 31, 'second')
+        rv = None if ta is None else np.empty(self.n_vision, np.int32)
+        ra = None if tv is None else np.empty(self.n_audio, np.int32)
+        h = self._handle()
+        check(self.lib.l3_pairs_ranks(h, _ptr(ta), _ptr(tv), _ptr(gv), _ptr(ga), _ptr(rv), _ptr(ra)))
+        return rv, ra
+
+    def time(self, what, n_rows=0, reps=10):
+        """l3_pairs_time: device ms per launch of 'matrix', 'ranks', 'project_vision' or 'project_audio' (n_rows rows)"""
+        kinds = ('matrix', 'ranks', 'project_vision', 'project_audio')
+        if what not in kinds:
+            raise ValueError('what must be one of %s' % (kinds,))
+        ms = C.c_double()
+        h = self._handle()
+        check(self.lib.l3_pairs_time(h, kinds.index(what), int(n_rows), int(reps), C.byref(ms)))
+        return ms.value
+
+
+def op_project(x, w, b=None, device=0):
+    """l3_op_project: x (n, K) w (K, H) [+ b] by the projection kernel of csrc/pairs.hip"""
+    x, w, b = _f32(x), _f32(w), _f32(b)
+    if x.ndim != 2 or w.ndim != 2 or x.shape[1] != w.shape[0] or x.shape[0] < 1 or not _head_width_ok(w.shape[1]) or \
+            (b is not None and b.shape != (w.shape[1],)):
+        raise ValueError('need x (n >= 1, K), w (K, H) with H a multiple of 32 in [32, 4096] and b (H,) or None')
+    out = np.empty((x.shape[0], w.shape[1]), np.float32)
+    check(load().l3_op_project(int(device), _ptr(x), _ptr(w), _ptr(b), x.shape[0], x.shape[1], w.shape[1], _ptr(out)))
+    return out
+
+
+def op_pair_margins(u, t, wd, bd, device=0):
+    """l3_op_pair_margins: margins (Nv, Na) of u (Nv, H) and t (Na, H) by the pair kernel alone"""
+    u, t, wd = _f32(u), _f32(t), _f32(wd)
+    if u.ndim != 2 or t.ndim != 2 or u.shape[0] < 1 or t.shape[0] < 1 or u.shape[1] != t.shape[1] or wd.shape != (u.shape[1],) or \
+            not _head_width_ok(u.shape[1]):
+        raise ValueError('need u (Nv >= 1, H), t (Na >= 1, H) and wd (H,) with H a multiple of 32 in [32, 4096]')
+    out = np.empty((u.shape[0], t.shape[0]), np.float32)
+    check(load().l3_op_pair_margins(int(device), _ptr(u), _ptr(t), _ptr(wd), float(np.float32(bd)), u.shape[0], t.shape[0], u.shape[1],
+                                    _ptr(out)))
+    return out
 
 
 # ---- downstream MLP classifier (classifier/train.py:230-391; csrc/mlp.hip) ---------------------------------------------------------

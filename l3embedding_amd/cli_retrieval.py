@@ -1,0 +1,54 @@
+"""Cross-modal retrieval metrics of a trained AVC model over decoded clips.
+
+    python -m l3embedding_amd.cli_retrieval WEIGHTS MODEL_TYPE CLIP.npz [CLIP.npz ...] [--output-path metrics.json]
+
+Each clip is an .npz holding `frames` (T, H, W, 3) uint8, `audio` (n,) or (n, C) int16 at 48 kHz and `rate` (avsample.load_clips).
+Every whole second of every clip becomes one (frame, second) item; the metrics are recall@k, median rank and mean reciprocal
+rank of the true partner among the items of the other clips, in both directions, and the AVC accuracy on the true pairs against as
+many cross-clip pairs (crossmodal.evaluate_bank).
+"""
+import argparse
+import json
+
+import numpy as np
+
+from . import avsample, crossmodal
+from .model import load_model
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(prog='python -m l3embedding_amd.cli_retrieval', description=__doc__.split('\n')[0])
+    p.add_argument('weights_path')
+    p.add_argument('model_type')
+    p.add_argument('clips', nargs='+')
+    p.add_argument('--fps', type=int, default=30)
+    p.add_argument('--recall-at', type=int, nargs='+', default=[1, 5, 10])
+    p.add_argument('--batch-size', type=int, default=32)
+    p.add_argument('--resize', type=int, default=256, help='0: the frames are already resized')
+    p.add_argument('--seed', type=int, default=0, help='of the cross-clip pairs of the AVC accuracy')
+    p.add_argument('--device', type=int, default=0)
+    p.add_argument('--output-path', default=None, help='also write the metrics there as JSON')
+    args = p.parse_args(argv)
+    pixels = samples = 0
+    for path in args.clips:
+        with np.load(path) as z:
+            pixels += z['frames'].size
+            samples += len(z['audio']) + 8
+    model = load_model(args.weights_path, args.model_type)
+    model.device = args.device
+    bank = avsample.load_clips(avsample.ClipBank(args.device, pixels, samples, args.resize or None), args.clips)
+    try:
+        metrics = crossmodal.evaluate_bank(model, bank, fps=args.fps, ks=tuple(args.recall_at), batch_size=args.batch_size,
+                                           seed=args.seed)
+    finally:
+        bank.close()
+    text = json.dumps(metrics, indent=2, sort_keys=True)
+    print(text)
+    if args.output_path:
+        with open(args.output_path, 'w') as fh:
+            fh.write(text + '\n')
+    return metrics
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,168 @@
+"""Cross-modal retrieval with a trained AVC model: does this frame go with this second of sound, asked of every (frame, second)
+pair of a held-out set -- the evaluation the L3 / "Objects that Sound" line of work reports beside AVC accuracy.
+
+The head factors over the concatenation: each tower runs once per item (`L3Model.predict_towers`, or
+`Engine.tower_features_sampled` straight from a `ClipBank`), the two halves of dense_1 are ordinary projections, and a pair costs
+`head` x (add, max, fma) on the GPU (csrc/pairs.hip).  `PairScorer` keeps the projected sets on the device and gives the matrix of
+margins (logit(corresponding) - logit(not)) in blocks, probabilities, listed pairs, and retrieval ranks in both directions without
+ever storing the matrix.
+"""
+import numpy as np
+
+from . import _lib
+
+T = 48000            # one second at the sampler's rate
+CROP = 224
+
+
+class PairScorer(object):
+    """The AVC head of `model` over pairs.  set_items(V, A): the towers' outputs as arrays or usc.DeviceFeatures."""
+
+    def __init__(self, model, device=None):
+        P = model._weights_dict()
+        w1, b1, w2, b2 = (np.asarray(P[k], np.float32) for k in ('dense_1/kernel', 'dense_1/bias', 'dense_2/kernel', 'dense_2/bias'))
+        nv = 360 if model.model_type == 'tiny_L3' else 512          # the vision tower's flattened output (TowerModel)
+        self.device = model.device if device is None else int(device)
+        self.handle = _lib.Pairs(nv, w1.shape[0] - nv, w1.shape[1], device=self.device)
+        self.handle.set_head(w1, b1, w2, b2)
+
+    @property
+    def shape(self):
+        return (self.handle.n_vision, self.handle.n_audio)
+
+    @staticmethod
+    def _rows(x):
+        handle = getattr(x, 'handle', None)          # usc.DeviceFeatures
+        return handle if isinstance(handle, _lib.Features) else x
+
+    def set_items(self, V=None, A=None):
+        """V (Nv, nv) frames' and A (Na, na) seconds' tower outputs; a side left None keeps its set"""
+        if V is None and A is None:
+            raise ValueError('give V, A or both')
+        if V is not None:
+            self.handle.set_vision(self._rows(V))
+        if A is not None:
+            self.handle.set_audio(self._rows(A))
+        return self
+
+    def _blocks(self, block_bytes, prob):
+        nv, na = self.shape
+        if nv < 1 or na < 1:
+            raise ValueError('set_items comes first')
+        rows = max(1, int(block_bytes) // (4 * na))
+        out = np.empty((nv, na), np.float32)
+        for v0 in range(0, nv, rows):
+            v1 = min(nv, v0 + rows)
+            out[v0:v1] = self.handle.matrix(v0, v1, 0, na, prob=prob)
+        return out
+
+    def margins(self, block_bytes=256 << 20):
+        """(Nv, Na) margins, downloaded in blocks of whole rows of at most block_bytes"""
+        return self._blocks(block_bytes, False)
+
+    def probabilities(self, block_bytes=256 << 20):
+        """(Nv, Na) P(corresponding) = sigmoid(margin)"""
+        return self._blocks(block_bytes, True)
+
+    def pairs(self, iv, ia):
+        """margins of the listed pairs (iv[q], ia[q])"""
+        return self.handle.list(iv, ia)
+
+    def ranks(self, truth=None, groups_v=None, groups_a=None):
+        """(rank_v2a, rank_a2v), 0-based: for every frame the number of seconds that score strictly above its own second, and for
+        every second the frames likewise; items of the same group (clip) as the query are not negatives.  truth None: frame i goes
+        with second i (Nv == Na).  Otherwise (truth_a, truth_v): the index of every frame's second and of every second's frame; one
+        of them may be None, and that direction comes back as None."""
+        nv, na = self.shape
+        if truth is None:
+            if nv != na:
+                raise ValueError('truth=None pairs frame i with second i and needs Nv == Na, not %d and %d' % (nv, na))
+            truth = (np.arange(nv, dtype=np.int32), np.arange(na, dtype=np.int32))
+        if not isinstance(truth, (tuple, list)) or len(truth) != 2:
+            raise ValueError('truth is None or the pair (truth_a, truth_v)')
+        return self.handle.ranks(truth[0], truth[1], groups_v, groups_a)
+
+    def close(self):
+        self.handle.close()
+
+
+def retrieval_metrics(ranks, ks=(1, 5, 10)):
+    """0-based ranks -> {'recall@k': mean(rank < k), 'median_rank': 1-based, 'mrr': mean(1 / (rank + 1)), 'n'}"""
+    r = np.asarray(ranks)
+    if r.ndim != 1 or len(r) < 1 or r.dtype.kind not in 'iu' or r.min() < 0:
+        raise ValueError('ranks must be a non-empty 1-d array of non-negative integers')
+    r = r.astype(np.int64)
+    out = {'recall@%d' % k: float(np.mean(r < k)) for k in ks}
+    out['median_rank'] = float(np.median(r + 1))
+    out['mrr'] = float(np.mean(1.0 / (r + 1)))
+    out['n'] = int(len(r))
+    return out
+
+
+def retrieval_records(clip_infos, fps=30):
+    """One SAMPLE record per whole second s of every clip (avsample.ClipInfo rows, by clip id): audio_start = 48000 s, frame =
+    min(int(s fps) + fps // 2, n_frames - 1) -- the middle of the second --, the centre crop of the resized frame, label 0 (the
+    pair corresponds), no augmentation.  A clip shorter than a second gives one record at start 0, which the seconds kernel pads
+    with zeros.  Returns (records, the clip id of each): the ids serve as the groups of PairScorer.ranks."""
+    fps = int(fps)
+    if fps < 1:
+        raise ValueError('fps must be >= 1')
+    rows = []
+    for cid, c in enumerate(clip_infos):
+        for s in range(max(1, int(c.samples) // T)):
+            rows.append((cid, min(int(s * fps) + fps // 2, int(c.frames) - 1), T * s, (int(c.out_height) - CROP) // 2,
+                         (int(c.out_width) - CROP) // 2))
+    rec = np.zeros(len(rows), _lib.SAMPLE_RECORD)
+    for i, (cid, frame, start, sx, sy) in enumerate(rows):
+        rec['video_clip'][i] = rec['audio_clip'][i] = cid
+        rec['frame'][i], rec['audio_start'][i] = frame, start
+        rec['start_x'][i], rec['start_y'][i] = sx, sy
+    rec['sat_first'], rec['saturation'] = 1, 1.0
+    return rec, np.array([r[0] for r in rows], np.int32)
+
+
+def cross_clip_pairs(groups, n, seed=0):
+    """n (frame, second) index pairs whose items come from different clips, drawn with np.random.RandomState(seed): a frame
+    uniformly, then a second uniformly among those of the other clips."""
+    groups = np.asarray(groups)
+    if len(np.unique(groups)) < 2:
+        raise ValueError('cross-clip pairs need items of at least two clips')
+    rng = np.random.RandomState(seed)
+    iv = rng.randint(len(groups), size=int(n)).astype(np.int32)
+    ia = np.empty(int(n), np.int32)
+    for q, i in enumerate(iv):
+        others = np.flatnonzero(groups != groups[i])
+        ia[q] = others[rng.randint(len(others))]
+    return iv, ia
+
+
+def evaluate_bank(model, bank, fps=30, ks=(1, 5, 10), batch_size=32, seed=0, return_ranks=False):
+    """Retrieval over every whole second of every clip of an avsample.ClipBank: retrieval_records -> both towers' outputs of each
+    record on the GPU (Engine.tower_features_sampled) -> PairScorer.ranks with the clips as groups.  Returns {'frame_to_audio',
+    'audio_to_frame': retrieval_metrics, 'avc_accuracy': accuracy at margin 0 on the true pairs against as many seeded cross-clip
+    pairs, 'items', 'clips'}; with return_ranks also the two rank vectors."""
+    records, groups = retrieval_records(bank.clips, fps=fps)
+    n = len(records)
+    e = model._ensure_engine(max(1, min(batch_size, n)) if model._engine is None else model._engine.batch)
+    V = _lib.Features.alloc(n, e.tower_dim(0), device=model.device)
+    A = _lib.Features.alloc(n, e.tower_dim(1), device=model.device)
+    scorer = None
+    try:
+        e.tower_features_sampled(bank, records, vis=V, aud=A)
+        scorer = PairScorer(model).set_items(V, A)
+        rv, ra = scorer.ranks(None, groups, groups)
+        idx = np.arange(n, dtype=np.int32)
+        pos = scorer.pairs(idx, idx)
+        out = {'frame_to_audio': retrieval_metrics(rv, ks), 'audio_to_frame': retrieval_metrics(ra, ks), 'items': n,
+               'clips': len(bank.clips)}
+        if len(np.unique(groups)) >= 2:
+            neg = scorer.pairs(*cross_clip_pairs(groups, n, seed))
+            out['avc_accuracy'] = float((np.sum(pos > 0) + np.sum(neg <= 0)) / (2.0 * n))
+        else:
+            out['avc_accuracy'] = None
+    finally:
+        if scorer is not None:
+            scorer.close()
+        V.close()
+        A.close()
+    return (out, rv, ra) if return_ranks else out

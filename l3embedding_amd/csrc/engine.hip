@@ -2785,6 +2785,7 @@ struct EmbedSource {
     const int64_t* descs = nullptr;       // device, n x IMAGE_DESC
     const int64_t* taps = nullptr;        // device
     const float* spec = nullptr;          // n rows (F, frames), host memory: the front-end's OUTPUT (audio only; l3_embed_audio_spec)
+    bool resident = false;                // the engine's float inputs hold the batch already (l3_tower_features_sampled_dev)
 };
 
 // Pooled rows stay on the device between two copies to the host; one copy (and one host wait) per call up to this many bytes.
@@ -2813,6 +2814,37 @@ struct EmbedDest {
     int64_t row0 = 0;
 };
 
+// Rows [s0, s0 + cnt) of a source as one engine batch (the rest of the batch zero), then that tower alone in inference mode: the
+// (audio) front-end unless the rows are its output already, the solo plan, the forward.  What l3_embed_* and l3_tower_features
+// share; they differ in what they take from the tower afterwards.
+static int solo_tower_batch(l3_engine* e, bool vision, const EmbedSource& src, int64_t s0, int64_t cnt) {
+    Tower& tw = vision ? e->vis : e->aud;
+    const int B = e->B;
+    const size_t per = vision ? (size_t)224 * 224 * 3 : (size_t)AUDIO_T;
+    float* dst_in = vision ? e->video : e->audio;
+    int rc = L3_OK;
+    if (src.spec) {
+        const size_t sper = (size_t)tw.t[0].batch_stride;
+        HIPCHK(e, hipMemcpyAsync(tw.t[0].d, src.spec + (size_t)s0 * sper, (size_t)cnt * sper * 4, hipMemcpyHostToDevice, e->stream));
+        if (cnt < B) HIPCHK(e, hipMemsetAsync(tw.t[0].d + (size_t)cnt * sper, 0, (size_t)(B - cnt) * sper * 4, e->stream));
+    } else if (src.host) {
+        HIPCHK(e, hipMemcpyAsync(dst_in, src.host + (size_t)s0 * per, (size_t)cnt * per * 4, hipMemcpyHostToDevice, e->stream));
+        if (cnt < B) HIPCHK(e, hipMemsetAsync(dst_in + (size_t)cnt * per, 0, (size_t)(B - cnt) * per * 4, e->stream));
+    } else if (src.pixels) {
+        ProfScope ps(e, F_FRONTEND, 0.0);          // profiled with the input-side kernels: the vision tower has no other
+        image_frames(src.pixels, src.descs + IMAGE_DESC * s0, src.taps, nullptr, dst_in, B, (int)cnt, e->stream);
+    } else if (!src.resident) {
+        gather_frames(src.samples, src.table + 3 * s0, dst_in, B, (int)cnt, AUDIO_T, e->stream);
+    }
+    if (!vision && !src.spec) {
+        rc = run_frontend(e);
+        if (rc) return rc;
+    }
+    if ((rc = plan_tower(e, tw, false, 1))) return rc;
+    tower_forward(e, tw);
+    return L3_OK;
+}
+
 // load_embedding(...).predict on n rows: per engine batch, the input rows -> (audio) front-end -> solo tower forward ->
 // MaxPooling2D.  To the host: into the device output buffer, whose pooled rows go to the host when the buffer is full and at the
 // end.  To a device matrix: straight into its rows, only the `cnt` real rows of the last engine batch (the matrix is not rounded up
@@ -2835,30 +2867,10 @@ static int embed_rows(l3_engine* e, bool vision, const EmbedSource& src, int64_t
     tf_same(t.H, ph, ph, &pg.Ho, &pg.padT);
     tf_same(t.W, pw, pw, &pg.Wo, &pg.padL);
     pg.out_batch_stride = D;
-    const size_t per = vision ? (size_t)224 * 224 * 3 : (size_t)AUDIO_T;
-    float* dst_in = vision ? e->video : e->audio;
     int64_t f0 = 0;                 // first row the device output buffer holds
     for (int64_t s0 = 0; s0 < n; s0 += B) {
         const int64_t cnt = n - s0 < B ? n - s0 : B;
-        if (src.spec) {
-            const size_t sper = (size_t)tw.t[0].batch_stride;
-            HIPCHK(e, hipMemcpyAsync(tw.t[0].d, src.spec + (size_t)s0 * sper, (size_t)cnt * sper * 4, hipMemcpyHostToDevice, e->stream));
-            if (cnt < B) HIPCHK(e, hipMemsetAsync(tw.t[0].d + (size_t)cnt * sper, 0, (size_t)(B - cnt) * sper * 4, e->stream));
-        } else if (src.host) {
-            HIPCHK(e, hipMemcpyAsync(dst_in, src.host + (size_t)s0 * per, (size_t)cnt * per * 4, hipMemcpyHostToDevice, e->stream));
-            if (cnt < B) HIPCHK(e, hipMemsetAsync(dst_in + (size_t)cnt * per, 0, (size_t)(B - cnt) * per * 4, e->stream));
-        } else if (src.pixels) {
-            ProfScope ps(e, F_FRONTEND, 0.0);          // profiled with the input-side kernels: the vision tower has no other
-            image_frames(src.pixels, src.descs + IMAGE_DESC * s0, src.taps, nullptr, dst_in, B, (int)cnt, e->stream);
-        } else {
-            gather_frames(src.samples, src.table + 3 * s0, dst_in, B, (int)cnt, AUDIO_T, e->stream);
-        }
-        if (!vision && !src.spec) {
-            rc = run_frontend(e);
-            if (rc) return rc;
-        }
-        if ((rc = plan_tower(e, tw, false, 1))) return rc;
-        tower_forward(e, tw);
+        if ((rc = solo_tower_batch(e, vision, src, s0, cnt))) return rc;
         if (dst.dev) {
             pg.N = (int)cnt;          // rows [row0 + s0, row0 + s0 + cnt) and not one more
             maxpool_fwd(t.d, dst.feat->x + (size_t)(dst.row0 + s0) * D, pg, e->stream);
@@ -2961,6 +2973,124 @@ int l3_embed_audio_frames_dev(l3_engine* e, const float* samples, int64_t n_samp
     EmbedDest dst;
     dst.dev = true, dst.feat = dst_feat, dst.row0 = row0;
     return embed_frames_to(e, "l3_embed_audio_frames_dev", samples, n_samples, table, n_frames, pool_h, pool_w, dst);
+}
+
+// ---- a tower's flattened output on its own ------------------------------------------------------------------------------
+int l3_tower_dim(const l3_engine* e, int tower) {
+    if (!e || (tower != 0 && tower != 1)) return L3_EINVAL;
+    return tower == 0 ? e->nv : e->na;
+}
+
+// The `cnt` real rows of the tower's half of h0 (row stride nv + na) -> rows [r0, r0 + cnt) of the destination, on the engine's stream
+static int tower_rows_out(l3_engine* e, bool vision, int64_t r0, int64_t cnt, const EmbedDest& dst) {
+    const size_t W = (size_t)(vision ? e->nv : e->na), D = (size_t)(e->nv + e->na);
+    const float* src = e->h0 + (vision ? 0 : e->nv);
+    float* to = dst.dev ? dst.feat->x + (size_t)(dst.row0 + r0) * W : dst.host + (size_t)r0 * W;
+    HIPCHK(e, hipMemcpy2DAsync(to, W * 4, src, D * 4, W * 4, (size_t)cnt, dst.dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream));
+    return L3_OK;
+}
+
+static int tower_features_to(l3_engine* e, const char* fn, int tower, const float* rows, int64_t n, const EmbedDest& dst) {
+    if (!e) return L3_EINVAL;
+    const std::string name(fn);
+    if (tower != 0 && tower != 1) {
+        e->err = name + ": tower must be 0 (vision_model) or 1 (audio_model), not " + std::to_string(tower);
+        return L3_EINVAL;
+    }
+    if (!rows || !(dst.host || dst.feat)) {
+        e->err = name + ": rows and " + (dst.dev ? "dst" : "out") + " must not be NULL";
+        return L3_EINVAL;
+    }
+    if (n < 0) {
+        e->err = name + ": n must be >= 0";
+        return L3_EINVAL;
+    }
+    const bool vision = tower == 0;
+    int rc = embed_dest_check(e, fn, dst, n, vision ? e->nv : e->na);
+    if (rc) return rc;
+    if (n == 0) return L3_OK;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    EmbedSource src;
+    src.host = rows;
+    for (int64_t s0 = 0; s0 < n; s0 += e->B) {
+        const int64_t cnt = n - s0 < e->B ? n - s0 : e->B;
+        if ((rc = solo_tower_batch(e, vision, src, s0, cnt))) return rc;
+        if ((rc = tower_rows_out(e, vision, s0, cnt, dst))) return rc;
+    }
+    HIPCHK(e, l3::stream_wait(e->stream));
+    e->fwd_done = false;
+    prof_collect(e);
+    return L3_OK;
+}
+
+int l3_tower_features(l3_engine* e, int tower, const float* rows, int64_t n, float* out) {
+    EmbedDest dst;
+    dst.host = out;
+    return tower_features_to(e, "l3_tower_features", tower, rows, n, dst);
+}
+
+int l3_tower_features_dev(l3_engine* e, int tower, const float* rows, int64_t n, l3_feat* dst_feat, int64_t row0) {
+    EmbedDest dst;
+    dst.dev = true, dst.feat = dst_feat, dst.row0 = row0;
+    return tower_features_to(e, "l3_tower_features_dev", tower, rows, n, dst);
+}
+
+int l3_tower_features_sampled_dev(l3_engine* e, l3_clipbank* bank, const l3_sample* records, int64_t n, l3_feat* vis, l3_feat* aud,
+                                  int64_t row0) {
+    if (!e) return L3_EINVAL;
+    const char* fn = "l3_tower_features_sampled_dev";
+    const std::string name(fn);
+    if (!bank || !records || (!vis && !aud)) {
+        e->err = name + ": NULL bank or records, or neither vis nor aud";
+        return L3_EINVAL;
+    }
+    if (n < 1 || n > INT32_MAX) {
+        e->err = name + ": need 1 <= n <= 2^31 - 1 records";
+        return L3_EINVAL;
+    }
+    if (l3::clipbank_device(bank) != e->cfg.device) {
+        e->err = name + ": the bank lives on device " + std::to_string(l3::clipbank_device(bank)) + ", the engine on device " +
+                 std::to_string(e->cfg.device);
+        return L3_EINVAL;
+    }
+    EmbedDest dv, da;
+    dv.dev = da.dev = true, dv.feat = vis, da.feat = aud, dv.row0 = da.row0 = row0;
+    int rc;
+    if (vis && (rc = embed_dest_check(e, fn, dv, n, e->nv))) return rc;
+    if (aud && (rc = embed_dest_check(e, fn, da, n, e->na))) return rc;
+    {
+        l3::SampledHost all;          // every record, before anything is launched; the message carries the record's number
+        if ((rc = l3::sampled_plan(bank, records, (int)n, false, &all, &e->err))) {
+            if (rc == L3_EINVAL) e->err = name + ": " + e->err;
+            return rc;
+        }
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    const int B = e->B;
+    std::vector<l3_sample> batch((size_t)B);
+    EmbedSource src;
+    src.resident = true;
+    for (int64_t s0 = 0; s0 < n; s0 += B) {
+        const int64_t cnt = n - s0 < B ? n - s0 : B;
+        for (int64_t r = 0; r < B; ++r) batch[(size_t)r] = records[s0 + (r < cnt ? r : cnt - 1)];
+        e->feed.mark = sampled_fill_mark, e->feed.mark_ctx = e;
+        if ((rc = e->feed.upload_sampled(bank, batch.data(), B, false, e->stream, &e->err))) {
+            if (rc == L3_EINVAL) e->err = name + ": " + e->err;
+            return rc;
+        }
+        if (vis) {
+            if ((rc = solo_tower_batch(e, true, src, 0, cnt))) return rc;
+            if ((rc = tower_rows_out(e, true, s0, cnt, dv))) return rc;
+        }
+        if (aud) {
+            if ((rc = solo_tower_batch(e, false, src, 0, cnt))) return rc;
+            if ((rc = tower_rows_out(e, false, s0, cnt, da))) return rc;
+        }
+    }
+    HIPCHK(e, l3::stream_wait(e->stream));
+    e->fwd_done = false;
+    prof_collect(e);
+    return L3_OK;
 }
 
 // ---- spectrograms out, spectrograms in ---------------------------------------------------------------------------------

@@ -625,6 +625,32 @@ class L3Model(object):
         e = self._ensure_engine(len(v))
         return e.forward(v, a, training=training)[1]
 
+    def predict_towers(self, video=None, audio=None, batch_size=32, to_device=False):
+        """The two towers' flattened outputs, each from its tower alone (inference-mode BatchNorm): video (Nv, 224, 224, 3) ->
+        V (Nv, nv), audio (Na, 1, 48000) -> A (Na, na), the halves of the concatenate input (model.py:25) that
+        crossmodal.PairScorer scores pair by pair.  Either input may be None (its output is None); Nv and Na need not be equal.
+        The engine is chosen as predict chooses it.  to_device: usc.DeviceFeatures, which the caller owns and closes."""
+        if video is None and audio is None:
+            raise ValueError('give video, audio or both')
+        ins = [None if x is None else np.ascontiguousarray(x, dtype=np.float32) for x in (video, audio)]
+        for x, name in zip(ins, ('video', 'audio')):
+            if x is not None and len(x) == 0:
+                raise ValueError('%s has no rows' % name)
+        n = max(len(x) for x in ins if x is not None)
+        e = self._ensure_engine(max(1, min(batch_size, n)) if self._engine is None else self._engine.batch)
+        outs = []
+        for tower, x in enumerate(ins):
+            if x is None:
+                outs.append(None)
+            elif to_device:
+                from . import usc
+                dst = _lib.Features.alloc(len(x), e.tower_dim(tower), device=self.device)
+                e.tower_features(tower, x, dst=dst)
+                outs.append(usc.DeviceFeatures.from_handle(dst))
+            else:
+                outs.append(e.tower_features(tower, x))
+        return tuple(outs)
+
     def fit_generator(self, generator, steps_per_epoch, epochs=1, verbose=1, callbacks=None, validation_data=None,
                       validation_steps=None, initial_epoch=0, **_):
         """keras fit_generator loop as driven by train.py:408-414: per step train_on_batch, per
