@@ -1033,12 +1033,31 @@ int l3_tower_features_sampled_dev(l3_engine *e, l3_clipbank *bank, const l3_samp
  *                            rank vectors are both NULL is not computed.  The matrix is never stored: a tile's comparisons are counted
  *                            in registers, summed over lanes, and added with one integer atomic per (row, tile); exact, and the same
  *                            from run to run.
+ *   l3_pairs_topk            for every frame the k best-scoring seconds (idx_v2a, margin_v2a: (Nv, k) int32 / float32, row major), for
+ *                            every second the k best-scoring frames (idx_a2v, margin_a2v: (Na, k)), by the order below.  A direction
+ *                            is asked for by giving both of its outputs; one at least is needed, and the truth of a direction that is
+ *                            not asked for is not read.  The matrix is never stored; the segment count is the library's choice.
  *   l3_pairs_time            device time in ms per launch over `reps` launches (hipEvents, one untimed launch first): what 0 the
  *                            whole matrix of margins, 1 the rank mode with the diagonal as truth (Nv == Na), 2 / 3 the vision / audio
- *                            projection of n_rows zero rows.  For the records under profiles/.
+ *                            projection of n_rows zero rows, 4 the top-k lists of both directions (all four launches) with the
+ *                            diagonal as truth and no groups (Nv == Na) at k = 10, or at k = n_rows when n_rows != 0, 5 the merge
+ *                            kernel of the frames' lists alone at that k.  For the records under profiles/.
+ * The order of a list.  For a query frame i the candidates are the seconds j with group_a[j] != group_v[i] -- every j when no groups
+ * are given -- and, when truth_a is given, j = truth_a[i] as well, whatever its group.  They stand in a strict total order:
+ *   1. the larger margin first, by float comparison (+0 and -0 are equal);
+ *   2. among equal margins the smaller index first;
+ *   3. a candidate whose margin is NaN is never listed.
+ * The list of i is the first k candidates of that order, in that order; a list with fewer than k candidates is filled up with index -1
+ * and margin -inf.  The other direction is the same with frames and seconds exchanged (truth_v, lists of shape (Na, k)).  Every listed
+ * margin has the bits l3_pairs_matrix and l3_pairs_list give for that pair: the same chain; fl32(u + t) is commutative, so the second
+ * direction is the same kernel with U and T exchanged.  The order is strict, so the result is a function of the inputs alone: not of
+ * the segment count, not of the order in which candidates meet inside a workgroup, not of the run.  No float atomics.
+ * k in [1, L3_PAIRS_TOPK_MAX].  A truth without groups is refused (nothing is excluded, so there is nothing to keep); group_v and
+ * group_a come together or not at all.  Truth values are checked before anything is launched.
  * L3_EINVAL (message in l3_last_error(NULL)): a NULL pointer, widths that do not match, an empty set or block, a block, a pair or a
  * truth index out of range, an l3_feat on another device.  L3_ESTATE: a call before the head or the sets it needs. */
 #define L3_PAIRS_TILE 64        /* frames and seconds of one workgroup's tile of pairs */
+#define L3_PAIRS_TOPK_MAX 64    /* entries of a top-k list: one per lane of a wave */
 typedef struct l3_pairs l3_pairs;
 int l3_pairs_create(int device, int nv, int na, int head, l3_pairs **p);
 void l3_pairs_destroy(l3_pairs *p);
@@ -1051,12 +1070,20 @@ int l3_pairs_matrix(l3_pairs *p, int64_t v0, int64_t v1, int64_t a0, int64_t a1,
 int l3_pairs_list(l3_pairs *p, const int32_t *iv, const int32_t *ia, int64_t n, float *margin_out);
 int l3_pairs_ranks(l3_pairs *p, const int32_t *truth_a, const int32_t *truth_v, const int32_t *group_v, const int32_t *group_a,
                    int32_t *rank_v2a, int32_t *rank_a2v);
+int l3_pairs_topk(l3_pairs *p, int k, const int32_t *truth_a, const int32_t *truth_v, const int32_t *group_v, const int32_t *group_a,
+                  int32_t *idx_v2a, float *margin_v2a, int32_t *idx_a2v, float *margin_a2v);
 int l3_pairs_time(l3_pairs *p, int what, int64_t n_rows, int reps, double *ms);
 /* The two kernels alone on host buffers: out (n, H) = x (n, K) w (K, H) [+ b when b != NULL]; out (Nv, Na) = the margins of u (Nv, H)
  * and t (Na, H). */
 int l3_op_project(int device, const float *x, const float *w, const float *b, int64_t n, int K, int H, float *out);
 int l3_op_pair_margins(int device, const float *u, const float *t, const float *wd, float bd, int64_t Nv, int64_t Na, int H,
                        float *out);
+/* One direction of l3_pairs_topk on projected rows from the host: the Nv rows of u are the queries, the Na rows of t the candidates
+ * (exchange them for the other direction); truth (Nv) or NULL, group_q (Nv) and group_c (Na) or both NULL; idx, margin (Nv, k).
+ * segments: into how many runs of tiles the candidates are cut, each with its own partial lists that a second kernel merges; 0 lets
+ * the library choose, as l3_pairs_topk does; a count above the number of tiles is clamped to it.  In [0, 256]. */
+int l3_op_pair_topk(int device, const float *u, const float *t, const float *wd, float bd, int64_t Nv, int64_t Na, int H, int k,
+                    const int32_t *truth, const int32_t *group_q, const int32_t *group_c, int segments, int32_t *idx, float *margin);
 
 /* ---- A group of MLP classifiers (the learning_rate x weight_decay search of classifier/train.py:638-651) ---------------------------
  * n_members models of one shape (D, C, batch) trained on ONE resident data set in the same launches: an epoch's step is seven

@@ -184,9 +184,12 @@ SIGNATURES = {
     'l3_pairs_matrix': (C.c_int, [C.c_void_p] + [C.c_int64] * 4 + [C.c_int, C.c_void_p]),
     'l3_pairs_list': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'l3_pairs_ranks': (C.c_int, [C.c_void_p] * 7),
+    'l3_pairs_topk': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8),
     'l3_pairs_time': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_double)]),
     'l3_op_project': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     'l3_op_pair_margins': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
+    'l3_op_pair_topk': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int64, C.c_int, C.c_int] +
+                        [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p]),
     'l3_frontend_cfg': (C.c_int, [C.c_int] * 5 + [C.c_void_p]),
     'l3_frontend_tables': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int64, C.POINTER(C.c_int64)]),
     'l3_op_frontend_frames': (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4),
@@ -1448,6 +1451,8 @@ def op_sample_batch(bank, records, augment=False):
 # ---- cross-modal retrieval: the AVC head over every (frame, second) pair (csrc/pairs.hip) ---------------------------
 PAIRS_TILE = 64                    # L3_PAIRS_TILE
 PAIRS_MAX_ITEMS = 65535 * PAIRS_TILE
+PAIRS_TOPK_MAX = 64                # L3_PAIRS_TOPK_MAX
+PAIRS_TOPK_MAX_SEGMENTS = 256
 
 
 def _head_width_ok(h):
@@ -1621,9 +1626,44 @@ class Pairs(object):
         check(self.lib.l3_pairs_ranks(h, _ptr(ta), _ptr(tv), _ptr(gv), _ptr(ga), _ptr(rv), _ptr(ra)))
         return rv, ra
 
+    def topk(self, k, truth_a=None, truth_v=None, groups_v=None, groups_a=None, directions=('v2a', 'a2v')):
+        """((idx_v2a, margin_v2a), (idx_a2v, margin_a2v)): for every frame its k best-scoring seconds among those of other groups
+        (all seconds without groups) plus, with truth_a, its own second truth_a[i]; for every second the frames likewise (truth_v).
+        (n, k) int32 indices and float32 margins, the larger margin first and the smaller index first among equal margins; a list
+        with fewer candidates ends in index -1 and margin -inf.  directions: 'v2a', 'a2v' or both; a direction that is not asked
+        for comes back as None, and its truth is checked but not used."""
+        self._need_sets()
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= PAIRS_TOPK_MAX:
+            raise ValueError('k must be an integer in [1, %d], not %r' % (PAIRS_TOPK_MAX, k))
+        if isinstance(directions, str):
+            directions = (directions,)
+        directions = tuple(directions)
+        if not directions or any(d not in ('v2a', 'a2v') for d in directions):
+            raise ValueError("directions must be 'v2a', 'a2v' or both, not %r" % (directions,))
+        if (groups_v is None) != (groups_a is None):
+            raise ValueError('groups_v and groups_a are given together or both left None')
+        if groups_v is None and (truth_a is not None or truth_v is not None):
+            raise ValueError('a truth without groups keeps nothing: nothing is excluded')
+        ta = None if truth_a is None else _index32(truth_a, 'truth_a', self.n_vision, self.n_audio, 'frame')
+        tv = None if truth_v is None else _index32(truth_v, 'truth_v', self.n_audio, self.n_vision, 'second')
+        gv = ga = None
+        if groups_v is not None:
+            gv = _index32(groups_v, 'groups_v', self.n_vision, 2 ** 31, 'frame')
+            ga = _index32(groups_a, 'groups_a', self.n_audio, 2 ** 31, 'second')
+        k = int(k)
+        iv = mv = ia = ma = None
+        if 'v2a' in directions:
+            iv, mv = np.empty((self.n_vision, k), np.int32), np.empty((self.n_vision, k), np.float32)
+        if 'a2v' in directions:
+            ia, ma = np.empty((self.n_audio, k), np.int32), np.empty((self.n_audio, k), np.float32)
+        h = self._handle()
+        check(self.lib.l3_pairs_topk(h, k, _ptr(ta), _ptr(tv), _ptr(gv), _ptr(ga), _ptr(iv), _ptr(mv), _ptr(ia), _ptr(ma)))
+        return (None if iv is None else (iv, mv)), (None if ia is None else (ia, ma))
+
     def time(self, what, n_rows=0, reps=10):
-        """l3_pairs_time: device ms per launch of 'matrix', 'ranks', 'project_vision' or 'project_audio' (n_rows rows)"""
-        kinds = ('matrix', 'ranks', 'project_vision', 'project_audio')
+        """l3_pairs_time: device ms per launch of 'matrix', 'ranks', 'project_vision' or 'project_audio' (n_rows rows), of 'topk'
+        (both directions, all four launches) or 'topk_merge' (the frames' merge kernel alone) at k = n_rows, 10 when that is 0"""
+        kinds = ('matrix', 'ranks', 'project_vision', 'project_audio', 'topk', 'topk_merge')
         if what not in kinds:
             raise ValueError('what must be one of %s' % (kinds,))
         ms = C.c_double()
@@ -1653,6 +1693,33 @@ def op_pair_margins(u, t, wd, bd, device=0):
     check(load().l3_op_pair_margins(int(device), _ptr(u), _ptr(t), _ptr(wd), float(np.float32(bd)), u.shape[0], t.shape[0], u.shape[1],
                                     _ptr(out)))
     return out
+
+
+def op_pair_topk(u, t, wd, bd, k, truth=None, group_q=None, group_c=None, segments=0, device=0):
+    """l3_op_pair_topk: (idx, margin), both (Nq, k): for every row of u (Nq, H) its k best-scoring rows of t (Nc, H) by the order of
+    Pairs.topk, by the top-k kernels alone.  segments: runs of candidate tiles with partial lists of their own, 0: the library's
+    choice."""
+    u, t, wd = _f32(u), _f32(t), _f32(wd)
+    if u.ndim != 2 or t.ndim != 2 or u.shape[0] < 1 or t.shape[0] < 1 or u.shape[1] != t.shape[1] or wd.shape != (u.shape[1],) or \
+            not _head_width_ok(u.shape[1]):
+        raise ValueError('need u (Nq >= 1, H), t (Nc >= 1, H) and wd (H,) with H a multiple of 32 in [32, 4096]')
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= PAIRS_TOPK_MAX:
+        raise ValueError('k must be an integer in [1, %d], not %r' % (PAIRS_TOPK_MAX, k))
+    if not 0 <= int(segments) <= PAIRS_TOPK_MAX_SEGMENTS:
+        raise ValueError('segments must be in [0, %d]' % PAIRS_TOPK_MAX_SEGMENTS)
+    if (group_q is None) != (group_c is None):
+        raise ValueError('group_q and group_c are given together or both left None')
+    if truth is not None and group_q is None:
+        raise ValueError('a truth without groups keeps nothing: nothing is excluded')
+    nq, nc = u.shape[0], t.shape[0]
+    tr = None if truth is None else _index32(truth, 'truth', nq, nc, 'query')
+    gq = gc = None
+    if group_q is not None:
+        gq, gc = _index32(group_q, 'group_q', nq, 2 ** 31, 'query'), _index32(group_c, 'group_c', nc, 2 ** 31, 'candidate')
+    idx, margin = np.empty((nq, int(k)), np.int32), np.empty((nq, int(k)), np.float32)
+    check(load().l3_op_pair_topk(int(device), _ptr(u), _ptr(t), _ptr(wd), float(np.float32(bd)), nq, nc, u.shape[1], int(k), _ptr(tr),
+                                 _ptr(gq), _ptr(gc), int(segments), _ptr(idx), _ptr(margin)))
+    return idx, margin
 
 
 # ---- downstream MLP classifier (classifier/train.py:230-391; csrc/mlp.hip) ---------------------------------------------------------

@@ -1,11 +1,14 @@
 """Cross-modal retrieval metrics of a trained AVC model over decoded clips.
 
     python -m l3embedding_amd.cli_retrieval WEIGHTS MODEL_TYPE CLIP.npz [CLIP.npz ...] [--output-path metrics.json]
+                                            [--top-k K [--lists-path lists.npz]]
 
 Each clip is an .npz holding `frames` (T, H, W, 3) uint8, `audio` (n,) or (n, C) int16 at 48 kHz and `rate` (avsample.load_clips).
 Every whole second of every clip becomes one (frame, second) item; the metrics are recall@k, median rank and mean reciprocal
 rank of the true partner among the items of the other clips, in both directions, and the AVC accuracy on the true pairs against as
-many cross-clip pairs (crossmodal.evaluate_bank).
+many cross-clip pairs (crossmodal.evaluate_bank).  --top-k K adds what was retrieved: 'lists' in the JSON, per item and direction
+the K best-scoring items of the other clips and the item's own partner, best first, as item indices (-1: none), clip ids and margins
+(-inf is written as null); --lists-path also writes them as arrays, `frame_to_audio_index` ... `audio_to_frame_margin`, `item_clip`.
 """
 import argparse
 import json
@@ -28,7 +31,13 @@ def main(argv=None):
     p.add_argument('--seed', type=int, default=0, help='of the cross-clip pairs of the AVC accuracy')
     p.add_argument('--device', type=int, default=0)
     p.add_argument('--output-path', default=None, help='also write the metrics there as JSON')
+    p.add_argument('--top-k', type=int, default=0, help='also list the K best-scoring items of every item, in both directions')
+    p.add_argument('--lists-path', default=None, help='with --top-k: also write the lists there as .npz arrays')
     args = p.parse_args(argv)
+    if args.lists_path and not args.top_k:
+        p.error('--lists-path needs --top-k')
+    if not 0 <= args.top_k <= 64:
+        p.error('--top-k must be in [1, 64]')
     pixels = samples = 0
     for path in args.clips:
         with np.load(path) as z:
@@ -39,9 +48,19 @@ def main(argv=None):
     bank = avsample.load_clips(avsample.ClipBank(args.device, pixels, samples, args.resize or None), args.clips)
     try:
         metrics = crossmodal.evaluate_bank(model, bank, fps=args.fps, ks=tuple(args.recall_at), batch_size=args.batch_size,
-                                           seed=args.seed)
+                                           seed=args.seed, topk=args.top_k)
+        item_clip = crossmodal.retrieval_records(bank.clips, fps=args.fps)[1]
     finally:
         bank.close()
+    if args.top_k:
+        lists = metrics['lists']
+        if args.lists_path:
+            arrays = {'%s_%s' % (d, f): lists[d][f] for d in lists for f in lists[d]}
+            with open(args.lists_path, 'wb') as fh:
+                np.savez(fh, item_clip=item_clip, **arrays)
+        metrics['lists'] = {d: {'index': lists[d]['index'].tolist(), 'clip': lists[d]['clip'].tolist(),
+                                'margin': [[float(m) if np.isfinite(m) else None for m in row] for row in lists[d]['margin']]}
+                            for d in lists}
     text = json.dumps(metrics, indent=2, sort_keys=True)
     print(text)
     if args.output_path:

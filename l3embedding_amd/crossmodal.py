@@ -4,8 +4,9 @@ pair of a held-out set -- the evaluation the L3 / "Objects that Sound" line of w
 The head factors over the concatenation: each tower runs once per item (`L3Model.predict_towers`, or
 `Engine.tower_features_sampled` straight from a `ClipBank`), the two halves of dense_1 are ordinary projections, and a pair costs
 `head` x (add, max, fma) on the GPU (csrc/pairs.hip).  `PairScorer` keeps the projected sets on the device and gives the matrix of
-margins (logit(corresponding) - logit(not)) in blocks, probabilities, listed pairs, and retrieval ranks in both directions without
-ever storing the matrix.
+margins (logit(corresponding) - logit(not)) in blocks, probabilities, listed pairs, and retrieval ranks and top-k lists in both
+directions without ever storing the matrix.  The lists without the truth pair are the hardest negatives (`hard_negatives`,
+`negative_records`).
 """
 import numpy as np
 
@@ -82,6 +83,18 @@ class PairScorer(object):
             raise ValueError('truth is None or the pair (truth_a, truth_v)')
         return self.handle.ranks(truth[0], truth[1], groups_v, groups_a)
 
+    def topk(self, k, truth=None, groups_v=None, groups_a=None):
+        """((idx_v2a, margin_v2a), (idx_a2v, margin_a2v)): every frame's k best-scoring seconds and every second's k best-scoring
+        frames, (n, k) each, best first (ties: the smaller index), filled up with index -1 and margin -inf; items of the query's
+        own group (clip) are skipped.  truth None: no truth pair is kept -- with groups these are the hardest negatives.  Otherwise
+        (truth_a, truth_v) as in ranks, one of them possibly None: the query's own partner stays a candidate, which gives the
+        retrieval list that goes with recall@k.  A truth needs groups."""
+        if truth is None:
+            truth = (None, None)
+        if not isinstance(truth, (tuple, list)) or len(truth) != 2:
+            raise ValueError('truth is None or the pair (truth_a, truth_v)')
+        return self.handle.topk(k, truth[0], truth[1], groups_v, groups_a)
+
     def close(self):
         self.handle.close()
 
@@ -136,11 +149,62 @@ def cross_clip_pairs(groups, n, seed=0):
     return iv, ia
 
 
-def evaluate_bank(model, bank, fps=30, ks=(1, 5, 10), batch_size=32, seed=0, return_ranks=False):
+def hard_negatives(scorer, groups, per_item):
+    """(iv, ia, margin): for every frame its `per_item` highest-scoring seconds of other clips and for every second its `per_item`
+    highest-scoring frames of other clips (scorer.topk without a truth; groups: the clip id of item i on both sides, Nv == Na),
+    concatenated frames' lists first, the fillers of short lists dropped and a pair that both directions found kept once, where it
+    first stands."""
+    nv, na = scorer.shape
+    groups = np.asarray(groups)
+    if groups.ndim != 1 or len(groups) != nv or nv != na:
+        raise ValueError('groups holds the clip of item i on both sides: %d frames and %d seconds need %d ids' % (nv, na, nv))
+    (jv, mv), (ja, ma) = scorer.topk(per_item, None, groups, groups)
+    k = jv.shape[1]
+    iv = np.concatenate([np.repeat(np.arange(nv, dtype=np.int32), k), ja.reshape(-1)])
+    ia = np.concatenate([jv.reshape(-1), np.repeat(np.arange(na, dtype=np.int32), k)])
+    m = np.concatenate([mv.reshape(-1), ma.reshape(-1)])
+    keep = np.flatnonzero((iv >= 0) & (ia >= 0))
+    _, first = np.unique(iv[keep].astype(np.int64) * na + ia[keep], return_index=True)
+    keep = keep[np.sort(first)]
+    return iv[keep].astype(np.int32), ia[keep].astype(np.int32), m[keep]
+
+
+VIDEO_FIELDS = ('video_clip', 'frame', 'start_x', 'start_y', 'flip', 'sat_first', 'saturation', 'brightness')
+AUDIO_FIELDS = ('audio_clip', 'audio_start', 'u_gain')
+
+
+def negative_records(records, iv, ia):
+    """SAMPLE records of the pairs (iv[q], ia[q]) of item records (retrieval_records): the video fields of records[iv], the audio
+    fields of records[ia], label 1 (not corresponding) -- ready for upload_batch_sampled / stage_batch_sampled."""
+    records = _lib.sample_records(records)
+    n = len(records)
+    iv, ia = np.asarray(iv), np.asarray(ia)
+    if iv.ndim != 1 or iv.shape != ia.shape or iv.dtype.kind not in 'iu' or ia.dtype.kind not in 'iu':
+        raise ValueError('iv and ia must be two equally long 1-d index arrays')
+    if len(iv) and (min(iv.min(), ia.min()) < 0 or max(iv.max(), ia.max()) >= n):
+        raise ValueError('an index outside the %d records' % n)
+    out = np.zeros(len(iv), _lib.SAMPLE_RECORD)
+    for name in VIDEO_FIELDS:
+        out[name] = records[name][iv]
+    for name in AUDIO_FIELDS:
+        out[name] = records[name][ia]
+    out['label'] = 1
+    return out
+
+
+def _lists(idx, margin, groups):
+    return {'index': idx, 'clip': np.where(idx >= 0, groups[np.maximum(idx, 0)], -1).astype(np.int32), 'margin': margin}
+
+
+def evaluate_bank(model, bank, fps=30, ks=(1, 5, 10), batch_size=32, seed=0, return_ranks=False, topk=0):
     """Retrieval over every whole second of every clip of an avsample.ClipBank: retrieval_records -> both towers' outputs of each
     record on the GPU (Engine.tower_features_sampled) -> PairScorer.ranks with the clips as groups.  Returns {'frame_to_audio',
     'audio_to_frame': retrieval_metrics, 'avc_accuracy': accuracy at margin 0 on the true pairs against as many seeded cross-clip
-    pairs, 'items', 'clips'}; with return_ranks also the two rank vectors."""
+    pairs, 'items', 'clips'}; with return_ranks also the two rank vectors.  topk > 0 adds 'lists': {'frame_to_audio', 'audio_to_frame':
+    {'index' (n, topk) the retrieved items best first (-1: none), 'clip' their clip ids (-1), 'margin'}}, the truth pair kept."""
+    topk = int(topk)
+    if not 0 <= topk <= _lib.PAIRS_TOPK_MAX:
+        raise ValueError('topk must be in [0, %d]' % _lib.PAIRS_TOPK_MAX)
     records, groups = retrieval_records(bank.clips, fps=fps)
     n = len(records)
     e = model._ensure_engine(max(1, min(batch_size, n)) if model._engine is None else model._engine.batch)
@@ -160,6 +224,9 @@ def evaluate_bank(model, bank, fps=30, ks=(1, 5, 10), batch_size=32, seed=0, ret
             out['avc_accuracy'] = float((np.sum(pos > 0) + np.sum(neg <= 0)) / (2.0 * n))
         else:
             out['avc_accuracy'] = None
+        if topk:
+            (jv, mv), (ja, ma) = scorer.topk(topk, (idx, idx), groups, groups)
+            out['lists'] = {'frame_to_audio': _lists(jv, mv, groups), 'audio_to_frame': _lists(ja, ma, groups)}
     finally:
         if scorer is not None:
             scorer.close()
