@@ -984,6 +984,17 @@ def op_conv2d_fwd_stats(x, w, b, same, stat_mode, dtype='f32', device=0):
     return y, part, mean, var
 
 
+def op_conv2d_stat_blocks(shape, cout, dtype='f32', same=True, kh=3, kw=3):
+    """The library's own count of statistics blocks (patches, flat tiles or tile blocks) of the forward launch op_conv2d_fwd makes for
+    an x of `shape` (N, H, W, Cin): the query form of op_conv2d_fwd_stats alone -- nothing is uploaded or launched."""
+    lib = load()
+    n, h, wd, cin = shape
+    nblk = C.c_int(0)
+    check(lib.l3_op_conv2d_fwd_stats(0, OP_DTYPES[dtype], None, None, None, None, None, C.byref(nblk), None, None,
+                                     n, h, wd, cin, cout, kh, kw, int(same), 1))
+    return nblk.value
+
+
 def op_conv2d_dgrad_bn_bwd(dy, w, same, bn_x, gamma, beta, mean, var, relu, bn_rows=None, dtype='f32', device=0):
     """The data gradient of the convolution with filter w (KH, KW, Cin, Cout) from dy (N, Ho, Wo, Cout), with the backward reduction
     of the BatchNorm(+ReLU) in front of the convolution -- input bn_x (N, H, W, Cin), moments over bn_rows rows (default: bn_x's) --
