@@ -1085,6 +1085,67 @@ int l3_op_pair_margins(int device, const float *u, const float *t, const float *
 int l3_op_pair_topk(int device, const float *u, const float *t, const float *wd, float bd, int64_t Nv, int64_t Na, int H, int k,
                     const int32_t *truth, const int32_t *group_q, const int32_t *group_c, int segments, int32_t *idx, float *margin);
 
+/* ---- Sound localisation maps: the AVC head at every location of a tower's last feature map (csrc/locmap.hip) ---------
+ * Both towers end in a global max pool -- the last MaxPooling2D of vision_model / audio_model reduces the feature map to 1 x 1, and
+ * model.py:25-31 concatenates the two pooled rows into dense_1 -- so a pooled feature is the maximum of a per-location activation, and
+ * the head has a value at every location: that location's C channels in place of the pooled row.  cnn_L3_melspec2: 28 x 28 image
+ * locations, 32 x 24 time-frequency locations, C = 512.  The network was trained on the pooled rows only: a map is a read-out.
+ *   l3_tower_locations_shape        H, W, C of the input of the tower's last pool (each may be NULL).  L3_EINVAL with a message when that
+ *                                   pool does not reduce to 1 x 1 or C != l3_tower_dim(e, tower): such a model (tiny_L3's vision tower)
+ *                                   has no per-location form of its head input.
+ *   l3_tower_locations_dev          the tower run as l3_tower_features_dev runs it; the H W C values of each of the n items go to rows
+ *                                   [(row0 + s) L, (row0 + s + 1) L) of dst, L = H W, a matrix with D == C: location-major (y, then x),
+ *                                   as stored.  The values are the stored ones (a bfloat16-stored map is widened, which is exact):
+ *                                   their maximum over the L rows of an item is that item's row of l3_tower_features, bit for bit.
+ *                                   Only the real items of the last engine batch are written.
+ *   l3_tower_locations_sampled_dev  the same from n >= 1 records of a bank, with the feed of l3_tower_features_sampled_dev; pooled
+ *                                   (n rows from row0; may be NULL) receives the pooled rows of the same run.
+ * Arguments and destinations are checked before anything is uploaded, with the conventions of l3_tower_features_dev.
+ *
+ * The map side of a pair handle.  One side's locations are projected like items -- vision: W1v, no bias; audio: W1a, + b1 -- into a
+ * resident matrix M (n_items L, head); the queries are the opposite projected set (side 0: l3_pairs_set_audio*, side 1:
+ * l3_pairs_set_vision*).  A (location, query) margin is the pair chain above, so it has the bits l3_pairs_list gives when that
+ * location row is set as an item.
+ *   l3_pairs_map_reserve   side 0: vision locations queried by seconds; 1: audio locations queried by frames.  n_items items of H x W
+ *                          locations, n_items H W <= 2^31 - 65.  Drops an earlier map.
+ *   l3_pairs_map_put       projects n_items L rows of loc (D == the tower's C, on the handle's device) from row lo_row into the items
+ *                          [item0, item0 + n_items) of M.  Callers put chunks: the raw locations of 64 frames are 103 MB, M is 0.4 MB a
+ *                          frame.  l3_pairs_set_head voids what was put (not the reservation); every item must be put again.
+ *   l3_pairs_map_list      listed (item, query) pairs in CSR form by item: the queries of item i are query_idx[item_ptr[i] ..
+ *                          item_ptr[i + 1]), item_ptr[0] == 0, n = item_ptr[n_items] >= 1.  For the q-th listed pair: maps (n, L) its
+ *                          map, peak[q] = max_l and arg[q] the location attaining it.  Any of the three may be NULL, not all.
+ *   l3_pairs_map_peaks     the block [i0, i1) x [j0, j1) of S_ij = max_l margin_ijl (row major, items x queries) and, when arg != NULL,
+ *                          the locations attaining it.  No map is stored.
+ *   l3_pairs_map_ranks     l3_pairs_ranks (its arguments and conventions; frames x seconds whichever side the map is) taken over S:
+ *                          the truth pairs' S by the list mode, then one counting pass with integer adds.  S is never stored; strict,
+ *                          exact and the same from run to run.
+ *   l3_pairs_map_time      device ms per launch: what 0 the list mode over the diagonal (maps and peaks stored), 1 the peaks mode over
+ *                          every (item, query), 2 the rank mode's counting pass with the diagonal as truth.  For the records.
+ * The order of a peak.  The locations l = 0 .. L-1 of a (item, query) pair stand in a strict total order:
+ *   1. the larger margin first, by float comparison (+0 and -0 are equal);
+ *   2. among equal margins the smaller location index first;
+ *   3. a location whose margin is NaN is never the peak.
+ * peak and arg are the first location's margin and index; a pair whose margins are all NaN gives peak -inf and arg -1.  The order is
+ * strict, so the result is a function of the inputs alone: not of the tiling, not of the order in which lanes meet.  No float atomics.
+ * Checked before any launch: L >= 1, indices and blocks in range, loc on the handle's device and C wide; L3_ESTATE before the head, the
+ * whole map or the query set is present.
+ * l3_op_map_list / l3_op_map_peaks: the kernel alone on host buffers, m (n_items L, H) projected locations, t (n_q, H) queries. */
+int l3_tower_locations_shape(const l3_engine *e, int tower, int *H, int *W, int *C);
+int l3_tower_locations_dev(l3_engine *e, int tower, const float *rows, int64_t n, l3_feat *dst, int64_t row0);
+int l3_tower_locations_sampled_dev(l3_engine *e, l3_clipbank *bank, const l3_sample *records, int64_t n, int tower, l3_feat *pooled,
+                                   l3_feat *loc, int64_t row0);
+int l3_pairs_map_reserve(l3_pairs *p, int side, int64_t n_items, int H, int W);
+int l3_pairs_map_put(l3_pairs *p, const l3_feat *loc, int64_t lo_row, int64_t item0, int64_t n_items);
+int l3_pairs_map_list(l3_pairs *p, const int64_t *item_ptr, const int32_t *query_idx, float *maps, float *peak, int32_t *arg);
+int l3_pairs_map_peaks(l3_pairs *p, int64_t i0, int64_t i1, int64_t j0, int64_t j1, float *S, int32_t *arg);
+int l3_pairs_map_ranks(l3_pairs *p, const int32_t *truth_a, const int32_t *truth_v, const int32_t *group_v, const int32_t *group_a,
+                       int32_t *rank_v2a, int32_t *rank_a2v);
+int l3_pairs_map_time(l3_pairs *p, int what, int reps, double *ms);
+int l3_op_map_list(int device, const float *m, const float *t, const float *wd, float bd, int64_t n_items, int64_t L, int64_t n_q, int H,
+                   const int64_t *item_ptr, const int32_t *query_idx, float *maps, float *peak, int32_t *arg);
+int l3_op_map_peaks(int device, const float *m, const float *t, const float *wd, float bd, int64_t n_items, int64_t L, int64_t n_q, int H,
+                    int64_t i0, int64_t i1, int64_t j0, int64_t j1, float *S, int32_t *arg);
+
 /* ---- A group of MLP classifiers (the learning_rate x weight_decay search of classifier/train.py:638-651) ---------------------------
  * n_members models of one shape (D, C, batch) trained on ONE resident data set in the same launches: an epoch's step is seven
  * launches whatever the number of members, and the validation pass and prediction run every member per launch too.

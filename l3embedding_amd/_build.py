@@ -17,10 +17,11 @@ LIBPATH = os.path.join(LIBDIR, 'libl3hip.so')
 # fp32-tensor entry points), first layers, BatchNorm / pool, head / loss / Adam, front-end, clip framing, image frames, resampling, the training-batch feed, engine, operator
 # entry points, RCCL, the downstream MLP and SVM classifiers, the VGGish baseline features, training-set augmentation, the
 # classifier's fold preprocessing, the SVM's scoring and sigmoid fits, the downstream random forest, the clip bank and the
-# kernels that cut training samples from it, the AVC head over every (frame, second) pair.
+# kernels that cut training samples from it, the AVC head over every (frame, second) pair and over every location of a tower's
+# last feature map.
 SOURCES = ['conv.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_bf16.hip', 'conv_bf16_halo.hip', 'conv_wgrad_bf16.hip', 'conv_wgrad_wino.hip',
            'conv_first.hip', 'conv_path.hip', 'elementwise.hip', 'bn_fused.hip', 'frontend.hip', 'clips.hip', 'frames.hip', 'resample.hip', 'batch_feed.hip', 'engine.hip', 'ops.hip',
-           'comm.hip', 'mlp.hip', 'svm.hip', 'vggish.hip', 'augment.hip', 'featprep.hip', 'svm_eval.hip', 'forest.hip', 'avsample.hip', 'pairs.hip']
+           'comm.hip', 'mlp.hip', 'svm.hip', 'vggish.hip', 'augment.hip', 'featprep.hip', 'svm_eval.hip', 'forest.hip', 'avsample.hip', 'pairs.hip', 'locmap.hip']
 # Measured-and-rejected kernel variants (split-bf16 fp32 convolutions, flat-tile MODE 5, tap-split bf16 weight gradient; round 6: the
 # filter-in-registers 64-channel halo kernel, the split-bf16 first convolution): records of negative results (profiles/r05_bx6_ablations.txt,
 # r05_bf16_conv_notes.txt, r06_halo64_regfilter.txt, r06_first_conv_mfma.txt), NOT product paths.  L3_BUILD_EXPERIMENTS=1 compiles them

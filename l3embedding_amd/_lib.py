@@ -174,6 +174,18 @@ SIGNATURES = {
     'l3_tower_features': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     'l3_tower_features_dev': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     'l3_tower_features_sampled_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_tower_locations_shape': (C.c_int, [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 3),
+    'l3_tower_locations_dev': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    'l3_tower_locations_sampled_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_pairs_map_reserve': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int]),
+    'l3_pairs_map_put': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64]),
+    'l3_pairs_map_list': (C.c_int, [C.c_void_p] * 6),
+    'l3_pairs_map_peaks': (C.c_int, [C.c_void_p] + [C.c_int64] * 4 + [C.c_void_p, C.c_void_p]),
+    'l3_pairs_map_ranks': (C.c_int, [C.c_void_p] * 7),
+    'l3_pairs_map_time': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    'l3_op_map_list': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 5),
+    'l3_op_map_peaks': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int64, C.c_int64, C.c_int] + [C.c_int64] * 4 +
+                        [C.c_void_p, C.c_void_p]),
     'l3_pairs_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     'l3_pairs_destroy': (None, [C.c_void_p]),
     'l3_pairs_set_head': (C.c_int, [C.c_void_p] * 5),
@@ -419,6 +431,7 @@ class Engine(object):
         self.lib = load()
         self.model_type = model_type
         self.batch = int(batch)
+        self.device = int(device)
         cfg = L3Config2()
         cfg.struct_size = C.sizeof(L3Config2)
         cfg.model_type = MODEL_IDS[model_type]
@@ -901,6 +914,48 @@ class Engine(object):
             raise ValueError('give vis, aud or both')
         check(self.lib.l3_tower_features_sampled_dev(self.h, bank.h, _ptr(r), len(r), None if vis is None else vis.h,
                                                      None if aud is None else aud.h, int(row0)), self.h)
+
+    def tower_locations_shape(self, tower):
+        """l3_tower_locations_shape: (H, W, C) of the input of the tower's last pool -- the locations of its last feature map.
+        ValueError for a tower whose last pool does not reduce to 1 x 1 (tiny_L3's vision tower)."""
+        if tower not in (0, 1):
+            raise ValueError('tower must be 0 (vision_model) or 1 (audio_model), not %r' % (tower,))
+        h, w, c = C.c_int(), C.c_int(), C.c_int()
+        try:
+            check(self.lib.l3_tower_locations_shape(self.h, int(tower), C.byref(h), C.byref(w), C.byref(c)), self.h)
+        except L3Error as err:
+            raise ValueError(str(err))
+        return h.value, w.value, c.value
+
+    def tower_locations(self, tower, rows, dst=None, row0=0):
+        """l3_tower_locations_dev: (n, 224, 224, 3) frames (tower 0) or (n, 1, 48000) waveforms (tower 1) -> the tower's last feature
+        map before its global max pool, one row of C channels per location: rows [(row0 + i) L, (row0 + i + 1) L) of the Features
+        dst (C columns) are item i's L = H W locations, y first.  dst None: a new Features of n L rows.  Returns dst."""
+        H, W, Cc = self.tower_locations_shape(tower)
+        x = _f32(rows)
+        n = x.shape[0]
+        per = 224 * 224 * 3 if tower == 0 else 48000
+        if x.size != n * per:
+            raise ValueError('tower %d takes rows of %d values, not an array of shape %s' % (tower, per, x.shape))
+        if dst is None:
+            if row0:
+                raise ValueError('row0 goes with dst')
+            dst = Features.alloc(max(n, 1) * H * W, Cc, device=self.device)
+        check(self.lib.l3_tower_locations_dev(self.h, int(tower), _ptr(x), n, dst.h, int(row0)), self.h)
+        return dst
+
+    def tower_locations_sampled(self, bank, records, tower, loc, pooled=None, row0=0):
+        """l3_tower_locations_sampled_dev: tower_locations of the frame (tower 0) or second (tower 1) of every record of a ClipBank
+        into the Features loc from item row0; pooled (or None) receives the tower's pooled rows of the same run from row row0.
+        Replaces the engine's resident batch."""
+        if tower not in (0, 1):
+            raise ValueError('tower must be 0 (vision_model) or 1 (audio_model), not %r' % (tower,))
+        if loc is None:
+            raise ValueError('loc must not be None')
+        r = sample_records(records)
+        check(self.lib.l3_tower_locations_sampled_dev(self.h, bank.h, _ptr(r), len(r), int(tower), None if pooled is None else pooled.h,
+                                                      loc.h, int(row0)), self.h)
+        return loc
 
     def activation(self, name):
         n = C.c_int64()
@@ -1483,6 +1538,35 @@ def _index32(a, name, n, bound, what):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+MAP_MAX_ROWS = 2 ** 31 - 1 - PAIRS_TILE          # location rows of a map; values of one call's output
+
+
+def csr_check(item_ptr, query_idx, n_items, n_queries):
+    """(item_ptr as int64, query_idx as int32) of listed (item, query) pairs in CSR form by item; ValueError unless item_ptr holds
+    n_items + 1 offsets from 0, not decreasing, ending at len(query_idx) >= 1, and every query is in [0, n_queries)"""
+    if item_ptr is None or query_idx is None:
+        raise ValueError('item_ptr and query_idx must not be None')
+    ptr, q = np.asarray(item_ptr), np.asarray(query_idx)
+    if ptr.ndim != 1 or len(ptr) != n_items + 1 or ptr.dtype.kind not in 'iu':
+        raise ValueError('item_ptr must be %d integers: one offset per item and the end' % (n_items + 1))
+    if ptr[0] != 0 or np.any(np.diff(ptr.astype(np.int64)) < 0):
+        raise ValueError('item_ptr must start at 0 and not decrease')
+    if q.ndim != 1 or len(q) < 1 or len(q) != ptr[-1]:
+        raise ValueError('query_idx must be item_ptr[-1] = %d >= 1 indices, not %s' % (int(ptr[-1]), q.shape))
+    return np.ascontiguousarray(ptr, dtype=np.int64), _index32(q, 'query_idx', len(q), n_queries, 'listed pair')
+
+
+def csr_by_item(items, n_items):
+    """Listed pairs with the item of each, in any order, repeated or absent items allowed -> (item_ptr (n_items + 1) int64, order):
+    order is the stable permutation that sorts the pairs by item, so pair order[r] stands at place r of the CSR list and a result
+    in CSR order goes back to the caller's with out[order] = result."""
+    items = _index32(items, 'items', len(items) if items is not None and np.ndim(items) == 1 else -1, n_items, 'listed pair')
+    order = np.argsort(items, kind='stable')
+    ptr = np.zeros(n_items + 1, np.int64)
+    np.cumsum(np.bincount(items, minlength=n_items), out=ptr[1:])
+    return ptr, order
+
+
 class Pairs(object):
     """RAII wrapper over an l3_pairs handle: the head and the two projected sets resident on one device.  Every argument is checked
     here first (ValueError) and the handle is created by the first call that needs the device."""
@@ -1530,6 +1614,7 @@ class Pairs(object):
         h = self._handle()
         self.head_set = False
         self.n_vision = self.n_audio = 0
+        self.map_done = set()
         check(self.lib.l3_pairs_set_head(h, *[_ptr(a) for a in arrs]))
         self.head_set = True
 
@@ -1671,6 +1756,118 @@ class Pairs(object):
         check(self.lib.l3_pairs_topk(h, k, _ptr(ta), _ptr(tv), _ptr(gv), _ptr(ga), _ptr(iv), _ptr(mv), _ptr(ia), _ptr(ma)))
         return (None if iv is None else (iv, mv)), (None if ia is None else (ia, ma))
 
+    # ---- the location map of one side (csrc/locmap.hip) ----
+    map_side = -1
+    map_items = map_done = 0
+    map_hw = (0, 0)
+
+    def map_reserve(self, side, n_items, H, W):
+        """l3_pairs_map_reserve: a map of n_items items of H x W locations; side 0: vision locations queried by the audio set, 1:
+        audio locations queried by the vision set"""
+        if side not in (0, 1):
+            raise ValueError('side must be 0 (vision locations) or 1 (audio locations), not %r' % (side,))
+        n_items, H, W = int(n_items), int(H), int(W)
+        if n_items < 1 or H < 1 or W < 1 or n_items * H * W > MAP_MAX_ROWS:
+            raise ValueError('need n_items >= 1 and H, W >= 1 with n_items H W <= %d; got %d items of %d x %d' % (MAP_MAX_ROWS, n_items, H, W))
+        h = self._handle()
+        self.map_side = -1
+        check(self.lib.l3_pairs_map_reserve(h, int(side), n_items, H, W))
+        self.map_side, self.map_items, self.map_hw, self.map_done = int(side), n_items, (H, W), set()
+
+    def map_put(self, loc, lo_row, item0, n_items):
+        """l3_pairs_map_put: the n_items H W rows of the Features loc from row lo_row -> the items [item0, item0 + n_items) of the map"""
+        if self.map_side < 0:
+            raise ValueError('map_reserve comes before map_put')
+        if not self.head_set:
+            raise ValueError('set_head comes before map_put')
+        if not isinstance(loc, Features) or not loc.h:
+            raise ValueError('the location rows must be an open Features')
+        if loc.device != self.device:
+            raise ValueError('the location rows are on device %d, the scorer on device %d' % (loc.device, self.device))
+        width = self.nv if self.map_side == 0 else self.na
+        n, d = loc.shape
+        lo_row, item0, n_items = int(lo_row), int(item0), int(n_items)
+        L = self.map_hw[0] * self.map_hw[1]
+        if d != width:
+            raise ValueError('the location rows have %d columns, the tower\'s last feature map %d channels' % (d, width))
+        if n_items < 1 or item0 < 0 or item0 + n_items > self.map_items:
+            raise ValueError('items [%d, %d) are empty or outside the %d items of the map' % (item0, item0 + n_items, self.map_items))
+        if lo_row < 0 or lo_row + n_items * L > n:
+            raise ValueError('rows [%d, %d) outside the %d rows of the location matrix' % (lo_row, lo_row + n_items * L, n))
+        check(self.lib.l3_pairs_map_put(self._handle(), loc.h, lo_row, item0, n_items))
+        self.map_done.update(range(item0, item0 + n_items))
+
+    @property
+    def map_queries(self):
+        """the number of queries of the map: the size of the opposite set"""
+        return self.n_audio if self.map_side == 0 else self.n_vision
+
+    def _need_map(self):
+        if not self.head_set or self.map_side < 0 or len(self.map_done) != self.map_items or self.map_queries < 1:
+            raise ValueError('set_head, map_reserve, map_put of every item and the query set (set_%s) come first' %
+                             ('audio' if self.map_side == 0 else 'vision'))
+
+    def map_list(self, item_ptr, query_idx, maps=True, peaks=True):
+        """l3_pairs_map_list: the listed (item, query) pairs in CSR form by item (item_ptr: map_items + 1 offsets into query_idx) ->
+        (maps (n, L) or None, peak (n,) or None, arg (n,) or None) in the order of query_idx"""
+        self._need_map()
+        if not maps and not peaks:
+            raise ValueError('maps, peaks or both')
+        ptr, q = csr_check(item_ptr, query_idx, self.map_items, self.map_queries)
+        n, L = len(q), self.map_hw[0] * self.map_hw[1]
+        if maps and n * L > MAP_MAX_ROWS:
+            raise ValueError('%d maps of %d locations are more than %d values: list fewer pairs a call' % (n, L, MAP_MAX_ROWS))
+        m = np.empty((n, L), np.float32) if maps else None
+        pk = np.empty(n, np.float32) if peaks else None
+        ar = np.empty(n, np.int32) if peaks else None
+        check(self.lib.l3_pairs_map_list(self._handle(), _ptr(ptr), _ptr(q), _ptr(m), _ptr(pk), _ptr(ar)))
+        return m, pk, ar
+
+    def map_peaks(self, i0=0, i1=None, j0=0, j1=None):
+        """l3_pairs_map_peaks: (S, arg) of the block [i0, i1) x [j0, j1) of items x queries: S_ij = max over item i's locations of
+        the margin with query j, arg the location attaining it (-1: every margin NaN)"""
+        self._need_map()
+        i1 = self.map_items if i1 is None else int(i1)
+        j1 = self.map_queries if j1 is None else int(j1)
+        i0, j0 = int(i0), int(j0)
+        if i0 < 0 or i1 > self.map_items or i0 >= i1 or j0 < 0 or j1 > self.map_queries or j0 >= j1 or (i1 - i0) * (j1 - j0) > MAP_MAX_ROWS:
+            raise ValueError('the block [%d, %d) x [%d, %d) is empty, too large or outside the %d items x %d queries' %
+                             (i0, i1, j0, j1, self.map_items, self.map_queries))
+        S, arg = np.empty((i1 - i0, j1 - j0), np.float32), np.empty((i1 - i0, j1 - j0), np.int32)
+        check(self.lib.l3_pairs_map_peaks(self._handle(), i0, i1, j0, j1, _ptr(S), _ptr(arg)))
+        return S, arg
+
+    def map_ranks(self, truth_a=None, truth_v=None, group_v=None, group_a=None):
+        """l3_pairs_map_ranks: Pairs.ranks over S, the best-location score of every (frame, second) pair; frames x seconds whichever
+        side the map is: the map's items stand for their side's set"""
+        self._need_map()
+        nv, na = (self.map_items, self.n_audio) if self.map_side == 0 else (self.n_vision, self.map_items)
+        if truth_a is None and truth_v is None:
+            raise ValueError('truth_a, truth_v or both are needed')
+        if (group_v is None) != (group_a is None):
+            raise ValueError('group_v and group_a are given together or both left None')
+        ta = None if truth_a is None else _index32(truth_a, 'truth_a', nv, na, 'frame')
+        tv = None if truth_v is None else _index32(truth_v, 'truth_v', na, nv, 'second')
+        gv = ga = None
+        if group_v is not None:
+            gv = _index32(group_v, 'group_v', nv, 2 ** 31, 'frame')
+            ga = _index32(group_a, 'group_a', na, 2 ** 31, 'second')
+        rv = None if ta is None else np.empty(nv, np.int32)
+        ra = None if tv is None else np.empty(na, np.int32)
+        check(self.lib.l3_pairs_map_ranks(self._handle(), _ptr(ta), _ptr(tv), _ptr(gv), _ptr(ga), _ptr(rv), _ptr(ra)))
+        return rv, ra
+
+    def map_time(self, what, reps=10):
+        """l3_pairs_map_time: device ms per launch of 'list' (the diagonal, maps stored), 'peaks' (every pair) or 'ranks' (the
+        counting pass, the diagonal as truth)"""
+        kinds = ('list', 'peaks', 'ranks')
+        if what not in kinds:
+            raise ValueError('what must be one of %s' % (kinds,))
+        self._need_map()
+        ms = C.c_double()
+        check(self.lib.l3_pairs_map_time(self._handle(), kinds.index(what), int(reps), C.byref(ms)))
+        return ms.value
+
     def time(self, what, n_rows=0, reps=10):
         """l3_pairs_time: device ms per launch of 'matrix', 'ranks', 'project_vision' or 'project_audio' (n_rows rows), of 'topk'
         (both directions, all four launches) or 'topk_merge' (the frames' merge kernel alone) at k = n_rows, 10 when that is 0"""
@@ -1704,6 +1901,48 @@ def op_pair_margins(u, t, wd, bd, device=0):
     check(load().l3_op_pair_margins(int(device), _ptr(u), _ptr(t), _ptr(wd), float(np.float32(bd)), u.shape[0], t.shape[0], u.shape[1],
                                     _ptr(out)))
     return out
+
+
+def _op_map_args(m, t, wd, L):
+    m, t, wd = _f32(m), _f32(t), _f32(wd)
+    L = int(L)
+    if m.ndim != 2 or t.ndim != 2 or L < 1 or m.shape[0] < 1 or m.shape[0] % L or t.shape[0] < 1 or m.shape[1] != t.shape[1] or \
+            wd.shape != (m.shape[1],) or not _head_width_ok(m.shape[1]) or m.shape[0] > MAP_MAX_ROWS:
+        raise ValueError('need m (n_items L, H), t (n_q >= 1, H) and wd (H,) with L >= 1 and H a multiple of 32 in [32, 4096]')
+    return m, t, wd, L, m.shape[0] // L
+
+
+def op_map_list(m, t, wd, bd, L, item_ptr, query_idx, maps=True, peaks=True, device=0):
+    """l3_op_map_list: (maps (n, L) | None, peak | None, arg | None) of the listed (item, query) pairs (CSR by item) of projected
+    location rows m (n_items L, H) and query rows t (n_q, H), by the map kernel alone"""
+    m, t, wd, L, n_items = _op_map_args(m, t, wd, L)
+    if not maps and not peaks:
+        raise ValueError('maps, peaks or both')
+    ptr, q = csr_check(item_ptr, query_idx, n_items, t.shape[0])
+    n = len(q)
+    if maps and n * L > MAP_MAX_ROWS:
+        raise ValueError('%d maps of %d locations are more than %d values' % (n, L, MAP_MAX_ROWS))
+    mp = np.empty((n, L), np.float32) if maps else None
+    pk = np.empty(n, np.float32) if peaks else None
+    ar = np.empty(n, np.int32) if peaks else None
+    check(load().l3_op_map_list(int(device), _ptr(m), _ptr(t), _ptr(wd), float(np.float32(bd)), n_items, L, t.shape[0], m.shape[1],
+                                _ptr(ptr), _ptr(q), _ptr(mp), _ptr(pk), _ptr(ar)))
+    return mp, pk, ar
+
+
+def op_map_peaks(m, t, wd, bd, L, i0=0, i1=None, j0=0, j1=None, device=0):
+    """l3_op_map_peaks: (S, arg) of the block [i0, i1) x [j0, j1) of items x queries, by the map kernel alone"""
+    m, t, wd, L, n_items = _op_map_args(m, t, wd, L)
+    i1 = n_items if i1 is None else int(i1)
+    j1 = t.shape[0] if j1 is None else int(j1)
+    i0, j0 = int(i0), int(j0)
+    if i0 < 0 or i1 > n_items or i0 >= i1 or j0 < 0 or j1 > t.shape[0] or j0 >= j1 or (i1 - i0) * (j1 - j0) > MAP_MAX_ROWS:
+        raise ValueError('the block [%d, %d) x [%d, %d) is empty, too large or outside the %d items x %d queries' %
+                         (i0, i1, j0, j1, n_items, t.shape[0]))
+    S, arg = np.empty((i1 - i0, j1 - j0), np.float32), np.empty((i1 - i0, j1 - j0), np.int32)
+    check(load().l3_op_map_peaks(int(device), _ptr(m), _ptr(t), _ptr(wd), float(np.float32(bd)), n_items, L, t.shape[0], m.shape[1],
+                                 i0, i1, j0, j1, _ptr(S), _ptr(arg)))
+    return S, arg
 
 
 def op_pair_topk(u, t, wd, bd, k, truth=None, group_q=None, group_c=None, segments=0, device=0):

@@ -1,7 +1,7 @@
 """Cross-modal retrieval metrics of a trained AVC model over decoded clips.
 
     python -m l3embedding_amd.cli_retrieval WEIGHTS MODEL_TYPE CLIP.npz [CLIP.npz ...] [--output-path metrics.json]
-                                            [--top-k K [--lists-path lists.npz]]
+                                            [--top-k K [--lists-path lists.npz]] [--maps-path maps.npz [--maps-top K]]
 
 Each clip is an .npz holding `frames` (T, H, W, 3) uint8, `audio` (n,) or (n, C) int16 at 48 kHz and `rate` (avsample.load_clips).
 Every whole second of every clip becomes one (frame, second) item; the metrics are recall@k, median rank and mean reciprocal
@@ -9,6 +9,10 @@ rank of the true partner among the items of the other clips, in both directions,
 many cross-clip pairs (crossmodal.evaluate_bank).  --top-k K adds what was retrieved: 'lists' in the JSON, per item and direction
 the K best-scoring items of the other clips and the item's own partner, best first, as item indices (-1: none), clip ids and margins
 (-inf is written as null); --lists-path also writes them as arrays, `frame_to_audio_index` ... `audio_to_frame_margin`, `item_clip`.
+--maps-path FILE.npz adds 'peak' to the JSON -- the same metrics when a pair is scored by the best of the frame's 28 x 28 image
+locations -- and writes `truth_map` (n, H, W), `truth_peak`, `truth_arg` (the location y W + x) of every true pair,
+`peak_rank_v2a`, `peak_rank_a2v` and `item_clip`; with --maps-top K (<= --top-k) also `top_map` (n, K, H, W), `top_peak`, `top_arg`
+of each frame's K retrieved seconds.
 """
 import argparse
 import json
@@ -33,9 +37,16 @@ def main(argv=None):
     p.add_argument('--output-path', default=None, help='also write the metrics there as JSON')
     p.add_argument('--top-k', type=int, default=0, help='also list the K best-scoring items of every item, in both directions')
     p.add_argument('--lists-path', default=None, help='with --top-k: also write the lists there as .npz arrays')
+    p.add_argument('--maps-path', default=None, help='also score every pair by its best image location and write the localisation '
+                                                      'maps, peaks and peak locations of every true pair there as .npz arrays')
+    p.add_argument('--maps-top', type=int, default=0, help='with --maps-path and --top-k: also those of each frame\'s K retrieved seconds')
     args = p.parse_args(argv)
     if args.lists_path and not args.top_k:
         p.error('--lists-path needs --top-k')
+    if args.maps_top and not args.maps_path:
+        p.error('--maps-top needs --maps-path')
+    if not 0 <= args.maps_top <= args.top_k:
+        p.error('--maps-top must be in [0, --top-k]')
     if not 0 <= args.top_k <= 64:
         p.error('--top-k must be in [1, 64]')
     pixels = samples = 0
@@ -47,11 +58,19 @@ def main(argv=None):
     model.device = args.device
     bank = avsample.load_clips(avsample.ClipBank(args.device, pixels, samples, args.resize or None), args.clips)
     try:
+        extra = {'peak': True, 'maps_top': args.maps_top} if args.maps_path else {}
         metrics = crossmodal.evaluate_bank(model, bank, fps=args.fps, ks=tuple(args.recall_at), batch_size=args.batch_size,
-                                           seed=args.seed, topk=args.top_k)
+                                           seed=args.seed, topk=args.top_k, **extra)
         item_clip = crossmodal.retrieval_records(bank.clips, fps=args.fps)[1]
     finally:
         bank.close()
+    if args.maps_path:
+        maps = metrics.pop('maps')
+        arrays = {'%s_%s' % (w, f): maps[w][f] for w in maps for f in maps[w]}
+        for name in ('rank_v2a', 'rank_a2v'):
+            arrays['peak_' + name] = metrics['peak'].pop(name)
+        with open(args.maps_path, 'wb') as fh:
+            np.savez(fh, item_clip=item_clip, **arrays)
     if args.top_k:
         lists = metrics['lists']
         if args.lists_path:

@@ -5,7 +5,8 @@ The head factors over the concatenation: each tower runs once per
 `Engine.tower_features_sampled` straight from a `ClipBank`), the two halves of dense_1 are ordinary projections, and a pair costs
 `head` x (add, max, fma) on the GPU (csrc/pairs.hip).  `PairScorer` keeps the projected sets on the device and gives the matrix of
 margins (logit(corresponding) - logit(not)) in blocks, probabilities, listed pairs, and retrieval ranks and top-k lists in both
-directions without ever storing the matrix.  The lists without the truth pair are the hardest negatives (`hard_negatives`,
+directions without ever storing the matrix.  `set_maps` puts one side's last feature map there location by location: `maps` are the
+sound localisation maps of listed pairs, `peaks` / `peak_ranks` score a pair by its best location (csrc/locmap.hip).  The lists without the truth pair are the hardest negatives (`hard_negatives`,
 `negative_records`).
 """
 import numpy as np
@@ -24,6 +25,7 @@ class PairScorer(object):
         w1, b1, w2, b2 = (np.asarray(P[k], np.float32) for k in ('dense_1/kernel', 'dense_1/bias', 'dense_2/kernel', 'dense_2/bias'))
         nv = 360 if model.model_type == 'tiny_L3' else 512          # the vision tower's flattened output (TowerModel)
         self.device = model.device if device is None else int(device)
+        self.model = model
         self.handle = _lib.Pairs(nv, w1.shape[0] - nv, w1.shape[1], device=self.device)
         self.handle.set_head(w1, b1, w2, b2)
 
@@ -95,8 +97,146 @@ class PairScorer(object):
             raise ValueError('truth is None or the pair (truth_a, truth_v)')
         return self.handle.topk(k, truth[0], truth[1], groups_v, groups_a)
 
+    # ---- sound localisation maps: the head at every location of one side's last feature map ----
+    def set_maps(self, side, source, chunk_items=64):
+        """The location map of one side: 0 the frames' image locations, queried by the seconds of set_items(A=...); 1 the seconds'
+        time-frequency locations, queried by the frames.  source: the model's input rows ((n, 224, 224, 3) frames / (n, 1, 48000)
+        waveforms), (bank, records) of an avsample.ClipBank, or (location rows, (H, W)) as L3Model.predict_locations returns them.
+        The towers run chunk_items items at a time and only the projected rows stay: 0.4 MB a frame against 1.6 MB of raw
+        locations."""
+        if side not in (0, 1):
+            raise ValueError('side must be 0 (vision locations) or 1 (audio locations), not %r' % (side,))
+        chunk = int(chunk_items)
+        if chunk < 1:
+            raise ValueError('chunk_items must be >= 1')
+        pair = isinstance(source, (tuple, list)) and len(source) == 2
+        if pair and isinstance(self._rows(source[0]), _lib.Features):
+            loc, (H, W) = self._rows(source[0]), source[1]
+            H, W = int(H), int(W)
+            rows = loc.shape[0]
+            if H < 1 or W < 1 or rows < 1 or rows % (H * W):
+                raise ValueError('%d location rows are not a whole number of %d x %d maps' % (rows, H, W))
+            n = rows // (H * W)
+            self.handle.map_reserve(side, n, H, W)
+            for i0 in range(0, n, chunk):
+                self.handle.map_put(loc, i0 * H * W, i0, min(chunk, n - i0))
+            return self
+        if pair:
+            bank, records = source[0], _lib.sample_records(source[1])
+            n = len(records)
+        else:
+            bank, records = None, np.ascontiguousarray(source, dtype=np.float32)
+            n = len(records)
+        if n < 1:
+            raise ValueError('the source holds no items')
+        model = self.model
+        e = model._ensure_engine(max(1, min(32, n)) if model._engine is None else model._engine.batch)
+        H, W, C = e.tower_locations_shape(side)
+        self.handle.map_reserve(side, n, H, W)
+        buf = _lib.Features.alloc(min(chunk, n) * H * W, C, device=self.device)
+        try:
+            for i0 in range(0, n, chunk):
+                i1 = min(n, i0 + chunk)
+                if bank is not None:
+                    e.tower_locations_sampled(bank, records[i0:i1], side, buf)
+                else:
+                    e.tower_locations(side, records[i0:i1], dst=buf)
+                self.handle.map_put(buf, 0, i0, i1 - i0)
+        finally:
+            buf.close()
+        return self
+
+    def _map_pairs(self, iv, ia):
+        side = self.handle.map_side
+        if side < 0:
+            raise ValueError('set_maps comes first')
+        n = len(iv) if iv is not None and np.ndim(iv) == 1 else -1
+        if n < 1 or ia is None or np.ndim(ia) != 1 or len(ia) != n:
+            raise ValueError('iv and ia must be two equally long, non-empty 1-d index arrays')
+        items, queries = (iv, ia) if side == 0 else (ia, iv)
+        queries = _lib._index32(queries, 'ia' if side == 0 else 'iv', n, self.handle.map_queries, 'pair')
+        ptr, order = _lib.csr_by_item(items, self.handle.map_items)
+        return ptr, order, queries[order]
+
+    def maps(self, iv, ia, peaks=False):
+        """The maps of the listed pairs (frame iv[q], second ia[q]) in the caller's order: (Q, H, W) margins over the locations of
+        the map's side -- of frame iv[q] scored against second ia[q] (side 0), or of second ia[q] against frame iv[q] (side 1).
+        peaks: (maps, peak (Q,), arg (Q,)) with the best location's margin and index y W + x (-1: every margin NaN)."""
+        ptr, order, q = self._map_pairs(iv, ia)
+        H, W = self.handle.map_hw
+        m, pk, ar = self.handle.map_list(ptr, q, maps=True, peaks=bool(peaks))
+        out = np.empty_like(m)
+        out[order] = m
+        out = out.reshape(len(q), H, W)
+        if not peaks:
+            return out
+        peak, arg = np.empty_like(pk), np.empty_like(ar)
+        peak[order], arg[order] = pk, ar
+        return out, peak, arg
+
+    def pair_peaks(self, iv, ia):
+        """(peak, arg) of the listed pairs without their maps"""
+        ptr, order, q = self._map_pairs(iv, ia)
+        _, pk, ar = self.handle.map_list(ptr, q, maps=False, peaks=True)
+        peak, arg = np.empty_like(pk), np.empty_like(ar)
+        peak[order], arg[order] = pk, ar
+        return peak, arg
+
+    def peaks(self, block_bytes=256 << 20):
+        """(S, arg), both (Nv, Na): the best-location margin of every (frame, second) pair and the location attaining it, downloaded
+        in blocks of whole items of at most block_bytes; no map is stored anywhere"""
+        h = self.handle
+        if h.map_side < 0:
+            raise ValueError('set_maps comes first')
+        ni, nq = h.map_items, h.map_queries
+        rows = max(1, int(block_bytes) // (8 * max(nq, 1)))
+        S, arg = np.empty((ni, nq), np.float32), np.empty((ni, nq), np.int32)
+        for i0 in range(0, ni, rows):
+            i1 = min(ni, i0 + rows)
+            S[i0:i1], arg[i0:i1] = h.map_peaks(i0, i1, 0, nq)
+        return (S, arg) if h.map_side == 0 else (np.ascontiguousarray(S.T), np.ascontiguousarray(arg.T))
+
+    def peak_ranks(self, truth=None, groups_v=None, groups_a=None):
+        """ranks() under best-location scoring: the score of a (frame, second) pair is the maximum of its map"""
+        h = self.handle
+        if h.map_side < 0:
+            raise ValueError('set_maps comes first')
+        nv, na = (h.map_items, h.n_audio) if h.map_side == 0 else (h.n_vision, h.map_items)
+        if truth is None:
+            if nv != na:
+                raise ValueError('truth=None pairs frame i with second i and needs Nv == Na, not %d and %d' % (nv, na))
+            truth = (np.arange(nv, dtype=np.int32), np.arange(na, dtype=np.int32))
+        if not isinstance(truth, (tuple, list)) or len(truth) != 2:
+            raise ValueError('truth is None or the pair (truth_a, truth_v)')
+        return h.map_ranks(truth[0], truth[1], groups_v, groups_a)
+
     def close(self):
         self.handle.close()
+
+
+def upsample_map(m, size):
+    """A map (..., H, W) -> (..., size[0], size[1]) for laying it over the frame it belongs to (28 x 28 -> 224 x 224): separable
+    linear interpolation with half-pixel centres -- output pixel y samples the input at (y + 0.5) H / size[0] - 0.5 -- and the
+    edges clamped.  Host NumPy, in float64; returned as float32 unless m is float64."""
+    m = np.asarray(m)
+    if isinstance(size, (int, np.integer)):
+        size = (size, size)
+    if m.ndim < 2 or m.shape[-1] < 1 or m.shape[-2] < 1 or m.dtype.kind != 'f':
+        raise ValueError('m must be a float array (..., H, W)')
+    if len(size) != 2 or int(size[0]) < 1 or int(size[1]) < 1:
+        raise ValueError('size must be (height, width) >= 1')
+
+    def taps(n_in, n_out):
+        x = np.clip((np.arange(n_out) + 0.5) * n_in / n_out - 0.5, 0.0, n_in - 1.0)
+        lo = np.floor(x).astype(np.int64)
+        hi = np.minimum(lo + 1, n_in - 1)
+        A = np.zeros((n_out, n_in))
+        np.add.at(A, (np.arange(n_out), lo), 1.0 - (x - lo))
+        np.add.at(A, (np.arange(n_out), hi), x - lo)
+        return A
+
+    out = taps(m.shape[-2], int(size[0])) @ m.astype(np.float64) @ taps(m.shape[-1], int(size[1])).T
+    return out if m.dtype == np.float64 else out.astype(np.float32)
 
 
 def retrieval_metrics(ranks, ks=(1, 5, 10)):
@@ -196,12 +336,19 @@ def _lists(idx, margin, groups):
     return {'index': idx, 'clip': np.where(idx >= 0, groups[np.maximum(idx, 0)], -1).astype(np.int32), 'margin': margin}
 
 
-def evaluate_bank(model, bank, fps=30, ks=(1, 5, 10), batch_size=32, seed=0, return_ranks=False, topk=0):
+def evaluate_bank(model, bank, fps=30, ks=(1, 5, 10), batch_size=32, seed=0, return_ranks=False, topk=0, peak=False, maps_top=None):
     """Retrieval over every whole second of every clip of an avsample.ClipBank: retrieval_records -> both towers' outputs of each
     record on the GPU (Engine.tower_features_sampled) -> PairScorer.ranks with the clips as groups.  Returns {'frame_to_audio',
     'audio_to_frame': retrieval_metrics, 'avc_accuracy': accuracy at margin 0 on the true pairs against as many seeded cross-clip
     pairs, 'items', 'clips'}; with return_ranks also the two rank vectors.  topk > 0 adds 'lists': {'frame_to_audio', 'audio_to_frame':
-    {'index' (n, topk) the retrieved items best first (-1: none), 'clip' their clip ids (-1), 'margin'}}, the truth pair kept."""
+    {'index' (n, topk) the retrieved items best first (-1: none), 'clip' their clip ids (-1), 'margin'}}, the truth pair kept.
+    peak adds 'peak': {'frame_to_audio', 'audio_to_frame': retrieval_metrics of the same ranks under best-location scoring -- a
+    pair's score is the maximum of the head over the frame's image locations (PairScorer.peak_ranks) --, 'rank_v2a',
+    'rank_a2v' the rank vectors}.  maps_top (needs peak; an integer >= 0) adds 'maps': {'truth': {'map' (n, H, W), 'peak', 'arg'} of
+    every true pair and, when maps_top > 0 (needs topk >= maps_top), 'top': the same with a leading (n, maps_top) for each frame's
+    first maps_top retrieved seconds (an empty slot: NaN maps, peak -inf, arg -1)}."""
+    if maps_top is not None and (not peak or int(maps_top) < 0 or int(maps_top) > int(topk)):
+        raise ValueError('maps_top needs peak=True and 0 <= maps_top <= topk')
     topk = int(topk)
     if not 0 <= topk <= _lib.PAIRS_TOPK_MAX:
         raise ValueError('topk must be in [0, %d]' % _lib.PAIRS_TOPK_MAX)
@@ -227,6 +374,23 @@ def evaluate_bank(model, bank, fps=30, ks=(1, 5, 10), batch_size=32, seed=0, ret
         if topk:
             (jv, mv), (ja, ma) = scorer.topk(topk, (idx, idx), groups, groups)
             out['lists'] = {'frame_to_audio': _lists(jv, mv, groups), 'audio_to_frame': _lists(ja, ma, groups)}
+        if peak:
+            scorer.set_maps(0, (bank, records), chunk_items=max(1, min(64, e.batch)))
+            pv, pa = scorer.peak_ranks(None, groups, groups)
+            out['peak'] = {'frame_to_audio': retrieval_metrics(pv, ks), 'audio_to_frame': retrieval_metrics(pa, ks),
+                           'rank_v2a': pv, 'rank_a2v': pa}
+        if maps_top is not None:
+            m, pk, ar = scorer.maps(idx, idx, peaks=True)
+            out['maps'] = {'truth': {'map': m, 'peak': pk, 'arg': ar}}
+            K = int(maps_top)
+            if K:
+                j = out['lists']['frame_to_audio']['index'][:, :K]
+                have = np.flatnonzero(j.reshape(-1) >= 0)
+                tm = np.full((n * K,) + m.shape[1:], np.nan, np.float32)
+                tp, ta = np.full(n * K, -np.inf, np.float32), np.full(n * K, -1, np.int32)
+                if len(have):
+                    tm[have], tp[have], ta[have] = scorer.maps(np.repeat(idx, K)[have], j.reshape(-1)[have], peaks=True)
+                out['maps']['top'] = {'map': tm.reshape((n, K) + m.shape[1:]), 'peak': tp.reshape(n, K), 'arg': ta.reshape(n, K)}
     finally:
         if scorer is not None:
             scorer.close()

@@ -1037,4 +1037,12 @@ void cast_bf16(const float* x, void* y, int64_t n, hipStream_t s) {
     hipLaunchKernelGGL(cast_bf16_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, x, (__bf16*)y, n);
 }
 
+// bfloat16 storage -> fp32 (exact): a bfloat16-stored activation handed out as float rows (l3_tower_locations_dev)
+__global__ __launch_bounds__(256) void widen_bf16_kernel(const uint16_t* x, float* y, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = __uint_as_float((uint32_t)x[i] << 16);
+}
+void widen_bf16_dev(const void* x, float* y, int64_t n, hipStream_t s) {
+    hipLaunchKernelGGL(widen_bf16_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, (const uint16_t*)x, y, n);
+}
+
 }  // namespace l3

@@ -3093,6 +3093,160 @@ int l3_tower_features_sampled_dev(l3_engine* e, l3_clipbank* bank, const l3_samp
     return L3_OK;
 }
 
+// ---- a tower's last feature map, location by location ------------------------------------------------------------------
+// The input of the tower's last pool -- the last BatchNorm's output after its ReLU, which no kernel fuses with that pool (the folded
+// form needs a 2 x 2 pool and a following op) -- is materialised after every solo forward.  It is the per-location form of the head's
+// input only when that pool reduces it to 1 x 1 and the pooled row is the tower's whole output.
+static int locations_tensor(const l3_engine* e, int tower, const Tensor** out, std::string* why) {
+    if (tower != 0 && tower != 1) {
+        *why = "tower must be 0 (vision_model) or 1 (audio_model), not " + std::to_string(tower);
+        return L3_EINVAL;
+    }
+    const Tower& tw = tower == 0 ? e->vis : e->aud;
+    const Op& pool = tw.ops.back();
+    const Tensor &x = tw.t[pool.in], &y = tw.t[pool.out];
+    const int width = tower == 0 ? e->nv : e->na;
+    if (pool.kind != OP_POOL || y.H != 1 || y.W != 1 || x.C != width || x.d == nullptr) {
+        *why = tw.prefix + ": the last pool leaves " + std::to_string(y.H) + " x " + std::to_string(y.W) + " x " + std::to_string(y.C) +
+               " values of the tower's " + std::to_string(width) + ", not 1 x 1: the head's input has no per-location form";
+        return L3_EINVAL;
+    }
+    *out = &x;
+    return L3_OK;
+}
+
+int l3_tower_locations_shape(const l3_engine* e, int tower, int* H, int* W, int* C) {
+    if (!e) return L3_EINVAL;
+    const Tensor* x = nullptr;
+    std::string why;
+    if (int rc = locations_tensor(e, tower, &x, &why)) {
+        const_cast<l3_engine*>(e)->err = "l3_tower_locations_shape: " + why;
+        return rc;
+    }
+    if (H) *H = x->H;
+    if (W) *W = x->W;
+    if (C) *C = x->C;
+    return L3_OK;
+}
+
+// The `cnt` real items of the current batch -> the location rows of items [r0, r0 + cnt) of the destination, on the engine's stream
+static int tower_locations_out(l3_engine* e, const Tensor& x, int64_t r0, int64_t cnt, const EmbedDest& dst) {
+    const size_t per = (size_t)x.H * x.W * x.C;
+    float* to = dst.feat->x + (size_t)(dst.row0 + r0 * x.H * x.W) * x.C;
+    if (x.d_bf16)
+        widen_bf16_dev(x.d, to, (int64_t)(cnt * per), e->stream);
+    else
+        HIPCHK(e, hipMemcpyAsync(to, x.d, (size_t)cnt * per * 4, hipMemcpyDeviceToDevice, e->stream));
+    return L3_OK;
+}
+
+// the destination of n items' location rows from item row0: dst.row0 counts rows of the matrix
+static int locations_dest(l3_engine* e, const char* fn, const Tensor& x, l3_feat* feat, int64_t n, int64_t row0, EmbedDest* dst) {
+    const int64_t L = (int64_t)x.H * x.W;
+    if (row0 < 0 || row0 > INT64_MAX / L || n > INT64_MAX / L) {
+        e->err = std::string(fn) + ": row0 or n out of range";
+        return L3_EINVAL;
+    }
+    dst->dev = true, dst->feat = feat, dst->row0 = row0 * L;
+    return embed_dest_check(e, fn, *dst, n * L, x.C);
+}
+
+int l3_tower_locations_dev(l3_engine* e, int tower, const float* rows, int64_t n, l3_feat* dst_feat, int64_t row0) {
+    if (!e) return L3_EINVAL;
+    const char* fn = "l3_tower_locations_dev";
+    const std::string name(fn);
+    const Tensor* x = nullptr;
+    std::string why;
+    int rc = locations_tensor(e, tower, &x, &why);
+    if (rc) {
+        e->err = name + ": " + why;
+        return rc;
+    }
+    if (!rows || !dst_feat) {
+        e->err = name + ": rows and dst must not be NULL";
+        return L3_EINVAL;
+    }
+    if (n < 0) {
+        e->err = name + ": n must be >= 0";
+        return L3_EINVAL;
+    }
+    EmbedDest dst;
+    if ((rc = locations_dest(e, fn, *x, dst_feat, n, row0, &dst))) return rc;
+    if (n == 0) return L3_OK;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    EmbedSource src;
+    src.host = rows;
+    for (int64_t s0 = 0; s0 < n; s0 += e->B) {
+        const int64_t cnt = n - s0 < e->B ? n - s0 : e->B;
+        if ((rc = solo_tower_batch(e, tower == 0, src, s0, cnt))) return rc;
+        if ((rc = tower_locations_out(e, *x, s0, cnt, dst))) return rc;
+    }
+    HIPCHK(e, l3::stream_wait(e->stream));
+    e->fwd_done = false;
+    prof_collect(e);
+    return L3_OK;
+}
+
+int l3_tower_locations_sampled_dev(l3_engine* e, l3_clipbank* bank, const l3_sample* records, int64_t n, int tower, l3_feat* pooled,
+                                   l3_feat* loc, int64_t row0) {
+    if (!e) return L3_EINVAL;
+    const char* fn = "l3_tower_locations_sampled_dev";
+    const std::string name(fn);
+    const Tensor* x = nullptr;
+    std::string why;
+    int rc = locations_tensor(e, tower, &x, &why);
+    if (rc) {
+        e->err = name + ": " + why;
+        return rc;
+    }
+    if (!bank || !records || !loc) {
+        e->err = name + ": bank, records and loc must not be NULL";
+        return L3_EINVAL;
+    }
+    if (n < 1 || n > INT32_MAX) {
+        e->err = name + ": need 1 <= n <= 2^31 - 1 records";
+        return L3_EINVAL;
+    }
+    if (l3::clipbank_device(bank) != e->cfg.device) {
+        e->err = name + ": the bank lives on device " + std::to_string(l3::clipbank_device(bank)) + ", the engine on device " +
+                 std::to_string(e->cfg.device);
+        return L3_EINVAL;
+    }
+    const bool vision = tower == 0;
+    EmbedDest dl, dp;
+    dp.dev = true, dp.feat = pooled, dp.row0 = row0;
+    if ((rc = locations_dest(e, fn, *x, loc, n, row0, &dl))) return rc;
+    if (pooled && (rc = embed_dest_check(e, fn, dp, n, vision ? e->nv : e->na))) return rc;
+    {
+        l3::SampledHost all;          // every record, before anything is launched; the message carries the record's number
+        if ((rc = l3::sampled_plan(bank, records, (int)n, false, &all, &e->err))) {
+            if (rc == L3_EINVAL) e->err = name + ": " + e->err;
+            return rc;
+        }
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    const int B = e->B;
+    std::vector<l3_sample> batch((size_t)B);
+    EmbedSource src;
+    src.resident = true;
+    for (int64_t s0 = 0; s0 < n; s0 += B) {
+        const int64_t cnt = n - s0 < B ? n - s0 : B;
+        for (int64_t r = 0; r < B; ++r) batch[(size_t)r] = records[s0 + (r < cnt ? r : cnt - 1)];
+        e->feed.mark = sampled_fill_mark, e->feed.mark_ctx = e;
+        if ((rc = e->feed.upload_sampled(bank, batch.data(), B, false, e->stream, &e->err))) {
+            if (rc == L3_EINVAL) e->err = name + ": " + e->err;
+            return rc;
+        }
+        if ((rc = solo_tower_batch(e, vision, src, 0, cnt))) return rc;
+        if ((rc = tower_locations_out(e, *x, s0, cnt, dl))) return rc;
+        if (pooled && (rc = tower_rows_out(e, vision, s0, cnt, dp))) return rc;
+    }
+    HIPCHK(e, l3::stream_wait(e->stream));
+    e->fwd_done = false;
+    prof_collect(e);
+    return L3_OK;
+}
+
 // ---- spectrograms out, spectrograms in ---------------------------------------------------------------------------------
 int l3_spectrogram_shape(const l3_engine* e, int64_t* rows, int64_t* frames) {
     if (!e) return L3_EINVAL;

@@ -527,5 +527,7 @@ enum { ARENA_FOLD_SET = 0, ARENA_FOLD_ADD = 1, ARENA_FOLD_OUT = 2 };
 void arena_fold(float* acc, float* g, int64_t n, int mode, hipStream_t s);
 // fp32 -> bfloat16 storage, round to nearest even (op-level entry points: emulates a mixed-precision writer)
 void cast_bf16(const float* x, void* y, int64_t n, hipStream_t s);
+// bfloat16 storage -> fp32, exact
+void widen_bf16_dev(const void* x, float* y, int64_t n, hipStream_t s);
 
 }  // namespace l3

@@ -22,9 +22,9 @@
 //   pair_topk_kernel   for 64 queries a workgroup, the k <= 64 best candidates of a segment of the other side in a strict order
 //                      (margin, then index), the tile's accumulation shared with pair_tile_kernel (accumulate_tile); nothing but the
 //                      lists is stored.  topk_merge_kernel joins the segments' lists, a wave per query.
-// Every mode runs pair_step() below over k = 0 .. H-1 in that order from acc = 0 and adds bd last, with explicit single-rounding
-// intrinsics: the same pair gives the same bits in every mode, block and position.  Rows past a tile's edge are loaded as zeros and
-// are neither stored nor counted.  No float atomics.
+// Every mode runs pair_step() (pair_tile.h, shared with locmap.hip) over k = 0 .. H-1 in that order from acc = 0 and adds bd last,
+// with explicit single-rounding intrinsics: the same pair gives the same bits in every mode, block and position.  Rows past a
+// tile's edge are loaded as zeros and are neither stored nor counted.  No float atomics.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,20 +34,14 @@
 #include "../../include/l3hip.h"
 #include "featprep.h"
 #include "host_common.h"
+#include "pair_tile.h"
 #include "pairs.h"
 
 namespace l3 {
 namespace {
 
-constexpr int TILE = L3_PAIRS_TILE;          // frames and seconds of a workgroup's tile
-constexpr int KC = 32;                       // columns of U / T per LDS pass
-constexpr int BLOCK = 256;
 constexpr int64_t MAX_ITEMS = (int64_t)65535 * TILE;          // gridDim.y
 constexpr int PROJ_ROWS = 32, PROJ_COLS = 128, PROJ_PAD = 36; // project_kernel: tile of rows x panel of outputs; LDS row of 32 + 4
-
-__device__ __forceinline__ float pair_step(float acc, float u, float t, float w) {
-    return __fmaf_rn(fmaxf(__fadd_rn(u, t), 0.0f), w, acc);
-}
 
 // 1 / (1 + exp(-m)): expf (1 ulp), one addition, one correctly rounded division
 __device__ __forceinline__ float sigmoid_of(float m) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-m))); }
@@ -96,37 +90,6 @@ __global__ __launch_bounds__(BLOCK) void project_kernel(const float* __restrict_
         float4 o = make_float4(acc[a][0], acc[a][1], acc[a][2], acc[a][3]);
         if (b) o = make_float4(__fadd_rn(o.x, bias.x), __fadd_rn(o.y, bias.y), __fadd_rn(o.z, bias.z), __fadd_rn(o.w, bias.w));
         *reinterpret_cast<float4*>(y + r * H + c) = o;
-    }
-}
-
-// The 4 x 4 accumulators of lane (ty, tx) over the tile of frames i0 .. i0 + 63 and seconds j0 .. j0 + 63: the one inner loop of every
-// tiled mode.  Rows at or past v1 / a1 are staged as zeros.  Every lane of the workgroup calls it; it ends on a barrier, after which
-// Us and Ts are free.
-__device__ __forceinline__ void accumulate_tile(float (&acc)[4][4], float (*Us)[TILE], float (*Ts)[TILE], const float* __restrict__ U,
-                                                const float* __restrict__ T, const float* __restrict__ wd, int H, int i0, int v1, int j0,
-                                                int a1, int tid, int tx, int ty) {
-    for (int k0 = 0; k0 < H; k0 += KC) {
-        for (int q = tid; q < TILE * KC / 4; q += BLOCK) {
-            const int r = q & (TILE - 1), k = (q / TILE) * 4;
-            float4 u = make_float4(0.0f, 0.0f, 0.0f, 0.0f), t = u;
-            if (i0 + r < v1) u = *reinterpret_cast<const float4*>(U + (int64_t)(i0 + r) * H + k0 + k);
-            if (j0 + r < a1) t = *reinterpret_cast<const float4*>(T + (int64_t)(j0 + r) * H + k0 + k);
-            Us[k][r] = u.x, Us[k + 1][r] = u.y, Us[k + 2][r] = u.z, Us[k + 3][r] = u.w;
-            Ts[k][r] = t.x, Ts[k + 1][r] = t.y, Ts[k + 2][r] = t.z, Ts[k + 3][r] = t.w;
-        }
-        __syncthreads();
-#pragma unroll 8
-        for (int k = 0; k < KC; ++k) {
-            const float4 uv = *reinterpret_cast<const float4*>(&Us[k][ty * 4]);
-            const float4 tv = *reinterpret_cast<const float4*>(&Ts[k][tx * 4]);
-            const float w = wd[k0 + k];
-            const float ur[4] = {uv.x, uv.y, uv.z, uv.w}, tc[4] = {tv.x, tv.y, tv.z, tv.w};
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[a][c] = pair_step(acc[a][c], ur[a], tc[c], w);
-        }
-        __syncthreads();
     }
 }
 
@@ -495,6 +458,16 @@ int set_side_dev(l3_pairs* p, bool vision, const l3_feat* f, int64_t lo, int64_t
 }
 
 }  // namespace
+
+// what csrc/locmap.hip shares with this file: the projection's launch and the handle's conventions
+void pairs_project(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t n, int K, int H, hipStream_t s) {
+    launch_project(x, ldx, w, b, y, n, K, H, s);
+}
+bool pairs_head_ok(int H) { return head_ok(H); }
+bool pairs_finished(hipStream_t s) { return finished(s); }
+int pairs_enter(l3_pairs* p, const char* fn) { return enter(p, fn); }
+int pairs_grow(l3_pairs* p, float** buf, size_t* cap, size_t count, const char* fn) { return grow(p, buf, cap, count, fn); }
+int pairs_grow(l3_pairs* p, int32_t** buf, size_t* cap, size_t count, const char* fn) { return grow(p, buf, cap, count, fn); }
 }  // namespace l3
 
 using namespace l3;
@@ -536,6 +509,7 @@ int l3_pairs_set_head(l3_pairs* p, const float* w1, const float* b1, const float
     std::vector<float> wd((size_t)H);
     for (int k = 0; k < H; ++k) wd[k] = w2[2 * k + 1] - w2[2 * k];          // one float32 rounding each
     p->head_set = false, p->Nv = p->Na = 0;                                // sets projected with another head are void
+    p->map_put.assign(p->map_put.size(), 0), p->map_done = 0;              // ... and so is the location map
     if (hipMemcpyAsync(p->w1, w1, (size_t)(p->nv + p->na) * H * sizeof(float), hipMemcpyHostToDevice, p->s) != hipSuccess ||
         hipMemcpyAsync(p->b1, b1, (size_t)H * sizeof(float), hipMemcpyHostToDevice, p->s) != hipSuccess ||
         hipMemcpyAsync(p->wd, wd.data(), (size_t)H * sizeof(float), hipMemcpyHostToDevice, p->s) != hipSuccess || !finished(p->s))

@@ -651,6 +651,30 @@ class L3Model(object):
                 outs.append(e.tower_features(tower, x))
         return tuple(outs)
 
+    def predict_locations(self, video=None, audio=None, batch_size=32):
+        """The two towers' last feature maps before their global max pool, location by location: for each input that
+        is given, (usc.DeviceFeatures of n L rows x C channels, (H, W)) with L = H W and item i's locations in rows [i L, (i + 1) L),
+        y first -- what crossmodal.PairScorer.set_maps projects; None for an input that is None.  The maximum over an item's rows is
+        its row of predict_towers, bit for bit.  The caller owns and closes the DeviceFeatures.  ValueError for a model whose last
+        pool does not reduce to 1 x 1 (tiny_L3's vision tower)."""
+        if video is None and audio is None:
+            raise ValueError('give video, audio or both')
+        ins = [None if x is None else np.ascontiguousarray(x, dtype=np.float32) for x in (video, audio)]
+        for x, name in zip(ins, ('video', 'audio')):
+            if x is not None and len(x) == 0:
+                raise ValueError('%s has no rows' % name)
+        n = max(len(x) for x in ins if x is not None)
+        e = self._ensure_engine(max(1, min(batch_size, n)) if self._engine is None else self._engine.batch)
+        from . import usc
+        outs = []
+        for tower, x in enumerate(ins):
+            if x is None:
+                outs.append(None)
+                continue
+            H, W, _ = e.tower_locations_shape(tower)
+            outs.append((usc.DeviceFeatures.from_handle(e.tower_locations(tower, x)), (H, W)))
+        return tuple(outs)
+
     def fit_generator(self, generator, steps_per_epoch, epochs=1, verbose=1, callbacks=None, validation_data=None,
                       validation_steps=None, initial_epoch=0, **_):
         """keras fit_generator loop as driven by train.py:408-414: per step train_on_batch, per
