@@ -1291,6 +1291,66 @@ int l3_forest_get_cuts(l3_forest *m, float *cuts, int32_t *ncuts);
  * the nodes searched at the level over all trees, those of them searched by the wide kernel, and the level's wall time in ms */
 int l3_forest_level_stats(const l3_forest *m, int max_levels, int64_t *nodes, int64_t *wide, double *ms);
 
+/* ---- Nearest neighbours among embedding rows: distance blocks, top-k lists, votes (csrc/knn.hip) ----------------------
+ * A handle holds a database of n rows of D float32 (its own copy, with int32 labels or without) and a query set: rows of its own, or
+ * the database itself (l3_knn_query_self: no second copy).  The N x N matrix is never stored: l3_knn_topk keeps only the lists.
+ * Arithmetic, which is the contract (tests/knn_ref.py derives the bounds from it), the same in every call:
+ *   dot(q, c) = fmaf(q[D-1], c[D-1], ... fmaf(q[0], c[0], 0)), one float32 chain in ascending feature order (what one accumulator of
+ *               the fp32 matrix-core instruction gives); nn(x) = dot(x, x), once per row when the rows are set.
+ *   L3_KNN_SQEUCLIDEAN  d = max(0, fl(fl(nn(q) + nn(c)) - 2 dot(q, c)))          (a NaN stays a NaN)
+ *   L3_KNN_COSINE       d = fl(1 - fl(fl(dot(q, c) r(q)) r(c))), r(x) = fl(1 / fl(sqrt(nn(x)))), correctly rounded, and 0 for a row of
+ *                       zero norm, whose distance to every row is therefore 1 (sklearn's convention).
+ * The same pair has the same bits in l3_knn_matrix, any block of it, l3_knn_list and the lists, at every segment count.
+ * The order of a neighbour list.  For a query i the candidates are the database rows j with group_c[j] != group_q[i] -- every j when
+ * no groups are given.  Entry (d, j) is ahead of (d', j') iff d < d', or d == d' and j < j' (float comparison: +0 == -0); a candidate
+ * whose distance is NaN is never listed.  The list of i is the first k candidates of that order, in that order; a list with fewer than
+ * k candidates is filled up with index -1 and distance +inf.  The order is strict, so the lists are a function of the inputs alone.
+ *   l3_knn_set_database[_dev]  n host rows (n, D), or rows [lo, hi) of an l3_feat on the handle's device (copied device to device);
+ *                              labels (n, each >= 0) or NULL.  At most 2^31 - 1 rows.  Voids a self query's set until it returns.
+ *   l3_knn_set_queries[_dev]   the same for the query side; l3_knn_query_self makes the database the query set.
+ *   l3_knn_matrix              the block [q0, q1) x [c0, c1) of distances to the host, row major (tests and small jobs)
+ *   l3_knn_list                out[p] = the distance of (query iq[p], database row ic[p]), n >= 1
+ *   l3_knn_topk                idx_out, dist_out (nQ, k) int32 / float32, row major; group_q (nQ) and group_c (n) together or both NULL
+ *   l3_knn_vote                l3_knn_topk at k, then, without downloading the lists, the votes of the neighbours' labels at the S <=
+ *                              L3_KNN_MAX_SIZES list sizes ks (strictly ascending, in [1, k]: the first ks[s] entries of a sorted k-list
+ *                              are the ks[s]-list).  Outputs, each NULL when not wanted: counts (nQ, S, n_classes) int32; pred (nQ, S)
+ *                              int32, the class of the most votes, the lowest class among equals, -1 for a query without neighbours
+ *                              (empty slots do not vote); with file_idxs (n_files int64 pairs [s, e) over the queries, 0 <= s < e <=
+ *                              nQ) file_counts (n_files, S, n_classes) int32, the sum of the rows' votes, and file_pred (n_files, S),
+ *                              chosen from them in the same way.  n_classes <= L3_KNN_MAX_CLASSES.  Integer arithmetic only.
+ *   l3_knn_time                device time in ms per launch over `reps` launches (hipEvents, one untimed launch first): what 0 the
+ *                              top-k pass at k (every segment's lists and their merge), 1 the matrix kernel over the block [0, min(nQ,
+ *                              8192)) x [0, min(n, 8192)).  For the records under profiles/.
+ *   l3_op_knn_topk             l3_knn_topk on host rows Q (nq, D) and C (nc, D) by the kernels alone.  segments: into how many runs of
+ *                              tiles the candidates are cut, each with partial lists of its own that a second kernel merges; 0 lets the
+ *                              library choose, as l3_knn_topk does; a count above the number of tiles is clamped to it.  In [0, 256].
+ * L3_EINVAL (message in l3_last_error(NULL), naming the call): a NULL pointer, D <= 0, an unknown metric, k outside [1,
+ * L3_KNN_TOPK_MAX], ks not ascending or above k, groups on one side only, a negative label, a label outside [0, n_classes), l3_knn_vote
+ * on a database without labels, a query before both sides are set, a block, a pair or a file out of range, an l3_feat of another
+ * width or on another device. */
+#define L3_KNN_SQEUCLIDEAN 0
+#define L3_KNN_COSINE 1
+#define L3_KNN_TOPK_MAX 64        /* entries of a neighbour list: one per lane of a wave (the value of L3_PAIRS_TOPK_MAX) */
+#define L3_KNN_MAX_SEGMENTS 256
+#define L3_KNN_MAX_SIZES 8        /* list sizes of one l3_knn_vote */
+#define L3_KNN_MAX_CLASSES 256
+typedef struct l3_knn l3_knn;
+int l3_knn_create(int device, int D, int metric, l3_knn **h);
+void l3_knn_destroy(l3_knn *h);
+int l3_knn_set_database(l3_knn *h, const float *rows, int64_t n, const int32_t *labels);
+int l3_knn_set_database_dev(l3_knn *h, const l3_feat *f, int64_t lo, int64_t hi, const int32_t *labels);
+int l3_knn_set_queries(l3_knn *h, const float *rows, int64_t n);
+int l3_knn_set_queries_dev(l3_knn *h, const l3_feat *f, int64_t lo, int64_t hi);
+int l3_knn_query_self(l3_knn *h);
+int l3_knn_matrix(l3_knn *h, int64_t q0, int64_t q1, int64_t c0, int64_t c1, float *out);
+int l3_knn_list(l3_knn *h, const int32_t *iq, const int32_t *ic, int64_t n, float *out);
+int l3_knn_topk(l3_knn *h, int k, const int32_t *group_q, const int32_t *group_c, int32_t *idx_out, float *dist_out);
+int l3_knn_vote(l3_knn *h, int k, const int32_t *ks, int S, int n_classes, const int32_t *group_q, const int32_t *group_c,
+                const int64_t *file_idxs, int64_t n_files, int32_t *counts, int32_t *pred, int32_t *file_counts, int32_t *file_pred);
+int l3_op_knn_topk(int device, const float *Q, const float *C, int64_t nq, int64_t nc, int D, int metric, int k, int segments,
+                   const int32_t *group_q, const int32_t *group_c, int32_t *idx, float *dist);
+int l3_knn_time(l3_knn *h, int what, int k, int reps, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,6 +202,21 @@ SIGNATURES = {
     'l3_op_pair_margins': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     'l3_op_pair_topk': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int64, C.c_int, C.c_int] +
                         [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p]),
+    # nearest neighbours among embedding rows (csrc/knn.hip)
+    'l3_knn_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    'l3_knn_destroy': (None, [C.c_void_p]),
+    'l3_knn_set_database': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_knn_set_database_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'l3_knn_set_queries': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_knn_set_queries_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    'l3_knn_query_self': (C.c_int, [C.c_void_p]),
+    'l3_knn_matrix': (C.c_int, [C.c_void_p] + [C.c_int64] * 4 + [C.c_void_p]),
+    'l3_knn_list': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_knn_topk': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+    'l3_knn_vote': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] +
+                    [C.c_void_p] * 4),
+    'l3_op_knn_topk': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_int] * 4 + [C.c_void_p] * 4),
+    'l3_knn_time': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     'l3_frontend_cfg': (C.c_int, [C.c_int] * 5 + [C.c_void_p]),
     'l3_frontend_tables': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int64, C.POINTER(C.c_int64)]),
     'l3_op_frontend_frames': (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4),
@@ -1970,6 +1985,264 @@ def op_pair_topk(u, t, wd, bd, k, truth=None, group_q=None, group_c=None, segmen
     check(load().l3_op_pair_topk(int(device), _ptr(u), _ptr(t), _ptr(wd), float(np.float32(bd)), nq, nc, u.shape[1], int(k), _ptr(tr),
                                  _ptr(gq), _ptr(gc), int(segments), _ptr(idx), _ptr(margin)))
     return idx, margin
+
+
+# ---- nearest neighbours among embedding rows (csrc/knn.hip) -----------------------------------------------------------
+KNN_METRICS = {'sqeuclidean': 0, 'cosine': 1}          # L3_KNN_SQEUCLIDEAN, L3_KNN_COSINE
+KNN_TOPK_MAX = 64                  # L3_KNN_TOPK_MAX
+KNN_MAX_SEGMENTS = 256             # L3_KNN_MAX_SEGMENTS
+KNN_MAX_SIZES = 8                  # L3_KNN_MAX_SIZES
+KNN_MAX_CLASSES = 256              # L3_KNN_MAX_CLASSES
+KNN_MAX_ROWS = 2 ** 31 - 1
+
+
+def knn_check_k(k):
+    """k as an int in [1, KNN_TOPK_MAX]; ValueError otherwise"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= KNN_TOPK_MAX:
+        raise ValueError('n_neighbors must be an integer in [1, %d], not %r' % (KNN_TOPK_MAX, k))
+    return int(k)
+
+
+def knn_check_sizes(ks, k):
+    """the list sizes of one vote as int32: 1 .. KNN_MAX_SIZES of them, strictly ascending, in [1, k]; ValueError otherwise"""
+    sizes = list(ks) if ks is not None and np.ndim(ks) == 1 else []
+    if not 1 <= len(sizes) <= KNN_MAX_SIZES or any(isinstance(s, bool) or not isinstance(s, (int, np.integer)) for s in sizes):
+        raise ValueError('ks must hold 1 to %d integers, not %r' % (KNN_MAX_SIZES, ks))
+    if sizes[0] < 1 or sizes[-1] > k or any(b <= a for a, b in zip(sizes, sizes[1:])):
+        raise ValueError('ks must ascend strictly within [1, n_neighbors = %d], not %r' % (k, ks))
+    return np.asarray(sizes, np.int32)
+
+
+def _group32(a, name, n, what):
+    if a is None:
+        raise ValueError('%s must not be None' % name)
+    a = np.asarray(a)
+    if a.ndim != 1 or len(a) != n or a.dtype.kind not in 'iu':
+        raise ValueError('%s must be %d integers, one per %s' % (name, n, what))
+    if n and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError('%s must fit 32-bit integers' % name)
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _knn_groups(group_q, group_c, nq, nc):
+    if (group_q is None) != (group_c is None):
+        raise ValueError('the groups of the queries and of the fitted rows are given together or both left None')
+    if group_q is None:
+        return None, None
+    return _group32(group_q, 'groups_q', nq, 'query'), _group32(group_c, 'groups_fit', nc, 'fitted row')
+
+
+def _knn_rows(rows, D, side):
+    """(Features or float32 array, count) of one side's rows; ValueError unless they are (n >= 1, D)"""
+    if rows is None:
+        raise ValueError('the %s rows must not be None' % side)
+    if isinstance(rows, Features):
+        if not rows.h:
+            raise ValueError('the %s features are closed' % side)
+        n, d = rows.shape
+        x = rows
+    else:
+        x = np.asarray(rows)
+        if x.dtype != np.float32:
+            raise ValueError('the %s rows must be float32, not %s (there is no silent conversion)' % (side, x.dtype))
+        x = np.ascontiguousarray(x)
+        if x.ndim != 2:
+            raise ValueError('the %s rows must have shape (n, %d), not %s' % (side, D, x.shape))
+        n, d = x.shape
+    if d != D:
+        raise ValueError('the %s rows have %d columns, the handle\'s %d' % (side, d, D))
+    if not 1 <= n <= KNN_MAX_ROWS:
+        raise ValueError('the %s set must hold 1 to 2^31 - 1 rows, not %d' % (side, n))
+    return x, n
+
+
+class KNN(object):
+    """RAII wrapper over an l3_knn handle: a database of float32 rows (with labels or without) and a query set resident on one
+    device.  Every argument is checked here first (ValueError) and the handle is created by the first call that needs the device."""
+
+    def __init__(self, D, metric='sqeuclidean', device=0):
+        if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or not 1 <= D <= 2 ** 20:
+            raise ValueError('D must be an integer in [1, 2^20], not %r' % (D,))
+        if metric not in KNN_METRICS:
+            raise ValueError('metric must be one of %s, not %r' % (sorted(KNN_METRICS), metric))
+        self.D, self.metric, self.device = int(D), metric, int(device)
+        self.lib = None
+        self.h = None
+        self.n_database = self.n_queries = 0
+        self.has_labels = False
+        self.label_max = -1
+        self.self_query = False
+
+    def _handle(self):
+        if self.h is None:
+            self.lib = load()
+            h = C.c_void_p()
+            check(self.lib.l3_knn_create(self.device, self.D, KNN_METRICS[self.metric], C.byref(h)))
+            self.h = h
+        return self.h
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_knn_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check_device(self, x, side):
+        if isinstance(x, Features) and x.device != self.device:
+            raise ValueError('the %s features are on device %d, the handle on device %d' % (side, x.device, self.device))
+
+    def set_database(self, rows, labels=None):
+        """(n, D) host rows or a Features on this device -> the handle's own copy; labels: n integers >= 0, or None"""
+        x, n = _knn_rows(rows, self.D, 'database')
+        self._check_device(x, 'database')
+        lab = None
+        if labels is not None:
+            lab = _index32(np.asarray(labels).reshape(-1), 'labels', n, 2 ** 31, 'database row')
+        h = self._handle()
+        self.n_database = 0
+        if self.self_query:
+            self.n_queries = 0
+        if isinstance(x, Features):
+            check(self.lib.l3_knn_set_database_dev(h, x.h, 0, n, _ptr(lab)))
+        else:
+            check(self.lib.l3_knn_set_database(h, _ptr(x), n, _ptr(lab)))
+        self.n_database = n
+        self.has_labels = lab is not None
+        self.label_max = int(lab.max()) if lab is not None else -1
+        if self.self_query:
+            self.n_queries = n
+
+    def set_queries(self, rows):
+        """(n, D) host rows or a Features on this device -> the handle's own copy"""
+        x, n = _knn_rows(rows, self.D, 'query')
+        self._check_device(x, 'query')
+        h = self._handle()
+        self.n_queries, self.self_query = 0, False
+        if isinstance(x, Features):
+            check(self.lib.l3_knn_set_queries_dev(h, x.h, 0, n))
+        else:
+            check(self.lib.l3_knn_set_queries(h, _ptr(x), n))
+        self.n_queries = n
+
+    def query_self(self):
+        """the database is the query set (no second copy)"""
+        if self.n_database < 1:
+            raise ValueError('set_database comes first')
+        check(self.lib.l3_knn_query_self(self._handle()))
+        self.self_query, self.n_queries = True, self.n_database
+
+    def _need_sets(self):
+        if self.n_database < 1 or self.n_queries < 1:
+            raise ValueError('set_database and set_queries (or query_self) come first')
+
+    def matrix(self, q0=0, q1=None, c0=0, c1=None):
+        """the block [q0, q1) x [c0, c1) of distances"""
+        self._need_sets()
+        q1 = self.n_queries if q1 is None else int(q1)
+        c1 = self.n_database if c1 is None else int(c1)
+        q0, c0 = int(q0), int(c0)
+        if q0 < 0 or q1 > self.n_queries or q0 >= q1 or c0 < 0 or c1 > self.n_database or c0 >= c1:
+            raise ValueError('the block [%d, %d) x [%d, %d) is empty or outside the %d x %d pairs' % (q0, q1, c0, c1, self.n_queries,
+                                                                                                      self.n_database))
+        out = np.empty((q1 - q0, c1 - c0), np.float32)
+        check(self.lib.l3_knn_matrix(self._handle(), q0, q1, c0, c1, _ptr(out)))
+        return out
+
+    def list(self, iq, ic):
+        """distances of the pairs (query iq[p], database row ic[p])"""
+        self._need_sets()
+        n = len(iq) if iq is not None and np.ndim(iq) == 1 else -1
+        if n < 1:
+            raise ValueError('iq and ic must be two equally long, non-empty 1-d index arrays')
+        iq = _index32(iq, 'iq', n, self.n_queries, 'pair')
+        ic = _index32(ic, 'ic', n, self.n_database, 'pair')
+        out = np.empty(n, np.float32)
+        check(self.lib.l3_knn_list(self._handle(), _ptr(iq), _ptr(ic), n, _ptr(out)))
+        return out
+
+    def topk(self, k, group_q=None, group_c=None):
+        """(idx, dist), both (n_queries, k): every query's k nearest database rows among those of other groups (all rows without
+        groups), the smaller distance first and the smaller index first among equal distances; a list with fewer candidates ends
+        in index -1 and distance +inf"""
+        self._need_sets()
+        k = knn_check_k(k)
+        gq, gc = _knn_groups(group_q, group_c, self.n_queries, self.n_database)
+        idx, dist = np.empty((self.n_queries, k), np.int32), np.empty((self.n_queries, k), np.float32)
+        check(self.lib.l3_knn_topk(self._handle(), k, _ptr(gq), _ptr(gc), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def vote(self, k, ks, n_classes, group_q=None, group_c=None, file_idxs=None, outputs=('pred',)):
+        """l3_knn_vote -> dict of what `outputs` names: 'counts' (n, S, C) and 'pred' (n, S) int32, and with file_idxs 'file_counts'
+        (F, S, C) and 'file_pred' (F, S); the lists stay on the device"""
+        self._need_sets()
+        k = knn_check_k(k)
+        sizes = knn_check_sizes(ks, k)
+        outputs = tuple(outputs)
+        unknown = set(outputs) - {'counts', 'pred', 'file_counts', 'file_pred'}
+        if unknown or not outputs:
+            raise ValueError("outputs must name some of 'counts', 'pred', 'file_counts', 'file_pred', not %r" % (outputs,))
+        if isinstance(n_classes, bool) or not isinstance(n_classes, (int, np.integer)) or not 1 <= n_classes <= KNN_MAX_CLASSES:
+            raise ValueError('n_classes must be an integer in [1, %d], not %r' % (KNN_MAX_CLASSES, n_classes))
+        if not self.has_labels:
+            raise ValueError('the database was set without labels')
+        if self.label_max >= n_classes:
+            raise ValueError('the database holds the label %d, outside [0, %d)' % (self.label_max, n_classes))
+        gq, gc = _knn_groups(group_q, group_c, self.n_queries, self.n_database)
+        files, F = None, 0
+        if 'file_counts' in outputs or 'file_pred' in outputs:
+            if file_idxs is None:
+                raise ValueError("'file_counts' and 'file_pred' need file_idxs")
+            files = np.ascontiguousarray(np.asarray(file_idxs, np.int64).reshape(-1, 2))
+            F = len(files)
+            if F < 1 or np.any(files[:, 0] < 0) or np.any(files[:, 0] >= files[:, 1]) or np.any(files[:, 1] > self.n_queries):
+                raise ValueError('file_idxs must hold row ranges [s, e) with 0 <= s < e <= %d' % self.n_queries)
+        n, S, nc = self.n_queries, len(sizes), int(n_classes)
+        got = {}
+        if 'counts' in outputs:
+            got['counts'] = np.empty((n, S, nc), np.int32)
+        if 'pred' in outputs:
+            got['pred'] = np.empty((n, S), np.int32)
+        if 'file_counts' in outputs:
+            got['file_counts'] = np.empty((F, S, nc), np.int32)
+        if 'file_pred' in outputs:
+            got['file_pred'] = np.empty((F, S), np.int32)
+        check(self.lib.l3_knn_vote(self._handle(), k, _ptr(sizes), S, nc, _ptr(gq), _ptr(gc), _ptr(files), F, _ptr(got.get('counts')),
+                                   _ptr(got.get('pred')), _ptr(got.get('file_counts')), _ptr(got.get('file_pred'))))
+        return got
+
+    def time(self, what, k=5, reps=3):
+        """l3_knn_time: device ms per launch of 'topk' (lists and merge at k) or 'matrix' (a block of at most 8192 x 8192)"""
+        kinds = ('topk', 'matrix')
+        if what not in kinds:
+            raise ValueError('what must be one of %s' % (kinds,))
+        self._need_sets()
+        ms = C.c_double()
+        check(self.lib.l3_knn_time(self._handle(), kinds.index(what), knn_check_k(k), int(reps), C.byref(ms)))
+        return ms.value
+
+
+def op_knn_topk(Q, X, k, metric='sqeuclidean', segments=0, group_q=None, group_c=None, device=0):
+    """l3_op_knn_topk: (idx, dist), both (nq, k): for every row of Q (nq, D) its k nearest rows of X (nc, D) by the order of KNN.topk,
+    by the kernels alone.  segments: runs of candidate tiles with partial lists of their own, 0: the library's choice."""
+    if metric not in KNN_METRICS:
+        raise ValueError('metric must be one of %s, not %r' % (sorted(KNN_METRICS), metric))
+    Q, X = _f32(Q), _f32(X)
+    if Q.ndim != 2 or X.ndim != 2 or Q.shape[0] < 1 or X.shape[0] < 1 or Q.shape[1] != X.shape[1] or Q.shape[1] < 1:
+        raise ValueError('need Q (nq >= 1, D) and X (nc >= 1, D) with D >= 1')
+    k = knn_check_k(k)
+    if not 0 <= int(segments) <= KNN_MAX_SEGMENTS:
+        raise ValueError('segments must be in [0, %d]' % KNN_MAX_SEGMENTS)
+    nq, nc = Q.shape[0], X.shape[0]
+    gq, gc = _knn_groups(group_q, group_c, nq, nc)
+    idx, dist = np.empty((nq, k), np.int32), np.empty((nq, k), np.float32)
+    check(load().l3_op_knn_topk(int(device), _ptr(Q), _ptr(X), nq, nc, Q.shape[1], KNN_METRICS[metric], k, int(segments), _ptr(gq), _ptr(gc),
+                                _ptr(idx), _ptr(dist)))
+    return idx, dist
 
 
 # ---- downstream MLP classifier (classifier/train.py:230-391; csrc/mlp.hip) ---------------------------------------------------------

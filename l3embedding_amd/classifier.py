@@ -32,11 +32,16 @@ it.  Deviations from the reference, all deliberate:
     _lib.MLPGroup: the rows resident once, every live point in the same seven launches per step, train_mlp's checkpoint and
     early-stopping rules per point): every metric, history, search record, the chosen point, the returned weights and
     history_csvlog.csv equal the loop of train_mlp over the grid bit for bit.  model_dir/model.h5 holds the returned model there
-    (the loop leaves the checkpoint of the run it made last).  train(parameter_search=True) and cross_validate still run the loop.
+    (the loop leaves the checkpoint of the run it made last).  train(parameter_search=True) and cross_validate still run the loop;
+  * train_knn / train_knn_search (and their folds, train_knn_fold / train_knn_search_fold) are not in the reference: a k-nearest-
+    neighbour classifier on the frozen features (knn.py, csrc/knn.hip), with train_rf's conventions.  Nothing is trained, so the
+    training metrics are leave-one-row-out; the search over k scores every size from one query at the largest.  train() and
+    cross_validate refuse 'knn' as they refuse every type but the MLP.
 
 How the file is put together: train, train_svm_fold, train_rf_fold and cross_validate pass their arguments, by name in one dict, to
-one fold driver (_run_fold), and the model types differ in one function each (_mlp_part, _svm_part, _rf_part; train_rf_search_fold
-and train_mlp_search_fold hand the driver their own, _rf_search_part and _mlp_search_part).  train_param_search, train_svm_search,
+one fold driver (_run_fold), and the model types differ in one function each (_mlp_part, _svm_part, _rf_part; train_rf_search_fold,
+train_mlp_search_fold, train_knn_fold and train_knn_search_fold hand the driver their own, _rf_search_part, _mlp_search_part,
+_knn_part and _knn_search_part).  train_param_search, train_svm_search,
 train_rf_search and train_mlp_search are one search body (_search) with four ways to fit the grid.  A usc.DeviceFeatures is closed by whoever made it, through _closing: the
 driver closes the fold's splits, a search the parts of its cut and its merged matrix, and nobody what a caller passed in.
 """
@@ -55,6 +60,7 @@ import numpy as np
 from . import _lib, callbacks, kerasfile
 from . import svm as _svm
 from .forest import FITTED_ROWS, RandomForestClassifier
+from .knn import KNeighborsClassifier
 from .svm import SVC, hinge_loss  # noqa: F401  (re-exported: the reference imports them into classifier/train.py)
 from .usc import DeviceFeatures, FoldBank, get_split, preprocess_split_data, stratified_shuffle_split
 
@@ -733,6 +739,94 @@ def train_rf_oob_search(train_data, valid_data, test_data, model_dir, n_estimato
     return model, train_metrics, valid_metrics, test_metrics
 
 
+KNN_SEARCH_KS = (1, 3, 5, 10, 20, 50)
+# the arguments of knn.KNeighborsClassifier that train_knn passes on from its keyword arguments
+KNN_ARGS = ('device',)
+
+
+def _knn_fit(data, n_neighbors, metric, num_classes, kwargs):
+    args = {k: kwargs[k] for k in KNN_ARGS if k in kwargs}
+    if isinstance(data['features'], DeviceFeatures):
+        args.setdefault('device', data['features'].device)
+    return KNeighborsClassifier(n_neighbors=n_neighbors, metric=metric, num_classes=num_classes, **args).fit(data['features'], data['labels'])
+
+
+def _knn_scores(clf, ks, train, valid, test_data, num_classes):
+    """-> [(train metrics, valid metrics, test metrics)] per size of ks (None: the classifier's own) of a classifier just fitted on
+    `train`: one query per split at the largest size.  The training rows leave themselves out; the test set is scored per file."""
+    on_train = np.atleast_2d(clf.evaluate(None, ks=ks)['predict'])
+    on_valid = np.atleast_2d(clf.evaluate(valid['features'], ks=ks)['predict']) if valid else None
+    per_file = None
+    if test_data:
+        per_file = np.atleast_2d(clf.evaluate(test_data['features'], file_idxs=test_data['file_idxs'], ks=ks,
+                                              outputs=('file_predict',))['file_predict'])
+    scored = []
+    for g in range(len(on_train)):
+        train_metrics = compute_metrics(train['labels'], on_train[g], num_classes=num_classes)
+        train_metrics['loss'] = 0
+        valid_metrics = {}
+        if valid:
+            valid_metrics = compute_metrics(valid['labels'], on_valid[g], num_classes=num_classes)
+            valid_metrics['loss'] = 0
+        test_metrics = compute_metrics(test_data['labels'], per_file[g], num_classes=num_classes) if test_data else {}
+        scored.append((train_metrics, valid_metrics, test_metrics))
+    return scored
+
+
+def train_knn(train_data, valid_data, test_data, model_dir, n_neighbors=5, metric='sqeuclidean', num_classes=10, **kwargs):
+    """-> (model, train_metrics, valid_metrics, test_metrics) with train_rf's conventions: knn.KNeighborsClassifier(n_neighbors,
+    metric) holding the training rows, pickled to model_dir/model.pkl; 'loss' is 0; the test set is classified per file by the sum of
+    its frames' votes.  Nothing is fitted, so a training row's nearest neighbour would be itself: the training metrics are
+    leave-one-row-out.  The splits' features may be NumPy rows or usc.DeviceFeatures (queried where they are).  Of kwargs KNN_ARGS
+    are passed on; the rest is ignored."""
+    clf = _knn_fit(train_data, n_neighbors, metric, num_classes, kwargs)
+    LOGGER.info('Saving model...')
+    _dump(os.path.join(model_dir, 'model.pkl'), clf)
+    train_metrics, valid_metrics, test_metrics = _knn_scores(clf, None, train_data, valid_data, test_data, num_classes)[0]
+    LOGGER.info('Train (leave-one-out) - acc: %s', train_metrics['accuracy'])
+    if valid_data:
+        LOGGER.info('Valid - acc: %s', valid_metrics['accuracy'])
+    return clf, train_metrics, valid_metrics, test_metrics
+
+
+def _knn_sizes(ks):
+    """the searched sizes as a list of distinct ints in [1, 64], at most 8, in the caller's order"""
+    sizes = list(ks)
+    if not 1 <= len(sizes) <= _lib.KNN_MAX_SIZES or len(set(sizes)) != len(sizes) or \
+            any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _lib.KNN_TOPK_MAX for k in sizes):
+        raise ValueError('ks must hold 1 to %d distinct ints in [1, %d], not %r' % (_lib.KNN_MAX_SIZES, _lib.KNN_TOPK_MAX, ks))
+    return [int(k) for k in sizes]
+
+
+def train_knn_search(train_data, valid_data, test_data, model_dir, ks=KNN_SEARCH_KS, train_with_valid=False, metric='sqeuclidean',
+                     num_classes=10, valid_ratio=0.15, split_random_state=None, n_neighbors=None, **kwargs):
+    """train_param_search(..., train_func=train_knn, search_space={'n_neighbors': ks}) from one query per split: the first k'
+    entries of a sorted k-list are the k'-list, so the lists at max(ks) score every size (KNeighborsClassifier.evaluate(ks=...)).
+    The size with the best validation accuracy is kept, the first one of ks on ties (_search's rule), and with train_with_valid
+    it is refitted as train_param_search refits it.  -> (model, train_metrics, valid_metrics, test_metrics) with the search records
+    train_rf_search writes; 'loss' is 0; model_dir/model.pkl holds the returned model.  n_neighbors is ignored (the search sets
+    it).  Without a validation fold (valid_data None): train_param_search's cut of valid_ratio of the training rows, seeded by
+    split_random_state (None refuses, NO_SSS)."""
+    grid = _knn_sizes(ks)
+    sizes = sorted(grid)
+
+    def run_grid(search_train, search_valid):
+        LOGGER.info('Scoring n_neighbors = %s from one query at %d', grid, sizes[-1])
+        whole = _knn_fit(search_train, sizes[-1], metric, num_classes, kwargs)
+        scored = _knn_scores(whole, sizes, search_train, search_valid, test_data, num_classes)
+        return [((k,), whole.with_neighbors(k)) + scored[sizes.index(k)] for k in grid]
+
+    def refit(point, data):
+        model = _knn_fit(data, point[0], metric, num_classes, kwargs)
+        train_metrics, _, test_metrics = _knn_scores(model, None, data, None, test_data, num_classes)[0]
+        return model, train_metrics, test_metrics
+
+    outcome = _search(train_data, valid_data, ['n_neighbors'], valid_ratio, split_random_state, train_with_valid, run_grid, refit)
+    LOGGER.info('Saving model...')
+    _dump(os.path.join(model_dir, 'model.pkl'), outcome[0])
+    return outcome
+
+
 MLP_SEARCH_SPACE = {'learning_rate': [1e-5, 1e-4, 1e-3], 'weight_decay': [1e-5, 1e-4, 1e-3]}        # classifier/train.py:638-651
 
 
@@ -1148,6 +1242,47 @@ def train_mlp_search_fold(features_dir, output_dir, fold_num, feature_mode='fram
     preprocess_device the splits stay on that GPU through the search.  model_args: train_mlp's (num_epochs, ...; learning_rate and
     weight_decay are recorded and then set by the search).  model.h5 holds the returned model.  -> that directory."""
     return _run_fold(dict(locals(), model_type='mlp', parameter_search=True, model_part=_mlp_search_part))      # the settings by name
+
+
+def _knn_part(splits, model_dir, fold):
+    """the nearest-neighbour classifier's part of a fold -> (model, train_metrics, valid_metrics, test_metrics): one train_knn"""
+    return train_knn(*splits, model_dir, **dict(dict(num_classes=fold['num_classes']), **fold['model_args']))
+
+
+def _knn_search_part(splits, model_dir, fold):
+    """the part of a fold that searches n_neighbors -> (model, train_metrics, valid_metrics, test_metrics): train_knn_search with
+    the fold's sizes (in model_args), on the validation fold or on a cut"""
+    args = dict(dict(num_classes=fold['num_classes']), **fold['model_args'])
+    if fold['search_on_cut']:
+        args.update(valid_ratio=fold['parameter_search_valid_ratio'], split_random_state=fold['parameter_search_split_seed'])
+    return train_knn_search(*splits, model_dir, train_with_valid=fold['parameter_search_train_with_valid'], **args)
+
+
+def train_knn_fold(features_dir, output_dir, fold_num, feature_mode='framewise', train_batch_size=64, patience=20,
+                   random_state=20171021, parameter_search_valid_fold=True, parameter_search_valid_ratio=0.15,
+                   parameter_search_train_with_valid=False, gsheet_id=None, google_dev_app_name=None, verbose=False,
+                   non_overlap=False, non_overlap_chunk_size=10, use_min_max=False, preprocess_device=None,
+                   parameter_search_split_seed=None, **model_args):
+    """One cross-validation fold as train_rf_fold runs it, for the nearest-neighbour classifier: written to
+    <output_dir>/classifier/<features desc>/<mode>/<overlap>/<min-max>/knn/fold<N>/<timestamp>/: config.json, min_max_scaler.pkl,
+    stdizer.pkl, model.pkl, results.pkl.  One train_knn with model_args (n_neighbors, metric and KNN_ARGS); no search
+    (train_knn_search_fold).  train_batch_size, patience and random_state are recorded as the reference records them; nothing here
+    uses them.  -> that directory."""
+    return _run_fold(dict(locals(), model_type='knn', parameter_search=False, model_part=_knn_part))      # the settings by name
+
+
+def train_knn_search_fold(features_dir, output_dir, fold_num, feature_mode='framewise', train_batch_size=64, patience=20,
+                          random_state=20171021, ks=KNN_SEARCH_KS, parameter_search_valid_fold=True,
+                          parameter_search_valid_ratio=0.15, parameter_search_train_with_valid=False, gsheet_id=None,
+                          google_dev_app_name=None, verbose=False, non_overlap=False, non_overlap_chunk_size=10, use_min_max=False,
+                          preprocess_device=None, parameter_search_split_seed=None, **model_args):
+    """train_knn_fold's fold, directory (.../knn/fold<N>/<timestamp>/) and five files, the model chosen by train_knn_search over
+    ks: on the validation fold, or with parameter_search_valid_fold=False on a stratified cut seeded by
+    parameter_search_split_seed (None refuses, NO_SSS).  config.json records parameter_search true and ks; model_args are metric
+    and KNN_ARGS.  -> that directory."""
+    fold = dict(locals(), model_type='knn', parameter_search=True, model_part=_knn_search_part)          # the fold's settings by name
+    fold['model_args'] = dict(model_args, ks=_knn_sizes(fold.pop('ks')))
+    return _run_fold(fold)
 
 
 # what a fold's metrics hold besides numbers and lists of numbers with one entry per class: the per-epoch histories (their length
