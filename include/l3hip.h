@@ -1351,6 +1351,82 @@ int l3_op_knn_topk(int device, const float *Q, const float *C, int64_t nq, int64
                    const int32_t *group_q, const int32_t *group_c, int32_t *idx, float *dist);
 int l3_knn_time(l3_knn *h, int what, int k, int reps, double *ms);
 
+/* ---- K-means over embedding rows: Lloyd iterations, k-means++ seeding, label statistics (csrc/kmeans.hip) -------------
+ * A handle holds n rows of D float32 (its own copy) and K centroids on one device.  Arithmetic, which is the contract (tests/
+ * cluster_ref.py is its NumPy oracle), the same in every call:
+ * Distances.  Squared Euclidean only (L3_KNN_COSINE is refused: a mean does not minimise it).  d(i, c) has exactly the bits that
+ *   l3_knn_matrix gives for row i against centroid c under L3_KNN_SQEUCLIDEAN: dot is the ascending fmaf chain, nn(x) = dot(x, x) is
+ *   computed once per row when the rows are set and once per centroid after every update, d = max(0, fl(fl(nn(q) + nn(c)) - 2 dot)),
+ *   and a NaN stays a NaN.
+ * Assignment.  label(i) is the centroid of the smallest distance, the smaller index among equal distances (the strict order of a
+ *   neighbour list; +0 == -0); a NaN distance never wins.  A row whose distances are all NaN has label -1 and distance NaN and is
+ *   left out of every count, sum and inertia.  The order is strict, so tiling and lane order do not enter.
+ * The order of a float64 sum.  The members of a set, in ascending row index, are cut into consecutive runs of L3_KMEANS_RUN members;
+ *   each run is summed sequentially from 0.0 in float64; the run sums are then added sequentially in ascending order.  There are no
+ *   float atomics.  The order holds for the centroid sums S_c (members: the rows of cluster c), the inertia (members: the rows with
+ *   label >= 0; terms: their float32 distances widened) and the seeding's cumulative potential (below).
+ * Update.  n_c members: C[c][f] = (float)(S_c[f] / (double)n_c) where n_c > 0; an empty cluster keeps its centroid bit for bit and
+ *   is counted (`empty`).  Empty clusters are not relocated.
+ * l3_kmeans_fit runs the iterations it = 0 .. max_iter - 1: assign with the current centroids; record history[3 it ..] = inertia,
+ *   changed (rows whose label differs from the iteration before; at it = 0 every row), empty (clusters without members); stop when
+ *   changed == 0 (labels and centroids agree), else update.  When max_iter is used up one more assignment runs, so the labels, the
+ *   distances and the inertia always belong to the centroids the handle holds.  *n_iter = the iterations run = history's rows.  The
+ *   iteration's only read-back is those scalars.
+ * Seeding.  l3_kmeans_seed_rows: centroid c = row rows[c].  l3_kmeans_seed_pp: plain k-means++, one candidate per step, from K draws
+ *   u in [0, 1) made by the caller.  Centre 0 is row floor(u[0] n); mind[i] = d(i, centre 0); for t = 1 .. K - 1: cum[i] = the
+ *   running total of mind in the order above (rows in runs of L3_KMEANS_RUN: within a run the sequential prefix from 0.0, a run's
+ *   offset the sequential sum of the earlier runs' totals, cum[i] = fl(offset + prefix)); the pick is the first i with cum[i] >
+ *   fl(u[t] cum[n - 1]); then mind[i] = d < mind[i] ? d : mind[i] with d = d(i, new centre).  Edge rules: a NaN mind counts as 0 in
+ *   cum (such a row is never picked by the search) and stays NaN; when the total is 0 the pick is floor(u[t] n); when no i qualifies
+ *   the pick is the last row with mind > 0.  A centre is a data row, so d(i, centre) has the bits l3_knn_list gives for that pair.
+ *   chosen_out (K int64, or NULL): the centres' rows.
+ *   l3_kmeans_set_rows[_dev]   n >= K host rows (n, D), or rows [lo, hi) of an l3_feat on the handle's device; voids the labels
+ *   l3_kmeans_set_centroids    K host centroids (K, D)
+ *   l3_kmeans_assign           one assignment of the rows: labels (n) int32, dist (n) float32, *inertia, *changed (against the
+ *                              assignment before; every row after l3_kmeans_set_rows or a seeding).  Every output may be NULL:
+ *                              nothing but the scalars is downloaded.  Also sorts the rows by label for l3_kmeans_update.
+ *   l3_kmeans_update           the centroids of the last assignment's labels; counts_out (K int64, or NULL) = n_c
+ *   l3_kmeans_get_labels       the last assignment's labels, distances and inertia (each may be NULL)
+ *   l3_kmeans_get_centroids    (K, D) float32
+ *   l3_kmeans_predict[_dev]    other rows against the current centroids: labels and dist (each may be NULL); they stay on the device
+ *   l3_kmeans_contingency      table (K, n_classes) int64, row major: table[label][class] counts the rows of `which` (0: the fitted
+ *                              rows' last assignment, 1: the last l3_kmeans_predict); classes: one int32 in [0, n_classes) per row;
+ *                              n_classes <= L3_KMEANS_MAX_CLASSES.  Rows of label -1 are not counted.  Integer adds only.
+ *   l3_kmeans_file_hist        hist (n_files, K) int32: the labels of the rows [s, e) of each file counted per cluster (file_idxs:
+ *                              n_files int64 pairs, 0 <= s < e <= the rows of `which`).  Integer adds only.
+ *   l3_kmeans_time             device time in ms per round over `reps` rounds (hipEvents, one untimed round first): what 0 the
+ *                              assignment kernel, 1 the update, 2 a whole iteration (the centroids move on), 3 a k-means++ seeding of
+ *                              all K centres (every draw 0.5; replaces the centroids), 4 the sort by label, 5 the inertia.  Voids
+ *                              the labels.  For the records under profiles/.
+ *   l3_op_kmeans_step          host rows (n, D) and centroids (K, D) in; labels, dist, *inertia, counts (K int64) and the updated
+ *                              centroids out (each may be NULL), by the kernels alone.
+ * L3_EINVAL (message in l3_last_error(NULL), naming the call, before the device is touched): a NULL pointer, D <= 0, K outside [1,
+ * L3_KMEANS_MAX_CLUSTERS], K > n, L3_KNN_COSINE, max_iter < 1, a draw outside [0, 1), a seed row, class or file out of range,
+ * n_classes outside [1, L3_KMEANS_MAX_CLASSES], a call before what it needs, an l3_feat of another width or on another device. */
+#define L3_KMEANS_RUN 256               /* members of a run of a float64 sum */
+#define L3_KMEANS_MAX_CLUSTERS 65536
+#define L3_KMEANS_MAX_CLASSES 256
+typedef struct l3_kmeans l3_kmeans;
+int l3_kmeans_create(int device, int D, int K, int metric, l3_kmeans **h);
+void l3_kmeans_destroy(l3_kmeans *h);
+int l3_kmeans_set_rows(l3_kmeans *h, const float *rows, int64_t n);
+int l3_kmeans_set_rows_dev(l3_kmeans *h, const l3_feat *f, int64_t lo, int64_t hi);
+int l3_kmeans_set_centroids(l3_kmeans *h, const float *centroids);
+int l3_kmeans_seed_rows(l3_kmeans *h, const int64_t *rows);
+int l3_kmeans_seed_pp(l3_kmeans *h, const double *u, int64_t *chosen_out);
+int l3_kmeans_assign(l3_kmeans *h, int32_t *labels, float *dist, double *inertia, int64_t *changed);
+int l3_kmeans_update(l3_kmeans *h, int64_t *counts_out);
+int l3_kmeans_fit(l3_kmeans *h, int max_iter, double *history_out, int *n_iter_out);
+int l3_kmeans_get_labels(l3_kmeans *h, int32_t *labels, float *dist, double *inertia);
+int l3_kmeans_get_centroids(l3_kmeans *h, float *out);
+int l3_kmeans_predict(l3_kmeans *h, const float *rows, int64_t n, int32_t *labels, float *dist);
+int l3_kmeans_predict_dev(l3_kmeans *h, const l3_feat *f, int64_t lo, int64_t hi, int32_t *labels, float *dist);
+int l3_kmeans_contingency(l3_kmeans *h, int which, const int32_t *classes, int n_classes, int64_t *table);
+int l3_kmeans_file_hist(l3_kmeans *h, int which, const int64_t *file_idxs, int64_t n_files, int32_t *hist);
+int l3_kmeans_time(l3_kmeans *h, int what, int reps, double *ms);
+int l3_op_kmeans_step(int device, const float *rows, const float *centroids, int64_t n, int K, int D, int32_t *labels, float *dist,
+                      double *inertia, int64_t *counts, float *new_centroids);
+
 #ifdef __cplusplus
 }
 #endif

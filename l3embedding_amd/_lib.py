@@ -217,6 +217,26 @@ SIGNATURES = {
                     [C.c_void_p] * 4),
     'l3_op_knn_topk': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_int] * 4 + [C.c_void_p] * 4),
     'l3_knn_time': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    # k-means over embedding rows (csrc/kmeans.hip)
+    'l3_kmeans_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    'l3_kmeans_destroy': (None, [C.c_void_p]),
+    'l3_kmeans_set_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_kmeans_set_rows_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    'l3_kmeans_set_centroids': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'l3_kmeans_seed_rows': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'l3_kmeans_seed_pp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_kmeans_assign': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'l3_kmeans_update': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'l3_kmeans_fit': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    'l3_kmeans_get_labels': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    'l3_kmeans_get_centroids': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'l3_kmeans_predict': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'l3_kmeans_predict_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    'l3_kmeans_contingency': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    'l3_kmeans_file_hist': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_kmeans_time': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    'l3_op_kmeans_step': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
+                                    C.c_void_p, C.c_void_p]),
     'l3_frontend_cfg': (C.c_int, [C.c_int] * 5 + [C.c_void_p]),
     'l3_frontend_tables': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int64, C.POINTER(C.c_int64)]),
     'l3_op_frontend_frames': (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4),
@@ -2243,6 +2263,261 @@ def op_knn_topk(Q, X, k, metric='sqeuclidean', segments=0, group_q=None, group_c
     check(load().l3_op_knn_topk(int(device), _ptr(Q), _ptr(X), nq, nc, Q.shape[1], KNN_METRICS[metric], k, int(segments), _ptr(gq), _ptr(gc),
                                 _ptr(idx), _ptr(dist)))
     return idx, dist
+
+
+# ---- k-means over embedding rows (csrc/kmeans.hip) --------------------------------------------------------------------
+KMEANS_RUN = 256                   # L3_KMEANS_RUN
+KMEANS_MAX_CLUSTERS = 65536        # L3_KMEANS_MAX_CLUSTERS
+KMEANS_MAX_CLASSES = 256           # L3_KMEANS_MAX_CLASSES
+KMEANS_TIMED = ('assign', 'update', 'iteration', 'seed', 'sort', 'inertia')
+
+
+def kmeans_check_k(K, n=None):
+    """K as an int in [1, min(n, KMEANS_MAX_CLUSTERS)]; ValueError otherwise"""
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= KMEANS_MAX_CLUSTERS:
+        raise ValueError('n_clusters must be an integer in [1, %d], not %r' % (KMEANS_MAX_CLUSTERS, K))
+    if n is not None and K > n:
+        raise ValueError('%d clusters need at least as many rows, not %d' % (K, n))
+    return int(K)
+
+
+def kmeans_check_metric(metric):
+    if metric == 'cosine':
+        raise ValueError("k-means is defined for the squared Euclidean distance only: a cluster's mean minimises it and not the cosine "
+                         "distance (normalise the rows and use 'sqeuclidean')")
+    if metric != 'sqeuclidean':
+        raise ValueError("metric must be 'sqeuclidean', not %r" % (metric,))
+    return metric
+
+
+def _file_ranges(file_idxs, n):
+    files = np.ascontiguousarray(np.asarray(file_idxs, np.int64).reshape(-1, 2))
+    if len(files) < 1 or np.any(files[:, 0] < 0) or np.any(files[:, 0] >= files[:, 1]) or np.any(files[:, 1] > n):
+        raise ValueError('file_idxs must hold row ranges [s, e) with 0 <= s < e <= %d' % n)
+    return files
+
+
+class KMeans(object):
+    """RAII wrapper over an l3_kmeans handle: float32 rows and K centroids resident on one device.  Every argument is checked here
+    first (ValueError) and the handle is created by the first call that needs the device."""
+
+    def __init__(self, D, K, metric='sqeuclidean', device=0):
+        if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or not 1 <= D <= 2 ** 20:
+            raise ValueError('D must be an integer in [1, 2^20], not %r' % (D,))
+        self.D, self.K, self.metric, self.device = int(D), kmeans_check_k(K), kmeans_check_metric(metric), int(device)
+        self.lib = None
+        self.h = None
+        self.n = self.n_predicted = 0
+        self.has_centroids = self.assigned = False
+
+    def _handle(self):
+        if self.h is None:
+            self.lib = load()
+            h = C.c_void_p()
+            check(self.lib.l3_kmeans_create(self.device, self.D, self.K, KNN_METRICS[self.metric], C.byref(h)))
+            self.h = h
+        return self.h
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_kmeans_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _rows(self, rows, side):
+        x, n = _knn_rows(rows, self.D, side)
+        if isinstance(x, Features) and x.device != self.device:
+            raise ValueError('the %s features are on device %d, the handle on device %d' % (side, x.device, self.device))
+        return x, n
+
+    def set_rows(self, rows):
+        """(n >= K, D) host rows or a Features on this device -> the handle's own copy; voids the labels"""
+        x, n = self._rows(rows, 'fitted')
+        kmeans_check_k(self.K, n)
+        h = self._handle()
+        self.n, self.assigned = 0, False
+        if isinstance(x, Features):
+            check(self.lib.l3_kmeans_set_rows_dev(h, x.h, 0, n))
+        else:
+            check(self.lib.l3_kmeans_set_rows(h, _ptr(x), n))
+        self.n = n
+
+    def _need_rows(self):
+        if self.n < 1:
+            raise ValueError('set_rows comes first')
+
+    def _need_centroids(self):
+        if not self.has_centroids:
+            raise ValueError('the centroids come first: set_centroids, seed_rows or seed_pp')
+
+    def set_centroids(self, centroids):
+        c = np.asarray(centroids)
+        if c.dtype != np.float32 or c.shape != (self.K, self.D):
+            raise ValueError('the centroids must be float32 of shape (%d, %d), not %s %s' % (self.K, self.D, c.dtype, c.shape))
+        c = np.ascontiguousarray(c)
+        h = self._handle()
+        self.has_centroids = self.assigned = False
+        check(self.lib.l3_kmeans_set_centroids(h, _ptr(c)))
+        self.has_centroids = True
+
+    def seed_rows(self, rows):
+        """the centroids become the fitted rows `rows` (K indices)"""
+        self._need_rows()
+        idx = np.asarray(rows)
+        if idx.ndim != 1 or len(idx) != self.K or idx.dtype.kind not in 'iu' or idx.min() < 0 or idx.max() >= self.n:
+            raise ValueError('rows must be %d indices in [0, %d)' % (self.K, self.n))
+        idx = np.ascontiguousarray(idx, np.int64)
+        self.has_centroids = self.assigned = False
+        check(self.lib.l3_kmeans_seed_rows(self._handle(), _ptr(idx)))
+        self.has_centroids = True
+
+    def seed_pp(self, u):
+        """k-means++ from the K draws u in [0, 1) -> the K chosen rows (int64)"""
+        self._need_rows()
+        u = np.asarray(u)
+        if u.dtype != np.float64 or u.shape != (self.K,) or not np.all((u >= 0.0) & (u < 1.0)):
+            raise ValueError('u must be %d float64 draws in [0, 1)' % self.K)
+        u = np.ascontiguousarray(u)
+        chosen = np.empty(self.K, np.int64)
+        self.has_centroids = self.assigned = False
+        check(self.lib.l3_kmeans_seed_pp(self._handle(), _ptr(u), _ptr(chosen)))
+        self.has_centroids = True
+        return chosen
+
+    def assign(self, outputs=('labels', 'dist')):
+        """one assignment -> dict with 'inertia', 'changed' and what `outputs` names of 'labels' (n int32) and 'dist' (n float32)"""
+        self._need_rows()
+        self._need_centroids()
+        got = {}
+        if 'labels' in outputs:
+            got['labels'] = np.empty(self.n, np.int32)
+        if 'dist' in outputs:
+            got['dist'] = np.empty(self.n, np.float32)
+        inertia, changed = C.c_double(), C.c_int64()
+        check(self.lib.l3_kmeans_assign(self._handle(), _ptr(got.get('labels')), _ptr(got.get('dist')), C.byref(inertia), C.byref(changed)))
+        self.assigned = True
+        got['inertia'], got['changed'] = inertia.value, changed.value
+        return got
+
+    def update(self):
+        """the centroids of the last assignment's labels -> the K member counts (int64)"""
+        if not self.assigned:
+            raise ValueError('assign comes first')
+        counts = np.empty(self.K, np.int64)
+        check(self.lib.l3_kmeans_update(self._handle(), _ptr(counts)))
+        return counts
+
+    def fit(self, max_iter):
+        """l3_kmeans_fit -> history (n_iter, 3) float64: inertia, changed, empty of every iteration"""
+        self._need_rows()
+        self._need_centroids()
+        if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or not 1 <= max_iter < 2 ** 31:
+            raise ValueError('max_iter must be an integer >= 1, not %r' % (max_iter,))
+        history = np.zeros((int(max_iter), 3), np.float64)
+        n_iter = C.c_int()
+        check(self.lib.l3_kmeans_fit(self._handle(), int(max_iter), _ptr(history), C.byref(n_iter)))
+        self.assigned = True
+        return history[:n_iter.value].copy()
+
+    def labels(self, outputs=('labels', 'dist')):
+        """the last assignment's 'labels', 'dist' (as `outputs` names them) and 'inertia'"""
+        if not self.assigned:
+            raise ValueError('assign or fit comes first')
+        got = {}
+        if 'labels' in outputs:
+            got['labels'] = np.empty(self.n, np.int32)
+        if 'dist' in outputs:
+            got['dist'] = np.empty(self.n, np.float32)
+        inertia = C.c_double()
+        check(self.lib.l3_kmeans_get_labels(self._handle(), _ptr(got.get('labels')), _ptr(got.get('dist')), C.byref(inertia)))
+        got['inertia'] = inertia.value
+        return got
+
+    def centroids(self):
+        self._need_centroids()
+        out = np.empty((self.K, self.D), np.float32)
+        check(self.lib.l3_kmeans_get_centroids(self._handle(), _ptr(out)))
+        return out
+
+    def predict(self, rows, outputs=('labels', 'dist')):
+        """other rows against the current centroids -> dict of 'labels' and 'dist' as `outputs` names them"""
+        self._need_centroids()
+        x, n = self._rows(rows, 'other')
+        got = {}
+        if 'labels' in outputs:
+            got['labels'] = np.empty(n, np.int32)
+        if 'dist' in outputs:
+            got['dist'] = np.empty(n, np.float32)
+        self.n_predicted = 0
+        if isinstance(x, Features):
+            check(self.lib.l3_kmeans_predict_dev(self._handle(), x.h, 0, n, _ptr(got.get('labels')), _ptr(got.get('dist'))))
+        else:
+            check(self.lib.l3_kmeans_predict(self._handle(), _ptr(x), n, _ptr(got.get('labels')), _ptr(got.get('dist'))))
+        self.n_predicted = n
+        return got
+
+    def _which(self, predicted):
+        if predicted and self.n_predicted < 1:
+            raise ValueError('predict comes first')
+        if not predicted and not self.assigned:
+            raise ValueError('assign or fit comes first')
+        return (1, self.n_predicted) if predicted else (0, self.n)
+
+    def contingency(self, classes, n_classes, predicted=False):
+        """(K, n_classes) int64: the rows of every (label, class) pair; of the fitted rows, or of the last predict's"""
+        which, n = self._which(predicted)
+        if isinstance(n_classes, bool) or not isinstance(n_classes, (int, np.integer)) or not 1 <= n_classes <= KMEANS_MAX_CLASSES:
+            raise ValueError('n_classes must be an integer in [1, %d], not %r' % (KMEANS_MAX_CLASSES, n_classes))
+        cls = _index32(np.asarray(classes).reshape(-1), 'classes', n, int(n_classes), 'row')
+        table = np.empty((self.K, int(n_classes)), np.int64)
+        check(self.lib.l3_kmeans_contingency(self._handle(), which, _ptr(cls), int(n_classes), _ptr(table)))
+        return table
+
+    def file_hist(self, file_idxs, predicted=False):
+        """(F, K) int32: the labels of each file's rows [s, e) counted per cluster"""
+        which, n = self._which(predicted)
+        files = _file_ranges(file_idxs, n)
+        hist = np.empty((len(files), self.K), np.int32)
+        check(self.lib.l3_kmeans_file_hist(self._handle(), which, _ptr(files), len(files), _ptr(hist)))
+        return hist
+
+    def time(self, what, reps=3):
+        """l3_kmeans_time: device ms per round of one of KMEANS_TIMED; voids the labels"""
+        if what not in KMEANS_TIMED:
+            raise ValueError('what must be one of %s' % (KMEANS_TIMED,))
+        self._need_rows()
+        if what != 'seed':
+            self._need_centroids()
+        ms = C.c_double()
+        self.assigned = False
+        check(self.lib.l3_kmeans_time(self._handle(), KMEANS_TIMED.index(what), int(reps), C.byref(ms)))
+        if what == 'seed':
+            self.has_centroids = True
+        return ms.value
+
+
+def op_kmeans_step(X, centroids, device=0):
+    """l3_op_kmeans_step: one assignment of the rows X (n, D) to the centroids (K, D) and the update that follows, by the kernels
+    alone -> dict of labels (n) int32, dist (n) float32, inertia, counts (K) int64 and the new centroids (K, D)"""
+    X, cen = np.asarray(X), np.asarray(centroids)
+    if X.dtype != np.float32 or cen.dtype != np.float32:
+        raise ValueError('the rows and the centroids must be float32 (there is no silent conversion)')
+    if X.ndim != 2 or cen.ndim != 2 or X.shape[1] != cen.shape[1] or X.shape[1] < 1:
+        raise ValueError('need X (n, D) and centroids (K, D) with D >= 1')
+    n, D = X.shape
+    K = kmeans_check_k(cen.shape[0], n)
+    X, cen = np.ascontiguousarray(X), np.ascontiguousarray(cen)
+    got = dict(labels=np.empty(n, np.int32), dist=np.empty(n, np.float32), counts=np.empty(K, np.int64), centroids=np.empty((K, D), np.float32))
+    inertia = C.c_double()
+    check(load().l3_op_kmeans_step(int(device), _ptr(X), _ptr(cen), n, K, D, _ptr(got['labels']), _ptr(got['dist']), C.byref(inertia),
+                                   _ptr(got['counts']), _ptr(got['centroids'])))
+    got['inertia'] = inertia.value
+    return got
 
 
 # ---- downstream MLP classifier (classifier/train.py:230-391; csrc/mlp.hip) ---------------------------------------------------------

@@ -14,6 +14,7 @@
 //   knn_side_kernel    a lane per row: nn(x) or r(x), the row's "side value"
 //   knn_tile_kernel    a 128 x 128 block of distances per workgroup of 4 waves; wave w owns the query rows 32 w .. 32 w + 31 and all
 //                      128 candidates: four independent 32 x 32 accumulators (the fp32 MFMA's issue rate needs no more).
+//                      The tile's code is in knn_tile.h, which kmeans.hip shares.
 //                      Query and candidate rows go through LDS 32 features at a time as [row][33]; the next chunk's global loads are
 //                      issued into registers before the current chunk's MFMAs.  Rows past a set's end and features past D are zeros
 //                      in the stage and are never read from memory.
@@ -35,13 +36,13 @@
 #include "featprep.h"
 #include "host_common.h"
 #include "knn.h"
+#include "knn_tile.h"
 
 namespace l3 {
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr int TQ = 128, TC = 128;           // queries and candidates of a workgroup's tile
-constexpr int KC = 32, LDK = KC + 1;        // features of a staged chunk; LDS row of 32 + 1
+using namespace knn_tile;          // BLOCK, TQ, TC, KC, LDK, distance_of and the tile's dot products
+
 constexpr int TOPK_MAX = L3_KNN_TOPK_MAX;
 constexpr int EMPTY = INT32_MAX;            // a real index is at most 2^31 - 2
 constexpr int MAX_SEGMENTS = L3_KNN_MAX_SEGMENTS;
@@ -56,12 +57,6 @@ constexpr int MIN_TILES = 4, MAX_ROUNDS = 8;
 constexpr int VOTE_MAX_SIZES = L3_KNN_MAX_SIZES, VOTE_MAX_CLASSES = L3_KNN_MAX_CLASSES;
 constexpr int64_t MAX_ROWS = INT32_MAX;     // indices 0 .. 2^31 - 2
 constexpr int64_t TIME_BLOCK = 8192;        // l3_knn_time what 1: the block [0, 8192) x [0, 8192) at most
-
-__device__ __forceinline__ float distance_of(int metric, float dot, float sq, float sc) {
-    if (metric == L3_KNN_COSINE) return __fsub_rn(1.0f, __fmul_rn(__fmul_rn(dot, sq), sc));
-    const float x = __fsub_rn(__fadd_rn(sq, sc), __fmul_rn(2.0f, dot));
-    return x < 0.0f ? 0.0f : x;          // (fmaxf would turn a NaN into 0)
-}
 
 __global__ __launch_bounds__(BLOCK) void knn_side_kernel(const float* __restrict__ x, int64_t n, int D, int metric, float* __restrict__ out) {
     const int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -82,80 +77,7 @@ __global__ __launch_bounds__(BLOCK) void knn_side_kernel(const float* __restrict
     out[r] = metric == L3_KNN_COSINE ? (acc == 0.0f ? 0.0f : __fdiv_rn(1.0f, __fsqrt_rn(acc))) : acc;
 }
 
-// ---- the tile's dot products ------------------------------------------------------------------------------------------------------
-// A chunk is 256 rows (128 queries, then 128 candidates) of 32 features: 2048 float4, 8 a lane; slot e = tid + 256 i is row e >> 3,
-// features 4 (e & 7) .. + 3, so i < 4 are query rows and i >= 4 candidate rows.
-__device__ __forceinline__ void fetch_chunk(float4 (&pre)[8], const float* __restrict__ Q, const float* __restrict__ Cd, int D, bool vec,
-                                            int64_t i0, int64_t nq, int64_t j0, int64_t nc, int k0, int tid) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int e = tid + BLOCK * i, row = e >> 3, k = k0 + (e & 7) * 4;
-        const bool isq = i < 4;
-        const int64_t g = isq ? i0 + row : j0 + (row - TQ);
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (g < (isq ? nq : nc) && k < D) {
-            const float* p = (isq ? Q : Cd) + g * D + k;
-            if (vec) {          // D % 4 == 0: the four features are inside the row together
-                v = *reinterpret_cast<const float4*>(p);
-            } else {
-                v.x = p[0];
-                if (k + 1 < D) v.y = p[1];
-                if (k + 2 < D) v.z = p[2];
-                if (k + 3 < D) v.w = p[3];
-            }
-        }
-        pre[i] = v;
-    }
-}
-
-__device__ __forceinline__ void store_chunk(const float4 (&pre)[8], float* stage, int tid) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int e = tid + BLOCK * i;
-        float* s = stage + (e >> 3) * LDK + (e & 7) * 4;
-        s[0] = pre[i].x, s[1] = pre[i].y, s[2] = pre[i].z, s[3] = pre[i].w;
-    }
-}
-
-// acc[t][i] += dot of query row i0 + 32 w + mfma_row(i, h) and candidate j0 + 32 t + r, lane = (r, h).  Every lane of the workgroup
-// comes here (barriers); stage holds (TQ + TC) x LDK floats.  The last chunk's reads of the stage may still be going on in other
-// waves when a wave returns.
-__device__ __forceinline__ void accumulate_tile(f32x16 (&acc)[4], float* stage, const float* __restrict__ Q, const float* __restrict__ Cd,
-                                                int D, int64_t i0, int64_t nq, int64_t j0, int64_t nc, int tid) {
-    const int lane = tid & 63, r = lane & 31, h = lane >> 5, w = tid >> 6;
-    const bool vec = (D & 3) == 0;
-    float4 pre[8];
-    fetch_chunk(pre, Q, Cd, D, vec, i0, nq, j0, nc, 0, tid);
-    const float* qrow = stage + (32 * w + r) * LDK + h;
-    const float* crow = stage + (TQ + r) * LDK + h;
-    for (int k0 = 0; k0 < D; k0 += KC) {
-        __syncthreads();          // the chunk before has been read
-        store_chunk(pre, stage, tid);
-        __syncthreads();
-        if (k0 + KC < D) fetch_chunk(pre, Q, Cd, D, vec, i0, nq, j0, nc, k0 + KC, tid);
-#pragma unroll 4
-        for (int s = 0; s < KC / 2; ++s) {          // k-step s: features k0 + 2 s (lanes h = 0) and k0 + 2 s + 1 (h = 1), in that order
-            const float a = qrow[2 * s];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, crow[t * 32 * LDK + 2 * s], acc[t], 0, 0, 0);
-        }
-    }
-}
-
-// The distances of the tile, from the accumulators to M[query][candidate] (TQ x TC floats): wave w writes the rows 32 w .. 32 w + 31.
-__device__ __forceinline__ void tile_distances(const f32x16 (&acc)[4], float* M, const float* qs, const float* cs, int metric, int tid) {
-    const int lane = tid & 63, r = lane & 31, h = lane >> 5, w = tid >> 6;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const float sc = cs[32 * t + r];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = 32 * w + mfma_row(i, h);
-            M[row * TC + 32 * t + r] = distance_of(metric, acc[t][i], qs[row], sc);
-        }
-    }
-}
-
+// ---- the tile (knn_tile.h: fetch_chunk, store_chunk, accumulate_tile, tile_distances) -----------------------------------------------
 // The block [q0, q1) x [c0, c1) of distances: out[(i - q0) ldo + (j - c0)].  Workgroup (x, y): candidates from c0 + 128 x, queries
 // from q0 + 128 y.
 __global__ __launch_bounds__(BLOCK) void knn_tile_kernel(const float* __restrict__ Q, const float* __restrict__ Cd, const float* __restrict__ sq,
