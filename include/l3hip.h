@@ -1427,6 +1427,75 @@ int l3_kmeans_time(l3_kmeans *h, int what, int reps, double *ms);
 int l3_op_kmeans_step(int device, const float *rows, const float *centroids, int64_t n, int K, int D, int32_t *labels, float *dist,
                       double *inertia, int64_t *counts, float *new_centroids);
 
+/* ---- t-SNE: a map of n points in the plane from neighbour lists (csrc/tsne.hip) ---------------------------------------
+ * Exact t-SNE (no tree, no grid, no approximation parameter) over a sparse symmetric P.  The map is 2-D only.  Arithmetic, which is
+ * the contract (tests/tsne_ref.py is its float64 oracle and derives the bounds), the same in every call; a fit is a function of its
+ * inputs alone, there are no float atomics, two runs give the same bits:
+ * Calibration.  l3_op_tsne_conditional: per row of k sorted-or-not distances d_j, p_j = exp(-beta (d_j - min_j d_j)) / sum_p with
+ *   H(beta) = log(perplexity), H the Shannon entropy in nats.  Everything is float64; every sum runs over j ascending from 0.0:
+ *   sum_p += p_j, sum_dp += fl(d_j p_j); H = log(sum_p) + fl(fl(beta sum_dp) / sum_p).  The search is the bracket rule: beta = 1, lo =
+ *   -inf, hi = +inf; H > log(perplexity): lo = beta, beta = hi == +inf ? 2 beta : (beta + hi) / 2; else hi = beta, beta = lo == -inf ?
+ *   beta / 2 : (beta + lo) / 2.  Exactly L3_TSNE_SEARCH_STEPS moves run, with no early exit; p_out and beta_out are those of the beta
+ *   the last move left (one more evaluation).  A row of equal distances gives the uniform row.  A row with a NaN or an infinite
+ *   distance gives a NaN row and beta, and *bad_rows (may be NULL) counts such rows.
+ * Repulsive pass.  R_i = sum_{j != i} q_ij^2 (y_i - y_j), z_i = sum_{j != i} q_ij, q_ij = 1 / (1 + |y_i - y_j|^2); the term j = i is
+ *   left out (not subtracted); a coincident other point counts 1 in z_i and 0 in R_i.  Per pair, float32: dx = y_i.x - y_j.x (dy
+ *   likewise), d2 = fmaf(dx, dx, fl(dy dy)), q = rcp(fl(1 + d2)) with the hardware's approximate reciprocal (1 ulp), R.x =
+ *   fmaf(fl(q q), dx, R.x), z = fl(z + q).  Order: j ascending in runs of L3_TSNE_RUN; a run is a float32 chain from 0; the run sums
+ *   are added into float64 in ascending order, per segment of consecutive runs, from 0.0; the segments' float64 partials are added in
+ *   ascending order from 0.0.  l3_tsne_geometry gives what the bits depend on, a function of n alone: row_block = 256 for n <= 8192,
+ *   else 1024 (rows of a workgroup; a lane owns row_block / 256 rows); with runs = ceil(n / 256) and row_blocks = ceil(n / row_block):
+ *   runs_per_segment = max(1, ceil(runs row_blocks / 1024)), segments = ceil(runs / runs_per_segment).
+ * Sums over rows.  Z = sum_i z_i and the KL part sum_i kl_i: rows ascending in runs of L3_TSNE_RUN, a run summed sequentially from 0.0
+ *   in float64, the run sums added sequentially in ascending order.
+ * Attractive pass.  A_i = sum_{j in row i} P_ij q_ij (y_i - y_j), kl_i = sum_j P_ij log1p(d2_ij), in float64 from the float32
+ *   coordinates: d2 = fma(dx, dx, fl(dy dy)), pq = fl(P fl(1 / fl(1 + d2))), A.x = fma(pq, dx, A.x), kl = fma(P, log1p(d2), kl).  Lane l
+ *   of 64 takes the row's entries l, l + 64, ... in order from 0.0; the lanes are folded by the xor butterfly 32, 16, ..., 1 (v = v +
+ *   v[lane ^ m]).  KL = sum P log P + sum_i kl_i + log Z, with P log P summed on the host over the entries in order (0 log 0 = 0).
+ * Update.  Per coordinate: g = (float)(4.0 * (exaggeration * A - R / Z)) in float64; inc = fl(u g) < 0.0f (a zero product is not an
+ *   increase); gain = inc ? fl(gain + 0.2f) : fl(gain 0.8f), then 0.01f where gain < 0.01f; u = fl(fl(momentum u) - fl(fl(lr gain)
+ *   g)) with momentum and lr narrowed to float32; y = fl(y + u).  There is no recentring.
+ *   l3_tsne_create             a handle for maps of n points on one device
+ *   l3_tsne_set_affinities     P as CSR: indptr (n + 1) int64, cols int32, vals float32.  Any symmetric P whose entries sum to 1 (the
+ *                              caller's to ensure); a row may be empty.  Refused: unsorted (not strictly ascending) or out-of-range
+ *                              columns, a diagonal entry, a negative or non-finite value.  Computes sum P log P once.
+ *   l3_tsne_set_embedding      y (n, 2) float32; the last update becomes 0, the gains 1, the iteration count 0
+ *   l3_tsne_get_embedding      y (n, 2) float32
+ *   l3_tsne_run                n_iter iterations (repulsive, attractive, update) with no read-back except the records: at every
+ *                              kl_every-th iteration of the call and at its last, one record of 3 float64 into history_out (may be
+ *                              NULL): the iteration's index since l3_tsne_set_embedding, KL (of the map before that iteration's
+ *                              update, with the P that was set: exaggeration does not enter), Z.  history_out holds n_iter / kl_every
+ *                              + 1 records; *n_records the number written.  Z stays on the device for the update.  A Z that is zero
+ *                              or not finite at a record stops the run with L3_EINVAL.
+ *   l3_tsne_time               device time in ms per round over `reps` rounds (hipEvents, one untimed round first): what 0 the
+ *                              repulsive pass with its finish and Z, 1 the attractive pass, 2 the update, 3 a whole iteration, 4 the
+ *                              pair kernel alone.  The map moves on under 2 and 3.  For the records under profiles/.
+ *   l3_op_tsne_repulsive       y (n, 2) in; R (n, 2), z (n) float64 and *Z out (each may be NULL), by the kernels alone
+ *   l3_op_tsne_attractive      y and a CSR P in; A (n, 2) float64, *kl_rows = sum_i kl_i and *plogp = sum P log P out
+ *   l3_op_tsne_update          y, update, gains (n, 2) float32 in and out; A, R (n, 2) float64 and Z in
+ * L3_EINVAL (message in l3_last_error(NULL), naming the call): a NULL pointer, n outside [1, 2^24], k outside [2, L3_KNN_TOPK_MAX],
+ * perplexity outside (1, k), a CSR as above, n_iter or kl_every < 1, exaggeration or learning rate <= 0, momentum outside [0, 1).
+ * L3_ESTATE: l3_tsne_run or l3_tsne_get_embedding before what it needs. */
+#define L3_TSNE_RUN 256                 /* pairs of a float32 chain; rows of a run of a float64 sum */
+#define L3_TSNE_SEARCH_STEPS 100        /* moves of the calibration's bracket, always all of them */
+typedef struct l3_tsne l3_tsne;
+int l3_op_tsne_conditional(int device, const float *dist, int64_t n, int k, double perplexity, double *p_out, double *beta_out,
+                           int64_t *bad_rows);
+int l3_tsne_geometry(int64_t n, int *row_block, int *segments);
+int l3_tsne_create(int device, int64_t n, l3_tsne **h);
+void l3_tsne_destroy(l3_tsne *h);
+int l3_tsne_set_affinities(l3_tsne *h, const int64_t *indptr, const int32_t *cols, const float *vals);
+int l3_tsne_set_embedding(l3_tsne *h, const float *y);
+int l3_tsne_get_embedding(l3_tsne *h, float *y);
+int l3_tsne_run(l3_tsne *h, int n_iter, double exaggeration, double momentum, double learning_rate, int kl_every, double *history_out,
+                int *n_records);
+int l3_tsne_time(l3_tsne *h, int what, int reps, double *ms);
+int l3_op_tsne_repulsive(int device, const float *y, int64_t n, double *R_out, double *z_out, double *Z_out);
+int l3_op_tsne_attractive(int device, const float *y, int64_t n, const int64_t *indptr, const int32_t *cols, const float *vals,
+                          double *A_out, double *kl_rows_out, double *plogp_out);
+int l3_op_tsne_update(int device, int64_t n, float *y, float *update, float *gains, const double *A, const double *R, double Z,
+                      double exaggeration, double momentum, double learning_rate);
+
 #ifdef __cplusplus
 }
 #endif

@@ -235,6 +235,20 @@ SIGNATURES = {
     'l3_kmeans_contingency': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     'l3_kmeans_file_hist': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     'l3_kmeans_time': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    # t-SNE maps (csrc/tsne.hip)
+    'l3_op_tsne_conditional': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    'l3_tsne_geometry': (C.c_int, [C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'l3_tsne_create': (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_void_p)]),
+    'l3_tsne_destroy': (None, [C.c_void_p]),
+    'l3_tsne_set_affinities': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_tsne_set_embedding': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'l3_tsne_get_embedding': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'l3_tsne_run': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    'l3_tsne_time': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    'l3_op_tsne_repulsive': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    'l3_op_tsne_attractive': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double)]),
+    'l3_op_tsne_update': (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_double] * 4),
     'l3_op_kmeans_step': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
                                     C.c_void_p, C.c_void_p]),
     'l3_frontend_cfg': (C.c_int, [C.c_int] * 5 + [C.c_void_p]),
@@ -2518,6 +2532,200 @@ def op_kmeans_step(X, centroids, device=0):
                                    _ptr(got['counts']), _ptr(got['centroids'])))
     got['inertia'] = inertia.value
     return got
+
+
+# ---- t-SNE maps of embedding rows (csrc/tsne.hip) ----------------------------------------------------------------------
+TSNE_RUN = 256                     # L3_TSNE_RUN
+TSNE_SEARCH_STEPS = 100            # L3_TSNE_SEARCH_STEPS
+TSNE_MAX_POINTS = 2 ** 24
+TSNE_TIMED = ('repulsive', 'attractive', 'update', 'iteration', 'pairs')
+
+
+def tsne_check_n(n):
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= TSNE_MAX_POINTS:
+        raise ValueError('a map holds 1 to 2^24 points, not %r' % (n,))
+    return int(n)
+
+
+def tsne_check_perplexity(perplexity, k):
+    """(perplexity as float, k as int) with 2 <= k <= KNN_TOPK_MAX and 1 < perplexity < k; ValueError otherwise"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 2 <= k <= KNN_TOPK_MAX:
+        raise ValueError('a neighbour list must hold 2 to %d entries, not %r' % (KNN_TOPK_MAX, k))
+    if isinstance(perplexity, bool) or not isinstance(perplexity, (int, float, np.integer, np.floating)) or not 1.0 < perplexity < k:
+        raise ValueError('perplexity must be a number with 1 < perplexity < k = %d, not %r' % (k, perplexity))
+    return float(perplexity), int(k)
+
+
+def tsne_check_csr(n, indptr, cols, vals):
+    """a CSR matrix over n points as (int64 indptr, int32 cols, float32 vals): strictly ascending columns inside [0, n) in every row,
+    no diagonal entry, values finite and >= 0; ValueError otherwise"""
+    indptr, cols, vals = np.asarray(indptr), np.asarray(cols), np.asarray(vals)
+    if indptr.ndim != 1 or len(indptr) != n + 1 or indptr.dtype.kind not in 'iu' or indptr[0] != 0 or np.any(np.diff(indptr) < 0):
+        raise ValueError('indptr must be %d ascending integers that start at 0' % (n + 1))
+    nnz = int(indptr[-1])
+    if cols.ndim != 1 or len(cols) != nnz or cols.dtype.kind not in 'iu':
+        raise ValueError('cols must be %d integers, one per entry' % nnz)
+    if vals.dtype != np.float32 or vals.shape != (nnz,):
+        raise ValueError('vals must be %d float32 values, one per entry, not %s %s' % (nnz, vals.dtype, vals.shape))
+    indptr, cols = np.ascontiguousarray(indptr, np.int64), cols.astype(np.int64)
+    row = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+    if nnz and (cols.min() < 0 or cols.max() >= n):
+        raise ValueError('a column lies outside the %d points' % n)
+    if np.any(cols == row):
+        raise ValueError('the affinities hold a diagonal entry (row %d)' % int(row[cols == row][0]))
+    same_row = row[1:] == row[:-1]
+    if np.any(same_row & (cols[1:] <= cols[:-1])):
+        raise ValueError("the columns of row %d are unsorted: every row's columns ascend strictly" % int(row[1:][same_row & (cols[1:] <= cols[:-1])][0]))
+    if not np.all(np.isfinite(vals)) or np.any(vals < 0):
+        raise ValueError('the affinities must be finite and >= 0')
+    return indptr, np.ascontiguousarray(cols, np.int32), np.ascontiguousarray(vals)
+
+
+def _tsne_map(y, n, name='y'):
+    y = np.asarray(y)
+    if y.dtype != np.float32 or y.shape != (n, 2):
+        raise ValueError('%s must be float32 of shape (%d, 2), not %s %s (the map is 2-D only)' % (name, n, y.dtype, y.shape))
+    return np.ascontiguousarray(y)
+
+
+def _tsne_schedule(exaggeration, momentum, learning_rate):
+    ex, mom, lr = float(exaggeration), float(momentum), float(learning_rate)
+    if not (np.isfinite(ex) and ex > 0 and 0 <= mom < 1 and np.isfinite(lr) and lr > 0):
+        raise ValueError('need exaggeration > 0, 0 <= momentum < 1 and learning_rate > 0, not %r, %r, %r' % (exaggeration, momentum, learning_rate))
+    return ex, mom, lr
+
+
+def tsne_geometry(n):
+    """l3_tsne_geometry -> (row_block, segments) of the repulsive pass at n points: what its bits depend on besides the points"""
+    rb, seg = C.c_int(), C.c_int()
+    check(load().l3_tsne_geometry(tsne_check_n(n), C.byref(rb), C.byref(seg)))
+    return rb.value, seg.value
+
+
+def op_tsne_conditional(dist, perplexity, device=0):
+    """l3_op_tsne_conditional: (p (n, k) float64, beta (n) float64, bad_rows) of the neighbour distances dist (n, k) float32"""
+    dist = np.asarray(dist)
+    if dist.dtype != np.float32 or dist.ndim != 2 or dist.shape[0] < 1:
+        raise ValueError('dist must be float32 of shape (n >= 1, k), not %s %s' % (dist.dtype, dist.shape))
+    n = tsne_check_n(dist.shape[0])
+    perplexity, k = tsne_check_perplexity(perplexity, dist.shape[1])
+    dist = np.ascontiguousarray(dist)
+    p, beta, bad = np.empty((n, k), np.float64), np.empty(n, np.float64), C.c_int64()
+    check(load().l3_op_tsne_conditional(int(device), _ptr(dist), n, k, perplexity, _ptr(p), _ptr(beta), C.byref(bad)))
+    return p, beta, bad.value
+
+
+class TSNE(object):
+    """RAII wrapper over an l3_tsne handle: a map of n points, its update and gains, and a CSR P resident on one device.  Every
+    argument is checked here first (ValueError) and the handle is created by the first call that needs the device."""
+
+    def __init__(self, n, device=0):
+        self.n, self.device = tsne_check_n(n), int(device)
+        self.lib = None
+        self.h = None
+        self.has_affinities = self.has_embedding = False
+
+    def _handle(self):
+        if self.h is None:
+            self.lib = load()
+            h = C.c_void_p()
+            check(self.lib.l3_tsne_create(self.device, self.n, C.byref(h)))
+            self.h = h
+        return self.h
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_tsne_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_affinities(self, indptr, cols, vals):
+        indptr, cols, vals = tsne_check_csr(self.n, indptr, cols, vals)
+        h = self._handle()
+        self.has_affinities = False
+        check(self.lib.l3_tsne_set_affinities(h, _ptr(indptr), _ptr(cols), _ptr(vals)))
+        self.has_affinities = True
+
+    def set_embedding(self, y):
+        """y (n, 2) float32; the update becomes 0 and the gains 1"""
+        y = _tsne_map(y, self.n)
+        h = self._handle()
+        self.has_embedding = False
+        check(self.lib.l3_tsne_set_embedding(h, _ptr(y)))
+        self.has_embedding = True
+
+    def embedding(self):
+        if not self.has_embedding:
+            raise ValueError('set_embedding comes first')
+        y = np.empty((self.n, 2), np.float32)
+        check(self.lib.l3_tsne_get_embedding(self._handle(), _ptr(y)))
+        return y
+
+    def run(self, n_iter, exaggeration, momentum, learning_rate, kl_every=50):
+        """l3_tsne_run -> records (m, 3) float64: iteration, KL, Z"""
+        if not (self.has_affinities and self.has_embedding):
+            raise ValueError('set_affinities and set_embedding come first')
+        for name, value in (('n_iter', n_iter), ('kl_every', kl_every)):
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= value < 2 ** 31:
+                raise ValueError('%s must be an integer >= 1, not %r' % (name, value))
+        ex, mom, lr = _tsne_schedule(exaggeration, momentum, learning_rate)
+        history = np.zeros((int(n_iter) // int(kl_every) + 1, 3), np.float64)
+        m = C.c_int()
+        try:
+            check(self.lib.l3_tsne_run(self._handle(), int(n_iter), ex, mom, lr, int(kl_every), _ptr(history), C.byref(m)))
+        finally:
+            self.records = history[:m.value].copy()
+        return self.records
+
+    def time(self, what, reps=3):
+        """l3_tsne_time: device ms per round of one of TSNE_TIMED; 'update' and 'iteration' move the map"""
+        if what not in TSNE_TIMED:
+            raise ValueError('what must be one of %s' % (TSNE_TIMED,))
+        if not self.has_embedding or (what not in ('repulsive', 'pairs') and not self.has_affinities):
+            raise ValueError('set_embedding (and set_affinities) come first')
+        ms = C.c_double()
+        check(self.lib.l3_tsne_time(self._handle(), TSNE_TIMED.index(what), int(reps), C.byref(ms)))
+        return ms.value
+
+
+def op_tsne_repulsive(y, device=0):
+    """l3_op_tsne_repulsive: dict of R (n, 2), z (n) float64 and Z of the map y (n, 2) float32, by the kernels alone"""
+    y = np.asarray(y)
+    n = tsne_check_n(y.shape[0] if y.ndim == 2 else 0)
+    y = _tsne_map(y, n)
+    R, z, Z = np.empty((n, 2), np.float64), np.empty(n, np.float64), C.c_double()
+    check(load().l3_op_tsne_repulsive(int(device), _ptr(y), n, _ptr(R), _ptr(z), C.byref(Z)))
+    return dict(R=R, z=z, Z=Z.value)
+
+
+def op_tsne_attractive(y, indptr, cols, vals, device=0):
+    """l3_op_tsne_attractive: dict of A (n, 2) float64, kl_rows = sum P log1p(d^2) and plogp = sum P log P"""
+    y = np.asarray(y)
+    n = tsne_check_n(y.shape[0] if y.ndim == 2 else 0)
+    y = _tsne_map(y, n)
+    indptr, cols, vals = tsne_check_csr(n, indptr, cols, vals)
+    A, kl, plogp = np.empty((n, 2), np.float64), C.c_double(), C.c_double()
+    check(load().l3_op_tsne_attractive(int(device), _ptr(y), n, _ptr(indptr), _ptr(cols), _ptr(vals), _ptr(A), C.byref(kl), C.byref(plogp)))
+    return dict(A=A, kl_rows=kl.value, plogp=plogp.value)
+
+
+def op_tsne_update(y, update, gains, A, R, Z, exaggeration, momentum, learning_rate, device=0):
+    """l3_op_tsne_update -> the new (y, update, gains), float32 (n, 2); the inputs are left as they are"""
+    y = np.asarray(y)
+    n = tsne_check_n(y.shape[0] if y.ndim == 2 else 0)
+    y, u, g = _tsne_map(y, n).copy(), _tsne_map(update, n, 'update').copy(), _tsne_map(gains, n, 'gains').copy()
+    A, R = np.asarray(A), np.asarray(R)
+    if A.dtype != np.float64 or R.dtype != np.float64 or A.shape != (n, 2) or R.shape != (n, 2):
+        raise ValueError('A and R must be float64 of shape (%d, 2)' % n)
+    A, R = np.ascontiguousarray(A), np.ascontiguousarray(R)
+    ex, mom, lr = _tsne_schedule(exaggeration, momentum, learning_rate)
+    check(load().l3_op_tsne_update(int(device), n, _ptr(y), _ptr(u), _ptr(g), _ptr(A), _ptr(R), float(Z), ex, mom, lr))
+    return y, u, g
 
 
 # ---- downstream MLP classifier (classifier/train.py:230-391; csrc/mlp.hip) ---------------------------------------------------------
