@@ -1496,6 +1496,73 @@ int l3_op_tsne_attractive(int device, const float *y, int64_t n, const int64_t *
 int l3_op_tsne_update(int device, int64_t n, float *y, float *update, float *gains, const double *A, const double *R, double Z,
                       double exaggeration, double momentum, double learning_rate);
 
+/* ---- Principal components of embedding rows: mean, scatter matrix, projection (csrc/pca.hip) -------------------------
+ * A handle holds n >= 2 rows of D float32 (its own copy) on one device and, apart from them, a model of k <= D components.  The
+ * eigendecomposition between the two is the caller's (l3embedding_amd/pca.py: numpy.linalg.eigh of S / (n - 1) in float64).
+ * Arithmetic, which is the contract (tests/pca_ref.py derives the bounds from it), the same in every call and on every device; there
+ * are no float atomics, and two calls give the same bits:
+ * Mean.  The rows are cut into segments of L3_PCA_MEAN_SEG consecutive rows.  A column's sum over a segment is sequential in float64,
+ *   in ascending row order from 0.0; the segment sums are added sequentially in ascending order from 0.0; m64 = sum / (double)n and m32
+ *   = (float)m64.  The handle keeps both.  l3_pca_set_mean instead gives the handle an m32 of the caller's (m64 is its widening).
+ * Scatter.  S = sum over the rows of xc xc^T with xc = fl32(x - m32): one float32 subtraction as a row is staged.  The rows are cut into
+ *   chains of L3_PCA_CHAIN consecutive rows: chain c is the rows [L3_PCA_CHAIN c, min(n, L3_PCA_CHAIN (c + 1))), C = ceil(n /
+ *   L3_PCA_CHAIN) of them.  Within a chain an entry (i, j) is one float32 accumulator of v_mfma_f32_32x32x2_f32 taking the rows in
+ *   ascending order from 0: fmaf(xc[r][i], xc[r][j], acc).  The chains are dealt to `splits` row ranges: split s is the chains [floor(s
+ *   C / splits), floor((s + 1) C / splits)).  A split's partial is the float64 sum of its chains' results, widened, in ascending chain
+ *   order from 0.0; S is the float64 sum of the splits' partials in ascending split order, starting from the first.  Only the entries
+ *   i <= j are computed; each is written to (i, j) and (j, i), so S equals its transpose bit for bit.  The error of an entry against
+ *   the exact sum of the float32 xc is at most gamma_R sum_rows |xc_i xc_j|, gamma_R = R u / (1 - R u) with R = L3_PCA_CHAIN and u =
+ *   2^-24, plus the float64 sums' term.  L3_PCA_CHAIN is 256: the bound grows with it, and the float64 fold at a chain's end (64
+ *   conversions and additions a lane against the chain's 512 matrix instructions a wave) is already about one percent of the time.
+ *   splits: in [0, L3_PCA_MAX_SPLITS]; a count above C is clamped to C; 0 means the count l3_pca_splits names, a function of n and D
+ *   alone and never of the device: max(1, min(C, L3_PCA_MAX_SPLITS, floor(L3_PCA_FILL / U))) with T = ceil(D / 128) and U = T (T + 1) / 2, the
+ *   128 x 128 tiles on or above the diagonal (D = 512: U = 10, 51 splits at n >= 12 801; D = 6144: U = 1176, 1 split).
+ *   Workspace rule: beside the rows the handle holds splits x D x D float64 of partials and D x D float64 of S, grown on demand and
+ *   kept (D = 512 at 51 splits: 107 MB + 2 MB; D = 6144 at 1 split: 302 MB + 302 MB).
+ * Projection.  l3_pca_transform: y[i][c] = the ascending fmaf chain over d from 0 of fl32(x[i][d] - mean[d]) w[c][d] (the dot product
+ *   of the nearest-neighbour tile: D is never split over waves or accumulators), then, with a scale, fl32(y scale[c]) once.
+ *   l3_pca_inverse: x[i][d] = fl32(chain + mean[d]), chain over c from 0 of fl32(y[i][c] / scale[c]) w[c][d], the same kernel on the transposed
+ *   components, which l3_pca_set_model makes once; without a scale there is no division.
+ *   l3_pca_set_rows[_dev]      n >= 2 host rows (n, D), or rows [lo, hi) of an l3_feat on the handle's device (copied device to device);
+ *                              voids the mean.  A NaN or an infinity in the rows is refused with the lowest such row named.
+ *   l3_pca_mean                computes m64 and m32 of the rows; mean_out (D float64) and mean32_out (D float32) may each be NULL
+ *   l3_pca_set_mean            m32 = mean32 (D finite float32): a scatter about a mean of the caller's
+ *   l3_pca_scatter             S_out (D, D) float64, row major, about the handle's m32
+ *   l3_pca_splits              the count that splits = 0 stands for at (n, D)
+ *   l3_pca_set_model           k components (k, D) row major, the model's mean32 (D) and scale (k, each finite and > 0) or NULL;
+ *                              independent of the rows and of the mean the scatter uses
+ *   l3_pca_transform[_dev]     n >= 1 host rows (n, D) -> out (n, k); the _dev form takes rows [lo, hi) of an l3_feat and writes to out
+ *                              (host, may be NULL) and / or to a new l3_feat of (hi - lo, k) on the same device (*out_feat, when
+ *                              out_feat is not NULL), which the caller destroys
+ *   l3_pca_inverse[_dev]       the same from (n, k) to (n, D)
+ *   l3_pca_time                device time in ms per round over `reps` rounds (hipEvents, one untimed round first): what 0 the mean, 1
+ *                              the scatter (both kernels, splits = 0), 2 the projection of the fitted rows, 3 the scatter's tile
+ *                              kernel alone.  For the records under profiles/.
+ * L3_EINVAL (message in l3_last_error(NULL), naming the call): a NULL pointer, D outside [1, L3_PCA_MAX_D], n outside [2, 2^31 - 1]
+ * (projections: [1, 2^31 - 1]), a row that is not finite, splits outside [0, L3_PCA_MAX_SPLITS], k outside [1, D], a scale that is not
+ * positive and finite, a projection with no output, an l3_feat of another width or on another device.  L3_ESTATE: a call before the
+ * rows, the mean or the model it needs. */
+#define L3_PCA_CHAIN 256                /* rows of a float32 chain of the scatter: R of the error bound */
+#define L3_PCA_MEAN_SEG 256             /* rows of a segment of the mean's float64 sums */
+#define L3_PCA_FILL 512                 /* workgroups that splits = 0 aims at: two on each of 256 compute units */
+#define L3_PCA_MAX_SPLITS 256
+#define L3_PCA_MAX_D 16384
+typedef struct l3_pca l3_pca;
+int l3_pca_create(int device, int D, l3_pca **h);
+void l3_pca_destroy(l3_pca *h);
+int l3_pca_splits(int64_t n, int D, int *splits);
+int l3_pca_set_rows(l3_pca *h, const float *rows, int64_t n);
+int l3_pca_set_rows_dev(l3_pca *h, const l3_feat *f, int64_t lo, int64_t hi);
+int l3_pca_mean(l3_pca *h, double *mean_out, float *mean32_out);
+int l3_pca_set_mean(l3_pca *h, const float *mean32);
+int l3_pca_scatter(l3_pca *h, int splits, double *S_out);
+int l3_pca_set_model(l3_pca *h, int k, const float *mean32, const float *components, const float *scale);
+int l3_pca_transform(l3_pca *h, const float *rows, int64_t n, float *out);
+int l3_pca_transform_dev(l3_pca *h, const l3_feat *f, int64_t lo, int64_t hi, float *out, l3_feat **out_feat);
+int l3_pca_inverse(l3_pca *h, const float *Y, int64_t n, float *out);
+int l3_pca_inverse_dev(l3_pca *h, const l3_feat *f, int64_t lo, int64_t hi, float *out, l3_feat **out_feat);
+int l3_pca_time(l3_pca *h, int what, int reps, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

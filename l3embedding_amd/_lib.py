@@ -249,6 +249,21 @@ SIGNATURES = {
     'l3_op_tsne_attractive': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
                                         C.POINTER(C.c_double)]),
     'l3_op_tsne_update': (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_double] * 4),
+    # principal components of embedding rows (csrc/pca.hip)
+    'l3_pca_create': (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    'l3_pca_destroy': (None, [C.c_void_p]),
+    'l3_pca_splits': (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_int)]),
+    'l3_pca_set_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    'l3_pca_set_rows_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    'l3_pca_mean': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_pca_set_mean': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'l3_pca_scatter': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    'l3_pca_set_model': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_pca_transform': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_pca_transform_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]),
+    'l3_pca_inverse': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'l3_pca_inverse_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]),
+    'l3_pca_time': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     'l3_op_kmeans_step': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
                                     C.c_void_p, C.c_void_p]),
     'l3_frontend_cfg': (C.c_int, [C.c_int] * 5 + [C.c_void_p]),
@@ -2726,6 +2741,190 @@ def op_tsne_update(y, update, gains, A, R, Z, exaggeration, momentum, learning_r
     ex, mom, lr = _tsne_schedule(exaggeration, momentum, learning_rate)
     check(load().l3_op_tsne_update(int(device), n, _ptr(y), _ptr(u), _ptr(g), _ptr(A), _ptr(R), float(Z), ex, mom, lr))
     return y, u, g
+
+
+# ---- principal components of embedding rows (csrc/pca.hip) --------------------------------------------------------------
+PCA_CHAIN = 256                    # L3_PCA_CHAIN
+PCA_MEAN_SEG = 256                 # L3_PCA_MEAN_SEG
+PCA_FILL = 512                     # L3_PCA_FILL
+PCA_MAX_SPLITS = 256               # L3_PCA_MAX_SPLITS
+PCA_MAX_D = 16384                  # L3_PCA_MAX_D
+PCA_TIMED = ('mean', 'scatter', 'transform', 'scatter_tiles')
+
+
+def pca_check_d(D):
+    if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or not 1 <= D <= PCA_MAX_D:
+        raise ValueError('D must be an integer in [1, %d], not %r' % (PCA_MAX_D, D))
+    return int(D)
+
+
+def pca_splits(n, D):
+    """l3_pca_splits: the split count that splits=0 stands for at n rows of D features (a function of the two alone; no device)"""
+    D = pca_check_d(D)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= n <= KNN_MAX_ROWS:
+        raise ValueError('n must be an integer in [2, 2^31 - 1], not %r' % (n,))
+    out = C.c_int()
+    check(load().l3_pca_splits(int(n), D, C.byref(out)))
+    return out.value
+
+
+class PCA(object):
+    """RAII wrapper over an l3_pca handle: float32 rows resident on one device, their mean and scatter matrix, and a model of k
+    components to project onto.  Every argument is checked here first (ValueError) and the handle is created by the first call that
+    needs the device."""
+
+    def __init__(self, D, device=0):
+        self.D, self.device = pca_check_d(D), int(device)
+        self.lib = None
+        self.h = None
+        self.n = self.k = 0
+        self.has_mean = False
+
+    def _handle(self):
+        if self.h is None:
+            self.lib = load()
+            h = C.c_void_p()
+            check(self.lib.l3_pca_create(self.device, self.D, C.byref(h)))
+            self.h = h
+        return self.h
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_pca_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _rows(self, rows, width, side):
+        x, n = _knn_rows(rows, width, side)
+        if isinstance(x, Features) and x.device != self.device:
+            raise ValueError('the %s features are on device %d, the handle on device %d' % (side, x.device, self.device))
+        return x, n
+
+    def set_rows(self, rows, lo=0, hi=None):
+        """(n >= 2, D) host rows, or the rows [lo, hi) of a Features on this device -> the handle's own copy; voids the mean.  A
+        row that is not finite is refused by the library (L3Error naming the row)."""
+        x, n = self._rows(rows, self.D, 'fitted')
+        hi = n if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo < hi <= n:
+            raise ValueError('rows [%d, %d) are empty or outside the %d rows' % (lo, hi, n))
+        if hi - lo < 2:
+            raise ValueError('principal components need at least 2 rows, not %d' % (hi - lo))
+        h = self._handle()
+        self.n, self.has_mean = 0, False
+        if isinstance(x, Features):
+            check(self.lib.l3_pca_set_rows_dev(h, x.h, lo, hi))
+        else:
+            check(self.lib.l3_pca_set_rows(h, _ptr(x[lo:hi]), hi - lo))
+        self.n = hi - lo
+
+    def _need_rows(self):
+        if self.n < 2:
+            raise ValueError('set_rows comes first')
+
+    def mean(self):
+        """l3_pca_mean -> (m64 (D) float64, m32 (D) float32), which the handle keeps"""
+        self._need_rows()
+        m64, m32 = np.empty(self.D, np.float64), np.empty(self.D, np.float32)
+        self.has_mean = False
+        check(self.lib.l3_pca_mean(self._handle(), _ptr(m64), _ptr(m32)))
+        self.has_mean = True
+        return m64, m32
+
+    def set_mean(self, mean32):
+        """the handle's m32 becomes `mean32` (D finite float32): a scatter about a mean of the caller's"""
+        m = np.asarray(mean32)
+        if m.dtype != np.float32 or m.shape != (self.D,) or not np.all(np.isfinite(m)):
+            raise ValueError('the mean must be %d finite float32, not %s %s' % (self.D, m.dtype, m.shape))
+        m = np.ascontiguousarray(m)
+        self.has_mean = False
+        check(self.lib.l3_pca_set_mean(self._handle(), _ptr(m)))
+        self.has_mean = True
+
+    def scatter(self, splits=0):
+        """l3_pca_scatter -> S (D, D) float64, the sum over the rows of xc xc^T with xc = float32(x - m32); splits 0: pca_splits"""
+        self._need_rows()
+        if not self.has_mean:
+            raise ValueError('the mean comes first: mean or set_mean')
+        if isinstance(splits, bool) or not isinstance(splits, (int, np.integer)) or not 0 <= splits <= PCA_MAX_SPLITS:
+            raise ValueError('splits must be an integer in [0, %d], not %r' % (PCA_MAX_SPLITS, splits))
+        S = np.empty((self.D, self.D), np.float64)
+        check(self.lib.l3_pca_scatter(self._handle(), int(splits), _ptr(S)))
+        return S
+
+    def set_model(self, mean32, components, scale=None):
+        """the model to project onto: mean (D), components (k <= D, D) and scale (k, > 0) or None, all float32"""
+        m, w = np.asarray(mean32), np.asarray(components)
+        if m.dtype != np.float32 or m.shape != (self.D,):
+            raise ValueError('the mean must be float32 of shape (%d,), not %s %s' % (self.D, m.dtype, m.shape))
+        if w.dtype != np.float32 or w.ndim != 2 or w.shape[1] != self.D or not 1 <= w.shape[0] <= self.D:
+            raise ValueError('the components must be float32 of shape (1 <= k <= %d, %d), not %s %s' % (self.D, self.D, w.dtype, w.shape))
+        sc = None
+        if scale is not None:
+            sc = np.asarray(scale)
+            if sc.dtype != np.float32 or sc.shape != (w.shape[0],) or not np.all(np.isfinite(sc) & (sc > 0)):
+                raise ValueError('the scale must be %d positive finite float32' % w.shape[0])
+            sc = np.ascontiguousarray(sc)
+        m, w = np.ascontiguousarray(m), np.ascontiguousarray(w)
+        h = self._handle()
+        self.k = 0
+        check(self.lib.l3_pca_set_model(h, w.shape[0], _ptr(m), _ptr(w), _ptr(sc)))
+        self.k = w.shape[0]
+
+    def _project(self, rows, lo, hi, to_device, forward):
+        if self.k < 1:
+            raise ValueError('set_model comes first')
+        win, wout = (self.D, self.k) if forward else (self.k, self.D)
+        x, n = self._rows(rows, win, 'projected')
+        hi = n if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo < hi <= n:
+            raise ValueError('rows [%d, %d) are empty or outside the %d rows' % (lo, hi, n))
+        host, dev = ((self.lib.l3_pca_transform, self.lib.l3_pca_transform_dev) if forward else
+                     (self.lib.l3_pca_inverse, self.lib.l3_pca_inverse_dev))
+        if not isinstance(x, Features):
+            if to_device:
+                raise ValueError('a result on the device needs rows on the device (a Features)')
+            out = np.empty((hi - lo, wout), np.float32)
+            check(host(self._handle(), _ptr(x[lo:hi]), hi - lo, _ptr(out)))
+            return out
+        if not to_device:
+            out = np.empty((hi - lo, wout), np.float32)
+            check(dev(self._handle(), x.h, lo, hi, _ptr(out), None))
+            return out
+        f = Features.__new__(Features)
+        f.lib, f.h, f.device = self.lib, C.c_void_p(), self.device
+        check(dev(self._handle(), x.h, lo, hi, None, C.byref(f.h)))
+        return f
+
+    def transform(self, rows, lo=0, hi=None, to_device=False):
+        """the rows [lo, hi) of host rows or a Features (n, D) projected onto the model -> (hi - lo, k) float32, or with to_device
+        (Features input only) a new Features on this device"""
+        return self._project(rows, lo, hi, to_device, True)
+
+    def inverse(self, Y, lo=0, hi=None, to_device=False):
+        """the rows of the input space that the rows [lo, hi) of Y (n, k) stand for -> (hi - lo, D)"""
+        return self._project(Y, lo, hi, to_device, False)
+
+    def time(self, what, reps=3):
+        """l3_pca_time: device ms per round of one of PCA_TIMED"""
+        if what not in PCA_TIMED:
+            raise ValueError('what must be one of %s' % (PCA_TIMED,))
+        self._need_rows()
+        if what == 'transform' and self.k < 1:
+            raise ValueError('set_model comes first')
+        if what not in ('mean', 'transform') and not self.has_mean:
+            raise ValueError('the mean comes first: mean or set_mean')
+        ms = C.c_double()
+        check(self.lib.l3_pca_time(self._handle(), PCA_TIMED.index(what), int(reps), C.byref(ms)))
+        if what == 'mean':
+            self.has_mean = True
+        return ms.value
 
 
 # ---- downstream MLP classifier (classifier/train.py:230-391; csrc/mlp.hip) ---------------------------------------------------------

@@ -5,7 +5,7 @@ nearest-neighbour kernels bit for bit, a row goes to the centroid of the smalles
 fixed order, so a fit is a function of its inputs and its seed alone -- two runs give the same bits.  `contingency` counts the rows
 of every (cluster, class) pair; `nmi`, `purity` and `adjusted_rand` score such a table on the host in float64.  `file_histograms`
 turns each file's frames into counts of "audio words", rows that `classifier` can take as features.  Rows are float32 NumPy arrays or
-`usc.DeviceFeatures`; there is no silent conversion and no CPU fallback.
+`usc.DeviceFeatures` (those of `pca.PCA.transform(X, to_device=True)` as they are); there is no silent conversion and no CPU fallback.
 
 Only the squared Euclidean distance is offered.  Seeding is random rows, given centroids, or plain k-means++ with one candidate per
 step (scikit-learn's greedy variant, which tries several candidates per step, is out of scope: restarts take its place).  An empty

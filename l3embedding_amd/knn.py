@@ -34,7 +34,8 @@ def _rows(X, what):
 
 class NearestNeighbors(object):
     """Query by example among fitted rows.  fit(X) copies the rows to the device (a DeviceFeatures is copied there, device to
-    device); kneighbors gives every query's nearest fitted rows."""
+    device -- pca.PCA.transform(X, to_device=True) gives one of reduced or whitened rows); kneighbors gives every query's nearest
+    fitted rows."""
 
     def __init__(self, n_neighbors=5, metric='sqeuclidean', device=0):
         self.n_neighbors = _lib.knn_check_k(n_neighbors)

@@ -168,7 +168,7 @@ class TSNE(object):
             knn.close()
 
     def fit(self, X):
-        """X: (n, D) float32 rows or a usc.DeviceFeatures"""
+        """X: (n, D) float32 rows or a usc.DeviceFeatures (the usual 50-dimensional input: pca.PCA(50).fit_transform(X, to_device=True))"""
         idx, dist = self.neighbors(X)
         return self.fit_neighbors(idx, dist)
 
