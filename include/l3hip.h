@@ -1527,7 +1527,8 @@ int l3_op_tsne_update(int device, int64_t n, float *y, float *update, float *gai
  *                              voids the mean.  A NaN or an infinity in the rows is refused with the lowest such row named.
  *   l3_pca_mean                computes m64 and m32 of the rows; mean_out (D float64) and mean32_out (D float32) may each be NULL
  *   l3_pca_set_mean            m32 = mean32 (D finite float32): a scatter about a mean of the caller's
- *   l3_pca_scatter             S_out (D, D) float64, row major, about the handle's m32
+ *   l3_pca_scatter             S_out (D, D) float64, row major, about the handle's m32; S_out may be NULL, and S then only stays on the
+ *                              device (l3_eig_set_matrix_pca)
  *   l3_pca_splits              the count that splits = 0 stands for at (n, D)
  *   l3_pca_set_model           k components (k, D) row major, the model's mean32 (D) and scale (k, each finite and > 0) or NULL;
  *                              independent of the rows and of the mean the scatter uses
@@ -1562,6 +1563,52 @@ int l3_pca_transform_dev(l3_pca *h, const l3_feat *f, int64_t lo, int64_t hi, fl
 int l3_pca_inverse(l3_pca *h, const float *Y, int64_t n, float *out);
 int l3_pca_inverse_dev(l3_pca *h, const l3_feat *f, int64_t lo, int64_t hi, float *out, l3_feat **out_feat);
 int l3_pca_time(l3_pca *h, int what, int reps, double *ms);
+
+/* ---- Symmetric top-k problems: the device side of block subspace iteration ("The subspace solver"; csrc/eig.hip) --------
+ * A handle holds a symmetric float64 matrix S (D, D) on one device and two blocks of m vectors, V and W: the rows of (m, D) row-major
+ * float64 matrices.  The iteration is the caller's (l3embedding_amd/eigen.py): its m x m problems go to LAPACK on the host, whatever
+ * is D long stays on the device.
+ * Arithmetic, which is the contract (tests/eig_ref.py derives the bounds from it).  Every entry of the result of apply, gram and mix is
+ *   ONE float64 accumulator of v_mfma_f64_16x16x4_f64 that takes its reduction index in ascending steps of 4 from 0, padded with zeros
+ *   past the end.  No reduction is split, so the order is a function of (D, m) alone, there are no float atomics, and two calls give
+ *   the same bits.  The order of the four products inside one instruction is the hardware's, so the claim is a bound and not equality
+ *   with an ascending chain: |c - exact| <= gamma_(K + 1) sum |a b|, gamma_n = n u / (1 - n u), u = 2^-53, K the reduction length (D
+ *   for apply and gram, m for mix).  Products and sums of small integers are exact.
+ *   l3_eig_create            1 <= D <= L3_PCA_MAX_D, 1 <= m <= min(D, L3_EIG_MAX_M).  The handle allocates S, three blocks (the third is
+ *                            what a mix writes) and two m x m matrices: 8 (D^2 + 3 m D + 2 m^2) bytes.  The blocks start as zeros.
+ *   l3_eig_set_matrix        S from the host (D, D).  Refused unless every entry is finite and S equals its transpose bit for bit; the
+ *                            message names the lowest offending (i, j) in row-major order.
+ *   l3_eig_set_matrix_pca    S = the scatter matrix that the last l3_pca_scatter of `pca` left on the same device (a copy on the
+ *                            device); L3_ESTATE if there is none, L3_EINVAL for another device or another D.
+ *   l3_eig_trace             the diagonal of S summed in ascending order in float64 on the host
+ *   l3_eig_set_block / l3_eig_get_block   block `which` (L3_EIG_V or L3_EIG_W) from / to the host (m, D)
+ *   l3_eig_apply             W_j = S V_j for every j: W[j][d] = sum over e of V[j][e] S[d][e]
+ *   l3_eig_gram              G[i][j] = <a_i, b_j> to the host (m, m), a and b each L3_EIG_V or L3_EIG_W.  With a == b only i <= j is
+ *                            computed and written to (i, j) and (j, i): G equals its transpose bit for bit.
+ *   l3_eig_mix               dst_j = sum over i of M[j][i] src_i, M (m, m) row major from the host.  The result is written to the third
+ *                            block, which then changes places with dst: dst may be src, with the same bits as into the other block.
+ *   l3_eig_residual          res[j] = ||W_j - theta_j V_j||_2 to the host (m): fl(w - fl(theta v)) squared, 256 interleaved sequential
+ *                            sums a row folded by a fixed tree, one square root
+ *   l3_eig_time              device time in ms per round over `reps` rounds (hipEvents, one untimed round first): what 0 apply, 1
+ *                            gram(V, W), 2 the product of a mix of V by the resident m x m matrix, 3 residual.  For profiles/.
+ * L3_EINVAL: a NULL pointer, D or m out of range, a block index that is neither L3_EIG_V nor L3_EIG_W, a matrix that is not finite or
+ * not symmetric.  L3_ESTATE: apply or trace before the matrix. */
+#define L3_EIG_MAX_M 1024
+#define L3_EIG_V 0
+#define L3_EIG_W 1
+typedef struct l3_eig l3_eig;
+int l3_eig_create(int device, int D, int m, l3_eig **h);
+void l3_eig_destroy(l3_eig *h);
+int l3_eig_set_matrix(l3_eig *h, const double *S);
+int l3_eig_set_matrix_pca(l3_eig *h, const l3_pca *pca);
+int l3_eig_trace(l3_eig *h, double *trace);
+int l3_eig_set_block(l3_eig *h, int which, const double *B);
+int l3_eig_get_block(l3_eig *h, int which, double *B);
+int l3_eig_apply(l3_eig *h);
+int l3_eig_gram(l3_eig *h, int a, int b, double *G);
+int l3_eig_mix(l3_eig *h, int src, const double *M, int dst);
+int l3_eig_residual(l3_eig *h, const double *theta, double *res);
+int l3_eig_time(l3_eig *h, int what, int reps, double *ms);
 
 #ifdef __cplusplus
 }

@@ -18,10 +18,11 @@ LIBPATH = os.path.join(LIBDIR, 'libl3hip.so')
 # entry points, RCCL, the downstream MLP and SVM classifiers, the VGGish baseline features, training-set augmentation, the
 # classifier's fold preprocessing, the SVM's scoring and sigmoid fits, the downstream random forest, the clip bank and the
 # kernels that cut training samples from it, the AVC head over every (frame, second) pair and over every location of a tower's
-# last feature map, nearest neighbours among embedding rows, k-means over embedding rows, t-SNE maps of them, their principal components.
+# last feature map, nearest neighbours among embedding rows, k-means over embedding rows, t-SNE maps of them, their principal components,
+# the top-k eigensolver's float64 matrix-core products.
 SOURCES = ['conv.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_bf16.hip', 'conv_bf16_halo.hip', 'conv_wgrad_bf16.hip', 'conv_wgrad_wino.hip',
            'conv_first.hip', 'conv_path.hip', 'elementwise.hip', 'bn_fused.hip', 'frontend.hip', 'clips.hip', 'frames.hip', 'resample.hip', 'batch_feed.hip', 'engine.hip', 'ops.hip',
-           'comm.hip', 'mlp.hip', 'svm.hip', 'vggish.hip', 'augment.hip', 'featprep.hip', 'svm_eval.hip', 'forest.hip', 'avsample.hip', 'pairs.hip', 'locmap.hip', 'knn.hip', 'kmeans.hip', 'tsne.hip', 'pca.hip']
+           'comm.hip', 'mlp.hip', 'svm.hip', 'vggish.hip', 'augment.hip', 'featprep.hip', 'svm_eval.hip', 'forest.hip', 'avsample.hip', 'pairs.hip', 'locmap.hip', 'knn.hip', 'kmeans.hip', 'tsne.hip', 'pca.hip', 'eig.hip']
 # Measured-and-rejected kernel variants (split-bf16 fp32 convolutions, flat-tile MODE 5, tap-split bf16 weight gradient; round 6: the
 # filter-in-registers 64-channel halo kernel, the split-bf16 first convolution): records of negative results (profiles/r05_bx6_ablations.txt,
 # r05_bf16_conv_notes.txt, r06_halo64_regfilter.txt, r06_first_conv_mfma.txt), NOT product paths.  L3_BUILD_EXPERIMENTS=1 compiles them
@@ -53,10 +54,11 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC'] + (['-DL3_EXPERI
 # bounds of the two passes count the fused multiply-adds that are written as such
 # pca.hip: likewise, the centring is one float32 subtraction, a scatter entry a counted chain of matrix-core fused multiply-adds folded
 # into float64 sums, and a projection knn.hip's dot product with one more rounding at either end (the shared knn_tile.h)
+# eig.hip: likewise, a residual entry is fl(w - fl(theta v)) and its square is rounded before it is added
 FILE_FLAGS = {'augment.hip': ['-ffp-contract=off'], 'conv_wino4.hip': ['-fno-slp-vectorize'], 'conv_wino_bx6.hip': ['-fno-slp-vectorize'], 'conv_wgrad_bx6.hip': ['-fno-slp-vectorize'],
               'conv_first.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'featprep.hip': ['-ffp-contract=off'], 'svm_eval.hip': ['-ffp-contract=off'],
               'forest.hip': ['-ffp-contract=off'], 'frames.hip': ['-ffp-contract=off'], 'knn.hip': ['-ffp-contract=off'], 'kmeans.hip': ['-ffp-contract=off'],
-              'tsne.hip': ['-ffp-contract=off'], 'pca.hip': ['-ffp-contract=off']}
+              'tsne.hip': ['-ffp-contract=off'], 'pca.hip': ['-ffp-contract=off'], 'eig.hip': ['-ffp-contract=off']}
 
 
 def _headers():

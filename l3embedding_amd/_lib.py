@@ -264,6 +264,19 @@ SIGNATURES = {
     'l3_pca_inverse': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'l3_pca_inverse_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]),
     'l3_pca_time': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    # symmetric top-k problems: the device side of block subspace iteration (csrc/eig.hip)
+    'l3_eig_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    'l3_eig_destroy': (None, [C.c_void_p]),
+    'l3_eig_set_matrix': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'l3_eig_set_matrix_pca': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'l3_eig_trace': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    'l3_eig_set_block': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    'l3_eig_get_block': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    'l3_eig_apply': (C.c_int, [C.c_void_p]),
+    'l3_eig_gram': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'l3_eig_mix': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    'l3_eig_residual': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'l3_eig_time': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     'l3_op_kmeans_step': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
                                     C.c_void_p, C.c_void_p]),
     'l3_frontend_cfg': (C.c_int, [C.c_int] * 5 + [C.c_void_p]),
@@ -2846,14 +2859,15 @@ class PCA(object):
         check(self.lib.l3_pca_set_mean(self._handle(), _ptr(m)))
         self.has_mean = True
 
-    def scatter(self, splits=0):
-        """l3_pca_scatter -> S (D, D) float64, the sum over the rows of xc xc^T with xc = float32(x - m32); splits 0: pca_splits"""
+    def scatter(self, splits=0, download=True):
+        """l3_pca_scatter -> S (D, D) float64, the sum over the rows of xc xc^T with xc = float32(x - m32); splits 0: pca_splits.
+        download=False leaves S on the device (for Eig.set_matrix_pca) and returns None."""
         self._need_rows()
         if not self.has_mean:
             raise ValueError('the mean comes first: mean or set_mean')
         if isinstance(splits, bool) or not isinstance(splits, (int, np.integer)) or not 0 <= splits <= PCA_MAX_SPLITS:
             raise ValueError('splits must be an integer in [0, %d], not %r' % (PCA_MAX_SPLITS, splits))
-        S = np.empty((self.D, self.D), np.float64)
+        S = np.empty((self.D, self.D), np.float64) if download else None
         check(self.lib.l3_pca_scatter(self._handle(), int(splits), _ptr(S)))
         return S
 
@@ -2924,6 +2938,144 @@ class PCA(object):
         check(self.lib.l3_pca_time(self._handle(), PCA_TIMED.index(what), int(reps), C.byref(ms)))
         if what == 'mean':
             self.has_mean = True
+        return ms.value
+
+
+# ---- symmetric top-k problems (csrc/eig.hip; DESIGN.md 8v, the subspace solver) ---------------------------------------------------------
+EIG_MAX_M = 1024                   # L3_EIG_MAX_M
+EIG_BLOCKS = {'V': 0, 'W': 1}      # L3_EIG_V, L3_EIG_W
+EIG_TIMED = ('apply', 'gram', 'mix', 'residual')
+
+
+def _eig_which(which):
+    if which not in EIG_BLOCKS:
+        raise ValueError("a block is 'V' or 'W', not %r" % (which,))
+    return EIG_BLOCKS[which]
+
+
+class Eig(object):
+    """RAII wrapper over an l3_eig handle: a symmetric float64 matrix S (D, D) on one device and two blocks 'V' and 'W' of m vectors,
+    the rows of (m, D) float64 matrices.  It is the `ops` of eigen.top_eigh.  Every argument is checked here first (ValueError) and
+    the handle is created by the first call that needs the device."""
+
+    def __init__(self, D, m, device=0):
+        self.D = pca_check_d(D)
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= min(self.D, EIG_MAX_M):
+            raise ValueError('m must be an integer in [1, min(D, %d) = %d], not %r' % (EIG_MAX_M, min(self.D, EIG_MAX_M), m))
+        self.m, self.device = int(m), int(device)
+        self.lib = None
+        self.h = None
+        self.has_matrix = False
+
+    def _handle(self):
+        if self.h is None:
+            self.lib = load()
+            h = C.c_void_p()
+            check(self.lib.l3_eig_create(self.device, self.D, self.m, C.byref(h)))
+            self.h = h
+        return self.h
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.l3_eig_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _square(self, M, what):
+        M = np.asarray(M)
+        if M.dtype != np.float64 or M.shape != (self.m, self.m):
+            raise ValueError('%s must be float64 of shape (%d, %d), not %s %s' % (what, self.m, self.m, M.dtype, M.shape))
+        return np.ascontiguousarray(M)
+
+    def set_matrix(self, S):
+        """S (D, D) float64 from the host; the library refuses one that is not finite or not equal to its transpose bit for bit"""
+        S = np.asarray(S)
+        if S.dtype != np.float64 or S.shape != (self.D, self.D):
+            raise ValueError('the matrix must be float64 of shape (%d, %d), not %s %s' % (self.D, self.D, S.dtype, S.shape))
+        S = np.ascontiguousarray(S)
+        h = self._handle()
+        self.has_matrix = False
+        check(self.lib.l3_eig_set_matrix(h, _ptr(S)))
+        self.has_matrix = True
+
+    def set_matrix_pca(self, pca):
+        """S = the scatter matrix that the last scatter() of the _lib.PCA `pca` left on this device: no trip through the host"""
+        if not isinstance(pca, PCA):
+            raise ValueError('a _lib.PCA is needed, not %r' % type(pca).__name__)
+        if pca.D != self.D or pca.device != self.device:
+            raise ValueError('the PCA handle has D = %d on device %d, this one D = %d on device %d' % (pca.D, pca.device, self.D, self.device))
+        if not pca.h:
+            raise ValueError('the PCA handle holds no scatter matrix: scatter comes first')
+        h = self._handle()
+        self.has_matrix = False
+        check(self.lib.l3_eig_set_matrix_pca(h, pca.h))
+        self.has_matrix = True
+
+    def _need_matrix(self):
+        if not self.has_matrix:
+            raise ValueError('the matrix comes first: set_matrix or set_matrix_pca')
+
+    def trace(self):
+        self._need_matrix()
+        t = C.c_double()
+        check(self.lib.l3_eig_trace(self._handle(), C.byref(t)))
+        return t.value
+
+    def set_block(self, which, B):
+        w = _eig_which(which)
+        B = np.asarray(B)
+        if B.dtype != np.float64 or B.shape != (self.m, self.D):
+            raise ValueError('a block is float64 of shape (%d, %d), not %s %s' % (self.m, self.D, B.dtype, B.shape))
+        B = np.ascontiguousarray(B)
+        check(self.lib.l3_eig_set_block(self._handle(), w, _ptr(B)))
+
+    def get_block(self, which):
+        w = _eig_which(which)
+        B = np.empty((self.m, self.D), np.float64)
+        check(self.lib.l3_eig_get_block(self._handle(), w, _ptr(B)))
+        return B
+
+    def apply(self):
+        """W_j = S V_j for every j"""
+        self._need_matrix()
+        check(self.lib.l3_eig_apply(self._handle()))
+
+    def gram(self, a, b):
+        """G (m, m): G[i][j] = <a_i, b_j>"""
+        ia, ib = _eig_which(a), _eig_which(b)
+        G = np.empty((self.m, self.m), np.float64)
+        check(self.lib.l3_eig_gram(self._handle(), ia, ib, _ptr(G)))
+        return G
+
+    def mix(self, src, M, dst):
+        """dst_j = sum_i M[j][i] src_i; dst may be src"""
+        isrc, idst = _eig_which(src), _eig_which(dst)
+        M = self._square(M, 'M')
+        check(self.lib.l3_eig_mix(self._handle(), isrc, _ptr(M), idst))
+
+    def residual(self, theta):
+        """res (m): ||W_j - theta_j V_j||_2"""
+        th = np.asarray(theta)
+        if th.dtype != np.float64 or th.shape != (self.m,):
+            raise ValueError('theta must be %d float64, not %s %s' % (self.m, th.dtype, th.shape))
+        th = np.ascontiguousarray(th)
+        res = np.empty(self.m, np.float64)
+        check(self.lib.l3_eig_residual(self._handle(), _ptr(th), _ptr(res)))
+        return res
+
+    def time(self, what, reps=3):
+        """l3_eig_time: device ms per round of one of EIG_TIMED"""
+        if what not in EIG_TIMED:
+            raise ValueError('what must be one of %s' % (EIG_TIMED,))
+        if what == 'apply':
+            self._need_matrix()
+        ms = C.c_double()
+        check(self.lib.l3_eig_time(self._handle(), EIG_TIMED.index(what), int(reps), C.byref(ms)))
         return ms.value
 
 

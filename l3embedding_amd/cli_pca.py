@@ -1,10 +1,14 @@
 """Command line of the principal components of an embedding (pca.py).
 
     python -m l3embedding_amd.cli_pca fit --features A.npz [...] --n-components 50 [--whiten] --out model.npz
+                                          [--solver full|subspace|auto] [--oversample N] [--tol T] [--max-iter N] [--seed N]
 
 PCA over the frames of the embedding files that cli_embedding_samples wrote (X: the frames of one clip, y: its class).  A path may be a
 directory of such files.  --n-components: an integer, a fraction in (0, 1) of the variance to keep, or `all`.  model.npz holds mean,
-components, explained_variance, explained_variance_ratio, n_samples and whiten.
+components, explained_variance, explained_variance_ratio, n_samples and whiten.  --solver subspace finds the components by block
+subspace iteration on the GPU instead of an eigendecomposition of the whole covariance on the host (pca.PCA; an integer
+--n-components); --oversample, --tol, --max-iter and --seed are its block width beyond the components, its residual tolerance, its
+limit of products and the seed of its start.
 
     python -m l3embedding_amd.cli_pca transform --model model.npz --features F --out G
 
@@ -50,6 +54,12 @@ def build_parser():
     fit.add_argument('--whiten', action='store_true', default=False, help='projections of unit variance')
     fit.add_argument('--device', type=int, default=0, help='GPU index')
     fit.add_argument('--out', type=str, required=True, help='the .npz file of the model')
+    # (absent unless given: the keyword arguments of fit() keep their defaults)
+    fit.add_argument('--solver', choices=('full', 'subspace', 'auto'), default=argparse.SUPPRESS, help='eigensolver (default: full)')
+    fit.add_argument('--oversample', type=int, default=argparse.SUPPRESS, help='subspace solver: vectors beyond the components (default: max(32, k // 4))')
+    fit.add_argument('--tol', type=float, default=argparse.SUPPRESS, help='subspace solver: residual tolerance relative to the largest eigenvalue (default: 1e-9)')
+    fit.add_argument('--max-iter', type=int, default=argparse.SUPPRESS, help='subspace solver: limit of products (default: 500)')
+    fit.add_argument('--seed', type=int, default=argparse.SUPPRESS, help='subspace solver: seed of the starting block (default: 0)')
     tr = sub.add_parser('transform', help="project embedding files onto a model's components")
     tr.add_argument('--model', type=str, required=True, help='model.npz written by `fit`')
     tr.add_argument('--features', type=str, required=True, help='an .npz embedding file, or a directory of them')
@@ -64,11 +74,11 @@ def parse_arguments(argv=None):
     return args.pop('command'), args
 
 
-def fit(features, n_components, out, whiten=False, device=0):
+def fit(features, n_components, out, whiten=False, device=0, solver='full', oversample=None, tol=1e-9, max_iter=500, seed=0):
     """the `fit` command -> the path written"""
     from .pca import PCA
+    model = PCA(n_components, whiten=whiten, device=device, solver=solver, oversample=oversample, tol=tol, max_iter=max_iter, random_state=seed)
     X = _load(_entries(features))[0]
-    model = PCA(n_components, whiten=whiten, device=device)
     try:
         model.fit(X)
     finally:

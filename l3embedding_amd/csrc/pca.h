@@ -21,6 +21,7 @@ struct l3_pca {
     // scratch of the mean (segment sums) and of the scatter (one float64 D x D partial per split), and the scatter matrix
     double *seg = nullptr, *part = nullptr, *S = nullptr;
     size_t cap_seg = 0, cap_part = 0, cap_S = 0;
+    bool has_S = false;          // S is the result of a finished l3_pca_scatter of the rows and the mean the handle holds now
     // the model: k components W (k, D), their transpose WT (D, k), the model's mean and, when whitening, scale (k)
     int k = 0;
     float *W = nullptr, *WT = nullptr, *mean = nullptr, *scale = nullptr;
@@ -30,3 +31,7 @@ struct l3_pca {
     float *P = nullptr, *Y = nullptr;
     size_t cap_P = 0, cap_Y = 0;
 };
+
+// the scatter matrix (D, D) that the last l3_pca_scatter left on the device, or nullptr when there is none: what l3_eig_set_matrix_pca
+// (eig.hip) copies, so that the eigensolver starts from S without a trip through the host
+inline const double* pca_resident_scatter(const l3_pca* h) { return h->has_S ? h->S : nullptr; }

@@ -300,7 +300,7 @@ int check_feat(const l3_pca* h, const l3_feat* f, int64_t lo, int64_t hi, int64_
 
 // the fitted rows: x_host or x_dev (n, D) -> the handle's copy, refused if a row is not finite; voids the mean
 int set_rows(l3_pca* h, const float* x_host, const float* x_dev, int64_t n, const char* fn) {
-    h->n = 0, h->has_mean = false;
+    h->n = 0, h->has_mean = false, h->has_S = false;
     if (int rc = grow(h, &h->X, &h->cap_X, (size_t)n * h->D, fn)) return rc;
     const hipMemcpyKind kind = x_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     unsigned long long bad = NO_ROW;
@@ -462,7 +462,7 @@ int l3_pca_mean(l3_pca* h, double* mean_out, float* mean32_out) {
     const char* fn = "l3_pca_mean";
     if (int rc = enter(h, fn)) return rc;
     if (int rc = need_rows(h, fn)) return rc;
-    h->has_mean = false;
+    h->has_mean = false, h->has_S = false;
     if (int rc = grow(h, &h->seg, &h->cap_seg, (size_t)((h->n + SEG - 1) / SEG) * h->D, fn)) return rc;
     launch_mean(h);
     bool ok = true;
@@ -477,7 +477,7 @@ int l3_pca_set_mean(l3_pca* h, const float* mean32) {
     const char* fn = "l3_pca_set_mean";
     if (int rc = enter(h, fn)) return rc;
     if (!mean32) return fail(L3_EINVAL, std::string(fn) + ": mean32 is NULL");
-    h->has_mean = false;
+    h->has_mean = false, h->has_S = false;
     std::vector<double> wide((size_t)h->D);
     for (int d = 0; d < h->D; ++d) {
         if (!std::isfinite(mean32[d])) return fail(L3_EINVAL, std::string(fn) + ": the mean of column " + std::to_string(d) + " is not finite");
@@ -493,16 +493,18 @@ int l3_pca_set_mean(l3_pca* h, const float* mean32) {
 int l3_pca_scatter(l3_pca* h, int splits, double* S_out) {
     const char* fn = "l3_pca_scatter";
     if (int rc = enter(h, fn)) return rc;
-    if (!S_out) return fail(L3_EINVAL, std::string(fn) + ": S_out is NULL");
     if (splits < 0 || splits > L3_PCA_MAX_SPLITS)
         return fail(L3_EINVAL, std::string(fn) + ": splits must be in [0, " + std::to_string(L3_PCA_MAX_SPLITS) + "], not " + std::to_string(splits));
     if (int rc = need_rows(h, fn)) return rc;
     if (!h->has_mean) return fail(L3_ESTATE, std::string(fn) + ": the mean comes first (l3_pca_mean or l3_pca_set_mean)");
     const int count = splits == 0 ? default_splits(h->n, h->D) : (int)std::min<int64_t>(splits, chains_of(h->n));
+    h->has_S = false;
     if (int rc = prepare_scatter(h, count, fn)) return rc;
     launch_scatter(h, count);
-    if (hipMemcpyAsync(S_out, h->S, (size_t)h->D * h->D * sizeof(double), hipMemcpyDeviceToHost, h->s) != hipSuccess || !finished(h->s))
+    // (S_out may be NULL: S then stays on the device, where l3_eig_set_matrix_pca takes it from)
+    if ((S_out && hipMemcpyAsync(S_out, h->S, (size_t)h->D * h->D * sizeof(double), hipMemcpyDeviceToHost, h->s) != hipSuccess) || !finished(h->s))
         return fail(L3_EHIP, std::string(fn) + ": the kernels or the copy from the device failed");
+    h->has_S = true;          // (for l3_eig_set_matrix_pca: pca.h)
     return L3_OK;
 }
 
@@ -576,7 +578,7 @@ int l3_pca_time(l3_pca* h, int what, int reps, double* ms) {
     if (int rc = need_rows(h, fn)) return rc;
     const int splits = default_splits(h->n, h->D);
     if (what == 0) {
-        h->has_mean = false;
+        h->has_mean = false, h->has_S = false;
         if (int rc = grow(h, &h->seg, &h->cap_seg, (size_t)((h->n + SEG - 1) / SEG) * h->D, fn)) return rc;
     } else if (what == 2) {
         if (int rc = need_model(h, fn)) return rc;

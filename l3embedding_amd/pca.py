@@ -2,10 +2,12 @@
 
 `PCA.fit` computes the column means and the scatter matrix S = sum of xc xc^T of the centred rows on the device (csrc/pca.hip: float64
 sums in one fixed order for the mean, the fp32 matrix cores in chains of 256 rows folded into float64 for S), then
-`numpy.linalg.eigh(S / (n - 1))` on the host in float64.  That step is on the host on purpose: at D = 512 it takes hundredths of a
-second and is as exact as LAPACK; for D = 6144 it takes tens of seconds, and a top-k eigensolver on the device is left open (DESIGN.md
-section 9).  A fit is a function of its rows alone: there are no float atomics and the split of the rows does not depend on the device,
-so two fits give the same bits on any GPU.
+`numpy.linalg.eigh(S / (n - 1))` on the host in float64 (`solver='full'`, the default).  That step is on the host on purpose: at D = 512
+it takes hundredths of a second and is as exact as LAPACK.  For D = 6144 it takes many seconds, and `solver='subspace'` instead finds
+the k leading pairs by block subspace iteration on S where it lies (eigen.py over csrc/eig.hip's float64 matrix-core products; only
+m x m problems, m = k + oversample, go to the host).  A fit is a function of its rows alone (and of `random_state` for the subspace
+solver): there are no float atomics and the split of the rows does not depend on the device, so two fits give the same bits on any
+GPU.
 
 `transform` centres at `mean_` and projects onto `components_` with the dot product of the nearest-neighbour kernels (one ascending
 float32 fused-multiply-add chain over D per entry), times `1 / sqrt(explained_variance_)` when whitening.  With `to_device=True` the
@@ -14,11 +16,16 @@ are float32 NumPy arrays or `usc.DeviceFeatures`; there is no silent conversion 
 """
 import numpy as np
 
-from . import _lib
+from . import _lib, eigen as _eigen
 from .knn import _rows
 from .usc import DeviceFeatures
 
 BLOCK = 65536          # host rows of one block of transform() / inverse_transform()
+SOLVERS = ('full', 'subspace', 'auto')
+# solver='auto' takes the subspace solver from this many features on (and k + oversample <= D // 4).  profiles/r39_pca_subspace.txt has
+# the crossover table this is read from: the smallest D of {512, 1024, 2048, 4096, 6144} at which the subspace fit at k = 64 was faster
+# than the full one in the same run.
+AUTO_MIN_D = 1024
 
 
 def sign_rule(components):
@@ -60,11 +67,27 @@ def check_n_components(n_components):
 
 class PCA(object):
     """Principal component analysis on the GPU.  n_components: None (every one of the D axes is kept), an integer k <= D, or a fraction in (0, 1): the fewest leading components whose explained variance ratios sum to it.  whiten: the
-    projections are divided by the components' standard deviations (a kept component of zero variance is refused)."""
+    projections are divided by the components' standard deviations (a kept component of zero variance is refused).  solver: 'full'
+    (numpy.linalg.eigh of the whole covariance on the host), 'subspace' (the n_components leading pairs by block subspace iteration on
+    the device: an integer n_components, block width n_components + oversample, residuals below tol times the largest eigenvalue within
+    max_iter products or eigen.NotConverged, the start drawn from random_state) or 'auto' (the rule of solver_for)."""
 
-    def __init__(self, n_components=None, whiten=False, device=0, keep_covariance=False):
+    def __init__(self, n_components=None, whiten=False, device=0, keep_covariance=False, solver='full', oversample=None, tol=1e-9, max_iter=500,
+                 random_state=0):
         self.n_components = check_n_components(n_components)
         self.whiten, self.device, self.keep_covariance = bool(whiten), int(device), bool(keep_covariance)
+        if solver not in SOLVERS:
+            raise ValueError('solver must be one of %s, not %r' % (SOLVERS, solver))
+        if solver == 'subspace' and not isinstance(self.n_components, int):
+            raise ValueError("solver='subspace' needs an integer n_components, not %r: how many components a share of the variance takes "
+                             "is not known without the whole spectrum (use solver='full')" % (n_components,))
+        if oversample is not None and (isinstance(oversample, bool) or not isinstance(oversample, (int, np.integer)) or oversample < 0):
+            raise ValueError('oversample must be None or an integer >= 0, not %r' % (oversample,))
+        if not tol > 0.0 or isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
+            raise ValueError('tol must be positive and max_iter an integer >= 1, not %r and %r' % (tol, max_iter))
+        self.solver, self.oversample = solver, None if oversample is None else int(oversample)
+        self.tol, self.max_iter, self.random_state = float(tol), int(max_iter), random_state
+        self.solver_info_ = None
         self.components_ = None
         self._h = None
 
@@ -116,7 +139,19 @@ class PCA(object):
         return state
 
     def __setstate__(self, state):
+        # (a model pickled before there was a choice of solver has none of these: it behaves as 'full')
+        self.__dict__.update(dict(solver='full', oversample=None, tol=1e-9, max_iter=500, random_state=0, solver_info_=None))
         self.__dict__.update(state)
+
+    def solver_for(self, D):
+        """the solver a fit of rows of D features takes: 'auto' is 'subspace' when n_components is an integer, n_components + oversample
+        <= min(D // 4, the library's widest block) and D >= AUTO_MIN_D, and 'full' otherwise"""
+        if self.solver != 'auto':
+            return self.solver
+        if not isinstance(self.n_components, int) or D < AUTO_MIN_D:
+            return 'full'
+        oversample = _eigen.default_oversample(self.n_components) if self.oversample is None else self.oversample
+        return 'subspace' if self.n_components + oversample <= min(D // 4, _lib.EIG_MAX_M) else 'full'
 
     def _check_fitted(self):
         if self.components_ is None:
@@ -158,6 +193,27 @@ class PCA(object):
         if self.keep_covariance:
             self.covariance_ = covariance
 
+    def _finish_subspace(self, n, mean32, h, m):
+        """the model from the scatter matrix that the handle h holds on the device, by block subspace iteration of width m: the k
+        leading eigenpairs, and the total variance from the trace"""
+        k = self.n_components
+        eig = _lib.Eig(h.D, m, device=self.device)
+        try:
+            eig.set_matrix_pca(h)
+            theta, vectors, info = _eigen.top_eigh(eig, k, oversample=m - k, tol=self.tol, max_iter=self.max_iter, random_state=self.random_state)
+            trace = eig.trace()
+        finally:
+            eig.close()
+        variance = np.maximum(theta / float(n - 1), 0.0)
+        total = trace / float(n - 1)
+        ratio = variance / total if total > 0.0 else np.zeros_like(variance)
+        self.n_components_, self.n_samples_ = k, int(n)
+        self.mean_ = mean32
+        self.explained_variance_, self.explained_variance_ratio_ = variance, ratio
+        self.solver_info_ = info
+        self.scale_ = self._scale()          # (refuses before the components are set: a refused fit leaves no model)
+        self.components_ = np.ascontiguousarray(sign_rule(vectors).astype(np.float32))
+
     def fit(self, X):
         """X: (n >= 2, D) float32 rows or a usc.DeviceFeatures.  The rows stay on the device until close()."""
         rows = _rows(X, 'X')
@@ -166,14 +222,25 @@ class PCA(object):
             raise ValueError('principal components need at least 2 rows, not %d' % n)
         if isinstance(self.n_components, int) and self.n_components > D:
             raise ValueError('n_components = %d, but the rows have only %d features' % (self.n_components, D))
+        subspace = self.solver_for(D) == 'subspace'
+        m = _eigen.block_width(self.n_components, self.oversample, D) if subspace else None          # (refused before the device)
+        if subspace and m > _lib.EIG_MAX_M:
+            raise ValueError('k + oversample = %d exceeds the %d vectors of a block of the subspace solver (use the full solver)' % (m, _lib.EIG_MAX_M))
         self.close()
         self.components_ = None
+        self.solver_info_ = None
         h = _lib.PCA(D, device=self.device)
         try:
             h.set_rows(rows)
             _, mean32 = h.mean()
-            S = h.scatter()
-            self._finish(n, mean32, S)
+            if subspace:
+                S = h.scatter(download=self.keep_covariance)
+                self._finish_subspace(n, mean32, h, m)
+                if self.keep_covariance:
+                    self.covariance_ = S / float(n - 1)
+            else:
+                S = h.scatter()
+                self._finish(n, mean32, S)
             h.set_model(self.mean_, self.components_, self.scale_)
         except Exception:
             h.close()
